@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: PixReferNet G+D training step, frames/s at 256x256, bf16, GLOBAL batch 32 (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W [--scaling strong|weak]
+  python bench.py --gpus N --steps K --warmup W [--scaling strong|weak] [--dump-outputs DIR]
 
 One process per GPU.  With N > 1 and no WORLD_SIZE in the environment this script itself starts the N ranks
 (`python -m torch.distributed.run --nproc-per-node N bench.py ...` as a CHILD process, before anything here has touched
@@ -57,7 +57,12 @@ def parse_args(argv=None):
   ap.add_argument("--tune", action="append", default=[], metavar="KEY=INT", help="vp_tune knob for experiments (repeatable)")
   ap.add_argument("--grad-dtype", default="auto", choices=["auto", "f32", "bf16"],
                   help="N > 1: transport type of the gradient all-reduce (f32 master either way); auto = the compute dtype")
-  return ap.parse_args(argv)
+  ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                  help="write what the last timed step computed (losses, generator outputs, updated weights) to DIR/<name>.npy")
+  args = ap.parse_args(argv)
+  if args.steps < 1 or args.warmup < 0:
+    ap.error("--steps must be >= 1 and --warmup >= 0")
+  return args
 
 
 def _free_port():
@@ -120,6 +125,32 @@ def synth_batch(n, h, seed, device):
   inputs, targets, ex_t = img(6), img(3), img(3)
   fg = torch.cat([ex_t * masks, targets * masks], dim=-1)
   return [t.to(device) for t in (inputs, fg, targets, masks)]
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+# elements kept per array; a larger array is replaced by a fixed seeded sample of its flattened elements (same indices every run)
+DUMP_CAP = {"Outputs": 8 << 20, "params_g": 4 << 20, "params_d": 2 << 20}
+
+
+def dump_outputs(eng, out_dir):
+  """What a caller of train_step holds after the last timed step: the step's losses (float64), the generator output of its forward pass
+  (Outputs, [N, H, H, 3] float32) and the generator / discriminator weights after its Adam updates (float32), as out_dir/<name>.npy."""
+  import numpy as np
+  import torch
+  torch.cuda.synchronize()
+  arrays = {k: np.array([v], np.float64) for k, v in eng.losses().items()}
+  for name, t in (("Outputs", eng.fetch("Outputs")), ("params_g", eng.params_g), ("params_d", eng.params_d)):
+    a = t.float().cpu().numpy()
+    if a.size > DUMP_CAP[name]:
+      idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_CAP[name], replace=False))
+      a = a.reshape(-1)[idx]
+    arrays[name] = a
+  total = sum(a.nbytes for a in arrays.values())
+  assert total <= DUMP_BUDGET_BYTES, total
+  os.makedirs(out_dir, exist_ok=True)
+  for k, a in arrays.items():
+    np.save(os.path.join(out_dir, k + ".npy"), a)
+  return {"dir": out_dir, "arrays": {k: list(a.shape) for k, a in arrays.items()}, "bytes": total}
 
 
 # ---- CPU restatements (rank 0, N = 1 only; the oracle is the thing timed here, never the GPU path) ---------------------
@@ -266,7 +297,7 @@ def make_engine(per_gpu, height, dtype):
   return eng
 
 
-def run_config(per_gpu, height, dtype, steps, warmup, rank, world, device, group, profile, grad_dtype="f32"):
+def run_config(per_gpu, height, dtype, steps, warmup, rank, world, device, group, profile, grad_dtype="f32", dump_dir=None):
   import torch
   import torch.distributed as dist
   eng = make_engine(per_gpu, height, dtype)
@@ -314,6 +345,9 @@ def run_config(per_gpu, height, dtype, steps, warmup, rank, world, device, group
   res = {"ms_per_step": ms, "frames_per_s": per_gpu * world * steps / dt, "per_gpu_batch": per_gpu,
          "global_batch": per_gpu * world,
          "step_tflops": GFLOP_PER_FRAME_256 * 1e9 * (height / 256) ** 2 * per_gpu * world / (ms * 1e-3) / 1e12}
+  if dump_dir is not None and rank == 0:
+    # before any later step below moves the weights
+    res["dumped"] = dump_outputs(eng, dump_dir)
   if world == 1 and profile:
     # the same step over a five times longer region (outside the judged one): the driver's 20-step region is 0.15 s, below the resolution
     # of the changes EXPERIMENTS.md discusses
@@ -524,7 +558,7 @@ def main():
       else:
         _lib.check(_lib.lib().vp_tune(k.encode(), int(v)), "vp_tune " + kv)
   main_res = run_config(per_gpu_batch(args, args.scaling, world), args.height, args.dtype, args.steps, args.warmup,
-                        rank, world, device, group, not args.no_profile, grad_dtype)
+                        rank, world, device, group, not args.no_profile, grad_dtype, dump_dir=args.dump_outputs)
   other = None
   if world > 1 and not args.no_other_scaling:
     mode = "weak" if args.scaling == "strong" else "strong"
@@ -576,6 +610,8 @@ def main():
            "conv_launches_per_step": main_res.get("conv_launches_per_step"), "step_tflops": main_res["step_tflops"]}
     if main_res.get("long_region"):
       out["long_region"] = main_res["long_region"]
+    if main_res.get("dumped"):
+      out["dumped_outputs"] = main_res["dumped"]
     if dist_info is not None:
       dist_info["buckets"] = main_res.get("buckets")
       out["distributed"] = dist_info

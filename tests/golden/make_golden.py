@@ -23,6 +23,8 @@
                      infer_bfmvid.py:92-99, and the frames the compiled reference rasteriser drew from them: reference-captured
   raster.npz         a synthetic mesh (oracle.raster_ref.synthetic_mesh) and the image / mask / depth the REFERENCE's own
                      compiled mesh_core.cpp (oracle/_ref, built by oracle/Makefile) rasterised from it: reference-captured
+  raster_seed17.npz  the same for the seed-17 mesh of tests/test_raster.py::test_restatement_matches_compiled_reference, so that the
+                     test runs without oracle/_ref (`python tests/golden/make_golden.py raster_seed17`): reference-captured
 
 The reference itself cannot produce vectors for this path (TF1.x is not installable: SURVEY.md 8c), so these
 pin the ORACLE against drift and give the GPU tests fixed inputs; they are not reference-captured outputs.
@@ -295,6 +297,14 @@ def raster():
   np.savez_compressed(os.path.join(HERE, "raster.npz"), **d)
 
 
+def raster_seed17():
+  from oracle import raster_ref as rr
+  assert rr.have_compiled_reference(), "run `make -C oracle` first"
+  v, t, c = rr.synthetic_mesh(seed=17, nlat=20, nlon=24, h=120, w=100)
+  img, mask, depth = rr.render_colors_ref(v, t, c, 120, 100)
+  np.savez_compressed(os.path.join(HERE, "raster_seed17.npz"), vertices=v, triangles=t, colors=c, image=img, mask=mask, depth=depth)
+
+
 def bfm_recon():
   from oracle import bfm_ref as br
   from oracle import raster_ref as rr
@@ -341,7 +351,11 @@ if __name__ == "__main__":
     sys.exit(0)
   if sys.argv[1:] == ["raster"]:
     raster()
+    raster_seed17()
     bfm_recon()
+    sys.exit(0)
+  if sys.argv[1:] == ["raster_seed17"]:
+    raster_seed17()
     sys.exit(0)
   panels, bg = sample22()
   toy_ops()
@@ -349,6 +363,7 @@ if __name__ == "__main__":
   mini_step(panels, bg)
   audio()
   raster()
+  raster_seed17()
   bfm_recon()
   for f in sorted(os.listdir(HERE)):
     print(f, os.path.getsize(os.path.join(HERE, f)))

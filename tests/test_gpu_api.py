@@ -21,7 +21,7 @@ def test_train_cli_runs_and_checkpoints(tmp_path, monkeypatch, capsys):
   assert os.path.isdir("ckpt_pixrefer") and os.path.isdir("log/summary_pixrefer")
 
 
-def test_build_train_op_nodes_and_lr_steps():
+def test_build_train_op_nodes_and_lr_steps(tmp_path):
   from voicepuppet_amd.generator.generator import PixReferDataGenerator
   from voicepuppet_amd.pixrefer.pixrefer import PixReferNet, TRAIN_KEYS
   from voicepuppet_amd.runtime import Session
@@ -50,7 +50,7 @@ def test_build_train_op_nodes_and_lr_steps():
   out, al, pr = sess.run([nodes["Outputs"], nodes["Alphas"], nodes["Predict_real"]])
   assert out.shape == (2, 256, 256, 3) and al.shape == (2, 256, 256, 3) and pr.shape == (2, 30, 30, 1)
   assert 0 <= al.min() and al.max() <= 1 and 0 < pr.min() and pr.max() < 1
-  path = net.save("/tmp/vp_test_ckpt.npz")
+  path = net.save(str(tmp_path / "vp_test_ckpt.npz"))
   z = np.load(path)
   assert "generator/encoder_1/conv2d/kernel" in z.files and "discriminator/layer_4/conv2d/kernel/Adam_1" in z.files
   assert int(z["global_step"]) == 6

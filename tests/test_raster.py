@@ -1,7 +1,7 @@
 """Rasteriser parity (SURVEY.md 8f-1 "next" row): vp_render_colors / utils.mesh_core vs the reference's mesh_core.cpp.
 
-CPU: the numpy restatement against the reference-captured golden (tests/golden/raster.npz, produced by the compiled
-     reference) and, when oracle/_ref is built, against the compiled reference itself on a fresh seed.
+CPU: the numpy restatement against the reference-captured goldens (tests/golden/raster.npz, raster_seed17.npz, produced by the
+     compiled reference) and, when oracle/_ref is built, against the compiled reference itself on the seed-17 mesh.
 GPU: the HIP kernels against the golden and the restatement, BIT-EXACT (uint8 image / mask, float32 depth bits),
      single frame through the reference's positional signature and a batch of frames in one launch."""
 import os
@@ -12,6 +12,7 @@ import pytest
 from oracle import raster_ref as rr
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "raster.npz")
+GOLD17 = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "raster_seed17.npz")
 
 
 def _case(tag):
@@ -29,10 +30,17 @@ def test_restatement_matches_reference_golden(tag):
   assert 0.2 < (mask > 0).mean() < 0.95            # the fixture really covers pixels, and leaves background
 
 
-@pytest.mark.skipif(not rr.have_compiled_reference(), reason="oracle/_ref not built (make -C oracle; needs /root/reference)")
 def test_restatement_matches_compiled_reference():
+  """The seed-17 mesh: the compiled reference's frame as tests/golden/raster_seed17.npz holds it, and the compiled reference itself
+  when oracle/_ref is built (make -C oracle)."""
   v, t, c = rr.synthetic_mesh(seed=17, nlat=20, nlon=24, h=120, w=100)
-  a = rr.render_colors_ref(v, t, c, 120, 100)
+  g = np.load(GOLD17)
+  for k, x in (("vertices", v), ("triangles", t), ("colors", c)):
+    assert np.array_equal(g[k], x), k                 # the mesh is the one the golden was captured on
+  a = (g["image"], g["mask"], g["depth"])
+  if rr.have_compiled_reference():
+    for x, y in zip(rr.render_colors_ref(v, t, c, 120, 100), a):
+      assert np.array_equal(x, y)
   b = rr.render_colors_py(v, t, c, 120, 100)
   for x, y in zip(a, b):
     assert np.array_equal(x, y)
