@@ -328,6 +328,58 @@ int vp_bfmnet_set_decoder_dropout(vp_bfmnet_t* h, const float* mask0, const floa
 int vp_bfmnet_tensor(vp_bfmnet_t* h, const char* name, void** ptr, int64_t shape[4]);
 
 /* ------------------------------------------------------------------------------------------------
+ * Streaming BFMNet inference (one session per handle): PCM goes in by chunks of any size, the 64 coefficients of a video frame come
+ * out as soon as the frame's receptive field has arrived - the same frames, with the same values up to kernel choice, as
+ * vp_logmel_forward + vp_bfmnet_forward on the whole clip padded as infer_bfmvid.py:162-167 pads it (pad_len = 1 + N / 640 frames).
+ *   - Every mel frame (512 samples, hop 128) is computed once, by the log-mel kernel of vp_logmel_forward, into a device history.
+ *   - Every MfccNet convolution has time stride 1, so a frame's pooled encoding depends on a bounded window of mel rows: left_mel /
+ *     right_mel (vp_bfmstream_context, derived from the layer table).  A push recomputes the trunk on a window of
+ *     T_win = max_chunk_frames + left + right frames around the frames it emits; the GRU runs over the emitted frames only, its state
+ *     carried across pushes (bit-identical to one uncut run).
+ *   - Emission counts follow from sample counts alone: the host never waits on the device inside push / finish.
+ * 640 samples per video frame, 5 mel frames per video frame (config/params.yml: 16 kHz, 25 frames/s, hop 128, window 512).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct vp_bfmstream_desc {
+  int struct_bytes;       /* sizeof(vp_bfmstream_desc) of the caller's build: must equal vp_bfmstream_desc_size() */
+  int max_chunk_frames;   /* most frames one window emits (1 .. 1024); a push that makes more ready runs several windows */
+  int num_mel_bins;       /* 80 */
+  int trunk_dtype;        /* VP_F32 or VP_BF16, as vp_bfmnet_desc */
+  int sample_rate;        /* mel matrix: 16000 */
+  float lower_hz, upper_hz;   /* 80, 7600 */
+} vp_bfmstream_desc;
+/* Same ABI rule as vp_pixrefer_desc: the struct only grows at the tail; entry points refuse a descriptor whose struct_bytes differs */
+size_t vp_bfmstream_desc_size(void);
+typedef struct vp_bfmstream vp_bfmstream_t;
+/* Host only.  Receptive field of one pooled frame in mel rows (left_mel, right_mel), the same in video frames, and the window plan's
+ * frames.  Any output pointer may be NULL.  VP_ERR_ARG on a bad descriptor. */
+int vp_bfmstream_context(const vp_bfmstream_desc* d, int* left_mel, int* right_mel, int* left_frames, int* right_frames, int* window_frames);
+/* Host only.  Frames emitted in all once `samples` samples have been pushed (finished = 0), or after finish (finished = 1: pad_len) */
+long long vp_bfmstream_frames_after(const vp_bfmstream_desc* d, long long samples, int finished);
+size_t vp_bfmstream_workspace_bytes(const vp_bfmstream_desc* d);
+/* params: the vp_bfmnet_* parameter arena (vp_bfmnet_param_info), device, read at every window; vp_bfmstream_params_changed after
+ * writing it */
+int vp_bfmstream_create(const vp_bfmstream_desc* d, void* workspace, size_t workspace_bytes, const float* params, void* stream,
+                        vp_bfmstream_t** out);
+void vp_bfmstream_destroy(vp_bfmstream_t* h);
+int vp_bfmstream_params_changed(vp_bfmstream_t* h);
+/* back to an empty session (no samples, zero GRU state), enqueued on stream */
+int vp_bfmstream_reset(vp_bfmstream_t* h, void* stream);
+/* Host only: frames the next push of n_new_samples emits (vp_bfmstream_ready) / finish emits (vp_bfmstream_ready_finish) */
+int vp_bfmstream_ready(const vp_bfmstream_t* h, long long n_new_samples);
+int vp_bfmstream_ready_finish(const vp_bfmstream_t* h);
+/* pcm [n] f32 device; ears [k,1] and coeff_out [k,64] device with k = vp_bfmstream_ready(h, n) (may be NULL when k = 0) */
+int vp_bfmstream_push(vp_bfmstream_t* h, const float* pcm, long long n, const float* ears, float* coeff_out, void* stream);
+/* end of the clip: zero-pads as prepare_pcm does and emits the last k = vp_bfmstream_ready_finish(h) frames; the session then takes
+ * no more pushes until vp_bfmstream_reset */
+int vp_bfmstream_finish(vp_bfmstream_t* h, const float* ears, float* coeff_out, void* stream);
+/* "mel" (the mel history ring, [rows][num_mel_bins]; row r of the clip sits at r % rows) */
+int vp_bfmstream_tensor(vp_bfmstream_t* h, const char* name, void** ptr, int64_t shape[4]);
+/* The stateful GRU step loop on its own (testing / other drivers): rows [t0, t0 + n) of each of b sequences of t rows, state in / out
+ * in hstate [b][256] (zeros = a fresh sequence).  Same layout as vp_gru_seq. */
+int vp_gru_seq_state(const float* xg, const float* xc, const float* whg, const float* whc, float* hstate, float* out, int b, int t, int t0,
+                     int n, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Single pointwise / audio ops of the two executors (the entry-point list of SURVEY.md 8b), for parity tests and reuse.
  *   vp_maxpool2x2_*      slim max_pool2d 2x2/2 of vgg_simple.py:141,146 (NHWC).  bwd goes through the pool AND the ReLU of the conv
  *                        that produced x (x is stored post-relu): the gradient lands on the FIRST maximum of a window if it is > 0

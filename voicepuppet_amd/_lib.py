@@ -33,6 +33,11 @@ class BfmNetDesc(ctypes.Structure):
   _fields_ = [("batch", ctypes.c_int), ("frames", ctypes.c_int), ("num_mel_bins", ctypes.c_int), ("trunk_dtype", ctypes.c_int)]
 
 
+class BfmStreamDesc(ctypes.Structure):
+  _fields_ = [("struct_bytes", ctypes.c_int), ("max_chunk_frames", ctypes.c_int), ("num_mel_bins", ctypes.c_int),
+              ("trunk_dtype", ctypes.c_int), ("sample_rate", ctypes.c_int), ("lower_hz", ctypes.c_float), ("upper_hz", ctypes.c_float)]
+
+
 class BfmModel(ctypes.Structure):
   _fields_ = [("nver", ctypes.c_int), ("ntri", ctypes.c_int), ("meanshape", ctypes.c_void_p), ("idBase", ctypes.c_void_p),
               ("exBase", ctypes.c_void_p), ("meantex", ctypes.c_void_p), ("texBase", ctypes.c_void_p), ("tri", ctypes.c_void_p),
@@ -125,6 +130,20 @@ _SIGNATURES = {
     "vp_bfmnet_forward": (ctypes.c_int, [_P, _P, _P, _P, _P, _P]),
     "vp_bfmnet_set_decoder_dropout": (ctypes.c_int, [_P, _P, _P]),
     "vp_bfmnet_tensor": (ctypes.c_int, [_P, ctypes.c_char_p, ctypes.POINTER(_P), ctypes.POINTER(ctypes.c_int64)]),
+    "vp_bfmstream_desc_size": (ctypes.c_size_t, []),
+    "vp_bfmstream_context": (ctypes.c_int, [ctypes.POINTER(BfmStreamDesc)] + [ctypes.POINTER(ctypes.c_int)] * 5),
+    "vp_bfmstream_frames_after": (ctypes.c_longlong, [ctypes.POINTER(BfmStreamDesc), ctypes.c_longlong, ctypes.c_int]),
+    "vp_bfmstream_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(BfmStreamDesc)]),
+    "vp_bfmstream_create": (ctypes.c_int, [ctypes.POINTER(BfmStreamDesc), _P, ctypes.c_size_t, _P, _P, ctypes.POINTER(_P)]),
+    "vp_bfmstream_destroy": (None, [_P]),
+    "vp_bfmstream_params_changed": (ctypes.c_int, [_P]),
+    "vp_bfmstream_reset": (ctypes.c_int, [_P, _P]),
+    "vp_bfmstream_ready": (ctypes.c_int, [_P, ctypes.c_longlong]),
+    "vp_bfmstream_ready_finish": (ctypes.c_int, [_P]),
+    "vp_bfmstream_push": (ctypes.c_int, [_P, _P, ctypes.c_longlong, _P, _P, _P]),
+    "vp_bfmstream_finish": (ctypes.c_int, [_P, _P, _P, _P]),
+    "vp_bfmstream_tensor": (ctypes.c_int, [_P, ctypes.c_char_p, ctypes.POINTER(_P), ctypes.POINTER(ctypes.c_int64)]),
+    "vp_gru_seq_state": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P]),
     "vp_maxpool2x2_fwd": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P]),
     "vp_maxpool2x2_bwd": (ctypes.c_int, [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P]),
     "vp_composite_fwd": (ctypes.c_int, [_P, _P, _P, _P, _P, ctypes.c_int, ctypes.c_int, _P]),
@@ -204,6 +223,10 @@ def lib():
       want = int(l.vp_pixrefer_desc_size())
       if want != ctypes.sizeof(PixReferDesc):
         raise RuntimeError("%s: vp_pixrefer_desc is %d bytes in the library, %d in this binding" % (LIB_PATH, want, ctypes.sizeof(PixReferDesc)))
+    if hasattr(l, "vp_bfmstream_desc_size") and l.vp_bfmstream_desc_size.argtypes is not None:
+      want = int(l.vp_bfmstream_desc_size())
+      if want != ctypes.sizeof(BfmStreamDesc):
+        raise RuntimeError("%s: vp_bfmstream_desc is %d bytes in the library, %d in this binding" % (LIB_PATH, want, ctypes.sizeof(BfmStreamDesc)))
     _lib = l
   return _lib
 

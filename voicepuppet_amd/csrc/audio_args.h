@@ -21,6 +21,11 @@ hipError_t launch_cvt_f32_bf16(const float* x, void* y, size_t n, hipStream_t st
 hipError_t launch_maxpool_same(const void* x, void* y, int in_bf16, int out_bf16, int B, int H, int W, int C, int kh, int kw, int sh, int sw, int pt, int pl, int Ho, int Wo, hipStream_t st);
 hipError_t launch_fold_bn(const float* w, const float* beta, const float* mean, const float* var, float eps, size_t n, int C, float* wf, float* bf, hipStream_t st);
 hipError_t launch_gru_seq(const float* xg, const float* xc, const float* whg, const float* whc, const int* seq_len, float* out, int B, int T, hipStream_t st);
+// gru_fwd_state_kernel: rows [t0, t0 + n) of each sequence's T rows, state in / out in hstate [B][256]
+hipError_t launch_gru_state(const float* xg, const float* xc, const float* whg, const float* whc, float* hstate, float* out, int B, int T, int t0, int n,
+                            hipStream_t st);
+// rows [r0, r0 + rows) of a mel ring buffer [cap][nmel] -> out [rows][nmel], rows >= avail zero
+hipError_t launch_mel_window(const float* ring, int cap, int nmel, long long r0, int rows, long long avail, float* out, hipStream_t st);
 hipError_t launch_add_ears(float* out, const float* ears, int n, hipStream_t st);
 hipError_t launch_mul_inplace(float* x, const float* m, size_t n, hipStream_t st);
 }  // namespace vp

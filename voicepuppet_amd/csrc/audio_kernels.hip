@@ -391,6 +391,32 @@ __global__ __launch_bounds__(256) void fold_bn_kernel(const float* __restrict__ 
 
 // tf.contrib.rnn.GRUCell over T steps (dynamic_rnn semantics): gru_device.h (gru_fwd_kernel<false>), one 1024-thread block per sequence
 
+// The same recurrence with the state carried in and out (streaming inference): sequence b starts from hstate[b] (h_{t0-1}), runs rows
+// [t0, t0 + n) of its T-row xg / xc / out blocks, and leaves h_{t0+n-1} in hstate[b].  The step is gru_step, so a sequence cut into
+// pieces gives the same bits as one uncut gru_fwd_kernel run.
+__global__ __launch_bounds__(1024) void gru_fwd_state_kernel(const float* __restrict__ xg, const float* __restrict__ xc, const float* __restrict__ whg,
+                                                             const float* __restrict__ whc, float* __restrict__ hstate, float* __restrict__ out,
+                                                             int t0, int n, int T) {
+  __shared__ float h[256], rh[256], part[1024];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  if (tid < 256) h[tid] = hstate[(size_t)b * 256 + tid];
+  __syncthreads();
+  for (int t = t0; t < t0 + n; ++t)
+    gru_step<false>(xg, xc, whg, whc, out, nullptr, nullptr, nullptr, nullptr, (size_t)b * T + t, tid, h, rh, part);
+  if (tid < 256) hstate[(size_t)b * 256 + tid] = h[tid];
+}
+
+// Streaming inference: rows [r0, r0 + rows) of the mel history (a ring of cap rows x nmel) as one contiguous MfccNet input; rows at or
+// past `avail` (not received yet) are zero.  A pure copy: the mel values are the bits the log-mel kernel wrote.
+__global__ __launch_bounds__(256) void mel_window_kernel(const float* __restrict__ ring, int cap, int nmel, long long r0, int rows, long long avail,
+                                                         float* __restrict__ out) {
+  const size_t n = (size_t)rows * nmel;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+    const long long r = r0 + (long long)(i / nmel);
+    out[i] = r < avail ? ring[(size_t)(r % cap) * nmel + i % nmel] : 0.f;
+  }
+}
+
 // x *= m, element-wise (the opt-in decoder dropout masks of BFMNet inference: 0 or 1 / keep_prob)
 __global__ void mul_inplace_kernel(float* __restrict__ x, const float* __restrict__ m, size_t n) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -470,6 +496,15 @@ hipError_t launch_fold_bn(const float* w, const float* beta, const float* mean, 
 hipError_t launch_gru_seq(const float* xg, const float* xc, const float* whg, const float* whc, const int* seq_len, float* out, int B, int T, hipStream_t st) {
   hipLaunchKernelGGL(gru_fwd_kernel<false>, dim3(B), dim3(1024), 0, st, xg, xc, whg, whc, seq_len, out, (float*)nullptr, (float*)nullptr, (float*)nullptr,
                      (float*)nullptr, T);
+  return hipGetLastError();
+}
+hipError_t launch_gru_state(const float* xg, const float* xc, const float* whg, const float* whc, float* hstate, float* out, int B, int T, int t0, int n,
+                            hipStream_t st) {
+  hipLaunchKernelGGL(gru_fwd_state_kernel, dim3(B), dim3(1024), 0, st, xg, xc, whg, whc, hstate, out, t0, n, T);
+  return hipGetLastError();
+}
+hipError_t launch_mel_window(const float* ring, int cap, int nmel, long long r0, int rows, long long avail, float* out, hipStream_t st) {
+  hipLaunchKernelGGL(mel_window_kernel, dim3(nblk((size_t)rows * nmel, 256)), dim3(256), 0, st, ring, cap, nmel, r0, rows, avail, out);
   return hipGetLastError();
 }
 hipError_t launch_mul_inplace(float* x, const float* m, size_t n, hipStream_t st) {

@@ -26,6 +26,43 @@ __device__ __forceinline__ float gru_dot(const float* __restrict__ v, const floa
   return (s0 + s1) + (s2 + s3);
 }
 
+// One step of the recurrence at row o of xg / xc (block-wide: every thread calls it).  h [256] in LDS holds h_{t-1} and h_t on
+// return; the new state is also written to out[o].  TRAIN: also saves r, u, c and h_prev (what the backward pass needs).
+template <bool TRAIN>
+__device__ __forceinline__ void gru_step(const float* __restrict__ xg, const float* __restrict__ xc, const float* __restrict__ whg,
+                                         const float* __restrict__ whc, float* __restrict__ out, float* __restrict__ sr, float* __restrict__ su,
+                                         float* __restrict__ sc, float* __restrict__ shp, size_t o, int tid, float* h, float* rh, float* part) {
+  {   // gates: column c of 512, half kh of the 256 h units
+    const int c = tid & 511, kh = tid >> 9;
+    part[tid] = gru_dot<128>(h + kh * 128, whg + (size_t)(kh * 128) * 512 + c, 512);
+  }
+  __syncthreads();
+  float r = 0.f, u = 0.f;
+  if (tid < 256) {
+    const float ar = xg[o * 512 + tid] + (part[tid] + part[512 + tid]);
+    const float au = xg[o * 512 + 256 + tid] + (part[256 + tid] + part[768 + tid]);
+    r = 1.f / (1.f + expf(-ar)); u = 1.f / (1.f + expf(-au));
+    rh[tid] = r * h[tid];
+  }
+  __syncthreads();
+  {   // candidate: column c of 256, quarter kq of the 256 (r * h) values
+    const int c = tid & 255, kq = tid >> 8;
+    part[tid] = gru_dot<64>(rh + kq * 64, whc + (size_t)(kq * 64) * 256 + c, 256);
+  }
+  __syncthreads();
+  float hn = 0.f;
+  if (tid < 256) {
+    const float ac = xc[o * 256 + tid] + ((part[tid] + part[256 + tid]) + (part[512 + tid] + part[768 + tid]));
+    const float c = tanhf(ac), hp = h[tid];
+    hn = u * hp + (1.f - u) * c;
+    if (TRAIN) { sr[o * 256 + tid] = r; su[o * 256 + tid] = u; sc[o * 256 + tid] = c; shp[o * 256 + tid] = hp; }
+    out[o * 256 + tid] = hn;
+  }
+  __syncthreads();                                 // every read of h (gate products, r * h, h_prev) is done
+  if (tid < 256) h[tid] = hn;
+  __syncthreads();
+}
+
 // TRAIN: also saves r, u, c and h_prev per step (what the backward pass needs)
 template <bool TRAIN>
 __global__ __launch_bounds__(1024) void gru_fwd_kernel(const float* __restrict__ xg, const float* __restrict__ xc, const float* __restrict__ whg,
@@ -45,35 +82,7 @@ __global__ __launch_bounds__(1024) void gru_fwd_kernel(const float* __restrict__
       }
       continue;
     }
-    {   // gates: column c of 512, half kh of the 256 h units
-      const int c = tid & 511, kh = tid >> 9;
-      part[tid] = gru_dot<128>(h + kh * 128, whg + (size_t)(kh * 128) * 512 + c, 512);
-    }
-    __syncthreads();
-    float r = 0.f, u = 0.f;
-    if (tid < 256) {
-      const float ar = xg[o * 512 + tid] + (part[tid] + part[512 + tid]);
-      const float au = xg[o * 512 + 256 + tid] + (part[256 + tid] + part[768 + tid]);
-      r = 1.f / (1.f + expf(-ar)); u = 1.f / (1.f + expf(-au));
-      rh[tid] = r * h[tid];
-    }
-    __syncthreads();
-    {   // candidate: column c of 256, quarter kq of the 256 (r * h) values
-      const int c = tid & 255, kq = tid >> 8;
-      part[tid] = gru_dot<64>(rh + kq * 64, whc + (size_t)(kq * 64) * 256 + c, 256);
-    }
-    __syncthreads();
-    float hn = 0.f;
-    if (tid < 256) {
-      const float ac = xc[o * 256 + tid] + ((part[tid] + part[256 + tid]) + (part[512 + tid] + part[768 + tid]));
-      const float c = tanhf(ac), hp = h[tid];
-      hn = u * hp + (1.f - u) * c;
-      if (TRAIN) { sr[o * 256 + tid] = r; su[o * 256 + tid] = u; sc[o * 256 + tid] = c; shp[o * 256 + tid] = hp; }
-      out[o * 256 + tid] = hn;
-    }
-    __syncthreads();                                 // every read of h (gate products, r * h, h_prev) is done
-    if (tid < 256) h[tid] = hn;
-    __syncthreads();
+    gru_step<TRAIN>(xg, xc, whg, whc, out, sr, su, sc, shp, o, tid, h, rh, part);
   }
 }
 

@@ -306,6 +306,16 @@ int vp_gru_seq(const float* xg, const float* xc, const float* whg, const float* 
   return VP_OK;
 }
 
+int vp_gru_seq_state(const float* xg, const float* xc, const float* whg, const float* whc, float* hstate, float* out, int b, int t, int t0,
+                     int n, void* stream) {
+  if (!xg || !xc || !whg || !whc || !hstate || !out || b < 1 || t < 1 || t0 < 0 || n < 0 || t0 + n > t) {
+    set_err("vp_gru_seq_state: bad argument"); return VP_ERR_ARG;
+  }
+  if (n == 0) return VP_OK;
+  VP_HIP_CHECK(launch_gru_state(xg, xc, whg, whc, hstate, out, b, t, t0, n, (hipStream_t)stream));
+  return VP_OK;
+}
+
 }  // extern "C"
 
 // CRC-32C (Castagnoli) of a host buffer, continuing from `crc` (0 to start): what TensorFlow's checkpoint bundles checksum every tensor

@@ -436,9 +436,11 @@ void vp_bfmnet_destroy(vp_bfmnet_t* h) { delete h; }
 
 int vp_bfmnet_params_changed(vp_bfmnet_t* h) { if (!h) return VP_ERR_ARG; h->dirty = true; return VP_OK; }
 
-int vp_bfmnet_forward(vp_bfmnet_t* h, const float* ears, const float* mfccs, const int* seq_len, float* out, void* stream) {
-  if (!h || !ears || !mfccs || !seq_len || !out) { set_err("vp_bfmnet_forward: null argument"); return VP_ERR_ARG; }
-  hipStream_t st = (hipStream_t)stream;
+}  // extern "C"
+
+// The forward in stages (the streaming executor below runs the same stages on a window plan, with its own recurrence between them):
+// bfm_trunk: mfccs [B,5T,80] -> MfccNet -> MfccEncoder -> RNNModule dense -> the GRU's input projections h->xg / h->xc
+static int bfm_trunk(vp_bfmnet* h, const float* mfccs, hipStream_t st) {
   int rc;
   if (h->dirty && (rc = prepare_weights(h, st))) return rc;
   BfmModel& m = h->m;
@@ -500,14 +502,36 @@ int vp_bfmnet_forward(vp_bfmnet_t* h, const float* ears, const float* mfccs, con
   if ((rc = run_gemm(h, m.g_rnn, h->enc, h->c1, ACT_LEAKY, 0, st))) return rc;
   if ((rc = run_gemm(h, m.g_xg, h->c1, h->xg, ACT_NONE, 0, st))) return rc;
   if ((rc = run_gemm(h, m.g_xc, h->c1, h->xc, ACT_NONE, 0, st))) return rc;
-  VP_HIP_CHECK(launch_gru_seq(h->xg, h->xc, h->params + m.gk + (size_t)256 * 512, h->params + m.ck + (size_t)256 * 256, seq_len, h->rnn, B, T, st));
+  return VP_OK;
+}
+
+// recurrent halves of the GRU's gate / candidate kernels (rows 256..511 of each)
+static const float* gru_whg(vp_bfmnet* h) { return h->params + h->m.gk + (size_t)256 * 512; }
+static const float* gru_whc(vp_bfmnet* h) { return h->params + h->m.ck + (size_t)256 * 256; }
+
+// bfm_decode: h->rnn [B,T,256] -> BFMCoeffDecoder -> out [B,T,64] (+ ears [B,T,1] when given)
+static int bfm_decode(vp_bfmnet* h, const float* ears, float* out, hipStream_t st) {
+  int rc;
+  BfmModel& m = h->m;
+  const int B = h->d.batch, T = h->d.frames;
   if ((rc = run_gemm(h, m.g_d0, h->rnn, h->dd0, ACT_LEAKY, 0, st))) return rc;
   if (h->drop0) VP_HIP_CHECK(launch_mul_inplace(h->dd0, h->drop0, (size_t)B * T * 128, st));
   if ((rc = run_gemm(h, m.g_d1, h->dd0, h->dd1, ACT_LEAKY, 0, st))) return rc;
   if (h->drop1) VP_HIP_CHECK(launch_mul_inplace(h->dd1, h->drop1, (size_t)B * T * 64, st));
   if ((rc = run_gemm(h, m.g_d2, h->dd1, out, ACT_NONE, 0, st))) return rc;
-  VP_HIP_CHECK(launch_add_ears(out, ears, B * T, st));
+  if (ears) VP_HIP_CHECK(launch_add_ears(out, ears, B * T, st));
   return VP_OK;
+}
+
+extern "C" {
+
+int vp_bfmnet_forward(vp_bfmnet_t* h, const float* ears, const float* mfccs, const int* seq_len, float* out, void* stream) {
+  if (!h || !ears || !mfccs || !seq_len || !out) { set_err("vp_bfmnet_forward: null argument"); return VP_ERR_ARG; }
+  hipStream_t st = (hipStream_t)stream;
+  int rc;
+  if ((rc = bfm_trunk(h, mfccs, st))) return rc;
+  VP_HIP_CHECK(launch_gru_seq(h->xg, h->xc, gru_whg(h), gru_whc(h), seq_len, h->rnn, h->d.batch, h->d.frames, st));
+  return bfm_decode(h, ears, out, st);
 }
 
 int vp_bfmnet_set_decoder_dropout(vp_bfmnet_t* h, const float* mask0, const float* mask1) {
@@ -527,6 +551,347 @@ int vp_bfmnet_tensor(vp_bfmnet_t* h, const char* name, void** ptr, int64_t shape
   else return VP_ERR_ARG;
   *ptr = p;
   if (shape) { shape[0] = B; shape[1] = T; shape[2] = c; shape[3] = 1; }
+  return VP_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------
+// Streaming BFMNet inference (include/vp_hip.h, vp_bfmstream_*)
+//   PCM  -> two staging buffers (ping-pong: the samples of the next mel frame are carried over, < 512) -> logmel512 -> mel ring
+//   ring -> window [w0, w0 + Tw) frames (mel_window_kernel, rows not received yet are zero) -> bfm_trunk on a window plan
+//        -> stateful GRU over the emitted frames only -> bfm_decode -> the emitted rows + ears to the caller
+// A frame f is emitted before finish once mel rows up to 5f + 4 + R have arrived; the window then starts Lf frames before the first
+// emitted frame (or at the clip start) and reaches Rf frames past the last, so every emitted frame sees exactly what the offline
+// forward shows it.  At finish the window's right edge sits at pad_len, where the offline sequence ends (its SAME padding).
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+constexpr int kHop = 128, kWin = 512, kMelPerFrame = 5, kSamplesPerFrame = kHop * kMelPerFrame;
+constexpr int kMaxChunkFrames = 1024;
+
+struct StreamGeo { int L, R, Lf, Rf, Tw, cap, piece; };
+
+// receptive field of a pooled frame's mel rows, from the layer table: the stem's SAME time padding, each block's depthwise SAME
+// padding, each SAME max-pool's (stride 1 in time: pads (0, k - 1)); the MfccEncoder pool is aligned to frames (5 rows, stride 5)
+void receptive_field(const BfmModel& m, int* L, int* R) {
+  auto kt = [&](size_t off) {
+    for (const PInfo& p : m.manifest) if (p.off == off) return (int)p.shape[0];
+    return 1;
+  };
+  int l = 0, r = 0, pb, o;
+  int k = kt(m.stem.w);
+  same_pad(1 << 20, k, 1, &pb, &o); l += pb; r += k - 1 - pb;
+  for (const Block& b : m.blocks) {
+    k = kt(b.dw.w);
+    same_pad(1 << 20, k, 1, &pb, &o); l += pb; r += k - 1 - pb;
+    if (b.pool) { same_pad(1 << 20, 2, 1, &pb, &o); l += pb; r += 2 - 1 - pb; }
+  }
+  *L = l; *R = r;
+}
+
+bool stream_ok(const vp_bfmstream_desc* d) {
+  return d && d->struct_bytes == (int)sizeof(vp_bfmstream_desc) && d->max_chunk_frames >= 1 && d->max_chunk_frames <= kMaxChunkFrames &&
+         d->num_mel_bins == 80 && (d->trunk_dtype == VP_F32 || d->trunk_dtype == VP_BF16) && d->sample_rate > 0 && d->lower_hz >= 0.f &&
+         d->upper_hz > d->lower_hz && d->upper_hz <= d->sample_rate * 0.5f;
+}
+
+StreamGeo stream_geo(const vp_bfmstream_desc* d, const BfmModel& m) {
+  StreamGeo g{};
+  receptive_field(m, &g.L, &g.R);
+  g.Lf = (g.L + kMelPerFrame - 1) / kMelPerFrame;
+  g.Rf = (g.R + kMelPerFrame - 1) / kMelPerFrame;
+  g.Tw = d->max_chunk_frames + g.Lf + g.Rf;
+  g.piece = kMelPerFrame * d->max_chunk_frames;            // most mel frames one staging buffer yields
+  // the ring keeps rows [5 w0, mel_done): before a piece that is < 5 Lf + R + 5 rows (the unemitted tail + the left context), a piece
+  // adds `piece`; at finish the last window reads 5 Tw rows
+  const int during = kMelPerFrame * g.Lf + g.R + kMelPerFrame + g.piece;
+  // (finish appends its <= 8 rows of padding without emitting: the kMelPerFrame + 16 rows of slack cover them)
+  g.cap = (during > kMelPerFrame * g.Tw ? during : kMelPerFrame * g.Tw) + 24;
+  return g;
+}
+
+long long mel_avail(long long n) { return n >= kWin ? (n - kWin) / kHop + 1 : 0; }
+long long pad_len_of(long long n) { return 1 + n / kSamplesPerFrame; }
+long long emitted_after(const StreamGeo& g, long long n, bool fin) {
+  if (fin) return pad_len_of(n);
+  const long long M = mel_avail(n);
+  return M >= kMelPerFrame + g.R ? (M - kMelPerFrame - g.R) / kMelPerFrame + 1 : 0;
+}
+
+size_t bfm_plan_bytes(vp_bfmnet* scratch, int frames) {
+  scratch->d.frames = frames;
+  return bfm_carve(scratch, nullptr);
+}
+
+}  // namespace
+
+struct vp_bfmstream {
+  vp_bfmstream_desc d;
+  StreamGeo g;
+  const float* params;
+  vp_logmel_t* lm;                 // constants of the log-mel kernel (window, twiddles, mel matrix)
+  vp_bfmnet* win;                  // the T_win window plan
+  vp_bfmnet* shrt;                 // exact-size plan of a clip shorter than T_win, carved at finish
+  char *lm_base, *win_base, *short_base;   // sub-regions of the workspace
+  size_t lm_bytes, win_bytes, short_bytes;
+  float *stage[2], *ring, *mwin, *hstate, *dout;
+  int cur, carry;                  // staging buffer holding the carried samples, and their count
+  long long samples, mel_done, emitted;
+  bool finished;
+};
+
+static size_t stream_carve(vp_bfmstream* s, char* base, vp_logmel_desc* lmd) {
+  Bump ar{base, 0};
+  const StreamGeo& g = s->g;
+  const size_t stage = (size_t)kWin + (size_t)kHop * g.piece;
+  s->stage[0] = (float*)ar.alloc(stage * 4);
+  s->stage[1] = (float*)ar.alloc(stage * 4);
+  s->ring = (float*)ar.alloc((size_t)g.cap * s->d.num_mel_bins * 4);
+  s->mwin = (float*)ar.alloc((size_t)kMelPerFrame * g.Tw * s->d.num_mel_bins * 4);
+  s->hstate = (float*)ar.alloc(256 * 4);
+  s->dout = (float*)ar.alloc((size_t)g.Tw * 64 * 4);
+  *lmd = vp_logmel_desc{s->d.sample_rate, s->d.num_mel_bins, kWin, kHop, kWin, s->d.lower_hz, s->d.upper_hz, 1, kWin};
+  s->lm_bytes = vp_logmel_workspace_bytes(lmd);
+  s->lm_base = (char*)ar.alloc(s->lm_bytes);
+  // the window plan, then the largest exact-size plan of a clip shorter than it
+  vp_bfmnet tmp{};
+  tmp.d = vp_bfmnet_desc{1, g.Tw, s->d.num_mel_bins, s->d.trunk_dtype};
+  build_model(tmp.m);
+  s->win_bytes = bfm_plan_bytes(&tmp, g.Tw);
+  s->win_base = (char*)ar.alloc(s->win_bytes);
+  size_t sb = 0;
+  for (int t = 1; t < g.Tw; ++t) { const size_t b = bfm_plan_bytes(&tmp, t); if (b > sb) sb = b; }
+  s->short_bytes = sb;
+  s->short_base = (char*)ar.alloc(sb);
+  return ar.off + 256;
+}
+
+static int stream_reset(vp_bfmstream* s, hipStream_t st) {
+  s->cur = 0; s->carry = 0; s->samples = 0; s->mel_done = 0; s->emitted = 0; s->finished = false;
+  VP_HIP_CHECK(hipMemsetAsync(s->hstate, 0, 256 * 4, st));
+  return VP_OK;
+}
+
+// n samples (src: device PCM, or NULL for zeros) through the staging buffers into mel rows; emission is the caller's
+static int stream_append(vp_bfmstream* s, const float* src, long long n, hipStream_t st) {
+  const int nmel = s->d.num_mel_bins;
+  const vp_logmel* lm = s->lm;
+  float* a = s->stage[s->cur];
+  const int q = (int)n;                                    // (<= kHop * piece: the caller splits)
+  if (src) VP_HIP_CHECK(hipMemcpyAsync(a + s->carry, src, (size_t)q * 4, hipMemcpyDeviceToDevice, st));
+  else VP_HIP_CHECK(hipMemsetAsync(a + s->carry, 0, (size_t)q * 4, st));
+  const int ls = s->carry + q;
+  const int F = ls >= kWin ? (ls - kWin) / kHop + 1 : 0;
+  if (F > 0) {
+    const int k = (int)(s->mel_done % s->g.cap);
+    const int n1 = F < s->g.cap - k ? F : s->g.cap - k;
+    VP_HIP_CHECK(launch_logmel512(a, lm->window, lm->w256, lm->w512, lm->mel, s->ring + (size_t)k * nmel, 1, ls, n1, kHop, nmel, st));
+    if (n1 < F)
+      VP_HIP_CHECK(launch_logmel512(a + (size_t)kHop * n1, lm->window, lm->w256, lm->w512, lm->mel, s->ring, 1, ls - kHop * n1, F - n1, kHop, nmel, st));
+    s->mel_done += F;
+    const int keep = ls - kHop * F;
+    VP_HIP_CHECK(hipMemcpyAsync(s->stage[s->cur ^ 1], a + (size_t)kHop * F, (size_t)keep * 4, hipMemcpyDeviceToDevice, st));
+    s->cur ^= 1;
+    s->carry = keep;
+  } else {
+    s->carry = ls;
+  }
+  s->samples += q;
+  return VP_OK;
+}
+
+// frames [f0, f0 + n) through one window; ears / out: their rows
+static int stream_window(vp_bfmstream* s, long long f0, int n, bool fin, const float* ears, float* out, hipStream_t st) {
+  const StreamGeo& g = s->g;
+  const long long pad = pad_len_of(s->samples);
+  vp_bfmnet* p = s->win;
+  if (fin && pad < g.Tw) {                                 // the whole clip is shorter than the window: an exact-size plan
+    if (!s->shrt || s->shrt->d.frames != (int)pad) {
+      delete s->shrt;
+      s->shrt = new vp_bfmnet{};
+      s->shrt->d = vp_bfmnet_desc{1, (int)pad, s->d.num_mel_bins, s->d.trunk_dtype};
+      build_model(s->shrt->m);
+      if (bfm_carve(s->shrt, nullptr) > s->short_bytes) { set_err("vp_bfmstream: short plan outgrew its region"); return VP_ERR_STATE; }
+      bfm_carve(s->shrt, s->short_base);
+      s->shrt->params = s->params;
+      s->shrt->dirty = true;
+      VP_HIP_CHECK(hipMemsetAsync(s->shrt->zeros, 0, 256, st));
+    }
+    p = s->shrt;
+  }
+  const int Tw = p->d.frames;
+  long long w0 = f0 - g.Lf > 0 ? f0 - g.Lf : 0;
+  if (fin && w0 + Tw > pad) w0 = pad - Tw > 0 ? pad - Tw : 0;
+  const int t0 = (int)(f0 - w0);
+  if ((long long)kMelPerFrame * w0 < s->mel_done - g.cap) { set_err("vp_bfmstream: window %lld left the mel history", w0); return VP_ERR_STATE; }
+  if (t0 < 0 || t0 + n > Tw) { set_err("vp_bfmstream: frames [%lld, %lld) outside window %lld + %d", f0, f0 + n, w0, Tw); return VP_ERR_STATE; }
+  int rc;
+  VP_HIP_CHECK(launch_mel_window(s->ring, g.cap, s->d.num_mel_bins, (long long)kMelPerFrame * w0, kMelPerFrame * Tw, s->mel_done, s->mwin, st));
+  if ((rc = bfm_trunk(p, s->mwin, st))) return rc;
+  VP_HIP_CHECK(launch_gru_state(p->xg, p->xc, gru_whg(p), gru_whc(p), s->hstate, p->rnn, 1, Tw, t0, n, st));
+  if ((rc = bfm_decode(p, nullptr, s->dout, st))) return rc;
+  VP_HIP_CHECK(hipMemcpyAsync(out, s->dout + (size_t)t0 * 64, (size_t)n * 64 * 4, hipMemcpyDeviceToDevice, st));
+  VP_HIP_CHECK(launch_add_ears(out, ears, n, st));
+  s->emitted += n;
+  return VP_OK;
+}
+
+// everything ready now, in windows of at most max_chunk_frames; *done: rows of ears / out used so far
+static int stream_emit(vp_bfmstream* s, bool fin, const float* ears, float* out, long long* done, hipStream_t st) {
+  const long long target = emitted_after(s->g, s->samples, fin);
+  int rc;
+  while (s->emitted < target) {
+    const long long left = target - s->emitted;
+    const int n = (int)(left < s->d.max_chunk_frames ? left : s->d.max_chunk_frames);
+    if ((rc = stream_window(s, s->emitted, n, fin, ears + *done, out + *done * 64, st))) return rc;
+    *done += n;
+  }
+  return VP_OK;
+}
+
+// n samples (NULL src: zeros) in pieces of at most one staging buffer, emitting behind each when `emit`
+static int stream_feed(vp_bfmstream* s, const float* src, long long n, bool emit, const float* ears, float* out, long long* done, hipStream_t st) {
+  const long long most = (long long)kHop * s->g.piece;
+  int rc;
+  while (n > 0) {
+    const long long q = n < most ? n : most;
+    if ((rc = stream_append(s, src, q, st))) return rc;
+    if (emit && (rc = stream_emit(s, false, ears, out, done, st))) return rc;
+    if (src) src += q;
+    n -= q;
+  }
+  return VP_OK;
+}
+
+extern "C" {
+
+size_t vp_bfmstream_desc_size(void) { return sizeof(vp_bfmstream_desc); }
+
+int vp_bfmstream_context(const vp_bfmstream_desc* d, int* left_mel, int* right_mel, int* left_frames, int* right_frames, int* window_frames) {
+  if (!stream_ok(d)) { set_err("vp_bfmstream_context: bad descriptor"); return VP_ERR_ARG; }
+  BfmModel m;
+  build_model(m);
+  const StreamGeo g = stream_geo(d, m);
+  if (left_mel) *left_mel = g.L;
+  if (right_mel) *right_mel = g.R;
+  if (left_frames) *left_frames = g.Lf;
+  if (right_frames) *right_frames = g.Rf;
+  if (window_frames) *window_frames = g.Tw;
+  return VP_OK;
+}
+
+long long vp_bfmstream_frames_after(const vp_bfmstream_desc* d, long long samples, int finished) {
+  if (!stream_ok(d) || samples < 0) return -1;
+  BfmModel m;
+  build_model(m);
+  return emitted_after(stream_geo(d, m), samples, finished != 0);
+}
+
+size_t vp_bfmstream_workspace_bytes(const vp_bfmstream_desc* d) {
+  if (!stream_ok(d)) return 0;
+  vp_bfmstream s{};
+  s.d = *d;
+  BfmModel m;
+  build_model(m);
+  s.g = stream_geo(d, m);
+  vp_logmel_desc lmd;
+  return stream_carve(&s, nullptr, &lmd);
+}
+
+int vp_bfmstream_create(const vp_bfmstream_desc* d, void* workspace, size_t bytes, const float* params, void* stream, vp_bfmstream_t** out) {
+  if (!stream_ok(d) || !workspace || !params || !out) { set_err("vp_bfmstream_create: bad argument"); return VP_ERR_ARG; }
+  if (bytes < vp_bfmstream_workspace_bytes(d)) { set_err("vp_bfmstream_create: workspace too small"); return VP_ERR_WORKSPACE; }
+  vp_bfmstream* s = new vp_bfmstream{};
+  s->d = *d;
+  s->params = params;
+  {
+    BfmModel m;
+    build_model(m);
+    s->g = stream_geo(d, m);
+  }
+  vp_logmel_desc lmd;
+  stream_carve(s, (char*)workspace, &lmd);
+  hipStream_t st = (hipStream_t)stream;
+  int rc;
+  // (every failure past this point goes through vp_bfmstream_destroy: nothing of the half-built handle is left behind)
+  if ((rc = vp_logmel_create(&lmd, s->lm_base, s->lm_bytes, stream, &s->lm))) { vp_bfmstream_destroy(s); return rc; }
+  s->win = new vp_bfmnet{};
+  s->win->d = vp_bfmnet_desc{1, s->g.Tw, d->num_mel_bins, d->trunk_dtype};
+  build_model(s->win->m);
+  bfm_carve(s->win, s->win_base);
+  s->win->params = params;
+  s->win->dirty = true;
+  const hipError_t e = hipMemsetAsync(s->win->zeros, 0, 256, st);
+  if (e != hipSuccess) { set_err("vp_bfmstream_create: %s", hipGetErrorString(e)); vp_bfmstream_destroy(s); return VP_ERR_HIP; }
+  if ((rc = stream_reset(s, st))) { vp_bfmstream_destroy(s); return rc; }
+  *out = s;
+  return VP_OK;
+}
+
+void vp_bfmstream_destroy(vp_bfmstream_t* h) {
+  if (!h) return;
+  vp_logmel_destroy(h->lm);
+  delete h->win;
+  delete h->shrt;
+  delete h;
+}
+
+int vp_bfmstream_params_changed(vp_bfmstream_t* h) {
+  if (!h) return VP_ERR_ARG;
+  h->win->dirty = true;
+  if (h->shrt) h->shrt->dirty = true;
+  return VP_OK;
+}
+
+int vp_bfmstream_reset(vp_bfmstream_t* h, void* stream) {
+  if (!h) { set_err("vp_bfmstream_reset: null handle"); return VP_ERR_ARG; }
+  return stream_reset(h, (hipStream_t)stream);
+}
+
+int vp_bfmstream_ready(const vp_bfmstream_t* h, long long n) {
+  if (!h || n < 0 || h->finished) return 0;
+  return (int)(emitted_after(h->g, h->samples + n, false) - h->emitted);
+}
+
+int vp_bfmstream_ready_finish(const vp_bfmstream_t* h) {
+  if (!h || h->finished) return 0;
+  return (int)(pad_len_of(h->samples) - h->emitted);
+}
+
+int vp_bfmstream_push(vp_bfmstream_t* h, const float* pcm, long long n, const float* ears, float* coeff_out, void* stream) {
+  if (!h || n < 0 || (n > 0 && !pcm)) { set_err("vp_bfmstream_push: bad argument"); return VP_ERR_ARG; }
+  if (h->finished) { set_err("vp_bfmstream_push: the session is finished (vp_bfmstream_reset)"); return VP_ERR_STATE; }
+  if (vp_bfmstream_ready(h, n) > 0 && (!ears || !coeff_out)) { set_err("vp_bfmstream_push: frames are ready and ears / coeff_out is NULL"); return VP_ERR_ARG; }
+  long long done = 0;
+  return stream_feed(h, pcm, n, true, ears, coeff_out, &done, (hipStream_t)stream);
+}
+
+int vp_bfmstream_finish(vp_bfmstream_t* h, const float* ears, float* coeff_out, void* stream) {
+  if (!h) { set_err("vp_bfmstream_finish: null handle"); return VP_ERR_ARG; }
+  if (h->finished) { set_err("vp_bfmstream_finish: the session is finished (vp_bfmstream_reset)"); return VP_ERR_STATE; }
+  if (!ears || !coeff_out) { set_err("vp_bfmstream_finish: null ears / coeff_out"); return VP_ERR_ARG; }
+  hipStream_t st = (hipStream_t)stream;
+  const long long n = h->samples;
+  // prepare_pcm: 128 (5 pad_len - 1) + 512 samples in all, zeros past the clip
+  const long long total = (long long)kHop * (kMelPerFrame * pad_len_of(n) - 1) + kWin;
+  long long done = 0;
+  int rc;
+  // (the padding only appends mel rows: every frame still pending is emitted below by the finish rule, so a clip shorter than the window
+  // runs all its remaining frames on the exact-size plan)
+  if ((rc = stream_feed(h, nullptr, total - n, false, ears, coeff_out, &done, st))) return rc;
+  h->samples = n;                                          // (pad_len and the schedule are those of the clip, not of its padding)
+  if (h->mel_done != (long long)kMelPerFrame * pad_len_of(n)) { set_err("vp_bfmstream_finish: %lld mel frames", h->mel_done); return VP_ERR_STATE; }
+  if ((rc = stream_emit(h, true, ears, coeff_out, &done, st))) return rc;
+  h->finished = true;
+  return VP_OK;
+}
+
+int vp_bfmstream_tensor(vp_bfmstream_t* h, const char* name, void** ptr, int64_t shape[4]) {
+  if (!h || !name || !ptr) return VP_ERR_ARG;
+  if (std::string(name) != "mel") return VP_ERR_ARG;
+  *ptr = h->ring;
+  if (shape) { shape[0] = h->g.cap; shape[1] = h->d.num_mel_bins; shape[2] = 1; shape[3] = 1; }
   return VP_OK;
 }
 

@@ -72,7 +72,76 @@ _GENERATORS = {}      # see main(): generator networks kept between clips of one
 _RENDERERS = {}
 
 
-def render_faces(renderer, center_x, center_y, ratio, bfm_coeff_seq, img_shape, transform_params, on_device=False):
+BFMNET_CKPT = 'ckpt_bfmnet/bfmnet-65000'
+PIX_CKPT = 'ckpt_pixrefer/pixrefernet-20000'
+
+
+def restore_or_init(net, ckpt):
+  """infer_bfmvid.py:217-218: the TensorFlow checkpoint itself (or an .npz archive with the same variable names)."""
+  if os.path.exists(ckpt + '.index'):
+    net.restore(ckpt)
+  elif os.path.exists(ckpt + '.npz'):
+    net.restore(ckpt + '.npz')
+  else:
+    logger.warning('%s not found: running with randomly initialised weights', ckpt)
+    if isinstance(net, BFMNet):
+      net.init_variables()
+
+
+def load_generator(config_path, nb, img_size):
+  """The PixReferNet inference plan for frame batches of nb, restored from PIX_CKPT: (net, inputs, fg_inputs, targets, nodes).
+  A process that runs many clips (infer_clips.py, the streaming CLI) keeps the generator - its plan, its 35 M restored parameters -
+  between calls: building and restoring it is 0.35 s, the frames of an 8 s clip take 0.25 s.  Keyed by what defines it (config, frame
+  batch, image size, the checkpoint file and its modification time)."""
+  pix_file = next((f for f in (PIX_CKPT + '.index', PIX_CKPT + '.npz') if os.path.exists(f)), None)
+  pix_key = (os.path.abspath(config_path), nb, img_size, os.path.abspath(pix_file) if pix_file else None,
+             os.path.getmtime(pix_file) if pix_file else None)
+  cached = _GENERATORS.get(pix_key)
+  if cached is not None:
+    return cached
+  vid2vidnet = PixReferNet(config_path)
+  params = vid2vidnet.params
+  params.batch_size = nb
+  params.add_hparam('is_training', False)
+  vid2vidnet.set_params(params)
+  inputs_holder = placeholder([None, img_size, img_size, 6])
+  fg_inputs_holder = placeholder([None, img_size, img_size, 3])
+  targets_holder = placeholder([None, img_size, img_size, 3])
+  vid2vid_nodes = vid2vidnet.build_inference_op(inputs_holder, fg_inputs_holder, targets_holder)
+  restore_or_init(vid2vidnet, PIX_CKPT)
+  if len(_GENERATORS) >= 4:
+    _GENERATORS.clear()                              # (a handful of shapes at most: do not grow without bound)
+  _GENERATORS[pix_key] = (vid2vidnet, inputs_holder, fg_inputs_holder, targets_holder, vid2vid_nodes)
+  return _GENERATORS[pix_key]
+
+
+def clip_renderer():
+  """ClipRenderer of BFM/BFM_model_front.mat (utils/bfm_load_data.py:9-21): the face model's bases on the device, once per process."""
+  from scipy.io import loadmat
+  from voicepuppet_amd.utils.reconstruct_mesh import ClipRenderer
+
+  class _BFM(object):
+    def __init__(self, model):
+      for k in ('meanshape', 'idBase', 'exBase', 'meantex', 'texBase', 'point_buf', 'tri'):
+        setattr(self, k, model[k])
+      self.keypoints = np.squeeze(model['keypoints']).astype(np.int32) - 1
+  mat = os.path.join('BFM', 'BFM_model_front.mat')
+  rkey = (os.path.abspath(mat), os.path.getmtime(mat))
+  if rkey not in _RENDERERS:
+    _RENDERERS.clear()
+    _RENDERERS[rkey] = ClipRenderer(_BFM(loadmat(mat)))
+  return _RENDERERS[rkey]
+
+
+def background_target(i, img_size):
+  """infer_bfmvid.py:236-238: background/<i % 100 + 1>.jpg of global frame i as an RGB float image, or None when it is absent."""
+  bg = 'background/{}.jpg'.format(i % 100 + 1)
+  if not os.path.exists(bg):
+    return None
+  return np.ascontiguousarray(ImageLoader(resize=(img_size, img_size)).get_data(bg)[:, :, ::-1], dtype=np.float32)
+
+
+def render_faces(renderer, center_x, center_y, ratio, bfm_coeff_seq, img_shape, transform_params, on_device=False, angles=None):
   """render_face (infer_bfmvid.py:79-122) for every frame of the clip: one device pass for reconstruction + rasterisation, then the
   reference's channel swap / cv2.resize / paste for all frames in one more launch (csrc/resize.hip: OpenCV's fixed-point bilinear,
   byte for byte; voicepuppet_amd/utils/cv_resize.py)."""
@@ -81,7 +150,9 @@ def render_faces(renderer, center_x, center_y, ratio, bfm_coeff_seq, img_shape, 
   tx = -int((transform_params[3] / ratio))
   ty = -int((transform_params[4] / ratio))
   T = bfm_coeff_seq.shape[0]
-  images, _ = renderer(bfm_coeff_seq.astype(np.float32), angle_sequence(T))      # [T, 224, 224, 3] uint8 on the device, rasteriser order
+  if angles is None:
+    angles = angle_sequence(T)                       # (a stream passes the head-sway angles of its frames' global indices)
+  images, _ = renderer(bfm_coeff_seq.astype(np.float32), angles)      # [T, 224, 224, 3] uint8 on the device, rasteriser order
   side = int(round(images.shape[1] / ratio))
   cx, cy = side // 2, side // 2
   out = resize_paste_u8(images, side, side, (img_shape[0], img_shape[1]), center_y - cy - ty, center_x - cx - tx, swap_rb=True)   # :110-121
@@ -142,67 +213,18 @@ def main(argv=None):
     bfmnet.set_params(params)
     bfmnet_nodes = bfmnet.build_inference_op(ear, mfcc, seq_len)
 
-    ### Vid2VidNet setting
-    # A process that runs many clips (infer_clips.py) keeps the generator - its plan, its 35 M restored parameters - between calls:
-    # building and restoring it is 0.35 s, the frames of an 8 s clip take 0.25 s.  Keyed by what defines it (config, frame batch, image
-    # size, the checkpoint file and its modification time)
+    ### Vid2VidNet setting (load_generator: kept between clips of one process)
     nb = max(1, min(opts.frame_batch, pad_len))
-    pix_ckpt = 'ckpt_pixrefer/pixrefernet-20000'
-    pix_file = next((f for f in (pix_ckpt + '.index', pix_ckpt + '.npz') if os.path.exists(f)), None)
-    pix_key = (os.path.abspath(config_path), nb, img_size, os.path.abspath(pix_file) if pix_file else None,
-               os.path.getmtime(pix_file) if pix_file else None)
-    cached = _GENERATORS.get(pix_key)
-    if cached is None:
-      vid2vidnet = PixReferNet(config_path)
-      params = vid2vidnet.params
-      params.batch_size = nb
-      params.add_hparam('is_training', False)
-      vid2vidnet.set_params(params)
-      inputs_holder = placeholder([None, img_size, img_size, 6])
-      fg_inputs_holder = placeholder([None, img_size, img_size, 3])
-      targets_holder = placeholder([None, img_size, img_size, 3])
-      vid2vid_nodes = vid2vidnet.build_inference_op(inputs_holder, fg_inputs_holder, targets_holder)
-    else:
-      vid2vidnet, inputs_holder, fg_inputs_holder, targets_holder, vid2vid_nodes = cached
-
-    # infer_bfmvid.py:217-218: the TensorFlow checkpoints themselves (or .npz archives with the same variable names)
-    for net, ckpt in ((bfmnet, 'ckpt_bfmnet/bfmnet-65000'), (vid2vidnet, pix_ckpt)):
-      if net is vid2vidnet and cached is not None:
-        continue                                     # restored when it was built
-      if os.path.exists(ckpt + '.index'):
-        net.restore(ckpt)
-      elif os.path.exists(ckpt + '.npz'):
-        net.restore(ckpt + '.npz')
-      else:
-        logger.warning('%s not found: running with randomly initialised weights', ckpt)
-        if net is bfmnet:
-          bfmnet.init_variables()
-
-    if cached is None:
-      if len(_GENERATORS) >= 4:
-        _GENERATORS.clear()                          # (a handful of shapes at most: do not grow without bound)
-      _GENERATORS[pix_key] = (vid2vidnet, inputs_holder, fg_inputs_holder, targets_holder, vid2vid_nodes)
+    restore_or_init(bfmnet, BFMNET_CKPT)
+    vid2vidnet, inputs_holder, fg_inputs_holder, targets_holder, vid2vid_nodes = load_generator(config_path, nb, img_size)
 
     ### Run inference
     bfm_coeff_seq = sess.run(bfmnet_nodes['BFMCoeffDecoder'])
     face3d_seq = None
     if opts.bfmcoeff and os.path.exists(os.path.join('BFM', 'BFM_model_front.mat')):
-      from scipy.io import loadmat
-      from voicepuppet_amd.utils.reconstruct_mesh import ClipRenderer
-
-      class _BFM(object):      # utils/bfm_load_data.py:9-21
-        def __init__(self, model):
-          for k in ('meanshape', 'idBase', 'exBase', 'meantex', 'texBase', 'point_buf', 'tri'):
-            setattr(self, k, model[k])
-          self.keypoints = np.squeeze(model['keypoints']).astype(np.int32) - 1
       photo = np.load(opts.bfmcoeff)
       coeff_seq = splice_coeff(photo['bfmcoeff'].reshape(1, 257), bfm_coeff_seq)[0]
-      mat = os.path.join('BFM', 'BFM_model_front.mat')
-      rkey = (os.path.abspath(mat), os.path.getmtime(mat))
-      if rkey not in _RENDERERS:
-        _RENDERERS.clear()
-        _RENDERERS[rkey] = ClipRenderer(_BFM(loadmat(mat)))           # the face model's bases on the device: once per process
-      face3d_seq = render_faces(_RENDERERS[rkey], int(photo['center_x']),
+      face3d_seq = render_faces(clip_renderer(), int(photo['center_x']),
                                 int(photo['center_y']), float(photo['ratio']), coeff_seq, (img_size, img_size, 3),
                                 photo['transform_params'], on_device=True)
     else:
@@ -236,9 +258,9 @@ def main(argv=None):
           # render_face returns a BGR canvas that the caller swaps again (infer_bfmvid.py:233): net effect = rasteriser order
           inputs[:, ..., 3:6] = face3d_seq[idx].flip(-1).to(torch.float32) / 255.0
         for k, i in enumerate(idx):
-          bg = 'background/{}.jpg'.format(i % 100 + 1)
-          if os.path.exists(bg):
-            targets[k] = torch.as_tensor(np.ascontiguousarray(ImageLoader(resize=(img_size, img_size)).get_data(bg)[:, :, ::-1], dtype=np.float32)).to(dev)
+          bg = background_target(i, img_size)
+          if bg is not None:
+            targets[k] = torch.as_tensor(bg).to(dev)
           else:
             targets[k] = 0.5
         # (the reference fetches 'Outputs' and the unused 'Outputs_FG' as float32 and scales on the host, infer_bfmvid.py:240-243; the

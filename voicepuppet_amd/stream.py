@@ -1,0 +1,269 @@
+"""Streaming audio-to-face inference (libvp_hip.so: vp_bfmstream_*).
+
+AudioStream takes PCM in chunks of any size and returns each video frame's 64 BFM coefficients as soon as the frame's receptive field
+has arrived: the frames infer_bfmvid computes offline for the whole clip (same checkpoint, same ears), with the values of the offline
+forward.  The lookahead is the receptive field's right side (right_frames video frames) plus the half frame the log-mel window reaches
+past its hop; nothing is approximated.  push / finish never wait on the device (host data is staged through pinned memory).
+
+PuppetStream puts the rest of infer_bfmvid behind it: splice_coeff -> ClipRenderer (the head-sway state carried across pushes) ->
+PixReferNet -> uint8 frames, conditioned on the same background and reference panels by global frame index.  It waits for each push's
+coefficients (the splice and the sway state are host-side, as in infer_bfmvid).
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import BfmStreamDesc
+from .audio import bfmnet_manifest
+
+SAMPLES_PER_FRAME = 640          # 16 kHz / 25 frames per second (config/params.yml)
+
+
+def _ptr(t):
+  return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
+
+
+def _stream():
+  return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def stream_desc(max_chunk_frames=1, dtype="f32", num_mel_bins=80, sample_rate=16000, lower_hz=80.0, upper_hz=7600.0):
+  return BfmStreamDesc(ctypes.sizeof(BfmStreamDesc), max_chunk_frames, num_mel_bins, {"f32": _lib.VP_F32, "bf16": _lib.VP_BF16}[dtype],
+                       sample_rate, lower_hz, upper_hz)
+
+
+def stream_context(desc):
+  """(left_mel, right_mel, left_frames, right_frames, window_frames), derived by the library from MfccNet's layer table."""
+  v = [ctypes.c_int() for _ in range(5)]
+  _lib.check(_lib.lib().vp_bfmstream_context(ctypes.byref(desc), *[ctypes.byref(x) for x in v]), "vp_bfmstream_context")
+  return tuple(x.value for x in v)
+
+
+def load_bfmnet_params(path):
+  """A BFMNet checkpoint as infer_bfmvid restores it: an .npz keyed by the TF variable names, or a TensorFlow checkpoint prefix."""
+  if path.endswith('.npz'):
+    z = np.load(path)
+    return {k: z[k] for k in z.files}
+  from .utils import tf_checkpoint
+  return tf_checkpoint.read_checkpoint(path)
+
+
+class AudioStream:
+  """One streaming session of BFMNet inference.
+
+  push(pcm) / finish() return [k, 64] f32 device tensors, k = ready(len(pcm)) / ready_finish(); finish zero-pads the clip the way
+  prepare_pcm does (pad_len = 1 + N // 640 frames in all).  ears: [k, 1] per call, or None to draw np.random.rand(k, 1) / 100 (numpy's
+  legacy generator: consecutive draws are the offline single draw of pad_len, so a seeded run gets infer_bfmvid's ears)."""
+
+  def __init__(self, params=None, max_chunk_frames=1, dtype="f32", num_mel_bins=80, sample_rate=16000, lower_hz=80.0, upper_hz=7600.0):
+    if not torch.cuda.is_available():
+      raise RuntimeError("AudioStream needs an MI355X (no CPU fallback)")
+    self.L = _lib.lib()
+    self.desc = stream_desc(max_chunk_frames, dtype, num_mel_bins, sample_rate, lower_hz, upper_hz)
+    d = ctypes.byref(self.desc)
+    ws = self.L.vp_bfmstream_workspace_bytes(d)
+    if ws == 0:
+      raise ValueError("invalid stream descriptor")
+    self.left_mel, self.right_mel, self.left_frames, self.right_frames, self.window_frames = stream_context(self.desc)
+    self.manifest = bfmnet_manifest()
+    self.params = torch.zeros(self.L.vp_bfmnet_param_count(), dtype=torch.float32, device="cuda")
+    self.workspace = torch.zeros(ws, dtype=torch.uint8, device="cuda")
+    h = ctypes.c_void_p()
+    _lib.check(self.L.vp_bfmstream_create(d, _ptr(self.workspace), ws, _ptr(self.params), _stream(), ctypes.byref(h)), "vp_bfmstream_create")
+    self.h = h
+    self.samples = 0
+    if params is not None:
+      self.load_params(load_bfmnet_params(params) if isinstance(params, str) else params)
+
+  @property
+  def lookahead_ms(self):
+    """Audio that must arrive after a frame's own 40 ms before the frame is emitted: its right context in mel rows plus the part of
+    the last mel window past its hop."""
+    return 1000.0 * (self.right_mel * 128 + (512 - 128)) / self.desc.sample_rate
+
+  def load_params(self, params):
+    host = self.params.cpu().numpy()
+    for name, off, shape in self.manifest:
+      if name in params:
+        v = np.asarray(params[name], dtype=np.float32)
+        assert v.shape == shape, (name, v.shape, shape)
+        host[off:off + v.size] = v.reshape(-1)
+    self.params.copy_(torch.from_numpy(host))
+    _lib.check(self.L.vp_bfmstream_params_changed(self.h), "vp_bfmstream_params_changed")
+
+  def ready(self, n_samples):
+    return int(self.L.vp_bfmstream_ready(self.h, int(n_samples)))
+
+  def ready_finish(self):
+    return int(self.L.vp_bfmstream_ready_finish(self.h))
+
+  @staticmethod
+  def _to_device(x):
+    """Host data -> device without a host wait: copied into a pinned block of torch's host allocator (which keeps the block until
+    the asynchronous copy has run), then enqueued on the current stream."""
+    if isinstance(x, np.ndarray):
+      x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
+    if not x.is_cuda:
+      x = x.pin_memory().to("cuda", non_blocking=True)
+    return x.contiguous()
+
+  def _ears(self, k, ears):
+    if ears is None:
+      ears = np.random.rand(k, 1).astype(np.float32) / 100
+    ears = self._to_device(ears)
+    assert ears.dtype == torch.float32 and ears.numel() == k, (tuple(ears.shape), k)
+    return ears
+
+  def push(self, pcm, ears=None):
+    """pcm: 1-D f32 (numpy or tensor) -> coefficients [k, 64] of the frames that became exact.  Enqueues only: the returned
+    tensor is ready when the current stream reaches it."""
+    pcm = self._to_device(pcm)
+    assert pcm.dtype == torch.float32 and pcm.dim() == 1
+    n = pcm.numel()
+    k = self.ready(n)
+    out = torch.empty(k, 64, dtype=torch.float32, device="cuda")
+    e = self._ears(k, ears) if k else None
+    _lib.check(self.L.vp_bfmstream_push(self.h, _ptr(pcm), n, _ptr(e), _ptr(out if k else None), _stream()), "vp_bfmstream_push")
+    self.samples += n
+    return out
+
+  def finish(self, ears=None):
+    k = self.ready_finish()
+    out = torch.empty(k, 64, dtype=torch.float32, device="cuda")
+    e = self._ears(k, ears)
+    _lib.check(self.L.vp_bfmstream_finish(self.h, _ptr(e), _ptr(out), _stream()), "vp_bfmstream_finish")
+    return out
+
+  def reset(self):
+    _lib.check(self.L.vp_bfmstream_reset(self.h, _stream()), "vp_bfmstream_reset")
+    self.samples = 0
+
+  def mel_history(self):
+    """The device mel history: [rows, num_mel_bins]; mel frame r of the clip sits at row r % rows while it is kept."""
+    p = ctypes.c_void_p()
+    shp = (ctypes.c_int64 * 4)()
+    _lib.check(self.L.vp_bfmstream_tensor(self.h, b"mel", ctypes.byref(p), shp), "vp_bfmstream_tensor")
+    rows, nmel = int(shp[0]), int(shp[1])
+    off = p.value - self.workspace.data_ptr()
+    return self.workspace[off:off + 4 * rows * nmel].view(torch.float32).view(rows, nmel)
+
+  def __del__(self):
+    try:
+      if getattr(self, "h", None):
+        self.L.vp_bfmstream_destroy(self.h)
+        self.h = None
+    except Exception:
+      pass
+
+
+class HeadSway:
+  """infer_bfmvid.angle_sequence with its state carried: next(n) returns the angles of the next n frames, so consecutive calls
+  concatenate to angle_sequence(total) (same float32 accumulation, same direction flips)."""
+
+  def __init__(self, start=(0.0, 0.0, 0.0), shift=0.005):
+    self.start, self.shift0 = start, shift
+    self.reset()
+
+  def reset(self):
+    self.angles = np.array([self.start], dtype=np.float32)
+    self.shift = self.shift0
+
+  def next(self, n):
+    angles, shift = self.angles, self.shift
+    out = np.zeros((n, 3), np.float32)
+    for i in range(n):
+      angles[0][0] += shift
+      angles[0][1] += shift
+      angles[0][2] += shift
+      if (angles[0][1] > 0.03 or angles[0][1] < -0.03):
+        shift = -shift
+      out[i] = angles[0]
+    self.shift = shift
+    return out
+
+
+class PuppetStream:
+  """Streaming infer_bfmvid: push(pcm) / finish() -> [(global frame index, uint8 frame [H, W, 3] RGB)] of the frames that became
+  exact.  image: the 512 x 1536 input (RGB float in [0,1], as infer_bfmvid reads it); bfmcoeff: the photo's coefficient npz
+  (bfmcoeff, transform_params, center_x, center_y, ratio) - with it and BFM/BFM_model_front.mat every frame is conditioned on its
+  rendered face, without them on the reference 3-D face panel.  BFMNet / PixReferNet weights: the checkpoints infer_bfmvid restores
+  (ckpt_bfmnet/bfmnet-65000, ckpt_pixrefer/pixrefernet-20000; TF prefix or .npz), the generator from infer_bfmvid's cache."""
+
+  def __init__(self, config_path, image, bfmcoeff=None, frame_batch=8, max_chunk_frames=1, dtype="f32", img_size=512):
+    import os
+    from .pixrefer import infer_bfmvid as ib
+    from .runtime import Session
+    self.ib = ib
+    bfm_file = next((f for f in (ib.BFMNET_CKPT + '.index', ib.BFMNET_CKPT + '.npz') if os.path.exists(f)), None)
+    if bfm_file is None:
+      from .bfmnet.bfmnet import random_variables
+      ib.logger.warning('%s not found: running with randomly initialised weights', ib.BFMNET_CKPT)
+      bfm_params = random_variables()
+    else:
+      bfm_params = load_bfmnet_params(bfm_file[:-len('.index')] if bfm_file.endswith('.index') else bfm_file)
+    self.audio = AudioStream(bfm_params, max_chunk_frames=max_chunk_frames, dtype=dtype)
+    self.nb, self.img_size = frame_batch, img_size
+    self.net, self.inputs_holder, self.fg_holder, self.targets_holder, self.nodes = ib.load_generator(config_path, frame_batch, img_size)
+    self.sess = Session()
+    self.photo = None
+    if bfmcoeff and os.path.exists(os.path.join('BFM', 'BFM_model_front.mat')):
+      self.photo = np.load(bfmcoeff)
+      self.renderer = ib.clip_renderer()
+    else:
+      ib.logger.warning('BFM assets unavailable: conditioning every frame on the reference 3-D face panel')
+    face3d_refer = image[:, 512:512 * 2, :]
+    fg_refer = image[:, :512, :] * image[:, 512 * 2:, :]
+    nb, H = frame_batch, img_size
+    self.inputs = torch.zeros([nb, H, H, 6], dtype=torch.float32, device="cuda")
+    self.fg_inputs = torch.zeros([nb, H, H, 3], dtype=torch.float32, device="cuda")
+    self.targets = torch.full([nb, H, H, 3], 0.5, dtype=torch.float32, device="cuda")
+    refer_t = torch.as_tensor(np.ascontiguousarray(face3d_refer, dtype=np.float32)).to("cuda")
+    self.inputs[:, ..., 0:3] = refer_t
+    self.fg_inputs[:, ..., 0:3] = torch.as_tensor(np.ascontiguousarray(fg_refer, dtype=np.float32)).to("cuda")
+    if self.photo is None:
+      self.inputs[:, ..., 3:6] = refer_t
+    self.sway = HeadSway()
+    self.frame = 0
+
+  def reset(self):
+    self.audio.reset()
+    self.sway.reset()
+    self.frame = 0
+
+  def push(self, pcm):
+    return self._frames(self.audio.push(pcm))
+
+  def finish(self):
+    return self._frames(self.audio.finish())
+
+  def _frames(self, coeff):
+    ib, H = self.ib, self.img_size
+    k = int(coeff.shape[0])
+    if k == 0:
+      return []
+    g0 = self.frame
+    self.frame += k
+    angles = self.sway.next(k)
+    face3d = None
+    if self.photo is not None:
+      p = self.photo
+      coeff_seq = ib.splice_coeff(p['bfmcoeff'].reshape(1, 257), coeff.cpu().numpy()[np.newaxis])[0]
+      face3d = ib.render_faces(self.renderer, int(p['center_x']), int(p['center_y']), float(p['ratio']), coeff_seq, (H, H, 3),
+                               p['transform_params'], on_device=True, angles=angles)
+    out = []
+    for i0 in range(0, k, self.nb):                    # batches of the generator plan, padded with the last frame as infer_bfmvid pads
+      idx = [min(i0 + j, k - 1) for j in range(self.nb)]
+      if face3d is not None:
+        self.inputs[:, ..., 3:6] = face3d[idx].flip(-1).to(torch.float32) / 255.0
+      for j, i in enumerate(idx):
+        bg = ib.background_target(g0 + i, H)
+        if bg is not None:
+          self.targets[j] = torch.as_tensor(bg).to("cuda")
+        else:
+          self.targets[j] = 0.5
+      frames = self.sess.run([self.nodes['Outputs_u8']],
+                             feed_dict={self.inputs_holder: self.inputs, self.fg_holder: self.fg_inputs, self.targets_holder: self.targets})[0]
+      out.extend((g0 + i0 + j, frames[j]) for j in range(self.nb) if i0 + j < k)
+    return out
