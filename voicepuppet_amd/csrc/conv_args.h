@@ -22,6 +22,29 @@ struct PixSrc {
   int group_n;              // samples per BN group
 };
 
+// The kernel of a convolution launch (IgemmArgs::kern).  The first five are the plan families (how the plan stages its operands and
+// packs its weights: conv_staging); the others run plans of one of those families.
+enum ConvKernel {
+  CK_IGEMM = 0,   // generic implicit GEMM (IgemmPlan::cfg picks the tile)
+  CK_PATCH,       // patch kernel, generic schedule (conv_patch.hip)
+  CK_PATCH2,      // 2x2-tap parity classes (conv_patch2.hip)
+  CK_SMALLP,      // few-pixel kernel (conv_smallp.hip)
+  CK_S2C64,       // 64 -> 128 channel 4x4 / stride-2 (conv_s2c64.hip)
+  CK_CIN8,        // 8-channel image inputs (conv_cin8_kernel)          - igemm plans
+  CK_COUT8,       // 3x3, 64 -> <= 8 channels (conv3x3_cout8_tile_kernel)
+  CK_DCOUT8,      // 4x4 / stride-2 transposed, 64 -> <= 8 channels (deconv_cout8_tile_kernel)
+  CK_COUT4,       // 4-channel float32 transposed conv (deconv_cout4_kernel)
+  CK_C64,         // 3x3, 64 / 128 -> 64 / 128 channels (conv_c64.hip)  - patch plans
+  CK_PATCH3,      // unrolled 3x3 patch schedule (conv_patch3.hip)
+  CK_PATCH4,      // unrolled 4x4 patch schedule (conv_patch3.hip, KW = 4)
+  CK_DC256,       // 2 x 128 -> 64 channel transposed conv (conv_dc64.hip) - patch2 plans
+  CK_DC64,        // 128 -> 64 channel transposed conv (conv_dc64.hip)
+};
+// plan family of a kernel: 0 igemm, 1 patch, 2 patch2, 3 smallp, 4 s2c64
+inline int conv_staging(int k) {
+  return k <= CK_S2C64 ? k : (k <= CK_COUT4 ? CK_IGEMM : (k <= CK_PATCH4 ? CK_PATCH : CK_PATCH2));
+}
+
 // Y[pixel, co] = epilogue( sum_{tap, ci} X~[pixel (+) tap, ci] * Wp[co][tap*Cin + ci] )
 // Covers conv fwd, conv bwd-data, transposed-conv fwd (4 output-parity classes) and its bwd-data.
 struct IgemmArgs {
@@ -77,9 +100,10 @@ struct IgemmArgs {
   double* bn_part2;
   double* colsum_part;      // conv_dc64_kernel only: also write the column sums of the stored output, one row [2][64] per block (null: no)
   const void* zeros;        // >= 16 bytes of zeros (padding source of the LDS-DMA loader); null: register loader
-  // patch kernel (conv_patch.hip; plan-time decision, the packed weights carry PackDesc::kswap): stride-1 taps on a regular grid,
+  // kern: the kernel every launch of this plan runs (ConvKernel, chosen when the plan is made: conv_ops.h plan_kernel; host only).
+  // patch kernels (conv_patch.hip; the packed weights carry PackDesc::kswap): stride-1 taps on a regular grid,
   // tap t = r * p_kw + c  ->  (dh, dw) = (p_dhf + r * p_dhs, p_dwf + c * p_dws)
-  int patch, p_kw, p_dhf, p_dhs, p_dwf, p_dws;
+  int kern, p_kw, p_dhf, p_dhs, p_dwf, p_dws;
   // first layers without batch-norm (encoder_1, encoder_fg_1, discriminator layer_1; conv_cin8_kernel only - conv_cin8_eligible): the
   // epilogue also writes the activations the consumers read - what act_apply would materialise from Y in a pass of its own (Y itself
   // is stored only when the caller passes Y != null: the rounding-aware oracle tests teacher-force on it, a step does not read it)
@@ -87,7 +111,7 @@ struct IgemmArgs {
   void* xa_relu;
   void* pool_out;           // patch kernel, 16 x 16-pixel tiles: also write the 2x2 max-pooled output [N][Hg/2][Wg/2][ldY] (null: no)
   int pool_only;            // with pool_out: write ONLY the pooled output (nobody reads the full-resolution tensor: the real half of the VGG trunk)
-  // few-pixel kernel (conv_smallp.hip; patch == 3, plan-time decision: packed rows unpermuted): 32 channels x sp_npt * 16 pixels per tile,
+  // few-pixel kernel (conv_smallp.hip; kern == CK_SMALLP, plan-time decision: packed rows unpermuted): 32 channels x sp_npt * 16 pixels per tile,
   // splitk = K splits over blocks, partial = their slabs [split][tile][pixels][32]
   unsigned* sp_cnt;         // [tiles + channel tiles] arrival counters: zero before the launch, left zero by it
   unsigned short sp_mask[4];   // per class: taps inside the image for at least one pixel

@@ -300,7 +300,7 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_c64_kernel(const IgemmArgs a,
 // of 128 channels to 64 / 128, plain store (no batch statistics, no accumulation, no affine on the reference), relu / no activation,
 // optional fused 2x2 max pool of relu outputs, optional relu'(reference) product, image sides multiples of the 4 x 16 tile
 bool conv_c64_eligible(const IgemmArgs& a, int is_bf16) {
-  if (!is_bf16 || a.patch != 1 || !patch3_eligible(a, 1)) return false;
+  if (!is_bf16 || conv_staging(a.kern) != CK_PATCH || !patch3_eligible(a, 1)) return false;
   if ((a.Cin != 64 && a.Cin != 128) || a.x.C[0] != a.Cin || (a.Cout != 64 && a.Cout != 128)) return false;
   if (a.CoutPad != a.Cout || a.ldY != a.Cout || !a.rowperm || a.splitk != 1) return false;
   if (a.Hg % TH || a.Wg % TW || a.Hin != a.Hg || a.Win != a.Wg || a.Hof != a.Hg || a.Wof != a.Wg) return false;

@@ -444,7 +444,7 @@ __global__ __launch_bounds__(512, 1) void conv_dc256_kernel(const IgemmArgs a, c
 
 // a patch2-plan transposed convolution from TWO 128-channel tensors to 64 channels, raw bf16 output, optional batch statistics of ONE group
 bool conv_dc256_eligible(const IgemmArgs& a, int is_bf16) {
-  if (!dc64_knob() || !is_bf16 || a.patch != 2 || a.nclass != 4 || a.ntaps != 4 || a.os != 2) return false;
+  if (!is_bf16 || conv_staging(a.kern) != CK_PATCH2 || a.nclass != 4 || a.ntaps != 4 || a.os != 2) return false;
   if (a.Cout != 64 || a.CoutPad != 64 || a.ldY != 64 || a.Cin != 256 || !a.rowperm || a.splitk != 1) return false;
   if (!((a.x.C[0] == 128 && a.x.C[1] == 128) || (a.x.C[0] == 256 && a.x.C[1] == 0))) return false;
   if (a.Hg % TH || a.Wg % TW || a.Hin != a.Hg || a.Win != a.Wg || a.Hof != 2 * a.Hg || a.Wof != 2 * a.Wg) return false;
@@ -482,7 +482,7 @@ hipError_t launch_conv_dc256(const IgemmArgs& a, hipStream_t st) {
 
 // a patch2-plan transposed convolution (conv_ops.h plan_make_patch2) from one 128-channel tensor to 64 channels, plain stores
 bool conv_dc64_eligible(const IgemmArgs& a, int is_bf16) {
-  if (!is_bf16 || a.patch != 2 || a.nclass != 4 || a.ntaps != 4 || a.os != 2) return false;
+  if (!is_bf16 || conv_staging(a.kern) != CK_PATCH2 || a.nclass != 4 || a.ntaps != 4 || a.os != 2) return false;
   if (a.Cout != 64 || a.CoutPad != 64 || a.ldY != 64 || a.Cin != 128 || a.x.C[0] != 128 || a.x.C[1] != 0 || !a.rowperm || a.splitk != 1) return false;
   if (a.Hg % TH || a.Wg % TW || a.Hin != a.Hg || a.Win != a.Wg || a.Hof != 2 * a.Hg || a.Wof != 2 * a.Wg) return false;
   if (a.bias || a.out_act != ACT_NONE || a.bn_part || a.y_f32 || a.ref_a || a.split_c || a.pool_out) return false;

@@ -27,6 +27,7 @@
 
 #include "conv_args.h"
 #include "conv_ops.h"
+#include "errors.h"
 #include "igemm_device.h"
 #include "smallp_args.h"
 #include "launch.h"
@@ -1807,18 +1808,78 @@ static hipError_t launch_igemm_cfg(const IgemmArgs& a, hipStream_t st) {
 }
 
 
-// 8-channel (padded image) inputs, 64 outputs: what conv_cin8_kernel handles (`zeros` is not looked at: the step executor asks before it
-// has filled the run-time pointers in)
+// 8-channel (padded image) inputs, 64 outputs: what conv_cin8_kernel handles
 bool conv_cin8_eligible(const IgemmArgs& a, int is_bf16) {
   const bool pow2 = (a.Wg & (a.Wg - 1)) == 0 && (a.Hg & (a.Hg - 1)) == 0;
-  return is_bf16 && a.Cin == 8 && a.x.C[0] == 8 && a.x.C[1] == 0 && a.Cout == 64 && a.ldY == 64 && a.nclass == 1 && a.splitk == 1 && a.os == 1 &&
+  return is_bf16 && a.zeros && a.Cin == 8 && a.x.C[0] == 8 && a.x.C[1] == 0 && a.Cout == 64 && a.ldY == 64 && a.nclass == 1 && a.splitk == 1 && a.os == 1 &&
          a.Hof == a.Hg && a.Wof == a.Wg && pow2 && !a.ref && !a.accumulate && !a.y_f32 && !a.bn_part && !a.x.aff_a[0] && a.x.act == ACT_NONE &&
          a.ntaps <= 16 && (a.Kpad == 96 || a.Kpad == 128) && (size_t)a.N * a.Hin * a.Win * 16 < 0x70000000ull &&
          (((long long)a.N * a.Hg * a.Wg) & 15) == 0 && (a.out_act == ACT_NONE || a.out_act == ACT_RELU) &&
          (a.Kpad == 128 || !(a.xa_lrelu || a.xa_relu)) && !(a.xa_relu && !a.xa_lrelu);      // (the instantiated output combinations: conv_cin8_kernel)
 }
 
+// 3x3 stride-1 conv from 64 to <= 8 channels with the kernel's plain epilogue: what conv3x3_cout8_tile_kernel handles
+bool conv_cout8_eligible(const IgemmArgs& a, int is_bf16) {
+  bool near = a.ntaps == 9;
+  for (int t = 0; near && t < 9; ++t) near = a.taps[0].dh[t] >= -1 && a.taps[0].dh[t] <= 1 && a.taps[0].dw[t] >= -1 && a.taps[0].dw[t] <= 1;
+  return is_bf16 && near && a.zeros && a.nclass == 1 && a.sh == 1 && a.sw == 1 && a.os == 1 && a.Cin == 64 && a.x.C[0] == 64 && a.x.C[1] == 0 &&
+         a.CoutPad == 16 && a.Cout <= 8 && a.ldY == 8 && a.splitk == 1 && !a.rowperm && !a.bn_part && !a.x.aff_a[0] && a.x.act == ACT_NONE &&
+         (a.Wg & (a.Wg - 1)) == 0 && (a.Hg & (a.Hg - 1)) == 0 && a.Wg >= 16 && a.Hg >= 4 && a.Hof == a.Hg && a.Wof == a.Wg && a.Hin == a.Hg &&
+         a.Win == a.Wg && !a.y_f32 && (size_t)a.N * a.Hin * a.Win * 64 * 2 < 0x70000000ull &&
+         !a.bias && a.out_act == ACT_NONE && !a.ref && !a.accumulate && !a.split_c;
+}
+
+// 4x4 stride-2 transposed conv from 64 to <= 8 channels with the kernel's plain epilogue: what deconv_cout8_tile_kernel handles
+bool conv_dcout8_eligible(const IgemmArgs& a, int is_bf16) {
+  return is_bf16 && a.zeros && a.nclass == 4 && a.os == 2 && a.ntaps == 4 && a.Cin == 64 && a.x.C[0] == 64 && a.x.C[1] == 0 && a.CoutPad == 16 &&
+         a.Cout <= 8 && a.ldY == 8 && !a.y_f32 && a.splitk == 1 && !a.rowperm && !a.bn_part && !a.x.aff_a[0] && a.x.act == ACT_NONE &&
+         (a.Wg & (a.Wg - 1)) == 0 && (a.Hg & (a.Hg - 1)) == 0 && a.Wg >= 16 && a.Hg >= 4 && a.Hof == 2 * a.Hg && a.Wof == 2 * a.Wg && a.Hin == a.Hg &&
+         a.Win == a.Wg && (size_t)a.N * a.Hin * a.Win * 64 * 2 < 0x70000000ull && (size_t)a.N * a.Hof * a.Wof * 8 * 2 < 0x70000000ull &&
+         !a.bias && a.out_act == ACT_NONE && !a.ref && !a.accumulate && !a.split_c;
+}
+
+// 4-channel float32 transposed conv (decoder_1): what deconv_cout4_kernel handles
+bool conv_cout4_eligible(const IgemmArgs& a, int is_bf16) {
+  const bool pow2 = (a.Wg & (a.Wg - 1)) == 0 && (a.Hg & (a.Hg - 1)) == 0;
+  const int spt = a.Cin / 32;
+  return is_bf16 && a.zeros && a.nclass == 4 && a.os == 2 && a.ntaps == 4 && a.Cout == 4 && a.y_f32 && a.ldY == 4 && a.splitk == 1 && pow2 &&
+         a.Cin % 32 == 0 && (spt == 2 || spt == 4) && a.x.C[0] % 32 == 0 && a.x.C[0] + a.x.C[1] == a.Cin && !a.ref && !a.accumulate &&
+         a.out_act == ACT_NONE && !a.x.aff_a[0] && !a.x.aff_a[1] && a.x.act == ACT_NONE && a.Hof == 2 * a.Hg && a.Wof == 2 * a.Wg &&
+         (size_t)a.N * a.Hin * a.Win * a.Cin * 2 < 0x70000000ull && (size_t)a.N * a.Hof * a.Wof * 16 < 0x70000000ull;
+}
+
+bool conv_kernel_ok(const IgemmArgs& a, int is_bf16) {
+  switch (a.kern) {
+    case CK_IGEMM: case CK_PATCH: case CK_PATCH2: case CK_SMALLP: return true;
+    case CK_S2C64: return conv_s2c64_eligible(a, is_bf16);
+    case CK_CIN8: return conv_cin8_eligible(a, is_bf16);
+    case CK_COUT8: return conv_cout8_eligible(a, is_bf16);
+    case CK_DCOUT8: return conv_dcout8_eligible(a, is_bf16);
+    case CK_COUT4: return conv_cout4_eligible(a, is_bf16);
+    case CK_C64: return conv_c64_eligible(a, is_bf16);
+    case CK_PATCH3: return patch3_eligible(a, is_bf16);
+    case CK_PATCH4: return patch4_eligible(a, is_bf16);
+    case CK_DC256: return conv_dc256_eligible(a, is_bf16);
+    case CK_DC64: return conv_dc64_eligible(a, is_bf16);
+    default: return false;
+  }
+}
+
+const char* conv_kernel_name(int kern) {
+  static const char* const names[] = {"igemm", "patch", "patch2", "smallp", "s2c64", "cin8", "cout8", "dcout8", "cout4", "c64", "patch3", "patch4",
+                                      "dc256", "dc64"};
+  return kern >= 0 && kern <= CK_DC64 ? names[kern] : "?";
+}
+
+// Runs the kernel the plan chose (IgemmArgs::kern, conv_ops.h plan_kernel).  A plan for one kernel runs on no other: arguments outside
+// that kernel's preconditions fail loudly.
 template <typename T> static hipError_t launch_igemm_t(const IgemmArgs& a, int cfg, hipStream_t st) {
+  constexpr bool bf = sizeof(T) == 2;
+  if (!conv_kernel_ok(a, bf)) {
+    set_err("launch_igemm: the arguments are outside the preconditions of the plan's kernel %s (%s, %d x %d x %d -> %d channels)",
+            conv_kernel_name(a.kern), bf ? "bf16" : "f32", a.N, a.Hg, a.Wg, a.Cout);
+    return hipErrorInvalidValue;
+  }
   hipError_t e;
   int pbc, pbp;
   igemm_tile(cfg, &pbc, &pbp);
@@ -1826,11 +1887,26 @@ template <typename T> static hipError_t launch_igemm_t(const IgemmArgs& a, int c
   const double Pn = (double)a.N * a.Hg * a.Wg * a.nclass;
   const double kreal = (double)a.ntaps * a.cin_real;
   const double es = sizeof(T);
-  if constexpr (sizeof(T) == 2) {
-    // 8-channel (padded image) inputs, 64 outputs: the direct register-resident form (conv_cin8_kernel)
-    if (a.zeros && conv_cin8_eligible(a, 1)) {
-      ProfScope prof("cin8", true, 64, 16, 2.0 * Pn * a.Cout * kreal,
-                     es * ((double)a.N * a.Hin * a.Win * a.cin_real + kreal * a.Cout + Pn * a.Cout), st);
+  const double flops = 2.0 * Pn * a.Cout * kreal;
+  const double bytes = es * ((double)a.N * a.Hin * a.Win * a.cin_real + kreal * a.nclass * a.Cout + Pn * a.Cout);
+  switch (a.kern) {
+    case CK_IGEMM: break;
+    case CK_PATCH: case CK_PATCH2: case CK_PATCH3: {   // stride-1 convs with the input patch staged once per channel chunk
+      // class name per kernel template: patch2 (parity classes, conv_patch2.hip), patch3 (unrolled 3x3, conv_patch3.hip), patch (generic, conv_patch.hip)
+      ProfScope prof(conv_kernel_name(a.kern), bf, pbc, pbp, flops, bytes, st);
+      if (a.kern == CK_PATCH2) return launch_igemm_patch2(a, bf, pbc, pbp, st);
+      if (a.kern == CK_PATCH3) return launch_igemm_patch3(a, bf, pbc, pbp, st);
+      return launch_igemm_patch(a, bf, pbc, pbp, st);
+    }
+    case CK_SMALLP: {   // few-pixel layers: conv_smallp.hip (plain epilogue; the fused batch-norm forms are launched by the step executor)
+      ProfScope prof("smallp", bf, pbc, pbp, flops, bytes, st);
+      return launch_igemm_smallp(a, bf, st);
+    }
+    default: break;
+  }
+  if constexpr (bf) switch (a.kern) {
+    case CK_CIN8: {    // 8-channel (padded image) inputs, 64 outputs: the direct register-resident form (conv_cin8_kernel)
+      ProfScope prof("cin8", true, 64, 16, flops, es * ((double)a.N * a.Hin * a.Win * a.cin_real + kreal * a.Cout + Pn * a.Cout), st);
       const int ntile = (int)((Pn + 15) / 16);
       int blocks = (ntile + 3) / 4;
       if (blocks > thin_blocks_knob(3)) blocks = thin_blocks_knob(3);
@@ -1853,18 +1929,8 @@ template <typename T> static hipError_t launch_igemm_t(const IgemmArgs& a, int c
       hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, st, a, lgW, lgH);
       return hipGetLastError();
     }
-  }
-  if constexpr (sizeof(T) == 2) {
-    // 3x3 stride-1 conv from 64 to <= 8 channels (conv1_1 backward-data): halo tile staged once (conv3x3_cout8_tile_kernel)
-    bool near = a.ntaps == 9;
-    for (int t = 0; near && t < 9; ++t) near = a.taps[0].dh[t] >= -1 && a.taps[0].dh[t] <= 1 && a.taps[0].dw[t] >= -1 && a.taps[0].dw[t] <= 1;
-    if (near && a.zeros && a.nclass == 1 && a.sh == 1 && a.sw == 1 && a.os == 1 && a.Cin == 64 && a.x.C[0] == 64 && a.x.C[1] == 0 &&
-        a.CoutPad == 16 && a.Cout <= 8 && a.ldY == 8 && a.splitk == 1 && !a.rowperm && !a.bn_part && !a.x.aff_a[0] && a.x.act == ACT_NONE &&
-        (a.Wg & (a.Wg - 1)) == 0 && (a.Hg & (a.Hg - 1)) == 0 && a.Wg >= 16 && a.Hg >= 4 && a.Hof == a.Hg && a.Wof == a.Wg && a.Hin == a.Hg &&
-        a.Win == a.Wg && !a.y_f32 && (size_t)a.N * a.Hin * a.Win * 64 * 2 < 0x70000000ull &&
-        !a.bias && a.out_act == ACT_NONE && !a.ref && !a.accumulate && !a.split_c) {          // (the kernel's plain epilogue)
-      ProfScope prof("cout8", true, 16, 64, 2.0 * Pn * a.Cout * kreal,
-                     es * ((double)a.N * a.Hin * a.Win * a.cin_real + kreal * a.Cout + Pn * a.Cout), st);
+    case CK_COUT8: {   // 3x3 stride-1 conv from 64 to <= 8 channels (conv1_1 backward-data): halo tile staged once (conv3x3_cout8_tile_kernel)
+      ProfScope prof("cout8", true, 16, 64, flops, es * ((double)a.N * a.Hin * a.Win * a.cin_real + kreal * a.Cout + Pn * a.Cout), st);
       int lgW = 0, lgH = 0;
       while ((1 << lgW) < a.Wg) ++lgW;
       while ((1 << lgH) < a.Hg) ++lgH;
@@ -1873,16 +1939,8 @@ template <typename T> static hipError_t launch_igemm_t(const IgemmArgs& a, int c
       hipLaunchKernelGGL(conv3x3_cout8_tile_kernel, dim3(tblocks), dim3(256), (size_t)6 * 18 * 144 + 256 * 16, st, a, lgW, lgH);
       return hipGetLastError();
     }
-  }
-  if constexpr (sizeof(T) == 2) {
-    // 4x4 stride-2 transposed conv from 64 to <= 8 channels (layer_1 backward-data): deconv_cout8_tile_kernel
-    if (a.zeros && a.nclass == 4 && a.os == 2 && a.ntaps == 4 && a.Cin == 64 && a.x.C[0] == 64 && a.x.C[1] == 0 && a.CoutPad == 16 && a.Cout <= 8 &&
-        a.ldY == 8 && !a.y_f32 && a.splitk == 1 && !a.rowperm && !a.bn_part && !a.x.aff_a[0] && a.x.act == ACT_NONE && (a.Wg & (a.Wg - 1)) == 0 &&
-        (a.Hg & (a.Hg - 1)) == 0 && a.Wg >= 16 && a.Hg >= 4 && a.Hof == 2 * a.Hg && a.Wof == 2 * a.Wg && a.Hin == a.Hg && a.Win == a.Wg &&
-        (size_t)a.N * a.Hin * a.Win * 64 * 2 < 0x70000000ull && (size_t)a.N * a.Hof * a.Wof * 8 * 2 < 0x70000000ull &&
-        !a.bias && a.out_act == ACT_NONE && !a.ref && !a.accumulate && !a.split_c) {          // (the kernel's plain epilogue)
-      ProfScope prof("dcout8", true, 32, 64, 2.0 * Pn * a.Cout * kreal,
-                     es * ((double)a.N * a.Hin * a.Win * a.cin_real + kreal * a.nclass * a.Cout + Pn * a.Cout), st);
+    case CK_DCOUT8: {  // 4x4 stride-2 transposed conv from 64 to <= 8 channels (layer_1 backward-data): deconv_cout8_tile_kernel
+      ProfScope prof("dcout8", true, 32, 64, flops, bytes, st);
       int lgW = 0, lgH = 0;
       while ((1 << lgW) < a.Wg) ++lgW;
       while ((1 << lgH) < a.Hg) ++lgH;
@@ -1893,17 +1951,9 @@ template <typename T> static hipError_t launch_igemm_t(const IgemmArgs& a, int c
       hipLaunchKernelGGL(deconv_cout8_tile_kernel<2>, dim3(tblocks), dim3(256), smt, st, a, lgW, lgH);
       return hipGetLastError();
     }
-  }
-  if constexpr (sizeof(T) == 2) {
-    // 4-channel f32 transposed conv (decoder_1): the four parity classes x four channels as one MFMA tile (deconv_cout4_kernel)
-    const bool pow2 = (a.Wg & (a.Wg - 1)) == 0 && (a.Hg & (a.Hg - 1)) == 0;
-    const int spt = a.Cin / 32;
-    if (a.zeros && a.nclass == 4 && a.os == 2 && a.ntaps == 4 && a.Cout == 4 && a.y_f32 && a.ldY == 4 && a.splitk == 1 && pow2 &&
-        a.Cin % 32 == 0 && (spt == 2 || spt == 4) && a.x.C[0] % 32 == 0 && a.x.C[0] + a.x.C[1] == a.Cin && !a.ref && !a.accumulate &&
-        a.out_act == ACT_NONE && !a.x.aff_a[0] && !a.x.aff_a[1] && a.x.act == ACT_NONE && a.Hof == 2 * a.Hg && a.Wof == 2 * a.Wg &&
-        (size_t)a.N * a.Hin * a.Win * a.Cin * 2 < 0x70000000ull && (size_t)a.N * a.Hof * a.Wof * 16 < 0x70000000ull) {
-      ProfScope prof("cout4", true, 16, 16, 2.0 * Pn * a.Cout * kreal,
-                     es * ((double)a.N * a.Hin * a.Win * a.cin_real + kreal * a.nclass * a.Cout) + 4.0 * Pn * a.Cout, st);
+    case CK_COUT4: {   // 4-channel f32 transposed conv (decoder_1): the four parity classes x four channels as one MFMA tile (deconv_cout4_kernel)
+      ProfScope prof("cout4", true, 16, 16, flops, es * ((double)a.N * a.Hin * a.Win * a.cin_real + kreal * a.nclass * a.Cout) + 4.0 * Pn * a.Cout, st);
+      const int spt = a.Cin / 32;
       const int ntile = (a.N * a.Hg * a.Wg + 15) / 16;
       int blocks = (ntile + 3) / 4;
       if (blocks > 2048) blocks = 2048;
@@ -1926,65 +1976,30 @@ template <typename T> static hipError_t launch_igemm_t(const IgemmArgs& a, int c
       else hipLaunchKernelGGL((deconv_cout4_kernel<4>), dim3(blocks), dim3(256), sm, st, a, lgW, lgH);
       return hipGetLastError();
     }
-  }
-  if (a.patch == 3) {   // few-pixel layers: conv_smallp.hip (plain epilogue; the fused batch-norm forms are launched by the step executor)
-    ProfScope prof("smallp", sizeof(T) == 2, pbc, pbp, 2.0 * Pn * a.Cout * kreal,
-                   es * ((double)a.N * a.Hin * a.Win * a.cin_real + kreal * a.nclass * a.Cout + Pn * a.Cout), st);
-    return launch_igemm_smallp(a, sizeof(T) == 2, st);
-  }
-  if constexpr (sizeof(T) == 2) {
-    // 3x3 stride-1 conv from 64 to 64 / 128 channels (VGG conv1_2 forward / backward-data, conv2_1 forward): weights resident in
-    // registers, 4 x 16-pixel tiles (conv_c64.hip)
-    if (c64_knob() && conv_c64_eligible(a, 1)) {
-      ProfScope prof("c64", true, a.Cout, 64, 2.0 * Pn * a.Cout * kreal,
-                     es * ((double)a.N * a.Hin * a.Win * a.cin_real + kreal * a.nclass * a.Cout + Pn * a.Cout), st);
+    case CK_C64: {     // 3x3 stride-1 conv from 64 to 64 / 128 channels (VGG conv1_2 forward / backward-data, conv2_1 forward): weights resident
+      ProfScope prof("c64", true, a.Cout, 64, flops, bytes, st);       // in registers, 4 x 16-pixel tiles (conv_c64.hip)
       return launch_conv_c64(a, st);
     }
-  }
-  if constexpr (sizeof(T) == 2) {
-    // 4x4 stride-2 transposed conv from 128 to 64 channels (backward-data of layer_2 / encoder_2 / encoder_fg_2): weights resident in
-    // registers, two parity classes per block (conv_dc64.hip)
-    if (conv_dc256_eligible(a, 1)) {
-      ProfScope prof("dc256", true, 64, 128, 2.0 * Pn * a.Cout * kreal,
-                     es * ((double)a.N * a.Hin * a.Win * a.cin_real + kreal * a.nclass * a.Cout + Pn * a.Cout), st);
+    case CK_DC256: {   // 4x4 stride-2 transposed conv from 2 x 128 to 64 channels (merged2_decoder_2 forward): conv_dc64.hip
+      ProfScope prof("dc256", true, 64, 128, flops, bytes, st);
       return launch_conv_dc256(a, st);
     }
-    if (dc64_knob() && conv_dc64_eligible(a, 1)) {
-      ProfScope prof("dc64", true, 64, 128, 2.0 * Pn * a.Cout * kreal,
-                     es * ((double)a.N * a.Hin * a.Win * a.cin_real + kreal * a.nclass * a.Cout + Pn * a.Cout), st);
+    case CK_DC64: {    // 4x4 stride-2 transposed conv from 128 to 64 channels (backward-data of layer_2 / encoder_2 / encoder_fg_2): weights resident
+      ProfScope prof("dc64", true, 64, 128, flops, bytes, st);        // in registers, two parity classes per block (conv_dc64.hip)
       return launch_conv_dc64(a, st);
     }
-  }
-  if constexpr (sizeof(T) == 2) {
-    // 4x4 stride-2 conv from 64 to 128 channels in front of a batch-norm (layer_2 / encoder_2 / encoder_fg_2 forward): weights resident
-    // in registers, parity-split input patch, batch statistics per block (conv_s2c64.hip)
-    if (a.patch == 4) {
-      if (!conv_s2c64_eligible(a, 1)) return hipErrorInvalidValue;       // (a plan for this kernel runs on no other: fail loudly)
-      ProfScope prof("s2c64", true, 128, 64, 2.0 * Pn * a.Cout * kreal,
-                     es * ((double)a.N * a.Hin * a.Win * a.cin_real + kreal * a.nclass * a.Cout + Pn * a.Cout), st);
+    case CK_S2C64: {   // 4x4 stride-2 conv from 64 to 128 channels in front of a batch-norm (layer_2 / encoder_2 / encoder_fg_2 forward): weights
+      ProfScope prof("s2c64", true, 128, 64, flops, bytes, st);       // resident in registers, parity-split input patch, statistics per block (conv_s2c64.hip)
       return launch_conv_s2c64(a, st);
     }
-  }
-  if (a.patch == 4) return hipErrorInvalidValue;
-  if constexpr (sizeof(T) == 2) {
-    // 4x4 / stride-1 taps without batch statistics (the discriminator's layer_4 backward-data passes): the unrolled patch kernel with
-    // 16 tap steps per chunk, 128-row x 16 x 16-pixel tiles (conv_patch3.hip, KW = 4)
-    if (a.patch == 1 && patch4_eligible(a, 1)) {
-      ProfScope prof("patch4", true, 128, 256, 2.0 * Pn * a.Cout * kreal,
-                     es * ((double)a.N * a.Hin * a.Win * a.cin_real + kreal * a.nclass * a.Cout + Pn * a.Cout), st);
+    case CK_PATCH4: {  // 4x4 / stride-1 taps (the discriminator's layer_4): the unrolled patch kernel with 16 tap steps per chunk, 128-row x
+      ProfScope prof("patch4", true, 128, 256, flops, bytes, st);     // 16 x 16-pixel tiles (conv_patch3.hip, KW = 4)
       return launch_igemm_patch4(a, st);
     }
+    default: break;
   }
-  if (a.patch) {   // stride-1 convs with the input patch staged once per channel chunk (conv_patch.hip)
-    // class name per kernel template: patch2 (parity classes, conv_patch2.hip), patch3 (unrolled 3x3, conv_patch3.hip), patch (generic)
-    const char* pk = a.patch == 2 ? "patch2" : (patch3_knob() && patch3_eligible(a, sizeof(T) == 2) ? "patch3" : "patch");
-    ProfScope prof(pk, sizeof(T) == 2, pbc, pbp, 2.0 * Pn * a.Cout * kreal,
-                   es * ((double)a.N * a.Hin * a.Win * a.cin_real + kreal * a.nclass * a.Cout + Pn * a.Cout), st);
-    return launch_igemm_patch(a, sizeof(T) == 2, pbc, pbp, st);
-  }
-  const bool use_patch = false;
-  ProfScope prof(use_patch ? "patch" : "igemm", sizeof(T) == 2, pbc, pbp, 2.0 * Pn * a.Cout * kreal,
-                 es * ((double)a.N * a.Hin * a.Win * a.cin_real + kreal * a.nclass * a.Cout + Pn * a.Cout), st);
+  if (a.kern != CK_IGEMM) return hipErrorInvalidValue;     // (a bf16-only kernel in a float32 plan: refused by conv_kernel_ok above)
+  ProfScope prof("igemm", bf, pbc, pbp, flops, bytes, st);
   switch (cfg) {
     case 0: e = launch_igemm_cfg<T, 2, 2, 4, 4>(a, st); break;   // 128 ch x 128 px (the same tile on 8 + 4 waves for small grids: +-0, EXPERIMENTS.md 0.2)
     case 1: e = launch_igemm_cfg<T, 1, 4, 4, 2>(a, st); break;   //  64 ch x 128 px

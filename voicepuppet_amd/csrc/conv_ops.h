@@ -82,9 +82,18 @@ inline void set_single_src(PixSrc& x, const void* p, int C, const float* a, cons
 // ---------------------------------------------------------------------------------------------
 // forward
 // ---------------------------------------------------------------------------------------------
+// What the launches of a plan pass besides the plan's own arguments, as far as the kernel choice depends on it (the executor fills in
+// the pointers; here it only says which of them are set).  ldY / y_f32 / out_act / split_c live in the plan's arguments.
+struct LaunchForm {
+  bool bias = false, ref = false, xa_lrelu = false, xa_relu = false, x_affine = false;
+  bool stats = false;       // forward batch statistics from the staged epilogue (IgemmArgs::bn_part with one row per pixel tile)
+  int x_act = 0, ref_act = 0;   // vp::Act
+};
+
 struct IgemmPlan {
   IgemmArgs a;
   int cfg;
+  LaunchForm form;        // what its launches pass (plan_kernel)
   PackDesc pack;
   size_t pack_elems;      // elements of the packed weight block
   size_t partial_bytes;
@@ -204,7 +213,7 @@ inline void plan_make_patch(IgemmPlan& p, int rows, int is_bf16) {
   const int bc = p4 ? 128 : patch_tile_rows(rows, patch_tiles_knob());
   int ks = 0;
   while (ks * ks < a.ntaps) ++ks;
-  a.patch = 1; a.p_kw = ks;
+  a.kern = CK_PATCH; a.p_kw = ks;
   a.p_dhf = a.taps[0].dh[0]; a.p_dwf = a.taps[0].dw[0];
   a.p_dhs = a.taps[0].dh[ks] - a.taps[0].dh[0]; a.p_dws = a.taps[0].dw[1] - a.taps[0].dw[0];
   const int bp = p4 ? 256 : patch_tile_pixels(bc);
@@ -239,7 +248,7 @@ inline bool plan_patch2_eligible(const IgemmPlan& p, int rows, int is_bf16, int 
 inline void plan_make_patch2(IgemmPlan& p, int rows, int is_bf16) {
   IgemmArgs& a = p.a;
   const int bc = rows % 128 == 0 ? 128 : 64;
-  a.patch = 2; a.p_kw = 2;
+  a.kern = CK_PATCH2; a.p_kw = 2;
   p.cfg = bc == 128 ? 13 : 14;
   a.CoutPad = round_up(rows, bc);
   a.splitk = 1;
@@ -273,7 +282,7 @@ inline void plan_make_smallp(IgemmPlan& p, int rows, int is_bf16) {
   IgemmArgs& a = p.a;
   const int kc = kc_elems(is_bf16);
   const int Pc = a.N * a.Hg * a.Wg;
-  a.patch = 3;
+  a.kern = CK_SMALLP;
   a.sp_npt = Pc <= 16 ? 1 : (Pc <= 32 ? 2 : 4);
   p.cfg = a.sp_npt == 1 ? 16 : (a.sp_npt == 2 ? 17 : 18);
   a.sp_lcpt = ilog2(a.Cin / kc);
@@ -322,12 +331,66 @@ inline bool plan_s2c64_eligible(const IgemmPlan& p, int rows, int is_bf16, int c
 }
 inline void plan_make_s2c64(IgemmPlan& p) {
   IgemmArgs& a = p.a;
-  a.patch = 4;
+  a.kern = CK_S2C64;
   p.cfg = 0;                 // (128 x 128: the class name's tile; the kernel has its own)
   a.CoutPad = a.Cout; a.wp_rows = a.Cout; p.pack.rows_pad = a.Cout;
   p.pack_elems = (size_t)a.wp_rows * a.Kpad;
   a.splitk = 1; p.partial_bytes = 0;
   a.rowperm = 1; p.pack.perm = 1; p.pack.kswap = 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// kernel choice: once per plan, when it is made
+// ---------------------------------------------------------------------------------------------
+// the arguments a launch of plan p with form f passes, pointers that are set standing in as a never-dereferenced address
+inline IgemmArgs launch_view(const IgemmPlan& p, const LaunchForm& f) {
+  static char set[16] = {};
+  IgemmArgs v = p.a;
+  v.Y = set; v.zeros = set;
+  if (v.split_c) v.Y2 = set;
+  if (f.bias) v.bias = (const float*)set;
+  if (f.ref) { v.ref = set; v.ref_act = f.ref_act; if (v.split_c) v.ref2 = set; }
+  if (f.xa_lrelu) v.xa_lrelu = set;
+  if (f.xa_relu) v.xa_relu = set;
+  if (f.x_affine) v.x.aff_a[0] = (const float*)set;
+  v.x.act = f.x_act;
+  if (f.stats) v.bn_part = (double*)set;       // (bn_tpg stays 0: not the one-group two-rows-per-block form of conv_dc256_kernel)
+  return v;
+}
+
+// the specialised kernel for a launch of this family, in priority order (the first whose preconditions hold), else the family's own
+inline int pick_conv_kernel(const IgemmArgs& v, int is_bf16) {
+  const int fam = conv_staging(v.kern);
+  if (fam == CK_SMALLP || fam == CK_S2C64) return fam;
+  if (is_bf16) {
+    if (conv_cin8_eligible(v, 1)) return CK_CIN8;
+    if (conv_cout8_eligible(v, 1)) return CK_COUT8;
+    if (conv_dcout8_eligible(v, 1)) return CK_DCOUT8;
+    if (conv_cout4_eligible(v, 1)) return CK_COUT4;
+    if (c64_knob() && conv_c64_eligible(v, 1)) return CK_C64;
+    if (dc64_knob() && conv_dc256_eligible(v, 1)) return CK_DC256;
+    if (dc64_knob() && conv_dc64_eligible(v, 1)) return CK_DC64;
+    if (patch4_knob() && patch4_eligible(v, 1)) return CK_PATCH4;
+  }
+  if (fam == CK_PATCH && patch3_knob() && patch3_eligible(v, is_bf16)) return CK_PATCH3;
+  return fam;
+}
+
+// plan families a caller allows (plan_kernel)
+enum { FAM_SMALLP = 1, FAM_PATCH = 2, FAM_PATCH2 = 4, FAM_S2C64 = 8, FAM_ALL = 15 };
+
+// The one place a convolution launch's kernel is chosen (and every kernel-selecting knob read): the plan family - how the plan stages
+// its operands and packs its weights - from those the caller allows, then the kernel within it (IgemmArgs::kern).  rows: output channels
+// of the GEMM; c0 / c1: channels of the one or two source tensors; any_grid: see plan_patch_eligible.  The plan's ldY / y_f32 / out_act /
+// ref_act / split_c must be those of its launches.
+inline void plan_kernel(IgemmPlan& p, int rows, int is_bf16, int c0, int c1, unsigned fams, const LaunchForm& f, bool any_grid = false) {
+  if ((fams & FAM_SMALLP) && plan_smallp_eligible(p, rows, is_bf16, c0, c1)) plan_make_smallp(p, rows, is_bf16);
+  else if ((fams & FAM_PATCH) && plan_patch_eligible(p, rows, is_bf16, c1 == 0 && c0 == p.a.Cin, any_grid)) plan_make_patch(p, rows, is_bf16);
+  else if ((fams & FAM_PATCH2) && plan_patch2_eligible(p, rows, is_bf16, c0, c1)) plan_make_patch2(p, rows, is_bf16);
+  else if ((fams & FAM_S2C64) && plan_s2c64_eligible(p, rows, is_bf16, c0, c1)) plan_make_s2c64(p);
+  p.form = f;
+  p.a.x.C[0] = c0; p.a.x.C[1] = c1;      // (what the launch's source operand will say)
+  p.a.kern = pick_conv_kernel(launch_view(p, f), is_bf16);
 }
 
 // x (PixSrc, total channels g.Cin) -> y [N,Hout,Wout,ldY]

@@ -245,7 +245,7 @@ static hipError_t launch_patch3_t(const IgemmArgs& b, hipStream_t st) {
 // 3x3 taps on a +1 / +1 or -1 / -1 grid, an even number of 64-byte channel chunks: what the unrolled kernel handles
 bool patch3_eligible(const IgemmArgs& a, int is_bf16) {
   const int kc = is_bf16 ? 32 : 16;
-  return a.patch && a.ntaps == 9 && a.p_kw == 3 && a.p_dhs == a.p_dws && (a.p_dhs == 1 || a.p_dhs == -1) && a.x.C[0] % (2 * kc) == 0 &&
+  return conv_staging(a.kern) == CK_PATCH && a.ntaps == 9 && a.p_kw == 3 && a.p_dhs == a.p_dws && (a.p_dhs == 1 || a.p_dhs == -1) && a.x.C[0] % (2 * kc) == 0 &&
          a.x.C[1] == 0;
 }
 
@@ -253,7 +253,7 @@ bool patch3_eligible(const IgemmArgs& a, int is_bf16) {
 // rows a multiple of 128: the 128-row x 16 x 16-pixel tile (80 KB of LDS with four ring stages: two blocks per CU; the 256-row tile would
 // need 96 KB) - plan_make_patch names that tile for 4x4 layers
 bool patch4_eligible(const IgemmArgs& a, int is_bf16) {
-  return patch4_knob() && is_bf16 && a.patch == 1 && a.ntaps == 16 && a.p_kw == 4 && a.p_dhs == a.p_dws && (a.p_dhs == 1 || a.p_dhs == -1) &&
+  return is_bf16 && conv_staging(a.kern) == CK_PATCH && a.ntaps == 16 && a.p_kw == 4 && a.p_dhs == a.p_dws && (a.p_dhs == 1 || a.p_dhs == -1) &&
          a.x.C[0] % 64 == 0 && a.x.C[1] == 0 && a.CoutPad % 128 == 0 && !a.pool_out;
 }
 hipError_t launch_igemm_patch4(const IgemmArgs& a, hipStream_t st) {

@@ -299,7 +299,7 @@ int conv_s2c64_tiles_per_image(const IgemmArgs& a) { return (a.Hg / TH) * (a.Wg 
 // run-time side of plan_s2c64_eligible (conv_ops.h): a plan made by plan_make_s2c64 with a raw bf16 output and a plain input; either the
 // forward form (128 output channels, no reference) or the two-output backward-data form (split_c = 128: 2 x 128 channels, relu'(reference))
 bool conv_s2c64_eligible(const IgemmArgs& a, int is_bf16) {
-  if (!is_bf16 || a.patch != 4 || a.ldY != 128 || a.Cin != 64 || a.x.C[0] != 64 || a.x.C[1] != 0 || !a.rowperm || a.splitk != 1) return false;
+  if (!is_bf16 || a.kern != CK_S2C64 || a.ldY != 128 || a.Cin != 64 || a.x.C[0] != 64 || a.x.C[1] != 0 || !a.rowperm || a.splitk != 1) return false;
   if (a.Hg % TH || a.Wg % TW || a.Hin != 2 * a.Hg || a.Win != 2 * a.Wg) return false;
   if (a.out_act != ACT_NONE || a.y_f32 || a.pool_out || a.x.aff_a[0] || a.x.act != ACT_NONE || a.ref_a) return false;
   if (a.split_c) {

@@ -429,7 +429,7 @@ hipError_t launch_smallp(const SmallPArgs& s, int is_bf16, hipStream_t st) {
   return hipErrorInvalidValue;
 }
 
-// plain-epilogue form behind launch_igemm (IgemmArgs::patch == 3): the stand-alone op entry points and BN-free layers
+// plain-epilogue form behind launch_igemm (IgemmArgs::kern == CK_SMALLP): the stand-alone op entry points and BN-free layers
 hipError_t launch_igemm_smallp(const IgemmArgs& a, int is_bf16, hipStream_t st) {
   SmallPArgs s;
   memset(&s, 0, sizeof(s));

@@ -110,8 +110,8 @@ size_t vp_conv_workspace_bytes(const vp_conv_desc* d) {
   {
     IgemmPlan p = plan_fwd(g, 0, bf);      // (the patch-kernel plan of the same layer needs no more: same packed block, no split-K slab)
     best = align256(p.pack_elems * es) + p.partial_bytes;
-    if (plan_smallp_eligible(p, g.Cout, bf, d->cin, 0)) {
-      plan_make_smallp(p, g.Cout, bf);
+    plan_kernel(p, g.Cout, bf, d->cin, 0, FAM_SMALLP, LaunchForm{});
+    if (p.a.kern == CK_SMALLP) {
       const size_t b = align256(p.pack_elems * es) + align256(p.partial_bytes) + 512 + (size_t)smallp_counters(p.a) * sizeof(unsigned);
       if (b > best) best = b;
     }
@@ -120,8 +120,8 @@ size_t vp_conv_workspace_bytes(const vp_conv_desc* d) {
     IgemmPlan p = plan_bwd_data(g, 0, 0, d->cin, d->cin, d->cin, bf);
     size_t b = align256(p.pack_elems * es) + p.partial_bytes;
     if (b > best) best = b;
-    if (plan_smallp_eligible(p, d->cin, bf, d->cout, 0)) {
-      plan_make_smallp(p, d->cin, bf);
+    plan_kernel(p, d->cin, bf, d->cout, 0, FAM_SMALLP, LaunchForm{});
+    if (p.a.kern == CK_SMALLP) {
       b = align256(p.pack_elems * es) + align256(p.partial_bytes) + 512 + (size_t)smallp_counters(p.a) * sizeof(unsigned);
       if (b > best) best = b;
     }
@@ -140,20 +140,21 @@ int vp_conv_fwd(const vp_conv_desc* d, const void* x, const float* in_scale, con
   hipStream_t st = (hipStream_t)stream;
   const ConvGeomX g = geom_of(d);
   IgemmPlan p = plan_fwd(g, 0, bf);
+  p.a.out_act = d->out_act;
+  LaunchForm f;
+  f.bias = bias != nullptr; f.x_affine = in_scale != nullptr; f.x_act = d->in_act;
   // the patch kernel moves plain bytes (LDS-DMA): only inputs that need no deferred affine / activation
-  if (d->in_act == ACT_NONE && !in_scale && plan_smallp_eligible(p, g.Cout, bf, d->cin, 0)) plan_make_smallp(p, g.Cout, bf);
-  else if (d->in_act == ACT_NONE && !in_scale && plan_patch_eligible(p, g.Cout, bf, true)) plan_make_patch(p, g.Cout, bf);
-  else if (d->in_act == ACT_NONE && !in_scale && plan_patch2_eligible(p, g.Cout, bf, d->cin, 0)) plan_make_patch2(p, g.Cout, bf);
-  else if (d->in_act == ACT_NONE && !in_scale && d->out_act == ACT_NONE && plan_s2c64_eligible(p, g.Cout, bf, d->cin, 0)) plan_make_s2c64(p);
+  const bool plain = d->in_act == ACT_NONE && !in_scale;
+  plan_kernel(p, g.Cout, bf, d->cin, 0, plain ? (FAM_SMALLP | FAM_PATCH | FAM_PATCH2 | (d->out_act == ACT_NONE ? FAM_S2C64 : 0)) : 0, f);
   char* ws = (char*)workspace;
   VP_HIP_CHECK(launch_pack_weights_one(p.pack, w, ws, bf, st));
   IgemmArgs a = p.a;
   set_single_src(a.x, x, d->cin, in_scale, in_shift, d->in_act, 0);
   a.Wp = ws;
   a.partial = (float*)(ws + align256(p.pack_elems * es));
-  a.Y = y; a.ldY = d->cout; a.bias = bias; a.out_act = d->out_act;
+  a.Y = y; a.bias = bias;
   a.zeros = zero_page(ws, align256(p.pack_elems * es) + p.partial_bytes, st);
-  if (a.patch == 3) a.sp_cnt = smallp_counter_page(ws, align256(p.pack_elems * es) + p.partial_bytes, a, st);
+  if (a.kern == CK_SMALLP) a.sp_cnt = smallp_counter_page(ws, align256(p.pack_elems * es) + p.partial_bytes, a, st);
   VP_HIP_CHECK(launch_igemm(a, bf, p.cfg, st));
   return VP_OK;
 }
@@ -165,9 +166,7 @@ int vp_conv_bwd_data(const vp_conv_desc* d, const void* dy, const float* w, void
   hipStream_t st = (hipStream_t)stream;
   const ConvGeomX g = geom_of(d);
   IgemmPlan p = plan_bwd_data(g, 0, 0, d->cin, d->cin, d->cin, bf);
-  if (plan_smallp_eligible(p, d->cin, bf, d->cout, 0)) plan_make_smallp(p, d->cin, bf);
-  else if (plan_patch_eligible(p, d->cin, bf, true)) plan_make_patch(p, d->cin, bf);
-  else if (plan_patch2_eligible(p, d->cin, bf, d->cout, 0)) plan_make_patch2(p, d->cin, bf);
+  plan_kernel(p, d->cin, bf, d->cout, 0, FAM_SMALLP | FAM_PATCH | FAM_PATCH2, LaunchForm{});
   char* ws = (char*)workspace;
   VP_HIP_CHECK(launch_pack_weights_one(p.pack, w, ws, bf, st));
   IgemmArgs a = p.a;
@@ -176,7 +175,7 @@ int vp_conv_bwd_data(const vp_conv_desc* d, const void* dy, const float* w, void
   a.partial = (float*)(ws + align256(p.pack_elems * es));
   a.Y = dx;
   a.zeros = zero_page(ws, align256(p.pack_elems * es) + p.partial_bytes, st);
-  if (a.patch == 3) a.sp_cnt = smallp_counter_page(ws, align256(p.pack_elems * es) + p.partial_bytes, a, st);
+  if (a.kern == CK_SMALLP) a.sp_cnt = smallp_counter_page(ws, align256(p.pack_elems * es) + p.partial_bytes, a, st);
   VP_HIP_CHECK(launch_igemm(a, bf, p.cfg, st));
   return VP_OK;
 }

@@ -111,6 +111,7 @@ struct Layer {
   // one-output-channel stride-1 conv (D layer_5) run as a GEMM over taps (TapArgs): x is read once per pass, not 16 times
   size_t desc0 = 0, desc1 = 0;   // this layer's pack descriptors: Net::descs[desc0, desc1)
   bool tapgemm = false;
+  bool fwd_stats = false;    // the forward launch writes the batch statistics from its staged epilogue, one row per pixel tile (epi_stat_chunks)
   float* tap_S = nullptr;    // [N,Hin,Win,16] f32
   void* tap_dyS = nullptr;   // [N,Hin,Win,16] T
   unsigned* sp_cnt_fwd = nullptr;               // few-pixel kernel (conv_smallp.hip): arrival counters of this layer's launches
@@ -303,6 +304,13 @@ static void build_vgg(Net& n, int N, int H) {
 }
 
 static int epi_stat_chunks(const IgemmPlan& p, int batch, int groups);
+// First layers (8-channel image inputs, no batch-norm: encoder_1, encoder_fg_1, discriminator layer_1) on the bf16 path whose consumers'
+// activations the direct kernel's epilogue can write (first_layer_acts_fused)
+static bool first_layer_shape(int bf16, const Net& n, const Layer& L) {
+  if (!bf16 || L.has_bn || L.tapgemm || L.out_act != ACT_NONE) return false;
+  const Tens& to = n.t[L.out];
+  return to.need_act[ACT_LRELU] && !to.is_f32;      // (the kernel's output combinations: lrelu copy [+ relu copy] [+ raw])
+}
 constexpr int BST_MAX_CHUNKS = 8192;      // rows per group of a backward-sums table (the finalize walks them 512 at a time)
 
 // plans + packed-weight layout for one net.  alt_batch > 0: also plan bwd-data for that batch (D, G-loss pass)
@@ -314,8 +322,11 @@ static void plan_net(Net& n, int bf16, bool training, bool want_wgrad, int alt_b
     n.descs.push_back(p.pack);
     if (p.partial_bytes > *scratch_max) *scratch_max = p.partial_bytes;
   };
+  for (Tens& t : n.t) t.is_f32 = t.name == "decoder_1" || t.name == "layer_5";   // thin float32 outputs (plan-level buffers)
   for (Layer& L : n.l) {
     L.desc0 = n.descs.size();
+    Tens& to = n.t[L.out];
+    const int c0 = n.t[L.src[0]].C, c1 = L.nsrc > 1 ? n.t[L.src[1]].C : 0;
     L.tapgemm = training && L.g.kind == 0 && L.g.stride == 1 && L.g.ks == 4 && L.g.Cout == 1 && L.nsrc == 1 && !L.has_bn &&
                 L.g.Cin == L.g.Cin_real;
     if (L.tapgemm) {
@@ -323,15 +334,28 @@ static void plan_net(Net& n, int bf16, bool training, bool want_wgrad, int alt_b
       ConvGeomX g1 = make_geom(0, 1, 1, 0, L.g.N, L.g.Hin, L.g.Win, L.g.Cin, L.g.Cin, 16);
       L.fwd = plan_fwd(g1, L.w_off, bf16);
       L.fwd.pack.s_row = L.g.Cin; L.fwd.pack.s_ch = 1; L.fwd.pack.s_kh = 0; L.fwd.pack.s_kw = 0;
+      L.fwd.a.y_f32 = 1;        // S, float32
+      plan_kernel(L.fwd, 16, bf16, L.g.Cin, 0, 0, LaunchForm{});
     } else {
       L.fwd = plan_fwd(L.g, L.w_off, bf16);
+      L.fwd.a.ldY = to.is_f32 ? L.g.Cout : to.C; L.fwd.a.y_f32 = to.is_f32 ? 1 : 0; L.fwd.a.out_act = L.out_act;
+      LaunchForm f;
+      f.bias = !L.has_bn;       // a bias in front of batch-norm cancels exactly
+      if (first_layer_shape(bf16, n, L)) { f.xa_lrelu = true; f.xa_relu = to.need_act[ACT_RELU]; }
       // the generator's few-pixel bottleneck: conv + K-split combine + batch-norm + activations in one launch (conv_smallp.hip)
-      if (n.groups == 1 && alt_batch == 0 && plan_smallp_eligible(L.fwd, L.g.Cout, bf16, n.t[L.src[0]].C, L.nsrc > 1 ? n.t[L.src[1]].C : 0))
-        plan_make_smallp(L.fwd, L.g.Cout, bf16);
-      else if (plan_patch_eligible(L.fwd, L.g.Cout, bf16, L.nsrc == 1 && n.t[L.src[0]].C == L.g.Cin)) plan_make_patch(L.fwd, L.g.Cout, bf16);
-      else if (plan_patch2_eligible(L.fwd, L.g.Cout, bf16, n.t[L.src[0]].C, L.nsrc > 1 ? n.t[L.src[1]].C : 0)) plan_make_patch2(L.fwd, L.g.Cout, bf16);
-      else if (L.has_bn && L.out_act == ACT_NONE && !L.tapgemm && plan_s2c64_eligible(L.fwd, L.g.Cout, bf16, n.t[L.src[0]].C, L.nsrc > 1 ? n.t[L.src[1]].C : 0))
-        plan_make_s2c64(L.fwd);
+      const unsigned fams = (n.groups == 1 && alt_batch == 0 ? FAM_SMALLP : 0) | FAM_PATCH | FAM_PATCH2 |
+                            (L.has_bn && L.out_act == ACT_NONE ? FAM_S2C64 : 0);
+      plan_kernel(L.fwd, L.g.Cout, bf16, c0, c1, fams, f);
+      // batch statistics from the conv epilogue (no re-read of the output) when every pixel tile lies inside one BN group; the
+      // one-group form of conv_dc256_kernel and conv_s2c64_kernel write rows of their own (run_layer_fwd)
+      const IgemmArgs& a = L.fwd.a;
+      const bool own_rows = (a.kern == CK_DC256 && n.groups == 1) || a.kern == CK_S2C64;
+      const int chunks = epi_stat_chunks(L.fwd, n.batch, n.groups);
+      if (L.has_bn && !own_rows && chunks > 0 && L.g.Cout % 8 == 0 && a.ldY % 8 == 0 && !a.y_f32 &&
+          (size_t)n.groups * chunks * 2 * to.C <= (size_t)1024 * 2 * 512) {
+        L.fwd_stats = L.fwd.form.stats = true;
+        L.fwd.a.kern = pick_conv_kernel(launch_view(L.fwd, L.fwd.form), bf16);
+      }
     }
     take(L.fwd);
     L.pk_fwd = L.fwd.pack.dst_off;
@@ -339,11 +363,13 @@ static void plan_net(Net& n, int bf16, bool training, bool want_wgrad, int alt_b
       ConvGeomX g2 = L.g;
       g2.N = alt_batch;
       L.fwd_half = plan_fwd(g2, L.w_off, bf16);
+      L.fwd_half.a.ldY = to.C; L.fwd_half.a.out_act = L.out_act;
+      LaunchForm f;
+      f.bias = true;
       // the half-batch launches take the kernel family of the layer's full-batch plan (the minimum-grid rule would otherwise pick the
       // patch kernel for 2N images and the gather kernel for N at small batches: same result up to the order of the K sum, but then
       // the overlapped step and the single-stream step are no longer bit-identical - seen at N = 8, 256x256)
-      if (L.fwd.a.patch == 1 && plan_patch_eligible(L.fwd_half, g2.Cout, bf16, L.nsrc == 1 && n.t[L.src[0]].C == g2.Cin, true))
-        plan_make_patch(L.fwd_half, g2.Cout, bf16);
+      plan_kernel(L.fwd_half, g2.Cout, bf16, c0, c1, conv_staging(L.fwd.a.kern) == CK_PATCH ? FAM_PATCH : 0, f, true);
       const PackDesc &pa = L.fwd.pack, &pb = L.fwd_half.pack;
       if (L.fwd_half.a.splitk == 1) {
         if (pa.kswap != pb.kswap || pa.perm != pb.perm || pa.kc != pb.kc || pa.Kpad != pb.Kpad || pa.rows_pad != pb.rows_pad) {
@@ -365,6 +391,11 @@ static void plan_net(Net& n, int bf16, bool training, bool want_wgrad, int alt_b
       // gradient w.r.t. network inputs is only needed for the discriminator (G loss) and VGG inputs
       L.need_bwd[s] = !ts.is_input || (n.groups == 3) || (n.l[0].g.ks == 3);
       if (L.need_bwd[s]) {
+        // the chain rule through the consumer's activation (lrelu' / relu' of the materialised input), or through the producer's relu
+        // epilogue (VGG: conv + relu outputs, pools excepted)
+        LaunchForm f;
+        f.ref_act = L.in_act != ACT_NONE ? L.in_act : (ts.producer >= 0 && n.l[ts.producer].out_act == ACT_RELU ? ACT_RELU : ACT_NONE);
+        f.ref = !ts.is_input && f.ref_act != ACT_NONE;
         L.bwd[s] = plan_bwd_data(L.g, L.w_off, row0, rows, rows_real, ts.C, bf16);
         if (alt_batch > 0) {
           ConvGeomX g2 = L.g;
@@ -376,15 +407,9 @@ static void plan_net(Net& n, int bf16, bool training, bool want_wgrad, int alt_b
             L.bwd[s].pack.perm = L.bwd_alt[s].pack.perm = 0;
           }
         }
-        if (n.groups == 1 && alt_batch == 0 && !ts.is_input && plan_smallp_eligible(L.bwd[s], rows, bf16, L.g.CoutT, 0)) {
-          plan_make_smallp(L.bwd[s], rows, bf16);
-        } else {
-          // backward-data of a stride-1 conv is a stride-1 conv over dY (one tensor of CoutT channels): patch kernel, per batch size
-          if (plan_patch_eligible(L.bwd[s], rows, bf16, true)) plan_make_patch(L.bwd[s], rows, bf16);
-          else if (plan_patch2_eligible(L.bwd[s], rows, bf16, L.g.CoutT, 0)) plan_make_patch2(L.bwd[s], rows, bf16);
-          if (alt_batch > 0 && plan_patch_eligible(L.bwd_alt[s], rows, bf16, true)) plan_make_patch(L.bwd_alt[s], rows, bf16);
-          else if (alt_batch > 0 && plan_patch2_eligible(L.bwd_alt[s], rows, bf16, L.g.CoutT, 0)) plan_make_patch2(L.bwd_alt[s], rows, bf16);
-        }
+        // backward-data of a stride-1 conv is a stride-1 conv over dY (one tensor of CoutT channels): patch kernel, per batch size
+        plan_kernel(L.bwd[s], rows, bf16, L.g.CoutT, 0, (n.groups == 1 && alt_batch == 0 && !ts.is_input ? FAM_SMALLP : 0) | FAM_PATCH | FAM_PATCH2, f);
+        if (alt_batch > 0) plan_kernel(L.bwd_alt[s], rows, bf16, L.g.CoutT, 0, FAM_PATCH | FAM_PATCH2, f);
         take(L.bwd[s]);
         L.pk_bwd[s] = L.pk_bwd_alt[s] = L.bwd[s].pack.dst_off;
         if (alt_batch > 0) {
@@ -401,20 +426,19 @@ static void plan_net(Net& n, int bf16, bool training, bool want_wgrad, int alt_b
       row0 += rows;
     }
     {
-      const int c0 = n.t[L.src[0]].C, c1 = L.nsrc > 1 ? n.t[L.src[1]].C : 0;
+      const int s0 = conv_staging(L.bwd[0].a.kern);
       if (L.nsrc == 2 && n.groups == 1 && alt_batch == 0 && L.need_bwd[0] && L.need_bwd[1] && c0 == c1 && !n.t[L.src[0]].is_input &&
-          !n.t[L.src[1]].is_input && L.bwd[0].a.patch == L.bwd[1].a.patch && (L.bwd[0].a.patch == 0 || L.bwd[0].a.patch == 3) &&
+          !n.t[L.src[1]].is_input && s0 == conv_staging(L.bwd[1].a.kern) && (s0 == CK_IGEMM || s0 == CK_SMALLP) &&
           L.g.Cin_real == c0 + c1 && c0 % 32 == 0) {     // (the two-output epilogues split at a 32-channel tile boundary: conv_smallp.hip, epi_store8)
         L.bwd_pair = plan_bwd_data(L.g, L.w_off, 0, c0 + c1, c0 + c1, c0, bf16);
-        bool ok = true;
-        if (L.bwd[0].a.patch == 3) {      // few-pixel layers: the pair runs on the few-pixel kernel too (first output with its batch-norm backward)
-          ok = plan_smallp_eligible(L.bwd_pair, c0 + c1, bf16, L.g.CoutT, 0);
-          if (ok) plan_make_smallp(L.bwd_pair, c0 + c1, bf16);
-        }
-        // the 256 -> 64 transposed convolution's pair (merged2_decoder_2: relu inputs): register-resident weights, conv_s2c64.hip
-        if (ok && s2c64_pair_knob() && L.bwd[0].a.patch == 0 && L.in_act == ACT_RELU && plan_s2c64_eligible(L.bwd_pair, c0 + c1, bf16, L.g.CoutT, 0)) plan_make_s2c64(L.bwd_pair);
-        if (ok) {
-          L.bwd_pair.a.split_c = c0;
+        L.bwd_pair.a.split_c = c0;
+        LaunchForm f;
+        f.ref = true; f.ref_act = L.in_act;
+        // few-pixel layers: the pair runs on the few-pixel kernel too (first output with its batch-norm backward); the 256 -> 64 transposed
+        // convolution's pair (merged2_decoder_2: relu inputs): register-resident weights, conv_s2c64.hip
+        const unsigned fams = s0 == CK_SMALLP ? FAM_SMALLP : (s2c64_pair_knob() && L.in_act == ACT_RELU ? FAM_S2C64 : 0);
+        plan_kernel(L.bwd_pair, c0 + c1, bf16, L.g.CoutT, 0, fams, f);
+        if (s0 != CK_SMALLP || L.bwd_pair.a.kern == CK_SMALLP) {
           take(L.bwd_pair);
           L.pk_bwd_pair = L.bwd_pair.pack.dst_off;
           L.has_pair = true;
@@ -434,11 +458,11 @@ static void plan_net(Net& n, int bf16, bool training, bool want_wgrad, int alt_b
   }
   n.packed_elems = pk;
   {
-    for (Tens& t : n.t) t.hi = bf16 && t.has_bn && n.groups == 1 && alt_batch == 0 && t.producer >= 0 && n.l[t.producer].fwd.a.patch == 3;
+    for (Tens& t : n.t) t.hi = bf16 && t.has_bn && n.groups == 1 && alt_batch == 0 && t.producer >= 0 && n.l[t.producer].fwd.a.kern == CK_SMALLP;
     if (training)
       for (Layer& L : n.l)
         for (int s = 0; s < L.nsrc; ++s)
-          if (L.need_bwd[s] && L.bwd[s].a.patch != 3) n.t[L.src[s]].hi = false;
+          if (L.need_bwd[s] && L.bwd[s].a.kern != CK_SMALLP) n.t[L.src[s]].hi = false;
     // a consumer without an input activation reads the tensor's raw storage as T (fill_src): such a tensor stays T (no consumer of a
     // batch-normalised tensor of the reference's nets does - a plan-time rule instead of a misread at run time)
     for (Layer& L : n.l)
@@ -473,13 +497,13 @@ static void plan_net(Net& n, int bf16, bool training, bool want_wgrad, int alt_b
   for (Tens& t : n.t) t.n_bwd_consumers = 0;
   n.sp_cnt_n = 0;
   for (Layer& L : n.l) {
-    if (L.fwd.a.patch == 3) n.sp_cnt_n += smallp_counters(L.fwd.a);
+    if (L.fwd.a.kern == CK_SMALLP) n.sp_cnt_n += smallp_counters(L.fwd.a);
     for (int s = 0; s < L.nsrc && training; ++s) {
       if (!L.need_bwd[s]) continue;
       n.t[L.src[s]].n_bwd_consumers++;
-      if (L.bwd[s].a.patch == 3) n.sp_cnt_n += smallp_counters(L.bwd[s].a);
+      if (L.bwd[s].a.kern == CK_SMALLP) n.sp_cnt_n += smallp_counters(L.bwd[s].a);
     }
-    if (training && L.has_pair && L.bwd_pair.a.patch == 3) n.sp_cnt_n += smallp_counters(L.bwd_pair.a);
+    if (training && L.has_pair && L.bwd_pair.a.kern == CK_SMALLP) n.sp_cnt_n += smallp_counters(L.bwd_pair.a);
   }
 }
 
@@ -513,10 +537,10 @@ static void carve_net(Net& n, Arena& ar, int es, bool training) {
   {
     unsigned* c = n.sp_cnt;
     for (Layer& L : n.l) {
-      if (L.fwd.a.patch == 3) { L.sp_cnt_fwd = c; c += c ? smallp_counters(L.fwd.a) : 0; }
+      if (L.fwd.a.kern == CK_SMALLP) { L.sp_cnt_fwd = c; c += c ? smallp_counters(L.fwd.a) : 0; }
       for (int s = 0; s < L.nsrc && training; ++s)
-        if (L.need_bwd[s] && L.bwd[s].a.patch == 3) { L.sp_cnt_bwd[s] = c; c += c ? smallp_counters(L.bwd[s].a) : 0; }
-      if (training && L.has_pair && L.bwd_pair.a.patch == 3) { L.sp_cnt_pair = c; c += c ? smallp_counters(L.bwd_pair.a) : 0; }
+        if (L.need_bwd[s] && L.bwd[s].a.kern == CK_SMALLP) { L.sp_cnt_bwd[s] = c; c += c ? smallp_counters(L.bwd[s].a) : 0; }
+      if (training && L.has_pair && L.bwd_pair.a.kern == CK_SMALLP) { L.sp_cnt_pair = c; c += c ? smallp_counters(L.bwd_pair.a) : 0; }
     }
   }
 }
@@ -665,7 +689,7 @@ static int run_bn_stats(vp_pixrefer* h, Net& n, Layer& L, int fused_chunks, hipS
 
 // the patch kernel's 16-pixel-wide tiles can write the 2x2 max pool of their output from the epilogue (even image sizes)
 static bool plan_can_pool(const IgemmPlan& p) {
-  if (p.a.patch != 1 || (p.a.Hg & 1) || (p.a.Wg & 1)) return false;
+  if (conv_staging(p.a.kern) != CK_PATCH || (p.a.Hg & 1) || (p.a.Wg & 1)) return false;
   int bc, bp;
   igemm_tile(p.cfg, &bc, &bp);
   int th, tw;
@@ -678,14 +702,15 @@ static bool plan_can_pool(const IgemmPlan& p) {
 // few-pixel / register-resident-weights kernels) or its pixel tiles straddle groups.
 static int epi_stat_chunks(const IgemmPlan& p, int batch, int groups) {
   const IgemmArgs& a = p.a;
-  if (a.splitk != 1 || a.patch == 3 || a.patch == 4 || batch % groups) return 0;
+  const int fam = conv_staging(a.kern);
+  if (a.splitk != 1 || fam == CK_SMALLP || fam == CK_S2C64 || batch % groups) return 0;
   int bc, bp;
   igemm_tile(p.cfg, &bc, &bp);
   const int pg = (batch / groups) * a.Hg * a.Wg;
-  if (!(a.patch || groups == 1 || pg % bp == 0)) return 0;
+  if (!(fam || groups == 1 || pg % bp == 0)) return 0;
   int pth = 16, ptw = 16;
   patch_tile_hw(bp, &pth, &ptw);
-  const int tpg = a.patch ? (batch / groups) * ((a.Hg + pth - 1) / pth) * ((a.Wg + ptw - 1) / ptw) : (pg + bp - 1) / bp;
+  const int tpg = fam ? (batch / groups) * ((a.Hg + pth - 1) / pth) * ((a.Wg + ptw - 1) / ptw) : (pg + bp - 1) / bp;
   return a.nclass * tpg;
 }
 
@@ -698,9 +723,8 @@ static int run_layer_fwd_half(vp_pixrefer* h, Net& n, Layer& L, int half, hipStr
   fill_src(n, L, a.x, nb, half * nb, 0, h->es);
   a.Wp = n.packed + L.pk_fwd_half * h->es;
   Tens& to = n.t[L.out];
-  a.Y = (char*)to.y + (size_t)half * nb * to.H * to.W * to.C * h->es; a.ldY = to.C; a.y_f32 = 0;
+  a.Y = (char*)to.y + (size_t)half * nb * to.H * to.W * to.C * h->es;      // (ldY, out_act: the plan's)
   a.bias = n.params + L.b_off;
-  a.out_act = L.out_act;
   a.partial = nullptr;        // (no K split on this path)
   a.zeros = h->zeros;
   profile_tag((L.scope + (half ? ":fwd1" : ":fwd0")).c_str());
@@ -713,13 +737,7 @@ static int run_layer_fwd_half(vp_pixrefer* h, Net& n, Layer& L, int half, hipStr
 // Nothing in a step reads the RAW output of such a layer then (consumers read the activations, the chain rule needs their sign only), so
 // it is not stored unless vp_pixrefer_set_option(h, "store_first_raw", 1) asks for it (vp_pixrefer_tensor refuses the tensor otherwise).
 static bool first_layer_acts_fused(const vp_pixrefer* h, const Net& n, const Layer& L) {
-  if (!h->bf16 || L.has_bn || L.tapgemm || L.out_act != ACT_NONE) return false;
-  const Tens& to = n.t[L.out];
-  if (!to.need_act[ACT_LRELU] || to.is_f32) return false;      // (the kernel's output combinations: lrelu copy [+ relu copy] [+ raw])
-  IgemmArgs a = L.fwd.a;
-  fill_src(n, L, a.x, n.batch / n.groups, 0, 0, h->es);
-  a.ldY = to.C; a.y_f32 = 0; a.out_act = L.out_act;
-  return conv_cin8_eligible(a, 1);
+  return first_layer_shape(h->bf16, n, L) && L.fwd.a.kern == CK_CIN8;
 }
 
 // forward of one conv layer (+ its batch statistics)
@@ -729,14 +747,11 @@ static int run_layer_fwd(vp_pixrefer* h, Net& n, Layer& L, hipStream_t st, void*
   fill_src(n, L, a.x, n.batch / n.groups, 0, 0, h->es);
   a.Wp = n.packed + L.pk_fwd * h->es;
   Tens& to = n.t[L.out];
-  a.Y = to.y; a.ldY = to.C; a.y_f32 = 0;
-  if (to.is_f32) { a.y_f32 = 1; a.ldY = L.g.Cout; }
-  a.bias = L.has_bn ? nullptr : n.params + L.b_off;   // a bias in front of batch-norm cancels exactly
-  a.out_act = L.out_act;
+  a.Y = L.tapgemm ? L.tap_S : to.y;      // (ldY, y_f32, out_act: the plan's)
+  a.bias = L.has_bn || L.tapgemm ? nullptr : n.params + L.b_off;   // a bias in front of batch-norm cancels exactly
   a.partial = (float*)scratch_of(h, ss);
   a.zeros = h->zeros;
-  if (L.tapgemm) { a.Y = L.tap_S; a.y_f32 = 1; a.ldY = 16; a.bias = nullptr; }
-  if (a.patch == 3) {
+  if (a.kern == CK_SMALLP) {
     // few-pixel layer: convolution, K-split combine, batch statistics, affine and the consumers' activations in ONE launch
     SmallPArgs sp;
     memset(&sp, 0, sizeof(sp));
@@ -760,15 +775,15 @@ static int run_layer_fwd(vp_pixrefer* h, Net& n, Layer& L, hipStream_t st, void*
                                     to.xa[ACT_LRELU], to.xa[ACT_RELU], h->bf16, st));
     return VP_OK;
   }
-  // batch statistics from the conv epilogue (no re-read of the output) when every pixel tile lies inside one BN group
+  // batch statistics from the conv epilogue (no re-read of the output): the layout of the plan's kernel (plan_net)
   bool fused_stats = false;
   int stat_chunks = 0;
-  if (L.has_bn && n.groups == 1 && h->bf16 && !L.tapgemm && conv_dc256_eligible(a, 1)) {
+  if (L.has_bn && a.kern == CK_DC256 && n.groups == 1) {
     // conv_dc64.hip conv_dc256_kernel: one partial row per block and column parity
     stat_chunks = 2 * conv_dc256_grid(a);
     a.bn_part = bnp_of(h, ss); a.bn_tpg = 1 << 30; a.bn_nchunk = stat_chunks;
     fused_stats = true;
-  } else if (L.has_bn && a.patch == 4) {
+  } else if (L.has_bn && a.kern == CK_S2C64) {
     // conv_s2c64.hip: one partial row per block and group
     const int grid = conv_s2c64_grid(a);
     if ((size_t)n.groups * grid * 2 * to.C <= (size_t)1024 * 2 * 512 && n.groups <= 32) {
@@ -776,21 +791,10 @@ static int run_layer_fwd(vp_pixrefer* h, Net& n, Layer& L, hipStream_t st, void*
       a.bn_part = bnp_of(h, ss); a.bn_tpg = (n.batch / n.groups) * conv_s2c64_tiles_per_image(a); a.bn_nchunk = grid;
       fused_stats = true;
     }
-  } else if (L.has_bn && a.splitk == 1 && L.g.Cout % 8 == 0 && a.ldY % 8 == 0 && !a.y_f32) {
-    int bc, bp;
-    igemm_tile(L.fwd.cfg, &bc, &bp);
-    const int pg = (n.batch / n.groups) * a.Hg * a.Wg;            // pixels of one group, per class
-    if (a.patch || n.groups == 1 || pg % bp == 0) {
-      // patch kernel: 2-D tiles of one image each (16 x 16 or 16 x 32 pixels), never across images or groups
-      int pth = 16, ptw = 16;
-      patch_tile_hw(bp, &pth, &ptw);
-      const int tpg = a.patch ? (n.batch / n.groups) * ((a.Hg + pth - 1) / pth) * ((a.Wg + ptw - 1) / ptw) : (pg + bp - 1) / bp;
-      stat_chunks = a.nclass * tpg;
-      if ((size_t)n.groups * stat_chunks * 2 * to.C <= (size_t)1024 * 2 * 512) {
-        a.bn_part = bnp_of(h, ss); a.bn_tpg = tpg; a.bn_nchunk = stat_chunks;
-        fused_stats = true;
-      }
-    }
+  } else if (L.fwd_stats) {       // one row per pixel tile and class
+    stat_chunks = epi_stat_chunks(L.fwd, n.batch, n.groups);
+    a.bn_part = bnp_of(h, ss); a.bn_tpg = stat_chunks / a.nclass; a.bn_nchunk = stat_chunks;
+    fused_stats = true;
   }
   // first layers (8-channel image inputs, no batch-norm: encoder_1, encoder_fg_1, discriminator layer_1): the direct kernel's epilogue
   // writes the consumers' activations itself - no act_apply pass over the (67 .. 201 MB) output
@@ -914,9 +918,9 @@ static int run_layer_bwd(vp_pixrefer* h, Net& n, Layer& L, const void* dy, bool 
     // 2x2-tap patch kernel and the plain implicit GEMM.  The sixteen accumulators do not fit beside the staged tile's registers in the
     // 128-register kernels: on the two-output launches (decoder_1: 0.090 -> 0.178 ms), the 4x4 patch kernel (layer_4: +0.063 ms) and the
     // 16-deep tap product of the generator-loss pass (layer_5: +0.010 ms against a 0.010 ms reduce) the spills cost as much or more than the reduce pass they replace.  2: every launch that can.
-    if (h->bst_on < 2 && (a.split_c || a.patch == 1 || (L.tapgemm && gpass))) return;
-    if (a.patch == 1 && !patch4_eligible(a, h->bf16)) return;
-    if (a.patch == 2 && (a.x.C[1] > 0 || (h->bf16 && conv_dc64_eligible(a, 1)))) return;
+    // Kernels with the staged epilogue: the plain implicit GEMM, the 2x2-tap patch kernel (single source) and the 4x4 patch kernel.
+    if (h->bst_on < 2 && (a.split_c || conv_staging(a.kern) == CK_PATCH || (L.tapgemm && gpass))) return;
+    if (a.kern != CK_IGEMM && a.kern != CK_PATCH4 && !(a.kern == CK_PATCH2 && a.x.C[1] == 0)) return;
     const int chunks = epi_stat_chunks(p, nb, groups);
     if (chunks <= 0 || chunks > (gpass ? ts.pbg_cap : ts.pb_cap)) return;
     double* part = gpass ? ts.bn.pbg : ts.bn.pb;
@@ -929,7 +933,7 @@ static int run_layer_bwd(vp_pixrefer* h, Net& n, Layer& L, const void* dy, bool 
   };
   // few-pixel pairs: only the usual case - this launch is the LAST contribution to the first tensor (its batch-norm backward runs in
   // the launch) and NOT the last one to the second (the skip tensor's own encoder consumer comes later)
-  const bool pair_sp = L.has_pair && L.bwd_pair.a.patch == 3;
+  const bool pair_sp = L.has_pair && L.bwd_pair.a.kern == CK_SMALLP;
   const bool pair_sp_ok = pair_sp && n.t[L.src[0]].has_bn && n.t[L.src[0]].dz_writes + 1 == n.t[L.src[0]].n_bwd_consumers &&
                           n.t[L.src[1]].dz_writes + 1 < n.t[L.src[1]].n_bwd_consumers;
   if (L.has_pair && (parts & 6) == 6 && !alt && !gpass && (!pair_sp || pair_sp_ok)) {
@@ -998,7 +1002,7 @@ static int run_layer_bwd(vp_pixrefer* h, Net& n, Layer& L, const void* dy, bool 
     } else {
       a.Y = gpass ? ts.dz2 : ts.dz;
       if (ts.hi) {
-        if (gpass || alt || a.patch != 3) { set_err("%s: float32 few-pixel tensor %s reached by a launch that is not the few-pixel kernel", L.scope.c_str(), ts.name.c_str()); return VP_ERR_STATE; }
+        if (gpass || alt || a.kern != CK_SMALLP) { set_err("%s: float32 few-pixel tensor %s reached by a launch that is not the few-pixel kernel", L.scope.c_str(), ts.name.c_str()); return VP_ERR_STATE; }
         a.Y = ts.dz32; a.y_f32 = 1;        // the gradient accumulates in float32 (Tens::hi)
       }
       bool& written = gpass ? ts.dz2_written : ts.dz_written;
@@ -1015,7 +1019,7 @@ static int run_layer_bwd(vp_pixrefer* h, Net& n, Layer& L, const void* dy, bool 
     }
     a.zeros = h->zeros;
     profile_tag((L.scope + (alt ? ":bwdG" : ":bwd")).c_str());
-    if (a.patch == 3 && !alt) {
+    if (a.kern == CK_SMALLP && !alt) {
       // few-pixel layer: K-split combine in the launch; when this is the last gradient contribution to a batch-normalised tensor, the
       // batch-norm backward of that tensor (sums, c1 / c2, dgamma / dbeta, dy in place) runs in the same launch
       SmallPArgs sp;
@@ -1071,7 +1075,7 @@ static int run_layer_bwd(vp_pixrefer* h, Net& n, Layer& L, const void* dy, bool 
     // the bias gradient of a producer without batch-norm (layer_1, encoder_1, encoder_fg_1) from this launch's epilogue when it completes
     // the tensor's gradient on conv_dc64.hip (the only kernel with that epilogue)
     if (h->bst_on && h->bf16 && !ts.is_input && !ts.has_bn && ts.cs_part && !gpass && !alt && ts.producer >= 0 && !n.l[ts.producer].tapgemm &&
-        (n.groups != 1 || ts.dz_writes == ts.n_bwd_consumers) && dc64_knob() && conv_dc64_eligible(a, 1)) {
+        (n.groups != 1 || ts.dz_writes == ts.n_bwd_consumers) && a.kern == CK_DC64) {
       a.colsum_part = ts.cs_part;
       ts.cs_chunks = conv_dc64_grid(a);
     }
@@ -1261,8 +1265,11 @@ int vp_pixrefer_validate_plan(const vp_pixrefer_desc* d) {
       auto plan_ok = [&](const IgemmPlan& p, const char* what) {
         if (p.partial_bytes > h->scratch_bytes) fail("%s %s: split-K slab %zu > scratch %zu", L.scope.c_str(), what, p.partial_bytes, h->scratch_bytes);
         if (p.a.splitk < 1 || p.a.CoutPad < p.a.Cout) fail("%s %s: splitk %d CoutPad %d", L.scope.c_str(), what, p.a.splitk, p.a.CoutPad);
+        if (!conv_kernel_ok(launch_view(p, p.form), h->bf16))
+          fail("%s %s: the launch is outside the preconditions of its kernel %s", L.scope.c_str(), what, conv_kernel_name(p.a.kern));
       };
       plan_ok(L.fwd, "fwd");
+      if (L.has_fwd_half) plan_ok(L.fwd_half, "fwd_half");
       if (d->training && L.has_pair) plan_ok(L.bwd_pair, "bwd_pair");
       if (d->training)
         for (int s2 = 0; s2 < L.nsrc; ++s2) if (L.need_bwd[s2]) { plan_ok(L.bwd[s2], "bwd"); if (n == &h->D || n == &h->V) plan_ok(L.bwd_alt[s2], "bwd_alt"); }
@@ -1350,10 +1357,10 @@ int vp_pixrefer_create(const vp_pixrefer_desc* d, void* workspace, size_t worksp
   h->D.params = params_d; h->D.grads = grads_d;
   h->V.params = const_cast<float*>(params_vgg);
   // thin f32 outputs
-  for (Tens& t : h->G.t) if (t.name == "decoder_1") { t.y = h->y4; t.is_f32 = true; t.dz = h->dy4; }
+  for (Tens& t : h->G.t) if (t.name == "decoder_1") { t.y = h->y4; t.dz = h->dy4; }
   hipStream_t st = (hipStream_t)stream;
   VP_HIP_CHECK(hipMemsetAsync(h->zeros, 0, 256, st));
-  if (d->training) for (Tens& t : h->D.t) if (t.name == "layer_5") { t.y = h->logits; t.is_f32 = true; t.dz = h->dl_d; }
+  if (d->training) for (Tens& t : h->D.t) if (t.name == "layer_5") { t.y = h->logits; t.dz = h->dl_d; }
   for (Net* n : {&h->G, &h->D, &h->V}) {
     if (n->descs.empty()) continue;
     VP_HIP_CHECK(hipMemcpyAsync(n->d_descs, n->descs.data(), n->descs.size() * sizeof(PackDesc), hipMemcpyHostToDevice, st));
