@@ -374,6 +374,53 @@ int vp_bfmstream_push(vp_bfmstream_t* h, const float* pcm, long long n, const fl
 int vp_bfmstream_finish(vp_bfmstream_t* h, const float* ears, float* coeff_out, void* stream);
 /* "mel" (the mel history ring, [rows][num_mel_bins]; row r of the clip sits at r % rows) */
 int vp_bfmstream_tensor(vp_bfmstream_t* h, const char* name, void** ptr, int64_t shape[4]);
+/* ------------------------------------------------------------------------------------------------
+ * Streaming groups: `slots` independent vp_bfmstream sessions behind one handle, for serving many talkers from one GPU.  A group push
+ * advances any subset of the slots by any number of samples each and runs ONE kernel chain per round for all of them: a ragged
+ * log-mel launch into each slot's mel ring, a ragged window gather, the MfccNet trunk on a plan of batch A (the active slots, rounded up
+ * to a bucket 1, 2, 4, .., slots), the stateful GRU with one block per slot, the decoder and one scatter into the packed output.  A slot
+ * with more than max_chunk_frames ready runs further rounds, with the other slots that still have frames.
+ *   - Each slot's coefficients are bit-identical to a vp_bfmstream with the same max_chunk_frames and trunk_dtype fed the same chunks:
+ *     the bucket plans reduce every row as the batch-1 window plan does (each GEMM's tile and K split pinned to that plan's).
+ *   - A slot that finishes a clip shorter than T_win runs its last frames alone on an exact-size plan (the vp_bfmstream rule), one
+ *     slot after the other: the slow path of short clips.
+ *   - Emission counts follow from sample counts alone (vp_bfmstream_group_ready); a push never waits on the device.
+ * ---------------------------------------------------------------------------------------------- */
+#define VP_BFMSTREAM_GROUP_MAX_SLOTS 128
+typedef struct vp_bfmstream_group_desc {
+  int struct_bytes;       /* sizeof(vp_bfmstream_group_desc) of the caller's build: must equal vp_bfmstream_group_desc_size() */
+  int slots;              /* 1 .. VP_BFMSTREAM_GROUP_MAX_SLOTS */
+  int max_chunk_frames;   /* per slot and round, as vp_bfmstream_desc */
+  int num_mel_bins;       /* 80 */
+  int trunk_dtype;        /* VP_F32 or VP_BF16 */
+  int sample_rate;        /* 16000 */
+  float lower_hz, upper_hz;   /* 80, 7600 */
+} vp_bfmstream_group_desc;
+/* Same ABI rule as vp_bfmstream_desc (the struct only grows at the tail; a wrong struct_bytes is refused) */
+size_t vp_bfmstream_group_desc_size(void);
+typedef struct vp_bfmstream_group vp_bfmstream_group_t;
+/* 0 on a refused descriptor (vp_last_error says why): bad struct_bytes / slots / stream fields, or a slots x max_chunk_frames whose
+ * batch-`slots` plan would exceed the 32-bit lane offsets of the kernels the one-stream plan runs (launch_dwproj, the GEMM loader) */
+size_t vp_bfmstream_group_workspace_bytes(const vp_bfmstream_group_desc* d);
+/* Host only (tests): GEMM `gemm` of bucket plan `bucket` (0: batch 1, 1: batch 2, ..): info = {batch, tile cfg, K splits, kernel,
+ * pixels, input channels, output channels, bf16 operands} */
+int vp_bfmstream_group_plan_info(const vp_bfmstream_group_desc* d, int bucket, int gemm, int info[8]);
+int vp_bfmstream_group_create(const vp_bfmstream_group_desc* d, void* workspace, size_t workspace_bytes, const float* params, void* stream,
+                              vp_bfmstream_group_t** out);
+void vp_bfmstream_group_destroy(vp_bfmstream_group_t* h);
+int vp_bfmstream_group_params_changed(vp_bfmstream_group_t* h);
+/* slot back to an empty session (a new clip); the other slots are untouched */
+int vp_bfmstream_group_reset_slot(vp_bfmstream_group_t* h, int slot, void* stream);
+/* Host only: frames k[s] (k may be NULL) the push of n[s] new samples per slot emits, finish[s] != 0 ending slot s's clip after them
+ * (finish may be NULL); returns the sum, or -1 on a bad argument (n[s] < 0, samples or finish for a finished slot) */
+long long vp_bfmstream_group_ready(const vp_bfmstream_group_t* h, const long long* n, const int* finish, int* k);
+/* pcm: device f32, the slots' new samples packed in slot order (n[s] each; n / finish are host arrays of `slots` entries, finish may be
+ * NULL).  finish[s]: append n[s] samples, then end slot s's clip as vp_bfmstream_finish does.  ears [K,1] / coeff_out [K,64]: device,
+ * K = vp_bfmstream_group_ready(...), rows packed in slot order (may be NULL when K = 0) */
+int vp_bfmstream_group_push(vp_bfmstream_group_t* h, const float* pcm, const long long* n, const int* finish, const float* ears, float* coeff_out,
+                            void* stream);
+/* "mel": the slots' mel rings [slots][rows][num_mel_bins]; mel frame r of slot s's clip sits at row r % rows */
+int vp_bfmstream_group_tensor(vp_bfmstream_group_t* h, const char* name, void** ptr, int64_t shape[4]);
 /* The stateful GRU step loop on its own (testing / other drivers): rows [t0, t0 + n) of each of b sequences of t rows, state in / out
  * in hstate [b][256] (zeros = a fresh sequence).  Same layout as vp_gru_seq. */
 int vp_gru_seq_state(const float* xg, const float* xc, const float* whg, const float* whc, float* hstate, float* out, int b, int t, int t0,

@@ -38,6 +38,14 @@ class BfmStreamDesc(ctypes.Structure):
               ("trunk_dtype", ctypes.c_int), ("sample_rate", ctypes.c_int), ("lower_hz", ctypes.c_float), ("upper_hz", ctypes.c_float)]
 
 
+class BfmStreamGroupDesc(ctypes.Structure):
+  _fields_ = [("struct_bytes", ctypes.c_int), ("slots", ctypes.c_int), ("max_chunk_frames", ctypes.c_int), ("num_mel_bins", ctypes.c_int),
+              ("trunk_dtype", ctypes.c_int), ("sample_rate", ctypes.c_int), ("lower_hz", ctypes.c_float), ("upper_hz", ctypes.c_float)]
+
+
+BFMSTREAM_GROUP_MAX_SLOTS = 128      # include/vp_hip.h VP_BFMSTREAM_GROUP_MAX_SLOTS
+
+
 class BfmModel(ctypes.Structure):
   _fields_ = [("nver", ctypes.c_int), ("ntri", ctypes.c_int), ("meanshape", ctypes.c_void_p), ("idBase", ctypes.c_void_p),
               ("exBase", ctypes.c_void_p), ("meantex", ctypes.c_void_p), ("texBase", ctypes.c_void_p), ("tri", ctypes.c_void_p),
@@ -143,6 +151,16 @@ _SIGNATURES = {
     "vp_bfmstream_push": (ctypes.c_int, [_P, _P, ctypes.c_longlong, _P, _P, _P]),
     "vp_bfmstream_finish": (ctypes.c_int, [_P, _P, _P, _P]),
     "vp_bfmstream_tensor": (ctypes.c_int, [_P, ctypes.c_char_p, ctypes.POINTER(_P), ctypes.POINTER(ctypes.c_int64)]),
+    "vp_bfmstream_group_desc_size": (ctypes.c_size_t, []),
+    "vp_bfmstream_group_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(BfmStreamGroupDesc)]),
+    "vp_bfmstream_group_plan_info": (ctypes.c_int, [ctypes.POINTER(BfmStreamGroupDesc), ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
+    "vp_bfmstream_group_create": (ctypes.c_int, [ctypes.POINTER(BfmStreamGroupDesc), _P, ctypes.c_size_t, _P, _P, ctypes.POINTER(_P)]),
+    "vp_bfmstream_group_destroy": (None, [_P]),
+    "vp_bfmstream_group_params_changed": (ctypes.c_int, [_P]),
+    "vp_bfmstream_group_reset_slot": (ctypes.c_int, [_P, ctypes.c_int, _P]),
+    "vp_bfmstream_group_ready": (ctypes.c_longlong, [_P, ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
+    "vp_bfmstream_group_push": (ctypes.c_int, [_P, _P, ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_int), _P, _P, _P]),
+    "vp_bfmstream_group_tensor": (ctypes.c_int, [_P, ctypes.c_char_p, ctypes.POINTER(_P), ctypes.POINTER(ctypes.c_int64)]),
     "vp_gru_seq_state": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P]),
     "vp_maxpool2x2_fwd": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P]),
     "vp_maxpool2x2_bwd": (ctypes.c_int, [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P]),
@@ -227,6 +245,10 @@ def lib():
       want = int(l.vp_bfmstream_desc_size())
       if want != ctypes.sizeof(BfmStreamDesc):
         raise RuntimeError("%s: vp_bfmstream_desc is %d bytes in the library, %d in this binding" % (LIB_PATH, want, ctypes.sizeof(BfmStreamDesc)))
+    if hasattr(l, "vp_bfmstream_group_desc_size") and l.vp_bfmstream_group_desc_size.argtypes is not None:
+      want = int(l.vp_bfmstream_group_desc_size())
+      if want != ctypes.sizeof(BfmStreamGroupDesc):
+        raise RuntimeError("%s: vp_bfmstream_group_desc is %d bytes in the library, %d in this binding" % (LIB_PATH, want, ctypes.sizeof(BfmStreamGroupDesc)))
     _lib = l
   return _lib
 

@@ -27,5 +27,28 @@ hipError_t launch_gru_state(const float* xg, const float* xc, const float* whg, 
 // rows [r0, r0 + rows) of a mel ring buffer [cap][nmel] -> out [rows][nmel], rows >= avail zero
 hipError_t launch_mel_window(const float* ring, int cap, int nmel, long long r0, int rows, long long avail, float* out, hipStream_t st);
 hipError_t launch_add_ears(float* out, const float* ears, int n, hipStream_t st);
+// Streaming groups (vp_bfmstream_group, plan_bfmnet.hip).  The per-launch tables travel BY VALUE as kernel arguments (a push never waits
+// on the device, so there is no host buffer whose reuse would need a fence): at most kGroupMaxSlots entries (<= 4 KB of arguments).
+constexpr int kGroupMaxSlots = 128;
+constexpr int kGroupCarry = 512;      // floats per carry buffer (the carried samples of a stream are fewer than one 512-sample frame)
+// one stream's log-mel piece: carry[slot][cur][0, carry_n) ++ (zeros ? 0 : pcm[pcm_off ..]), F * hop + keep samples, staged in row e
+// of stage [entries][stage_len] -> logmel512_kernel -> frames [entries][max_frames][nmel] -> F frames at ring rows ring_row .. (mod cap)
+// of ring[slot]; the `keep` samples from F * hop on -> carry[slot][cur ^ 1].  Three launches; max_samples: the longest piece
+struct LmGroupEntry { int pcm_off, ring_row; short slot, carry_n, F, keep; unsigned char cur, zeros; };
+struct LmGroupTable { LmGroupEntry e[kGroupMaxSlots]; };
+hipError_t launch_logmel512_group(const float* pcm, float* carry, float* stage, int stage_len, float* frames, float* ring, int cap, const float* window,
+                                  const float* w256, const float* w512, const float* mel, int nmel, int hop, const LmGroupTable& tab, int nentries,
+                                  int max_frames, int max_samples, hipStream_t st);
+// window rows of one active stream: ring[slot] rows r0 (mod cap) .., the first `valid` received
+struct WinGroupEntry { int slot, r0, valid; };
+struct WinGroupTable { WinGroupEntry e[kGroupMaxSlots]; };
+hipError_t launch_mel_window_group(const float* ring, int cap, int nmel, int rows, int A, int B, const WinGroupTable& tab, float* out, hipStream_t st);
+// the emitted rows [t0, t0 + n) of one active stream's window; row: where they go in the packed output
+struct RowsGroupEntry { int slot, t0, n, row; };
+struct RowsGroupTable { RowsGroupEntry e[kGroupMaxSlots]; };
+hipError_t launch_gru_state_group(const float* xg, const float* xc, const float* whg, const float* whc, float* hstate, float* out, int T, const RowsGroupTable& tab,
+                                  int A, hipStream_t st);
+hipError_t launch_rows_scatter_group(const float* src, int T, float* dst, const RowsGroupTable& tab, int A, int max_rows, hipStream_t st);
+
 hipError_t launch_mul_inplace(float* x, const float* m, size_t n, hipStream_t st);
 }  // namespace vp

@@ -417,6 +417,82 @@ __global__ __launch_bounds__(256) void mel_window_kernel(const float* __restrict
   }
 }
 
+// The same frames for a group of independent streams (vp_bfmstream_group), in three launches around an UNCHANGED logmel512_kernel:
+// entry e of the table is one stream's piece - its carry_n carried samples (carry[slot][cur]) followed by its new samples (pcm +
+// pcm_off, or zeros), F * hop + keep samples in all.
+//   logmel512_stage_group_kernel   piece e -> row e of a staging matrix [entries][stage_len]
+//   logmel512_kernel               batch = entries, L = stage_len, F = the most frames of an entry -> frames [entries][F][nmel]
+//   mel_scatter_group_kernel       frame f < F_e of entry e -> row (ring_row + f) % cap of ring[slot]; the `keep` samples after the
+//                                  last frame's hop -> carry[slot][cur ^ 1]
+// Every frame is logmel512_kernel's computation on the same 512 samples, so the mel rows are the single session's bits.  (Frames
+// f >= F_e of a shorter piece read stale staging samples and are discarded.)
+__global__ __launch_bounds__(256) void logmel512_stage_group_kernel(const float* __restrict__ pcm, const float* __restrict__ carry, float* __restrict__ stage,
+                                                                    int stage_len, int hop, const LmGroupTable tab) {
+  const LmGroupEntry e = tab.e[blockIdx.y];
+  const float* cin = carry + ((size_t)e.slot * 2 + e.cur) * kGroupCarry;
+  const float* src = e.zeros ? nullptr : pcm + e.pcm_off;
+  float* st = stage + (size_t)blockIdx.y * stage_len;
+  const int n = hop * e.F + e.keep;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256)
+    st[i] = i < e.carry_n ? cin[i] : (src ? src[i - e.carry_n] : 0.f);
+}
+
+__global__ __launch_bounds__(256) void mel_scatter_group_kernel(const float* __restrict__ frames, int F, const float* __restrict__ stage, int stage_len,
+                                                                float* __restrict__ carry, float* __restrict__ ring, int cap, int nmel, int hop,
+                                                                const LmGroupTable tab) {
+  const LmGroupEntry e = tab.e[blockIdx.y];
+  if (blockIdx.x == 0) {
+    const float* st = stage + (size_t)blockIdx.y * stage_len + (size_t)hop * e.F;
+    float* cout = carry + ((size_t)e.slot * 2 + (e.cur ^ 1)) * kGroupCarry;
+    for (int i = threadIdx.x; i < e.keep; i += 256) cout[i] = st[i];
+  }
+  const float* src = frames + (size_t)blockIdx.y * F * nmel;
+  float* r = ring + (size_t)e.slot * cap * nmel;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < e.F * nmel; i += gridDim.x * 256)
+    r[(size_t)((e.ring_row + i / nmel) % cap) * nmel + i % nmel] = src[i];
+}
+
+// Streaming groups (vp_bfmstream_group): the window gather, the stateful GRU and the output copy for A active streams at once; entry b
+// of the table is the stream in batch row b of the bucket plan.
+// out [B][rows][nmel]: batch row b < A = rows ring[slot][r0 + r (mod cap)] for r < valid, zero after (mel_window_kernel per stream);
+// rows b >= A (the bucket's padding) are zero.
+__global__ __launch_bounds__(256) void mel_window_group_kernel(const float* __restrict__ ring, int cap, int nmel, int rows, int A, int B,
+                                                               const WinGroupTable tab, float* __restrict__ out) {
+  const size_t per = (size_t)rows * nmel, n = (size_t)B * per;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+    const int b = (int)(i / per);
+    const int r = (int)((i % per) / nmel);
+    float v = 0.f;
+    if (b < A) {
+      const WinGroupEntry e = tab.e[b];
+      if (r < e.valid) v = ring[((size_t)e.slot * cap + (size_t)((e.r0 + r) % cap)) * nmel + i % nmel];
+    }
+    out[i] = v;
+  }
+}
+
+// gru_fwd_state_kernel with a table: block b runs rows [t0, t0 + n) of batch row b's T rows from state hstate[slot]
+__global__ __launch_bounds__(1024) void gru_state_group_kernel(const float* __restrict__ xg, const float* __restrict__ xc, const float* __restrict__ whg,
+                                                               const float* __restrict__ whc, float* __restrict__ hstate, float* __restrict__ out, int T,
+                                                               const RowsGroupTable tab) {
+  __shared__ float h[256], rh[256], part[1024];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const RowsGroupEntry e = tab.e[b];
+  if (tid < 256) h[tid] = hstate[(size_t)e.slot * 256 + tid];
+  __syncthreads();
+  for (int t = e.t0; t < e.t0 + e.n; ++t)
+    gru_step<false>(xg, xc, whg, whc, out, nullptr, nullptr, nullptr, nullptr, (size_t)b * T + t, tid, h, rh, part);
+  if (tid < 256) hstate[(size_t)e.slot * 256 + tid] = h[tid];
+}
+
+// rows [t0, t0 + n) of batch row b of src [B][T][64] -> dst rows [row, row + n) (a copy: the decoder's bits)
+__global__ __launch_bounds__(256) void rows_scatter_group_kernel(const float* __restrict__ src, int T, float* __restrict__ dst, const RowsGroupTable tab) {
+  const RowsGroupEntry e = tab.e[blockIdx.y];
+  const float* s = src + ((size_t)blockIdx.y * T + e.t0) * 64;
+  float* d = dst + (size_t)e.row * 64;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < e.n * 64; i += gridDim.x * 256) d[i] = s[i];
+}
+
 // x *= m, element-wise (the opt-in decoder dropout masks of BFMNet inference: 0 or 1 / keep_prob)
 __global__ void mul_inplace_kernel(float* __restrict__ x, const float* __restrict__ m, size_t n) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -505,6 +581,36 @@ hipError_t launch_gru_state(const float* xg, const float* xc, const float* whg, 
 }
 hipError_t launch_mel_window(const float* ring, int cap, int nmel, long long r0, int rows, long long avail, float* out, hipStream_t st) {
   hipLaunchKernelGGL(mel_window_kernel, dim3(nblk((size_t)rows * nmel, 256)), dim3(256), 0, st, ring, cap, nmel, r0, rows, avail, out);
+  return hipGetLastError();
+}
+hipError_t launch_logmel512_group(const float* pcm, float* carry, float* stage, int stage_len, float* frames, float* ring, int cap, const float* window,
+                                  const float* w256, const float* w512, const float* mel, int nmel, int hop, const LmGroupTable& tab, int nentries,
+                                  int max_frames, int max_samples, hipStream_t st) {
+  if (nentries < 1 || nentries > kGroupMaxSlots || max_samples > stage_len || (max_frames > 0 && (max_frames - 1) * hop + 512 > stage_len))
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(logmel512_stage_group_kernel, dim3(nblk((size_t)max_samples, 64), nentries), dim3(256), 0, st, pcm, carry, stage, stage_len, hop, tab);
+  if (max_frames > 0) {
+    hipError_t e = launch_logmel512(stage, window, w256, w512, mel, frames, nentries, stage_len, max_frames, hop, nmel, st);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(mel_scatter_group_kernel, dim3(nblk((size_t)max_frames * nmel, 64), nentries), dim3(256), 0, st, frames, max_frames, stage, stage_len,
+                     carry, ring, cap, nmel, hop, tab);
+  return hipGetLastError();
+}
+hipError_t launch_mel_window_group(const float* ring, int cap, int nmel, int rows, int A, int B, const WinGroupTable& tab, float* out, hipStream_t st) {
+  if (A < 1 || A > B || A > kGroupMaxSlots) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(mel_window_group_kernel, dim3(nblk((size_t)B * rows * nmel, 1024)), dim3(256), 0, st, ring, cap, nmel, rows, A, B, tab, out);
+  return hipGetLastError();
+}
+hipError_t launch_gru_state_group(const float* xg, const float* xc, const float* whg, const float* whc, float* hstate, float* out, int T, const RowsGroupTable& tab,
+                                  int A, hipStream_t st) {
+  if (A < 1 || A > kGroupMaxSlots) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(gru_state_group_kernel, dim3(A), dim3(1024), 0, st, xg, xc, whg, whc, hstate, out, T, tab);
+  return hipGetLastError();
+}
+hipError_t launch_rows_scatter_group(const float* src, int T, float* dst, const RowsGroupTable& tab, int A, int max_rows, hipStream_t st) {
+  if (A < 1 || A > kGroupMaxSlots) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(rows_scatter_group_kernel, dim3(nblk((size_t)max_rows * 64, 64), A), dim3(256), 0, st, src, T, dst, tab);
   return hipGetLastError();
 }
 hipError_t launch_mul_inplace(float* x, const float* m, size_t n, hipStream_t st) {

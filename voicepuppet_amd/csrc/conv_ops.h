@@ -99,7 +99,12 @@ struct IgemmPlan {
   size_t partial_bytes;
 };
 
-inline void finish_igemm(IgemmPlan& p, int rows, int is_bf16) {
+// A plan that must reduce every output row exactly as another plan of the same layer does, whatever its own pixel count (the batch
+// buckets of a streaming group against the one-stream window plan, plan_bfmnet.hip): the tile - which fixes the K order inside a block
+// - and the K split are the other plan's instead of the choices for this plan's grid.
+struct IgemmPin { int cfg, splitk; };
+
+inline void finish_igemm(IgemmPlan& p, int rows, int is_bf16, const IgemmPin* pin = nullptr) {
   IgemmArgs& a = p.a;
   const int P = a.N * a.Hg * a.Wg;
   a.Kpad = round_up(a.ntaps * a.Cin, kc_elems(is_bf16));
@@ -111,13 +116,14 @@ inline void finish_igemm(IgemmPlan& p, int rows, int is_bf16) {
     const long long b128 = (long long)((P + 127) / 128) * (rows / 128), b64 = 2 * b128;
     if (((b64 + 255) / 256) * 64 < ((b128 + 255) / 256) * 128) p.cfg = 1;
   }
+  if (pin) p.cfg = pin->cfg;
   int bc, bp;
   igemm_tile(p.cfg, &bc, &bp);
   a.CoutPad = round_up(rows, bc);
   if (a.ntaps == 1) { a.log2Cin = 30; a.cin_mask = 0x3fffffff; }   // 1x1: any channel count
   else { a.log2Cin = ilog2(a.Cin); a.cin_mask = a.Cin - 1; }
   const int blocks = ((P + bp - 1) / bp) * (a.CoutPad / bc) * a.nclass;
-  a.splitk = pick_igemm_splitk(blocks, a.Kpad / kc_elems(is_bf16));
+  a.splitk = pin ? pin->splitk : pick_igemm_splitk(blocks, a.Kpad / kc_elems(is_bf16));
   p.partial_bytes = a.splitk > 1 ? (size_t)a.nclass * a.splitk * P * a.CoutPad * sizeof(float) : 0;
   // row permutation inside 64-row blocks (IgemmArgs::rowperm) where the tile's waves own whole 64-row blocks
   {
@@ -393,8 +399,8 @@ inline void plan_kernel(IgemmPlan& p, int rows, int is_bf16, int c0, int c1, uns
   p.a.kern = pick_conv_kernel(launch_view(p, f), is_bf16);
 }
 
-// x (PixSrc, total channels g.Cin) -> y [N,Hout,Wout,ldY]
-inline IgemmPlan plan_fwd(const ConvGeomX& g, size_t w_off, int is_bf16) {
+// x (PixSrc, total channels g.Cin) -> y [N,Hout,Wout,ldY]; pin: see IgemmPin (null for every plan but a streaming group's)
+inline IgemmPlan plan_fwd(const ConvGeomX& g, size_t w_off, int is_bf16, const IgemmPin* pin = nullptr) {
   IgemmPlan p;
   memset(&p, 0, sizeof(p));
   IgemmArgs& a = p.a;
@@ -426,7 +432,7 @@ inline IgemmPlan plan_fwd(const ConvGeomX& g, size_t w_off, int is_bf16) {
     d.s_kh = 4 * g.Cout * g.Cin_real; d.s_kw = g.Cout * g.Cin_real; d.s_row = g.Cin_real; d.s_ch = 1;
   }
   d.nclass = a.nclass; d.ntaps = a.ntaps;
-  finish_igemm(p, g.Cout, is_bf16);
+  finish_igemm(p, g.Cout, is_bf16, pin);
   return p;
 }
 

@@ -281,14 +281,16 @@ struct vp_bfmnet {
   bool dirty;
   int T5, Wm[6];
   const float *drop0, *drop1;   // opt-in: the reference's unconditional decoder dropout (bfmnet.py:114,116) as explicit masks
+  const vp_bfmnet* like;        // streaming-group bucket plans: every GEMM reduces its rows as this plan's does (IgemmPin); null otherwise
 };
 
 namespace {
 
-void plan_gemm(vp_bfmnet* h, Gemm& g, int pixels, int cin, int cout, int which, size_t w_src, int src_ld, size_t bias, int bf = 0) {
+void plan_gemm(vp_bfmnet* h, Gemm& g, int pixels, int cin, int cout, int which, size_t w_src, int src_ld, size_t bias, int bf = 0, const Gemm* like = nullptr) {
   g.cin = cin; g.cout = cout; g.which = which; g.w_src = w_src; g.src_ld = src_ld; g.bias = bias; g.bf = bf;
   ConvGeomX geo = make_geom(0, 1, 1, 0, 1, pixels, 1, cin, cin, cout);
-  g.plan = plan_fwd(geo, w_src, bf);
+  const IgemmPin pin = like ? IgemmPin{like->plan.cfg, like->plan.a.splitk} : IgemmPin{};
+  g.plan = plan_fwd(geo, w_src, bf, like ? &pin : nullptr);
   g.plan.pack.s_ch = src_ld;      // row stride of the [cin, cout] source matrix (HWIO with H = W = 1)
   g.pk = h->packed_elems;         // (bytes: the arena mixes bf16 and f32 blocks; every block is packed relative to its own base)
   g.plan.pack.dst_off = 0;
@@ -307,28 +309,31 @@ size_t bfm_carve(vp_bfmnet* h, char* base) {
   size_t max_net = 0, max_exp = 0;
   const int tb = h->d.trunk_dtype == VP_BF16 ? 1 : 0;      // MfccNet activations / 1x1-conv operands in bf16 (f32 accumulation)
   const size_t tes = tb ? 2 : 4;
-  for (Block& b : m.blocks) {
+  const BfmModel* lm = h->like ? &h->like->m : nullptr;     // (same layer table: the i-th GEMM of both plans is the same layer)
+  for (size_t bi = 0; bi < m.blocks.size(); ++bi) {
+    Block& b = m.blocks[bi];
+    const Block* lb = lm ? &lm->blocks[bi] : nullptr;
     const int P = B * h->T5 * W;
-    plan_gemm(h, b.g_expand, P, b.cin, b.cexp, 0, b.expand.wf, b.cexp, b.expand.bf, tb);
-    plan_gemm(h, b.g_project, P, b.cexp, b.cout, 0, b.project.wf, b.cout, b.project.bf, tb);
+    plan_gemm(h, b.g_expand, P, b.cin, b.cexp, 0, b.expand.wf, b.cexp, b.expand.bf, tb, lb ? &lb->g_expand : nullptr);
+    plan_gemm(h, b.g_project, P, b.cexp, b.cout, 0, b.project.wf, b.cout, b.project.bf, tb, lb ? &lb->g_project : nullptr);
     // (the fused kernel addresses the expanded tensor with 32-bit lane offsets - launch_dwproj refuses 0xF0000000 bytes and more: very long
     // clips fall back to the depthwise kernel + the GEMM here, at plan time, instead of failing at run time: ADVICE r5)
     b.fusable = !tb && dwproj_eligible(W, b.cexp, b.cout) && (size_t)P * b.cexp * sizeof(float) < 0xF0000000ull;
     if (b.fusable) { b.g_project.plan.pack.perm = 0; b.g_project.plan.a.rowperm = 0; }     // (the fused kernel reads plain packed rows; the GEMM kernels take either)
-    if (b.shortcut) plan_gemm(h, b.g_sc, P, b.cin, b.cout, 0, b.sc.wf, b.cout, b.sc.bf, tb);
+    if (b.shortcut) plan_gemm(h, b.g_sc, P, b.cin, b.cout, 0, b.sc.wf, b.cout, b.sc.bf, tb, lb ? &lb->g_sc : nullptr);
     if ((size_t)P * b.cexp > max_exp) max_exp = (size_t)P * b.cexp;
     if ((size_t)P * (b.cin > b.cout ? b.cin : b.cout) > max_net) max_net = (size_t)P * (b.cin > b.cout ? b.cin : b.cout);
     if (b.pool) W = (W + 1) / 2;
   }
-  plan_gemm(h, m.g_last, B * h->T5 * W, 256, 256, 0, m.last.wf, 256, m.last.bf, tb);
+  plan_gemm(h, m.g_last, B * h->T5 * W, 256, 256, 0, m.last.wf, 256, m.last.bf, tb, lm ? &lm->g_last : nullptr);
   const int BT = B * T;
-  plan_gemm(h, m.g_enc, BT, 256, 256, 1, m.enc_w, 256, m.enc_b);
-  plan_gemm(h, m.g_rnn, BT, 256, 256, 1, m.rnn_w, 256, m.rnn_b);
-  plan_gemm(h, m.g_xg, BT, 256, 512, 1, m.gk, 512, m.gb);       // rows 0..255 of the [512,512] gate kernel (the x part)
-  plan_gemm(h, m.g_xc, BT, 256, 256, 1, m.ck, 256, m.cb);
-  plan_gemm(h, m.g_d0, BT, 256, 128, 1, m.d0w, 128, m.d0b);
-  plan_gemm(h, m.g_d1, BT, 128, 64, 1, m.d1w, 64, m.d1b);
-  plan_gemm(h, m.g_d2, BT, 64, 64, 1, m.d2w, 64, m.d2b);
+  plan_gemm(h, m.g_enc, BT, 256, 256, 1, m.enc_w, 256, m.enc_b, 0, lm ? &lm->g_enc : nullptr);
+  plan_gemm(h, m.g_rnn, BT, 256, 256, 1, m.rnn_w, 256, m.rnn_b, 0, lm ? &lm->g_rnn : nullptr);
+  plan_gemm(h, m.g_xg, BT, 256, 512, 1, m.gk, 512, m.gb, 0, lm ? &lm->g_xg : nullptr);       // rows 0..255 of the [512,512] gate kernel (the x part)
+  plan_gemm(h, m.g_xc, BT, 256, 256, 1, m.ck, 256, m.cb, 0, lm ? &lm->g_xc : nullptr);
+  plan_gemm(h, m.g_d0, BT, 256, 128, 1, m.d0w, 128, m.d0b, 0, lm ? &lm->g_d0 : nullptr);
+  plan_gemm(h, m.g_d1, BT, 128, 64, 1, m.d1w, 64, m.d1b, 0, lm ? &lm->g_d1 : nullptr);
+  plan_gemm(h, m.g_d2, BT, 64, 64, 1, m.d2w, 64, m.d2b, 0, lm ? &lm->g_d2 : nullptr);
   h->folded = (float*)ar.alloc(m.nfolded * sizeof(float));
   h->packed = (char*)ar.alloc(h->packed_elems);
   h->n0 = (float*)ar.alloc(max_net * sizeof(float));      // the residual stream stays f32 in both modes
@@ -892,6 +897,453 @@ int vp_bfmstream_tensor(vp_bfmstream_t* h, const char* name, void** ptr, int64_t
   if (std::string(name) != "mel") return VP_ERR_ARG;
   *ptr = h->ring;
   if (shape) { shape[0] = h->g.cap; shape[1] = h->d.num_mel_bins; shape[2] = 1; shape[3] = 1; }
+  return VP_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------
+// Streaming groups (include/vp_hip.h, vp_bfmstream_group_*): S independent vp_bfmstream sessions ("slots") behind one handle, advanced
+// together.  A group push runs, per round, ONE launch chain for all the slots that take part in it:
+//   pieces:  the slots' next pieces of samples (the single session's piece sizes) -> a staging matrix -> logmel512_kernel (unchanged,
+//            batch = the pieces) -> mel_scatter_group_kernel -> each slot's mel ring
+//   windows: the slots with frames ready, compacted to batch rows 0..A-1 -> mel_window_group_kernel -> bfm_trunk on the bucket plan of
+//            batch >= A (1, 2, 4, .., S) -> gru_state_group_kernel (each slot's state) -> bfm_decode -> rows_scatter_group_kernel
+// Every slot's sequence of pieces and windows is the one its own vp_bfmstream would run for the same pushes, and every kernel of the
+// chain computes a batch row as the one-stream window plan computes its one row: the bucket plans pin each GEMM's tile and K split to
+// the batch-1 plan's (IgemmPin), the stem, depthwise, depthwise + projection and pooling kernels are per pixel.  So each slot's
+// coefficients are bit-identical to a vp_bfmstream fed the same chunks.  A slot that finishes a clip shorter than T_win runs its
+// remaining frames alone on an exact-size plan (as vp_bfmstream does), one slot after the other.
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+struct GroupSlot { int cur, carry; long long samples, mel_done, emitted; bool finished; };
+
+bool group_ok(const vp_bfmstream_group_desc* d, vp_bfmstream_desc* sd) {
+  if (!d || d->struct_bytes != (int)sizeof(vp_bfmstream_group_desc) || d->slots < 1 || d->slots > kGroupMaxSlots) return false;
+  *sd = vp_bfmstream_desc{(int)sizeof(vp_bfmstream_desc), d->max_chunk_frames, d->num_mel_bins, d->trunk_dtype, d->sample_rate, d->lower_hz, d->upper_hz};
+  return stream_ok(sd);
+}
+
+std::vector<int> group_buckets(int S) {
+  std::vector<int> b;
+  for (int x = 1; x < S; x *= 2) b.push_back(x);
+  b.push_back(S);
+  return b;
+}
+
+void model_gemms(const BfmModel& m, std::vector<const Gemm*>& v) {
+  for (const Block& b : m.blocks) {
+    v.push_back(&b.g_expand); v.push_back(&b.g_project);
+    if (b.shortcut) v.push_back(&b.g_sc);
+  }
+  for (const Gemm* g : {&m.g_last, &m.g_enc, &m.g_rnn, &m.g_xg, &m.g_xc, &m.g_d0, &m.g_d1, &m.g_d2}) v.push_back(g);
+}
+
+// the bucket plans (not carved yet) and the bytes of their shared region.  Refuses (VP_ERR_ARG) a group whose larger buckets would leave
+// the batch-1 plan's kernels: the depthwise + projection kernel's and the GEMM loader's 32-bit lane offsets (bfm_dwproj.hip, conv_kernels.hip)
+int group_plans(const vp_bfmstream_desc& sd, int S, const StreamGeo& g, std::vector<vp_bfmnet*>& plans, size_t* bytes) {
+  *bytes = 0;
+  for (int B : group_buckets(S)) {
+    vp_bfmnet* p = new vp_bfmnet{};
+    p->d = vp_bfmnet_desc{B, g.Tw, sd.num_mel_bins, sd.trunk_dtype};
+    build_model(p->m);
+    p->like = plans.empty() ? nullptr : plans[0];
+    const size_t n = bfm_carve(p, nullptr);
+    plans.push_back(p);
+    if (n > *bytes) *bytes = n;
+    const vp_bfmnet* r = plans[0];
+    std::vector<const Gemm*> ga, gr;
+    model_gemms(p->m, ga);
+    model_gemms(r->m, gr);
+    // the lane-offset limits first (a larger batch outgrowing them is the expected way to fail), then anything else that would make a
+    // bucket run other kernels or another weight image than the batch-1 plan, named
+    const char* lim = nullptr;
+    int at = -1;
+    auto big = [](const Gemm* x) { const IgemmArgs& a = x->plan.a; return (size_t)a.N * a.Hin * a.Win * a.Cin * (x->bf ? 2 : 4) >= 0x70000000ull; };
+    for (size_t i = 0; !lim && i < ga.size() && i < gr.size(); ++i)
+      if (big(ga[i]) != big(gr[i])) { lim = "the implicit-GEMM loader"; at = (int)i; }
+    for (size_t i = 0; !lim && i < p->m.blocks.size(); ++i)
+      if (p->m.blocks[i].fusable != r->m.blocks[i].fusable) { lim = "launch_dwproj"; at = (int)i; }
+    if (lim) {
+      set_err("vp_bfmstream_group: %d slots of %d-frame windows need a batch-%d plan whose tensors exceed the 32-bit lane offsets of %s "
+              "(%s %d); use fewer slots or a smaller max_chunk_frames", S, g.Tw, B, lim, lim[0] == 'l' ? "block" : "GEMM", at);
+      return VP_ERR_ARG;
+    }
+    const char* what = p->packed_elems != r->packed_elems || ga.size() != gr.size() ? "packed weight image" : nullptr;
+    for (size_t i = 0; !what && i < ga.size(); ++i) {
+      const IgemmPlan &a = ga[i]->plan, &b = gr[i]->plan;
+      at = (int)i;
+      if (a.cfg != b.cfg) what = "tile";
+      else if (a.a.splitk != b.a.splitk) what = "K split";
+      else if (a.a.kern != b.a.kern) what = "kernel";
+      else if (ga[i]->pk != gr[i]->pk || memcmp(&a.pack, &b.pack, sizeof(PackDesc))) what = "weight packing";
+    }
+    if (what) {
+      set_err("vp_bfmstream_group: the batch-%d plan of %d slots x %d-frame windows differs from the batch-1 plan in the %s (GEMM %d): its "
+              "rows would not be the one-stream plan's", B, S, g.Tw, what, at);
+      return VP_ERR_ARG;
+    }
+  }
+  return VP_OK;
+}
+
+void free_plans(std::vector<vp_bfmnet*>& plans) {
+  for (vp_bfmnet* p : plans) delete p;
+  plans.clear();
+}
+
+}  // namespace
+
+struct vp_bfmstream_group {
+  vp_bfmstream_group_desc d;
+  vp_bfmstream_desc sd;            // one slot's session descriptor
+  StreamGeo g;
+  const float* params;
+  vp_logmel_t* lm;                 // constants of the log-mel kernel
+  std::vector<vp_bfmnet*> plans;   // bucket plans of batch 1, 2, 4, .., S: carved on ONE region (they run in stream order), so they also
+                                   // share one folded / packed weight image (same offsets, same packing: group_plans checks it)
+  vp_bfmnet* shrt;                 // exact-size plan of a clip shorter than T_win, carved at finish
+  char *lm_base, *plan_base, *short_base;
+  size_t lm_bytes, plan_bytes, short_bytes;
+  float *carry, *stage, *frames, *ring, *mwin, *hstate, *dout;   // [S][2][kGroupCarry], [S][stage_len], [S][piece][nmel], [S][cap][nmel],
+                                   // [S][5 T_win][nmel], [S][256], [S][T_win][64]
+  int stage_len;                   // kWin + kHop * piece: a piece with its carried samples
+  void* zeros;                     // the bucket plans' 256 zero bytes (their own `zeros` lie in the shared region, overwritten by others)
+  std::vector<GroupSlot> slot;
+  bool dirty;
+};
+
+static size_t group_carve(vp_bfmstream_group* G, char* base, vp_logmel_desc* lmd) {
+  Bump ar{base, 0};
+  const StreamGeo& g = G->g;
+  const size_t S = G->d.slots, nmel = G->d.num_mel_bins;
+  G->carry = (float*)ar.alloc(S * 2 * kGroupCarry * 4);
+  G->stage_len = kWin + kHop * g.piece;
+  G->stage = (float*)ar.alloc(S * G->stage_len * 4);
+  G->frames = (float*)ar.alloc(S * g.piece * nmel * 4);
+  G->ring = (float*)ar.alloc(S * g.cap * nmel * 4);
+  G->mwin = (float*)ar.alloc(S * kMelPerFrame * g.Tw * nmel * 4);
+  G->hstate = (float*)ar.alloc(S * 256 * 4);
+  G->dout = (float*)ar.alloc(S * g.Tw * 64 * 4);
+  G->zeros = ar.alloc(256);
+  *lmd = vp_logmel_desc{G->d.sample_rate, G->d.num_mel_bins, kWin, kHop, kWin, G->d.lower_hz, G->d.upper_hz, 1, kWin};
+  G->lm_bytes = vp_logmel_workspace_bytes(lmd);
+  G->lm_base = (char*)ar.alloc(G->lm_bytes);
+  G->plan_base = (char*)ar.alloc(G->plan_bytes);
+  vp_bfmnet tmp{};
+  tmp.d = vp_bfmnet_desc{1, g.Tw, G->d.num_mel_bins, G->d.trunk_dtype};
+  build_model(tmp.m);
+  size_t sb = 0;
+  for (int t = 1; t < g.Tw; ++t) { const size_t b = bfm_plan_bytes(&tmp, t); if (b > sb) sb = b; }
+  G->short_bytes = sb;
+  G->short_base = (char*)ar.alloc(sb);
+  return ar.off + 256;
+}
+
+// the layout of a descriptor's group (plans made, nothing carved on memory); VP_ERR_ARG with the reason on a refused descriptor
+static int group_layout(vp_bfmstream_group* G, const vp_bfmstream_group_desc* d, size_t* bytes) {
+  if (!group_ok(d, &G->sd)) { set_err("vp_bfmstream_group: bad descriptor"); return VP_ERR_ARG; }
+  G->d = *d;
+  BfmModel m;
+  build_model(m);
+  G->g = stream_geo(&G->sd, m);
+  int rc;
+  if ((rc = group_plans(G->sd, d->slots, G->g, G->plans, &G->plan_bytes))) return rc;
+  vp_logmel_desc lmd;
+  *bytes = group_carve(G, nullptr, &lmd);
+  return VP_OK;
+}
+
+static int group_prepare(vp_bfmstream_group* G, hipStream_t st) {
+  if (!G->dirty) return VP_OK;
+  int rc;
+  if ((rc = prepare_weights(G->plans[0], st))) return rc;       // (the image every bucket plan reads)
+  for (vp_bfmnet* p : G->plans) p->dirty = false;
+  G->dirty = false;
+  return VP_OK;
+}
+
+// one piece for each slot in `who` (left[s] samples still to go, from pcm + pos[s], or zeros when pcm is null) -> mel rows; one launch
+static int group_pieces(vp_bfmstream_group* G, const float* pcm, std::vector<long long>& pos, std::vector<long long>& left, std::vector<int>& who,
+                        hipStream_t st) {
+  const long long most = (long long)kHop * G->g.piece;
+  LmGroupTable tab;
+  int ne = 0, maxF = 0, maxN = 0;
+  who.clear();
+  for (int s = 0; s < G->d.slots; ++s) {
+    if (left[s] <= 0) continue;
+    GroupSlot& z = G->slot[s];
+    const int q = (int)(left[s] < most ? left[s] : most);
+    const int ls = z.carry + q;
+    const int F = ls >= kWin ? (ls - kWin) / kHop + 1 : 0;
+    LmGroupEntry& e = tab.e[ne++];
+    e.pcm_off = pcm ? (int)pos[s] : 0;
+    e.ring_row = (int)(z.mel_done % G->g.cap);
+    e.slot = (short)s; e.carry_n = (short)z.carry; e.F = (short)F; e.keep = (short)(ls - kHop * F);
+    e.cur = (unsigned char)z.cur; e.zeros = pcm ? 0 : 1;
+    if (F > maxF) maxF = F;
+    if (ls > maxN) maxN = ls;
+    z.mel_done += F; z.carry = ls - kHop * F; z.cur ^= 1; z.samples += q;
+    pos[s] += q; left[s] -= q;
+    who.push_back(s);
+  }
+  if (!ne) return VP_OK;
+  const vp_logmel* lm = G->lm;
+  VP_HIP_CHECK(launch_logmel512_group(pcm, G->carry, G->stage, G->stage_len, G->frames, G->ring, G->g.cap, lm->window, lm->w256, lm->w512, lm->mel,
+                                      G->d.num_mel_bins, kHop, tab, ne, maxF, maxN, st));
+  return VP_OK;
+}
+
+// the frames of one slot whose finished clip is shorter than T_win: stream_window's exact-size path, alone
+static int group_short(vp_bfmstream_group* G, int s, long long target, float* out, std::vector<long long>& row, hipStream_t st) {
+  GroupSlot& z = G->slot[s];
+  const StreamGeo& g = G->g;
+  const long long pad = pad_len_of(z.samples);
+  const int nmel = G->d.num_mel_bins;
+  if (!G->shrt || G->shrt->d.frames != (int)pad) {
+    delete G->shrt;
+    G->shrt = new vp_bfmnet{};
+    G->shrt->d = vp_bfmnet_desc{1, (int)pad, G->d.num_mel_bins, G->d.trunk_dtype};
+    build_model(G->shrt->m);
+    if (bfm_carve(G->shrt, nullptr) > G->short_bytes) { set_err("vp_bfmstream_group: short plan outgrew its region"); return VP_ERR_STATE; }
+    bfm_carve(G->shrt, G->short_base);
+    G->shrt->params = G->params;
+    G->shrt->dirty = true;
+    VP_HIP_CHECK(hipMemsetAsync(G->shrt->zeros, 0, 256, st));
+  }
+  vp_bfmnet* p = G->shrt;
+  const int Tw = p->d.frames;
+  int rc;
+  while (z.emitted < target) {
+    const long long f0 = z.emitted;
+    const int n = (int)(target - f0 < G->d.max_chunk_frames ? target - f0 : G->d.max_chunk_frames);
+    long long w0 = f0 - g.Lf > 0 ? f0 - g.Lf : 0;
+    if (w0 + Tw > pad) w0 = pad - Tw > 0 ? pad - Tw : 0;
+    const int t0 = (int)(f0 - w0);
+    if (t0 < 0 || t0 + n > Tw) { set_err("vp_bfmstream_group: slot %d frames [%lld, %lld) outside window %lld + %d", s, f0, f0 + n, w0, Tw); return VP_ERR_STATE; }
+    VP_HIP_CHECK(launch_mel_window(G->ring + (size_t)s * g.cap * nmel, g.cap, nmel, (long long)kMelPerFrame * w0, kMelPerFrame * Tw, z.mel_done, G->mwin, st));
+    if ((rc = bfm_trunk(p, G->mwin, st))) return rc;
+    VP_HIP_CHECK(launch_gru_state(p->xg, p->xc, gru_whg(p), gru_whc(p), G->hstate + (size_t)s * 256, p->rnn, 1, Tw, t0, n, st));
+    if ((rc = bfm_decode(p, nullptr, G->dout, st))) return rc;
+    VP_HIP_CHECK(hipMemcpyAsync(out + row[s] * 64, G->dout + (size_t)t0 * 64, (size_t)n * 64 * 4, hipMemcpyDeviceToDevice, st));
+    z.emitted += n; row[s] += n;
+  }
+  return VP_OK;
+}
+
+// everything ready now for the slots in `who`, in rounds of at most max_chunk_frames per slot; out rows of slot s from row[s] on
+static int group_emit(vp_bfmstream_group* G, const std::vector<int>& who, bool fin, float* out, std::vector<long long>& row, hipStream_t st) {
+  const StreamGeo& g = G->g;
+  const int S = G->d.slots, Tw = g.Tw, nmel = G->d.num_mel_bins;
+  std::vector<long long> target(S, 0);
+  std::vector<int> live;
+  int rc;
+  for (int s : who) {
+    GroupSlot& z = G->slot[s];
+    target[s] = emitted_after(g, z.samples, fin);
+    if (z.emitted >= target[s]) continue;
+    if (fin && pad_len_of(z.samples) < Tw) { if ((rc = group_short(G, s, target[s], out, row, st))) return rc; }
+    else live.push_back(s);
+  }
+  const std::vector<int> buckets = group_buckets(S);
+  WinGroupTable win;
+  RowsGroupTable rows;
+  while (true) {
+    int A = 0, most = 0;
+    for (int s : live) {
+      GroupSlot& z = G->slot[s];
+      if (z.emitted >= target[s]) continue;
+      const long long f0 = z.emitted, pad = pad_len_of(z.samples);
+      const int n = (int)(target[s] - f0 < G->d.max_chunk_frames ? target[s] - f0 : G->d.max_chunk_frames);
+      long long w0 = f0 - g.Lf > 0 ? f0 - g.Lf : 0;
+      if (fin && w0 + Tw > pad) w0 = pad - Tw > 0 ? pad - Tw : 0;
+      const int t0 = (int)(f0 - w0);
+      if ((long long)kMelPerFrame * w0 < z.mel_done - g.cap) { set_err("vp_bfmstream_group: slot %d window %lld left the mel history", s, w0); return VP_ERR_STATE; }
+      if (t0 < 0 || t0 + n > Tw) { set_err("vp_bfmstream_group: slot %d frames [%lld, %lld) outside window %lld + %d", s, f0, f0 + n, w0, Tw); return VP_ERR_STATE; }
+      const long long r0 = (long long)kMelPerFrame * w0, got = z.mel_done - r0;
+      win.e[A] = WinGroupEntry{s, (int)(r0 % g.cap), (int)(got < 0 ? 0 : got > kMelPerFrame * Tw ? kMelPerFrame * Tw : got)};
+      rows.e[A] = RowsGroupEntry{s, t0, n, (int)row[s]};
+      if (n > most) most = n;
+      z.emitted += n; row[s] += n;
+      ++A;
+    }
+    if (!A) break;
+    size_t bi = 0;
+    while (buckets[bi] < A) ++bi;
+    vp_bfmnet* p = G->plans[bi];
+    VP_HIP_CHECK(launch_mel_window_group(G->ring, g.cap, nmel, kMelPerFrame * Tw, A, p->d.batch, win, G->mwin, st));
+    if ((rc = bfm_trunk(p, G->mwin, st))) return rc;
+    VP_HIP_CHECK(launch_gru_state_group(p->xg, p->xc, gru_whg(p), gru_whc(p), G->hstate, p->rnn, Tw, rows, A, st));
+    if ((rc = bfm_decode(p, nullptr, G->dout, st))) return rc;
+    VP_HIP_CHECK(launch_rows_scatter_group(G->dout, Tw, out, rows, A, most, st));
+  }
+  return VP_OK;
+}
+
+extern "C" {
+
+size_t vp_bfmstream_group_desc_size(void) { return sizeof(vp_bfmstream_group_desc); }
+
+size_t vp_bfmstream_group_workspace_bytes(const vp_bfmstream_group_desc* d) {
+  vp_bfmstream_group G{};
+  size_t n = 0;
+  const int rc = group_layout(&G, d, &n);
+  free_plans(G.plans);
+  return rc ? 0 : n;
+}
+
+int vp_bfmstream_group_plan_info(const vp_bfmstream_group_desc* d, int bucket, int gemm, int info[8]) {
+  vp_bfmstream_group G{};
+  size_t n = 0;
+  int rc = group_layout(&G, d, &n);
+  if (!rc) {
+    std::vector<const Gemm*> gs;
+    if (bucket < 0 || bucket >= (int)G.plans.size()) rc = VP_ERR_ARG;
+    else {
+      model_gemms(G.plans[bucket]->m, gs);
+      if (gemm < 0 || gemm >= (int)gs.size() || !info) rc = VP_ERR_ARG;
+      else {
+        const IgemmPlan& p = gs[gemm]->plan;
+        info[0] = G.plans[bucket]->d.batch; info[1] = p.cfg; info[2] = p.a.splitk; info[3] = p.a.kern;
+        info[4] = p.a.N * p.a.Hg * p.a.Wg; info[5] = gs[gemm]->cin; info[6] = gs[gemm]->cout; info[7] = gs[gemm]->bf;
+      }
+    }
+  }
+  free_plans(G.plans);
+  return rc;
+}
+
+int vp_bfmstream_group_create(const vp_bfmstream_group_desc* d, void* workspace, size_t bytes, const float* params, void* stream,
+                              vp_bfmstream_group_t** out) {
+  if (!workspace || !params || !out) { set_err("vp_bfmstream_group_create: null argument"); return VP_ERR_ARG; }
+  vp_bfmstream_group* G = new vp_bfmstream_group{};
+  size_t need = 0;
+  int rc;
+  if ((rc = group_layout(G, d, &need))) { vp_bfmstream_group_destroy(G); return rc; }
+  if (bytes < need) { vp_bfmstream_group_destroy(G); set_err("vp_bfmstream_group_create: workspace too small"); return VP_ERR_WORKSPACE; }
+  vp_logmel_desc lmd;
+  group_carve(G, (char*)workspace, &lmd);
+  G->params = params;
+  hipStream_t st = (hipStream_t)stream;
+  if ((rc = vp_logmel_create(&lmd, G->lm_base, G->lm_bytes, stream, &G->lm))) { vp_bfmstream_group_destroy(G); return rc; }
+  for (vp_bfmnet* p : G->plans) {
+    bfm_carve(p, G->plan_base);
+    p->params = params;
+    p->zeros = G->zeros;
+  }
+  G->dirty = true;
+  G->slot.assign(d->slots, GroupSlot{});
+  hipError_t e = hipMemsetAsync(G->zeros, 0, 256, st);
+  if (e == hipSuccess) e = hipMemsetAsync(G->hstate, 0, (size_t)d->slots * 256 * 4, st);
+  if (e != hipSuccess) { set_err("vp_bfmstream_group_create: %s", hipGetErrorString(e)); vp_bfmstream_group_destroy(G); return VP_ERR_HIP; }
+  *out = G;
+  return VP_OK;
+}
+
+void vp_bfmstream_group_destroy(vp_bfmstream_group_t* h) {
+  if (!h) return;
+  vp_logmel_destroy(h->lm);
+  free_plans(h->plans);
+  delete h->shrt;
+  delete h;
+}
+
+int vp_bfmstream_group_params_changed(vp_bfmstream_group_t* h) {
+  if (!h) return VP_ERR_ARG;
+  h->dirty = true;
+  if (h->shrt) h->shrt->dirty = true;
+  return VP_OK;
+}
+
+int vp_bfmstream_group_reset_slot(vp_bfmstream_group_t* h, int slot, void* stream) {
+  if (!h || slot < 0 || slot >= h->d.slots) { set_err("vp_bfmstream_group_reset_slot: bad handle or slot"); return VP_ERR_ARG; }
+  h->slot[slot] = GroupSlot{};
+  VP_HIP_CHECK(hipMemsetAsync(h->hstate + (size_t)slot * 256, 0, 256 * 4, (hipStream_t)stream));
+  return VP_OK;
+}
+
+long long vp_bfmstream_group_ready(const vp_bfmstream_group_t* h, const long long* n, const int* finish, int* k) {
+  if (!h || !n) return -1;
+  long long total = 0;
+  for (int s = 0; s < h->d.slots; ++s) {
+    const GroupSlot& z = h->slot[s];
+    const bool fin = finish && finish[s];
+    long long ks = 0;
+    if (n[s] < 0 || (z.finished && (n[s] > 0 || fin))) return -1;
+    if (!z.finished) ks = (fin ? pad_len_of(z.samples + n[s]) : emitted_after(h->g, z.samples + n[s], false)) - z.emitted;
+    if (k) k[s] = (int)ks;
+    total += ks;
+  }
+  return total;
+}
+
+int vp_bfmstream_group_push(vp_bfmstream_group_t* h, const float* pcm, const long long* n, const int* finish, const float* ears, float* coeff_out,
+                            void* stream) {
+  if (!h || !n) { set_err("vp_bfmstream_group_push: null handle / n"); return VP_ERR_ARG; }
+  const int S = h->d.slots;
+  long long total = 0;
+  for (int s = 0; s < S; ++s) {
+    if (n[s] < 0) { set_err("vp_bfmstream_group_push: n[%d] < 0", s); return VP_ERR_ARG; }
+    if (h->slot[s].finished && (n[s] > 0 || (finish && finish[s]))) {
+      set_err("vp_bfmstream_group_push: slot %d is finished (vp_bfmstream_group_reset_slot)", s);
+      return VP_ERR_STATE;
+    }
+    total += n[s];
+  }
+  if (total > 0 && !pcm) { set_err("vp_bfmstream_group_push: samples and no pcm"); return VP_ERR_ARG; }
+  if (total >= (1ll << 31)) { set_err("vp_bfmstream_group_push: %lld samples in one push (at most 2^31 - 1)", total); return VP_ERR_ARG; }
+  const long long K = vp_bfmstream_group_ready(h, n, finish, nullptr);
+  if (K > 0 && (!ears || !coeff_out)) { set_err("vp_bfmstream_group_push: frames are ready and ears / coeff_out is NULL"); return VP_ERR_ARG; }
+  hipStream_t st = (hipStream_t)stream;
+  int rc;
+  if ((rc = group_prepare(h, st))) return rc;
+  std::vector<long long> pos(S), left(S), row(S), clip(S);
+  std::vector<int> who;
+  {
+    std::vector<int> k(S);
+    vp_bfmstream_group_ready(h, n, finish, k.data());
+    long long p = 0, r = 0;
+    for (int s = 0; s < S; ++s) { pos[s] = p; p += n[s]; row[s] = r; r += k[s]; left[s] = n[s]; }
+  }
+  // the samples, piece by piece, emitting behind each piece (vp_bfmstream_push)
+  while (true) {
+    if ((rc = group_pieces(h, pcm, pos, left, who, st))) return rc;
+    if (who.empty()) break;
+    if ((rc = group_emit(h, who, false, coeff_out, row, st))) return rc;
+  }
+  // then the finishing slots: prepare_pcm's zero padding without emitting, then every pending frame by the finish rule (vp_bfmstream_finish)
+  std::vector<int> fin;
+  for (int s = 0; s < S; ++s) {
+    left[s] = 0;
+    if (!finish || !finish[s]) continue;
+    GroupSlot& z = h->slot[s];
+    clip[s] = z.samples;
+    left[s] = (long long)kHop * (kMelPerFrame * pad_len_of(z.samples) - 1) + kWin - z.samples;
+    fin.push_back(s);
+  }
+  if (!fin.empty()) {
+    while (true) {
+      if ((rc = group_pieces(h, nullptr, pos, left, who, st))) return rc;
+      if (who.empty()) break;
+    }
+    for (int s : fin) {
+      GroupSlot& z = h->slot[s];
+      z.samples = clip[s];
+      if (z.mel_done != (long long)kMelPerFrame * pad_len_of(z.samples)) { set_err("vp_bfmstream_group_push: slot %d: %lld mel frames", s, z.mel_done); return VP_ERR_STATE; }
+    }
+    if ((rc = group_emit(h, fin, true, coeff_out, row, st))) return rc;
+    for (int s : fin) h->slot[s].finished = true;
+  }
+  if (K > 0) VP_HIP_CHECK(launch_add_ears(coeff_out, ears, (int)K, st));
+  return VP_OK;
+}
+
+int vp_bfmstream_group_tensor(vp_bfmstream_group_t* h, const char* name, void** ptr, int64_t shape[4]) {
+  if (!h || !name || !ptr) return VP_ERR_ARG;
+  if (std::string(name) != "mel") return VP_ERR_ARG;
+  *ptr = h->ring;
+  if (shape) { shape[0] = h->d.slots; shape[1] = h->g.cap; shape[2] = h->d.num_mel_bins; shape[3] = 1; }
   return VP_OK;
 }
 

@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import BfmStreamDesc
+from ._lib import BfmStreamDesc, BfmStreamGroupDesc
 from .audio import bfmnet_manifest
 
 SAMPLES_PER_FRAME = 640          # 16 kHz / 25 frames per second (config/params.yml)
@@ -153,6 +153,139 @@ class AudioStream:
     try:
       if getattr(self, "h", None):
         self.L.vp_bfmstream_destroy(self.h)
+        self.h = None
+    except Exception:
+      pass
+
+
+def group_desc(slots, max_chunk_frames=1, dtype="f32", num_mel_bins=80, sample_rate=16000, lower_hz=80.0, upper_hz=7600.0):
+  return BfmStreamGroupDesc(ctypes.sizeof(BfmStreamGroupDesc), slots, max_chunk_frames, num_mel_bins,
+                            {"f32": _lib.VP_F32, "bf16": _lib.VP_BF16}[dtype], sample_rate, lower_hz, upper_hz)
+
+
+class AudioStreamGroup:
+  """`slots` independent AudioStream sessions behind one handle (libvp_hip.so: vp_bfmstream_group_*), for serving many talkers at once.
+
+  One push advances any subset of the slots by any number of samples each and runs one kernel chain per round for all of them.  Every
+  slot's coefficients are bit-identical to an AudioStream with the same max_chunk_frames and dtype fed the same chunks (finish: the
+  chunk, then AudioStream.finish).  ears: {slot: [k, 1]} per push, or None to draw np.random.rand(k, 1) / 100 per slot in slot order."""
+
+  def __init__(self, params=None, slots=1, max_chunk_frames=1, dtype="f32", num_mel_bins=80, sample_rate=16000, lower_hz=80.0, upper_hz=7600.0):
+    if not torch.cuda.is_available():
+      raise RuntimeError("AudioStreamGroup needs an MI355X (no CPU fallback)")
+    self.L = _lib.lib()
+    self.slots = int(slots)
+    self.desc = group_desc(self.slots, max_chunk_frames, dtype, num_mel_bins, sample_rate, lower_hz, upper_hz)
+    d = ctypes.byref(self.desc)
+    ws = self.L.vp_bfmstream_group_workspace_bytes(d)
+    if ws == 0:
+      raise ValueError("invalid stream group descriptor: " + self.L.vp_last_error().decode())
+    self.left_mel, self.right_mel, self.left_frames, self.right_frames, self.window_frames = stream_context(
+        stream_desc(max_chunk_frames, dtype, num_mel_bins, sample_rate, lower_hz, upper_hz))
+    self.manifest = bfmnet_manifest()
+    self.params = torch.zeros(self.L.vp_bfmnet_param_count(), dtype=torch.float32, device="cuda")
+    self.workspace = torch.zeros(ws, dtype=torch.uint8, device="cuda")
+    h = ctypes.c_void_p()
+    _lib.check(self.L.vp_bfmstream_group_create(d, _ptr(self.workspace), ws, _ptr(self.params), _stream(), ctypes.byref(h)),
+               "vp_bfmstream_group_create")
+    self.h = h
+    if params is not None:
+      self.load_params(load_bfmnet_params(params) if isinstance(params, str) else params)
+
+  @property
+  def lookahead_ms(self):
+    """As AudioStream.lookahead_ms (the same for every slot)."""
+    return 1000.0 * (self.right_mel * 128 + (512 - 128)) / self.desc.sample_rate
+
+  def load_params(self, params):
+    host = self.params.cpu().numpy()
+    for name, off, shape in self.manifest:
+      if name in params:
+        v = np.asarray(params[name], dtype=np.float32)
+        assert v.shape == shape, (name, v.shape, shape)
+        host[off:off + v.size] = v.reshape(-1)
+    self.params.copy_(torch.from_numpy(host))
+    _lib.check(self.L.vp_bfmstream_group_params_changed(self.h), "vp_bfmstream_group_params_changed")
+
+  def _arrays(self, n_by_slot, finish_by_slot):
+    n = (ctypes.c_longlong * self.slots)()
+    fin = (ctypes.c_int * self.slots)()
+    items = n_by_slot.items() if isinstance(n_by_slot, dict) else enumerate(n_by_slot or ())
+    for s, v in items:
+      n[int(s)] = int(v)
+    for s in finish_by_slot or ():
+      fin[int(s)] = 1
+    return n, fin
+
+  def ready(self, n_by_slot, finish_by_slot=()):
+    """Frames per slot (a list of `slots` counts) that a push of n_by_slot ({slot: samples} or a sequence) new samples emits, the slots
+    in finish_by_slot ending their clips after them.  Host only."""
+    n, fin = self._arrays(n_by_slot, finish_by_slot)
+    k = (ctypes.c_int * self.slots)()
+    if self.L.vp_bfmstream_group_ready(self.h, n, fin, k) < 0:
+      raise ValueError("bad ready query (negative count, or samples / finish for a finished slot)")
+    return list(k)
+
+  def push(self, pcm_by_slot, finish=(), ears=None):
+    """{slot: 1-D f32 pcm (numpy or tensor)} -> {slot: coefficients [k, 64]} for every slot pushed or finished.  Enqueues only: the
+    tensors are ready when the current stream reaches them."""
+    slots = sorted(set(int(s) for s in pcm_by_slot) | set(int(s) for s in finish))
+    for s in slots:
+      if not 0 <= s < self.slots:
+        raise IndexError("slot %d of %d" % (s, self.slots))
+    chunks = {int(s): v for s, v in pcm_by_slot.items()}
+    sizes = {s: (int(chunks[s].numel()) if torch.is_tensor(chunks[s]) else int(np.asarray(chunks[s]).size)) if s in chunks else 0 for s in slots}
+    k = self.ready(sizes, finish)
+    total = sum(sizes.values())
+    if total == 0:
+      pcm = None
+    elif all(not (torch.is_tensor(chunks[s]) and chunks[s].is_cuda) for s in chunks):
+      # host chunks: packed on the host, staged through pinned memory in one copy
+      pcm = AudioStream._to_device(np.concatenate([np.asarray(chunks[s].numpy() if torch.is_tensor(chunks[s]) else chunks[s], dtype=np.float32).reshape(-1)
+                                                   for s in slots if s in chunks]))
+    else:
+      pcm = torch.empty(total, dtype=torch.float32, device="cuda")
+      o = 0
+      for s in slots:
+        if sizes[s]:
+          pcm[o:o + sizes[s]].copy_(AudioStream._to_device(chunks[s]).reshape(-1))
+          o += sizes[s]
+    K = sum(k)
+    out = torch.empty(K, 64, dtype=torch.float32, device="cuda")
+    e = None
+    if K:
+      if ears is None:
+        e = np.concatenate([np.random.rand(k[s], 1).astype(np.float32) / 100 for s in range(self.slots) if k[s]])
+      else:
+        e = np.concatenate([np.asarray(ears[s], dtype=np.float32).reshape(k[s], 1) for s in range(self.slots) if k[s]])
+      e = AudioStream._to_device(e)
+    n, fin = self._arrays(sizes, finish)
+    _lib.check(self.L.vp_bfmstream_group_push(self.h, _ptr(pcm), n, fin, _ptr(e), _ptr(out if K else None), _stream()),
+               "vp_bfmstream_group_push")
+    res, row = {}, 0
+    for s in range(self.slots):
+      if s in sizes:
+        res[s] = out[row:row + k[s]]
+      row += k[s]
+    return res
+
+  def reset_slot(self, slot):
+    """Slot `slot` starts a new clip; the other slots are untouched."""
+    _lib.check(self.L.vp_bfmstream_group_reset_slot(self.h, int(slot), _stream()), "vp_bfmstream_group_reset_slot")
+
+  def mel_history(self):
+    """The device mel rings: [slots, rows, num_mel_bins]."""
+    p = ctypes.c_void_p()
+    shp = (ctypes.c_int64 * 4)()
+    _lib.check(self.L.vp_bfmstream_group_tensor(self.h, b"mel", ctypes.byref(p), shp), "vp_bfmstream_group_tensor")
+    S, rows, nmel = int(shp[0]), int(shp[1]), int(shp[2])
+    off = p.value - self.workspace.data_ptr()
+    return self.workspace[off:off + 4 * S * rows * nmel].view(torch.float32).view(S, rows, nmel)
+
+  def __del__(self):
+    try:
+      if getattr(self, "h", None):
+        self.L.vp_bfmstream_group_destroy(self.h)
         self.h = None
     except Exception:
       pass
