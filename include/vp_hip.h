@@ -337,6 +337,7 @@ int vp_bfmnet_tensor(vp_bfmnet_t* h, const char* name, void** ptr, int64_t shape
  *     T_win = max_chunk_frames + left + right frames around the frames it emits; the GRU runs over the emitted frames only, its state
  *     carried across pushes (bit-identical to one uncut run).
  *   - Emission counts follow from sample counts alone: the host never waits on the device inside push / finish.
+ *   - A session is a stream group of one slot (vp_bfmstream_group_*, below): the same executor, its workspace that group's.
  * 640 samples per video frame, 5 mel frames per video frame (config/params.yml: 16 kHz, 25 frames/s, hop 128, window 512).
  * ---------------------------------------------------------------------------------------------- */
 typedef struct vp_bfmstream_desc {
@@ -367,7 +368,7 @@ int vp_bfmstream_reset(vp_bfmstream_t* h, void* stream);
 /* Host only: frames the next push of n_new_samples emits (vp_bfmstream_ready) / finish emits (vp_bfmstream_ready_finish) */
 int vp_bfmstream_ready(const vp_bfmstream_t* h, long long n_new_samples);
 int vp_bfmstream_ready_finish(const vp_bfmstream_t* h);
-/* pcm [n] f32 device; ears [k,1] and coeff_out [k,64] device with k = vp_bfmstream_ready(h, n) (may be NULL when k = 0) */
+/* pcm [n] f32 device, any n; ears [k,1] and coeff_out [k,64] device with k = vp_bfmstream_ready(h, n) (may be NULL when k = 0) */
 int vp_bfmstream_push(vp_bfmstream_t* h, const float* pcm, long long n, const float* ears, float* coeff_out, void* stream);
 /* end of the clip: zero-pads as prepare_pcm does and emits the last k = vp_bfmstream_ready_finish(h) frames; the session then takes
  * no more pushes until vp_bfmstream_reset */
@@ -380,10 +381,11 @@ int vp_bfmstream_tensor(vp_bfmstream_t* h, const char* name, void** ptr, int64_t
  * log-mel launch into each slot's mel ring, a ragged window gather, the MfccNet trunk on a plan of batch A (the active slots, rounded up
  * to a bucket 1, 2, 4, .., slots), the stateful GRU with one block per slot, the decoder and one scatter into the packed output.  A slot
  * with more than max_chunk_frames ready runs further rounds, with the other slots that still have frames.
- *   - Each slot's coefficients are bit-identical to a vp_bfmstream with the same max_chunk_frames and trunk_dtype fed the same chunks:
- *     the bucket plans reduce every row as the batch-1 window plan does (each GEMM's tile and K split pinned to that plan's).
- *   - A slot that finishes a clip shorter than T_win runs its last frames alone on an exact-size plan (the vp_bfmstream rule), one
- *     slot after the other: the slow path of short clips.
+ *   - Each slot's coefficients are bit-identical to a vp_bfmstream with the same max_chunk_frames and trunk_dtype fed the same chunks.
+ *     A vp_bfmstream is a group of one slot, so this holds by construction; the bucket plans of more slots reduce every row as the
+ *     batch-1 window plan does (each GEMM's tile and K split pinned to that plan's).
+ *   - A slot that finishes a clip shorter than T_win runs its last frames alone on an exact-size plan, one slot after the other: the
+ *     slow path of short clips.
  *   - Emission counts follow from sample counts alone (vp_bfmstream_group_ready); a push never waits on the device.
  * ---------------------------------------------------------------------------------------------- */
 #define VP_BFMSTREAM_GROUP_MAX_SLOTS 128

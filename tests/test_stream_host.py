@@ -135,6 +135,17 @@ def test_bad_descriptors_are_refused():
   assert lib.vp_bfmstream_create(ctypes.byref(stream_desc(max_chunk_frames=0)), None, 0, None, None, None) != 0
 
 
+def test_session_is_a_one_slot_group():
+  """A vp_bfmstream is a stream group of one slot: its workspace is that group's, for every chunk size and trunk."""
+  from voicepuppet_amd import _lib
+  from voicepuppet_amd.stream import group_desc, stream_desc
+  lib = _lib.lib()
+  for dtype in ("f32", "bf16"):
+    for c in (1, 5, 64):
+      n = lib.vp_bfmstream_workspace_bytes(ctypes.byref(stream_desc(max_chunk_frames=c, dtype=dtype)))
+      assert n > 0 and n == lib.vp_bfmstream_group_workspace_bytes(ctypes.byref(group_desc(1, max_chunk_frames=c, dtype=dtype))), (dtype, c)
+
+
 _ASAN_SCRIPT = r'''
 import ctypes, sys
 sys.path.insert(0, sys.argv[1])

@@ -24,8 +24,6 @@ hipError_t launch_gru_seq(const float* xg, const float* xc, const float* whg, co
 // gru_fwd_state_kernel: rows [t0, t0 + n) of each sequence's T rows, state in / out in hstate [B][256]
 hipError_t launch_gru_state(const float* xg, const float* xc, const float* whg, const float* whc, float* hstate, float* out, int B, int T, int t0, int n,
                             hipStream_t st);
-// rows [r0, r0 + rows) of a mel ring buffer [cap][nmel] -> out [rows][nmel], rows >= avail zero
-hipError_t launch_mel_window(const float* ring, int cap, int nmel, long long r0, int rows, long long avail, float* out, hipStream_t st);
 hipError_t launch_add_ears(float* out, const float* ears, int n, hipStream_t st);
 // Streaming groups (vp_bfmstream_group, plan_bfmnet.hip).  The per-launch tables travel BY VALUE as kernel arguments (a push never waits
 // on the device, so there is no host buffer whose reuse would need a fence): at most kGroupMaxSlots entries (<= 4 KB of arguments).

@@ -406,25 +406,15 @@ __global__ __launch_bounds__(1024) void gru_fwd_state_kernel(const float* __rest
   if (tid < 256) hstate[(size_t)b * 256 + tid] = h[tid];
 }
 
-// Streaming inference: rows [r0, r0 + rows) of the mel history (a ring of cap rows x nmel) as one contiguous MfccNet input; rows at or
-// past `avail` (not received yet) are zero.  A pure copy: the mel values are the bits the log-mel kernel wrote.
-__global__ __launch_bounds__(256) void mel_window_kernel(const float* __restrict__ ring, int cap, int nmel, long long r0, int rows, long long avail,
-                                                         float* __restrict__ out) {
-  const size_t n = (size_t)rows * nmel;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-    const long long r = r0 + (long long)(i / nmel);
-    out[i] = r < avail ? ring[(size_t)(r % cap) * nmel + i % nmel] : 0.f;
-  }
-}
-
-// The same frames for a group of independent streams (vp_bfmstream_group), in three launches around an UNCHANGED logmel512_kernel:
+// Streaming inference (vp_bfmstream_group; a vp_bfmstream is a group of one): log-mel frames of independent streams, in three
+// launches around an UNCHANGED logmel512_kernel:
 // entry e of the table is one stream's piece - its carry_n carried samples (carry[slot][cur]) followed by its new samples (pcm +
 // pcm_off, or zeros), F * hop + keep samples in all.
 //   logmel512_stage_group_kernel   piece e -> row e of a staging matrix [entries][stage_len]
 //   logmel512_kernel               batch = entries, L = stage_len, F = the most frames of an entry -> frames [entries][F][nmel]
 //   mel_scatter_group_kernel       frame f < F_e of entry e -> row (ring_row + f) % cap of ring[slot]; the `keep` samples after the
 //                                  last frame's hop -> carry[slot][cur ^ 1]
-// Every frame is logmel512_kernel's computation on the same 512 samples, so the mel rows are the single session's bits.  (Frames
+// Every frame is logmel512_kernel's computation on the same 512 samples, so the mel rows are vp_logmel_forward's bits.  (Frames
 // f >= F_e of a shorter piece read stale staging samples and are discarded.)
 __global__ __launch_bounds__(256) void logmel512_stage_group_kernel(const float* __restrict__ pcm, const float* __restrict__ carry, float* __restrict__ stage,
                                                                     int stage_len, int hop, const LmGroupTable tab) {
@@ -452,9 +442,9 @@ __global__ __launch_bounds__(256) void mel_scatter_group_kernel(const float* __r
     r[(size_t)((e.ring_row + i / nmel) % cap) * nmel + i % nmel] = src[i];
 }
 
-// Streaming groups (vp_bfmstream_group): the window gather, the stateful GRU and the output copy for A active streams at once; entry b
+// Streaming inference: the window gather, the stateful GRU and the output copy for A active streams at once; entry b
 // of the table is the stream in batch row b of the bucket plan.
-// out [B][rows][nmel]: batch row b < A = rows ring[slot][r0 + r (mod cap)] for r < valid, zero after (mel_window_kernel per stream);
+// out [B][rows][nmel]: batch row b < A = rows ring[slot][r0 + r (mod cap)] for r < valid, zero after;
 // rows b >= A (the bucket's padding) are zero.
 __global__ __launch_bounds__(256) void mel_window_group_kernel(const float* __restrict__ ring, int cap, int nmel, int rows, int A, int B,
                                                                const WinGroupTable tab, float* __restrict__ out) {
@@ -577,10 +567,6 @@ hipError_t launch_gru_seq(const float* xg, const float* xc, const float* whg, co
 hipError_t launch_gru_state(const float* xg, const float* xc, const float* whg, const float* whc, float* hstate, float* out, int B, int T, int t0, int n,
                             hipStream_t st) {
   hipLaunchKernelGGL(gru_fwd_state_kernel, dim3(B), dim3(1024), 0, st, xg, xc, whg, whc, hstate, out, t0, n, T);
-  return hipGetLastError();
-}
-hipError_t launch_mel_window(const float* ring, int cap, int nmel, long long r0, int rows, long long avail, float* out, hipStream_t st) {
-  hipLaunchKernelGGL(mel_window_kernel, dim3(nblk((size_t)rows * nmel, 256)), dim3(256), 0, st, ring, cap, nmel, r0, rows, avail, out);
   return hipGetLastError();
 }
 hipError_t launch_logmel512_group(const float* pcm, float* carry, float* stage, int stage_len, float* frames, float* ring, int cap, const float* window,

@@ -562,13 +562,23 @@ int vp_bfmnet_tensor(vp_bfmnet_t* h, const char* name, void** ptr, int64_t shape
 }  // extern "C"
 
 // ------------------------------------------------------------------------------------------------
-// Streaming BFMNet inference (include/vp_hip.h, vp_bfmstream_*)
-//   PCM  -> two staging buffers (ping-pong: the samples of the next mel frame are carried over, < 512) -> logmel512 -> mel ring
-//   ring -> window [w0, w0 + Tw) frames (mel_window_kernel, rows not received yet are zero) -> bfm_trunk on a window plan
-//        -> stateful GRU over the emitted frames only -> bfm_decode -> the emitted rows + ears to the caller
-// A frame f is emitted before finish once mel rows up to 5f + 4 + R have arrived; the window then starts Lf frames before the first
-// emitted frame (or at the clip start) and reaches Rf frames past the last, so every emitted frame sees exactly what the offline
-// forward shows it.  At finish the window's right edge sits at pad_len, where the offline sequence ends (its SAME padding).
+// Streaming BFMNet inference (include/vp_hip.h, vp_bfmstream_group_* and vp_bfmstream_*).  One executor: a group of S independent
+// sessions ("slots") behind one handle; a vp_bfmstream is a group of one slot.  A push runs, per round, ONE launch chain for all the
+// slots that take part in it:
+//   pieces:  each slot's next piece of samples (at most 5 max_chunk_frames mel frames' worth) behind its carried samples (< 512: the
+//            start of its next mel frame) -> a staging matrix -> logmel512_kernel (batch = the pieces) -> mel_scatter_group_kernel ->
+//            each slot's mel ring
+//   windows: the slots with frames ready, compacted to batch rows 0..A-1 -> mel_window_group_kernel (rows not received yet are zero)
+//            -> bfm_trunk on the bucket plan of batch >= A (1, 2, 4, .., S) -> gru_state_group_kernel (each slot's state, over the
+//            emitted frames only) -> bfm_decode -> rows_scatter_group_kernel -> the packed output; the ears are added once per push
+// A frame f is emitted before finish once mel rows up to 5f + 4 + R have arrived; its window starts Lf frames before the first emitted
+// frame (or at the clip start) and reaches Rf frames past the last, so every emitted frame sees exactly what the offline forward shows
+// it.  At finish the window's right edge sits at pad_len, where the offline sequence ends (its SAME padding); a finished clip shorter
+// than T_win runs its last frames on an exact-size plan instead, in rounds of its own (A = B = 1).
+// Every kernel of the chain computes a batch row as the batch-1 window plan computes its one row: the bucket plans pin each GEMM's tile
+// and K split to the batch-1 plan's (IgemmPin), the stem, depthwise, depthwise + projection and pooling kernels are per pixel.  So a
+// slot's coefficients do not depend on the slots that share its rounds: they are those of a one-slot group, a vp_bfmstream, fed the
+// same chunks.
 // ------------------------------------------------------------------------------------------------
 namespace {
 
@@ -628,294 +638,6 @@ size_t bfm_plan_bytes(vp_bfmnet* scratch, int frames) {
   scratch->d.frames = frames;
   return bfm_carve(scratch, nullptr);
 }
-
-}  // namespace
-
-struct vp_bfmstream {
-  vp_bfmstream_desc d;
-  StreamGeo g;
-  const float* params;
-  vp_logmel_t* lm;                 // constants of the log-mel kernel (window, twiddles, mel matrix)
-  vp_bfmnet* win;                  // the T_win window plan
-  vp_bfmnet* shrt;                 // exact-size plan of a clip shorter than T_win, carved at finish
-  char *lm_base, *win_base, *short_base;   // sub-regions of the workspace
-  size_t lm_bytes, win_bytes, short_bytes;
-  float *stage[2], *ring, *mwin, *hstate, *dout;
-  int cur, carry;                  // staging buffer holding the carried samples, and their count
-  long long samples, mel_done, emitted;
-  bool finished;
-};
-
-static size_t stream_carve(vp_bfmstream* s, char* base, vp_logmel_desc* lmd) {
-  Bump ar{base, 0};
-  const StreamGeo& g = s->g;
-  const size_t stage = (size_t)kWin + (size_t)kHop * g.piece;
-  s->stage[0] = (float*)ar.alloc(stage * 4);
-  s->stage[1] = (float*)ar.alloc(stage * 4);
-  s->ring = (float*)ar.alloc((size_t)g.cap * s->d.num_mel_bins * 4);
-  s->mwin = (float*)ar.alloc((size_t)kMelPerFrame * g.Tw * s->d.num_mel_bins * 4);
-  s->hstate = (float*)ar.alloc(256 * 4);
-  s->dout = (float*)ar.alloc((size_t)g.Tw * 64 * 4);
-  *lmd = vp_logmel_desc{s->d.sample_rate, s->d.num_mel_bins, kWin, kHop, kWin, s->d.lower_hz, s->d.upper_hz, 1, kWin};
-  s->lm_bytes = vp_logmel_workspace_bytes(lmd);
-  s->lm_base = (char*)ar.alloc(s->lm_bytes);
-  // the window plan, then the largest exact-size plan of a clip shorter than it
-  vp_bfmnet tmp{};
-  tmp.d = vp_bfmnet_desc{1, g.Tw, s->d.num_mel_bins, s->d.trunk_dtype};
-  build_model(tmp.m);
-  s->win_bytes = bfm_plan_bytes(&tmp, g.Tw);
-  s->win_base = (char*)ar.alloc(s->win_bytes);
-  size_t sb = 0;
-  for (int t = 1; t < g.Tw; ++t) { const size_t b = bfm_plan_bytes(&tmp, t); if (b > sb) sb = b; }
-  s->short_bytes = sb;
-  s->short_base = (char*)ar.alloc(sb);
-  return ar.off + 256;
-}
-
-static int stream_reset(vp_bfmstream* s, hipStream_t st) {
-  s->cur = 0; s->carry = 0; s->samples = 0; s->mel_done = 0; s->emitted = 0; s->finished = false;
-  VP_HIP_CHECK(hipMemsetAsync(s->hstate, 0, 256 * 4, st));
-  return VP_OK;
-}
-
-// n samples (src: device PCM, or NULL for zeros) through the staging buffers into mel rows; emission is the caller's
-static int stream_append(vp_bfmstream* s, const float* src, long long n, hipStream_t st) {
-  const int nmel = s->d.num_mel_bins;
-  const vp_logmel* lm = s->lm;
-  float* a = s->stage[s->cur];
-  const int q = (int)n;                                    // (<= kHop * piece: the caller splits)
-  if (src) VP_HIP_CHECK(hipMemcpyAsync(a + s->carry, src, (size_t)q * 4, hipMemcpyDeviceToDevice, st));
-  else VP_HIP_CHECK(hipMemsetAsync(a + s->carry, 0, (size_t)q * 4, st));
-  const int ls = s->carry + q;
-  const int F = ls >= kWin ? (ls - kWin) / kHop + 1 : 0;
-  if (F > 0) {
-    const int k = (int)(s->mel_done % s->g.cap);
-    const int n1 = F < s->g.cap - k ? F : s->g.cap - k;
-    VP_HIP_CHECK(launch_logmel512(a, lm->window, lm->w256, lm->w512, lm->mel, s->ring + (size_t)k * nmel, 1, ls, n1, kHop, nmel, st));
-    if (n1 < F)
-      VP_HIP_CHECK(launch_logmel512(a + (size_t)kHop * n1, lm->window, lm->w256, lm->w512, lm->mel, s->ring, 1, ls - kHop * n1, F - n1, kHop, nmel, st));
-    s->mel_done += F;
-    const int keep = ls - kHop * F;
-    VP_HIP_CHECK(hipMemcpyAsync(s->stage[s->cur ^ 1], a + (size_t)kHop * F, (size_t)keep * 4, hipMemcpyDeviceToDevice, st));
-    s->cur ^= 1;
-    s->carry = keep;
-  } else {
-    s->carry = ls;
-  }
-  s->samples += q;
-  return VP_OK;
-}
-
-// frames [f0, f0 + n) through one window; ears / out: their rows
-static int stream_window(vp_bfmstream* s, long long f0, int n, bool fin, const float* ears, float* out, hipStream_t st) {
-  const StreamGeo& g = s->g;
-  const long long pad = pad_len_of(s->samples);
-  vp_bfmnet* p = s->win;
-  if (fin && pad < g.Tw) {                                 // the whole clip is shorter than the window: an exact-size plan
-    if (!s->shrt || s->shrt->d.frames != (int)pad) {
-      delete s->shrt;
-      s->shrt = new vp_bfmnet{};
-      s->shrt->d = vp_bfmnet_desc{1, (int)pad, s->d.num_mel_bins, s->d.trunk_dtype};
-      build_model(s->shrt->m);
-      if (bfm_carve(s->shrt, nullptr) > s->short_bytes) { set_err("vp_bfmstream: short plan outgrew its region"); return VP_ERR_STATE; }
-      bfm_carve(s->shrt, s->short_base);
-      s->shrt->params = s->params;
-      s->shrt->dirty = true;
-      VP_HIP_CHECK(hipMemsetAsync(s->shrt->zeros, 0, 256, st));
-    }
-    p = s->shrt;
-  }
-  const int Tw = p->d.frames;
-  long long w0 = f0 - g.Lf > 0 ? f0 - g.Lf : 0;
-  if (fin && w0 + Tw > pad) w0 = pad - Tw > 0 ? pad - Tw : 0;
-  const int t0 = (int)(f0 - w0);
-  if ((long long)kMelPerFrame * w0 < s->mel_done - g.cap) { set_err("vp_bfmstream: window %lld left the mel history", w0); return VP_ERR_STATE; }
-  if (t0 < 0 || t0 + n > Tw) { set_err("vp_bfmstream: frames [%lld, %lld) outside window %lld + %d", f0, f0 + n, w0, Tw); return VP_ERR_STATE; }
-  int rc;
-  VP_HIP_CHECK(launch_mel_window(s->ring, g.cap, s->d.num_mel_bins, (long long)kMelPerFrame * w0, kMelPerFrame * Tw, s->mel_done, s->mwin, st));
-  if ((rc = bfm_trunk(p, s->mwin, st))) return rc;
-  VP_HIP_CHECK(launch_gru_state(p->xg, p->xc, gru_whg(p), gru_whc(p), s->hstate, p->rnn, 1, Tw, t0, n, st));
-  if ((rc = bfm_decode(p, nullptr, s->dout, st))) return rc;
-  VP_HIP_CHECK(hipMemcpyAsync(out, s->dout + (size_t)t0 * 64, (size_t)n * 64 * 4, hipMemcpyDeviceToDevice, st));
-  VP_HIP_CHECK(launch_add_ears(out, ears, n, st));
-  s->emitted += n;
-  return VP_OK;
-}
-
-// everything ready now, in windows of at most max_chunk_frames; *done: rows of ears / out used so far
-static int stream_emit(vp_bfmstream* s, bool fin, const float* ears, float* out, long long* done, hipStream_t st) {
-  const long long target = emitted_after(s->g, s->samples, fin);
-  int rc;
-  while (s->emitted < target) {
-    const long long left = target - s->emitted;
-    const int n = (int)(left < s->d.max_chunk_frames ? left : s->d.max_chunk_frames);
-    if ((rc = stream_window(s, s->emitted, n, fin, ears + *done, out + *done * 64, st))) return rc;
-    *done += n;
-  }
-  return VP_OK;
-}
-
-// n samples (NULL src: zeros) in pieces of at most one staging buffer, emitting behind each when `emit`
-static int stream_feed(vp_bfmstream* s, const float* src, long long n, bool emit, const float* ears, float* out, long long* done, hipStream_t st) {
-  const long long most = (long long)kHop * s->g.piece;
-  int rc;
-  while (n > 0) {
-    const long long q = n < most ? n : most;
-    if ((rc = stream_append(s, src, q, st))) return rc;
-    if (emit && (rc = stream_emit(s, false, ears, out, done, st))) return rc;
-    if (src) src += q;
-    n -= q;
-  }
-  return VP_OK;
-}
-
-extern "C" {
-
-size_t vp_bfmstream_desc_size(void) { return sizeof(vp_bfmstream_desc); }
-
-int vp_bfmstream_context(const vp_bfmstream_desc* d, int* left_mel, int* right_mel, int* left_frames, int* right_frames, int* window_frames) {
-  if (!stream_ok(d)) { set_err("vp_bfmstream_context: bad descriptor"); return VP_ERR_ARG; }
-  BfmModel m;
-  build_model(m);
-  const StreamGeo g = stream_geo(d, m);
-  if (left_mel) *left_mel = g.L;
-  if (right_mel) *right_mel = g.R;
-  if (left_frames) *left_frames = g.Lf;
-  if (right_frames) *right_frames = g.Rf;
-  if (window_frames) *window_frames = g.Tw;
-  return VP_OK;
-}
-
-long long vp_bfmstream_frames_after(const vp_bfmstream_desc* d, long long samples, int finished) {
-  if (!stream_ok(d) || samples < 0) return -1;
-  BfmModel m;
-  build_model(m);
-  return emitted_after(stream_geo(d, m), samples, finished != 0);
-}
-
-size_t vp_bfmstream_workspace_bytes(const vp_bfmstream_desc* d) {
-  if (!stream_ok(d)) return 0;
-  vp_bfmstream s{};
-  s.d = *d;
-  BfmModel m;
-  build_model(m);
-  s.g = stream_geo(d, m);
-  vp_logmel_desc lmd;
-  return stream_carve(&s, nullptr, &lmd);
-}
-
-int vp_bfmstream_create(const vp_bfmstream_desc* d, void* workspace, size_t bytes, const float* params, void* stream, vp_bfmstream_t** out) {
-  if (!stream_ok(d) || !workspace || !params || !out) { set_err("vp_bfmstream_create: bad argument"); return VP_ERR_ARG; }
-  if (bytes < vp_bfmstream_workspace_bytes(d)) { set_err("vp_bfmstream_create: workspace too small"); return VP_ERR_WORKSPACE; }
-  vp_bfmstream* s = new vp_bfmstream{};
-  s->d = *d;
-  s->params = params;
-  {
-    BfmModel m;
-    build_model(m);
-    s->g = stream_geo(d, m);
-  }
-  vp_logmel_desc lmd;
-  stream_carve(s, (char*)workspace, &lmd);
-  hipStream_t st = (hipStream_t)stream;
-  int rc;
-  // (every failure past this point goes through vp_bfmstream_destroy: nothing of the half-built handle is left behind)
-  if ((rc = vp_logmel_create(&lmd, s->lm_base, s->lm_bytes, stream, &s->lm))) { vp_bfmstream_destroy(s); return rc; }
-  s->win = new vp_bfmnet{};
-  s->win->d = vp_bfmnet_desc{1, s->g.Tw, d->num_mel_bins, d->trunk_dtype};
-  build_model(s->win->m);
-  bfm_carve(s->win, s->win_base);
-  s->win->params = params;
-  s->win->dirty = true;
-  const hipError_t e = hipMemsetAsync(s->win->zeros, 0, 256, st);
-  if (e != hipSuccess) { set_err("vp_bfmstream_create: %s", hipGetErrorString(e)); vp_bfmstream_destroy(s); return VP_ERR_HIP; }
-  if ((rc = stream_reset(s, st))) { vp_bfmstream_destroy(s); return rc; }
-  *out = s;
-  return VP_OK;
-}
-
-void vp_bfmstream_destroy(vp_bfmstream_t* h) {
-  if (!h) return;
-  vp_logmel_destroy(h->lm);
-  delete h->win;
-  delete h->shrt;
-  delete h;
-}
-
-int vp_bfmstream_params_changed(vp_bfmstream_t* h) {
-  if (!h) return VP_ERR_ARG;
-  h->win->dirty = true;
-  if (h->shrt) h->shrt->dirty = true;
-  return VP_OK;
-}
-
-int vp_bfmstream_reset(vp_bfmstream_t* h, void* stream) {
-  if (!h) { set_err("vp_bfmstream_reset: null handle"); return VP_ERR_ARG; }
-  return stream_reset(h, (hipStream_t)stream);
-}
-
-int vp_bfmstream_ready(const vp_bfmstream_t* h, long long n) {
-  if (!h || n < 0 || h->finished) return 0;
-  return (int)(emitted_after(h->g, h->samples + n, false) - h->emitted);
-}
-
-int vp_bfmstream_ready_finish(const vp_bfmstream_t* h) {
-  if (!h || h->finished) return 0;
-  return (int)(pad_len_of(h->samples) - h->emitted);
-}
-
-int vp_bfmstream_push(vp_bfmstream_t* h, const float* pcm, long long n, const float* ears, float* coeff_out, void* stream) {
-  if (!h || n < 0 || (n > 0 && !pcm)) { set_err("vp_bfmstream_push: bad argument"); return VP_ERR_ARG; }
-  if (h->finished) { set_err("vp_bfmstream_push: the session is finished (vp_bfmstream_reset)"); return VP_ERR_STATE; }
-  if (vp_bfmstream_ready(h, n) > 0 && (!ears || !coeff_out)) { set_err("vp_bfmstream_push: frames are ready and ears / coeff_out is NULL"); return VP_ERR_ARG; }
-  long long done = 0;
-  return stream_feed(h, pcm, n, true, ears, coeff_out, &done, (hipStream_t)stream);
-}
-
-int vp_bfmstream_finish(vp_bfmstream_t* h, const float* ears, float* coeff_out, void* stream) {
-  if (!h) { set_err("vp_bfmstream_finish: null handle"); return VP_ERR_ARG; }
-  if (h->finished) { set_err("vp_bfmstream_finish: the session is finished (vp_bfmstream_reset)"); return VP_ERR_STATE; }
-  if (!ears || !coeff_out) { set_err("vp_bfmstream_finish: null ears / coeff_out"); return VP_ERR_ARG; }
-  hipStream_t st = (hipStream_t)stream;
-  const long long n = h->samples;
-  // prepare_pcm: 128 (5 pad_len - 1) + 512 samples in all, zeros past the clip
-  const long long total = (long long)kHop * (kMelPerFrame * pad_len_of(n) - 1) + kWin;
-  long long done = 0;
-  int rc;
-  // (the padding only appends mel rows: every frame still pending is emitted below by the finish rule, so a clip shorter than the window
-  // runs all its remaining frames on the exact-size plan)
-  if ((rc = stream_feed(h, nullptr, total - n, false, ears, coeff_out, &done, st))) return rc;
-  h->samples = n;                                          // (pad_len and the schedule are those of the clip, not of its padding)
-  if (h->mel_done != (long long)kMelPerFrame * pad_len_of(n)) { set_err("vp_bfmstream_finish: %lld mel frames", h->mel_done); return VP_ERR_STATE; }
-  if ((rc = stream_emit(h, true, ears, coeff_out, &done, st))) return rc;
-  h->finished = true;
-  return VP_OK;
-}
-
-int vp_bfmstream_tensor(vp_bfmstream_t* h, const char* name, void** ptr, int64_t shape[4]) {
-  if (!h || !name || !ptr) return VP_ERR_ARG;
-  if (std::string(name) != "mel") return VP_ERR_ARG;
-  *ptr = h->ring;
-  if (shape) { shape[0] = h->g.cap; shape[1] = h->d.num_mel_bins; shape[2] = 1; shape[3] = 1; }
-  return VP_OK;
-}
-
-}  // extern "C"
-
-// ------------------------------------------------------------------------------------------------
-// Streaming groups (include/vp_hip.h, vp_bfmstream_group_*): S independent vp_bfmstream sessions ("slots") behind one handle, advanced
-// together.  A group push runs, per round, ONE launch chain for all the slots that take part in it:
-//   pieces:  the slots' next pieces of samples (the single session's piece sizes) -> a staging matrix -> logmel512_kernel (unchanged,
-//            batch = the pieces) -> mel_scatter_group_kernel -> each slot's mel ring
-//   windows: the slots with frames ready, compacted to batch rows 0..A-1 -> mel_window_group_kernel -> bfm_trunk on the bucket plan of
-//            batch >= A (1, 2, 4, .., S) -> gru_state_group_kernel (each slot's state) -> bfm_decode -> rows_scatter_group_kernel
-// Every slot's sequence of pieces and windows is the one its own vp_bfmstream would run for the same pushes, and every kernel of the
-// chain computes a batch row as the one-stream window plan computes its one row: the bucket plans pin each GEMM's tile and K split to
-// the batch-1 plan's (IgemmPin), the stem, depthwise, depthwise + projection and pooling kernels are per pixel.  So each slot's
-// coefficients are bit-identical to a vp_bfmstream fed the same chunks.  A slot that finishes a clip shorter than T_win runs its
-// remaining frames alone on an exact-size plan (as vp_bfmstream does), one slot after the other.
-// ------------------------------------------------------------------------------------------------
-namespace {
 
 struct GroupSlot { int cur, carry; long long samples, mel_done, emitted; bool finished; };
 
@@ -1095,90 +817,90 @@ static int group_pieces(vp_bfmstream_group* G, const float* pcm, std::vector<lon
   return VP_OK;
 }
 
-// the frames of one slot whose finished clip is shorter than T_win: stream_window's exact-size path, alone
-static int group_short(vp_bfmstream_group* G, int s, long long target, float* out, std::vector<long long>& row, hipStream_t st) {
-  GroupSlot& z = G->slot[s];
-  const StreamGeo& g = G->g;
+// the exact-size plan of a finished clip of pad frames (shorter than T_win), carved on its region of the workspace
+static int short_plan(vp_bfmstream_group* G, int pad, hipStream_t st) {
+  if (G->shrt && G->shrt->d.frames == pad) return VP_OK;
+  delete G->shrt;
+  G->shrt = new vp_bfmnet{};
+  G->shrt->d = vp_bfmnet_desc{1, pad, G->d.num_mel_bins, G->d.trunk_dtype};
+  build_model(G->shrt->m);
+  if (bfm_carve(G->shrt, nullptr) > G->short_bytes) { set_err("vp_bfmstream_group: short plan outgrew its region"); return VP_ERR_STATE; }
+  bfm_carve(G->shrt, G->short_base);
+  G->shrt->params = G->params;
+  G->shrt->dirty = true;
+  VP_HIP_CHECK(hipMemsetAsync(G->shrt->zeros, 0, 256, st));
+  return VP_OK;
+}
+
+// the window of Tw frames that emits slot s's frames [f0, f0 + n): it starts Lf frames before f0 (or at the clip start) and, at finish,
+// ends at pad_len at the latest.  *w0: its first frame
+static int place_window(const vp_bfmstream_group* G, int s, long long f0, int n, int Tw, bool fin, long long* w0) {
+  const GroupSlot& z = G->slot[s];
   const long long pad = pad_len_of(z.samples);
-  const int nmel = G->d.num_mel_bins;
-  if (!G->shrt || G->shrt->d.frames != (int)pad) {
-    delete G->shrt;
-    G->shrt = new vp_bfmnet{};
-    G->shrt->d = vp_bfmnet_desc{1, (int)pad, G->d.num_mel_bins, G->d.trunk_dtype};
-    build_model(G->shrt->m);
-    if (bfm_carve(G->shrt, nullptr) > G->short_bytes) { set_err("vp_bfmstream_group: short plan outgrew its region"); return VP_ERR_STATE; }
-    bfm_carve(G->shrt, G->short_base);
-    G->shrt->params = G->params;
-    G->shrt->dirty = true;
-    VP_HIP_CHECK(hipMemsetAsync(G->shrt->zeros, 0, 256, st));
-  }
-  vp_bfmnet* p = G->shrt;
-  const int Tw = p->d.frames;
-  int rc;
-  while (z.emitted < target) {
+  long long w = f0 - G->g.Lf > 0 ? f0 - G->g.Lf : 0;
+  if (fin && w + Tw > pad) w = pad - Tw > 0 ? pad - Tw : 0;
+  if ((long long)kMelPerFrame * w < z.mel_done - G->g.cap) { set_err("vp_bfmstream_group: slot %d window %lld left the mel history", s, w); return VP_ERR_STATE; }
+  if (f0 < w || f0 + n > w + Tw) { set_err("vp_bfmstream_group: slot %d frames [%lld, %lld) outside window %lld + %d", s, f0, f0 + n, w, Tw); return VP_ERR_STATE; }
+  *w0 = w;
+  return VP_OK;
+}
+
+// one round on plan p (batch >= act.size()): the next (at most max_chunk_frames) frames up to target[s] of every slot s in act, out rows of
+// slot s from row[s] on
+static int group_round(vp_bfmstream_group* G, vp_bfmnet* p, const std::vector<int>& act, const std::vector<long long>& target, bool fin, float* out,
+                       std::vector<long long>& row, hipStream_t st) {
+  const StreamGeo& g = G->g;
+  const int A = (int)act.size(), Tw = p->d.frames;
+  WinGroupTable win;
+  RowsGroupTable rows;
+  int most = 0, rc;
+  for (int b = 0; b < A; ++b) {
+    const int s = act[b];
+    GroupSlot& z = G->slot[s];
     const long long f0 = z.emitted;
-    const int n = (int)(target - f0 < G->d.max_chunk_frames ? target - f0 : G->d.max_chunk_frames);
-    long long w0 = f0 - g.Lf > 0 ? f0 - g.Lf : 0;
-    if (w0 + Tw > pad) w0 = pad - Tw > 0 ? pad - Tw : 0;
-    const int t0 = (int)(f0 - w0);
-    if (t0 < 0 || t0 + n > Tw) { set_err("vp_bfmstream_group: slot %d frames [%lld, %lld) outside window %lld + %d", s, f0, f0 + n, w0, Tw); return VP_ERR_STATE; }
-    VP_HIP_CHECK(launch_mel_window(G->ring + (size_t)s * g.cap * nmel, g.cap, nmel, (long long)kMelPerFrame * w0, kMelPerFrame * Tw, z.mel_done, G->mwin, st));
-    if ((rc = bfm_trunk(p, G->mwin, st))) return rc;
-    VP_HIP_CHECK(launch_gru_state(p->xg, p->xc, gru_whg(p), gru_whc(p), G->hstate + (size_t)s * 256, p->rnn, 1, Tw, t0, n, st));
-    if ((rc = bfm_decode(p, nullptr, G->dout, st))) return rc;
-    VP_HIP_CHECK(hipMemcpyAsync(out + row[s] * 64, G->dout + (size_t)t0 * 64, (size_t)n * 64 * 4, hipMemcpyDeviceToDevice, st));
+    const int n = (int)(target[s] - f0 < G->d.max_chunk_frames ? target[s] - f0 : G->d.max_chunk_frames);
+    long long w0;
+    if ((rc = place_window(G, s, f0, n, Tw, fin, &w0))) return rc;
+    const long long r0 = (long long)kMelPerFrame * w0, got = z.mel_done - r0;
+    win.e[b] = WinGroupEntry{s, (int)(r0 % g.cap), (int)(got < 0 ? 0 : got > kMelPerFrame * Tw ? kMelPerFrame * Tw : got)};
+    rows.e[b] = RowsGroupEntry{s, (int)(f0 - w0), n, (int)row[s]};
+    if (n > most) most = n;
     z.emitted += n; row[s] += n;
   }
+  VP_HIP_CHECK(launch_mel_window_group(G->ring, g.cap, G->d.num_mel_bins, kMelPerFrame * Tw, A, p->d.batch, win, G->mwin, st));
+  if ((rc = bfm_trunk(p, G->mwin, st))) return rc;
+  VP_HIP_CHECK(launch_gru_state_group(p->xg, p->xc, gru_whg(p), gru_whc(p), G->hstate, p->rnn, Tw, rows, A, st));
+  if ((rc = bfm_decode(p, nullptr, G->dout, st))) return rc;
+  VP_HIP_CHECK(launch_rows_scatter_group(G->dout, Tw, out, rows, A, most, st));
   return VP_OK;
 }
 
 // everything ready now for the slots in `who`, in rounds of at most max_chunk_frames per slot; out rows of slot s from row[s] on
 static int group_emit(vp_bfmstream_group* G, const std::vector<int>& who, bool fin, float* out, std::vector<long long>& row, hipStream_t st) {
-  const StreamGeo& g = G->g;
-  const int S = G->d.slots, Tw = g.Tw, nmel = G->d.num_mel_bins;
+  const int S = G->d.slots;
   std::vector<long long> target(S, 0);
   std::vector<int> live;
   int rc;
   for (int s : who) {
     GroupSlot& z = G->slot[s];
-    target[s] = emitted_after(g, z.samples, fin);
+    target[s] = emitted_after(G->g, z.samples, fin);
     if (z.emitted >= target[s]) continue;
-    if (fin && pad_len_of(z.samples) < Tw) { if ((rc = group_short(G, s, target[s], out, row, st))) return rc; }
-    else live.push_back(s);
+    const long long pad = pad_len_of(z.samples);
+    if (!fin || pad >= G->g.Tw) { live.push_back(s); continue; }
+    // a finished clip shorter than T_win: its frames alone, on the exact-size plan
+    if ((rc = short_plan(G, (int)pad, st))) return rc;
+    while (z.emitted < target[s])
+      if ((rc = group_round(G, G->shrt, {s}, target, fin, out, row, st))) return rc;
   }
   const std::vector<int> buckets = group_buckets(S);
-  WinGroupTable win;
-  RowsGroupTable rows;
   while (true) {
-    int A = 0, most = 0;
-    for (int s : live) {
-      GroupSlot& z = G->slot[s];
-      if (z.emitted >= target[s]) continue;
-      const long long f0 = z.emitted, pad = pad_len_of(z.samples);
-      const int n = (int)(target[s] - f0 < G->d.max_chunk_frames ? target[s] - f0 : G->d.max_chunk_frames);
-      long long w0 = f0 - g.Lf > 0 ? f0 - g.Lf : 0;
-      if (fin && w0 + Tw > pad) w0 = pad - Tw > 0 ? pad - Tw : 0;
-      const int t0 = (int)(f0 - w0);
-      if ((long long)kMelPerFrame * w0 < z.mel_done - g.cap) { set_err("vp_bfmstream_group: slot %d window %lld left the mel history", s, w0); return VP_ERR_STATE; }
-      if (t0 < 0 || t0 + n > Tw) { set_err("vp_bfmstream_group: slot %d frames [%lld, %lld) outside window %lld + %d", s, f0, f0 + n, w0, Tw); return VP_ERR_STATE; }
-      const long long r0 = (long long)kMelPerFrame * w0, got = z.mel_done - r0;
-      win.e[A] = WinGroupEntry{s, (int)(r0 % g.cap), (int)(got < 0 ? 0 : got > kMelPerFrame * Tw ? kMelPerFrame * Tw : got)};
-      rows.e[A] = RowsGroupEntry{s, t0, n, (int)row[s]};
-      if (n > most) most = n;
-      z.emitted += n; row[s] += n;
-      ++A;
-    }
-    if (!A) break;
+    std::vector<int> act;
+    for (int s : live) if (G->slot[s].emitted < target[s]) act.push_back(s);
+    if (act.empty()) return VP_OK;
     size_t bi = 0;
-    while (buckets[bi] < A) ++bi;
-    vp_bfmnet* p = G->plans[bi];
-    VP_HIP_CHECK(launch_mel_window_group(G->ring, g.cap, nmel, kMelPerFrame * Tw, A, p->d.batch, win, G->mwin, st));
-    if ((rc = bfm_trunk(p, G->mwin, st))) return rc;
-    VP_HIP_CHECK(launch_gru_state_group(p->xg, p->xc, gru_whg(p), gru_whc(p), G->hstate, p->rnn, Tw, rows, A, st));
-    if ((rc = bfm_decode(p, nullptr, G->dout, st))) return rc;
-    VP_HIP_CHECK(launch_rows_scatter_group(G->dout, Tw, out, rows, A, most, st));
+    while (buckets[bi] < (int)act.size()) ++bi;
+    if ((rc = group_round(G, G->plans[bi], act, target, fin, out, row, st))) return rc;
   }
-  return VP_OK;
 }
 
 extern "C" {
@@ -1306,13 +1028,13 @@ int vp_bfmstream_group_push(vp_bfmstream_group_t* h, const float* pcm, const lon
     long long p = 0, r = 0;
     for (int s = 0; s < S; ++s) { pos[s] = p; p += n[s]; row[s] = r; r += k[s]; left[s] = n[s]; }
   }
-  // the samples, piece by piece, emitting behind each piece (vp_bfmstream_push)
+  // the samples, piece by piece, emitting behind each piece
   while (true) {
     if ((rc = group_pieces(h, pcm, pos, left, who, st))) return rc;
     if (who.empty()) break;
     if ((rc = group_emit(h, who, false, coeff_out, row, st))) return rc;
   }
-  // then the finishing slots: prepare_pcm's zero padding without emitting, then every pending frame by the finish rule (vp_bfmstream_finish)
+  // then the finishing slots: prepare_pcm's zero padding without emitting, then every pending frame by the finish rule
   std::vector<int> fin;
   for (int s = 0; s < S; ++s) {
     left[s] = 0;
@@ -1345,6 +1067,119 @@ int vp_bfmstream_group_tensor(vp_bfmstream_group_t* h, const char* name, void** 
   *ptr = h->ring;
   if (shape) { shape[0] = h->d.slots; shape[1] = h->g.cap; shape[2] = h->d.num_mel_bins; shape[3] = 1; }
   return VP_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------
+// vp_bfmstream_*: one session = a group of one slot (its one bucket is the batch-1 window plan, which group_plans never refuses)
+// ------------------------------------------------------------------------------------------------
+struct vp_bfmstream { vp_bfmstream_group* G; };
+
+static bool one_slot(const vp_bfmstream_desc* d, vp_bfmstream_group_desc* gd) {
+  if (!stream_ok(d)) return false;
+  *gd = vp_bfmstream_group_desc{(int)sizeof(vp_bfmstream_group_desc), 1, d->max_chunk_frames, d->num_mel_bins, d->trunk_dtype, d->sample_rate,
+                                d->lower_hz, d->upper_hz};
+  return true;
+}
+
+extern "C" {
+
+size_t vp_bfmstream_desc_size(void) { return sizeof(vp_bfmstream_desc); }
+
+int vp_bfmstream_context(const vp_bfmstream_desc* d, int* left_mel, int* right_mel, int* left_frames, int* right_frames, int* window_frames) {
+  if (!stream_ok(d)) { set_err("vp_bfmstream_context: bad descriptor"); return VP_ERR_ARG; }
+  BfmModel m;
+  build_model(m);
+  const StreamGeo g = stream_geo(d, m);
+  if (left_mel) *left_mel = g.L;
+  if (right_mel) *right_mel = g.R;
+  if (left_frames) *left_frames = g.Lf;
+  if (right_frames) *right_frames = g.Rf;
+  if (window_frames) *window_frames = g.Tw;
+  return VP_OK;
+}
+
+long long vp_bfmstream_frames_after(const vp_bfmstream_desc* d, long long samples, int finished) {
+  if (!stream_ok(d) || samples < 0) return -1;
+  BfmModel m;
+  build_model(m);
+  return emitted_after(stream_geo(d, m), samples, finished != 0);
+}
+
+size_t vp_bfmstream_workspace_bytes(const vp_bfmstream_desc* d) {
+  vp_bfmstream_group_desc gd;
+  return one_slot(d, &gd) ? vp_bfmstream_group_workspace_bytes(&gd) : 0;
+}
+
+int vp_bfmstream_create(const vp_bfmstream_desc* d, void* workspace, size_t bytes, const float* params, void* stream, vp_bfmstream_t** out) {
+  vp_bfmstream_group_desc gd;
+  if (!one_slot(d, &gd) || !workspace || !params || !out) { set_err("vp_bfmstream_create: bad argument"); return VP_ERR_ARG; }
+  vp_bfmstream_group* G;
+  int rc;
+  if ((rc = vp_bfmstream_group_create(&gd, workspace, bytes, params, stream, &G))) return rc;
+  *out = new vp_bfmstream{G};
+  return VP_OK;
+}
+
+void vp_bfmstream_destroy(vp_bfmstream_t* h) {
+  if (!h) return;
+  vp_bfmstream_group_destroy(h->G);
+  delete h;
+}
+
+int vp_bfmstream_params_changed(vp_bfmstream_t* h) { return h ? vp_bfmstream_group_params_changed(h->G) : VP_ERR_ARG; }
+
+int vp_bfmstream_reset(vp_bfmstream_t* h, void* stream) {
+  if (!h) { set_err("vp_bfmstream_reset: null handle"); return VP_ERR_ARG; }
+  return vp_bfmstream_group_reset_slot(h->G, 0, stream);
+}
+
+int vp_bfmstream_ready(const vp_bfmstream_t* h, long long n) {
+  int k = 0;
+  return h && vp_bfmstream_group_ready(h->G, &n, nullptr, &k) >= 0 ? k : 0;
+}
+
+int vp_bfmstream_ready_finish(const vp_bfmstream_t* h) {
+  const long long n = 0;
+  const int fin = 1;
+  int k = 0;
+  return h && vp_bfmstream_group_ready(h->G, &n, &fin, &k) >= 0 ? k : 0;
+}
+
+int vp_bfmstream_push(vp_bfmstream_t* h, const float* pcm, long long n, const float* ears, float* coeff_out, void* stream) {
+  if (!h || n < 0 || (n > 0 && !pcm)) { set_err("vp_bfmstream_push: bad argument"); return VP_ERR_ARG; }
+  if (h->G->slot[0].finished) { set_err("vp_bfmstream_push: the session is finished (vp_bfmstream_reset)"); return VP_ERR_STATE; }
+  if (vp_bfmstream_ready(h, n) > 0 && (!ears || !coeff_out)) { set_err("vp_bfmstream_push: frames are ready and ears / coeff_out is NULL"); return VP_ERR_ARG; }
+  // a group push takes fewer than 2^31 samples: a longer push runs as several, cut at whole pieces (the piece sizes, and so the windows,
+  // stay those of the uncut push)
+  const long long piece = (long long)kHop * h->G->g.piece, most = ((1ll << 31) - 1) / piece * piece;
+  while (n > 0) {
+    long long q = n < most ? n : most;
+    const int k = vp_bfmstream_ready(h, q);
+    int rc;
+    if ((rc = vp_bfmstream_group_push(h->G, pcm, &q, nullptr, ears, coeff_out, stream))) return rc;
+    pcm += q; n -= q;
+    if (k) { ears += k; coeff_out += (size_t)k * 64; }
+  }
+  return VP_OK;
+}
+
+int vp_bfmstream_finish(vp_bfmstream_t* h, const float* ears, float* coeff_out, void* stream) {
+  if (!h) { set_err("vp_bfmstream_finish: null handle"); return VP_ERR_ARG; }
+  if (h->G->slot[0].finished) { set_err("vp_bfmstream_finish: the session is finished (vp_bfmstream_reset)"); return VP_ERR_STATE; }
+  if (!ears || !coeff_out) { set_err("vp_bfmstream_finish: null ears / coeff_out"); return VP_ERR_ARG; }
+  const long long n = 0;
+  const int fin = 1;
+  return vp_bfmstream_group_push(h->G, nullptr, &n, &fin, ears, coeff_out, stream);
+}
+
+int vp_bfmstream_tensor(vp_bfmstream_t* h, const char* name, void** ptr, int64_t shape[4]) {
+  if (!h) return VP_ERR_ARG;
+  int64_t gs[4];
+  const int rc = vp_bfmstream_group_tensor(h->G, name, ptr, gs);
+  if (!rc && shape) { shape[0] = gs[1]; shape[1] = gs[2]; shape[2] = 1; shape[3] = 1; }
+  return rc;
 }
 
 }  // extern "C"

@@ -50,6 +50,21 @@ def load_bfmnet_params(path):
   return tf_checkpoint.read_checkpoint(path)
 
 
+def _write_params(arena, manifest, params):
+  """The named arrays of `params` into their places of the device parameter arena (names it does not hold are left as they are)."""
+  host = arena.cpu().numpy()
+  for name, off, shape in manifest:
+    if name in params:
+      v = np.asarray(params[name], dtype=np.float32)
+      assert v.shape == shape, (name, v.shape, shape)
+      host[off:off + v.size] = v.reshape(-1)
+  arena.copy_(torch.from_numpy(host))
+
+
+def _lookahead_ms(right_mel, sample_rate):
+  return 1000.0 * (right_mel * 128 + (512 - 128)) / sample_rate
+
+
 class AudioStream:
   """One streaming session of BFMNet inference.
 
@@ -81,16 +96,10 @@ class AudioStream:
   def lookahead_ms(self):
     """Audio that must arrive after a frame's own 40 ms before the frame is emitted: its right context in mel rows plus the part of
     the last mel window past its hop."""
-    return 1000.0 * (self.right_mel * 128 + (512 - 128)) / self.desc.sample_rate
+    return _lookahead_ms(self.right_mel, self.desc.sample_rate)
 
   def load_params(self, params):
-    host = self.params.cpu().numpy()
-    for name, off, shape in self.manifest:
-      if name in params:
-        v = np.asarray(params[name], dtype=np.float32)
-        assert v.shape == shape, (name, v.shape, shape)
-        host[off:off + v.size] = v.reshape(-1)
-    self.params.copy_(torch.from_numpy(host))
+    _write_params(self.params, self.manifest, params)
     _lib.check(self.L.vp_bfmstream_params_changed(self.h), "vp_bfmstream_params_changed")
 
   def ready(self, n_samples):
@@ -195,16 +204,10 @@ class AudioStreamGroup:
   @property
   def lookahead_ms(self):
     """As AudioStream.lookahead_ms (the same for every slot)."""
-    return 1000.0 * (self.right_mel * 128 + (512 - 128)) / self.desc.sample_rate
+    return _lookahead_ms(self.right_mel, self.desc.sample_rate)
 
   def load_params(self, params):
-    host = self.params.cpu().numpy()
-    for name, off, shape in self.manifest:
-      if name in params:
-        v = np.asarray(params[name], dtype=np.float32)
-        assert v.shape == shape, (name, v.shape, shape)
-        host[off:off + v.size] = v.reshape(-1)
-    self.params.copy_(torch.from_numpy(host))
+    _write_params(self.params, self.manifest, params)
     _lib.check(self.L.vp_bfmstream_group_params_changed(self.h), "vp_bfmstream_group_params_changed")
 
   def _arrays(self, n_by_slot, finish_by_slot):
