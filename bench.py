@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: PixReferNet G+D training step, frames/s at 256x256, bf16, GLOBAL batch 32 (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W [--scaling strong|weak] [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--scaling strong|weak] [--dump-outputs DIR] [--full]
 
 One process per GPU.  With N > 1 and no WORLD_SIZE in the environment this script itself starts the N ranks
 (`python -m torch.distributed.run --nproc-per-node N bench.py ...` as a CHILD process, before anything here has touched
@@ -11,12 +11,16 @@ MASTER_* from the environment), over RCCL.
 A step = forward (G, composite, 3xD, VGG trunk on 2N, all losses) + both backward passes + all-reduce of the G/D gradient
 arenas + Adam(D) + Adam(G) on synthetic inputs already resident in HBM.
   --scaling strong (default, SURVEY.md 8d/8e): the global batch stays 32, each rank runs 32/N samples;
-  --scaling weak: every rank runs 32 samples.  With N > 1 the other mode is measured too and reported under "other_scaling".
-Rank 0 prints ONE JSON line (contract in the task statement) with
-  roofline      the dominant kernel class, timed live with HIP events on the launch stream,
+  --scaling weak: every rank runs 32 samples.
+Rank 0 prints ONE JSON line.  A plain run does only what the line's headline needs: set-up, the warm-up steps, the timed
+steps, --dump-outputs, the line.  --full then measures everything else, after the timed steps, into the same line (the --no-*
+options leave single legs of it out), among others
+  roofline      the dominant kernel class, timed live with HIP events on the launch stream (with `kernels`, `long_region`),
+  other_scaling (N > 1) the other --scaling mode; `distributed.buckets`: per-bucket timing of the gradient exchange,
   f32           (N = 1) the same step on the float32 path - the path that meets the 1e-3 pixel tolerance,
   cpu_baseline  (N = 1) CPU restatements of the same step on the host cores: the numpy port (oracle/pixrefer_ref.py) and
-                a torch-CPU float32 (oneDNN) restatement as the TF-CPU proxy (oracle/pixrefer_torch.py), bounded samples.
+                a torch-CPU float32 (oneDNN) restatement as the TF-CPU proxy (oracle/pixrefer_torch.py), bounded samples,
+and the strong-scaling ceiling, the PCIe-inclusive rate, the BFMNet training step and the other BASELINE workloads.
 """
 import argparse
 import glob
@@ -46,6 +50,9 @@ def parse_args(argv=None):
   ap.add_argument("--batch", type=int, default=32, help="weak scaling: samples per step per rank")
   ap.add_argument("--height", type=int, default=256)
   ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
+  ap.add_argument("--full", action="store_true",
+                  help="after the timed steps, also measure the sub-records (per-kernel roofline, f32 path, other configurations, "
+                       "CPU baselines, ...); the --no-* options below leave single ones out")
   ap.add_argument("--no-cpu-baseline", action="store_true")
   ap.add_argument("--no-profile", action="store_true")
   ap.add_argument("--no-f32", action="store_true")
@@ -297,7 +304,8 @@ def make_engine(per_gpu, height, dtype):
   return eng
 
 
-def run_config(per_gpu, height, dtype, steps, warmup, rank, world, device, group, profile, grad_dtype="f32", dump_dir=None):
+def run_config(per_gpu, height, dtype, steps, warmup, rank, world, device, group, profile, grad_dtype="f32", dump_dir=None,
+               exchange_timing=True):
   import torch
   import torch.distributed as dist
   eng = make_engine(per_gpu, height, dtype)
@@ -357,7 +365,7 @@ def run_config(per_gpu, height, dtype, steps, warmup, rank, world, device, group
       step()
     torch.cuda.synchronize()
     res["long_region"] = {"steps": 5 * steps, "ms_per_step": (time.perf_counter() - t1) / (5 * steps) * 1e3}
-  if world > 1:
+  if world > 1 and exchange_timing:
     # where the exchange's time goes (outside the timed region): HIP events on the communication stream around every bucket of two
     # more steps; every rank runs them (they are collectives), rank 0 reports the second one
     ex = eng._exchange
@@ -558,15 +566,17 @@ def main():
       else:
         _lib.check(_lib.lib().vp_tune(k.encode(), int(v)), "vp_tune " + kv)
   main_res = run_config(per_gpu_batch(args, args.scaling, world), args.height, args.dtype, args.steps, args.warmup,
-                        rank, world, device, group, not args.no_profile, grad_dtype, dump_dir=args.dump_outputs)
+                        rank, world, device, group, args.full and not args.no_profile, grad_dtype, dump_dir=args.dump_outputs,
+                        exchange_timing=args.full)
+  # everything below measures the sub-records of --full: a plain run ends at its headline
   other = None
-  if world > 1 and not args.no_other_scaling:
+  if args.full and world > 1 and not args.no_other_scaling:
     mode = "weak" if args.scaling == "strong" else "strong"
     other = run_config(per_gpu_batch(args, mode, world), args.height, args.dtype, args.steps, args.warmup,
                        rank, world, device, group, False, grad_dtype)
     other["scaling"] = mode
   f32 = None
-  if world == 1 and args.dtype == "bf16" and not args.no_f32:
+  if args.full and world == 1 and args.dtype == "bf16" and not args.no_f32:
     r = run_config(per_gpu_batch(args, args.scaling, world), args.height, "f32", max(3, args.steps // 4), 2,
                    rank, world, device, group, not args.no_profile)
     f32 = {"ms_per_step": r["ms_per_step"], "value": r["frames_per_s"], "unit": "frames/s", "step_tflops": r["step_tflops"],
@@ -575,7 +585,7 @@ def main():
   # What strong scaling of the global batch can reach at 8 GPUs before any communication: the single-GPU step at the per-GPU share
   # (global batch / 8 frames), measured here so that a SCALE record explains itself
   ceiling = None
-  if world == 1 and not args.no_scaling_ceiling and args.scaling == "strong" and args.global_batch % 8 == 0:
+  if args.full and world == 1 and not args.no_scaling_ceiling and args.scaling == "strong" and args.global_batch % 8 == 0:
     share = args.global_batch // 8
     # two engines, the faster one counts (the record is an upper bound by definition).  Until the end of round 6 this leg now and then
     # measured 2.8 - 4.6 ms instead of 2.15: its engine's HIP streams were created while streams of earlier legs' engines existed and got
@@ -587,15 +597,15 @@ def main():
                "note": "single-GPU step time at the 8-GPU share of the global batch (the faster of two engines), no gradient exchange: an upper bound of value(8 GPUs) / value(1 GPU)"}
 
   pcie = None
-  if world == 1 and not args.no_input_pipeline:
+  if args.full and world == 1 and not args.no_input_pipeline:
     pcie = run_with_input_pipeline(per_gpu_batch(args, args.scaling, world), args.height, args.dtype, max(5, args.steps // 2), 3, device)
 
   f4 = None
-  if world == 1 and not args.no_bfmnet_train:
+  if args.full and world == 1 and not args.no_bfmnet_train:
     f4 = bfmnet_train_record(device, not args.no_cpu_baseline)
 
   secondary = None
-  if world == 1 and not args.no_secondary and args.dtype == "bf16":
+  if args.full and world == 1 and not args.no_secondary and args.dtype == "bf16":
     secondary = secondary_records(device, min(args.steps, 10), rank, world, group)
 
   if rank == 0:
@@ -627,7 +637,7 @@ def main():
       out["bfmnet_train"] = f4
     if secondary is not None:
       out.update(secondary)           # h512_bs2, h512_bs8, bs8_256, config3: top-level keys of the line
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
       out["cpu_baseline"] = cpu_baseline(args.height)
     print(json.dumps(out), flush=True)
   if world > 1:

@@ -1,5 +1,5 @@
 #!/bin/bash
-# the driver's round-end sequence: every -m gpu test, smoke(), the default bench line
+# every -m gpu test, smoke(), the bench line with all its sub-records (--full)
 cd "$GRAFT_REPO_ROOT"
 o=gpurun_out/full_check
 mkdir -p $o
@@ -7,7 +7,7 @@ timeout 2400 python -m pytest tests/ -x -q -m gpu > $o/pytest.log 2>&1
 grep -E "passed|failed|error" $o/pytest.log | tail -3
 grep -E "^E  |Error" $o/pytest.log | head -10
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1
-timeout 900 python bench.py > $o/bench.json 2> $o/bench.err
+timeout 900 python bench.py --full > $o/bench.json 2> $o/bench.err
 python - <<'P'
 import json
 d=json.load(open('gpurun_out/full_check/bench.json'))

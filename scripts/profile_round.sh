@@ -7,7 +7,7 @@ out=gpurun_out
 mkdir -p $out
 cd "${GRAFT_REPO_ROOT:-.}"
 export TMPDIR=/tmp
-python3 bench.py --steps 30 --warmup 10 > $out/${tag}_bench.json 2> $out/${tag}_bench.err
+python3 bench.py --full --steps 30 --warmup 10 > $out/${tag}_bench.json 2> $out/${tag}_bench.err
 # kernel stats twice: the step as it runs (three streams: co-running kernels stretch each other) and single-stream
 # (--tune streams=1: the per-kernel durations bench.py's HIP-event pass measures - it also runs on one stream)
 rocprofv3 --kernel-trace --stats -d $out/${tag}_prof -o ${tag} --output-format csv -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-profile --no-f32 --no-input-pipeline --no-bfmnet-train --no-scaling-ceiling --no-secondary > $out/${tag}_prof.log 2>&1

@@ -4,7 +4,7 @@ cd "${GRAFT_REPO_ROOT:-.}"
 o=gpurun_out/r06a; mkdir -p $o
 export TMPDIR=/tmp
 timeout 900 python -m pytest tests -m gpu -x -q > $o/pytest.log 2>&1; echo "pytest rc $?" >> $o/pytest.log; tail -5 $o/pytest.log
-( time python bench.py ) > $o/bench.json 2> $o/bench.err; tail -3 $o/bench.err
+( time python bench.py --full ) > $o/bench.json 2> $o/bench.err; tail -3 $o/bench.err
 python - <<'P'
 import json
 d=json.loads([l for l in open('gpurun_out/r06a/bench.json') if l.startswith('{')][-1])
