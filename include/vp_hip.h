@@ -437,6 +437,15 @@ int vp_gru_seq_state(const float* xg, const float* xc, const float* whg, const f
  *   vp_gan_loss          pixrefer.py:334-347: logits [3][m] = D(real1) | D(real2) | D(fake) -> predict [2][m], losses[0] = Discrim_loss,
  *                        losses[1] = Gen_loss_GAN, and the loss seeds w.r.t. the logits ([3][m][8] / [m][8] of dtype, channel 0)
  *   vp_dwconv7x3_bn_act  tinynet.py depthwise [7,3] stride 1 'same' + folded BatchNorm (bias) + relu6; w [21][c], float32 NHWC
+ *   vp_dwconv7x3_bn_act_t  the same with x / y stored as dtype (VP_F32: the column-pair kernel; VP_BF16: the bf16 trunk's kernel, f32 sums)
+ *   vp_conv_first_fwd    tinynet.py:168 stem: conv [9,5] stride [1,2] 'same' of x [b][h][w] (one channel) + folded bias + relu;
+ *                        w [45][cout] (row 5 kh + kw), y [b][h][ceil(w/2)][cout], float32
+ *   vp_dwproj_fwd        the second half of an inverted-residual block in ONE kernel (bfm_dwproj.hip), float32: depthwise [7,3] 'same'
+ *                        + folded bias + relu6 of ex [b][h][w][ce], then the 1x1 projection w_proj [ce][cout] + b_proj into
+ *                        y [b][h][w][cout] (add != 0: added to what y holds - the residual).  w_dw [21][ce], b_dw [ce].  The projection
+ *                        weights are packed as the forward plan packs them, into the workspace (vp_dwproj_workspace_bytes; 0 for a
+ *                        channel count the kernel never takes).  VP_ERR_ARG, before any launch, for a (w, ce, cout) without a kernel
+ *                        (w / cout pairs of MfccNet; ce a multiple of 16) or an expanded tensor of 0xF0000000 bytes or more
  *   vp_maxpool_hw        tf.layers.max_pooling2d(k, s, 'same') (tinynet.py:178-190, bfmnet.py:35); output ceil(h/sh) x ceil(w/sw)
  *   vp_gru_seq           tf.contrib.rnn.GRUCell under dynamic_rnn (bfmnet.py:53-61), 256 units: xg [b,t,512] / xc [b,t,256] are the input
  *                        projections (+ biases), whg [256][512] / whc [256][256] the recurrent halves of gates / candidate kernels
@@ -448,6 +457,11 @@ int vp_composite_fwd(const float* gen_out4, const float* targets, float* out4, f
 int vp_gan_loss(const float* logits, void* seed_d, void* seed_g, float* predict, float* losses, int m, float gan_weight, int dtype,
                 void* stream);
 int vp_dwconv7x3_bn_act(const float* x, const float* w, const float* bias, float* y, int b, int h, int wd, int c, void* stream);
+int vp_dwconv7x3_bn_act_t(const void* x, const float* w, const float* bias, void* y, int dtype, int b, int h, int wd, int c, void* stream);
+int vp_conv_first_fwd(const float* x, const float* w, const float* bias, float* y, int b, int h, int w_in, int cout, void* stream);
+size_t vp_dwproj_workspace_bytes(int ce, int cout);
+int vp_dwproj_fwd(const float* ex, const float* w_dw, const float* b_dw, const float* w_proj, const float* b_proj, float* y, int add, int b, int h,
+                  int w, int ce, int cout, void* workspace, void* stream);
 int vp_maxpool_hw(const float* x, float* y, int b, int h, int w, int c, int kh, int kw, int sh, int sw, void* stream);
 int vp_gru_seq(const float* xg, const float* xc, const float* whg, const float* whc, const int* seq_len, float* out, int b, int t,
                void* stream);

@@ -167,6 +167,10 @@ _SIGNATURES = {
     "vp_composite_fwd": (ctypes.c_int, [_P, _P, _P, _P, _P, ctypes.c_int, ctypes.c_int, _P]),
     "vp_gan_loss": (ctypes.c_int, [_P, _P, _P, _P, _P, ctypes.c_int, ctypes.c_float, ctypes.c_int, _P]),
     "vp_dwconv7x3_bn_act": (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P]),
+    "vp_dwconv7x3_bn_act_t": (ctypes.c_int, [_P, _P, _P, _P] + [ctypes.c_int] * 5 + [_P]),
+    "vp_conv_first_fwd": (ctypes.c_int, [_P, _P, _P, _P] + [ctypes.c_int] * 4 + [_P]),
+    "vp_dwproj_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
+    "vp_dwproj_fwd": (ctypes.c_int, [_P] * 6 + [ctypes.c_int] * 6 + [_P, _P]),
     "vp_maxpool_hw": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                      ctypes.c_int, _P]),
     "vp_gru_seq": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, ctypes.c_int, ctypes.c_int, _P]),

@@ -9,6 +9,13 @@ hipError_t launch_frame_window(const float* pcm, const float* window, float* fra
 hipError_t launch_logmel512(const float* pcm, const float* window, const float* w256, const float* w512, const float* mel, float* out, int B, int L, int F, int hop,
                             int nmel, hipStream_t st);
 hipError_t launch_mag_mel_log(const float* spec, int ld, int nb, const float* mel, int nmel, float* out, int nframes, hipStream_t st);
+// TF 'SAME': out = ceil(size / s), total pad = max((out - 1) s + k - size, 0), the odd unit goes to the end; *pb is the leading pad
+inline void same_pad(int size, int k, int s, int* pb, int* out) {
+  const int o = (size + s - 1) / s;
+  int total = (o - 1) * s + k - size;
+  if (total < 0) total = 0;
+  *pb = total / 2; *out = o;
+}
 hipError_t launch_conv_first(const float* x, const float* w, const float* bias, void* y, int out_bf16, int B, int H, int W, int Wo, int Cout, int pt, int pl, hipStream_t st);
 hipError_t launch_dwconv7x3(const void* x, const float* w, const float* bias, void* y, int is_bf16, int B, int H, int W, int C, hipStream_t st, int rev = 0);
 // bfm_dwproj.hip: depthwise 7x3 + ReLU6 + 1x1 projection (+ residual) of an inverted-residual block in one kernel (float32, mel widths <= 20);

@@ -288,6 +288,63 @@ int vp_dwconv7x3_bn_act(const float* x, const float* w, const float* bias, float
   return VP_OK;
 }
 
+int vp_dwconv7x3_bn_act_t(const void* x, const float* w, const float* bias, void* y, int dtype, int b, int h, int wd, int c, void* stream) {
+  if (!x || !w || !bias || !y || b < 1 || h < 1 || wd < 1 || c < 4 || (c & 3) || (dtype != VP_F32 && dtype != VP_BF16)) {
+    set_err("vp_dwconv7x3_bn_act_t: bad argument"); return VP_ERR_ARG;
+  }
+  VP_HIP_CHECK(launch_dwconv7x3(x, w, bias, y, dtype == VP_BF16, b, h, wd, c, (hipStream_t)stream));
+  return VP_OK;
+}
+
+// the stem as bfm_trunk launches it: same_pad of the [9,5] kernel at stride [1,2] (4 time rows either side; mel: the odd unit goes to the end)
+int vp_conv_first_fwd(const float* x, const float* w, const float* bias, float* y, int b, int h, int w_in, int cout, void* stream) {
+  if (!x || !w || !bias || !y || b < 1 || h < 1 || w_in < 1 || cout < 1) { set_err("vp_conv_first_fwd: bad argument"); return VP_ERR_ARG; }
+  int pt, ho, pl, wo;
+  same_pad(h, 9, 1, &pt, &ho);
+  same_pad(w_in, 5, 2, &pl, &wo);
+  VP_HIP_CHECK(launch_conv_first(x, w, bias, y, 0, b, h, w_in, wo, cout, pt, pl, (hipStream_t)stream));
+  return VP_OK;
+}
+
+// The fused depthwise + projection kernel on its own.  The projection weights go through the plan and the packing kernel that
+// bfm_carve / prepare_weights use for a fusable block (plan_gemm's geometry, perm = rowperm = 0), so the packed layout and wp_rows the
+// kernel reads are the ones of the forward.  Workspace: the [22][ce] tap + bias block, then the packed weights.
+static IgemmPlan dwproj_pack_plan(int pixels, int ce, int cout) {
+  IgemmPlan p = plan_fwd(make_geom(0, 1, 1, 0, 1, pixels, 1, ce, ce, cout), 0, 0);
+  p.pack.s_ch = cout;
+  p.pack.dst_off = 0;
+  p.pack.perm = 0; p.a.rowperm = 0;
+  return p;
+}
+
+size_t vp_dwproj_workspace_bytes(int ce, int cout) {
+  if (ce < 16 || ce % 16 || cout < 1) return 0;
+  return align256((size_t)22 * ce * sizeof(float)) + align256(dwproj_pack_plan(1, ce, cout).pack_elems * sizeof(float)) + 256;
+}
+
+int vp_dwproj_fwd(const float* ex, const float* w_dw, const float* b_dw, const float* w_proj, const float* b_proj, float* y, int add, int b, int h,
+                  int w, int ce, int cout, void* workspace, void* stream) {
+  if (!ex || !w_dw || !b_dw || !w_proj || !b_proj || !y || !workspace || b < 1 || h < 1 || w < 1) { set_err("vp_dwproj_fwd: bad argument"); return VP_ERR_ARG; }
+  if (!dwproj_eligible(w, ce, cout)) {
+    set_err("vp_dwproj_fwd: no kernel for mel width %d, %d expanded and %d output channels (dwproj_eligible)", w, ce, cout);
+    return VP_ERR_ARG;
+  }
+  const size_t ex_bytes = (size_t)b * h * w * ce * sizeof(float);
+  if (ex_bytes >= 0xF0000000ull) {
+    set_err("vp_dwproj_fwd: the expanded tensor is %zu bytes, the kernel's 32-bit lane offsets stop below 0xF0000000 (%llu)", ex_bytes, 0xF0000000ull);
+    return VP_ERR_ARG;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  float* wdw22 = (float*)workspace;
+  float* packed = (float*)((char*)workspace + align256((size_t)22 * ce * sizeof(float)));
+  VP_HIP_CHECK(hipMemcpyAsync(wdw22, w_dw, (size_t)21 * ce * sizeof(float), hipMemcpyDeviceToDevice, st));
+  VP_HIP_CHECK(hipMemcpyAsync(wdw22 + (size_t)21 * ce, b_dw, (size_t)ce * sizeof(float), hipMemcpyDeviceToDevice, st));
+  const IgemmPlan p = dwproj_pack_plan(b * h * w, ce, cout);
+  VP_HIP_CHECK(launch_pack_weights_one(p.pack, w_proj, packed, 0, st));
+  VP_HIP_CHECK(launch_dwproj(ex, wdw22, packed, p.a.wp_rows, b_proj, y, add ? 1 : 0, b, h, w, ce, cout, st));
+  return VP_OK;
+}
+
 int vp_maxpool_hw(const float* x, float* y, int b, int h, int w, int c, int kh, int kw, int sh, int sw, void* stream) {
   if (!x || !y || b < 1 || h < 1 || w < 1 || c < 4 || (c & 3) || kh < 1 || kw < 1 || sh < 1 || sw < 1) { set_err("vp_maxpool_hw: bad argument"); return VP_ERR_ARG; }
   // TF 'same': out = ceil(in / stride); total pad = max((out-1)*stride + k - in, 0), the odd unit goes to the end

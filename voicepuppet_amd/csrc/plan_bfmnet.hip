@@ -28,13 +28,6 @@ struct Bump {
   void* alloc(size_t bytes) { off = (off + 255) & ~(size_t)255; void* p = base ? base + off : nullptr; off += bytes; return p; }
 };
 
-void same_pad(int size, int k, int s, int* pb, int* out) {
-  const int o = (size + s - 1) / s;
-  int total = (o - 1) * s + k - size;
-  if (total < 0) total = 0;
-  *pb = total / 2; *out = o;
-}
-
 // a 1x1 conv / dense layer as an igemm over `pixels` rows
 struct Gemm {
   int cin = 0, cout = 0;
