@@ -15,6 +15,7 @@
  *   vp_bfmnet_*     replaces  voicepuppet/bfmnet/bfmnet.py:189-213,325-333 + tinynet.py:159-212
  *   vp_render_colors   replaces  utils/cython/mesh_core.h:63 _render_colors_core (mesh_core.cpp:169-231)
  *   vp_bfm_reconstruct replaces  utils/reconstruct_mesh.py:198-223 Reconstruction_rotation + infer_bfmvid.py:92-99
+ *   vp_puppet_*        replaces  infer_bfmvid.py:110-121, :223-224, :229-238 for the rows of many talkers (stream groups)
  *
  * Conventions: every function returns 0 on success and a negative vp_status otherwise (never throws);
  * all tensor pointers are DEVICE pointers owned by the caller (NHWC, row-major); nothing is allocated
@@ -511,6 +512,14 @@ size_t vp_bfm_reconstruct_workspace_bytes(int nver, int ntri, int frames);
 int vp_bfm_reconstruct(const vp_bfm_model* m, const float* coeff, const double* rotation, int frames, int shared_texture,
                        double* face_shape, double* face_texture, double* face_color, double* face_projection, double* z_buffer,
                        float* vertices, float* colors, void* workspace, size_t workspace_bytes, void* stream);
+/* The same for rows of several identities in one call (stream groups: frames of many talkers in one render launch chain).  The
+ * texture - vp_bfm_reconstruct(shared_texture = 1) computes it once, from row 0 - is computed once per identity present: texture t
+ * (0 .. textures-1) from the coefficients of row tex_src[t], and row r is lit with texture tex_row[r].  tex_src [textures] and
+ * tex_row [frames] are DEVICE int arrays (the caller sends them with its other per-push tables); entries out of range leave the
+ * row unwritten.  Per-row arithmetic is that of vp_bfm_reconstruct: the rows of one identity equal, bit for bit, what
+ * vp_bfm_reconstruct(shared_texture = 1) returns for that identity's frames alone.  Same workspace query; never waits. */
+int vp_bfm_reconstruct_rows(const vp_bfm_model* m, const float* coeff, const double* rotation, int frames, const int* tex_src, int textures,
+                            const int* tex_row, float* vertices, float* colors, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * BFMNet TRAINING step (voicepuppet/bfmnet/bfmnet.py:215-323, tinynet.py:7-212): the non-GEMM kernels, float32 NHWC,
@@ -614,6 +623,52 @@ size_t vp_resize_paste_workspace_bytes(int dst_h, int dst_w);
 int vp_resize_paste_u8(const unsigned char* src, int frames, int src_h, int src_w, int dst_h, int dst_w, int swap_rb,
                        unsigned char* canvas, int canvas_h, int canvas_w, int y0, int x0, void* workspace, void* stream);
 int vp_resize_linear_table(int src_size, int dst_size, int rows, int* ofs, short* a0, short* a1, int* row1);
+
+/* ------------------------------------------------------------------------------------------------
+ * Frames for stream groups: the steps between a group push's packed expression coefficients and the generator's inputs, for rows of
+ * up to VP_PUPPET_MAX_SLOTS talkers, each with its own photo, coefficients and paste geometry (voicepuppet_amd.stream.PuppetStreamGroup).
+ * A handle owns the per-slot state in a caller-owned device workspace: photo coefficients [slots,257], the two float reference panels
+ * [slots,H,H,3] each, the slot's cv2.resize tables.  attach may wait (once per talker); splice / condition only enqueue and read their
+ * per-push tables from DEVICE memory (the caller stages them through pinned memory).
+ *   vp_puppet_splice      replaces infer_bfmvid.py:223-224 (np.tile + np.concatenate of the photo's coefficients around the predicted
+ *                         expression).  rows [count][4] int: {slot, row of expr, -, -}; coeff_out [count,257].  Copies only.
+ *   vp_puppet_condition   replaces, for `count` <= frame_batch rows in ONE launch: render_face's cvtColor + cv2.resize + paste into a zero
+ *                         canvas (infer_bfmvid.py:110-121), the caller's second channel swap and /255 (:233), the reference panels in
+ *                         channels 0:3 of inputs / fg_inputs (:200-203, :229-230) and the background target of the row's global frame
+ *                         index or 0.5 (:236-238).  rows [count][4] int: {slot, row of faces or -1, row of the background bank or -1,
+ *                         global frame index}.  faces [face_rows][face_size][face_size][3] uint8 in rasteriser order.  A slot attached
+ *                         without coefficients takes its reference panel for channels 3:6.  inputs [frame_batch,H,H,6], fg_inputs /
+ *                         targets [frame_batch,H,H,3] float32; the uint8 -> float step gives the bits of the expression it replaces (csrc/puppet_cond.hip).
+ *                         A row whose table entries are out of range is left unwritten.
+ * ---------------------------------------------------------------------------------------------- */
+#define VP_PUPPET_MAX_SLOTS 128
+typedef struct vp_puppet_desc {
+  int struct_bytes;       /* sizeof(vp_puppet_desc) of the caller's build: must equal vp_puppet_desc_size() */
+  int slots;              /* 1 .. VP_PUPPET_MAX_SLOTS */
+  int frame_batch;        /* rows per vp_puppet_condition launch (the generator plan's batch): 1 .. 1024 */
+  int img_size;           /* H: a multiple of 256 (every image line is then whole 1 KB store runs) */
+  int face_size;          /* side of the rasterised face images: 224 */
+} vp_puppet_desc;
+size_t vp_puppet_desc_size(void);
+typedef struct vp_puppet vp_puppet_t;
+/* 0 on a refused descriptor (vp_last_error says why) */
+size_t vp_puppet_workspace_bytes(const vp_puppet_desc* d);
+int vp_puppet_create(const vp_puppet_desc* d, void* workspace, size_t workspace_bytes, void* stream, vp_puppet_t** out);
+void vp_puppet_destroy(vp_puppet_t* h);
+/* refer / fg_refer: DEVICE float [H,H,3] (copied).  photo_coeff: HOST float [257], or NULL for a slot conditioned on its reference panel
+ * (side / y0 / x0 are then ignored).  side: the face is resized to side x side (1 .. 4 * img_size) and pasted at (y0, x0); its
+ * resize tables (vp_resize_linear_table) are built here, once. */
+int vp_puppet_attach(vp_puppet_t* h, int slot, const float* refer, const float* fg_refer, const float* photo_coeff, int side, int y0, int x0,
+                     void* stream);
+/* bank: DEVICE uint8 [count,H,H,3], caller-owned, the backgrounds that exist (the table rows of vp_puppet_condition index it) */
+int vp_puppet_set_backgrounds(vp_puppet_t* h, const unsigned char* bank, int count);
+int vp_puppet_splice(vp_puppet_t* h, const float* expr, int expr_rows, const int* rows, int count, float* coeff_out, void* stream);
+int vp_puppet_condition(vp_puppet_t* h, const unsigned char* faces, int face_rows, const int* rows, int count, float* inputs, float* fg_inputs,
+                        float* targets, void* stream);
+/* "coeff" [slots,257], "refer" / "fg" [slots,H,H,3]: the per-slot state in the workspace */
+int vp_puppet_tensor(vp_puppet_t* h, const char* name, void** ptr, int64_t shape[4]);
+/* Host only: info = {kind (0 empty, 1 reference panel, 2 copy, 3 exact 2x reduction, 4 bilinear), side, y0, x0} */
+int vp_puppet_slot_info(const vp_puppet_t* h, int slot, int info[4]);
 
 /* Host helper: CRC-32C (Castagnoli, the checksum of TensorFlow checkpoint bundles) of `n` bytes, continuing from `crc` (0 to start). */
 unsigned vp_crc32c(const void* data, size_t n, unsigned crc);

@@ -46,6 +46,14 @@ class BfmStreamGroupDesc(ctypes.Structure):
 BFMSTREAM_GROUP_MAX_SLOTS = 128      # include/vp_hip.h VP_BFMSTREAM_GROUP_MAX_SLOTS
 
 
+class PuppetDesc(ctypes.Structure):
+  _fields_ = [("struct_bytes", ctypes.c_int), ("slots", ctypes.c_int), ("frame_batch", ctypes.c_int), ("img_size", ctypes.c_int),
+              ("face_size", ctypes.c_int)]
+
+
+PUPPET_MAX_SLOTS = 128               # include/vp_hip.h VP_PUPPET_MAX_SLOTS
+
+
 class BfmModel(ctypes.Structure):
   _fields_ = [("nver", ctypes.c_int), ("ntri", ctypes.c_int), ("meanshape", ctypes.c_void_p), ("idBase", ctypes.c_void_p),
               ("exBase", ctypes.c_void_p), ("meantex", ctypes.c_void_p), ("texBase", ctypes.c_void_p), ("tri", ctypes.c_void_p),
@@ -152,6 +160,17 @@ _SIGNATURES = {
     "vp_bfmstream_finish": (ctypes.c_int, [_P, _P, _P, _P]),
     "vp_bfmstream_tensor": (ctypes.c_int, [_P, ctypes.c_char_p, ctypes.POINTER(_P), ctypes.POINTER(ctypes.c_int64)]),
     "vp_bfmstream_group_desc_size": (ctypes.c_size_t, []),
+    "vp_puppet_desc_size": (ctypes.c_size_t, []),
+    "vp_puppet_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(PuppetDesc)]),
+    "vp_puppet_create": (ctypes.c_int, [ctypes.POINTER(PuppetDesc), _P, ctypes.c_size_t, _P, ctypes.POINTER(_P)]),
+    "vp_puppet_destroy": (None, [_P]),
+    "vp_puppet_attach": (ctypes.c_int, [_P, ctypes.c_int, _P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P]),
+    "vp_puppet_set_backgrounds": (ctypes.c_int, [_P, _P, ctypes.c_int]),
+    "vp_puppet_splice": (ctypes.c_int, [_P, _P, ctypes.c_int, _P, ctypes.c_int, _P, _P]),
+    "vp_puppet_condition": (ctypes.c_int, [_P, _P, ctypes.c_int, _P, ctypes.c_int, _P, _P, _P, _P]),
+    "vp_puppet_tensor": (ctypes.c_int, [_P, ctypes.c_char_p, ctypes.POINTER(_P), ctypes.POINTER(ctypes.c_int64)]),
+    "vp_puppet_slot_info": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
+    "vp_bfm_reconstruct_rows": (ctypes.c_int, [ctypes.POINTER(BfmModel), _P, _P, ctypes.c_int, _P, ctypes.c_int, _P, _P, _P, _P, ctypes.c_size_t, _P]),
     "vp_bfmstream_group_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(BfmStreamGroupDesc)]),
     "vp_bfmstream_group_plan_info": (ctypes.c_int, [ctypes.POINTER(BfmStreamGroupDesc), ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
     "vp_bfmstream_group_create": (ctypes.c_int, [ctypes.POINTER(BfmStreamGroupDesc), _P, ctypes.c_size_t, _P, _P, ctypes.POINTER(_P)]),
@@ -253,6 +272,10 @@ def lib():
       want = int(l.vp_bfmstream_group_desc_size())
       if want != ctypes.sizeof(BfmStreamGroupDesc):
         raise RuntimeError("%s: vp_bfmstream_group_desc is %d bytes in the library, %d in this binding" % (LIB_PATH, want, ctypes.sizeof(BfmStreamGroupDesc)))
+    if hasattr(l, "vp_puppet_desc_size") and l.vp_puppet_desc_size.argtypes is not None:
+      want = int(l.vp_puppet_desc_size())
+      if want != ctypes.sizeof(PuppetDesc):
+        raise RuntimeError("%s: vp_puppet_desc is %d bytes in the library, %d in this binding" % (LIB_PATH, want, ctypes.sizeof(PuppetDesc)))
     _lib = l
   return _lib
 

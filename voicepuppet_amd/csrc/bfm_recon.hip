@@ -27,6 +27,8 @@ struct LinearArgs {
   const float* coeff;                    // [T,257]
   double* out;                           // [T,rows]
   int rows, frames;
+  const int* src_row;                    // optional: output frame f is computed from coefficient row src_row[f] (of src_rows rows)
+  int src_rows;
 };
 
 // out[f][row] = sum_k base[k][row] * coeff[f][k] + mean[row] - sub[row % 3].  One thread per row: the k-major base makes
@@ -38,7 +40,9 @@ __global__ __launch_bounds__(BFM_LIN_THREADS) void bfm_linear_kernel(LinearArgs 
   const int f0 = blockIdx.y * BFM_FT;
   for (int i = threadIdx.x; i < K * BFM_FT; i += BFM_LIN_THREADS) {
     const int k = i / BFM_FT, f = f0 + i % BFM_FT;
-    sc[i] = (f < a.frames) ? (double)a.coeff[(size_t)f * 257 + (k < a.k1 ? a.o1 + k : a.o2 + k - a.k1)] : 0.0;
+    int fr = f;
+    if (a.src_row && f < a.frames) { fr = a.src_row[f]; if (fr < 0 || fr >= a.src_rows) fr = -1; }
+    sc[i] = (f < a.frames && fr >= 0) ? (double)a.coeff[(size_t)fr * 257 + (k < a.k1 ? a.o1 + k : a.o2 + k - a.k1)] : 0.0;
   }
   __syncthreads();
   const int row = blockIdx.x * BFM_LIN_THREADS + threadIdx.x;
@@ -99,6 +103,7 @@ struct VertexArgs {
   float* vertices;           // [T,N,3]  x, 224-y, z_buffer   (infer_bfmvid.py:92-96)
   float* colors;             // [T,N,3]  clip(0,255) -> int -> float   (:98,102)
   int nver, ntri, frames, tex_frames;
+  const int* tex_row;        // optional [T]: the texture row of each frame (rows of several identities)
   double focal, center;
   double sh[9];              // a_i*c_i products of Illumination_layer (:138-143), evaluated on the host in double
 };
@@ -107,6 +112,8 @@ __global__ __launch_bounds__(256) void bfm_vertex_kernel(VertexArgs a) {
   const int v = blockIdx.x * 256 + threadIdx.x;
   const int f = blockIdx.y;
   if (v >= a.nver) return;
+  int tr = a.tex_frames == 1 ? 0 : f;
+  if (a.tex_row) { tr = a.tex_row[f]; if (tr < 0 || tr >= a.tex_frames) return; }
   const double* R = a.rot + f * 9;
   const double r00 = R[0], r01 = R[1], r02 = R[2], r10 = R[3], r11 = R[4], r12 = R[5], r20 = R[6], r21 = R[7], r22 = R[8];
   // one-ring vertex normal
@@ -142,7 +149,7 @@ __global__ __launch_bounds__(256) void bfm_vertex_kernel(VertexArgs a) {
   Y[6] = a.sh[3] * (3.0 * (mz * mz) - 1.0);
   Y[7] = -a.sh[2] * mx * mz;
   Y[8] = a.sh[4] * (mx * mx - my * my);
-  const double* TX = a.tex + ((size_t)(a.tex_frames == 1 ? 0 : f) * a.nver + v) * 3;
+  const double* TX = a.tex + ((size_t)tr * a.nver + v) * 3;
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     double lit = 0;
@@ -163,21 +170,21 @@ size_t vp_bfm_reconstruct_workspace_bytes(int nver, int ntri, int frames) {
   return ((size_t)frames * nver * 3 * 2 + (size_t)frames * (ntri + 1) * 3) * sizeof(double) + 512;
 }
 
-int vp_bfm_reconstruct(const vp_bfm_model* m, const float* coeff, const double* rotation, int frames, int shared_texture,
-                       double* face_shape, double* face_texture, double* face_color, double* face_projection, double* z_buffer,
-                       float* vertices, float* colors, void* workspace, size_t workspace_bytes, void* stream) {
+static int reconstruct_impl(const char* who, const vp_bfm_model* m, const float* coeff, const double* rotation, int frames, int tex_frames,
+                            const int* tex_src, const int* tex_row,
+                            double* face_shape, double* face_texture, double* face_color, double* face_projection, double* z_buffer,
+                            float* vertices, float* colors, void* workspace, size_t workspace_bytes, void* stream) {
   if (!m || !coeff || !rotation || !vertices || !colors || !workspace || frames < 1 || m->nver < 1 || m->ntri < 1 || !m->idBase ||
       !m->exBase || !m->texBase || !m->meanshape || !m->meantex || !m->tri || !m->point_buf) {
-    vp::set_err("vp_bfm_reconstruct: bad argument");
+    vp::set_err("%s: bad argument", who);
     return VP_ERR_ARG;
   }
   if (workspace_bytes < vp_bfm_reconstruct_workspace_bytes(m->nver, m->ntri, frames)) {
-    vp::set_err("vp_bfm_reconstruct: workspace too small");
+    vp::set_err("%s: workspace too small", who);
     return VP_ERR_ARG;
   }
   hipStream_t st = (hipStream_t)stream;
   const int rows = 3 * m->nver;
-  const int tex_frames = shared_texture ? 1 : frames;
   double* shape = (double*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
   double* tex = face_texture ? face_texture : shape + (size_t)frames * rows;
   double* fn = shape + (size_t)frames * rows * 2;
@@ -189,18 +196,36 @@ int vp_bfm_reconstruct(const vp_bfm_model* m, const float* coeff, const double* 
   hipLaunchKernelGGL(vp::bfm_linear_kernel, dim3(nb, (frames + vp::BFM_FT - 1) / vp::BFM_FT), dim3(vp::BFM_LIN_THREADS), 0, st, la);
   vp::LinearArgs lt{};
   lt.b1 = m->texBase; lt.k1 = 80; lt.o1 = 144; lt.b2 = nullptr; lt.k2 = 0; lt.o2 = 0; lt.mean = m->meantex;
-  lt.coeff = coeff; lt.out = tex; lt.rows = rows; lt.frames = tex_frames;
+  lt.coeff = coeff; lt.out = tex; lt.rows = rows; lt.frames = tex_frames; lt.src_row = tex_src; lt.src_rows = frames;
   hipLaunchKernelGGL(vp::bfm_linear_kernel, dim3(nb, (tex_frames + vp::BFM_FT - 1) / vp::BFM_FT), dim3(vp::BFM_LIN_THREADS), 0, st, lt);
   hipLaunchKernelGGL(vp::bfm_fnormal_kernel, dim3((m->ntri + 1 + 255) / 256, frames), dim3(256), 0, st, shape, m->tri, fn, m->nver, m->ntri);
   vp::VertexArgs va{};
   va.shape = shape; va.tex = tex; va.fn = fn; va.point_buf = m->point_buf; va.rot = rotation; va.coeff = coeff;
   va.face_shape = face_shape; va.face_color = face_color; va.face_projection = face_projection; va.z_buffer = z_buffer;
-  va.vertices = vertices; va.colors = colors; va.nver = m->nver; va.ntri = m->ntri; va.frames = frames; va.tex_frames = tex_frames;
+  va.vertices = vertices; va.colors = colors; va.nver = m->nver; va.ntri = m->ntri; va.frames = frames; va.tex_frames = tex_frames; va.tex_row = tex_row;
   va.focal = m->focal; va.center = m->image_center;
   for (int i = 0; i < 5; ++i) va.sh[i] = m->sh[i];
   hipLaunchKernelGGL(vp::bfm_vertex_kernel, dim3((m->nver + 255) / 256, frames), dim3(256), 0, st, va);
   VP_HIP_CHECK(hipGetLastError());
   return VP_OK;
+}
+
+int vp_bfm_reconstruct(const vp_bfm_model* m, const float* coeff, const double* rotation, int frames, int shared_texture,
+                       double* face_shape, double* face_texture, double* face_color, double* face_projection, double* z_buffer,
+                       float* vertices, float* colors, void* workspace, size_t workspace_bytes, void* stream) {
+  return reconstruct_impl("vp_bfm_reconstruct", m, coeff, rotation, frames, shared_texture ? 1 : frames, nullptr, nullptr, face_shape, face_texture,
+                          face_color, face_projection, z_buffer, vertices, colors, workspace, workspace_bytes, stream);
+}
+
+// rows of several identities: texture t from coefficient row tex_src[t], row r lit with texture tex_row[r] (include/vp_hip.h)
+int vp_bfm_reconstruct_rows(const vp_bfm_model* m, const float* coeff, const double* rotation, int frames, const int* tex_src, int textures,
+                            const int* tex_row, float* vertices, float* colors, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!tex_src || !tex_row || textures < 1 || textures > frames) {
+    vp::set_err("vp_bfm_reconstruct_rows: bad argument (1 .. frames textures, device tables)");
+    return VP_ERR_ARG;
+  }
+  return reconstruct_impl("vp_bfm_reconstruct_rows", m, coeff, rotation, frames, textures, tex_src, tex_row, nullptr, nullptr, nullptr, nullptr,
+                          nullptr, vertices, colors, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

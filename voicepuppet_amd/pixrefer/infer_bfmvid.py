@@ -141,21 +141,28 @@ def background_target(i, img_size):
   return np.ascontiguousarray(ImageLoader(resize=(img_size, img_size)).get_data(bg)[:, :, ::-1], dtype=np.float32)
 
 
+def paste_geometry(center_x, center_y, ratio, transform_params, face_size=224):
+  """render_face's paste arithmetic (infer_bfmvid.py:83-86, :111-121): the rasterised face_size x face_size image is resized to
+  side x side and pasted with its top-left corner at row y0, column x0 of the canvas: (side, y0, x0)."""
+  ratio = ratio * transform_params[2]
+  tx = -int((transform_params[3] / ratio))
+  ty = -int((transform_params[4] / ratio))
+  side = int(round(face_size / ratio))
+  cx, cy = side // 2, side // 2
+  return side, center_y - cy - ty, center_x - cx - tx
+
+
 def render_faces(renderer, center_x, center_y, ratio, bfm_coeff_seq, img_shape, transform_params, on_device=False, angles=None):
   """render_face (infer_bfmvid.py:79-122) for every frame of the clip: one device pass for reconstruction + rasterisation, then the
   reference's channel swap / cv2.resize / paste for all frames in one more launch (csrc/resize.hip: OpenCV's fixed-point bilinear,
   byte for byte; voicepuppet_amd/utils/cv_resize.py)."""
   from voicepuppet_amd.utils.cv_resize import resize_paste_u8
-  ratio = ratio * transform_params[2]
-  tx = -int((transform_params[3] / ratio))
-  ty = -int((transform_params[4] / ratio))
   T = bfm_coeff_seq.shape[0]
   if angles is None:
     angles = angle_sequence(T)                       # (a stream passes the head-sway angles of its frames' global indices)
   images, _ = renderer(bfm_coeff_seq.astype(np.float32), angles)      # [T, 224, 224, 3] uint8 on the device, rasteriser order
-  side = int(round(images.shape[1] / ratio))
-  cx, cy = side // 2, side // 2
-  out = resize_paste_u8(images, side, side, (img_shape[0], img_shape[1]), center_y - cy - ty, center_x - cx - tx, swap_rb=True)   # :110-121
+  side, y0, x0 = paste_geometry(center_x, center_y, ratio, transform_params, images.shape[1])
+  out = resize_paste_u8(images, side, side, (img_shape[0], img_shape[1]), y0, x0, swap_rb=True)   # :110-121
   return out if on_device else out.cpu().numpy()      # on_device: the clip loop consumes the frames where they are (no PCIe round trip)
 
 

@@ -1,0 +1,148 @@
+#!/usr/bin/env python
+# -*- encoding: utf-8 -*-
+"""Streaming end-to-end inference for many talkers at once: infer_stream's command line with a list file in place of one image / audio.
+
+    python voicepuppet/pixrefer/infer_streams.py --config_path config/params.yml --chunk_ms 40 --output_dir output <list.txt>
+
+Every line of the list is `image audio.wav [photo.npz]`: a talker's 1536x512 photo, its wav and, optionally, the photo's coefficient
+npz (infer_bfmvid's --bfmcoeff).  Talker s (the s-th line) is slot s of one voicepuppet_amd.stream.PuppetStreamGroup: every push hands
+each talker that still has audio its next chunk_ms milliseconds, all frames that became exact run through render and generator
+together, and talker s's frames go to <output_dir>/<s>/<i>.jpg.  The per-push latency is logged.  A talker whose wav has ended is
+finished in a push of its own, as infer_stream finishes its clip.  --seed S gives every talker the ears of an infer_stream run on it
+alone under np.random.seed(S) (each slot draws from its own generator); without it the ears come from numpy's global generator in slot
+order.  Each directory is muxed with its wav as infer_stream muxes (when ffmpeg exists).
+"""
+import logging
+import math
+import os
+import shutil
+import subprocess
+import sys
+import time
+from optparse import OptionParser
+
+import numpy as np
+
+sys.path.append(os.getcwd())
+
+from voicepuppet_amd.generator.generator import DataGenerator
+from voicepuppet_amd.generator.loader import ImageLoader, WavLoader
+
+logging.basicConfig(level=logging.INFO, format='%(asctime)s - %(name)s - %(levelname)s - %(message)s')
+logger = logging.getLogger(__name__)
+
+
+def read_list(path):
+  """[(image, audio, npz or None)] of a list file; blank lines and lines starting with # are skipped."""
+  talkers = []
+  with open(path) as f:
+    for line in f:
+      w = line.split()
+      if not w or w[0].startswith('#'):
+        continue
+      if len(w) not in (2, 3):
+        raise ValueError('%s: expected "image audio.wav [photo.npz]", got %r' % (path, line.strip()))
+      talkers.append((w[0], w[1], w[2] if len(w) == 3 else None))
+  return talkers
+
+
+def main(argv=None):
+  cmd_parser = OptionParser(usage="usage: %prog [options] --config_path <> list_file")
+  cmd_parser.add_option('--config_path', type="string", dest="config_path", help='the config yaml file')
+  cmd_parser.add_option('--frame_batch', type="int", dest="frame_batch", default=8, help='frames per generator launch')
+  cmd_parser.add_option('--output_dir', type="string", dest="output_dir", default='output', help='talker s writes <output_dir>/<s>/<i>.jpg')
+  cmd_parser.add_option('--chunk_ms', type="float", dest="chunk_ms", default=40.0, help='audio per talker and push, milliseconds')
+  cmd_parser.add_option('--seed', type="int", dest="seed", default=None, help='every talker draws its ears as np.random.seed(SEED) would alone')
+  opts, argv = cmd_parser.parse_args(argv)
+
+  if (opts.config_path is None or len(argv) != 1):
+    logger.error('Please check your parameters.')
+    exit(0)
+  config_path = opts.config_path
+  if (not os.path.exists(config_path)):
+    logger.error('config_path not exists')
+    exit(0)
+  if not opts.chunk_ms > 0:
+    logger.error('--chunk_ms must be positive')
+    exit(0)
+
+  talkers = read_list(argv[0])
+  S = len(talkers)
+  if S < 1:
+    logger.error('%s lists no talker', argv[0])
+    exit(0)
+  out_dirs = [os.path.join(opts.output_dir, str(s)) for s in range(S)]
+  for d in out_dirs:
+    if os.path.exists(d):
+      shutil.rmtree(d)
+    os.makedirs(d)
+
+  gen = DataGenerator(config_path)
+  params = gen.params
+  params.batch_size = 1
+  gen.set_params(params)
+  pcm = [WavLoader(sr=gen.sample_rate).get_data(a).astype(np.float32) for _, a, _ in talkers]
+
+  from voicepuppet_amd.stream import PuppetStreamGroup
+  chunk = max(1, int(round(opts.chunk_ms * gen.sample_rate / 1000.0)))
+  frame_ms = 1000.0 * gen.frame_wav_scale / gen.sample_rate
+  group = PuppetStreamGroup(config_path, S, frame_batch=opts.frame_batch, max_chunk_frames=max(1, int(math.ceil(opts.chunk_ms / frame_ms))))
+  for s, (image, _, npz) in enumerate(talkers):
+    group.attach(s, ImageLoader().get_data(image)[:, :, ::-1], npz)      # RGB float in [0,1], 512 x 1536
+  rngs = [np.random.RandomState(opts.seed) for _ in range(S)] if opts.seed is not None else None
+  logger.info('streaming %d talkers in chunks of %d samples (%.0f ms), lookahead %.0f ms', S, chunk, opts.chunk_ms, group.audio.lookahead_ms)
+
+  from PIL import Image
+  from concurrent.futures import ThreadPoolExecutor
+  pool = ThreadPoolExecutor(max_workers=max(1, min(8, (os.cpu_count() or 2) - 1)))
+  pending, lat, total = [], [], 0
+
+  def write_jpg(arr_u8, path):
+    Image.fromarray(arr_u8).save(path)
+
+  def push(chunks, finish):
+    ears = None
+    if rngs is not None:
+      k = group.audio.ready({s: len(c) for s, c in chunks.items()}, finish)
+      ears = {s: rngs[s].rand(k[s], 1).astype(np.float32) / 100 for s in range(S) if k[s]}
+    t = time.perf_counter()
+    res = group.push(chunks, finish=finish, ears=ears)
+    n = sum(len(v) for v in res.values())
+    frames = group.last_frames.cpu().numpy() if n else None            # the one wait of the push: the frames go to the encoders
+    lat.append(1000.0 * (time.perf_counter() - t))
+    row = 0
+    for s in sorted(res):
+      for i, _ in res[s]:
+        pending.append(pool.submit(write_jpg, frames[row], os.path.join(out_dirs[s], '{}.jpg'.format(i))))
+        row += 1
+    logger.debug('push %d: %d frames, %.2f ms', len(lat), n, lat[-1])
+    return n
+
+  try:
+    at, live = 0, set(range(S))
+    while live:
+      chunks = {s: pcm[s][at:at + chunk] for s in live if at < pcm[s].shape[0]}
+      if chunks:
+        total += push(chunks, ())
+      ended = sorted(s for s in live if at + chunk >= pcm[s].shape[0])
+      if ended:
+        total += push({}, ended)
+        live -= set(ended)
+      at += chunk
+    for f in pending:
+      f.result()
+  finally:
+    pool.shutdown()
+  logger.info('%d pushes: latency median %.2f ms, max %.2f ms (frames included); %d frames of %d talkers', len(lat), float(np.median(lat)),
+              float(np.max(lat)), total, S)
+
+  for s, (_, audio, _) in enumerate(talkers):
+    if shutil.which('ffmpeg'):
+      subprocess.call(['ffmpeg', '-i', os.path.join(out_dirs[s], '%d.jpg'), '-i', audio, '-c:v', 'libx264', '-c:a', 'aac',
+                       '-strict', 'experimental', '-y', out_dirs[s] + '.mp4'])
+    else:
+      logger.warning('ffmpeg not found: frames are in %s/, no mp4 written', out_dirs[s])
+
+
+if (__name__ == '__main__'):
+  main()

@@ -5,9 +5,10 @@ has arrived: the frames infer_bfmvid computes offline for the whole clip (same c
 forward.  The lookahead is the receptive field's right side (right_frames video frames) plus the half frame the log-mel window reaches
 past its hop; nothing is approximated.  push / finish never wait on the device (host data is staged through pinned memory).
 
-PuppetStream puts the rest of infer_bfmvid behind it: splice_coeff -> ClipRenderer (the head-sway state carried across pushes) ->
-PixReferNet -> uint8 frames, conditioned on the same background and reference panels by global frame index.  It waits for each push's
-coefficients (the splice and the sway state are host-side, as in infer_bfmvid).
+PuppetStreamGroup puts the rest of infer_bfmvid behind an AudioStreamGroup, for many talkers at once: splice_coeff -> ClipRenderer (the
+head-sway state carried across pushes) -> PixReferNet -> uint8 frames, conditioned on the same background and reference panels by global
+frame index (libvp_hip.so: vp_puppet_*, vp_bfm_reconstruct_rows).  Its push only enqueues too: the sway state and every per-row table
+are host arithmetic on frame counts.  PuppetStream is a group of one slot that hands out host arrays.
 """
 import ctypes
 
@@ -232,6 +233,16 @@ class AudioStreamGroup:
   def push(self, pcm_by_slot, finish=(), ears=None):
     """{slot: 1-D f32 pcm (numpy or tensor)} -> {slot: coefficients [k, 64]} for every slot pushed or finished.  Enqueues only: the
     tensors are ready when the current stream reaches them."""
+    out, k, sizes = self.push_packed(pcm_by_slot, finish, ears)
+    res, row = {}, 0
+    for s in range(self.slots):
+      if s in sizes:
+        res[s] = out[row:row + k[s]]
+      row += k[s]
+    return res
+
+  def push_packed(self, pcm_by_slot, finish=(), ears=None):
+    """push, returning (the packed coefficients [K, 64] in slot order, frames per slot, {slot pushed or finished: samples})."""
     slots = sorted(set(int(s) for s in pcm_by_slot) | set(int(s) for s in finish))
     for s in slots:
       if not 0 <= s < self.slots:
@@ -265,12 +276,7 @@ class AudioStreamGroup:
     n, fin = self._arrays(sizes, finish)
     _lib.check(self.L.vp_bfmstream_group_push(self.h, _ptr(pcm), n, fin, _ptr(e), _ptr(out if K else None), _stream()),
                "vp_bfmstream_group_push")
-    res, row = {}, 0
-    for s in range(self.slots):
-      if s in sizes:
-        res[s] = out[row:row + k[s]]
-      row += k[s]
-    return res
+    return out, k, sizes
 
   def reset_slot(self, slot):
     """Slot `slot` starts a new clip; the other slots are untouched."""
@@ -320,18 +326,117 @@ class HeadSway:
     return out
 
 
-class PuppetStream:
-  """Streaming infer_bfmvid: push(pcm) / finish() -> [(global frame index, uint8 frame [H, W, 3] RGB)] of the frames that became
-  exact.  image: the 512 x 1536 input (RGB float in [0,1], as infer_bfmvid reads it); bfmcoeff: the photo's coefficient npz
-  (bfmcoeff, transform_params, center_x, center_y, ratio) - with it and BFM/BFM_model_front.mat every frame is conditioned on its
-  rendered face, without them on the reference 3-D face panel.  BFMNet / PixReferNet weights: the checkpoints infer_bfmvid restores
-  (ckpt_bfmnet/bfmnet-65000, ckpt_pixrefer/pixrefernet-20000; TF prefix or .npz), the generator from infer_bfmvid's cache."""
+class PuppetRowPlan:
+  """Host side of a PuppetStreamGroup push, a pure function of the frame counts: which slot, global frame index and head-sway angles
+  every packed row of a push has.  Per slot the angles of consecutive pushes concatenate to infer_bfmvid.angle_sequence(total) and
+  the indices to 0 .. total-1; reset_slot starts a slot's clip again.  No device involved."""
 
-  def __init__(self, config_path, image, bfmcoeff=None, frame_batch=8, max_chunk_frames=1, dtype="f32", img_size=512):
+  def __init__(self, slots):
+    self.slots = int(slots)
+    self.sway = [HeadSway() for _ in range(self.slots)]
+    self.frame = [0] * self.slots
+
+  def reset_slot(self, slot):
+    self.sway[slot].reset()
+    self.frame[slot] = 0
+
+  def rows(self, k_by_slot):
+    """k_by_slot: `slots` frame counts -> (slot [K] int32, global frame index [K] int64, angles [K, 3] f32), rows packed in slot order."""
+    assert len(k_by_slot) == self.slots
+    slot, g, ang = [], [], []
+    for s, k in enumerate(k_by_slot):
+      k = int(k)
+      if k:
+        slot.append(np.full(k, s, np.int32))
+        g.append(np.arange(self.frame[s], self.frame[s] + k, dtype=np.int64))
+        ang.append(self.sway[s].next(k))
+        self.frame[s] += k
+    if not slot:
+      return np.zeros(0, np.int32), np.zeros(0, np.int64), np.zeros((0, 3), np.float32)
+    return np.concatenate(slot), np.concatenate(g), np.concatenate(ang)
+
+
+def launch_tables(slot, g, has_coeff, bg_row, frame_batch):
+  """The device tables of one push from its rows (PuppetRowPlan.rows), host only.  has_coeff [slots] bool: the slots conditioned on
+  their rendered face; bg_row [100]: row of the background bank for global frame index % 100, or -1.  Returns
+    render [R, 4] int32   {slot, packed row, 0, 0} of the R rows that are rendered (vp_puppet_splice)
+    tex_src [n] / tex_row [R] int32   one texture per slot present among them (vp_bfm_reconstruct_rows)
+    cond [Kp, 4] int32    {slot, render row or -1, background row or -1, global frame index} for every row, padded with the last row to a
+                          multiple of frame_batch (vp_puppet_condition; as infer_bfmvid pads a short last batch)"""
+  K = int(slot.shape[0])
+  rendered = np.flatnonzero(np.asarray(has_coeff, bool)[slot]) if K else np.zeros(0, np.int64)
+  R = int(rendered.shape[0])
+  render = np.zeros((R, 4), np.int32)
+  render[:, 0], render[:, 1] = slot[rendered], rendered
+  present, first = np.unique(slot[rendered], return_index=True)
+  tex_src = first.astype(np.int32)
+  tex_row = np.searchsorted(present, slot[rendered]).astype(np.int32)
+  Kp = -(-K // frame_batch) * frame_batch
+  cond = np.zeros((Kp, 4), np.int32)
+  face = np.full(K, -1, np.int32)
+  face[rendered] = np.arange(R, dtype=np.int32)
+  cond[:K, 0], cond[:K, 1], cond[:K, 2], cond[:K, 3] = slot, face, np.asarray(bg_row, np.int32)[g % 100], g
+  if K:
+    cond[K:] = cond[K - 1]
+  return render, tex_src, tex_row, cond
+
+
+def puppet_desc(slots, frame_batch=8, img_size=512, face_size=224):
+  return _lib.PuppetDesc(ctypes.sizeof(_lib.PuppetDesc), slots, frame_batch, img_size, face_size)
+
+
+_BANKS = {}      # background banks by (directory, image size, the files and their modification times): decoded once per process
+
+
+def background_bank(img_size):
+  """The backgrounds that exist, as infer_bfmvid.background_target reads them: (uint8 device bank [n, H, H, 3] or None, bg_row [100] with
+  the bank row of global frame index % 100 or -1).  background_target's float image is float32(u8) / 255.0 of the resized uint8 image, so
+  the uint8 bank loses nothing (checked here, value for value)."""
+  import os
+  from .pixrefer import infer_bfmvid as ib
+  names = ['background/{}.jpg'.format(j + 1) for j in range(100)]
+  key = (os.path.abspath('background'), img_size, tuple(os.path.getmtime(f) if os.path.exists(f) else None for f in names))
+  if key not in _BANKS:
+    imgs, bg_row = [], np.full(100, -1, np.int32)
+    for j in range(100):
+      f = ib.background_target(j, img_size)
+      if f is not None:
+        u8 = np.rint(f * 255.0).astype(np.uint8)
+        if not np.array_equal(u8.astype(np.float32) / 255.0, f):
+          raise RuntimeError("%s: not float32(uint8) / 255.0" % names[j])
+        bg_row[j] = len(imgs)
+        imgs.append(u8)
+    if len(_BANKS) >= 4:
+      _BANKS.clear()
+    _BANKS[key] = (torch.from_numpy(np.stack(imgs)).to("cuda") if imgs else None, bg_row)
+  return _BANKS[key]
+
+
+class PuppetStreamGroup:
+  """Streaming infer_bfmvid for `slots` talkers behind one handle: one AudioStreamGroup, one generator plan (infer_bfmvid's cache, batch
+  frame_batch, per-sample batch norm), one ClipRenderer; per slot a photo, its coefficients, a head-sway state and a frame counter.
+
+  attach(slot, image, bfmcoeff): that talker's 512 x 1536 photo (RGB float in [0,1], as infer_bfmvid reads it) and coefficient npz
+  (bfmcoeff, transform_params, center_x, center_y, ratio); without the npz (or without BFM/BFM_model_front.mat) the slot is conditioned
+  on its reference 3-D face panel.  Restarts the slot's clip.
+  push({slot: pcm}, finish=()) -> {slot: [(global frame index, uint8 [H, W, 3] RGB device tensor)]} for every slot pushed or finished.
+  The frames of all slots that emitted run packed in slot order through splice, render, conditioning (libvp_hip.so: vp_puppet_*,
+  vp_bfm_reconstruct_rows) and the generator in launches of frame_batch rows, a short last launch padded with the last row.  A push
+  only enqueues: frame counts follow from sample counts, the per-row tables (slot, sway rotation, background, geometry) are computed
+  on the host first and reach the device through pinned memory; the frames are views of one [K, H, W, 3] tensor (last_frames) that is
+  ready when the current stream reaches it."""
+
+  def __init__(self, config_path, slots, frame_batch=8, max_chunk_frames=1, dtype="f32", img_size=512):
     import os
     from .pixrefer import infer_bfmvid as ib
-    from .runtime import Session
-    self.ib = ib
+    if not torch.cuda.is_available():
+      raise RuntimeError("PuppetStreamGroup needs an MI355X (no CPU fallback)")
+    self.ib, self.L = ib, _lib.lib()
+    self.slots, self.nb, self.img_size = int(slots), int(frame_batch), int(img_size)
+    self.desc = puppet_desc(self.slots, self.nb, self.img_size)
+    ws = self.L.vp_puppet_workspace_bytes(ctypes.byref(self.desc))
+    if ws == 0:
+      raise ValueError("invalid puppet group descriptor: " + self.L.vp_last_error().decode())
     bfm_file = next((f for f in (ib.BFMNET_CKPT + '.index', ib.BFMNET_CKPT + '.npz') if os.path.exists(f)), None)
     if bfm_file is None:
       from .bfmnet.bfmnet import random_variables
@@ -339,67 +444,159 @@ class PuppetStream:
       bfm_params = random_variables()
     else:
       bfm_params = load_bfmnet_params(bfm_file[:-len('.index')] if bfm_file.endswith('.index') else bfm_file)
-    self.audio = AudioStream(bfm_params, max_chunk_frames=max_chunk_frames, dtype=dtype)
-    self.nb, self.img_size = frame_batch, img_size
-    self.net, self.inputs_holder, self.fg_holder, self.targets_holder, self.nodes = ib.load_generator(config_path, frame_batch, img_size)
-    self.sess = Session()
-    self.photo = None
-    if bfmcoeff and os.path.exists(os.path.join('BFM', 'BFM_model_front.mat')):
-      self.photo = np.load(bfmcoeff)
-      self.renderer = ib.clip_renderer()
+    self.audio = AudioStreamGroup(bfm_params, slots=self.slots, max_chunk_frames=max_chunk_frames, dtype=dtype)
+    self.net = ib.load_generator(config_path, self.nb, self.img_size)[0]
+    self.engine = self.net.engine
+    self.renderer = ib.clip_renderer() if os.path.exists(os.path.join('BFM', 'BFM_model_front.mat')) else None
+    self.workspace = torch.empty(ws, dtype=torch.uint8, device="cuda")
+    h = ctypes.c_void_p()
+    _lib.check(self.L.vp_puppet_create(ctypes.byref(self.desc), _ptr(self.workspace), ws, _stream(), ctypes.byref(h)), "vp_puppet_create")
+    self.h = h
+    self.bank, self.bg_row = background_bank(self.img_size)
+    _lib.check(self.L.vp_puppet_set_backgrounds(self.h, _ptr(self.bank), 0 if self.bank is None else int(self.bank.shape[0])),
+               "vp_puppet_set_backgrounds")
+    nb, H = self.nb, self.img_size
+    self.inputs = torch.empty([nb, H, H, 6], dtype=torch.float32, device="cuda")
+    self.fg_inputs = torch.empty([nb, H, H, 3], dtype=torch.float32, device="cuda")
+    self.targets = torch.empty([nb, H, H, 3], dtype=torch.float32, device="cuda")
+    self.plan = PuppetRowPlan(self.slots)
+    self.has_coeff = np.zeros(self.slots, bool)
+    self.attached = np.zeros(self.slots, bool)
+    self.last_frames = None
+    self.keep_conditioning = False     # tests: keep every row's generator inputs and float Outputs of a push in last_conditioning
+    self.last_conditioning = None
+
+  def attach(self, slot, image, bfmcoeff=None):
+    ib, H = self.ib, self.img_size
+    slot = int(slot)
+    if not 0 <= slot < self.slots:
+      raise IndexError("slot %d of %d" % (slot, self.slots))
+    image = np.asarray(image)
+    face3d_refer = image[:, H:H * 2, :]
+    fg_refer = image[:, :H, :] * image[:, H * 2:, :]
+    refer_t = torch.as_tensor(np.ascontiguousarray(face3d_refer, dtype=np.float32)).to("cuda")
+    fg_t = torch.as_tensor(np.ascontiguousarray(fg_refer, dtype=np.float32)).to("cuda")
+    if tuple(refer_t.shape) != (H, H, 3) or tuple(fg_t.shape) != (H, H, 3):
+      raise ValueError("attach: the photo must be %d x %d x 3 (three panels side by side)" % (H, 3 * H))
+    coeff, side, y0, x0 = None, 0, 0, 0
+    if bfmcoeff and self.renderer is not None:
+      p = np.load(bfmcoeff) if isinstance(bfmcoeff, str) else bfmcoeff
+      coeff = np.ascontiguousarray(np.asarray(p['bfmcoeff'], dtype=np.float32).reshape(257))
+      side, y0, x0 = ib.paste_geometry(int(p['center_x']), int(p['center_y']), float(p['ratio']), p['transform_params'], self.desc.face_size)
     else:
       ib.logger.warning('BFM assets unavailable: conditioning every frame on the reference 3-D face panel')
-    face3d_refer = image[:, 512:512 * 2, :]
-    fg_refer = image[:, :512, :] * image[:, 512 * 2:, :]
-    nb, H = frame_batch, img_size
-    self.inputs = torch.zeros([nb, H, H, 6], dtype=torch.float32, device="cuda")
-    self.fg_inputs = torch.zeros([nb, H, H, 3], dtype=torch.float32, device="cuda")
-    self.targets = torch.full([nb, H, H, 3], 0.5, dtype=torch.float32, device="cuda")
-    refer_t = torch.as_tensor(np.ascontiguousarray(face3d_refer, dtype=np.float32)).to("cuda")
-    self.inputs[:, ..., 0:3] = refer_t
-    self.fg_inputs[:, ..., 0:3] = torch.as_tensor(np.ascontiguousarray(fg_refer, dtype=np.float32)).to("cuda")
-    if self.photo is None:
-      self.inputs[:, ..., 3:6] = refer_t
-    self.sway = HeadSway()
-    self.frame = 0
+    _lib.check(self.L.vp_puppet_attach(self.h, slot, _ptr(refer_t), _ptr(fg_t), coeff.ctypes.data_as(ctypes.c_void_p) if coeff is not None else None,
+                                       int(side), int(y0), int(x0), _stream()), "vp_puppet_attach")
+    self.has_coeff[slot] = coeff is not None
+    self.attached[slot] = True
+    self.reset_slot(slot)
+
+  def reset_slot(self, slot):
+    """Slot `slot` starts a new clip (audio session, head sway, frame counter); its photo stays."""
+    self.audio.reset_slot(slot)
+    self.plan.reset_slot(int(slot))
+
+  def frame(self, slot):
+    """Frames emitted so far in slot `slot`'s clip."""
+    return self.plan.frame[int(slot)]
+
+  @staticmethod
+  def _upload(parts):
+    """Host arrays -> device tensors in ONE pinned-memory copy (no host wait): a list of numpy arrays -> their device copies."""
+    offs, n = [], 0
+    for a in parts:
+      n = (n + 15) & ~15
+      offs.append(n)
+      n += a.nbytes
+    host = torch.empty(max(n, 16), dtype=torch.uint8).pin_memory()
+    hv = host.numpy()
+    for a, o in zip(parts, offs):
+      hv[o:o + a.nbytes] = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
+    dev = host.to("cuda", non_blocking=True)
+    tdt = {np.dtype(np.int32): torch.int32, np.dtype(np.float64): torch.float64}
+    return [dev[o:o + a.nbytes].view(tdt[a.dtype]).view(a.shape) for a, o in zip(parts, offs)]
+
+  def push(self, pcm_by_slot, finish=(), ears=None):
+    from .utils.reconstruct_mesh import Compute_rotation_matrix
+    L, nb, H = self.L, self.nb, self.img_size
+    for s in set(int(s) for s in pcm_by_slot) | set(int(s) for s in finish):
+      if not (0 <= s < self.slots and self.attached[s]):
+        raise ValueError("slot %d has no photo attached" % s)
+    # host first: frame counts from sample counts, then every per-row quantity
+    coeff, k, sizes = self.audio.push_packed(pcm_by_slot, finish, ears)
+    slot, g, angles = self.plan.rows(k)
+    K = int(slot.shape[0])
+    res = {s: [] for s in sizes}
+    self.last_frames, self.last_conditioning = None, None
+    if K == 0:
+      return res
+    render, tex_src, tex_row, cond = launch_tables(slot, g, self.has_coeff, self.bg_row, nb)
+    R = int(render.shape[0])
+    faces = None
+    if R:
+      rot = Compute_rotation_matrix(angles[render[:, 1]])
+      rot_d, render_d, tex_src_d, tex_row_d, cond_d = self._upload([rot, render, tex_src, tex_row, cond])
+      spliced = torch.empty(R, 257, dtype=torch.float32, device="cuda")
+      _lib.check(L.vp_puppet_splice(self.h, _ptr(coeff), K, _ptr(render_d), R, _ptr(spliced), _stream()), "vp_puppet_splice")
+      faces, _ = self.renderer.render_rows(spliced, rot_d, tex_src_d, int(tex_src.shape[0]), tex_row_d)
+    else:
+      cond_d, = self._upload([cond])
+    Kp = int(cond.shape[0])
+    out = torch.empty(Kp, H, H, 3, dtype=torch.uint8, device="cuda")
+    kept = [] if self.keep_conditioning else None
+    eng = self.engine
+    for i0 in range(0, Kp, nb):
+      _lib.check(L.vp_puppet_condition(self.h, _ptr(faces), R, _ptr(cond_d[i0:i0 + nb]), nb, _ptr(self.inputs), _ptr(self.fg_inputs),
+                                       _ptr(self.targets), _stream()), "vp_puppet_condition")
+      eng.forward(self.inputs, self.fg_inputs, self.targets)
+      _lib.check(L.vp_pixrefer_fetch(eng.h, eng.FETCH["Outputs_u8"], _ptr(out[i0:i0 + nb]), _stream()), "vp_pixrefer_fetch(Outputs_u8)")
+      if kept is not None:
+        n = min(nb, K - i0)
+        kept.append([t[:n].clone() for t in (self.inputs, self.fg_inputs, self.targets, eng.fetch("Outputs"))])
+    self.last_frames = out[:K]
+    if kept is not None:
+      self.last_conditioning = {"slot": slot, "frame": g,
+                                **{name: torch.cat([b[i] for b in kept]) for i, name in enumerate(("inputs", "fg_inputs", "targets", "Outputs"))}}
+    for r in range(K):
+      res[int(slot[r])].append((int(g[r]), out[r]))
+    return res
+
+  def __del__(self):
+    try:
+      if getattr(self, "h", None):
+        self.L.vp_puppet_destroy(self.h)
+        self.h = None
+    except Exception:
+      pass
+
+
+class PuppetStream:
+  """Streaming infer_bfmvid for one talker: a PuppetStreamGroup of one slot.  push(pcm) / finish() -> [(global frame index, uint8 frame
+  [H, W, 3] RGB, host array)] of the frames that became exact.  image / bfmcoeff: as PuppetStreamGroup.attach.  BFMNet / PixReferNet
+  weights: the checkpoints infer_bfmvid restores (ckpt_bfmnet/bfmnet-65000, ckpt_pixrefer/pixrefernet-20000; TF prefix or .npz), the
+  generator from infer_bfmvid's cache.  The group's push only enqueues; this class hands out host-readable frames, so it waits once, at
+  the end of a push that emitted frames."""
+
+  def __init__(self, config_path, image, bfmcoeff=None, frame_batch=8, max_chunk_frames=1, dtype="f32", img_size=512):
+    self.group = PuppetStreamGroup(config_path, 1, frame_batch=frame_batch, max_chunk_frames=max_chunk_frames, dtype=dtype, img_size=img_size)
+    self.group.attach(0, image, bfmcoeff)
+    self.audio = self.group.audio
+
+  @property
+  def frame(self):
+    return self.group.frame(0)
 
   def reset(self):
-    self.audio.reset()
-    self.sway.reset()
-    self.frame = 0
+    self.group.reset_slot(0)
 
   def push(self, pcm):
-    return self._frames(self.audio.push(pcm))
+    return self._host(self.group.push({0: pcm}))
 
   def finish(self):
-    return self._frames(self.audio.finish())
+    return self._host(self.group.push({}, finish=(0,)))
 
-  def _frames(self, coeff):
-    ib, H = self.ib, self.img_size
-    k = int(coeff.shape[0])
-    if k == 0:
+  def _host(self, res):
+    if not res[0]:
       return []
-    g0 = self.frame
-    self.frame += k
-    angles = self.sway.next(k)
-    face3d = None
-    if self.photo is not None:
-      p = self.photo
-      coeff_seq = ib.splice_coeff(p['bfmcoeff'].reshape(1, 257), coeff.cpu().numpy()[np.newaxis])[0]
-      face3d = ib.render_faces(self.renderer, int(p['center_x']), int(p['center_y']), float(p['ratio']), coeff_seq, (H, H, 3),
-                               p['transform_params'], on_device=True, angles=angles)
-    out = []
-    for i0 in range(0, k, self.nb):                    # batches of the generator plan, padded with the last frame as infer_bfmvid pads
-      idx = [min(i0 + j, k - 1) for j in range(self.nb)]
-      if face3d is not None:
-        self.inputs[:, ..., 3:6] = face3d[idx].flip(-1).to(torch.float32) / 255.0
-      for j, i in enumerate(idx):
-        bg = ib.background_target(g0 + i, H)
-        if bg is not None:
-          self.targets[j] = torch.as_tensor(bg).to("cuda")
-        else:
-          self.targets[j] = 0.5
-      frames = self.sess.run([self.nodes['Outputs_u8']],
-                             feed_dict={self.inputs_holder: self.inputs, self.fg_holder: self.fg_inputs, self.targets_holder: self.targets})[0]
-      out.extend((g0 + i0 + j, frames[j]) for j in range(self.nb) if i0 + j < k)
-    return out
+    frames = self.group.last_frames.cpu().numpy()
+    return [(g, frames[i]) for i, (g, _) in enumerate(res[0])]

@@ -115,6 +115,24 @@ def reconstruct_clip(coeff, model, angles, shared_texture=False, full=True):
   return out
 
 
+def reconstruct_rows(coeff, rot, tex_src, textures, tex_row, model):
+  """Rows of several identities in one call (vp_bfm_reconstruct_rows; stream groups): coeff [R,257] f32, rot [R,3,3] f64, tex_src
+  [textures] / tex_row [R] int32 - all DEVICE tensors, so the call only enqueues.  Returns (vertices, colors) [R,N,3] f32."""
+  dev = model.device
+  R, N = coeff.shape[0], model.nver
+  for t, dt in ((coeff, torch.float32), (rot, torch.float64), (tex_src, torch.int32), (tex_row, torch.int32)):
+    if not (t.is_cuda and t.is_contiguous() and t.dtype == dt):
+      raise ValueError("reconstruct_rows: contiguous device tensors (f32 coeff, f64 rot, int32 tables) expected")
+  if coeff.shape[1] != 257 or rot.numel() != 9 * R or tex_row.numel() != R or tex_src.numel() < textures:
+    raise ValueError("reconstruct_rows: inconsistent shapes")
+  vertices = torch.empty(R, N, 3, dtype=torch.float32, device=dev)
+  colors = torch.empty(R, N, 3, dtype=torch.float32, device=dev)
+  ws = model.workspace(R)
+  _lib.check(_lib.lib().vp_bfm_reconstruct_rows(ctypes.byref(model.c), _ptr(coeff), _ptr(rot), R, _ptr(tex_src), int(textures), _ptr(tex_row),
+                                                _ptr(vertices), _ptr(colors), _ptr(ws), ws.numel(), _stream()), "vp_bfm_reconstruct_rows")
+  return vertices, colors
+
+
 def Reconstruction_rotation(coeff, facemodel, angles):
   """reconstruct_mesh.py:198-223, same arguments and return tuple (numpy float64, batch dimension = coeff.shape[0]).
   `facemodel` may be the reference's BFM object (uploaded on every call) or a DeviceFaceModel (resident)."""
@@ -133,9 +151,18 @@ class ClipRenderer:
 
   def __call__(self, coeff, angles, shared_texture=True):
     o = reconstruct_clip(coeff, self.model, angles, shared_texture=shared_texture, full=False)
-    T, dev = o["vertices"].shape[0], self.model.device
+    return self._raster(o["vertices"], o["colors"])
+
+  def render_rows(self, coeff, rot, tex_src, textures, tex_row):
+    """__call__ for rows of several identities (reconstruct_rows: device tensors in, nothing waits): row r's image equals what
+    __call__ gives for that identity's frames alone."""
+    vertices, colors = reconstruct_rows(coeff, rot, tex_src, textures, tex_row, self.model)
+    return self._raster(vertices, colors)
+
+  def _raster(self, vertices, colors):
+    T, dev = vertices.shape[0], self.model.device
     image = torch.zeros(T, self.h, self.w, 3, dtype=torch.uint8, device=dev)
     mask = torch.zeros(T, self.h, self.w, dtype=torch.uint8, device=dev)
     depth = torch.full((T, self.h, self.w), -99999.0, dtype=torch.float32, device=dev)       # infer_bfmvid.py:104
-    mesh_core.render_colors(image, mask, o["vertices"], self.model.tri, o["colors"], depth)
+    mesh_core.render_colors(image, mask, vertices, self.model.tri, colors, depth)
     return image, mask
