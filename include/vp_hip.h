@@ -155,7 +155,9 @@ int vp_pixrefer_use_streams(vp_pixrefer_t* h, int n);
  * / spread over the executor's streams, default 1), "d_backward_fork" 0..2 (where vp_pixrefer_backward starts the discriminator-loss
  * pass, default 2), "d_beside_vgg" 0 / 1 (default 1); and "store_first_raw" 0 / 1 (default 0): encoder_1 / encoder_fg_1 / discriminator
  * layer_1 of a bf16 plan write their consumers' activations from the conv epilogue and skip the raw output nobody reads - 1 stores it
- * too (vp_pixrefer_tensor refuses "g/encoder_1" ... otherwise).  Per handle: two plans in one process do not change each other's schedule; the
+ * too (vp_pixrefer_tensor refuses "g/encoder_1" ... otherwise).  The option also governs the full-resolution outputs of VGG conv1_2 /
+ * conv2_2: with 0 the fake half of a bf16 step on the overlapped schedule writes only their 2x2 max pool and one byte per pooled element
+ * for the pool's backward pass ("v/conv1/conv1_2" and "v/conv2/conv2_2" are refused the same way); 1 stores them as before.  Per handle: two plans in one process do not change each other's schedule; the
  * initial values come from the descriptor (vp_pixrefer_desc::streams / d_backward_fork / d_beside_vgg).  Bit-identical results under
  * every setting. */
 int vp_pixrefer_set_option(vp_pixrefer_t* h, const char* key, int value);
@@ -163,7 +165,8 @@ int vp_pixrefer_set_option(vp_pixrefer_t* h, const char* key, int value);
  * epilogue of the launch that completes the tensor's gradient instead of a pass of their own over y and dz (same values up to the order of
  * float32 partial sums); "vgg_real_fork" k (default 3): the VGG pass of the real half starts on the side stream in front of generator layer
  * k (TF scope order; 0 = right behind the input packing).  vp_pixrefer_counter: "bwd_sums_launches" = launches since create that carried
- * such sums (-1: unknown key); for tests. */
+ * such sums; "pool_codes_written" = 1 when the last forward pass wrote the VGG pool codes in place of the full-resolution conv1_2 /
+ * conv2_2 outputs of the fake half, else 0 (-1: unknown key); for tests. */
 long long vp_pixrefer_counter(vp_pixrefer_t* h, const char* key);
 /* Node values PixReferNet.execute hands to a caller, formed on the device from the last forward pass into `dst` (device memory,
  * N * H * H * 3 elements): what = 0 Outputs (float32, (x + 1) / 2: pixrefer.py:424 / :380), 1 the same as uint8 frames (clamp, * 255,
@@ -433,6 +436,9 @@ int vp_gru_seq_state(const float* xg, const float* xc, const float* whg, const f
  * Single pointwise / audio ops of the two executors (the entry-point list of SURVEY.md 8b), for parity tests and reuse.
  *   vp_maxpool2x2_*      slim max_pool2d 2x2/2 of vgg_simple.py:141,146 (NHWC).  bwd goes through the pool AND the ReLU of the conv
  *                        that produced x (x is stored post-relu): the gradient lands on the FIRST maximum of a window if it is > 0
+ *   vp_maxpool2x2_bwd_code  the same from one byte per pooled element instead of x (code [n][h/2][w/2][c], uint8: 0 = the window maximum
+ *                        is <= 0, no gradient; 1 + k = position k of the window in the order (0,0), (0,1), (1,0), (1,1) is its first
+ *                        maximum): what a training step's fused-pool conv epilogues record in place of the full-resolution tensor
  *   vp_composite_fwd     pixrefer.py:279-290 inference compositing: out4 = tanh(gen_out4), alpha = (out4[3]+1)/2,
  *                        outputs = rgb*alpha + (2*targets-1)*(1-alpha), outputs_fg = rgb*alpha + alpha - 1   (all float32)
  *   vp_gan_loss          pixrefer.py:334-347: logits [3][m] = D(real1) | D(real2) | D(fake) -> predict [2][m], losses[0] = Discrim_loss,
@@ -453,6 +459,7 @@ int vp_gru_seq_state(const float* xg, const float* xc, const float* whg, const f
  * ---------------------------------------------------------------------------------------------- */
 int vp_maxpool2x2_fwd(const void* x, void* y, int n, int h, int w, int c, int dtype, void* stream);
 int vp_maxpool2x2_bwd(const void* x, const void* dy, void* dx, int n, int h, int w, int c, int dtype, void* stream);
+int vp_maxpool2x2_bwd_code(const void* code, const void* dy, void* dx, int n, int h, int w, int c, int dtype, void* stream);
 int vp_composite_fwd(const float* gen_out4, const float* targets, float* out4, float* outputs, float* outputs_fg, int n, int hw,
                      void* stream);
 int vp_gan_loss(const float* logits, void* seed_d, void* seed_g, float* predict, float* losses, int m, float gan_weight, int dtype,

@@ -111,6 +111,10 @@ struct IgemmArgs {
   void* xa_relu;
   void* pool_out;           // patch kernel, 16 x 16-pixel tiles: also write the 2x2 max-pooled output [N][Hg/2][Wg/2][ldY] (null: no)
   int pool_only;            // with pool_out: write ONLY the pooled output (nobody reads the full-resolution tensor: the real half of the VGG trunk)
+  // with pool_out (bf16, relu outputs): also one byte per pooled element [N][Hg/2][Wg/2][ldY], laid out like pool_out - all the pool's
+  // backward pass needs of the full-resolution tensor (maxpool_bwd_code_kernel).  0: the window maximum is <= 0 (no gradient);
+  // 1 + k: k is the FIRST arg-max of the window in the order (0,0), (0,1), (1,0), (1,1) of the values as stored (rounded to bf16)
+  unsigned char* pool_code;
   // few-pixel kernel (conv_smallp.hip; kern == CK_SMALLP, plan-time decision: packed rows unpermuted): 32 channels x sp_npt * 16 pixels per tile,
   // splitk = K splits over blocks, partial = their slabs [split][tile][pixels][32]
   unsigned* sp_cnt;         // [tiles + channel tiles] arrival counters: zero before the launch, left zero by it

@@ -57,20 +57,45 @@ __device__ __forceinline__ unsigned pk_mul_lo_u16(unsigned x, unsigned y) {
   asm("v_pk_mul_lo_u16 %0, %1, %2" : "=v"(r) : "v"(x), "v"(y));
   return r;
 }
+__device__ __forceinline__ unsigned pk_sub_u16(unsigned x, unsigned y) {
+  unsigned r;
+  asm("v_pk_sub_u16 %0, %1, %2" : "=v"(r) : "v"(x), "v"(y));
+  return r;
+}
+__device__ __forceinline__ unsigned pk_add_u16(unsigned x, unsigned y) {
+  unsigned r;
+  asm("v_pk_add_u16 %0, %1, %2" : "=v"(r) : "v"(x), "v"(y));
+  return r;
+}
+__device__ __forceinline__ unsigned pk_max_u16(unsigned x, unsigned y) {
+  unsigned r;
+  asm("v_pk_max_u16 %0, %1, %2" : "=v"(r) : "v"(x), "v"(y));
+  return r;
+}
+// per 16-bit half: 1 where y > x, else 0, for relu outputs (bit patterns 0 .. 0x7fff: the difference is negative exactly then)
+__device__ __forceinline__ unsigned pk_gt_relu(unsigned x, unsigned y) {
+  unsigned r;
+  // (the shift count from a register: a packed instruction reads an inline constant's upper half - zero - for its upper lane)
+  asm("v_pk_lshrrev_b16 %0, %1, %2" : "=v"(r) : "v"(0x000F000Fu), "v"(pk_sub_u16(x, y)));
+  return r;
+}
 __device__ __forceinline__ unsigned dpp_xor1(unsigned v) {       // value of lane ^ 1: quad_perm [1, 0, 3, 2]
   return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, true);
 }
 
 // REF: backward-data (output *= relu'(reference)); RELU: forward activation; POOL: also write the 2x2 max pool (RELU outputs only);
 // STORE: write the full-resolution output (false with POOL: the real half of the perceptual trunk, nobody reads it)
+// CODE: with POOL and without STORE, also write IgemmArgs::pool_code - the fake half of a training step, whose pool backward reads the
+//   one-byte codes instead of the full-resolution tensor
 // NCH: 64-byte channel chunks of the input (2: 64 channels, 4: 128); TPW: 16-channel MFMA tiles per wave - 36 NCH TPW weight registers:
 //   NCH 2, TPW 2: 64 -> 64 (NW 2: VGG conv1_2 both passes) and 64 -> 128 (NW 4: conv2_1 forward);
 //   NCH 4, TPW 1: 128 -> 128 (NW 8: conv2_2 both passes) and 128 -> 64 (NW 4: conv2_1 backward-data) - a fragment read then feeds half
 //   the MFMAs, still 72 reads for 144 MFMAs per wave and tile
 // NW: waves of a block; the block's output channels are 16 TPW NW
-template <int NCH, int TPW, int NW, bool REF, bool RELU, bool POOL, bool STORE>
+template <int NCH, int TPW, int NW, bool REF, bool RELU, bool POOL, bool STORE, bool CODE = false>
 __global__ __launch_bounds__(NW * 64, 2) void conv_c64_kernel(const IgemmArgs a, const int ntiles) {
   static_assert(!POOL || (RELU && !REF), "the packed max pool compares relu outputs");
+  static_assert(!CODE || (POOL && !STORE), "pool codes stand in for the full-resolution store");
   static_assert((NCH == 2 && TPW == 2) || (NCH == 4 && TPW == 1), "36 NCH TPW <= 144 weight registers");
   constexpr int JP = PPAD / (16 * NW);          // patch DMA instructions per wave and chunk
   constexpr int CW = 16 * TPW;                  // output channels of a wave
@@ -141,7 +166,7 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_c64_kernel(const IgemmArgs a,
   bf16* Yp = reinterpret_cast<bf16*>(a.Y);
   bf16* Pp = reinterpret_cast<bf16*>(a.pool_out);
   constexpr int NSTY = TH * 16 * CB / 1024 / NW;                     // 1 KB store instructions of the staged tile per wave (2 TPW)
-  constexpr int NST = (STORE ? NSTY : 0) + (POOL ? TH / 2 : 0);      // store instructions per tile and wave
+  constexpr int NST = (STORE ? NSTY : 0) + (POOL ? TH / 2 : 0) + (CODE ? TH / 2 : 0);      // store instructions per tile and wave
 
   // XCD-aware tile order: blocks go round-robin over the 8 XCDs, so each XCD takes a contiguous run of every round's tiles and the
   // halo rows / columns of neighbouring tiles meet in one L2
@@ -280,16 +305,35 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_c64_kernel(const IgemmArgs a,
     if constexpr (POOL) {
 #pragma unroll
       for (int q = 0; q < TH; q += 2) {
-        unsigned m[NV / 2];
+        unsigned m[NV / 2], cd[NV / 2];
 #pragma unroll
         for (int e = 0; e < NV / 2; ++e) {
-          m[e] = pk_max_i16(pk[q][e], pk[q + 1][e]);
-          m[e] = pk_max_i16(m[e], dpp_xor1(m[e]));
+          if constexpr (CODE) {
+            // the window in the order (0,0), (0,1), (1,0), (1,1) on an even lane (the odd neighbour's results are not stored): a later
+            // value takes the arg-max only when strictly greater, so the index is the largest k whose value beat the running maximum
+            // = max(g1, 2 g2, 3 g3); the code is 0 when the maximum is 0 (relu outputs: no negative values, -0 is stored as +0)
+            const unsigned v0 = pk[q][e], v1 = dpp_xor1(v0), v2 = pk[q + 1][e], v3 = dpp_xor1(v2);
+            const unsigned g1 = pk_gt_relu(v0, v1), m1 = pk_max_i16(v0, v1);
+            const unsigned g2 = pk_gt_relu(m1, v2), m2 = pk_max_i16(m1, v2);
+            const unsigned g3 = pk_gt_relu(m2, v3);
+            m[e] = pk_max_i16(m2, v3);
+            const unsigned best = pk_max_u16(pk_max_u16(g1, pk_add_u16(g2, g2)), pk_mul_lo_u16(g3, 0x00030003u));
+            cd[e] = pk_mul_lo_u16(pk_min_u16(m[e], 0x00010001u), pk_add_u16(best, 0x00010001u));
+          } else {
+            m[e] = pk_max_i16(pk[q][e], pk[q + 1][e]);
+            m[e] = pk_max_i16(m[e], dpp_xor1(m[e]));
+          }
         }
         if (!(fi & 1)) {
           const size_t po = ((size_t)(n * (a.Hg >> 1) + ((y0 + q) >> 1)) * (a.Wg >> 1) + ((x0 + fi) >> 1)) * COUT + c0;
           if constexpr (NV == 8) *reinterpret_cast<uint4*>(Pp + po) = make_uint4(m[0], m[1], m[NV / 2 - 2], m[NV / 2 - 1]);
           else *reinterpret_cast<uint2*>(Pp + po) = make_uint2(m[0], m[1]);
+          if constexpr (CODE) {
+            // the low bytes of the four 16-bit codes of a register pair into one word (bytes 0, 2 of the first, 0, 2 of the second)
+            const unsigned w0 = __builtin_amdgcn_perm(cd[1], cd[0], 0x06040200u);
+            if constexpr (NV == 8) *reinterpret_cast<uint2*>(a.pool_code + po) = make_uint2(w0, __builtin_amdgcn_perm(cd[NV / 2 - 1], cd[NV / 2 - 2], 0x06040200u));
+            else *reinterpret_cast<unsigned*>(a.pool_code + po) = w0;
+          }
         }
       }
     }
@@ -307,6 +351,7 @@ bool conv_c64_eligible(const IgemmArgs& a, int is_bf16) {
   if ((a.out_act != ACT_NONE && a.out_act != ACT_RELU) || (a.ref && (a.ref_act != ACT_RELU || a.out_act != ACT_NONE || a.pool_out))) return false;
   if (a.pool_out && (a.out_act != ACT_RELU || (a.Hg & 1))) return false;
   if (a.pool_only && !a.pool_out) return false;
+  if (a.pool_code && !a.pool_only) return false;
   if (a.bn_part || a.accumulate || a.y_f32 || a.ref_a || a.split_c || a.x.aff_a[0] || a.x.act != ACT_NONE) return false;
   if (a.p_dhs != a.p_dws || a.p_dhf != a.p_dwf || a.p_dhf != (a.p_dhs > 0 ? -1 : 1)) return false;          // pad 1
   return (size_t)a.N * a.Hin * a.Win * a.Cin * 2 < 0x70000000ull;
@@ -317,6 +362,7 @@ static hipError_t launch_c64_t(const IgemmArgs& a, hipStream_t st) {
   const int ntiles = a.N * (a.Hg / TH) * (a.Wg / TW);
   void (*kern)(const IgemmArgs, const int);
   if (a.ref) kern = conv_c64_kernel<NCH, TPW, NW, true, false, false, true>;
+  else if (a.pool_out && a.pool_code) kern = conv_c64_kernel<NCH, TPW, NW, false, true, true, false, true>;
   else if (a.pool_out) kern = a.pool_only ? conv_c64_kernel<NCH, TPW, NW, false, true, true, false> : conv_c64_kernel<NCH, TPW, NW, false, true, true, true>;
   else kern = a.out_act == ACT_RELU ? conv_c64_kernel<NCH, TPW, NW, false, true, false, true> : conv_c64_kernel<NCH, TPW, NW, false, false, false, true>;
   // LDS: two patch buffers + the output staging tile; blocks per CU: 8 / NW (two waves per SIMD) - all of them fit (40 .. 80 KB each)

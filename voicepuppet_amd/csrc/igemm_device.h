@@ -153,6 +153,17 @@ __device__ __forceinline__ void epi_store8(const IgemmArgs& a, long long ot, int
 }
 
 
+// IgemmArgs::pool_code of one pooled element from the four STORED values of its window in the order (0,0), (0,1), (1,0), (1,1): the rule of
+// maxpool_bwd_kernel (first arg-max by strict >, no gradient unless the maximum is > 0)
+__device__ __forceinline__ unsigned pool_code_of(float v0, float v1, float v2, float v3) {
+  unsigned best = 0;
+  float m = v0;
+  if (v1 > m) { m = v1; best = 1; }
+  if (v2 > m) { m = v2; best = 2; }
+  if (v3 > m) { m = v3; best = 3; }
+  return m > 0.f ? 1u + best : 0u;
+}
+
 // STATS (a batch-normalised layer): the epilogue also produces the layer's batch statistics.  While a pass's f32 tile sits in
 // LDS, thread t sums column (channel) t % BC over its share of the rows - of the values AS STORED, i.e. rounded to T - into two
 // registers; after the last pass the NT / BC threads of a channel fold through LDS and the block writes one [2][channels]
@@ -244,6 +255,16 @@ __device__ __forceinline__ void staged_epilogue(const IgemmArgs& a, const PixFn&
                 for (int e = 0; e < 8; ++e) m[e] = k == 0 ? v[e] : fmaxf(m[e], v[e]);
               }
               *reinterpret_cast<uint4*>(reinterpret_cast<bf16*>(a.pool_out) + po + c0) = Elem<bf16>::pack(m);
+              if (a.pool_code) {                      // (the staged values are the stored ones)
+                float vv[4][8];
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                  Elem<bf16>::unpack(*reinterpret_cast<const uint4*>(smem + (r00 + (k >> 1) * 16 + (k & 1)) * PITCHB + cgp * 16), vv[k]);
+                unsigned w[2] = {0u, 0u};
+#pragma unroll
+                for (int e = 0; e < 8; ++e) w[e >> 2] |= pool_code_of(vv[0][e], vv[1][e], vv[2][e], vv[3][e]) << (8 * (e & 3));
+                *reinterpret_cast<uint2*>(a.pool_code + po + c0) = make_uint2(w[0], w[1]);
+              }
             }
           }
         }
@@ -373,6 +394,28 @@ __device__ __forceinline__ void staged_epilogue(const IgemmArgs& a, const PixFn&
           if (a.out_act != ACT_NONE) {
 #pragma unroll
             for (int e = 0; e < 8; ++e) m[e] = act_apply(a.out_act, m[e]);
+          }
+          if constexpr (sizeof(T) == 2) {
+            if (a.pool_code) {                        // the staged values are raw accumulators: bias, activation and rounding first, as the store does
+              float vv[4][8];
+#pragma unroll
+              for (int k = 0; k < 4; ++k) {
+                const int rr = r00 + (k >> 1) * 16 + (k & 1);
+                const float4 v0 = *reinterpret_cast<const float4*>(smem + rr * PITCH + cgp * 32);
+                const float4 v1 = *reinterpret_cast<const float4*>(smem + rr * PITCH + cgp * 32 + 16);
+                float v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                  if (a.bias) v[e] += a.bias[c0 + e];
+                  if (a.out_act != ACT_NONE) v[e] = act_apply(a.out_act, v[e]);
+                }
+                Elem<bf16>::unpack(Elem<bf16>::pack(v), vv[k]);
+              }
+              unsigned w[2] = {0u, 0u};
+#pragma unroll
+              for (int e = 0; e < 8; ++e) w[e >> 2] |= pool_code_of(vv[0][e], vv[1][e], vv[2][e], vv[3][e]) << (8 * (e & 3));
+              *reinterpret_cast<uint2*>(a.pool_code + po + c0) = make_uint2(w[0], w[1]);
+            }
           }
           if (sizeof(T) == 2) *reinterpret_cast<uint4*>(reinterpret_cast<bf16*>(a.pool_out) + po + c0) = Elem<bf16>::pack(m);
           else {

@@ -80,6 +80,7 @@ hipError_t launch_perceptual(const PerceptualArgs& a, int is_bf16, hipStream_t s
 hipError_t launch_loss_final(const LossFinalArgs& a, hipStream_t st);
 hipError_t launch_maxpool_fwd(const void* x, void* y, int B, int H, int W, int C, int is_bf16, hipStream_t st);
 hipError_t launch_maxpool_bwd(const void* x, const void* dy, void* dx, int B, int H, int W, int C, int is_bf16, hipStream_t st);
+hipError_t launch_maxpool_bwd_code(const void* code, const void* dy, void* dx, int B, int H, int W, int C, int is_bf16, hipStream_t st);   // code: IgemmArgs::pool_code
 hipError_t launch_relu_bwd(const void* y, void* d, size_t n, int is_bf16, hipStream_t st);
 hipError_t launch_adam(const AdamArgs& a, hipStream_t st);
 hipError_t launch_fetch(const FetchArgs& a, hipStream_t st);

@@ -262,6 +262,13 @@ int vp_maxpool2x2_bwd(const void* x, const void* dy, void* dx, int n, int h, int
   return VP_OK;
 }
 
+int vp_maxpool2x2_bwd_code(const void* code, const void* dy, void* dx, int n, int h, int w, int c, int dtype, void* stream) {
+  const int e = dtype == VP_BF16 ? 8 : 4;
+  if (!code || !dy || !dx || n < 1 || h < 2 || w < 2 || (h & 1) || (w & 1) || c < e || c % e) { set_err("vp_maxpool2x2_bwd_code: bad argument"); return VP_ERR_ARG; }
+  VP_HIP_CHECK(launch_maxpool_bwd_code(code, dy, dx, n, h, w, c, dtype == VP_BF16, (hipStream_t)stream));
+  return VP_OK;
+}
+
 int vp_composite_fwd(const float* gen_out4, const float* targets, float* out4, float* outputs, float* outputs_fg, int n, int hw,
                      void* stream) {
   if (!gen_out4 || !targets || !out4 || !outputs || !outputs_fg || n < 1 || hw < 1) { set_err("vp_composite_fwd: bad argument"); return VP_ERR_ARG; }

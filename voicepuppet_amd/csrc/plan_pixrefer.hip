@@ -150,6 +150,10 @@ struct vp_pixrefer {
   float *y4, *o4, *outputs, *outputs_fg, *logits, *predict, *losses;
   void *dl_d, *dl_g, *d_din, *d_vin, *dy4, *df3;
   void *vpool1, *vpool2, *d_vpool1, *d_vpool2;
+  // VGG conv1_2 / conv2_2, fake half: one byte per pooled element from the fused-pool epilogue (IgemmArgs::pool_code) - what the pool's
+  // backward pass reads instead of the full-resolution output, which is then not stored
+  unsigned char* vpool_code[2];
+  bool pool_codes_written;    // the last forward pass took that path: the backward pass follows THIS, not the options (vp_pixrefer_set_option may come in between)
   double *comp_partial, *perc_partial, *bn_partial;
   char* scratch;
   char* scratch2;             // split-K / slab scratch and batch-norm partials of the side stream (backward_d when overlapped)
@@ -583,6 +587,11 @@ static size_t carve_all(vp_pixrefer* h, char* base, size_t cap, std::vector<std:
       for (Tens& t : n->t) if (h->bf16 && !t.is_input && !t.has_bn && t.C == 64) t.cs_part = (double*)ar.alloc((size_t)512 * 2 * 64 * sizeof(double));
     // VGG backward runs on the fake half only
     for (Tens& t : h->V.t) if (!t.is_input) t.dz = ar.alloc(t.elems() / 2 * es);
+    // ... and the arg-max codes of its two pools (one byte per pooled element of the fake half)
+    for (const Tens& t : h->V.t) {
+      if (t.name == "pool1") h->vpool_code[0] = (unsigned char*)ar.alloc(t.elems() / 2);
+      if (t.name == "pool2") h->vpool_code[1] = (unsigned char*)ar.alloc(t.elems() / 2);
+    }
     h->n_comp = composite_nblocks(N, H * H);
     h->n_perc = perceptual_nblocks((size_t)N * (H / 4) * (H / 4) * 256, h->bf16);
     h->comp_partial = (double*)ar.alloc((size_t)h->n_comp * 2 * sizeof(double));
@@ -715,10 +724,13 @@ static int epi_stat_chunks(const IgemmPlan& p, int batch, int groups) {
 }
 
 // forward of one half of the batch of a plain conv layer (VGG: no batch-norm, activation in the epilogue): half 0 / 1
-static int run_layer_fwd_half(vp_pixrefer* h, Net& n, Layer& L, int half, hipStream_t st, void* pool_out = nullptr, bool pool_only = false) {
+// (pool_code: with pool_only, the epilogue also records the pool's arg-max codes for the backward pass)
+static int run_layer_fwd_half(vp_pixrefer* h, Net& n, Layer& L, int half, hipStream_t st, void* pool_out = nullptr, bool pool_only = false,
+                              unsigned char* pool_code = nullptr) {
   IgemmArgs a = L.fwd_half.a;
   a.pool_out = pool_out;
   a.pool_only = pool_out && pool_only ? 1 : 0;
+  a.pool_code = a.pool_only ? pool_code : nullptr;
   const int nb = a.N;
   fill_src(n, L, a.x, nb, half * nb, 0, h->es);
   a.Wp = n.packed + L.pk_fwd_half * h->es;
@@ -1289,6 +1301,10 @@ int vp_pixrefer_validate_plan(const vp_pixrefer_desc* d) {
     region_of(h->logits, 3 * M * 4, "logits"); region_of(h->predict, 2 * M * 4, "predict");
     region_of(h->dl_d, 3 * M * 8 * es, "dl_d"); region_of(h->dl_g, M * 8 * es, "dl_g");
     region_of(h->d_din, px * 8 * es, "d_din"); region_of(h->d_vin, px * 8 * es, "d_vin"); region_of(h->dy4, px * 8 * es, "dy4");
+    for (const Tens& t : h->V.t) {
+      if (t.name == "pool1") region_of(h->vpool_code[0], t.elems() / 2, "pool1 codes");
+      if (t.name == "pool2") region_of(h->vpool_code[1], t.elems() / 2, "pool2 codes");
+    }
     region_of(h->scratch2, h->scratch_bytes, "scratch2"); region_of(h->scratch3, h->scratch_bytes, "scratch3");
     region_of(h->scratch4, h->scratch_bytes, "scratch4"); region_of(h->bn_partial4, (size_t)1024 * 2 * 512 * 8, "bn_partial4");
     region_of(h->bn_partial2, (size_t)1024 * 2 * 512 * 8, "bn_partial2"); region_of(h->bn_partial3, (size_t)1024 * 2 * 512 * 8, "bn_partial3");
@@ -1534,6 +1550,13 @@ static int forward_impl(vp_pixrefer_t* h, const float* inputs, const float* fg_i
   // VGG trunk on [real fg | Outputs_FG] (pixrefer.py:321).  The real half does not depend on the generator: when every layer has
   // a half-batch plan it was started on the side stream right after pack_inputs (below, `vgg_half`) and only the fake half runs here
   Net& V = h->V;
+  // The fake half of conv1_2 / conv2_2: after the fused pool only the pool's backward pass reads the full-resolution output, and only for
+  // the first arg-max of a window and the sign of its maximum.  The epilogue records that as one byte per pooled element and the output
+  // is not stored (as for the real half).  bf16 plans whose two layers can fuse the pool; store_first_raw = 1 keeps the stored tensors
+  bool codes = split_vgg && bf && !h->store_first_raw && h->vpool_code[0] && h->vpool_code[1];
+  for (Layer& L : V.l)
+    if (L.scope == "conv1/conv1_2" || L.scope == "conv2/conv2_2") codes = codes && plan_can_pool(L.fwd_half);
+  h->pool_codes_written = codes;
   auto vgg_half = [&](int half, hipStream_t s2) -> int {
     for (size_t i = 0; i < V.l.size(); ++i) {
       Layer& L = V.l[i];
@@ -1543,7 +1566,8 @@ static int forward_impl(vp_pixrefer_t* h, const float* inputs, const float* fg_i
       const Tens& ti = V.t[L.out];
       Tens& tp = V.t[pooled ? L.out + 1 : L.out];   // pool tensor follows in creation order
       const size_t oi = (size_t)half * N * ti.H * ti.W * ti.C * h->es, op = (size_t)half * N * tp.H * tp.W * tp.C * h->es;
-      if ((rc2 = run_layer_fwd_half(h, V, L, half, s2, fuse ? (char*)tp.y + op : nullptr))) return rc2;
+      const bool code = fuse && codes && half == 1;
+      if ((rc2 = run_layer_fwd_half(h, V, L, half, s2, fuse ? (char*)tp.y + op : nullptr, code, code ? h->vpool_code[L.scope == "conv2/conv2_2"] : nullptr))) return rc2;
       if (pooled && !fuse) VP_HIP_CHECK(launch_maxpool_fwd((const char*)ti.y + oi, (char*)tp.y + op, N, ti.H, ti.W, ti.C, bf, s2));
     }
     return VP_OK;
@@ -1754,6 +1778,7 @@ int vp_pixrefer_set_option(vp_pixrefer_t* h, const char* key, int value) {
 long long vp_pixrefer_counter(vp_pixrefer_t* h, const char* key) {
   if (!h || !key) return -1;
   if (std::string(key) == "bwd_sums_launches") return h->bst_count;
+  if (std::string(key) == "pool_codes_written") return h->pool_codes_written ? 1 : 0;
   return -1;
 }
 
@@ -1865,7 +1890,8 @@ int vp_pixrefer_backward_g_stage(vp_pixrefer_t* h, int stage, void* stream) {
       const int ci = L.src[0] - 1;
       Tens& tc = V.t[ci];
       const char* xin = (const char*)tc.y + tc.elems() / 2 * es;
-      VP_HIP_CHECK(launch_maxpool_bwd(xin, ti.dz, tc.dz, N, tc.H, tc.W, tc.C, bf, st));
+      if (h->pool_codes_written) VP_HIP_CHECK(launch_maxpool_bwd_code(h->vpool_code[ti.name == "pool2"], ti.dz, tc.dz, N, tc.H, tc.W, tc.C, bf, st));
+      else VP_HIP_CHECK(launch_maxpool_bwd(xin, ti.dz, tc.dz, N, tc.H, tc.W, tc.C, bf, st));
     }
   }
   if (split_d) VP_HIP_CHECK(hipStreamWaitEvent(st, h->ev_bjoin, 0));
@@ -2005,6 +2031,10 @@ int vp_pixrefer_tensor(vp_pixrefer_t* h, const char* name, void** ptr, int64_t s
     if (t.name != rest) continue;
     if (field.empty() && !h->store_first_raw && t.producer >= 0 && first_layer_acts_fused(h, *n, n->l[t.producer])) {
       set_err("vp_pixrefer_tensor: the raw output of %s is not stored (its kernel writes the consumers' activations); vp_pixrefer_set_option(h, \"store_first_raw\", 1) before the forward pass", s.c_str());
+      return VP_ERR_STATE;
+    }
+    if (field.empty() && n == &h->V && h->pool_codes_written && (t.name == "conv1/conv1_2" || t.name == "conv2/conv2_2")) {
+      set_err("vp_pixrefer_tensor: the full-resolution output of %s is not stored (the step keeps its 2x2 max pool and the pool's arg-max codes); vp_pixrefer_set_option(h, \"store_first_raw\", 1) before the forward pass", s.c_str());
       return VP_ERR_STATE;
     }
     if (field.empty()) return ret(t.y, t.N, t.H, t.W, t.is_f32 ? (t.name == "decoder_1" ? 4 : 1) : t.C, (t.is_f32 || t.hi) ? VP_F32 : cd);

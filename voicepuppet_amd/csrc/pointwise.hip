@@ -846,6 +846,38 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(const T* __restrict__ 
   }
 }
 
+// The same from the one-byte codes a fused-pool conv epilogue wrote (IgemmArgs::pool_code, [B][H/2][W/2][C] like dy: 0 = no gradient,
+// 1 + k = position k of the window takes it) instead of the full-resolution x: reads 1 + sizeof(T) bytes per pooled element, not 5 sizeof(T)
+template <typename T>
+__global__ __launch_bounds__(256) void maxpool_bwd_code_kernel(const unsigned char* __restrict__ code, const T* __restrict__ dy, T* __restrict__ dx, int B, int H, int W, int C) {
+  constexpr int E = Elem<T>::E;
+  const int ncg = C / E, Ho = H / 2, Wo = W / 2;
+  const size_t total = (size_t)B * Ho * Wo * ncg;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    const int cg = (int)(i % ncg);
+    size_t t = i / ncg;
+    const int ow = (int)(t % Wo); t /= Wo;
+    const int oh = (int)(t % Ho);
+    const int n = (int)(t / Ho);
+    const size_t base = (((size_t)n * H + 2 * oh) * W + 2 * ow) * C + cg * E;
+    const size_t offs[4] = {0, (size_t)C, (size_t)W * C, (size_t)W * C + C};
+    unsigned cw[2];
+    if constexpr (E == 8) { const uint2 c2 = *reinterpret_cast<const uint2*>(code + i * E); cw[0] = c2.x; cw[1] = c2.y; }
+    else { cw[0] = *reinterpret_cast<const unsigned*>(code + i * E); cw[1] = 0; }
+    float g[E];
+    Elem<T>::unpack(*reinterpret_cast<const uint4*>(dy + i * E), g);
+    float o[4][E];
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+      const unsigned c = (cw[e >> 2] >> (8 * (e & 3))) & 0xffu;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) o[k][e] = c == (unsigned)(k + 1) ? g[e] : 0.f;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) *reinterpret_cast<uint4*>(dx + base + offs[k]) = Elem<T>::pack(o[k]);
+  }
+}
+
 // relu' on a stored post-relu tensor: d *= (y > 0)   (used where no bwd-data epilogue can do it)
 template <typename T>
 __global__ __launch_bounds__(256) void relu_bwd_kernel(const T* __restrict__ y, T* __restrict__ d, size_t nvec) {
@@ -1111,6 +1143,13 @@ hipError_t launch_maxpool_bwd(const void* x, const void* dy, void* dx, int B, in
   const size_t work = (size_t)B * (H / 2) * (W / 2) * (C / (is_bf16 ? 8 : 4));
   if (is_bf16) hipLaunchKernelGGL((maxpool_bwd_kernel<bf16>), dim3(nblocks(work)), dim3(256), 0, st, (const bf16*)x, (const bf16*)dy, (bf16*)dx, B, H, W, C);
   else hipLaunchKernelGGL((maxpool_bwd_kernel<float>), dim3(nblocks(work)), dim3(256), 0, st, (const float*)x, (const float*)dy, (float*)dx, B, H, W, C);
+  return hipGetLastError();
+}
+
+hipError_t launch_maxpool_bwd_code(const void* code, const void* dy, void* dx, int B, int H, int W, int C, int is_bf16, hipStream_t st) {
+  const size_t work = (size_t)B * (H / 2) * (W / 2) * (C / (is_bf16 ? 8 : 4));
+  if (is_bf16) hipLaunchKernelGGL((maxpool_bwd_code_kernel<bf16>), dim3(nblocks(work)), dim3(256), 0, st, (const unsigned char*)code, (const bf16*)dy, (bf16*)dx, B, H, W, C);
+  else hipLaunchKernelGGL((maxpool_bwd_code_kernel<float>), dim3(nblocks(work)), dim3(256), 0, st, (const unsigned char*)code, (const float*)dy, (float*)dx, B, H, W, C);
   return hipGetLastError();
 }
 

@@ -306,7 +306,9 @@ class PixReferEngine:
     self.set_option("overlap", 0 if on else 1)
 
   def set_option(self, key, value):
-    """Schedule option of THIS engine's plan (vp_pixrefer_set_option: "overlap", "d_backward_fork", "d_beside_vgg", "store_first_raw")."""
+    """Schedule option of THIS engine's plan (vp_pixrefer_set_option: "overlap", "d_backward_fork", "d_beside_vgg", "store_first_raw").
+    "store_first_raw" = 1 keeps the tensors a step does not need: the raw outputs of encoder_1 / encoder_fg_1 / layer_1 and, on the
+    overlapped bf16 schedule, the full-resolution outputs of VGG conv1_2 / conv2_2 for the fake half (tensor() refuses them otherwise)."""
     _lib.check(self.L.vp_pixrefer_set_option(self.h, key.encode(), int(value)), "vp_pixrefer_set_option(%s)" % key)
 
   def phase_ms(self):
