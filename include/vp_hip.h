@@ -16,6 +16,7 @@
  *   vp_render_colors   replaces  utils/cython/mesh_core.h:63 _render_colors_core (mesh_core.cpp:169-231)
  *   vp_bfm_reconstruct replaces  utils/reconstruct_mesh.py:198-223 Reconstruction_rotation + infer_bfmvid.py:92-99
  *   vp_puppet_*        replaces  infer_bfmvid.py:110-121, :223-224, :229-238 for the rows of many talkers (stream groups)
+ *   vp_jpeg_*          replaces  infer_bfmvid.py:243-244 (cv2.imwrite per frame) with a baseline JPEG encode on the device
  *
  * Conventions: every function returns 0 on success and a negative vp_status otherwise (never throws);
  * all tensor pointers are DEVICE pointers owned by the caller (NHWC, row-major); nothing is allocated
@@ -676,6 +677,50 @@ int vp_puppet_condition(vp_puppet_t* h, const unsigned char* faces, int face_row
 int vp_puppet_tensor(vp_puppet_t* h, const char* name, void** ptr, int64_t shape[4]);
 /* Host only: info = {kind (0 empty, 1 reference panel, 2 copy, 3 exact 2x reduction, 4 bilinear), side, y0, x0} */
 int vp_puppet_slot_info(const vp_puppet_t* h, int slot, int info[4]);
+
+/* ------------------------------------------------------------------------------------------------
+ * JPEG encoding of emitted frames on the device: replaces infer_bfmvid.py:243-244 (cv2.imwrite('output/{}.jpg') per frame, on the host)
+ * for the uint8 RGB frames of a whole launch (Outputs_u8, PuppetStreamGroup.last_frames).  csrc/jpeg_enc.hip.
+ *
+ * The stream is a JFIF 1.01 baseline file: SOI, APP0 (density 1:1), DQT x 2, SOF0 (8 bit, height x width, Y 2x2, Cb 1x1, Cr 1x1), DHT x 4,
+ * DRI, SOS, entropy-coded data with RSTn markers, EOI.  Colour: full-range YCbCr in float32 from the uint8 frame, not rounded; chroma the
+ * mean of each 2 x 2; level shift 128; float32 8 x 8 DCT; the ITU T.81 Annex K quantisation tables scaled by libjpeg's quality rule
+ * (quality 1 .. 100; 75 is what PIL's save() uses), quotient rounded to nearest, ties away from zero; the four Annex K Huffman tables;
+ * restart interval = one MCU row (width / 16 MCUs), RSTn cycling 0 .. 7.
+ *
+ * Capacity rule.  Every restart interval (16 image rows) is coded into a slot of VP_JPEG_SLOT_BYTES(width) = 24 * width bytes of the
+ * workspace: half the interval's raw RGB, 64 bytes per 8 x 8 block on average.  (Uniform random noise at quality 75 takes two fifths of
+ * that in its largest interval, a photograph a tenth.)  An interval whose code, before or after byte stuffing, does not fit its slot is dropped: nothing is
+ * written past a slot or past the caller's row, and out_bytes[frame] becomes -1; the caller encodes that frame on the host.
+ * vp_jpeg_frame_capacity is header + (height / 16) * (slot + 2) + padding: a row of that many bytes holds every frame whose intervals fit.
+ * ---------------------------------------------------------------------------------------------- */
+#define VP_JPEG_MAX_FRAMES 4096
+#define VP_JPEG_SLOT_BYTES(width) (24 * (width))
+typedef struct vp_jpeg_desc {
+  uint32_t struct_bytes;  /* sizeof(vp_jpeg_desc) of the caller's build: must equal vp_jpeg_desc_size() */
+  int32_t max_frames;     /* frames per vp_jpeg_encode: 1 .. VP_JPEG_MAX_FRAMES */
+  int32_t height;         /* multiples of 16 (4:2:0 MCUs), height up to 4096; width up to 832 (an MCU row's coefficients and bit */
+  int32_t width;          /* buffer live in one workgroup's 64 KB of LDS); the product's sizes are 256 and 512 */
+  int32_t quality;        /* 1 .. 100 */
+} vp_jpeg_desc;
+size_t vp_jpeg_desc_size(void);
+typedef struct vp_jpeg vp_jpeg_t;
+/* 0 on a refused descriptor (vp_last_error says why) */
+size_t vp_jpeg_workspace_bytes(const vp_jpeg_desc* d);
+size_t vp_jpeg_frame_capacity(const vp_jpeg_desc* d);
+/* Builds the header and uploads the tables; may wait, once per encoder (replaces nothing per frame: cv2.imwrite, infer_bfmvid.py:243-244,
+ * rebuilds its tables for every file) */
+int vp_jpeg_create(const vp_jpeg_desc* d, void* workspace, size_t workspace_bytes, void* stream, vp_jpeg_t** out);
+/* rgb: DEVICE uint8 [frames,height,width,3] on a 4-byte boundary, 1 .. max_frames frames.  out: DEVICE bytes, frame f's file starts at
+ * out + f * out_row_bytes; out_bytes: DEVICE int [frames], the file's length or -1 (capacity rule above; rows f >= frames are not
+ * touched).  Two launches on `stream`; never waits, never allocates.  Replaces the per-frame cv2.imwrite of infer_bfmvid.py:243-244. */
+int vp_jpeg_encode(vp_jpeg_t* h, const unsigned char* rgb, int frames, unsigned char* out, size_t out_row_bytes, int* out_bytes, void* stream);
+/* "coefficients": int16 [max_frames, height/16, 6 * width/16, 64], per MCU row the blocks in scan order (Y Y Y Y Cb Cr per MCU), zig-zag
+ * inside a block, as quantised.  For tests: encodes store them from the first call of this function on (a second write of 1.5x the frame). */
+int vp_jpeg_tensor(vp_jpeg_t* h, const char* name, void** ptr, int64_t shape[4]);
+/* Host only: the bytes before the entropy-coded data (SOI .. SOS), *n their count; host_out may be NULL to ask for the count alone */
+int vp_jpeg_header(const vp_jpeg_t* h, unsigned char* host_out, size_t cap, size_t* n);
+void vp_jpeg_destroy(vp_jpeg_t* h);
 
 /* Host helper: CRC-32C (Castagnoli, the checksum of TensorFlow checkpoint bundles) of `n` bytes, continuing from `crc` (0 to start). */
 unsigned vp_crc32c(const void* data, size_t n, unsigned crc);

@@ -54,6 +54,11 @@ class PuppetDesc(ctypes.Structure):
 PUPPET_MAX_SLOTS = 128               # include/vp_hip.h VP_PUPPET_MAX_SLOTS
 
 
+class JpegDesc(ctypes.Structure):
+  _fields_ = [("struct_bytes", ctypes.c_uint32), ("max_frames", ctypes.c_int32), ("height", ctypes.c_int32), ("width", ctypes.c_int32),
+              ("quality", ctypes.c_int32)]
+
+
 class BfmModel(ctypes.Structure):
   _fields_ = [("nver", ctypes.c_int), ("ntri", ctypes.c_int), ("meanshape", ctypes.c_void_p), ("idBase", ctypes.c_void_p),
               ("exBase", ctypes.c_void_p), ("meantex", ctypes.c_void_p), ("texBase", ctypes.c_void_p), ("tri", ctypes.c_void_p),
@@ -170,6 +175,14 @@ _SIGNATURES = {
     "vp_puppet_condition": (ctypes.c_int, [_P, _P, ctypes.c_int, _P, ctypes.c_int, _P, _P, _P, _P]),
     "vp_puppet_tensor": (ctypes.c_int, [_P, ctypes.c_char_p, ctypes.POINTER(_P), ctypes.POINTER(ctypes.c_int64)]),
     "vp_puppet_slot_info": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
+    "vp_jpeg_desc_size": (ctypes.c_size_t, []),
+    "vp_jpeg_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(JpegDesc)]),
+    "vp_jpeg_frame_capacity": (ctypes.c_size_t, [ctypes.POINTER(JpegDesc)]),
+    "vp_jpeg_create": (ctypes.c_int, [ctypes.POINTER(JpegDesc), _P, ctypes.c_size_t, _P, ctypes.POINTER(_P)]),
+    "vp_jpeg_encode": (ctypes.c_int, [_P, _P, ctypes.c_int, _P, ctypes.c_size_t, _P, _P]),
+    "vp_jpeg_tensor": (ctypes.c_int, [_P, ctypes.c_char_p, ctypes.POINTER(_P), ctypes.POINTER(ctypes.c_int64)]),
+    "vp_jpeg_header": (ctypes.c_int, [_P, _P, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]),
+    "vp_jpeg_destroy": (None, [_P]),
     "vp_bfm_reconstruct_rows": (ctypes.c_int, [ctypes.POINTER(BfmModel), _P, _P, ctypes.c_int, _P, ctypes.c_int, _P, _P, _P, _P, ctypes.c_size_t, _P]),
     "vp_bfmstream_group_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(BfmStreamGroupDesc)]),
     "vp_bfmstream_group_plan_info": (ctypes.c_int, [ctypes.POINTER(BfmStreamGroupDesc), ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
@@ -277,6 +290,10 @@ def lib():
       want = int(l.vp_puppet_desc_size())
       if want != ctypes.sizeof(PuppetDesc):
         raise RuntimeError("%s: vp_puppet_desc is %d bytes in the library, %d in this binding" % (LIB_PATH, want, ctypes.sizeof(PuppetDesc)))
+    if hasattr(l, "vp_jpeg_desc_size") and l.vp_jpeg_desc_size.argtypes is not None:
+      want = int(l.vp_jpeg_desc_size())
+      if want != ctypes.sizeof(JpegDesc):
+        raise RuntimeError("%s: vp_jpeg_desc is %d bytes in the library, %d in this binding" % (LIB_PATH, want, ctypes.sizeof(JpegDesc)))
     _lib = l
   return _lib
 

@@ -174,6 +174,8 @@ def main(argv=None):
                         help='npz with the photo\'s bfmcoeff [1,257], transform_params [5], center_x, center_y, ratio')
   cmd_parser.add_option('--output_dir', type="string", dest="output_dir", default='output',
                         help='frame directory (the reference always writes output/; infer_clips.py gives every clip its own)')
+  cmd_parser.add_option('--device_jpeg', action="store_true", dest="device_jpeg", default=False,
+                        help='encode the .jpg files on the device (quality 75) instead of PIL on the host pool')
   opts, argv = cmd_parser.parse_args(argv)
 
   if (opts.config_path is None):
@@ -258,6 +260,15 @@ def main(argv=None):
 
     def write_jpg(arr_u8, path):
       Image.fromarray(arr_u8).save(path)
+
+    def write_bytes(data, path):
+      with open(path, 'wb') as fh:
+        fh.write(data)
+    encoder = None
+    if opts.device_jpeg:
+      # the frames never leave the device raw: voicepuppet_amd.jpeg encodes Outputs_u8 where it is, the pool only writes the files
+      from voicepuppet_amd.jpeg import JpegEncoder
+      encoder = JpegEncoder(img_size, img_size, nb, quality=75)
     try:
       for i0 in range(0, T, nb):
         idx = [min(i0 + k, T - 1) for k in range(nb)]
@@ -272,6 +283,15 @@ def main(argv=None):
             targets[k] = 0.5
         # (the reference fetches 'Outputs' and the unused 'Outputs_FG' as float32 and scales on the host, infer_bfmvid.py:240-243; the
         # uint8 frame is formed on the device here: 6 MB instead of 50 MB across PCIe per batch of 8, identical bytes)
+        if encoder is not None:
+          eng = vid2vidnet.engine
+          eng.forward(inputs, fg_inputs, targets)
+          u8 = eng.fetch('Outputs_u8')
+          n = min(nb, T - i0)
+          files = encoder.to_host(*encoder.encode(u8[:n]), u8)
+          for k in range(n):
+            pending.append(pool.submit(write_bytes, files[k], os.path.join(out_dir, '{}.jpg'.format(i0 + k))))
+          continue
         frames = sess.run([vid2vid_nodes['Outputs_u8']],
                           feed_dict={inputs_holder: inputs, fg_inputs_holder: fg_inputs, targets_holder: targets})[0]
         for k in range(nb):

@@ -39,7 +39,8 @@ def rank_commands(opts, clip_list, world):
   out = []
   for r in range(world):
     argv = [sys.executable, '-m', 'voicepuppet_amd.pixrefer.infer_clips', '--config_path', opts.config_path,
-            '--frame_batch', str(opts.frame_batch), '--out_root', opts.out_root, '--gpus', str(world), clip_list]
+            '--frame_batch', str(opts.frame_batch), '--out_root', opts.out_root, '--gpus', str(world)] + \
+           (['--device_jpeg'] if getattr(opts, 'device_jpeg', False) else []) + [clip_list]
     env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(world))
     env.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')
     out.append((argv, env))
@@ -59,6 +60,8 @@ def run_rank(opts, clips, rank, world):
             '--output_dir', os.path.join(opts.out_root, 'clip_%d' % i)]
     if len(clip) == 3:
       argv += ['--bfmcoeff', clip[2]]
+    if getattr(opts, 'device_jpeg', False):
+      argv += ['--device_jpeg']
     infer_bfmvid.main(argv + [clip[0], clip[1]])
   return len(mine)
 
@@ -69,6 +72,8 @@ def main(argv=None):
   cmd_parser.add_option('--gpus', type="int", dest="gpus", default=1, help='ranks (one per GPU)')
   cmd_parser.add_option('--frame_batch', type="int", dest="frame_batch", default=8, help='frames per device batch')
   cmd_parser.add_option('--out_root', type="string", dest="out_root", default='output_clips', help='clip_<i>/ directories go here')
+  cmd_parser.add_option('--device_jpeg', action="store_true", dest="device_jpeg", default=False,
+                        help='passed to infer_bfmvid: encode the .jpg files on the device')
   opts, args = cmd_parser.parse_args(argv)
   if (opts.config_path is None or len(args) != 1):
     logger.error('Please check your parameters.')

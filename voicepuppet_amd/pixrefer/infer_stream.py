@@ -6,7 +6,7 @@
 
 The wav is fed to voicepuppet_amd.stream.PuppetStream in chunks of chunk_ms milliseconds, as a live source would deliver it. Every
 frame is written to output/<i>.jpg as soon as it is emitted, and the per-push latency is logged. At the end the clip is finished and
-muxed as infer_bfmvid muxes it. Under the same np.random.seed the frames are infer_bfmvid's: same count, same ears, same conditioning
+muxed as infer_bfmvid muxes it. --device_jpeg encodes the frames on the device (voicepuppet_amd.jpeg) and writes those bytes. Under the same np.random.seed the frames are infer_bfmvid's: same count, same ears, same conditioning
 by global frame index, coefficients bit-identical or within 1e-5 of max|offline| (tests/test_gpu_stream_cli.py
 states what that means in pixels).
 """
@@ -38,6 +38,8 @@ def main(argv=None):
                         help='npz with the photo\'s bfmcoeff [1,257], transform_params [5], center_x, center_y, ratio')
   cmd_parser.add_option('--output_dir', type="string", dest="output_dir", default='output', help='frame directory')
   cmd_parser.add_option('--chunk_ms', type="float", dest="chunk_ms", default=40.0, help='audio per push, milliseconds')
+  cmd_parser.add_option('--device_jpeg', action="store_true", dest="device_jpeg", default=False,
+                        help='encode the .jpg files on the device (quality 75) instead of PIL on the host pool')
   opts, argv = cmd_parser.parse_args(argv)
 
   if (opts.config_path is None):
@@ -71,7 +73,8 @@ def main(argv=None):
   frame_ms = 1000.0 * gen.frame_wav_scale / gen.sample_rate
   # a window emits at most the frames one chunk completes (a catch-up push runs several windows)
   stream = PuppetStream(config_path, img, bfmcoeff=opts.bfmcoeff, frame_batch=opts.frame_batch,
-                        max_chunk_frames=max(1, int(math.ceil(opts.chunk_ms / frame_ms))))
+                        max_chunk_frames=max(1, int(math.ceil(opts.chunk_ms / frame_ms))),
+                        **({'jpeg_quality': 75} if opts.device_jpeg else {}))
   logger.info('streaming %d samples in chunks of %d (%.0f ms), lookahead %.0f ms', pcm.shape[0], chunk, opts.chunk_ms,
               stream.audio.lookahead_ms)
 
@@ -81,6 +84,10 @@ def main(argv=None):
   pending, lat = [], []
 
   def write_jpg(arr_u8, path):
+    if opts.device_jpeg:               # the device's bytes: a plain file write
+      with open(path, 'wb') as fh:
+        fh.write(arr_u8)
+      return
     Image.fromarray(arr_u8).save(path)
 
   def emit(frames):

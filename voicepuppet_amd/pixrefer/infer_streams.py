@@ -10,7 +10,8 @@ each talker that still has audio its next chunk_ms milliseconds, all frames that
 together, and talker s's frames go to <output_dir>/<s>/<i>.jpg.  The per-push latency is logged.  A talker whose wav has ended is
 finished in a push of its own, as infer_stream finishes its clip.  --seed S gives every talker the ears of an infer_stream run on it
 alone under np.random.seed(S) (each slot draws from its own generator); without it the ears come from numpy's global generator in slot
-order.  Each directory is muxed with its wav as infer_stream muxes (when ffmpeg exists).
+order.  --device_jpeg encodes the frames on the device (voicepuppet_amd.jpeg) and writes those bytes to <i>.jpg: no raw frame is copied
+to the host and the pool only writes files.  Each directory is muxed with its wav as infer_stream muxes (when ffmpeg exists).
 """
 import logging
 import math
@@ -53,6 +54,8 @@ def main(argv=None):
   cmd_parser.add_option('--output_dir', type="string", dest="output_dir", default='output', help='talker s writes <output_dir>/<s>/<i>.jpg')
   cmd_parser.add_option('--chunk_ms', type="float", dest="chunk_ms", default=40.0, help='audio per talker and push, milliseconds')
   cmd_parser.add_option('--seed', type="int", dest="seed", default=None, help='every talker draws its ears as np.random.seed(SEED) would alone')
+  cmd_parser.add_option('--device_jpeg', action="store_true", dest="device_jpeg", default=False,
+                        help='encode the .jpg files on the device (quality 75) instead of PIL on the host pool')
   opts, argv = cmd_parser.parse_args(argv)
 
   if (opts.config_path is None or len(argv) != 1):
@@ -86,7 +89,8 @@ def main(argv=None):
   from voicepuppet_amd.stream import PuppetStreamGroup
   chunk = max(1, int(round(opts.chunk_ms * gen.sample_rate / 1000.0)))
   frame_ms = 1000.0 * gen.frame_wav_scale / gen.sample_rate
-  group = PuppetStreamGroup(config_path, S, frame_batch=opts.frame_batch, max_chunk_frames=max(1, int(math.ceil(opts.chunk_ms / frame_ms))))
+  group = PuppetStreamGroup(config_path, S, frame_batch=opts.frame_batch, max_chunk_frames=max(1, int(math.ceil(opts.chunk_ms / frame_ms))),
+                            **({'jpeg_quality': 75} if opts.device_jpeg else {}))
   for s, (image, _, npz) in enumerate(talkers):
     group.attach(s, ImageLoader().get_data(image)[:, :, ::-1], npz)      # RGB float in [0,1], 512 x 1536
   rngs = [np.random.RandomState(opts.seed) for _ in range(S)] if opts.seed is not None else None
@@ -100,6 +104,10 @@ def main(argv=None):
   def write_jpg(arr_u8, path):
     Image.fromarray(arr_u8).save(path)
 
+  def write_bytes(data, path):
+    with open(path, 'wb') as f:
+      f.write(data)
+
   def push(chunks, finish):
     ears = None
     if rngs is not None:
@@ -108,6 +116,14 @@ def main(argv=None):
     t = time.perf_counter()
     res = group.push(chunks, finish=finish, ears=ears)
     n = sum(len(v) for v in res.values())
+    if opts.device_jpeg:
+      files = group.last_jpeg() if n else {}                           # the one wait of the push: the encoded bytes
+      lat.append(1000.0 * (time.perf_counter() - t))
+      for s in sorted(files):
+        for i, data in files[s]:
+          pending.append(pool.submit(write_bytes, data, os.path.join(out_dirs[s], '{}.jpg'.format(i))))
+      logger.debug('push %d: %d frames, %.2f ms', len(lat), n, lat[-1])
+      return n
     frames = group.last_frames.cpu().numpy() if n else None            # the one wait of the push: the frames go to the encoders
     lat.append(1000.0 * (time.perf_counter() - t))
     row = 0

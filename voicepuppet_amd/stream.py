@@ -424,9 +424,14 @@ class PuppetStreamGroup:
   vp_bfm_reconstruct_rows) and the generator in launches of frame_batch rows, a short last launch padded with the last row.  A push
   only enqueues: frame counts follow from sample counts, the per-row tables (slot, sway rotation, background, geometry) are computed
   on the host first and reach the device through pinned memory; the frames are views of one [K, H, W, 3] tensor (last_frames) that is
-  ready when the current stream reaches it."""
+  ready when the current stream reaches it.
 
-  def __init__(self, config_path, slots, frame_batch=8, max_chunk_frames=1, dtype="f32", img_size=512):
+  jpeg_quality=Q (1 .. 100; None, the default: no encoder exists and push is what it is without the keyword): the group owns a
+  voicepuppet_amd.jpeg.JpegEncoder of frame_batch frames, a push also enqueues the JPEG encode of last_frames in launches of at most
+  frame_batch rows, and last_jpeg() -> {slot: [(global frame index, bytes of the .jpg file)]} for the frames of the last push (the one
+  wait: the lengths, then the used part of the byte rows; the raw frames stay on the device)."""
+
+  def __init__(self, config_path, slots, frame_batch=8, max_chunk_frames=1, dtype="f32", img_size=512, jpeg_quality=None):
     import os
     from .pixrefer import infer_bfmvid as ib
     if not torch.cuda.is_available():
@@ -465,6 +470,11 @@ class PuppetStreamGroup:
     self.last_frames = None
     self.keep_conditioning = False     # tests: keep every row's generator inputs and float Outputs of a push in last_conditioning
     self.last_conditioning = None
+    self.jpeg = None
+    self._jpeg_rows = None
+    if jpeg_quality is not None:
+      from .jpeg import JpegEncoder
+      self.jpeg = JpegEncoder(self.img_size, self.img_size, self.nb, quality=jpeg_quality)
 
   def attach(self, slot, image, bfmcoeff=None):
     ib, H = self.ib, self.img_size
@@ -528,6 +538,7 @@ class PuppetStreamGroup:
     K = int(slot.shape[0])
     res = {s: [] for s in sizes}
     self.last_frames, self.last_conditioning = None, None
+    self._jpeg_rows = None
     if K == 0:
       return res
     render, tex_src, tex_row, cond = launch_tables(slot, g, self.has_coeff, self.bg_row, nb)
@@ -554,11 +565,32 @@ class PuppetStreamGroup:
         n = min(nb, K - i0)
         kept.append([t[:n].clone() for t in (self.inputs, self.fg_inputs, self.targets, eng.fetch("Outputs"))])
     self.last_frames = out[:K]
+    if self.jpeg is not None:
+      # a finishing push flushes the lookahead: K has no small bound, the encoder's launches have (frame_batch rows)
+      data = torch.empty(K, self.jpeg.capacity, dtype=torch.uint8, device="cuda")
+      lengths = torch.empty(K, dtype=torch.int32, device="cuda")
+      for i0 in range(0, K, nb):
+        n = min(nb, K - i0)
+        self.jpeg.encode(out[i0:i0 + n], data[i0:i0 + n], lengths[i0:i0 + n])
+      self._jpeg_rows = (data, lengths, slot, g)
     if kept is not None:
       self.last_conditioning = {"slot": slot, "frame": g,
                                 **{name: torch.cat([b[i] for b in kept]) for i, name in enumerate(("inputs", "fg_inputs", "targets", "Outputs"))}}
     for r in range(K):
       res[int(slot[r])].append((int(g[r]), out[r]))
+    return res
+
+  def last_jpeg(self):
+    """{slot: [(global frame index, .jpg bytes)]} of the last push's frames (jpeg_quality groups); waits for them."""
+    if self.jpeg is None:
+      raise RuntimeError("last_jpeg: the group was created without jpeg_quality")
+    if self._jpeg_rows is None:
+      return {}
+    data, lengths, slot, g = self._jpeg_rows
+    files = self.jpeg.to_host(data, lengths, self.last_frames)
+    res = {}
+    for r, f in enumerate(files):
+      res.setdefault(int(slot[r]), []).append((int(g[r]), f))
     return res
 
   def __del__(self):
@@ -575,10 +607,13 @@ class PuppetStream:
   [H, W, 3] RGB, host array)] of the frames that became exact.  image / bfmcoeff: as PuppetStreamGroup.attach.  BFMNet / PixReferNet
   weights: the checkpoints infer_bfmvid restores (ckpt_bfmnet/bfmnet-65000, ckpt_pixrefer/pixrefernet-20000; TF prefix or .npz), the
   generator from infer_bfmvid's cache.  The group's push only enqueues; this class hands out host-readable frames, so it waits once, at
-  the end of a push that emitted frames."""
+  the end of a push that emitted frames.  With jpeg_quality=Q the second element of every pair is the bytes of the frame's .jpg file,
+  encoded on the device (PuppetStreamGroup), and no raw frame crosses to the host."""
 
-  def __init__(self, config_path, image, bfmcoeff=None, frame_batch=8, max_chunk_frames=1, dtype="f32", img_size=512):
-    self.group = PuppetStreamGroup(config_path, 1, frame_batch=frame_batch, max_chunk_frames=max_chunk_frames, dtype=dtype, img_size=img_size)
+  def __init__(self, config_path, image, bfmcoeff=None, frame_batch=8, max_chunk_frames=1, dtype="f32", img_size=512, jpeg_quality=None):
+    self.group = PuppetStreamGroup(config_path, 1, frame_batch=frame_batch, max_chunk_frames=max_chunk_frames, dtype=dtype, img_size=img_size,
+                                   jpeg_quality=jpeg_quality)
+    self.jpeg_quality = jpeg_quality
     self.group.attach(0, image, bfmcoeff)
     self.audio = self.group.audio
 
@@ -598,5 +633,7 @@ class PuppetStream:
   def _host(self, res):
     if not res[0]:
       return []
+    if self.jpeg_quality is not None:      # the device's .jpg bytes in place of host arrays; no raw frame is copied
+      return self.group.last_jpeg()[0]
     frames = self.group.last_frames.cpu().numpy()
     return [(g, frames[i]) for i, (g, _) in enumerate(res[0])]
