@@ -17,6 +17,7 @@
  *   vp_bfm_reconstruct replaces  utils/reconstruct_mesh.py:198-223 Reconstruction_rotation + infer_bfmvid.py:92-99
  *   vp_puppet_*        replaces  infer_bfmvid.py:110-121, :223-224, :229-238 for the rows of many talkers (stream groups)
  *   vp_jpeg_*          replaces  infer_bfmvid.py:243-244 (cv2.imwrite per frame) with a baseline JPEG encode on the device
+ *   vp_pcmin_*         replaces  generator/loader.py:39-54 (WavLoader: scale, channel mean, resample_poly over a whole file) for live PCM
  *
  * Conventions: every function returns 0 on success and a negative vp_status otherwise (never throws);
  * all tensor pointers are DEVICE pointers owned by the caller (NHWC, row-major); nothing is allocated
@@ -721,6 +722,60 @@ int vp_jpeg_tensor(vp_jpeg_t* h, const char* name, void** ptr, int64_t shape[4])
 /* Host only: the bytes before the entropy-coded data (SOI .. SOS), *n their count; host_out may be NULL to ask for the count alone */
 int vp_jpeg_header(const vp_jpeg_t* h, unsigned char* host_out, size_t cap, size_t* n);
 void vp_jpeg_destroy(vp_jpeg_t* h);
+
+/* ------------------------------------------------------------------------------------------------
+ * Stream ingest: client PCM (interleaved int16 or float32, 1 .. 8 channels, any of up to 8 rates named at create) to the mono float32
+ * out_rate signal vp_bfmstream_group_push takes, on the device and chunk by chunk.  Replaces, for live audio, the whole-file host
+ * conversion of generator/loader.py:39-54 (WavLoader.get_data: scale, mean over the channels, scipy.signal.resample_poly).  csrc/pcm_in.hip.
+ *
+ *   convert   VP_PCM_S16: float32(v) / 32768.  VP_PCM_F32: as is.
+ *   down-mix  1 channel: nothing.  2: (a + b) / 2 in float32.  3 .. 8: float32 sum left to right, one division by the count.
+ *   resample  g = gcd(in_rate, out_rate), up = out_rate / g, down = in_rate / g.  up == down: a copy (no filter, no delay).  Else scipy's
+ *             default design: half = 10 * max(up, down), h = float32(firwin(2 half + 1, 1 / max(up, down), ('kaiser', 5.0))) * up,
+ *             y[m] = sum_k h[m down - k up + half] x[k], x zero outside the clip, m = 0 .. ceil(N up / down) - 1 for a clip of N frames:
+ *             resample_poly(x, up, down).  Each y[m] is one float32 fma chain over the taps of its phase in a fixed order, so the bits of
+ *             a clip's output do not depend on how pushes cut it, on the slot, or on the other slots of a push.
+ *   emission  after n frames of a clip that has not finished: the outputs m with m down + half <= n up - 1 (every tap has arrived),
+ *             at most ceil(n up / down); at finish all ceil(N up / down).  Host arithmetic (vp_pcmin_samples_after): a push never waits.
+ *             The lookahead is half / up input frames = 10 output samples (0.625 ms) when downsampling.
+ * A rate is accepted when its polyphase bank [up][ceil((2 half + 1) / up)] float32 is at most 1 MiB, up <= 65535 and one tile of 256
+ * outputs reads at most 4096 input frames (all of 8000, 11025, 12000, 16000, 22050, 24000, 32000, 44100, 48000, 88200, 96000 and 192000
+ * Hz to 16000 Hz are; 44101 Hz, 3.5 MB, is not).
+ * ---------------------------------------------------------------------------------------------- */
+#define VP_PCMIN_MAX_SLOTS 128
+#define VP_PCMIN_MAX_CHANNELS 8
+enum vp_pcm_format { VP_PCM_S16 = 0, VP_PCM_F32 = 1 };
+typedef struct vp_pcmin_desc {
+  int struct_bytes;       /* sizeof(vp_pcmin_desc) of the caller's build: must equal vp_pcmin_desc_size() */
+  int slots;              /* 1 .. VP_PCMIN_MAX_SLOTS */
+  int out_rate;           /* 16000 */
+  int max_in_frames;      /* input frames per slot and push: 1 .. 4194304 (lane offsets are 32-bit; callers split longer chunks) */
+  int n_rates;            /* 1 .. 8 */
+  int rates[8];           /* the input rates slots may be opened with, each once */
+} vp_pcmin_desc;
+size_t vp_pcmin_desc_size(void);
+typedef struct vp_pcmin vp_pcmin_t;
+/* Host only, no handle.  vp_pcmin_ratio: up, down, half and the taps per phase (any may be NULL); up == down gives half 0, 1 tap.
+ * vp_pcmin_bank: h[2 half + 1] as above (h[0] = 1 for up == down).  vp_pcmin_samples_after: the emission rule, -1 on a bad argument. */
+int vp_pcmin_ratio(int in_rate, int out_rate, int* up, int* down, int* half, int* taps_per_phase);
+int vp_pcmin_bank(int in_rate, int out_rate, float* h);
+long long vp_pcmin_samples_after(int in_rate, int out_rate, long long in_frames, int finished);
+/* 0 on a refused descriptor (vp_last_error names the field) */
+size_t vp_pcmin_workspace_bytes(const vp_pcmin_desc* d);
+/* Designs the filters and uploads their banks; may wait, once per handle */
+int vp_pcmin_create(const vp_pcmin_desc* d, void* workspace, size_t workspace_bytes, void* stream, vp_pcmin_t** out);
+void vp_pcmin_destroy(vp_pcmin_t* h);
+/* Slot `slot` starts a clip of in_rate (one of the descriptor's), `channels` interleaved channels of `format`; also restarts an open slot.
+ * Enqueues the clearing of the slot's history on `stream`; does not wait. */
+int vp_pcmin_open_slot(vp_pcmin_t* h, int slot, int in_rate, int channels, int format, void* stream);
+/* Host only: out_samples[s] (may be NULL) a push of in_frames[s] new frames per slot emits, finish[s] != 0 ending slot s's clip after them
+ * (finish may be NULL); returns the sum, or -1 (frames or finish for a slot that is not open or has finished, a count outside
+ * 0 .. max_in_frames) */
+long long vp_pcmin_ready(const vp_pcmin_t* h, const long long* in_frames, const int* finish, long long* out_samples);
+/* raw: DEVICE bytes on a 16-byte boundary, the slots' new frames packed in slot order: slot s's segment is in_frames[s] * channels * sample
+ * bytes long and starts at the next 16-byte boundary after the previous one.  pcm_out: DEVICE float32, the slots' new samples packed in
+ * slot order - the pcm argument of vp_bfmstream_group_push with n[s] = out_samples[s].  One launch on `stream`; never waits, never allocates. */
+int vp_pcmin_push(vp_pcmin_t* h, const void* raw, const long long* in_frames, const int* finish, float* pcm_out, void* stream);
 
 /* Host helper: CRC-32C (Castagnoli, the checksum of TensorFlow checkpoint bundles) of `n` bytes, continuing from `crc` (0 to start). */
 unsigned vp_crc32c(const void* data, size_t n, unsigned crc);

@@ -59,6 +59,15 @@ class JpegDesc(ctypes.Structure):
               ("quality", ctypes.c_int32)]
 
 
+class PcmInDesc(ctypes.Structure):
+  _fields_ = [("struct_bytes", ctypes.c_int), ("slots", ctypes.c_int), ("out_rate", ctypes.c_int), ("max_in_frames", ctypes.c_int),
+              ("n_rates", ctypes.c_int), ("rates", ctypes.c_int * 8)]
+
+
+PCMIN_MAX_SLOTS, PCMIN_MAX_CHANNELS = 128, 8      # include/vp_hip.h VP_PCMIN_MAX_SLOTS, VP_PCMIN_MAX_CHANNELS
+PCM_S16, PCM_F32 = 0, 1
+
+
 class BfmModel(ctypes.Structure):
   _fields_ = [("nver", ctypes.c_int), ("ntri", ctypes.c_int), ("meanshape", ctypes.c_void_p), ("idBase", ctypes.c_void_p),
               ("exBase", ctypes.c_void_p), ("meantex", ctypes.c_void_p), ("texBase", ctypes.c_void_p), ("tri", ctypes.c_void_p),
@@ -183,6 +192,16 @@ _SIGNATURES = {
     "vp_jpeg_tensor": (ctypes.c_int, [_P, ctypes.c_char_p, ctypes.POINTER(_P), ctypes.POINTER(ctypes.c_int64)]),
     "vp_jpeg_header": (ctypes.c_int, [_P, _P, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]),
     "vp_jpeg_destroy": (None, [_P]),
+    "vp_pcmin_desc_size": (ctypes.c_size_t, []),
+    "vp_pcmin_ratio": (ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [ctypes.POINTER(ctypes.c_int)] * 4),
+    "vp_pcmin_bank": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _P]),
+    "vp_pcmin_samples_after": (ctypes.c_longlong, [ctypes.c_int, ctypes.c_int, ctypes.c_longlong, ctypes.c_int]),
+    "vp_pcmin_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(PcmInDesc)]),
+    "vp_pcmin_create": (ctypes.c_int, [ctypes.POINTER(PcmInDesc), _P, ctypes.c_size_t, _P, ctypes.POINTER(_P)]),
+    "vp_pcmin_destroy": (None, [_P]),
+    "vp_pcmin_open_slot": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P]),
+    "vp_pcmin_ready": (ctypes.c_longlong, [_P, ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_longlong)]),
+    "vp_pcmin_push": (ctypes.c_int, [_P, _P, ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_int), _P, _P]),
     "vp_bfm_reconstruct_rows": (ctypes.c_int, [ctypes.POINTER(BfmModel), _P, _P, ctypes.c_int, _P, ctypes.c_int, _P, _P, _P, _P, ctypes.c_size_t, _P]),
     "vp_bfmstream_group_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(BfmStreamGroupDesc)]),
     "vp_bfmstream_group_plan_info": (ctypes.c_int, [ctypes.POINTER(BfmStreamGroupDesc), ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
@@ -294,6 +313,10 @@ def lib():
       want = int(l.vp_jpeg_desc_size())
       if want != ctypes.sizeof(JpegDesc):
         raise RuntimeError("%s: vp_jpeg_desc is %d bytes in the library, %d in this binding" % (LIB_PATH, want, ctypes.sizeof(JpegDesc)))
+    if hasattr(l, "vp_pcmin_desc_size") and l.vp_pcmin_desc_size.argtypes is not None:
+      want = int(l.vp_pcmin_desc_size())
+      if want != ctypes.sizeof(PcmInDesc):
+        raise RuntimeError("%s: vp_pcmin_desc is %d bytes in the library, %d in this binding" % (LIB_PATH, want, ctypes.sizeof(PcmInDesc)))
     _lib = l
   return _lib
 

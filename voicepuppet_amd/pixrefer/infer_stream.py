@@ -6,7 +6,8 @@
 
 The wav is fed to voicepuppet_amd.stream.PuppetStream in chunks of chunk_ms milliseconds, as a live source would deliver it. Every
 frame is written to output/<i>.jpg as soon as it is emitted, and the per-push latency is logged. At the end the clip is finished and
-muxed as infer_bfmvid muxes it. --device_jpeg encodes the frames on the device (voicepuppet_amd.jpeg) and writes those bytes. Under the same np.random.seed the frames are infer_bfmvid's: same count, same ears, same conditioning
+muxed as infer_bfmvid muxes it. --native_pcm pushes the wav as stored (its rate, channels, int16 or float32 samples; chunk_ms of source
+frames per push) and leaves conversion, down-mix and resampling to the device (voicepuppet_amd.pcm) instead of WavLoader. --device_jpeg encodes the frames on the device (voicepuppet_amd.jpeg) and writes those bytes. Under the same np.random.seed the frames are infer_bfmvid's: same count, same ears, same conditioning
 by global frame index, coefficients bit-identical or within 1e-5 of max|offline| (tests/test_gpu_stream_cli.py
 states what that means in pixels).
 """
@@ -40,6 +41,8 @@ def main(argv=None):
   cmd_parser.add_option('--chunk_ms', type="float", dest="chunk_ms", default=40.0, help='audio per push, milliseconds')
   cmd_parser.add_option('--device_jpeg', action="store_true", dest="device_jpeg", default=False,
                         help='encode the .jpg files on the device (quality 75) instead of PIL on the host pool')
+  cmd_parser.add_option('--native_pcm', action="store_true", dest="native_pcm", default=False,
+                        help='push the wav as it is (its rate, channels and sample type): converted and resampled on the device, chunk by chunk')
   opts, argv = cmd_parser.parse_args(argv)
 
   if (opts.config_path is None):
@@ -65,16 +68,23 @@ def main(argv=None):
   params = gen.params
   params.batch_size = 1
   gen.set_params(params)
-  pcm = WavLoader(sr=gen.sample_rate).get_data(audio_file).astype(np.float32)
+  pcm_format = None
+  if opts.native_pcm:
+    from voicepuppet_amd.pcm import read_wav
+    rate, pcm, fmt = read_wav(audio_file)                   # [frames, channels] as stored; chunk_ms of SOURCE frames per push
+    pcm_format = (rate, pcm.shape[1], fmt)
+  else:
+    rate = gen.sample_rate
+    pcm = WavLoader(sr=gen.sample_rate).get_data(audio_file).astype(np.float32)
   img = ImageLoader().get_data(image_file)[:, :, ::-1]      # RGB float in [0,1], 512 x 1536
 
   from voicepuppet_amd.stream import PuppetStream
-  chunk = max(1, int(round(opts.chunk_ms * gen.sample_rate / 1000.0)))
+  chunk = max(1, int(round(opts.chunk_ms * rate / 1000.0)))
   frame_ms = 1000.0 * gen.frame_wav_scale / gen.sample_rate
   # a window emits at most the frames one chunk completes (a catch-up push runs several windows)
   stream = PuppetStream(config_path, img, bfmcoeff=opts.bfmcoeff, frame_batch=opts.frame_batch,
                         max_chunk_frames=max(1, int(math.ceil(opts.chunk_ms / frame_ms))),
-                        **({'jpeg_quality': 75} if opts.device_jpeg else {}))
+                        **({'jpeg_quality': 75} if opts.device_jpeg else {}), **({'pcm_format': pcm_format} if pcm_format else {}))
   logger.info('streaming %d samples in chunks of %d (%.0f ms), lookahead %.0f ms', pcm.shape[0], chunk, opts.chunk_ms,
               stream.audio.lookahead_ms)
 
@@ -97,7 +107,7 @@ def main(argv=None):
   try:
     for at in range(0, pcm.shape[0], chunk):
       t = time.perf_counter()
-      frames = stream.push(pcm[at:at + chunk])
+      frames = stream.push_raw(pcm[at:at + chunk]) if opts.native_pcm else stream.push(pcm[at:at + chunk])
       lat.append(1000.0 * (time.perf_counter() - t))
       emit(frames)
       logger.debug('push %d: %d frames, %.2f ms', len(lat), len(frames), lat[-1])

@@ -10,7 +10,9 @@ each talker that still has audio its next chunk_ms milliseconds, all frames that
 together, and talker s's frames go to <output_dir>/<s>/<i>.jpg.  The per-push latency is logged.  A talker whose wav has ended is
 finished in a push of its own, as infer_stream finishes its clip.  --seed S gives every talker the ears of an infer_stream run on it
 alone under np.random.seed(S) (each slot draws from its own generator); without it the ears come from numpy's global generator in slot
-order.  --device_jpeg encodes the frames on the device (voicepuppet_amd.jpeg) and writes those bytes to <i>.jpg: no raw frame is copied
+order.  --native_pcm pushes every wav as stored (its rate, channels, int16 or float32 samples; chunk_ms of source frames per push):
+conversion, down-mix and resampling run on the device in the same push (voicepuppet_amd.pcm) instead of WavLoader on the whole file.
+--device_jpeg encodes the frames on the device (voicepuppet_amd.jpeg) and writes those bytes to <i>.jpg: no raw frame is copied
 to the host and the pool only writes files.  Each directory is muxed with its wav as infer_stream muxes (when ffmpeg exists).
 """
 import logging
@@ -56,6 +58,8 @@ def main(argv=None):
   cmd_parser.add_option('--seed', type="int", dest="seed", default=None, help='every talker draws its ears as np.random.seed(SEED) would alone')
   cmd_parser.add_option('--device_jpeg', action="store_true", dest="device_jpeg", default=False,
                         help='encode the .jpg files on the device (quality 75) instead of PIL on the host pool')
+  cmd_parser.add_option('--native_pcm', action="store_true", dest="native_pcm", default=False,
+                        help='push every wav as it is (its rate, channels and sample type): converted and resampled on the device, chunk by chunk')
   opts, argv = cmd_parser.parse_args(argv)
 
   if (opts.config_path is None or len(argv) != 1):
@@ -84,15 +88,26 @@ def main(argv=None):
   params = gen.params
   params.batch_size = 1
   gen.set_params(params)
-  pcm = [WavLoader(sr=gen.sample_rate).get_data(a).astype(np.float32) for _, a, _ in talkers]
+  formats = None
+  if opts.native_pcm:
+    from voicepuppet_amd.pcm import read_wav
+    wavs = [read_wav(a) for _, a, _ in talkers]             # (rate, [frames, channels] as stored, fmt)
+    pcm = [w[1] for w in wavs]
+    formats = [(w[0], w[1].shape[1], w[2]) for w in wavs]
+    chunks_of = [max(1, int(round(opts.chunk_ms * f[0] / 1000.0))) for f in formats]       # chunk_ms of SOURCE frames per push
+  else:
+    pcm = [WavLoader(sr=gen.sample_rate).get_data(a).astype(np.float32) for _, a, _ in talkers]
 
   from voicepuppet_amd.stream import PuppetStreamGroup
   chunk = max(1, int(round(opts.chunk_ms * gen.sample_rate / 1000.0)))
+  if formats is None:
+    chunks_of = [chunk] * S
   frame_ms = 1000.0 * gen.frame_wav_scale / gen.sample_rate
   group = PuppetStreamGroup(config_path, S, frame_batch=opts.frame_batch, max_chunk_frames=max(1, int(math.ceil(opts.chunk_ms / frame_ms))),
-                            **({'jpeg_quality': 75} if opts.device_jpeg else {}))
+                            **({'jpeg_quality': 75} if opts.device_jpeg else {}),
+                            **({'ingest_rates': sorted(set(f[0] for f in formats))} if formats else {}))
   for s, (image, _, npz) in enumerate(talkers):
-    group.attach(s, ImageLoader().get_data(image)[:, :, ::-1], npz)      # RGB float in [0,1], 512 x 1536
+    group.attach(s, ImageLoader().get_data(image)[:, :, ::-1], npz, *(formats[s] if formats else ()))      # RGB float in [0,1], 512 x 1536
   rngs = [np.random.RandomState(opts.seed) for _ in range(S)] if opts.seed is not None else None
   logger.info('streaming %d talkers in chunks of %d samples (%.0f ms), lookahead %.0f ms', S, chunk, opts.chunk_ms, group.audio.lookahead_ms)
 
@@ -111,10 +126,14 @@ def main(argv=None):
   def push(chunks, finish):
     ears = None
     if rngs is not None:
-      k = group.audio.ready({s: len(c) for s, c in chunks.items()}, finish)
+      n = {s: len(c) for s, c in chunks.items()}
+      if formats is not None:                # 16 kHz samples the ingest will emit for these source frames (host arithmetic)
+        r = group.ingest.ready(n, finish)
+        n = {s: r[s] for s in set(n) | set(finish)}
+      k = group.audio.ready(n, finish)
       ears = {s: rngs[s].rand(k[s], 1).astype(np.float32) / 100 for s in range(S) if k[s]}
     t = time.perf_counter()
-    res = group.push(chunks, finish=finish, ears=ears)
+    res = (group.push_raw if formats is not None else group.push)(chunks, finish=finish, ears=ears)
     n = sum(len(v) for v in res.values())
     if opts.device_jpeg:
       files = group.last_jpeg() if n else {}                           # the one wait of the push: the encoded bytes
@@ -135,16 +154,16 @@ def main(argv=None):
     return n
 
   try:
-    at, live = 0, set(range(S))
+    at, live = 0, set(range(S))              # `at`: pushes so far; talker s is at frame at * chunks_of[s] of its wav
     while live:
-      chunks = {s: pcm[s][at:at + chunk] for s in live if at < pcm[s].shape[0]}
+      chunks = {s: pcm[s][at * chunks_of[s]:(at + 1) * chunks_of[s]] for s in live if at * chunks_of[s] < pcm[s].shape[0]}
       if chunks:
         total += push(chunks, ())
-      ended = sorted(s for s in live if at + chunk >= pcm[s].shape[0])
+      ended = sorted(s for s in live if (at + 1) * chunks_of[s] >= pcm[s].shape[0])
       if ended:
         total += push({}, ended)
         live -= set(ended)
-      at += chunk
+      at += 1
     for f in pending:
       f.result()
   finally:

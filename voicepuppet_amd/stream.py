@@ -249,7 +249,6 @@ class AudioStreamGroup:
         raise IndexError("slot %d of %d" % (s, self.slots))
     chunks = {int(s): v for s, v in pcm_by_slot.items()}
     sizes = {s: (int(chunks[s].numel()) if torch.is_tensor(chunks[s]) else int(np.asarray(chunks[s]).size)) if s in chunks else 0 for s in slots}
-    k = self.ready(sizes, finish)
     total = sum(sizes.values())
     if total == 0:
       pcm = None
@@ -264,6 +263,25 @@ class AudioStreamGroup:
         if sizes[s]:
           pcm[o:o + sizes[s]].copy_(AudioStream._to_device(chunks[s]).reshape(-1))
           o += sizes[s]
+    return self.push_device_packed(pcm, sizes, finish, ears)
+
+  def push_device_packed(self, pcm, sizes, finish=(), ears=None):
+    """push_packed for samples that are already packed on the device: pcm, a 1-D f32 device tensor with the slots' new samples in slot
+    order (None when there are none; voicepuppet_amd.pcm.PcmIngest.push returns it so), sizes {slot: samples} (or a sequence of `slots`
+    counts) of the slots pushed.  Nothing is copied."""
+    sizes = {int(s): int(v) for s, v in (sizes.items() if isinstance(sizes, dict) else enumerate(sizes))}
+    for s in finish:
+      sizes.setdefault(int(s), 0)
+    for s in sizes:
+      if not 0 <= s < self.slots:
+        raise IndexError("slot %d of %d" % (s, self.slots))
+    total = sum(sizes.values())
+    if total:
+      if not (torch.is_tensor(pcm) and pcm.is_cuda and pcm.dtype == torch.float32 and pcm.is_contiguous() and pcm.numel() == total):
+        raise ValueError("push_device_packed: a contiguous f32 device tensor of %d samples" % total)
+    else:
+      pcm = None
+    k = self.ready(sizes, finish)
     K = sum(k)
     out = torch.empty(K, 64, dtype=torch.float32, device="cuda")
     e = None
@@ -431,7 +449,7 @@ class PuppetStreamGroup:
   frame_batch rows, and last_jpeg() -> {slot: [(global frame index, bytes of the .jpg file)]} for the frames of the last push (the one
   wait: the lengths, then the used part of the byte rows; the raw frames stay on the device)."""
 
-  def __init__(self, config_path, slots, frame_batch=8, max_chunk_frames=1, dtype="f32", img_size=512, jpeg_quality=None):
+  def __init__(self, config_path, slots, frame_batch=8, max_chunk_frames=1, dtype="f32", img_size=512, jpeg_quality=None, ingest_rates=None):
     import os
     from .pixrefer import infer_bfmvid as ib
     if not torch.cuda.is_available():
@@ -475,8 +493,14 @@ class PuppetStreamGroup:
     if jpeg_quality is not None:
       from .jpeg import JpegEncoder
       self.jpeg = JpegEncoder(self.img_size, self.img_size, self.nb, quality=jpeg_quality)
+    self.ingest = None
+    self._ingest_fmt = {}
+    if ingest_rates is not None:
+      from .pcm import PcmIngest
+      self.ingest = PcmIngest(self.slots, rates=ingest_rates, out_rate=self.audio.desc.sample_rate)
 
-  def attach(self, slot, image, bfmcoeff=None):
+  def attach(self, slot, image, bfmcoeff=None, rate=16000, channels=1, fmt="s16"):
+    """rate / channels / fmt: what push_raw will be given for this slot (groups created with ingest_rates; ignored otherwise)."""
     ib, H = self.ib, self.img_size
     slot = int(slot)
     if not 0 <= slot < self.slots:
@@ -499,12 +523,16 @@ class PuppetStreamGroup:
                                        int(side), int(y0), int(x0), _stream()), "vp_puppet_attach")
     self.has_coeff[slot] = coeff is not None
     self.attached[slot] = True
+    if self.ingest is not None:
+      self._ingest_fmt[slot] = (int(rate), int(channels), fmt)
     self.reset_slot(slot)
 
   def reset_slot(self, slot):
-    """Slot `slot` starts a new clip (audio session, head sway, frame counter); its photo stays."""
+    """Slot `slot` starts a new clip (audio session, head sway, frame counter, ingest filter state); its photo stays."""
     self.audio.reset_slot(slot)
     self.plan.reset_slot(int(slot))
+    if self.ingest is not None and int(slot) in self._ingest_fmt:
+      self.ingest.open_slot(int(slot), *self._ingest_fmt[int(slot)])
 
   def frame(self, slot):
     """Frames emitted so far in slot `slot`'s clip."""
@@ -527,13 +555,29 @@ class PuppetStreamGroup:
     return [dev[o:o + a.nbytes].view(tdt[a.dtype]).view(a.shape) for a, o in zip(parts, offs)]
 
   def push(self, pcm_by_slot, finish=(), ears=None):
-    from .utils.reconstruct_mesh import Compute_rotation_matrix
-    L, nb, H = self.L, self.nb, self.img_size
     for s in set(int(s) for s in pcm_by_slot) | set(int(s) for s in finish):
       if not (0 <= s < self.slots and self.attached[s]):
         raise ValueError("slot %d has no photo attached" % s)
     # host first: frame counts from sample counts, then every per-row quantity
-    coeff, k, sizes = self.audio.push_packed(pcm_by_slot, finish, ears)
+    return self._frames(*self.audio.push_packed(pcm_by_slot, finish, ears))
+
+  def push_raw(self, raw_by_slot, finish=(), ears=None):
+    """push for client PCM as it arrives: {slot: interleaved int16 / float32 frames at the rate, channel count and format the slot was
+    attached with} -> the same result.  The ingest (voicepuppet_amd.pcm.PcmIngest: convert, down-mix, resample to 16 kHz, on the device)
+    and the push that exists are enqueued back to back; a slot in `finish` flushes its last samples and ends its clip in the same push."""
+    if self.ingest is None:
+      raise RuntimeError("push_raw: the group was created without ingest_rates")
+    slots = set(int(s) for s in raw_by_slot) | set(int(s) for s in finish)
+    for s in slots:
+      if not (0 <= s < self.slots and self.attached[s]):
+        raise ValueError("slot %d has no photo attached" % s)
+    pcm, n = self.ingest.push(raw_by_slot, finish)
+    return self._frames(*self.audio.push_device_packed(pcm, {s: n[s] for s in slots}, finish, ears))
+
+  def _frames(self, coeff, k, sizes):
+    """The frame half of a push: the packed coefficients of AudioStreamGroup.push_packed -> {slot: [(global frame index, frame)]}."""
+    from .utils.reconstruct_mesh import Compute_rotation_matrix
+    L, nb, H = self.L, self.nb, self.img_size
     slot, g, angles = self.plan.rows(k)
     K = int(slot.shape[0])
     res = {s: [] for s in sizes}
@@ -610,11 +654,13 @@ class PuppetStream:
   the end of a push that emitted frames.  With jpeg_quality=Q the second element of every pair is the bytes of the frame's .jpg file,
   encoded on the device (PuppetStreamGroup), and no raw frame crosses to the host."""
 
-  def __init__(self, config_path, image, bfmcoeff=None, frame_batch=8, max_chunk_frames=1, dtype="f32", img_size=512, jpeg_quality=None):
+  def __init__(self, config_path, image, bfmcoeff=None, frame_batch=8, max_chunk_frames=1, dtype="f32", img_size=512, jpeg_quality=None,
+               pcm_format=None):
+    """pcm_format=(rate, channels, fmt): the stream also takes client PCM of that form through push_raw (PuppetStreamGroup.push_raw)."""
     self.group = PuppetStreamGroup(config_path, 1, frame_batch=frame_batch, max_chunk_frames=max_chunk_frames, dtype=dtype, img_size=img_size,
-                                   jpeg_quality=jpeg_quality)
+                                   jpeg_quality=jpeg_quality, **({'ingest_rates': (pcm_format[0],)} if pcm_format else {}))
     self.jpeg_quality = jpeg_quality
-    self.group.attach(0, image, bfmcoeff)
+    self.group.attach(0, image, bfmcoeff, *(pcm_format or ()))
     self.audio = self.group.audio
 
   @property
@@ -627,7 +673,12 @@ class PuppetStream:
   def push(self, pcm):
     return self._host(self.group.push({0: pcm}))
 
+  def push_raw(self, raw):
+    return self._host(self.group.push_raw({0: raw}))
+
   def finish(self):
+    if self.group.ingest is not None:       # the resampler's last samples first: one push ends both
+      return self._host(self.group.push_raw({}, finish=(0,)))
     return self._host(self.group.push({}, finish=(0,)))
 
   def _host(self, res):
