@@ -32,8 +32,8 @@ Reduced case tables (the full cross products need not run; every value of every 
            five of them split the rows into several segments with a shorter last one (the launcher's formula is recomputed and asserted).
   stem     (B, H, W) = (1, 5, 80) (3, 125, 80) (2, 8, 80) (1, 9, 7), cout = 32.
   in place one f32 BFMNetEngine forward with vp_tune("bfm_dwproj", 1) and 0: both `pooled` tensors against the float64 MfccNet + pool.
-Not here: conv_first_kernel<bf16> and the bf16 instantiations of maxpool_same_kernel - no plan launches them (dead code is not tested);
-the training kernels of bfm_train.hip.
+Not here: conv_first_kernel<bf16> and the bf16 instantiations of maxpool_same_kernel - no plan launches them (dead code is not tested).
+The training kernels of bfm_train.hip and gru_device.h have their own file, test_gpu_bfmnet_train_ops.py.
 
 Measured on an MI355X (worst |got - ref| / bound per kernel, over all cases of the kernel):
   dwproj_kernel 0.149 (ce = 16 and 32; 0.012 or less from ce = 384 up, 0.014 just under the address limit)    conv_first_kernel 0.099

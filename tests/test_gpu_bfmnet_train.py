@@ -73,7 +73,9 @@ def test_train_step_matches_oracle(B, T, seq, with_masks):
 
 
 def test_single_kernels_against_numpy():
-  """depthwise weight gradient, SAME max-pool backward, GRU backward through time and the vertex loss on their own."""
+  """The depthwise weight gradient at (2, 9, 5, 8) and the SAME max-pool backward at one tie-free shape of each of the net's two
+  geometries, against numpy / autograd.  The per-element float64 parity of every training kernel - these two over their launch classes
+  and with ties, the batch-norm, GRU, vertex-loss, reduction and optimiser kernels - is tests/test_gpu_bfmnet_train_ops.py."""
   from voicepuppet_amd import _lib
   import ctypes
   L = _lib.lib()

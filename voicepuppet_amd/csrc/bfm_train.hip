@@ -547,6 +547,7 @@ int vp_bn_act_train_bwd(const float* x, const float* da, size_t pixels, int c, c
 // the same without a following activation
 int vp_bn_train_bwd(const float* x, const float* dz, size_t pixels, int c, const float* mean, const float* rstd, float* dx, float* dbeta,
                     void* workspace, void* stream) {
+  if (!x || !dz || !mean || !rstd || !dx || !dbeta || !workspace || pixels < 1 || c < 4 || c % 4) { set_err("vp_bn_train_bwd: bad argument"); return VP_ERR_ARG; }
   return vp_bn_act_train_bwd(x, dz, pixels, c, mean, rstd, nullptr, 0, dx, dbeta, workspace, stream);
 }
 
@@ -622,7 +623,7 @@ int vp_dwconv7x3_wgrad(const float* x, const float* dy, float* dw, int b, int h,
 
 // backward of vp_maxpool_hw (tf.layers.max_pooling2d 'same')
 int vp_maxpool_hw_bwd(const float* x, const float* dy, float* dx, int b, int h, int w, int c, int kh, int kw, int sh, int sw, void* stream) {
-  if (!x || !dy || !dx || b < 1 || c < 4 || c % 4 || kh < 1 || kw < 1 || sh < 1 || sw < 1) { set_err("vp_maxpool_hw_bwd: bad argument"); return VP_ERR_ARG; }
+  if (!x || !dy || !dx || b < 1 || h < 1 || w < 1 || c < 4 || c % 4 || kh < 1 || kw < 1 || sh < 1 || sw < 1) { set_err("vp_maxpool_hw_bwd: bad argument"); return VP_ERR_ARG; }
   const int ho = (h + sh - 1) / sh, wo = (w + sw - 1) / sw;
   int th = (ho - 1) * sh + kh - h; if (th < 0) th = 0;
   int tw = (wo - 1) * sw + kw - w; if (tw < 0) tw = 0;
@@ -698,8 +699,7 @@ int vp_gru_split_recurrent(const float* gates_kernel, const float* cand_kernel, 
 }
 
 __global__ __launch_bounds__(256) void mul_kernel(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ out, size_t n) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < n) out[i] = a[i] * b[i];
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) out[i] = a[i] * b[i];   // tblk caps the grid
 }
 int vp_mul_f32(const float* a, const float* b, float* out, size_t n, void* stream) {
   if (!a || !b || !out || n < 1) { set_err("vp_mul_f32: bad argument"); return VP_ERR_ARG; }
