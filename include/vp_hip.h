@@ -168,7 +168,9 @@ int vp_pixrefer_set_option(vp_pixrefer_t* h, const char* key, int value);
  * float32 partial sums); "vgg_real_fork" k (default 3): the VGG pass of the real half starts on the side stream in front of generator layer
  * k (TF scope order; 0 = right behind the input packing).  vp_pixrefer_counter: "bwd_sums_launches" = launches since create that carried
  * such sums; "pool_codes_written" = 1 when the last forward pass wrote the VGG pool codes in place of the full-resolution conv1_2 /
- * conv2_2 outputs of the fake half, else 0 (-1: unknown key); for tests. */
+ * conv2_2 outputs of the fake half, else 0; "pool_bwd_fused" = 1 when the last backward pass left the VGG pools' gradients to the loader
+ * of the conv_c64 backward-data launches below them (vp_tune "pool_bwd_fused"; "v/conv1/conv1_2:dy" / "v/conv2/conv2_2:dy" are then
+ * written out when vp_pixrefer_tensor asks for them), else 0 (-1: unknown key); for tests. */
 long long vp_pixrefer_counter(vp_pixrefer_t* h, const char* key);
 /* Node values PixReferNet.execute hands to a caller, formed on the device from the last forward pass into `dst` (device memory,
  * N * H * H * 3 elements): what = 0 Outputs (float32, (x + 1) / 2: pixrefer.py:424 / :380), 1 the same as uint8 frames (clamp, * 255,
@@ -224,7 +226,10 @@ int vp_pixrefer_pack_frames(const unsigned char* example_frames, const unsigned 
  * those layers ran on before), "s2c64" (smallest launch, in 4 x 16-pixel tiles, of the 64 -> 128 stride-2 convolutions that runs on
  * conv_s2c64.hip: default 512, 0 = never), "s2c64_pair" (default 1: its two-output backward-data form for merged2_decoder_2), "patch4"
  * (default 1: 4x4 stride-1 layers on the unrolled patch kernel with 16 tap steps), "bfm_dwproj" (default 1: BFMNet's depthwise + projection
- * in one kernel; read at every forward call).  No counterpart in the reference.  (The step executor's schedule is per plan: vp_pixrefer_desc / vp_pixrefer_set_option.) */
+ * in one kernel; read at every forward call), "pool_bwd_fused" (default 1: where the forward pass wrote VGG pool codes and the backward-data
+ * launch of conv1_2 / conv2_2 is planned on conv_c64.hip, that launch reads the pool's gradient and codes and expands them in its loader -
+ * no pool-backward launch, no full-resolution gradient in memory - conv1_2 always, conv2_2 where its launch has at least 4096 tiles of 4 x 16
+ * pixels, 16 frames at 256 x 256; 0: vp_maxpool2x2_bwd_code's kernel writes it out; 2 / 3 / 4: conv1_2 only / conv2_2 only / both at every size).  No counterpart in the reference.  (The step executor's schedule is per plan: vp_pixrefer_desc / vp_pixrefer_set_option.) */
 int vp_tune(const char* key, int value);
 /* Round-6 plan heuristics: "igemm_small_grid" (default 128: a launch whose 128 x 128 tiling has at most that many blocks per class takes the
  * 64-row x 128-pixel tile - twice the blocks; 0: off), "igemm_splitk_target" (default 64, rounds 2-5: 128: resident blocks a K split aims at;
@@ -274,6 +279,14 @@ int vp_conv_fwd(const vp_conv_desc* d, const void* x, const float* in_scale, con
                 const float* w, const float* bias, void* y, void* workspace, void* stream);
 /* dx = d/d(in_act(...) input)  (i.e. w.r.t. the activated tensor the conv reads), [n,h,w,cin] in `dtype` */
 int vp_conv_bwd_data(const vp_conv_desc* d, const void* dy, const float* w, void* dx, void* workspace, void* stream);
+/* Backward-data of a 3x3 / stride-1 / pad-1 bf16 convolution with cin == cout in {64, 128} (h % 4 == 0, w % 16 == 0, h >= 16: conv_c64.hip) whose
+ * output went through a 2x2 max pool - VGG conv1_2 / conv2_2 in the perceptual backward pass: dx [n,h,w,cin] = conv_bwd_data(unpool(dy_pool,
+ * code)) * relu'(ref), with dy_pool [n,h/2,w/2,cout] the pool's gradient, code [n,h/2,w/2,cout] uint8 as for vp_maxpool2x2_bwd_code and ref
+ * [n,h,w,cin] the stored relu output of the producer.  fused = 0: the unpooled gradient is written to the workspace (vp_maxpool2x2_bwd_code's
+ * kernel) and read back by the convolution; fused = 1: the convolution's loader builds it in LDS from dy_pool and code.  Bit-identical. */
+size_t vp_conv3x3_c64_bwd_data_pooled_workspace_bytes(const vp_conv_desc* d);
+int vp_conv3x3_c64_bwd_data_pooled(const vp_conv_desc* d, const void* dy_pool, const unsigned char* code, const float* w, const void* ref,
+                                   void* dx, void* workspace, int fused, void* stream);
 /* dw in the TF layout of `kind`, f32 */
 int vp_conv_bwd_weight(const vp_conv_desc* d, const void* x, const float* in_scale, const float* in_shift,
                        const void* dy, float* dw, void* workspace, void* stream);

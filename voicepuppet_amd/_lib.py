@@ -143,6 +143,8 @@ _SIGNATURES = {
     "vp_conv_fwd": (ctypes.c_int, [ctypes.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P, _P, _P]),
     "vp_conv_bwd_data": (ctypes.c_int, [ctypes.POINTER(ConvDesc), _P, _P, _P, _P, _P]),
     "vp_conv_bwd_weight": (ctypes.c_int, [ctypes.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P, _P]),
+    "vp_conv3x3_c64_bwd_data_pooled_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(ConvDesc)]),
+    "vp_conv3x3_c64_bwd_data_pooled": (ctypes.c_int, [ctypes.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P, ctypes.c_int, _P]),
     "vp_bn_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "vp_bn_stats": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P, ctypes.c_float, _P, _P, _P, _P, _P, _P]),
     "vp_logmel_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(LogMelDesc)]),

@@ -115,6 +115,10 @@ struct IgemmArgs {
   // backward pass needs of the full-resolution tensor (maxpool_bwd_code_kernel).  0: the window maximum is <= 0 (no gradient);
   // 1 + k: k is the FIRST arg-max of the window in the order (0,0), (0,1), (1,0), (1,1) of the values as stored (rounded to bf16)
   unsigned char* pool_code;
+  // conv_c64 backward-data below a 2x2 max pool (ref set, Cin == Cout): x is the POOLED gradient [N][Hin/2][Win/2][Cin] and pool_code (read,
+  // not written) the pool's codes; the kernel's loader expands them to the full-resolution gradient in LDS (conv_c64_kernel PSRC) - the
+  // bits maxpool_bwd_code_kernel would write, without the tensor in HBM
+  int pool_src;
   // few-pixel kernel (conv_smallp.hip; kern == CK_SMALLP, plan-time decision: packed rows unpermuted): 32 channels x sp_npt * 16 pixels per tile,
   // splitk = K splits over blocks, partial = their slabs [split][tile][pixels][32]
   unsigned* sp_cnt;         // [tiles + channel tiles] arrival counters: zero before the launch, left zero by it

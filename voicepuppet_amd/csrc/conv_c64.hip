@@ -79,6 +79,16 @@ __device__ __forceinline__ unsigned pk_gt_relu(unsigned x, unsigned y) {
   asm("v_pk_lshrrev_b16 %0, %1, %2" : "=v"(r) : "v"(0x000F000Fu), "v"(pk_sub_u16(x, y)));
   return r;
 }
+__device__ __forceinline__ unsigned pk_ashr15_i16(unsigned x) {   // per 16-bit half: 0xffff where the half is negative, else 0
+  unsigned r;
+  asm("v_pk_ashrrev_i16 %0, %1, %2" : "=v"(r) : "v"(0x000F000Fu), "v"(x));
+  return r;
+}
+// LDS store as inline asm, like the fragment reads of patch_device.h (hipcc drains vmcnt in front of an LDS access it can see while an
+// LDS-DMA is pending); counted in lgkmcnt by the caller.  (s_nop: the data registers are free for the next instruction)
+__device__ __forceinline__ void lds_wr128(int addr, u32x4 v) {
+  asm volatile("ds_write_b128 %0, %1\n\ts_nop 1" ::"v"(addr), "v"(v) : "memory");
+}
 __device__ __forceinline__ unsigned dpp_xor1(unsigned v) {       // value of lane ^ 1: quad_perm [1, 0, 3, 2]
   return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, true);
 }
@@ -92,10 +102,17 @@ __device__ __forceinline__ unsigned dpp_xor1(unsigned v) {       // value of lan
 //   NCH 4, TPW 1: 128 -> 128 (NW 8: conv2_2 both passes) and 128 -> 64 (NW 4: conv2_1 backward-data) - a fragment read then feeds half
 //   the MFMAs, still 72 reads for 144 MFMAs per wave and tile
 // NW: waves of a block; the block's output channels are 16 TPW NW
-template <int NCH, int TPW, int NW, bool REF, bool RELU, bool POOL, bool STORE, bool CODE = false>
+// PSRC (with REF, IgemmArgs::pool_src): the input is the gradient of a 2x2 max pool that has not been expanded: x is the POOLED gradient
+//   [N][Hin/2][Win/2][CIN] and IgemmArgs::pool_code the pool's arg-max codes.  The block fetches the (2 + 2) x (8 + 2) pooled pixels that
+//   cover the patch and their code bytes into an LDS staging area (double-buffered: the next tile's are in flight under this tile's MFMAs)
+//   and builds the patch itself - element (y, x, c) = the pooled gradient's bits where the code of pooled pixel (y >> 1, x >> 1) is
+//   1 + 2 (y & 1) + (x & 1), else 0: what maxpool_bwd_code_kernel would have written to HBM for this launch to read back.  ONE patch
+//   buffer (the two staging buffers take the place of the second), one more barrier per tile; from there on the kernel is the same
+template <int NCH, int TPW, int NW, bool REF, bool RELU, bool POOL, bool STORE, bool CODE = false, bool PSRC = false>
 __global__ __launch_bounds__(NW * 64, 2) void conv_c64_kernel(const IgemmArgs a, const int ntiles) {
   static_assert(!POOL || (RELU && !REF), "the packed max pool compares relu outputs");
   static_assert(!CODE || (POOL && !STORE), "pool codes stand in for the full-resolution store");
+  static_assert(!PSRC || (REF && NW % NCH == 0 && PH % (NW / NCH) == 0), "pooled source: backward-data, whole waves per channel chunk");
   static_assert((NCH == 2 && TPW == 2) || (NCH == 4 && TPW == 1), "36 NCH TPW <= 144 weight registers");
   constexpr int JP = PPAD / (16 * NW);          // patch DMA instructions per wave and chunk
   constexpr int CW = 16 * TPW;                  // output channels of a wave
@@ -104,6 +121,14 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_c64_kernel(const IgemmArgs a,
   constexpr int BUFB = NCH * PBUFB;             // one patch buffer; two per block
   constexpr int KS = 9 * NCH;                   // (patch position, chunk) steps of the K loop
   static_assert(PPAD % (16 * NW) == 0, "whole DMA rounds per wave");
+  // PSRC staging buffer: per channel chunk NQ pooled pixels x 64 bytes of gradient, then per chunk NQ x 32 code bytes; chunk-major so
+  // that neighbouring pooled pixels are 64 / 32 bytes apart (the expansion's ds_read_b128 / b64 of 16 patch pixels: distinct banks)
+  constexpr int QH = TH / 2 + 2, QW = TW / 2 + 2, NQ = QH * QW;
+  constexpr int SGB = NQ * 64, SCB = NQ * 32, SCODE = NCH * SGB;
+  constexpr int NSG = NCH * NQ * 4 / 64;                                    // DMA instructions (1 KB) of the gradient, the codes follow
+  constexpr int JS = ((NCH * (SGB + SCB) + 1023) / 1024 + NW - 1) / NW;     // staging DMA instructions per wave
+  constexpr int STGB = JS * NW * 1024;                                      // one staging buffer; two behind the patch buffer
+  static_assert(!PSRC || (2 * STGB <= BUFB && NCH * NQ * 4 % 64 == 0), "the staging buffers take the second patch buffer's place");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -160,7 +185,26 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_c64_kernel(const IgemmArgs a,
     prel[j] = pp < NPATCH ? (ppy[j] * a.Win + ppx[j]) * (CIN * 2) + (((lane & 3) ^ ((ppx[j] >> 1) & 3)) * 8) * (int)sizeof(bf16) : 0;
   }
 
-  __amdgpu_buffer_rsrc_t rsX = make_rsrc(a.x.ptr[0], (unsigned)((size_t)a.N * a.Hin * a.Win * CIN * sizeof(bf16)));
+  // PSRC staging DMA lanes: instruction j of this wave covers staging units (16 bytes) (wave + NW j) * 64 .. + 63, lane -> (pooled pixel
+  // of the 4 x 10 window, chunk, piece); instructions below NSG fetch gradient, the others codes (a wave-uniform choice)
+  const int Hq = a.Hin >> 1, Wq = a.Win >> 1;
+  int sqy[JS], sqx[JS], srel[JS];
+  if constexpr (PSRC) {
+#pragma unroll
+    for (int j = 0; j < JS; ++j) {
+      const bool g = wave + NW * j < NSG;
+      const int v = (wave + NW * j - (g ? 0 : NSG)) * 64 + lane;
+      const int upc = g ? NQ * 4 : NQ * 2;                 // units per chunk
+      const int c = v / upc, q = (v % upc) >> (g ? 2 : 1), piece = v & (g ? 3 : 1);
+      sqy[j] = c < NCH ? q / QW : 1 << 20;                 // (units beyond the codes: never inside the image)
+      sqx[j] = q % QW;
+      srel[j] = c < NCH ? ((q / QW) * Wq + sqx[j]) * (g ? CIN * 2 : CIN) + c * (g ? 64 : 32) + piece * 16 : 0;
+    }
+  }
+
+  __amdgpu_buffer_rsrc_t rsX = make_rsrc(a.x.ptr[0], PSRC ? (unsigned)((size_t)a.N * Hq * Wq * CIN * sizeof(bf16))
+                                                          : (unsigned)((size_t)a.N * a.Hin * a.Win * CIN * sizeof(bf16)));
+  __amdgpu_buffer_rsrc_t rsC = make_rsrc(PSRC ? (const void*)a.pool_code : a.x.ptr[0], (unsigned)((size_t)a.N * Hq * Wq * CIN));
   const int tiles_x = a.Wg / TW, tpi = tiles_x * (a.Hg / TH);
   const bf16* refp = reinterpret_cast<const bf16*>(a.ref);
   bf16* Yp = reinterpret_cast<bf16*>(a.Y);
@@ -191,7 +235,47 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_c64_kernel(const IgemmArgs a,
     }
   };
 
-  if (bt < ntiles) issue_patch(bt, 0);
+  // PSRC: the pooled pixels (gradient + codes) under the patch of tile t into staging buffer `sb`: JS LDS-DMAs per wave
+  auto issue_stage = [&](int t, int sb) {
+    const int n = t / tpi, rem = t - n * tpi;
+    const int qy0 = (rem / tiles_x) * (TH / 2) - 1, qx0 = (rem % tiles_x) * (TW / 2) - 1;
+    const int pix0 = (n * Hq + qy0) * Wq + qx0;
+#pragma unroll
+    for (int j = 0; j < JS; ++j) {
+      const bool g = wave + NW * j < NSG;
+      const bool ok = (unsigned)(qy0 + sqy[j]) < (unsigned)Hq && (unsigned)(qx0 + sqx[j]) < (unsigned)Wq;
+      const unsigned vo = ok ? (unsigned)(pix0 * (g ? CIN * 2 : CIN) + srel[j]) : DMA_OOB;
+      uint4* l0 = reinterpret_cast<uint4*>(smem + BUFB + sb * STGB) + (wave + NW * j) * 64;
+      if (g) dma16_buf(rsX, vo, 0u, l0);
+      else dma16_buf(rsC, vo, 0u, l0);
+    }
+  };
+  // PSRC expansion lanes.  A wave expands patch rows [er0, er0 + RPW) of channel chunk ec, 16 columns x 4 pieces per instruction, and
+  // then the two right-hand columns of all rows (lane -> row, column 16 / 17, piece; with two waves per chunk both write them)
+  constexpr int WPC = PSRC ? NW / NCH : 1, RPW = PH / WPC;
+  int ex_src = 0, ex_cod = 0, ex_dst = 0, ex_k = 0, ee_src = 0, ee_cod = 0, ee_dst = 0, ee_k = 0;
+  const int ec = wave / WPC, er0 = (wave % WPC) * RPW;
+  if constexpr (PSRC) {
+    const int p = lane & 3;
+    {
+      const int px = lane >> 2, qx = (px + 1) >> 1;
+      ex_src = BUFB + ec * SGB + (qx * 4 + p) * 16;
+      ex_cod = BUFB + SCODE + ec * SCB + qx * 32 + p * 8;
+      ex_dst = ec * PBUFB + (px << 6) + (((p ^ (px >> 1)) & 3) << 4);
+      ex_k = (1 + ((px + 1) & 1)) * 0x00010001;
+    }
+    {
+      const int e = lane >> 2, py = (e >> 1) < PH ? (e >> 1) : PH - 1, px = TW + (e & 1);
+      const int q = ((py + 1) >> 1) * QW + ((px + 1) >> 1);
+      ee_src = BUFB + ec * SGB + (q * 4 + p) * 16;
+      ee_cod = BUFB + SCODE + ec * SCB + q * 32 + p * 8;
+      ee_dst = ec * PBUFB + ((py * PW + px) << 6) + (((p ^ (px >> 1)) & 3) << 4);
+      ee_k = (1 + 2 * ((py + 1) & 1) + ((px + 1) & 1)) * 0x00010001;
+    }
+  }
+
+  if constexpr (PSRC) { if (bt < ntiles) issue_stage(bt, 0); }
+  else { if (bt < ntiles) issue_patch(bt, 0); }
   int it = 0;
   for (int t = bt; t < ntiles; t += G, ++it) {
     const int buf = it & 1;
@@ -220,10 +304,46 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_c64_kernel(const IgemmArgs a,
         }
       }
     }
-    if (t + G < ntiles && (!(C64_ABL & 1) || it < 1)) issue_patch(t + G, buf ^ 1);
+    if constexpr (PSRC) {
+      if (t + G < ntiles && (!(C64_ABL & 1) || it < 1)) issue_stage(t + G, buf ^ 1);
+      // ---- the patch from staging buffer `buf` (landed: the wait and the barrier above): per instruction 16 bytes of gradient and their
+      // 8 code bytes per lane, the codes widened to 16 bits and compared in packed arithmetic (code ^ wanted is 0 exactly for the pooled
+      // element's arg-max position; minus one, sign-filled: the mask), one 16-byte store into the patch's slot.  Reads one step ahead ----
+      const int sb = buf * STGB;
+      u32x4 eg[2];
+      u32x2 ew[2];
+      auto erd = [&](auto jc) {
+        constexpr int j = decltype(jc)::value;
+        const int qo = j < RPW ? ((er0 + j + 1) >> 1) * QW : 0;
+        eg[j & 1] = lds_rd128<0>((j < RPW ? ex_src + qo * 64 : ee_src) + sb);
+        ew[j & 1] = lds_rd64<0>((j < RPW ? ex_cod + qo * 32 : ee_cod) + sb);
+      };
+      erd(std::integral_constant<int, 0>{});
+      static_steps([&](auto jc) {
+        constexpr int j = decltype(jc)::value;
+        if constexpr (j < RPW) erd(std::integral_constant<int, j + 1>{});
+        // behind this step's two reads: the previous step's store and the next step's reads
+        asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"((j > 0 ? 1 : 0) + (j < RPW ? 2 : 0)) : "memory");
+        asm volatile("" : "+v"(eg[j & 1]), "+v"(ew[j & 1]));
+        const unsigned k = j < RPW ? (unsigned)ex_k + (unsigned)((er0 + j + 1) & 1) * 0x00020002u : (unsigned)ee_k;
+        u32x4 o;
+#pragma unroll
+        for (int d = 0; d < 4; ++d) {
+          const unsigned cw = d < 2 ? ew[j & 1].x : ew[j & 1].y;
+          const unsigned c16 = __builtin_amdgcn_perm(0u, cw, (d & 1) ? 0x0c030c02u : 0x0c010c00u);
+          o[d] = eg[j & 1][d] & pk_ashr15_i16(pk_sub_u16(c16 ^ k, 0x00010001u));
+        }
+        lds_wr128(j < RPW ? ex_dst + (er0 + j) * (PW * 64) : ee_dst, o);
+      }, std::make_integer_sequence<int, RPW + 1>{});
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+      asm volatile("" ::: "memory");
+    } else {
+      if (t + G < ntiles && (!(C64_ABL & 1) || it < 1)) issue_patch(t + G, buf ^ 1);
+    }
     int tb[3];
 #pragma unroll
-    for (int pc = 0; pc < 3; ++pc) tb[pc] = tb0[pc] + buf * BUFB;
+    for (int pc = 0; pc < 3; ++pc) tb[pc] = tb0[pc] + (PSRC ? 0 : buf * BUFB);
 
     // ---- the MFMAs of the tile: 36 fragment steps.  Step (cc, pc, R) reads ONE B fragment - patch row R, column shift pc, chunk cc - and
     // feeds it to every tile row r it belongs to (patch position pr = R - r in 0..2): 2 .. 6 MFMAs per read, 144 per tile and wave,
@@ -351,7 +471,8 @@ bool conv_c64_eligible(const IgemmArgs& a, int is_bf16) {
   if ((a.out_act != ACT_NONE && a.out_act != ACT_RELU) || (a.ref && (a.ref_act != ACT_RELU || a.out_act != ACT_NONE || a.pool_out))) return false;
   if (a.pool_out && (a.out_act != ACT_RELU || (a.Hg & 1))) return false;
   if (a.pool_only && !a.pool_out) return false;
-  if (a.pool_code && !a.pool_only) return false;
+  if (a.pool_code && !a.pool_only && !a.pool_src) return false;
+  if (a.pool_src && (!a.ref || !a.pool_code || a.Cin != a.Cout)) return false;      // pooled source: conv1_2 / conv2_2 backward-data
   if (a.bn_part || a.accumulate || a.y_f32 || a.ref_a || a.split_c || a.x.aff_a[0] || a.x.act != ACT_NONE) return false;
   if (a.p_dhs != a.p_dws || a.p_dhf != a.p_dwf || a.p_dhf != (a.p_dhs > 0 ? -1 : 1)) return false;          // pad 1
   return (size_t)a.N * a.Hin * a.Win * a.Cin * 2 < 0x70000000ull;
@@ -361,11 +482,15 @@ template <int NCH, int TPW, int NW>
 static hipError_t launch_c64_t(const IgemmArgs& a, hipStream_t st) {
   const int ntiles = a.N * (a.Hg / TH) * (a.Wg / TW);
   void (*kern)(const IgemmArgs, const int);
-  if (a.ref) kern = conv_c64_kernel<NCH, TPW, NW, true, false, false, true>;
+  if (a.ref && a.pool_src) {
+    if constexpr (16 * TPW * NW == 32 * NCH) kern = conv_c64_kernel<NCH, TPW, NW, true, false, false, true, false, true>;
+    else return hipErrorInvalidValue;
+  } else if (a.ref) kern = conv_c64_kernel<NCH, TPW, NW, true, false, false, true>;
   else if (a.pool_out && a.pool_code) kern = conv_c64_kernel<NCH, TPW, NW, false, true, true, false, true>;
   else if (a.pool_out) kern = a.pool_only ? conv_c64_kernel<NCH, TPW, NW, false, true, true, false> : conv_c64_kernel<NCH, TPW, NW, false, true, true, true>;
   else kern = a.out_act == ACT_RELU ? conv_c64_kernel<NCH, TPW, NW, false, true, false, true> : conv_c64_kernel<NCH, TPW, NW, false, false, false, true>;
-  // LDS: two patch buffers + the output staging tile; blocks per CU: 8 / NW (two waves per SIMD) - all of them fit (40 .. 80 KB each)
+  // LDS: two patch buffers (pooled source: one + two staging buffers of half its size) + the output staging tile; blocks per CU: 8 / NW
+  // (two waves per SIMD) - all of them fit (40 .. 80 KB each)
   const int smem = 2 * NCH * PBUFB + TH * 16 * (16 * TPW * NW * 2);
   const int blocks = 256 * (8 / NW);
   (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem);

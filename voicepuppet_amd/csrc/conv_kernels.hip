@@ -1849,6 +1849,7 @@ bool conv_cout4_eligible(const IgemmArgs& a, int is_bf16) {
 }
 
 bool conv_kernel_ok(const IgemmArgs& a, int is_bf16) {
+  if (a.pool_src && a.kern != CK_C64) return false;      // only conv_c64_kernel has the pooled-source loader
   switch (a.kern) {
     case CK_IGEMM: case CK_PATCH: case CK_PATCH2: case CK_SMALLP: return true;
     case CK_S2C64: return conv_s2c64_eligible(a, is_bf16);
@@ -1888,7 +1889,9 @@ template <typename T> static hipError_t launch_igemm_t(const IgemmArgs& a, int c
   const double kreal = (double)a.ntaps * a.cin_real;
   const double es = sizeof(T);
   const double flops = 2.0 * Pn * a.Cout * kreal;
-  const double bytes = es * ((double)a.N * a.Hin * a.Win * a.cin_real + kreal * a.nclass * a.Cout + Pn * a.Cout);
+  // (IgemmArgs::pool_src: a quarter of the input pixels, each with one code byte per channel)
+  const double xbytes = a.pool_src ? (es + 1) * ((double)a.N * (a.Hin / 2) * (a.Win / 2) * a.cin_real) : es * ((double)a.N * a.Hin * a.Win * a.cin_real);
+  const double bytes = xbytes + es * (kreal * a.nclass * a.Cout + Pn * a.Cout);
   switch (a.kern) {
     case CK_IGEMM: break;
     case CK_PATCH: case CK_PATCH2: case CK_PATCH3: {   // stride-1 convs with the input patch staged once per channel chunk

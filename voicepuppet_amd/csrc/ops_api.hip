@@ -67,6 +67,7 @@ int vp_tune(const char* key, int value) {
   if (k == "patch3") { patch3_knob() = value; return VP_OK; }
   if (k == "c64") { c64_knob() = value; return VP_OK; }
   if (k == "dc64") { dc64_knob() = value; return VP_OK; }
+  if (k == "pool_bwd_fused") { pool_bwd_fused_knob() = value < 0 || value > 4 ? 1 : value; return VP_OK; }
   if (k == "cout1_wgrad_rows" && value > 0) { wgrad1_rows_knob() = value; return VP_OK; }
   if (k == "cout1_bwd") { cout1_knob() = value < 0 ? 256 : value; return VP_OK; }
   if (k == "s2c64") { s2c64_knob() = value; return VP_OK; }
@@ -177,6 +178,55 @@ int vp_conv_bwd_data(const vp_conv_desc* d, const void* dy, const float* w, void
   a.zeros = zero_page(ws, align256(p.pack_elems * es) + p.partial_bytes, st);
   if (a.kern == CK_SMALLP) a.sp_cnt = smallp_counter_page(ws, align256(p.pack_elems * es) + p.partial_bytes, a, st);
   VP_HIP_CHECK(launch_igemm(a, bf, p.cfg, st));
+  return VP_OK;
+}
+
+// Backward-data of a 3x3 / stride-1 / pad-1 convolution (64 -> 64 or 128 -> 128 channels, bf16) whose OUTPUT went through a 2x2 max pool,
+// from the pool's gradient dy_pool [n][h/2][w/2][c] and its arg-max codes (IgemmArgs::pool_code layout), times relu'(ref): what the VGG
+// backward pass of a step runs below pool1 / pool2.  fused = 0: maxpool_bwd_code_kernel expands the gradient into the workspace and
+// conv_c64_kernel reads it back; fused = 1: the kernel's pooled-source loader expands it in LDS (IgemmArgs::pool_src).  Same kernel
+// family, same arithmetic: the two results are bit-identical.  No other kernel is substituted: a shape outside conv_c64 is an error.
+static bool pooled_desc_ok(const vp_conv_desc* d) {
+  return conv_desc_ok(d) && d->kind == 0 && d->ksize == 3 && d->stride == 1 && d->pad == 1 && d->dtype == VP_BF16 && d->cin == d->cout &&
+         (d->cin == 64 || d->cin == 128) && d->h % 4 == 0 && d->w % 16 == 0 && d->h >= 16;      // (the patch plans start at 16 x 16 pixels)
+}
+
+size_t vp_conv3x3_c64_bwd_data_pooled_workspace_bytes(const vp_conv_desc* d) {
+  if (!pooled_desc_ok(d)) return 0;
+  return align256(vp_conv_workspace_bytes(d)) + align256((size_t)d->n * d->h * d->w * d->cout * 2) + 256;
+}
+
+int vp_conv3x3_c64_bwd_data_pooled(const vp_conv_desc* d, const void* dy_pool, const unsigned char* code, const float* w, const void* ref,
+                                   void* dx, void* workspace, int fused, void* stream) {
+  if (!pooled_desc_ok(d) || !dy_pool || !code || !w || !ref || !dx || !workspace) { set_err("vp_conv3x3_c64_bwd_data_pooled: bad argument"); return VP_ERR_ARG; }
+  hipStream_t st = (hipStream_t)stream;
+  const ConvGeomX g = geom_of(d);
+  IgemmPlan p = plan_bwd_data(g, 0, 0, d->cin, d->cin, d->cin, 1);
+  LaunchForm f;
+  f.ref = true; f.ref_act = ACT_RELU;
+  plan_kernel(p, d->cin, 1, d->cout, 0, FAM_PATCH, f);
+  if (p.a.kern != CK_C64) {
+    set_err("vp_conv3x3_c64_bwd_data_pooled: %d x %d x %d x %d is planned on kernel %s, not c64", d->n, d->h, d->w, d->cin, conv_kernel_name(p.a.kern));
+    return VP_ERR_ARG;
+  }
+  char* ws = (char*)workspace;
+  VP_HIP_CHECK(launch_pack_weights_one(p.pack, w, ws, 1, st));
+  IgemmArgs a = p.a;
+  a.Wp = ws;
+  a.partial = (float*)(ws + align256(p.pack_elems * 2));
+  a.Y = dx;
+  a.ref = ref; a.ref_act = ACT_RELU;
+  a.zeros = zero_page(ws, align256(p.pack_elems * 2) + p.partial_bytes, st);
+  if (fused) {
+    set_single_src(a.x, dy_pool, d->cout, nullptr, nullptr, ACT_NONE, 0);
+    a.pool_code = const_cast<unsigned char*>(code);
+    a.pool_src = 1;
+  } else {
+    char* full = ws + align256(vp_conv_workspace_bytes(d));
+    VP_HIP_CHECK(launch_maxpool_bwd_code(code, dy_pool, full, d->n, d->h, d->w, d->cout, 1, st));
+    set_single_src(a.x, full, d->cout, nullptr, nullptr, ACT_NONE, 0);
+  }
+  VP_HIP_CHECK(launch_igemm(a, 1, p.cfg, st));
   return VP_OK;
 }
 

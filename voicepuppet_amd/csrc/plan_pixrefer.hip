@@ -154,6 +154,12 @@ struct vp_pixrefer {
   // backward pass reads instead of the full-resolution output, which is then not stored
   unsigned char* vpool_code[2];
   bool pool_codes_written;    // the last forward pass took that path: the backward pass follows THIS, not the options (vp_pixrefer_set_option may come in between)
+  // vp_tune("pool_bwd_fused") when the plan was made, per pool (conv1_2 / conv2_2): the backward-data launch of the conv below the pool is
+  // planned on conv_c64 and takes the pooled gradient + codes itself (IgemmArgs::pool_src) - no maxpool_bwd_code launch, the conv's
+  // full-resolution gradient is not written.  Taken only when the forward pass wrote codes
+  bool pool_fuse_ok[2];
+  bool pool_bwd_fused;        // the last backward pass took that path (vp_pixrefer_counter("pool_bwd_fused"))
+  bool pool_dz_stale[2];      // ... and the conv's :dy tensor has not been materialised since (vp_pixrefer_tensor does it on demand)
   double *comp_partial, *perc_partial, *bn_partial;
   char* scratch;
   char* scratch2;             // split-K / slab scratch and batch-norm partials of the side stream (backward_d when overlapped)
@@ -611,6 +617,15 @@ static size_t carve_all(vp_pixrefer* h, char* base, size_t cap, std::vector<std:
   return ar.off + 256;
 }
 
+// the backward-data launch of a VGG conv below a pool in its pooled-source form (see vp_pixrefer::pool_fuse_ok), as launch_view shows it
+static IgemmArgs pool_fused_view(const IgemmPlan& p) {
+  static unsigned char set[16] = {};
+  IgemmArgs v = launch_view(p, p.form);
+  v.pool_code = set;
+  v.pool_src = 1;
+  return v;
+}
+
 static void init_handle(vp_pixrefer* h, const vp_pixrefer_desc* d) {
   h->d = *d;
   h->bf16 = d->dtype == VP_BF16;
@@ -625,6 +640,16 @@ static void init_handle(vp_pixrefer* h, const vp_pixrefer_desc* d) {
     // VGG backward (dX only) is planned for the fake half: batch N
     for (Layer& L : h->V.l) L.g.N = 2 * d->batch;
     plan_net(h->V, h->bf16, true, false, d->batch, &smax, true);
+    for (const Layer& L : h->V.l) {
+      if (L.scope != "conv1/conv1_2" && L.scope != "conv2/conv2_2") continue;
+      // knob 1: pool1 always; pool2 from 4096 tiles of the conv2_2 launch (16 frames at 256 x 256) - below that its pooled-source form
+      // measured +0.01 .. 0.02 ms on the 8-frame step against pool1 alone, from 16 frames up it gains (EXPERIMENTS.md 0.Q).  2 / 3: pool1 /
+      // pool2 only, 4: both at every size (experiments and tests)
+      const int k = L.scope == "conv2/conv2_2", knob = pool_bwd_fused_knob();
+      const IgemmArgs& ba = L.bwd_alt[0].a;
+      const bool big = !k || (long long)ba.N * (ba.Hg / 4) * (ba.Wg / 16) >= 4096;
+      h->pool_fuse_ok[k] = ((knob == 1 && big) || knob == 2 + k || knob == 4) && h->bf16 && conv_kernel_ok(pool_fused_view(L.bwd_alt[0]), h->bf16);
+    }
   }
   h->scratch_bytes = smax + 256;
   h->params_dirty = true;
@@ -1305,6 +1330,17 @@ int vp_pixrefer_validate_plan(const vp_pixrefer_desc* d) {
       if (t.name == "pool1") region_of(h->vpool_code[0], t.elems() / 2, "pool1 codes");
       if (t.name == "pool2") region_of(h->vpool_code[1], t.elems() / 2, "pool2 codes");
     }
+    // the pooled-source backward-data launches: the plan's kernel takes that form, and what its loader reads instead of the conv's own
+    // gradient - the fake half of the pool's gradient and one code byte per element of it - is carved
+    for (const Layer& L : h->V.l) {
+      const int k = L.scope == "conv2/conv2_2";
+      if ((L.scope != "conv1/conv1_2" && !k) || !h->pool_fuse_ok[k]) continue;
+      const Tens& tp = h->V.t[L.out + 1];
+      if (tp.name != (k ? "pool2" : "pool1") || tp.H * 2 != h->V.t[L.out].H || tp.C != h->V.t[L.out].C) fail("%s: the tensor behind it is not its 2x2 pool", L.scope.c_str());
+      if (L.bwd_alt[0].a.kern != CK_C64 || !conv_kernel_ok(pool_fused_view(L.bwd_alt[0]), h->bf16)) fail("%s bwd_alt: no pooled-source form of kernel %s", L.scope.c_str(), conv_kernel_name(L.bwd_alt[0].a.kern));
+      region_of(tp.dz, tp.elems() / 2 * es, (tp.name + ".dz (pooled-source read)").c_str());
+      region_of(h->vpool_code[k], tp.elems() / 2, (tp.name + " codes (pooled-source read)").c_str());
+    }
     region_of(h->scratch2, h->scratch_bytes, "scratch2"); region_of(h->scratch3, h->scratch_bytes, "scratch3");
     region_of(h->scratch4, h->scratch_bytes, "scratch4"); region_of(h->bn_partial4, (size_t)1024 * 2 * 512 * 8, "bn_partial4");
     region_of(h->bn_partial2, (size_t)1024 * 2 * 512 * 8, "bn_partial2"); region_of(h->bn_partial3, (size_t)1024 * 2 * 512 * 8, "bn_partial3");
@@ -1779,6 +1815,7 @@ long long vp_pixrefer_counter(vp_pixrefer_t* h, const char* key) {
   if (!h || !key) return -1;
   if (std::string(key) == "bwd_sums_launches") return h->bst_count;
   if (std::string(key) == "pool_codes_written") return h->pool_codes_written ? 1 : 0;
+  if (std::string(key) == "pool_bwd_fused") return h->pool_bwd_fused ? 1 : 0;
   return -1;
 }
 
@@ -1863,6 +1900,8 @@ int vp_pixrefer_backward_g_stage(vp_pixrefer_t* h, int stage, void* stream) {
   if (h->dfork_pending == 1 && (rc = fork_d(h, st))) return rc;
   // (b) perceptual term through the VGG trunk, fake half only (dX only: VGG is frozen)
   for (Tens& t : V.t) t.dz_written = false;
+  h->pool_bwd_fused = false;
+  h->pool_dz_stale[0] = h->pool_dz_stale[1] = false;
   for (int i = (int)V.l.size() - 1; i >= 0; --i) {
     Layer& L = V.l[i];
     Tens& to = V.t[L.out];
@@ -1870,6 +1909,13 @@ int vp_pixrefer_backward_g_stage(vp_pixrefer_t* h, int stage, void* stream) {
     // dz of a conv output here is already w.r.t. the pre-relu value (perceptual seed / epilogue / pool bwd)
     IgemmArgs a = L.bwd_alt[0].a;
     set_single_src(a.x, to.dz, L.g.CoutT, nullptr, nullptr, ACT_NONE, 0);
+    const int pk = L.scope == "conv2/conv2_2";
+    if ((pk || L.scope == "conv1/conv1_2") && h->pool_dz_stale[pk]) {
+      // the pool behind this conv left its gradient unexpanded (below): the launch reads the pooled gradient and the codes
+      a.x.ptr[0] = V.t[L.out + 1].dz;
+      a.pool_code = h->vpool_code[pk];
+      a.pool_src = 1;
+    }
     a.Wp = V.packed + L.pk_bwd_alt[0] * es;
     a.partial = (float*)h->scratch;
     const bool from_pool = (ti.name == "pool1" || ti.name == "pool2");
@@ -1890,7 +1936,12 @@ int vp_pixrefer_backward_g_stage(vp_pixrefer_t* h, int stage, void* stream) {
       const int ci = L.src[0] - 1;
       Tens& tc = V.t[ci];
       const char* xin = (const char*)tc.y + tc.elems() / 2 * es;
-      if (h->pool_codes_written) VP_HIP_CHECK(launch_maxpool_bwd_code(h->vpool_code[ti.name == "pool2"], ti.dz, tc.dz, N, tc.H, tc.W, tc.C, bf, st));
+      const int k = ti.name == "pool2";
+      if (h->pool_codes_written && h->pool_fuse_ok[k]) {
+        // the conv below the pool expands the gradient in its loader (the next trip of this loop): nothing to launch, tc.dz stays unwritten
+        h->pool_dz_stale[k] = true;
+        h->pool_bwd_fused = true;
+      } else if (h->pool_codes_written) VP_HIP_CHECK(launch_maxpool_bwd_code(h->vpool_code[k], ti.dz, tc.dz, N, tc.H, tc.W, tc.C, bf, st));
       else VP_HIP_CHECK(launch_maxpool_bwd(xin, ti.dz, tc.dz, N, tc.H, tc.W, tc.C, bf, st));
     }
   }
@@ -2039,6 +2090,15 @@ int vp_pixrefer_tensor(vp_pixrefer_t* h, const char* name, void** ptr, int64_t s
     }
     if (field.empty()) return ret(t.y, t.N, t.H, t.W, t.is_f32 ? (t.name == "decoder_1" ? 4 : 1) : t.C, (t.is_f32 || t.hi) ? VP_F32 : cd);
     if (field == "dz32") return t.hi ? ret(t.dz32, t.N, t.H, t.W, t.C, VP_F32) : VP_ERR_ARG;
+    if (field == "dy" && n == &h->V && (t.name == "conv1/conv1_2" || t.name == "conv2/conv2_2") && h->pool_dz_stale[t.name == "conv2/conv2_2"]) {
+      // the last backward pass expanded this gradient inside the conv's loader only: write the tensor out now (tests / debugging)
+      const int k = t.name == "conv2/conv2_2";
+      const Tens& tp = n->t[(&t - n->t.data()) + 1];   // the pool tensor follows in creation order
+      VP_HIP_CHECK(hipDeviceSynchronize());
+      VP_HIP_CHECK(launch_maxpool_bwd_code(h->vpool_code[k], tp.dz, t.dz, t.N / 2, t.H, t.W, t.C, h->bf16, nullptr));
+      VP_HIP_CHECK(hipDeviceSynchronize());
+      h->pool_dz_stale[k] = false;
+    }
     if (field == "dy") return ret(t.dz, n == &h->V ? t.N / 2 : t.N, t.H, t.W, t.C, cd);
     if (!t.has_bn) return VP_ERR_ARG;
     if (field == "scale") return ret(t.bn.a, n->groups, t.C, 1, 1, VP_F32);
