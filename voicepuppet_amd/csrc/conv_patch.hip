@@ -23,35 +23,19 @@
 #include "igemm_device.h"
 #include "launch.h"
 #include "conv_ops.h"
+#include "patch_device.h"
 
 namespace vp {
 
-// output pixel of tile row `row` (pixel block row / 16, lane row % 16) -> offset into Y, -1 outside the image
-template <int TW>
-struct PatchTilePix {
-  const IgemmArgs& a; int n, y0, x0;
-  __device__ __forceinline__ long long operator()(int row) const {
-    constexpr int BPR = TW / 16;                         // 16-pixel blocks per tile row
-    const int pb = row >> 4, i = row & 15;
-    const int y = y0 + pb / BPR, x = x0 + (pb % BPR) * 16 + i;
-    if (y >= a.Hg || x >= a.Wg) return -1;
-    const long long off = (((long long)n * a.Hof + y) * a.Wof + x) * a.ldY;
-    return (off << 8) | (long long)(n / a.ref_group_n);
-  }
-  // 2x2 max pool of the tile: pooled pixel (row pr, column pc) of this tile -> element offset in the pooled image, -1 outside.
-  // Meaningful for 16-pixel-wide tiles (the staged epilogue walks 8 pooled pixels per pooled row) and even image sizes.
-  static constexpr bool HAS_POOL = (TW == 16);
-  __device__ __forceinline__ long long pool(int pr, int pc) const {
-    const int y = (y0 >> 1) + pr, x = (x0 >> 1) + pc;
-    if (y >= (a.Hg >> 1) || x >= (a.Wg >> 1)) return -1;
-    return (((long long)n * (a.Hg >> 1) + y) * (a.Wg >> 1) + x) * a.ldY;
-  }
-};
+// kw is a run-time value in this kernel: its patch buffers are sized for HALO = 3, the widest layer it serves (4x4); PW / PH of a
+// launch are TW / TH + kw - 1 <= the geometry's
+template <typename T, int WC, int WP, int TC, int TP, int TH, int TW, int NSTW>
+using GenericPatchGeom = PatchGeom<T, WC, WP, TC, TP, TH, TW, 3, NSTW>;
 
 // fragment reads behind __restrict__ parameters: keeps hipcc from draining vmcnt in front of LDS reads that may alias a pending
 // LDS-DMA (EXPERIMENTS.md, "double-buffered register fragments", has the story); the counted vmcnt + barrier of the loop is what orders them
 template <int TC, int TP>
-__device__ __forceinline__ void patch_frag_read(const uint4* __restrict__ pa, const char* __restrict__ pbuf, const int (&boff)[TP],
+__device__ __forceinline__ void patch_frag_read_restrict(const uint4* __restrict__ pa, const char* __restrict__ pbuf, const int (&boff)[TP],
                                                 uint4 (&fa)[TC], uint4 (&fb)[TP]) {
 #pragma unroll
   for (int t = 0; t < TP; ++t) {
@@ -65,30 +49,19 @@ __device__ __forceinline__ void patch_frag_read(const uint4* __restrict__ pa, co
 
 template <typename T, int WC, int WP, int TC, int TP, int TH, int TW, int NSTW, int STATS, int OCC>
 __global__ __launch_bounds__(WC * WP * 64, OCC) void igemm_patch_kernel(const IgemmArgs a) {
-  constexpr int E = Elem<T>::E, KC = 4 * E;
-  constexpr int NW = WC * WP, NT = NW * 64;
-  static_assert(NW == 8, "eight waves");
-  constexpr int BC = WC * TC * 16, BP = TH * TW;
-  static_assert(BP == WP * TP * 16, "pixel blocks of the tile = pixel blocks of the waves");
-  constexpr int NBA = BC / 16;
-  static_assert(NBA % NW == 0 || NBA == 4, "weight DMAs: whole instructions per wave (64-row tiles: half an instruction per wave)");
-  constexpr int JA = (NBA + NW - 1) / NW;
-  constexpr int PPAD = ((TH + 3) * (TW + 3) + 127) / 128 * 128;      // patch pixels, padded to whole DMA rounds of the 8 waves
-  constexpr int JP = PPAD / 128;                                     // patch DMA instructions per wave
-  constexpr int WST = 4 * BC;                                        // uint4 slots of one weight stage
-  constexpr int PBUF = 4 * PPAD;                                     // uint4 slots of one patch buffer
+  using G = GenericPatchGeom<T, WC, WP, TC, TP, TH, TW, NSTW>;
+  constexpr int E = G::E, KC = G::KC, NW = G::NW, JA = G::JA, JP = G::JP;
+  constexpr int WST = G::WSTB / 16;                                  // uint4 slots of one weight stage
+  constexpr int PBUF = G::PBUFB / 16;                                // uint4 slots of one patch buffer
   extern __shared__ __attribute__((aligned(16))) char smem[];
   uint4* lds = reinterpret_cast<uint4*>(smem);
-  uint4* lpatch = lds + NSTW * WST;
+  uint4* lpatch = lds + NSTW * WST;                                  // the ring first, the patches behind it
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int c_base = blockIdx.y * BC;
-  const int tiles_x = (a.Wg + TW - 1) / TW, tiles_y = (a.Hg + TH - 1) / TH;
-  const int bt = blockIdx.x;
-  const int n = bt / (tiles_x * tiles_y);
-  const int trem = bt - n * (tiles_x * tiles_y);
-  const int y0 = (trem / tiles_x) * TH, x0 = (trem % tiles_x) * TW;
+  const int c_base = blockIdx.y * G::BC;
+  const PatchTile tile = patch_tile_origin<TH, TW>(a);
+  const int n = tile.n, y0 = tile.y0, x0 = tile.x0;
   // tap t = r * kw + c  ->  (dh, dw) = (p_dhf + r * p_dhs, p_dwf + c * p_dws)
   const int kw = a.p_kw, kh = a.ntaps / kw;
   const int dh0 = a.p_dhs > 0 ? a.p_dhf : a.p_dhf - (kh - 1), dw0 = a.p_dws > 0 ? a.p_dwf : a.p_dwf - (kw - 1);
@@ -113,32 +86,12 @@ __global__ __launch_bounds__(WC * WP * 64, OCC) void igemm_patch_kernel(const Ig
     const int piece = (lane & 3) ^ ((pp >> 2) & 3);
     pvo[j] = ok ? (unsigned)((((n * a.Hin + ih) * a.Win + iw) * C0 + piece * E) * es) : DMA_OOB;
   }
-  // weight DMA lanes (rb_swz image, as in igemm_dma_kernel).  64-row tiles have four 16-row blocks for eight waves: every wave
-  // moves HALF a block (lanes 0-31: 8 rows), so that all waves keep issuing the same number of DMAs per step (the counted vmcnt
-  // below relies on it)
-  constexpr bool HALFW = NBA < NW;
-  unsigned wvo[JA];
-  {
-    const int r = HALFW ? (wave & 1) * 8 + (lane >> 2) : lane >> 2;       // row inside the 16-row block
-    const int g = (lane & 3) ^ rb_swz(r & 15);
-#pragma unroll
-    for (int j = 0; j < JA; ++j) {
-      const int blk = HALFW ? (wave >> 1) : wave + NW * j;
-      wvo[j] = (unsigned)(((c_base + blk * 16 + r) * KC + g * E) * es);
-    }
-  }
+  const PatchWeightDma<G> wdma(c_base, wave, lane);
   const unsigned wstep = (unsigned)(a.wp_rows * KC * es);
   // weight issue cursor: step (wc_c, wc_t) -> packed chunk index wc_t * nchunkc + wc_c (tap-major K)
   int wc_c = 0, wc_t = 0, wc_stage = 0;
   auto issue_w = [&]() {
-    const unsigned wso = (unsigned)(wc_t * nchunkc + wc_c) * wstep;
-    uint4* la = lds + wc_stage * WST;
-    if constexpr (HALFW) {
-      if (lane < 32) dma16_buf(rsW, wvo[0], wso, la + (wave >> 1) * 64 + (wave & 1) * 32);
-    } else {
-#pragma unroll
-      for (int j = 0; j < JA; ++j) dma16_buf(rsW, wvo[j], wso, la + (wave + NW * j) * 64);
-    }
+    wdma.issue(rsW, (unsigned)(wc_t * nchunkc + wc_c) * wstep, lds + wc_stage * WST);
     if (++wc_t == a.ntaps) { wc_t = 0; ++wc_c; }
     wc_stage = wc_stage == NSTW - 1 ? 0 : wc_stage + 1;
   };
@@ -193,7 +146,7 @@ __global__ __launch_bounds__(WC * WP * 64, OCC) void igemm_patch_kernel(const Ig
       boff[q] = (pp << 6) + (((fg ^ (pp >> 2)) & 3) << 4) + ((fg & 1) << 3);
     }
     uint4 fa[TC], fb[TP];
-    patch_frag_read<TC, TP>(lds + st * WST + blkA0 * 64 + so, reinterpret_cast<const char*>(lpatch + (c & 1) * PBUF), boff, fa, fb);
+    patch_frag_read_restrict<TC, TP>(lds + st * WST + blkA0 * 64 + so, reinterpret_cast<const char*>(lpatch + (c & 1) * PBUF), boff, fa, fb);
 #pragma unroll
     for (int tc = 0; tc < TC; ++tc)
 #pragma unroll
@@ -203,28 +156,15 @@ __global__ __launch_bounds__(WC * WP * 64, OCC) void igemm_patch_kernel(const Ig
     if (++t == a.ntaps) { t = 0; tr = 0; ++c; }
   }
 
-  constexpr int RINGB = (NSTW * WST + 2 * PBUF) * 16;
-  constexpr int NPASS = epi_passes(BC, BP, WP, RINGB);
-  staged_epilogue<T, TC, TP, BC, BP, NPASS, NT, STATS>(a, PatchTilePix<TW>{a, n, y0, x0}, c_base, blkA0, blkB0, acc, smem, bt, 0);
+  staged_epilogue<T, TC, TP, G::BC, G::BP, G::NPASS, G::NT, STATS>(a, PatchTilePix<TW>{a, n, y0, x0}, c_base, blkA0, blkB0, acc, smem, tile.bt, 0);
 }
 
 // OCC: waves per SIMD the register allocation must allow (2: one 8-wave block per CU, 4: two)
 template <typename T, int WC, int WP, int TC, int TP, int TH, int TW, int NSTW, int OCC>
 static hipError_t launch_patch_t(const IgemmArgs& b, hipStream_t st) {
-  constexpr int BC = WC * TC * 16, BP = TH * TW;
-  constexpr int PPAD = ((TH + 3) * (TW + 3) + 127) / 128 * 128;
-  constexpr int RINGB = (NSTW * 4 * BC + 2 * 4 * PPAD) * 16;
-  constexpr int NPE = epi_passes(BC, BP, WP, RINGB);
-  size_t sm = RINGB;
-  const size_t se = (size_t)(BP / NPE) * (BC * 4 + 16) + (BP / NPE) * 8;
-  if (se > sm) sm = se;
-  const int tiles = b.N * ((b.Hg + TH - 1) / TH) * ((b.Wg + TW - 1) / TW);
-  dim3 grid(tiles, b.CoutPad / BC, 1);
   if (b.bst_y || b.bst_y2) return hipErrorInvalidValue;      // (backward sums in the epilogue: the unrolled 4x4 kernel and the 2x2-tap kernel only; the host asks accordingly)
   auto kern = b.bn_part ? igemm_patch_kernel<T, WC, WP, TC, TP, TH, TW, NSTW, 1, OCC> : igemm_patch_kernel<T, WC, WP, TC, TP, TH, TW, NSTW, 0, OCC>;
-  (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-  hipLaunchKernelGGL(kern, grid, dim3(512), sm, st, b);
-  return hipGetLastError();
+  return launch_patch_grid<GenericPatchGeom<T, WC, WP, TC, TP, TH, TW, NSTW>>(kern, b, 1, st);
 }
 
 // bc: channel rows of the tile, bp: pixels of the tile (128: 8 x 16, 256: 16 x 16, 512: 16 x 32).  The 256-pixel tiles of the 128- and 64-row

@@ -19,51 +19,25 @@
 
 namespace vp {
 
-// tile row -> output element offset: grid pixel (y, x) of class (o0h, o0w) lands on output pixel (y * os + o0h, x * os + o0w)
-template <int TW>
-struct Patch2TilePix {
-  const IgemmArgs& a; int n, y0, x0, oh, ow;
-  __device__ __forceinline__ long long operator()(int row) const {
-    constexpr int BPR = TW / 16;
-    const int pb = row >> 4, i = row & 15;
-    const int y = y0 + pb / BPR, x = x0 + (pb % BPR) * 16 + i;
-    if (y >= a.Hg || x >= a.Wg) return -1;
-    const long long off = (((long long)n * a.Hof + (y * a.os + oh)) * a.Wof + (x * a.os + ow)) * a.ldY;
-    return (off << 8) | (long long)(n / a.ref_group_n);
-  }
-};
+// 2x2 taps: a halo of one pixel; four ring stages
+template <typename T, int WC, int WP, int TC, int TP, int TH, int TW>
+using Patch2Geom = PatchGeom<T, WC, WP, TC, TP, TH, TW, 1, 4>;
 
 // TWOSRC: the pixel operand is a virtual concat of two tensors (decoder layers); single-source launches carry one set of lane offsets
 template <typename T, int WC, int WP, int TC, int TP, int TH, int TW, int STATS, int OCC, bool TWOSRC>
 __global__ __launch_bounds__(512, OCC) void igemm_patch2_kernel(const IgemmArgs a) {
-  constexpr int E = Elem<T>::E, KC = 4 * E;
-  constexpr int NW = 8, NT = 512, NSTW = 4, NSTEP = 8;
-  static_assert(WC * WP == NW, "eight waves");
-  constexpr int BC = WC * TC * 16, BP = TH * TW;
-  static_assert(BP == WP * TP * 16, "pixel blocks of the tile = pixel blocks of the waves");
-  constexpr int NBA = BC / 16;
-  static_assert(NBA % NW == 0 || NBA == 4, "weight DMAs: whole instructions per wave (64-row tiles: half an instruction per wave)");
-  constexpr int JA = (NBA + NW - 1) / NW;
-  constexpr bool HALFW = NBA < NW;
-  constexpr int PW = TW + 1, PH = TH + 1, NPATCH = PW * PH;
-  constexpr int PPAD = (NPATCH + 127) / 128 * 128;
-  constexpr int JP = PPAD / 128;
+  using G = Patch2Geom<T, WC, WP, TC, TP, TH, TW>;
+  constexpr int NSTW = G::NSTW, NSTEP = 8;
+  constexpr int E = G::E, KC = G::KC, NW = G::NW, JA = G::JA, PW = G::PW, JP = G::JP, PBUFB = G::PBUFB, WSTB = G::WSTB, WBASE = G::WBASE;
   static_assert(JP <= 4, "one patch DMA per tap step");
-  constexpr int PBUFB = PPAD * 64;
-  constexpr int WSTB = 4 * BC * 16;
-  constexpr int WBASE = 2 * PBUFB;
-  static_assert(PBUFB + PW * 64 + 64 < 65536 && 3 * WSTB + 7 * 1024 + 16 < 65536, "read offsets are DS immediates");
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int c_base = blockIdx.y * BC;
+  const int c_base = blockIdx.y * G::BC;
   const int cls = blockIdx.z;
-  const int tiles_x = (a.Wg + TW - 1) / TW, tiles_y = (a.Hg + TH - 1) / TH;
-  const int bt = blockIdx.x;
-  const int n = bt / (tiles_x * tiles_y);
-  const int trem = bt - n * (tiles_x * tiles_y);
-  const int y0 = (trem / tiles_x) * TH, x0 = (trem % tiles_x) * TW;
+  const PatchTile tile = patch_tile_origin<TH, TW>(a);
+  const int n = tile.n, y0 = tile.y0, x0 = tile.x0;
   const int dh0 = a.taps[cls].dh[3], dw0 = a.taps[cls].dw[3];        // patch origin = tap 3 (ta = tb = 1)
   const unsigned es = sizeof(T);
   const int C0 = a.x.C[0], C1 = TWOSRC ? a.x.C[1] : 0;
@@ -81,32 +55,16 @@ __global__ __launch_bounds__(512, OCC) void igemm_patch2_kernel(const IgemmArgs 
     const int pp = (wave + NW * j) * 16 + (lane >> 2);
     const int py = pp / PW, px = pp - py * PW;
     const int ih = y0 + dh0 + py, iw = x0 + dw0 + px;
-    const bool ok = pp < NPATCH && (unsigned)ih < (unsigned)a.Hin && (unsigned)iw < (unsigned)a.Win;
+    const bool ok = pp < G::NPATCH && (unsigned)ih < (unsigned)a.Hin && (unsigned)iw < (unsigned)a.Win;
     const int piece = (lane & 3) ^ ((px >> 2) & 3);
     const int pix = (n * a.Hin + ih) * a.Win + iw;
     pvo0[j] = ok ? (unsigned)((pix * C0 + piece * E) * es) : DMA_OOB;
     if (TWOSRC) pvo1[TWOSRC ? j : 0] = ok ? (unsigned)((pix * C1 + piece * E) * es) : DMA_OOB;
   }
-  unsigned wvo[JA];
-  {
-    const int r = HALFW ? (wave & 1) * 8 + (lane >> 2) : lane >> 2;
-    const int g = (lane & 3) ^ rb_swz(r & 15);
-#pragma unroll
-    for (int j = 0; j < JA; ++j) {
-      const int blk = HALFW ? (wave >> 1) : wave + NW * j;
-      wvo[j] = (unsigned)(((c_base + blk * 16 + r) * KC + g * E) * es);
-    }
-  }
+  const PatchWeightDma<G> wdma(c_base, wave, lane);
   const unsigned wstep = (unsigned)(a.wp_rows * KC * es);
-  auto issue_w = [&](int u, int chunk, int stage) {
-    const unsigned wso = (unsigned)((3 - u) * nchunkc + chunk) * wstep;       // patch position u holds tap 3 - u
-    uint4* la = reinterpret_cast<uint4*>(smem + WBASE + stage * WSTB);
-    if constexpr (HALFW) {
-      if (lane < 32) dma16_buf(rsW, wvo[0], wso, la + (wave >> 1) * 64 + (wave & 1) * 32);
-    } else {
-#pragma unroll
-      for (int j = 0; j < JA; ++j) dma16_buf(rsW, wvo[j], wso, la + (wave + NW * j) * 64);
-    }
+  auto issue_w = [&](int u, int chunk, int stage) {       // patch position u holds tap 3 - u
+    wdma.issue(rsW, (unsigned)((3 - u) * nchunkc + chunk) * wstep, reinterpret_cast<uint4*>(smem + WBASE + stage * WSTB));
   };
   auto issue_p = [&](int chunk, int buf, int j) {
     uint4* lb = reinterpret_cast<uint4*>(smem + buf * PBUFB) + (wave + NW * j) * 64;
@@ -179,32 +137,19 @@ __global__ __launch_bounds__(512, OCC) void igemm_patch2_kernel(const IgemmArgs 
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the trailing patch pieces: the epilogue reuses the LDS
 
-  constexpr int RINGB = NSTW * WSTB + 2 * PBUFB;
-  constexpr int NPASS = epi_passes(BC, BP, WP, RINGB);
-  staged_epilogue<T, TC, TP, BC, BP, NPASS, NT, STATS>(a, Patch2TilePix<TW>{a, n, y0, x0, a.o0h[cls], a.o0w[cls]}, c_base, blkA0, blkB0, acc,
-                                                       smem, bt, cls);
+  staged_epilogue<T, TC, TP, G::BC, G::BP, G::NPASS, G::NT, STATS>(a, PatchTilePix<TW, true>{a, n, y0, x0, a.o0h[cls], a.o0w[cls]}, c_base, blkA0, blkB0,
+                                                                   acc, smem, tile.bt, cls);
 }
 
 template <typename T, int WC, int WP, int TC, int TP, int TH, int TW, int OCC>
 static hipError_t launch_patch2_t(const IgemmArgs& b, hipStream_t st) {
-  constexpr int BC = WC * TC * 16, BP = TH * TW;
-  constexpr int PPAD = ((TH + 1) * (TW + 1) + 127) / 128 * 128;
-  constexpr int RINGB = 4 * 4 * BC * 16 + 2 * PPAD * 64;
-  constexpr int NPE = epi_passes(BC, BP, WP, RINGB);
-  size_t sm = RINGB;
-  const size_t se = (size_t)(BP / NPE) * (BC * 4 + 16) + (BP / NPE) * 8;
-  if (se > sm) sm = se;
-  const int tiles = b.N * ((b.Hg + TH - 1) / TH) * ((b.Wg + TW - 1) / TW);
-  dim3 grid(tiles, b.CoutPad / BC, b.nclass);
   const bool two = b.x.C[1] > 0;
   const bool bst = b.bst_y != nullptr;                       // backward sums of the tensor this launch completes the gradient of (single-source launches: backward-data)
   if (bst && two) return hipErrorInvalidValue;
   auto kern = bst ? igemm_patch2_kernel<T, WC, WP, TC, TP, TH, TW, 2, OCC, false>
             : b.bn_part ? (two ? igemm_patch2_kernel<T, WC, WP, TC, TP, TH, TW, 1, OCC, true> : igemm_patch2_kernel<T, WC, WP, TC, TP, TH, TW, 1, OCC, false>)
                         : (two ? igemm_patch2_kernel<T, WC, WP, TC, TP, TH, TW, 0, OCC, true> : igemm_patch2_kernel<T, WC, WP, TC, TP, TH, TW, 0, OCC, false>);
-  (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-  hipLaunchKernelGGL(kern, grid, dim3(512), sm, st, b);
-  return hipGetLastError();
+  return launch_patch_grid<Patch2Geom<T, WC, WP, TC, TP, TH, TW>>(kern, b, b.nclass, st);
 }
 
 // 128- or 64-row tiles of 16 x 16 grid pixels, two blocks per CU

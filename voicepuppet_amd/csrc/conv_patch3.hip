@@ -33,24 +33,8 @@
 
 namespace vp {
 
-template <int TW>
-struct Patch3TilePix {
-  const IgemmArgs& a; int n, y0, x0;
-  __device__ __forceinline__ long long operator()(int row) const {
-    constexpr int BPR = TW / 16;
-    const int pb = row >> 4, i = row & 15;
-    const int y = y0 + pb / BPR, x = x0 + (pb % BPR) * 16 + i;
-    if (y >= a.Hg || x >= a.Wg) return -1;
-    const long long off = (((long long)n * a.Hof + y) * a.Wof + x) * a.ldY;
-    return (off << 8) | (long long)(n / a.ref_group_n);
-  }
-  static constexpr bool HAS_POOL = (TW == 16);
-  __device__ __forceinline__ long long pool(int pr, int pc) const {
-    const int y = (y0 >> 1) + pr, x = (x0 >> 1) + pc;
-    if (y >= (a.Hg >> 1) || x >= (a.Wg >> 1)) return -1;
-    return (((long long)n * (a.Hg >> 1) + y) * (a.Wg >> 1) + x) * a.ldY;
-  }
-};
+template <typename T, int WC, int WP, int TC, int TP, int TH, int TW, int NSTW, int KW>
+using Patch3Geom = PatchGeom<T, WC, WP, TC, TP, TH, TW, KW - 1, NSTW>;
 
 // NSTW: stages of the weight ring = NSTW - 1 steps of weights in flight.  A step of a 64-row tile is 8 MFMAs per wave, far shorter than
 // the 1-1.5 us an LDS-DMA takes to land under load: with 3 stages the loop ran at the DMA latency (0.7 us per step whatever the tile),
@@ -58,39 +42,19 @@ struct Patch3TilePix {
 // KW: 3 (3x3 taps) or 4 (4x4 taps: the discriminator's layer_4 backward-data passes, round 5 - 32 steps per trip, four ring stages)
 template <typename T, int WC, int WP, int TC, int TP, int TH, int TW, int STATS, int OCC, int NSTW = 3, int KW = 3>
 __global__ __launch_bounds__(512, OCC) void igemm_patch3_kernel(const IgemmArgs a) {
-  constexpr int E = Elem<T>::E, KC = 4 * E;
-  constexpr int NW = 8, NT = 512, LA = NSTW - 1;
+  using G = Patch3Geom<T, WC, WP, TC, TP, TH, TW, NSTW, KW>;
+  constexpr int E = G::E, KC = G::KC, NW = G::NW, LA = NSTW - 1;
   constexpr int KS2 = KW * KW, TRIP = 2 * KS2;                       // patch positions of a chunk, steps of a trip (two chunks)
   static_assert(TRIP % NSTW == 0 && NSTW >= 3, "ring stages");
-  static_assert(WC * WP == NW, "eight waves");
-  constexpr int BC = WC * TC * 16, BP = TH * TW;
-  static_assert(BP == WP * TP * 16, "pixel blocks of the tile = pixel blocks of the waves");
-  constexpr int NBA = BC / 16;
-  static_assert(NBA % NW == 0 || NBA == 4, "weight DMAs: whole instructions per wave (64-row tiles: half an instruction per wave)");
-  constexpr int JA = (NBA + NW - 1) / NW;
-  constexpr bool HALFW = NBA < NW;
-  constexpr int PW = TW + KW - 1, PH = TH + KW - 1, NPATCH = PW * PH;
-  constexpr int PPAD = (NPATCH + 127) / 128 * 128;                   // patch pixels, padded to whole DMA rounds of the 8 waves
-  constexpr int JP = PPAD / 128;                                     // patch DMA instructions per wave and chunk
+  constexpr int JA = G::JA, PW = G::PW, JP = G::JP, PBUFB = G::PBUFB, WSTB = G::WSTB, WBASE = G::WBASE;
   static_assert(JP + LA <= KS2, "one patch DMA per tap step, none in the last LA steps of a chunk");
-  constexpr int PBUFB = PPAD * 64;                                   // bytes of one patch buffer
-  constexpr int WSTB = 4 * BC * 16;                                  // bytes of one weight stage
-  constexpr int WBASE = 2 * PBUFB;
-  static_assert(PBUFB + (KW - 1) * PW * 64 + 64 < 65536 && (NSTW - 1) * WSTB + 7 * 1024 + 16 < 65536, "read offsets are DS immediates");
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int c_base = blockIdx.y * BC;
-  const int tiles_x = (a.Wg + TW - 1) / TW, tiles_y = (a.Hg + TH - 1) / TH;
-  // XCD-aware tile order (a.xcd_remap): each XCD a contiguous run of tiles, so that halo pixels meet in one L2.  No change for the
-  // kernel alone (the shared infinity cache already serves the halos); it takes L2-miss traffic off the fabric the co-running
-  // streams share
-  int bt = blockIdx.x;
-  if (a.xcd_remap && (gridDim.x & 7) == 0) bt = (bt & 7) * (gridDim.x >> 3) + (bt >> 3);
-  const int n = bt / (tiles_x * tiles_y);
-  const int trem = bt - n * (tiles_x * tiles_y);
-  const int y0 = (trem / tiles_x) * TH, x0 = (trem % tiles_x) * TW;
+  const int c_base = blockIdx.y * G::BC;
+  const PatchTile tile = patch_tile_origin<TH, TW>(a, a.xcd_remap);
+  const int n = tile.n, y0 = tile.y0, x0 = tile.x0;
   // tap t = 3r + c reads input pixel (y + p_dhf + r * p_dhs, x + p_dwf + c * p_dws); both steps are +1 (forward) or both -1
   // (backward-data: the flipped kernel).  The loop walks PATCH positions (pr, pc) in a fixed order; the weight chunk that belongs
   // to patch position u is tap u (forward) or tap 8 - u (flipped)
@@ -110,33 +74,16 @@ __global__ __launch_bounds__(512, OCC) void igemm_patch3_kernel(const IgemmArgs 
     const int pp = (wave + NW * j) * 16 + (lane >> 2);
     const int py = pp / PW, px = pp - py * PW;
     const int ih = y0 + dh0 + py, iw = x0 + dw0 + px;
-    const bool ok = pp < NPATCH && (unsigned)ih < (unsigned)a.Hin && (unsigned)iw < (unsigned)a.Win;
+    const bool ok = pp < G::NPATCH && (unsigned)ih < (unsigned)a.Hin && (unsigned)iw < (unsigned)a.Win;
     const int piece = (lane & 3) ^ ((px >> 2) & 3);
     pvo[j] = ok ? (unsigned)((((n * a.Hin + ih) * a.Win + iw) * C0 + piece * E) * es) : DMA_OOB;
   }
-  // weight DMA lanes (rb_swz image); 64-row tiles: every wave moves half a 16-row block (lanes 0-31)
-  unsigned wvo[JA];
-  {
-    const int r = HALFW ? (wave & 1) * 8 + (lane >> 2) : lane >> 2;
-    const int g = (lane & 3) ^ rb_swz(r & 15);
-#pragma unroll
-    for (int j = 0; j < JA; ++j) {
-      const int blk = HALFW ? (wave >> 1) : wave + NW * j;
-      wvo[j] = (unsigned)(((c_base + blk * 16 + r) * KC + g * E) * es);
-    }
-  }
+  const PatchWeightDma<G> wdma(c_base, wave, lane);
   const unsigned wstep = (unsigned)(a.wp_rows * KC * es);
   // weights of patch position u (tap u or 8 - u) and channel chunk c -> ring stage `stage`
   auto issue_w = [&](int u, int chunk, int stage) {
     const int tap = flip ? KS2 - 1 - u : u;
-    const unsigned wso = (unsigned)(tap * nchunkc + chunk) * wstep;
-    uint4* la = reinterpret_cast<uint4*>(smem + WBASE + stage * WSTB);
-    if constexpr (HALFW) {
-      if (lane < 32) dma16_buf(rsW, wvo[0], wso, la + (wave >> 1) * 64 + (wave & 1) * 32);
-    } else {
-#pragma unroll
-      for (int j = 0; j < JA; ++j) dma16_buf(rsW, wvo[j], wso, la + (wave + NW * j) * 64);
-    }
+    wdma.issue(rsW, (unsigned)(tap * nchunkc + chunk) * wstep, reinterpret_cast<uint4*>(smem + WBASE + stage * WSTB));
   };
   auto issue_p = [&](int chunk, int buf, int j) {
     uint4* lb = reinterpret_cast<uint4*>(smem + buf * PBUFB);
@@ -211,35 +158,22 @@ __global__ __launch_bounds__(512, OCC) void igemm_patch3_kernel(const IgemmArgs 
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the trailing patch pieces: the epilogue reuses the LDS
 
-  constexpr int RINGB = NSTW * WSTB + 2 * PBUFB;
-  constexpr int NPASS = epi_passes(BC, BP, WP, RINGB);
 #ifndef VP_P3_NO_FASTEPI
-  constexpr int NPASS16 = BC == 64 ? epi_passes16(BC, BP, WP, RINGB) : 0;    // 64-row tiles: +4 %; 128 rows: -8 %, 256 rows: +-0
+  constexpr int NPASS16 = G::BC == 64 ? epi_passes16(G::BC, G::BP, WP, G::RINGB) : 0;    // 64-row tiles: +4 %; 128 rows: -8 %, 256 rows: +-0
 #else
   constexpr int NPASS16 = 0;
 #endif
-  if (!(VP_P3_ABL & 8) || acc[0][0][0] == 1.2345f) staged_epilogue<T, TC, TP, BC, BP, NPASS, NT, STATS, NPASS16>(a, Patch3TilePix<TW>{a, n, y0, x0}, c_base, blkA0, blkB0, acc, smem, bt, 0);
+  if (!(VP_P3_ABL & 8) || acc[0][0][0] == 1.2345f) staged_epilogue<T, TC, TP, G::BC, G::BP, G::NPASS, G::NT, STATS, NPASS16>(a, PatchTilePix<TW>{a, n, y0, x0}, c_base, blkA0, blkB0, acc, smem, tile.bt, 0);
 }
 
 template <typename T, int WC, int WP, int TC, int TP, int TH, int TW, int OCC, int NSTW = 3, int KW = 3>
 static hipError_t launch_patch3_t(const IgemmArgs& b, hipStream_t st) {
-  constexpr int BC = WC * TC * 16, BP = TH * TW;
-  constexpr int PPAD = ((TH + KW - 1) * (TW + KW - 1) + 127) / 128 * 128;
-  constexpr int RINGB = NSTW * 4 * BC * 16 + 2 * PPAD * 64;
-  constexpr int NPE = epi_passes(BC, BP, WP, RINGB);
-  size_t sm = RINGB;
-  const size_t se = (size_t)(BP / NPE) * (BC * 4 + 16) + (BP / NPE) * 8;
-  if (se > sm) sm = se;
-  const int tiles = b.N * ((b.Hg + TH - 1) / TH) * ((b.Wg + TW - 1) / TW);
-  dim3 grid(tiles, b.CoutPad / BC, 1);
   auto kern = b.bn_part ? igemm_patch3_kernel<T, WC, WP, TC, TP, TH, TW, 1, OCC, NSTW, KW> : igemm_patch3_kernel<T, WC, WP, TC, TP, TH, TW, 0, OCC, NSTW, KW>;
   if (b.bst_y) {       // backward sums of a batch-normalised tensor (the discriminator's layer_3 under layer_4's backward-data): the 4x4 form only
     if constexpr (KW == 4) kern = igemm_patch3_kernel<T, WC, WP, TC, TP, TH, TW, 2, OCC, NSTW, KW>;
     else return hipErrorInvalidValue;
   }
-  (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-  hipLaunchKernelGGL(kern, grid, dim3(512), sm, st, b);
-  return hipGetLastError();
+  return launch_patch_grid<Patch3Geom<T, WC, WP, TC, TP, TH, TW, NSTW, KW>>(kern, b, 1, st);
 }
 
 // 3x3 taps on a +1 / +1 or -1 / -1 grid, an even number of 64-byte channel chunks: what the unrolled kernel handles
