@@ -17,6 +17,7 @@
  *   vp_bfm_reconstruct replaces  utils/reconstruct_mesh.py:198-223 Reconstruction_rotation + infer_bfmvid.py:92-99
  *   vp_puppet_*        replaces  infer_bfmvid.py:110-121, :223-224, :229-238 for the rows of many talkers (stream groups)
  *   vp_jpeg_*          replaces  infer_bfmvid.py:243-244 (cv2.imwrite per frame) with a baseline JPEG encode on the device
+ *   vp_jpegdec_*       replaces  generator/generator.py:956-1019 (cv2.imread per sample) and loader.py ImageLoader with a baseline JPEG decode on the device
  *   vp_pcmin_*         replaces  generator/loader.py:39-54 (WavLoader: scale, channel mean, resample_poly over a whole file) for live PCM
  *
  * Conventions: every function returns 0 on success and a negative vp_status otherwise (never throws);
@@ -789,6 +790,76 @@ long long vp_pcmin_ready(const vp_pcmin_t* h, const long long* in_frames, const 
  * bytes long and starts at the next 16-byte boundary after the previous one.  pcm_out: DEVICE float32, the slots' new samples packed in
  * slot order - the pcm argument of vp_bfmstream_group_push with n[s] = out_samples[s].  One launch on `stream`; never waits, never allocates. */
 int vp_pcmin_push(vp_pcmin_t* h, const void* raw, const long long* in_frames, const int* finish, float* pcm_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * JPEG decoding of training frames on the device: replaces the two cv2.imread calls per sample of generator/generator.py:956-1019 and
+ * generator/loader.py's ImageLoader (a host libjpeg decode per file) for the files of a whole batch.  csrc/jpeg_dec.hip.
+ *
+ * Accepted: baseline sequential Huffman (SOF0), 8 bit, three components in one interleaved scan, sampling 4:2:0 (2x2, 1x1, 1x1) or 4:4:4,
+ * any width and height up to the descriptor's, up to four 8-bit quantisation tables and two DC + two AC Huffman tables from the file, any
+ * restart interval.  The host parses the headers (voicepuppet_amd/jpeg_dec.py::parse) and refuses the rest before anything is enqueued.
+ *
+ * The output is defined in integers, libjpeg's default decode (what PIL runs): dequantise; the "islow" inverse DCT (13-bit constants, two
+ * passes, descale by 11 and 18, +128, clamp); for 4:2:0 "fancy" triangle up-sampling of chroma (3:1 vertically, then 3:1 horizontally with
+ * +8 / +7 rounding on even / odd columns, the edge sample replicated at the border of the component's own ceil(W/2) x ceil(H/2) samples);
+ * R = Y + ((91881 Cr' + 32768) >> 16), G = Y + ((-22554 Cb' - 46802 Cr' + 32768) >> 16), B = Y + ((116130 Cb' + 32768) >> 16) with
+ * C' = C - 128, clamped.  All of it int32 (wrapping, which only coefficients no encoder writes can reach).  tests/jpeg_dec_ref.py restates it.
+ *
+ * Per-file meta blob (little endian, 16-byte aligned, VP_JPEGDEC_META_BYTES + 24 * n_segments bytes):
+ *   [0, 128)       reserved for the host (the device reads none of it: what it needs of the header travels in vp_jpegdec_file)
+ *   [128, 640)     uint16 quant[4][64], row-major inside a block
+ *   [640, 6336)    four Huffman tables (DC 0, DC 1, AC 0, AC 1) of 1424 bytes: uint16 lut[512], entry (length << 8) | symbol of the code
+ *                  that the next 9 bits start with, 0 when that code is longer; int32 maxcode[18] by length (-1: none); int32
+ *                  valoff[18], symbol index = code + valoff[length]; uint8 vals[256]
+ *   [6336, ...)    int32 segments[n][6]: byte offset in the file of the byte that holds the segment's first bit; that bit (0 = most
+ *                  significant); DC predictors Y | Cb << 16; predictor Cr; first MCU; MCU count.  A segment may be any run of MCUs: a
+ *                  restart boundary inside it is crossed at its marker.
+ * "entries" [max_files][mcu rows][4] int32: the first four of those fields as a lane met them at every MCU-row start: fed back as segments
+ * (first MCU = row * MCUs per row) they decode a file without restart markers with one lane per MCU row.
+ * ---------------------------------------------------------------------------------------------- */
+#define VP_JPEGDEC_MAX_FILES 4096
+#define VP_JPEGDEC_META_BYTES 6336
+#define VP_JPEGDEC_FILES_PER_LAUNCH 32
+typedef struct vp_jpegdec_desc {
+  uint32_t struct_bytes;          /* sizeof(vp_jpegdec_desc) of the caller's build: must equal vp_jpegdec_desc_size() */
+  int32_t max_files;              /* files per vp_jpegdec_decode: 1 .. VP_JPEGDEC_MAX_FILES */
+  int32_t max_height;             /* 1 .. 8192 */
+  int32_t max_width;              /* 1 .. 8192 */
+  int32_t max_file_bytes;         /* 1 .. 2^30 */
+  int32_t max_segments_per_file;  /* 1 .. 2^20 */
+  int32_t bgr;                    /* 0: R G B byte order, 1: B G R (what vp_pixrefer_pack_frames takes) */
+} vp_jpegdec_desc;
+typedef struct vp_jpegdec_file {
+  uint64_t meta_offset;           /* of the file's meta blob in `blob`, a multiple of 16 */
+  uint64_t file_offset;           /* of the file's bytes in `blob` */
+  int32_t file_bytes;
+  int32_t width, height;
+  int32_t sampling;               /* 2: 4:2:0, 1: 4:4:4 */
+  int32_t restart_interval;       /* MCUs, 0: none */
+  int32_t n_segments;
+  uint8_t tq[3], td[3], ta[3];    /* per component: quantisation table 0 .. 3, DC table 0 .. 1, AC table 0 .. 1 */
+  uint8_t reserved[3];
+} vp_jpegdec_file;
+size_t vp_jpegdec_desc_size(void);
+typedef struct vp_jpegdec vp_jpegdec_t;
+/* 0 on a refused descriptor (vp_last_error names the field) */
+size_t vp_jpegdec_workspace_bytes(const vp_jpegdec_desc* d);
+/* Host only: touches no device memory.  Replaces nothing per file (ImageLoader, generator/loader.py, sets libjpeg up for every file) */
+int vp_jpegdec_create(const vp_jpegdec_desc* d, void* workspace, size_t workspace_bytes, vp_jpegdec_t** out);
+void vp_jpegdec_destroy(vp_jpegdec_t* h);
+/* blob: DEVICE bytes, metas and files as packed by the host, on a 16-byte boundary.  files: HOST, n entries, read before the call returns:
+ * the per-file table travels as kernel arguments, VP_JPEGDEC_FILES_PER_LAUNCH files per group of three launches (entropy, planes, rgb).
+ * out: DEVICE uint8, file f's pixel (y, x) at out + f * frame_stride + y * row_pitch + 3 x; only the file's own width x height pixels are
+ * written.  status: DEVICE int [n], 0 or -1 (a lane ran out of data, met an invalid code or a missing restart marker, or overran a block).
+ * A file with n_segments == 0 is a gap: its other fields are ignored, nothing is read or written for its position (a row the caller fills
+ * itself, a file the host parser refused), its status is 0.
+ * Enqueues on `stream`; never waits, never allocates.  Replaces the cv2.imread pair of generator/generator.py:956-1019 and ImageLoader. */
+int vp_jpegdec_decode(vp_jpegdec_t* h, const unsigned char* blob, const vp_jpegdec_file* files, int n, unsigned char* out, size_t row_pitch,
+                      size_t frame_stride, int* status, void* stream);
+/* "coefficients": int16 [max_files, blocks, 64], the blocks of a file in scan order, row-major inside a block, as decoded (not dequantised).
+ * "entries": int32 [max_files, mcu rows, 4].  "planes": uint8 [max_files, 3, padded height, padded width] (Y, Cb, Cr; chroma of a 4:2:0
+ * file fills the top left quarter).  Rows of the first axis are positions in the last decode call. */
+int vp_jpegdec_tensor(vp_jpegdec_t* h, const char* name, void** ptr, int64_t shape[4]);
 
 /* Host helper: CRC-32C (Castagnoli, the checksum of TensorFlow checkpoint bundles) of `n` bytes, continuing from `crc` (0 to start). */
 unsigned vp_crc32c(const void* data, size_t n, unsigned crc);

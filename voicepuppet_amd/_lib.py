@@ -59,6 +59,20 @@ class JpegDesc(ctypes.Structure):
               ("quality", ctypes.c_int32)]
 
 
+class JpegDecDesc(ctypes.Structure):
+  _fields_ = [("struct_bytes", ctypes.c_uint32), ("max_files", ctypes.c_int32), ("max_height", ctypes.c_int32), ("max_width", ctypes.c_int32),
+              ("max_file_bytes", ctypes.c_int32), ("max_segments_per_file", ctypes.c_int32), ("bgr", ctypes.c_int32)]
+
+
+class JpegDecFile(ctypes.Structure):
+  _fields_ = [("meta_offset", ctypes.c_uint64), ("file_offset", ctypes.c_uint64), ("file_bytes", ctypes.c_int32), ("width", ctypes.c_int32),
+              ("height", ctypes.c_int32), ("sampling", ctypes.c_int32), ("restart_interval", ctypes.c_int32), ("n_segments", ctypes.c_int32),
+              ("tq", ctypes.c_uint8 * 3), ("td", ctypes.c_uint8 * 3), ("ta", ctypes.c_uint8 * 3), ("reserved", ctypes.c_uint8 * 3)]
+
+
+JPEGDEC_META_BYTES = 6336            # include/vp_hip.h VP_JPEGDEC_META_BYTES
+
+
 class PcmInDesc(ctypes.Structure):
   _fields_ = [("struct_bytes", ctypes.c_int), ("slots", ctypes.c_int), ("out_rate", ctypes.c_int), ("max_in_frames", ctypes.c_int),
               ("n_rates", ctypes.c_int), ("rates", ctypes.c_int * 8)]
@@ -194,6 +208,12 @@ _SIGNATURES = {
     "vp_jpeg_tensor": (ctypes.c_int, [_P, ctypes.c_char_p, ctypes.POINTER(_P), ctypes.POINTER(ctypes.c_int64)]),
     "vp_jpeg_header": (ctypes.c_int, [_P, _P, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]),
     "vp_jpeg_destroy": (None, [_P]),
+    "vp_jpegdec_desc_size": (ctypes.c_size_t, []),
+    "vp_jpegdec_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(JpegDecDesc)]),
+    "vp_jpegdec_create": (ctypes.c_int, [ctypes.POINTER(JpegDecDesc), _P, ctypes.c_size_t, ctypes.POINTER(_P)]),
+    "vp_jpegdec_destroy": (None, [_P]),
+    "vp_jpegdec_decode": (ctypes.c_int, [_P, _P, ctypes.POINTER(JpegDecFile), ctypes.c_int, _P, ctypes.c_size_t, ctypes.c_size_t, _P, _P]),
+    "vp_jpegdec_tensor": (ctypes.c_int, [_P, ctypes.c_char_p, ctypes.POINTER(_P), ctypes.POINTER(ctypes.c_int64)]),
     "vp_pcmin_desc_size": (ctypes.c_size_t, []),
     "vp_pcmin_ratio": (ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [ctypes.POINTER(ctypes.c_int)] * 4),
     "vp_pcmin_bank": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _P]),
@@ -315,6 +335,10 @@ def lib():
       want = int(l.vp_jpeg_desc_size())
       if want != ctypes.sizeof(JpegDesc):
         raise RuntimeError("%s: vp_jpeg_desc is %d bytes in the library, %d in this binding" % (LIB_PATH, want, ctypes.sizeof(JpegDesc)))
+    if hasattr(l, "vp_jpegdec_desc_size") and l.vp_jpegdec_desc_size.argtypes is not None:
+      want = int(l.vp_jpegdec_desc_size())
+      if want != ctypes.sizeof(JpegDecDesc):
+        raise RuntimeError("%s: vp_jpegdec_desc is %d bytes in the library, %d in this binding" % (LIB_PATH, want, ctypes.sizeof(JpegDecDesc)))
     if hasattr(l, "vp_pcmin_desc_size") and l.vp_pcmin_desc_size.argtypes is not None:
       want = int(l.vp_pcmin_desc_size())
       if want != ctypes.sizeof(PcmInDesc):

@@ -1,0 +1,494 @@
+// Baseline JPEG decoding of a batch of files on the device (vp_jpegdec_*): what the reference does per sample on the host with two
+// cv2.imread calls (generator/generator.py:956-1019) and in ImageLoader (generator/loader.py).  The host parses the headers and packs, per
+// file, a meta blob (quantisation tables, Huffman look-up tables, segment table: include/vp_hip.h) and the file itself into one buffer.
+//
+//   jpegdec_entropy_kernel  one lane per segment, the 64 lanes of a workgroup on one file (its four Huffman tables in LDS).  A lane runs a
+//        64-bit bit buffer refilled bytewise (stuffed 0x00 dropped; from a marker or the end of the file on it feeds zeros and counts
+//        them), decodes a symbol by a 9-bit look-up or, for longer codes, the canonical maxcode walk, and stores every block's int16
+//        coefficients row-major to the workspace (the block zeroed first).  At every MCU-row start it records where it stands (byte, bit,
+//        predictors) in `entries`.  Reads are bounded by the file's length, writes by the segment's MCU range clamped to the file's MCU
+//        count, both taken from the kernel arguments the host validated against the descriptor, never from the blob.
+//   jpegdec_planes_kernel   one thread per 8 x 8 block: dequantise, libjpeg's "islow" inverse DCT in registers, uint8 to the padded plane.
+//   jpegdec_rgb_kernel      one thread per 4 pixels of a row: fancy up-sampling of chroma (4:2:0), YCbCr -> RGB, three dword stores where
+//        the row is dword aligned (a wave writes 768 contiguous bytes), bytes at a ragged right edge or on an unaligned row.
+//
+// Only vector loads / stores and plain C++.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <string.h>
+
+#include <new>
+#include <string>
+
+#include "errors.h"
+
+namespace vp {
+
+constexpr int kLookupBits = 9;
+constexpr int kHuffBytes = 1424;             // uint16 lut[512], int32 maxcode[18], int32 valoff[18], uint8 vals[256]
+constexpr int kQuantAt = 128, kHuffAt = 640, kSegAt = VP_JPEGDEC_META_BYTES;
+constexpr int kLanes = 64;
+
+struct DecFile {                             // one file of a launch, as kernel argument
+  uint32_t meta, file;                       // offsets in the blob
+  uint32_t bytes, nseg, dri;
+  uint16_t W, H, mcux, mcuy;
+  uint8_t sampling, tq[3], td[3], ta[3], pad[2];
+};
+
+struct DecArgs {
+  const unsigned char* blob;
+  short* coef;                               // [slot][blocks_cap][64]
+  int* entries;                              // [slot][rows_cap][4]
+  unsigned char* planes;                     // [slot][3][Hp][Wp]
+  unsigned char* out;
+  int* status;
+  size_t row_pitch, frame_stride;
+  int first;                                 // slot of f[0]
+  int blocks_cap, rows_cap, Hp, Wp, bgr;
+  DecFile f[VP_JPEGDEC_FILES_PER_LAUNCH];
+};
+
+struct HuffLds {
+  uint16_t lut[512];
+  int maxcode[18];
+  int valoff[18];
+  unsigned char vals[256];
+};
+static_assert(sizeof(HuffLds) == kHuffBytes, "meta blob layout");
+
+struct ZigzagNat {
+  unsigned char at[64];
+  constexpr ZigzagNat() : at() {
+    constexpr unsigned char zz[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+                                      41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+                                      30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+    for (int i = 0; i < 64; ++i) at[i] = zz[i];
+  }
+};
+__device__ __constant__ ZigzagNat kZigzagNat{};      // zig-zag position -> row-major index
+
+struct BitReader {
+  const unsigned char* p;        // the file
+  uint32_t pos, end;             // next byte to fetch; the file's length
+  uint64_t buf;                  // left aligned
+  int nbits;                     // valid bits in buf
+  int real;                      // of them from the file (the zeros fed behind the data are the last); negative: zeros were consumed
+  bool stopped;
+
+  __device__ __forceinline__ void start(uint32_t at, int bit) {
+    pos = at < end ? at : end; buf = 0; nbits = 0; real = 0; stopped = false;
+    refill();
+    take(bit & 7);
+  }
+  __device__ __forceinline__ void refill() {
+    while (nbits <= 56) {
+      uint32_t b = 0;
+      bool got = false;
+      if (!stopped && pos < end) {
+        b = p[pos];
+        if (b != 0xff) { ++pos; got = true; }
+        else if (pos + 1 < end && p[pos + 1] == 0) { pos += 2; got = true; }
+      }
+      if (got) real += 8; else { stopped = true; b = 0; }
+      buf |= (uint64_t)b << (56 - nbits);
+      nbits += 8;
+    }
+  }
+  __device__ __forceinline__ uint32_t peek(int n) const { return (uint32_t)(buf >> (64 - n)); }     // 1 <= n <= 32
+  __device__ __forceinline__ void skip(int n) { buf <<= n; nbits -= n; real -= n; }
+  __device__ __forceinline__ uint32_t take(int n) {
+    if (n == 0) return 0;
+    const uint32_t v = peek(n);
+    skip(n);
+    return v;
+  }
+  // where the next unread bit lies in the file: walks back over the data bytes still in the buffer (a 0x00 behind a 0xff is stuffing)
+  __device__ __forceinline__ void where(int* byte, int* bit) const {
+    uint32_t at = pos;
+    const int k = real > 0 ? (real + 7) >> 3 : 0;
+    for (int i = 0; i < k && at > 0; ++i) {
+      --at;
+      if (at > 0 && p[at] == 0 && p[at - 1] == 0xff) --at;
+    }
+    *byte = (int)at;
+    *bit = real > 0 ? (8 - (real & 7)) & 7 : 0;
+  }
+};
+
+// -1: no code of up to 16 bits starts the buffer
+__device__ __forceinline__ int huff_symbol(BitReader& r, const HuffLds& t) {
+  r.refill();
+  const uint32_t e = t.lut[r.peek(kLookupBits)];
+  if (e) { r.skip((int)(e >> 8)); return (int)(e & 255u); }
+  const int look = (int)r.peek(16);
+  for (int l = kLookupBits + 1; l <= 16; ++l) {
+    const int code = look >> (16 - l);
+    if (code <= t.maxcode[l]) { r.skip(l); return t.vals[(code + t.valoff[l]) & 255]; }
+  }
+  return -1;
+}
+
+__device__ __forceinline__ int extend(uint32_t v, int s) { return s == 0 || v >= (1u << (s - 1)) ? (int)v : (int)v - (1 << s) + 1; }
+
+__global__ __launch_bounds__(kLanes) void jpegdec_entropy_kernel(const DecArgs a) {
+  __shared__ HuffLds huff[4];
+  const DecFile& f = a.f[blockIdx.y];
+  const int seg = blockIdx.x * kLanes + threadIdx.x;
+  if ((uint32_t)(blockIdx.x * kLanes) >= f.nseg) return;        // the whole workgroup
+  const unsigned char* meta = a.blob + f.meta;
+  {
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(meta + kHuffAt);
+    uint32_t* dst = reinterpret_cast<uint32_t*>(huff);
+    for (int i = threadIdx.x; i < 4 * kHuffBytes / 4; i += kLanes) dst[i] = src[i];
+  }
+  __syncthreads();
+  if ((uint32_t)seg >= f.nseg) return;
+  const int slot = a.first + blockIdx.y;
+  const int* sg = reinterpret_cast<const int*>(meta + kSegAt) + 6 * seg;
+  const int bpm = f.sampling == 2 ? 6 : 3;
+  const int total = (int)f.mcux * f.mcuy;
+  int mcu0 = sg[4], count = sg[5];
+  if (mcu0 < 0 || mcu0 >= total || count < 1) return;           // nothing this lane may write
+  if (count > total - mcu0) count = total - mcu0;
+  int pred[3] = {(int)(short)(sg[2] & 0xffff), (int)(short)((uint32_t)sg[2] >> 16), (int)(short)(sg[3] & 0xffff)};
+
+  BitReader r;
+  r.p = a.blob + f.file;
+  r.end = f.bytes;
+  r.start((uint32_t)sg[0], sg[1]);
+  short* coef = a.coef + (size_t)slot * a.blocks_cap * 64;     // total * bpm <= blocks_cap: checked by the host against the descriptor
+  int* entries = a.entries + (size_t)slot * a.rows_cap * 4;    // mcuy <= rows_cap: likewise
+  bool bad = false;
+  for (int mcu = mcu0; mcu < mcu0 + count && !bad; ++mcu) {
+    if (f.dri && mcu > mcu0 && mcu % (int)f.dri == 0) {         // a restart inside the segment: the marker, predictors zero
+      r.refill();
+      const uint32_t m = r.pos;
+      if (r.real < 8 && m + 1 < r.end && r.p[m] == 0xff && (r.p[m + 1] & 0xf8) == 0xd0) {
+        r.start(m + 2, 0);
+        pred[0] = pred[1] = pred[2] = 0;
+      } else { bad = true; break; }
+    }
+    if (mcu % (int)f.mcux == 0) {
+      int byte, bit;
+      r.where(&byte, &bit);
+      int4 e;
+      e.x = byte; e.y = bit;
+      e.z = (int)(((uint32_t)pred[0] & 0xffffu) | ((uint32_t)pred[1] << 16));
+      e.w = (int)((uint32_t)pred[2] & 0xffffu);
+      *reinterpret_cast<int4*>(entries + 4 * (mcu / (int)f.mcux)) = e;
+    }
+    for (int j = 0; j < bpm && !bad; ++j) {
+      const int c = bpm == 6 ? (j < 4 ? 0 : j - 3) : j;
+      short* blk = coef + ((size_t)mcu * bpm + j) * 64;
+      uint4* z = reinterpret_cast<uint4*>(blk);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) z[i] = make_uint4(0, 0, 0, 0);
+      int s = huff_symbol(r, huff[f.td[c]]);
+      if (s < 0 || s > 15) { bad = true; break; }
+      pred[c] += extend(r.take(s), s);
+      blk[0] = (short)pred[c];
+      const HuffLds& ac = huff[2 + f.ta[c]];
+      int k = 1;
+      while (k < 64) {
+        const int rs = huff_symbol(r, ac);
+        if (rs < 0) { bad = true; break; }
+        const int run = rs >> 4;
+        s = rs & 15;
+        if (s == 0) {
+          if (run == 15) { k += 16; continue; }
+          break;                                               // EOB
+        }
+        k += run;
+        if (k > 63) { bad = true; break; }
+        blk[kZigzagNat.at[k]] = (short)extend(r.take(s), s);
+        ++k;
+      }
+      if (k > 64 || r.real < 0) bad = true;                     // ZRL past the block; bits taken from behind the data
+    }
+  }
+  if (bad) a.status[slot] = -1;
+}
+
+// ---- pixels ------------------------------------------------------------------------------------------------------------------------------
+// libjpeg's jidctint.c pass over v[0], v[S], .. v[7 S]; uint32 arithmetic wraps like the restatement's int32
+template <int S, int SHIFT>
+__device__ __forceinline__ void idct8(int* v) {
+  typedef uint32_t u;
+  const u i0 = v[0], i1 = v[S], i2 = v[2 * S], i3 = v[3 * S], i4 = v[4 * S], i5 = v[5 * S], i6 = v[6 * S], i7 = v[7 * S];
+  u z1 = (i2 + i6) * 4433u;
+  u tmp2 = z1 + i6 * (u)(-15137);
+  u tmp3 = z1 + i2 * 6270u;
+  u tmp0 = (i0 + i4) << 13, tmp1 = (i0 - i4) << 13;
+  const u t10 = tmp0 + tmp3, t13 = tmp0 - tmp3, t11 = tmp1 + tmp2, t12 = tmp1 - tmp2;
+  tmp0 = i7; tmp1 = i5; tmp2 = i3; tmp3 = i1;
+  z1 = tmp0 + tmp3;
+  u z2 = tmp1 + tmp2, z3 = tmp0 + tmp2, z4 = tmp1 + tmp3;
+  const u z5 = (z3 + z4) * 9633u;
+  tmp0 *= 2446u; tmp1 *= 16819u; tmp2 *= 25172u; tmp3 *= 12299u;
+  z1 *= (u)(-7373); z2 *= (u)(-20995);
+  z3 = z3 * (u)(-16069) + z5; z4 = z4 * (u)(-3196) + z5;
+  tmp0 += z1 + z3; tmp1 += z2 + z4; tmp2 += z2 + z3; tmp3 += z1 + z4;
+  const u r = 1u << (SHIFT - 1);
+  v[0] = (int)(t10 + tmp3 + r) >> SHIFT;     v[7 * S] = (int)(t10 - tmp3 + r) >> SHIFT;
+  v[S] = (int)(t11 + tmp2 + r) >> SHIFT;     v[6 * S] = (int)(t11 - tmp2 + r) >> SHIFT;
+  v[2 * S] = (int)(t12 + tmp1 + r) >> SHIFT; v[5 * S] = (int)(t12 - tmp1 + r) >> SHIFT;
+  v[3 * S] = (int)(t13 + tmp0 + r) >> SHIFT; v[4 * S] = (int)(t13 - tmp0 + r) >> SHIFT;
+}
+
+__device__ __forceinline__ int clamp255(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
+
+__global__ __launch_bounds__(256) void jpegdec_planes_kernel(const DecArgs a) {
+  const DecFile& f = a.f[blockIdx.y];
+  const int bpm = f.sampling == 2 ? 6 : 3;
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= (int)f.mcux * f.mcuy * bpm) return;
+  const int slot = a.first + blockIdx.y;
+  const int mcu = b / bpm, j = b - mcu * bpm;
+  const int my = mcu / (int)f.mcux, mx = mcu - my * (int)f.mcux;
+  int c, by, bx;
+  if (bpm == 6 && j < 4) { c = 0; by = 2 * my + (j >> 1); bx = 2 * mx + (j & 1); }
+  else { c = bpm == 6 ? j - 3 : j; by = my; bx = mx; }
+  const uint4* src = reinterpret_cast<const uint4*>(a.coef + ((size_t)slot * a.blocks_cap + b) * 64);
+  const uint4* q4 = reinterpret_cast<const uint4*>(a.blob + f.meta + kQuantAt + 128 * f.tq[c]);
+  int v[64];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const uint4 w = src[i], q = q4[i];
+    const uint32_t ww[4] = {w.x, w.y, w.z, w.w}, qq[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      v[8 * i + 2 * e] = (int)(short)(ww[e] & 0xffffu) * (int)(qq[e] & 0xffffu);
+      v[8 * i + 2 * e + 1] = (int)(short)(ww[e] >> 16) * (int)(qq[e] >> 16);
+    }
+  }
+#pragma unroll
+  for (int x = 0; x < 8; ++x) idct8<8, 11>(v + x);
+#pragma unroll
+  for (int y = 0; y < 8; ++y) idct8<1, 18>(v + 8 * y);
+  unsigned char* plane = a.planes + ((size_t)slot * 3 + c) * a.Hp * a.Wp;       // 8 by <  Hp, 8 bx < Wp: padded sizes of the descriptor
+#pragma unroll
+  for (int y = 0; y < 8; ++y) {
+    uint32_t lo = 0, hi = 0;
+#pragma unroll
+    for (int x = 0; x < 4; ++x) {
+      lo |= (uint32_t)clamp255(v[8 * y + x] + 128) << (8 * x);
+      hi |= (uint32_t)clamp255(v[8 * y + 4 + x] + 128) << (8 * x);
+    }
+    *reinterpret_cast<uint2*>(plane + (size_t)(8 * by + y) * a.Wp + 8 * bx) = make_uint2(lo, hi);
+  }
+}
+
+__global__ __launch_bounds__(256) void jpegdec_rgb_kernel(const DecArgs a) {
+  const DecFile& f = a.f[blockIdx.y];
+  const int W = f.W, H = f.H, groups = (W + 3) >> 2;
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= groups * H) return;
+  const int slot = a.first + blockIdx.y;
+  const int y = t / groups, x0 = 4 * (t - y * groups);
+  const unsigned char* Y = a.planes + (size_t)slot * 3 * a.Hp * a.Wp;
+  const unsigned char* Cb = Y + (size_t)a.Hp * a.Wp;
+  const unsigned char* Cr = Cb + (size_t)a.Hp * a.Wp;
+  int cb[4], cr[4];
+  if (f.sampling == 2) {
+    const int ch = (H + 1) >> 1, cw = (W + 1) >> 1;
+    const int r = y >> 1;
+    int rn = (y & 1) ? r + 1 : r - 1;
+    rn = rn < 0 ? 0 : (rn > ch - 1 ? ch - 1 : rn);
+    const int c0 = x0 >> 1;
+    int sb[4], sr[4];                          // column sums 3 * near row + far row at columns c0 - 1 .. c0 + 2, clamped to the component
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      int c = c0 - 1 + i;
+      c = c < 0 ? 0 : (c > cw - 1 ? cw - 1 : c);
+      sb[i] = 3 * Cb[(size_t)r * a.Wp + c] + Cb[(size_t)rn * a.Wp + c];
+      sr[i] = 3 * Cr[(size_t)r * a.Wp + c] + Cr[(size_t)rn * a.Wp + c];
+    }
+    // (3 this + this + 8) >> 4 at a replicated edge is libjpeg's (4 this + 8) >> 4
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      cb[2 * i] = (3 * sb[1 + i] + sb[i] + 8) >> 4;     cb[2 * i + 1] = (3 * sb[1 + i] + sb[2 + i] + 7) >> 4;
+      cr[2 * i] = (3 * sr[1 + i] + sr[i] + 8) >> 4;     cr[2 * i + 1] = (3 * sr[1 + i] + sr[2 + i] + 7) >> 4;
+    }
+  } else {
+    const uint32_t wb = *reinterpret_cast<const uint32_t*>(Cb + (size_t)y * a.Wp + x0);
+    const uint32_t wr = *reinterpret_cast<const uint32_t*>(Cr + (size_t)y * a.Wp + x0);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { cb[i] = (wb >> (8 * i)) & 255; cr[i] = (wr >> (8 * i)) & 255; }
+  }
+  const uint32_t wy = *reinterpret_cast<const uint32_t*>(Y + (size_t)y * a.Wp + x0);      // x0 + 3 < Wp: Wp is a multiple of 8
+  unsigned char px[12];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int l = (wy >> (8 * i)) & 255, u = cb[i] - 128, v = cr[i] - 128;
+    const int R = clamp255(l + ((91881 * v + 32768) >> 16));
+    const int G = clamp255(l + ((-22554 * u - 46802 * v + 32768) >> 16));
+    const int B = clamp255(l + ((116130 * u + 32768) >> 16));
+    px[3 * i] = (unsigned char)(a.bgr ? B : R);
+    px[3 * i + 1] = (unsigned char)G;
+    px[3 * i + 2] = (unsigned char)(a.bgr ? R : B);
+  }
+  unsigned char* dst = a.out + (size_t)slot * a.frame_stride + (size_t)y * a.row_pitch + (size_t)x0 * 3;
+  if (x0 + 4 <= W && ((uintptr_t)dst & 3) == 0) {
+    uint32_t* d = reinterpret_cast<uint32_t*>(dst);
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+      d[i] = (uint32_t)px[4 * i] | ((uint32_t)px[4 * i + 1] << 8) | ((uint32_t)px[4 * i + 2] << 16) | ((uint32_t)px[4 * i + 3] << 24);
+  } else {
+    const int n = 3 * (W - x0 < 4 ? W - x0 : 4);
+#pragma unroll
+    for (int i = 0; i < 12; ++i)
+      if (i < n) dst[i] = px[i];
+  }
+}
+
+// ---- host -------------------------------------------------------------------------------------------------------------------------------
+static size_t dec_align(size_t n) { return (n + 255) & ~(size_t)255; }
+
+struct DecLayout {
+  int Hp, Wp, blocks_cap, rows_cap;
+  size_t coef, entries, planes, total;
+};
+
+static int dec_layout(const vp_jpegdec_desc* d, DecLayout* L) {
+  if (!d) { set_err("vp_jpegdec: bad descriptor (null)"); return VP_ERR_ARG; }
+  if (d->struct_bytes != (uint32_t)sizeof(vp_jpegdec_desc)) {
+    set_err("vp_jpegdec: bad descriptor (struct_bytes %u, this library's vp_jpegdec_desc is %d bytes)", d->struct_bytes, (int)sizeof(vp_jpegdec_desc));
+    return VP_ERR_ARG;
+  }
+  if (d->max_files < 1 || d->max_files > VP_JPEGDEC_MAX_FILES) { set_err("vp_jpegdec: bad descriptor (max_files %d, 1 .. %d)", d->max_files, VP_JPEGDEC_MAX_FILES); return VP_ERR_ARG; }
+  if (d->max_height < 1 || d->max_height > 8192) { set_err("vp_jpegdec: bad descriptor (max_height %d, 1 .. 8192)", d->max_height); return VP_ERR_ARG; }
+  if (d->max_width < 1 || d->max_width > 8192) { set_err("vp_jpegdec: bad descriptor (max_width %d, 1 .. 8192)", d->max_width); return VP_ERR_ARG; }
+  if (d->max_file_bytes < 1 || d->max_file_bytes > (1 << 30)) { set_err("vp_jpegdec: bad descriptor (max_file_bytes %d, 1 .. 2^30)", d->max_file_bytes); return VP_ERR_ARG; }
+  if (d->max_segments_per_file < 1 || d->max_segments_per_file > (1 << 20)) {
+    set_err("vp_jpegdec: bad descriptor (max_segments_per_file %d, 1 .. 2^20)", d->max_segments_per_file);
+    return VP_ERR_ARG;
+  }
+  if (d->bgr != 0 && d->bgr != 1) { set_err("vp_jpegdec: bad descriptor (bgr %d, 0 or 1)", d->bgr); return VP_ERR_ARG; }
+  L->Hp = (d->max_height + 15) & ~15;
+  L->Wp = (d->max_width + 15) & ~15;
+  L->blocks_cap = 3 * (L->Hp / 8) * (L->Wp / 8);         // 4:4:4; 4:2:0 needs half of it
+  L->rows_cap = L->Hp / 8;
+  size_t o = 0;
+  L->coef = o; o += dec_align((size_t)d->max_files * L->blocks_cap * 64 * sizeof(short));
+  L->entries = o; o += dec_align((size_t)d->max_files * L->rows_cap * 4 * sizeof(int));
+  L->planes = o; o += dec_align((size_t)d->max_files * 3 * L->Hp * L->Wp);
+  L->total = o + 256;
+  return VP_OK;
+}
+
+}  // namespace vp
+
+struct vp_jpegdec {
+  vp_jpegdec_desc d;
+  vp::DecLayout L;
+  char* base;
+};
+
+using namespace vp;
+
+extern "C" {
+
+size_t vp_jpegdec_desc_size(void) { return sizeof(vp_jpegdec_desc); }
+
+size_t vp_jpegdec_workspace_bytes(const vp_jpegdec_desc* d) {
+  DecLayout L;
+  return dec_layout(d, &L) ? 0 : L.total;
+}
+
+int vp_jpegdec_create(const vp_jpegdec_desc* d, void* workspace, size_t bytes, vp_jpegdec_t** out) {
+  DecLayout L;
+  if (!out) { set_err("vp_jpegdec_create: bad argument"); return VP_ERR_ARG; }
+  *out = nullptr;
+  const int rc = dec_layout(d, &L);
+  if (rc) return rc;
+  if (!workspace || bytes < L.total) { set_err("vp_jpegdec_create: workspace too small (%zu of %zu bytes)", bytes, L.total); return VP_ERR_WORKSPACE; }
+  vp_jpegdec* h = new (std::nothrow) vp_jpegdec();
+  if (!h) { set_err("vp_jpegdec_create: out of host memory"); return VP_ERR_STATE; }
+  h->d = *d; h->L = L;
+  h->base = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  *out = h;
+  return VP_OK;
+}
+
+void vp_jpegdec_destroy(vp_jpegdec_t* h) { delete h; }
+
+int vp_jpegdec_decode(vp_jpegdec_t* h, const unsigned char* blob, const vp_jpegdec_file* files, int n, unsigned char* out, size_t row_pitch,
+                      size_t frame_stride, int* status, void* stream) {
+  if (!h || !blob || !files || !out || !status || n < 1 || n > h->d.max_files) {
+    set_err("vp_jpegdec_decode: bad argument (1 .. max_files files, device blob, output and status, host file table)");
+    return VP_ERR_ARG;
+  }
+  if ((uintptr_t)blob & 15) { set_err("vp_jpegdec_decode: the blob must start on a 16-byte boundary"); return VP_ERR_ARG; }
+  const vp_jpegdec_desc& d = h->d;
+  for (int i = 0; i < n; ++i) {
+    const vp_jpegdec_file& f = files[i];
+    const char* what = nullptr;
+    if (f.n_segments == 0) continue;              // a gap: nothing is read or written for this position
+    if (f.width < 1 || f.width > d.max_width || f.height < 1 || f.height > d.max_height) what = "width / height outside 1 .. the descriptor's maxima";
+    else if (f.sampling != 1 && f.sampling != 2) what = "sampling (1: 4:4:4, 2: 4:2:0)";
+    else if (f.file_bytes < 1 || f.file_bytes > d.max_file_bytes) what = "file_bytes outside 1 .. max_file_bytes";
+    else if (f.n_segments < 1 || f.n_segments > d.max_segments_per_file) what = "n_segments outside 1 .. max_segments_per_file";
+    else if (f.restart_interval < 0) what = "restart_interval";
+    else if (f.meta_offset & 15) what = "meta_offset is not a multiple of 16";
+    else if (f.meta_offset >> 32 || f.file_offset >> 32 || (f.file_offset + (uint64_t)f.file_bytes) >> 32) what = "offsets past 4 GiB";
+    else if ((size_t)f.width * 3 > row_pitch || (size_t)(f.height - 1) * row_pitch + (size_t)f.width * 3 > frame_stride) what = "the image does not fit row_pitch / frame_stride";
+    for (int c = 0; c < 3 && !what; ++c)
+      if (f.tq[c] > 3 || f.td[c] > 1 || f.ta[c] > 1) what = "table selector (tq 0 .. 3, td / ta 0 .. 1)";
+    if (what) { set_err("vp_jpegdec_decode: file %d: %s", i, what); return VP_ERR_ARG; }
+  }
+  const DecLayout& L = h->L;
+  hipStream_t st = (hipStream_t)stream;
+  VP_HIP_CHECK(hipMemsetAsync(status, 0, (size_t)n * sizeof(int), st));
+  for (int i0 = 0; i0 < n; i0 += VP_JPEGDEC_FILES_PER_LAUNCH) {
+    const int m = n - i0 < VP_JPEGDEC_FILES_PER_LAUNCH ? n - i0 : VP_JPEGDEC_FILES_PER_LAUNCH;
+    DecArgs a;
+    memset(&a, 0, sizeof(a));
+    a.blob = blob;
+    a.coef = (short*)(h->base + L.coef);
+    a.entries = (int*)(h->base + L.entries);
+    a.planes = (unsigned char*)(h->base + L.planes);
+    a.out = out; a.status = status; a.row_pitch = row_pitch; a.frame_stride = frame_stride;
+    a.first = i0; a.blocks_cap = L.blocks_cap; a.rows_cap = L.rows_cap; a.Hp = L.Hp; a.Wp = L.Wp; a.bgr = d.bgr;
+    int max_seg = 1, max_blocks = 1, max_groups = 1;
+    for (int i = 0; i < m; ++i) {
+      const vp_jpegdec_file& f = files[i0 + i];
+      DecFile& g = a.f[i];
+      if (f.n_segments == 0) continue;            // all zero: every kernel's bound check ends its workgroups
+      const int s = 8 * f.sampling;
+      g.meta = (uint32_t)f.meta_offset; g.file = (uint32_t)f.file_offset; g.bytes = (uint32_t)f.file_bytes;
+      g.nseg = (uint32_t)f.n_segments; g.dri = (uint32_t)f.restart_interval;
+      g.W = (uint16_t)f.width; g.H = (uint16_t)f.height;
+      g.mcux = (uint16_t)((f.width + s - 1) / s); g.mcuy = (uint16_t)((f.height + s - 1) / s);
+      g.sampling = (uint8_t)f.sampling;
+      for (int c = 0; c < 3; ++c) { g.tq[c] = f.tq[c]; g.td[c] = f.td[c]; g.ta[c] = f.ta[c]; }
+      const int blocks = (int)g.mcux * g.mcuy * (f.sampling == 2 ? 6 : 3);
+      const int groups = ((f.width + 3) / 4) * f.height;
+      if (f.n_segments > max_seg) max_seg = f.n_segments;
+      if (blocks > max_blocks) max_blocks = blocks;
+      if (groups > max_groups) max_groups = groups;
+    }
+    hipLaunchKernelGGL(jpegdec_entropy_kernel, dim3((max_seg + kLanes - 1) / kLanes, m), dim3(kLanes), 0, st, a);
+    VP_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(jpegdec_planes_kernel, dim3((max_blocks + 255) / 256, m), dim3(256), 0, st, a);
+    VP_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(jpegdec_rgb_kernel, dim3((max_groups + 255) / 256, m), dim3(256), 0, st, a);
+    VP_HIP_CHECK(hipGetLastError());
+  }
+  return VP_OK;
+}
+
+int vp_jpegdec_tensor(vp_jpegdec_t* h, const char* name, void** ptr, int64_t shape[4]) {
+  if (!h || !name || !ptr) { set_err("vp_jpegdec_tensor: bad argument"); return VP_ERR_ARG; }
+  const std::string s(name);
+  const DecLayout& L = h->L;
+  int64_t shp[4] = {h->d.max_files, 0, 0, 1};
+  if (s == "coefficients") { *ptr = h->base + L.coef; shp[1] = L.blocks_cap; shp[2] = 64; }
+  else if (s == "entries") { *ptr = h->base + L.entries; shp[1] = L.rows_cap; shp[2] = 4; }
+  else if (s == "planes") { *ptr = h->base + L.planes; shp[1] = 3; shp[2] = L.Hp; shp[3] = L.Wp; }
+  else { set_err("vp_jpegdec_tensor: no tensor '%s' (coefficients, entries, planes)", name); return VP_ERR_ARG; }
+  if (shape) for (int i = 0; i < 4; ++i) shape[i] = shp[i];
+  return VP_OK;
+}
+
+}  // extern "C"

@@ -49,6 +49,14 @@ class DeviceFramePacker:
     return self.out
 
 
+class CompressedBatch:
+  """A batch whose frames are still .jpg files: ex / cur are lists of N entries, each an item of JpegDecoder.decode_into, (bytes,
+  JpegInfo, key, None, path), or - for a file the parser refused - the decoded [S, 3S, 3] uint8 BGR frame; crops as in the raw form."""
+
+  def __init__(self, ex, cur, crops):
+    self.ex, self.cur, self.crops = ex, cur, crops
+
+
 class FramePrefetcher:
   """Double-buffered host -> device hand-over of uint8 frame batches on a side stream.
 
@@ -56,6 +64,12 @@ class FramePrefetcher:
   torch tensors cross PCIe straight from where they are (they must stay unchanged until two batches later).  next() returns the four packed
   float32 tensors of the oldest batch in flight (valid until the next call) and starts the copies of a following one; the
   copies and the pack kernel of batch k+1 overlap the training step of batch k.
+
+  A source may also yield CompressedBatch objects (the data generator with device_jpeg_decode): the files of the batch cross PCIe in
+  one pinned blob, vp_jpegdec_decode writes the frames straight into the slot's device tensors on the side stream, and the same packer
+  follows.  The decoder's status and entry points are copied to pinned memory behind it and looked at three batches later (when the
+  decoder's staging buffer is reused, long after they arrived): a file that did not decode raises RuntimeError naming it; no host wait
+  is added.  segments_used: the segment count per file of the last compressed batch filled (0: a frame that came decoded).
   """
 
   def __init__(self, source, batch, img_size, depth=2, device=None):
@@ -76,6 +90,9 @@ class FramePrefetcher:
       self.slots.append({"host": host, "dev": dev, "packer": DeviceFramePacker(batch, img_size, self.device),
                          "ready": torch.cuda.Event(), "free": torch.cuda.Event(), "busy": False})
     self.head = self.tail = 0
+    self.batch, self.img_size = batch, img_size
+    self.decoder = None                               # JpegDecoder of 2 * batch files, made by the first CompressedBatch
+    self.segments_used = []
     self._copied = []                                 # copy-done events of the last batches whose sources were read in place
     for _ in range(depth):
       self._fill()
@@ -89,9 +106,15 @@ class FramePrefetcher:
     if len(self._copied) >= 2:
       self._copied[-2].synchronize()
     try:
-      ex, cur, crops = next(self.source)
+      got = next(self.source)
     except StopIteration:
       return False
+    if isinstance(got, CompressedBatch):
+      self._fill_compressed(slot, got)
+      slot["busy"] = True
+      self.head += 1
+      return True
+    ex, cur, crops = got
     # a source that already decodes into PINNED torch tensors (what a decoder thread should do) is copied from directly; anything
     # else is staged through this slot's pinned buffers first (a host memcpy of 18 * S * S bytes per sample on the calling thread)
     srcs = []
@@ -120,6 +143,46 @@ class FramePrefetcher:
     slot["busy"] = True
     self.head += 1
     return True
+
+  def _fill_compressed(self, slot, b):
+    N, S = self.batch, self.img_size
+    if self.decoder is None:
+      from ..jpeg_dec import JpegDecoder
+      self.decoder = JpegDecoder(2 * N, S, 3 * S, bgr=True)
+      self._status = torch.empty(2 * N, dtype=torch.int32, device=self.device)
+    if "frames" not in slot:                          # ex and cur as the two halves of one tensor: one decode call fills both
+      slot["frames"] = torch.empty(2, N, S, 3 * S, 3, dtype=torch.uint8, device=self.device)
+    frames = slot["frames"]
+    items = list(b.ex) + list(b.cur)
+    assert len(items) == 2 * N
+    raw = [i for i, it in enumerate(items) if not isinstance(it, tuple)]
+    if raw and slot["busy"]:
+      slot["ready"].synchronize()                     # the staging rows below were last read by this slot's previous batch
+    with torch.cuda.stream(self.stream):
+      if slot["busy"]:
+        self.stream.wait_event(slot["free"])
+      for i in raw:                                   # frames that came decoded (refused files): staged through the slot's pinned rows
+        h = slot["host"][i // N][i % N]
+        h.copy_(torch.from_numpy(np.ascontiguousarray(items[i])))
+        frames[i // N][i % N].copy_(h, non_blocking=True)
+        items[i] = None
+      crops = b.crops if isinstance(b.crops, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(b.crops))
+      if not crops.is_pinned():
+        slot["host"][2].copy_(crops)
+        crops = slot["host"][2]
+      slot["dev"][2].copy_(crops, non_blocking=True)
+      if any(it is not None for it in items):
+        flat = frames.view(2 * N, S, 3 * S, 3)
+        self.decoder.decode_into(items, flat, flat.stride(1), flat.stride(0), self._status)
+        self.segments_used = list(self.decoder.last_segments)
+      else:
+        self.segments_used = [0] * (2 * N)
+      ev = torch.cuda.Event()
+      ev.record(self.stream)
+      self._copied = self._copied[-2:] + [ev]
+      slot["src"] = [crops]
+      slot["packer"](frames[0], frames[1], slot["dev"][2])
+      slot["ready"].record(self.stream)
 
   def next(self):
     if self.tail == self.head:

@@ -371,6 +371,9 @@ class PixReferDataGenerator(DataGenerator):
     self.img_size = params.img_size
     self.crop_ratio = params.crop_ratio
     self.seq_len = params.seq_len
+    # amd: {device_jpeg_decode: true}: the device pipeline hands over the .jpg files themselves (voicepuppet_amd/jpeg_dec.py)
+    # (force_device_jpeg_decode: the launcher's --device_jpeg_decode, which overrides the key)
+    self.device_jpeg_decode = getattr(self, 'force_device_jpeg_decode', False) or amd.get('device_jpeg_decode', False) in (True, 'true', 'yes', 1)
 
   def _load_triptych(self, image_loader, path):
     """jpg (S x 3S BGR) -> random square crop + resize of the three panels -> [S, 3S, 3] RGB float."""
@@ -424,7 +427,9 @@ class PixReferDataGenerator(DataGenerator):
   def _frame_samples(self):
     """(example frame, current frame, crops) per sample, as the device pipeline takes them: the two DECODED jpg triptychs
     [S, 3S, 3] uint8 BGR (what cv2.imread returns) and the (rx, ry, rsize) each would be cropped with (generator.py:975-977) - the
-    crop / resize / packing themselves run in vp_pixrefer_pack_frames.  Decoding runs on a thread pool (PIL releases the GIL)."""
+    crop / resize / packing themselves run in vp_pixrefer_pack_frames.  Decoding runs on a thread pool (PIL releases the GIL).
+    With device_jpeg_decode a frame is instead the file as JpegDecoder.decode_into takes it, (bytes, JpegInfo, key, None, path): the pool
+    only reads files and parses headers.  A file the parser refuses (or of another size than S x 3S) is decoded by PIL as before."""
     from concurrent.futures import ThreadPoolExecutor
     from PIL import Image
     from .device_pipeline import draw_crop
@@ -447,6 +452,18 @@ class PixReferDataGenerator(DataGenerator):
 
     def decode(path):
       return np.ascontiguousarray(np.asarray(Image.open(path).convert("RGB"), dtype=np.uint8)[:, :, ::-1])      # BGR, as cv2.imread
+    if self.device_jpeg_decode and self.data_list is not None:
+      from .. import jpeg_dec
+      pil_decode = decode
+
+      def decode(path):
+        with open(path, "rb") as fh:
+          data = fh.read()
+        info = jpeg_dec.parse(data, S, 3 * S)
+        if info.refused or (info.height, info.width) != (S, 3 * S):
+          return pil_decode(path)
+        st = os.stat(path)
+        return (data, info, (os.path.abspath(path), st.st_size, st.st_mtime_ns), None, path)
     workers = max(2, min(16, (os.cpu_count() or 4) - 1))
     with ThreadPoolExecutor(max_workers=workers) as pool:
       while True:
@@ -489,9 +506,13 @@ class _DeviceFrameIterator(object):
     import torch
     g = self.ds.owner
     N, S = self.ds.batch_size, g.img_size
-    ring = [(torch.empty(N, S, 3 * S, 3, dtype=torch.uint8).pin_memory(), torch.empty(N, S, 3 * S, 3, dtype=torch.uint8).pin_memory(),
-             torch.empty(N, 2, 3, dtype=torch.int32).pin_memory()) for _ in range(4)]
-    views = [tuple(t.numpy() for t in slot) for slot in ring]
+    files = ([], []) if g.device_jpeg_decode and g.data_list is not None else None
+    if files is None:
+      ring = [(torch.empty(N, S, 3 * S, 3, dtype=torch.uint8).pin_memory(), torch.empty(N, S, 3 * S, 3, dtype=torch.uint8).pin_memory(),
+               torch.empty(N, 2, 3, dtype=torch.int32).pin_memory()) for _ in range(4)]
+    else:                                             # compressed source: only the crops live in the ring
+      ring = [(None, None, torch.empty(N, 2, 3, dtype=torch.int32).pin_memory()) for _ in range(4)]
+    views = [tuple(t.numpy() if t is not None else None for t in slot) for slot in ring]
     buf, it = [], g._frame_samples()
     rng = np.random.default_rng()
     k = 0
@@ -501,8 +522,16 @@ class _DeviceFrameIterator(object):
         while len(buf) < max(1, g.shuffle_bufsize):
           buf.append(next(it))
         s = buf.pop(int(rng.integers(len(buf))) if g.shuffle_bufsize > 1 else 0)
+        if files is not None:                         # compressed source: the files (or, for a refused one, its decoded frame)
+          files[0].append(s[0]); files[1].append(s[1]); crops[j] = s[2]
+          continue
         ex[j] = s[0]; cur[j] = s[1]; crops[j] = s[2]
-      yield ring[k % 4]
+      if files is not None:
+        from .device_pipeline import CompressedBatch
+        yield CompressedBatch(files[0], files[1], ring[k % 4][2])
+        files = ([], [])
+      else:
+        yield ring[k % 4]
       k += 1
 
   def next_batch(self):

@@ -1,0 +1,393 @@
+"""JPEG decoding of training frames on the device (libvp_hip.so: vp_jpegdec_*, csrc/jpeg_dec.hip).
+
+What the reference does per sample on the host (generator/generator.py:956-1019: two cv2.imread calls; loader.py: ImageLoader): here the
+host only parses headers.  parse() accepts baseline 4:2:0 / 4:4:4 files (include/vp_hip.h) and gives a refusal reason for the rest, finds
+the restart markers with one numpy scan and packs the meta blob the kernels read.  JpegDecoder packs the metas and files of a batch into
+one pinned buffer, copies it once and enqueues the decode; it never waits in decode_into.
+
+Segments.  A file with restart markers is decoded one lane per interval, a file without them by one lane - and every decode records, per
+MCU row, where the lane stood (`entries`).  Those records are the file's entry-point index: pure data, kept in a cache keyed by (path,
+size, mtime); the next decode of the file runs one lane per MCU row.  save_index / load_index keep the cache in one .npz.
+"""
+import ctypes
+import functools
+import os
+
+import numpy as np
+import torch
+
+from . import _lib
+
+LOOKUP_BITS = 9
+META_BYTES = _lib.JPEGDEC_META_BYTES
+_ZIGZAG = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
+                    35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63])
+_SOF_OTHER = {0xc1: "extended sequential", 0xc2: "progressive", 0xc3: "lossless", 0xc5: "differential", 0xc6: "differential progressive",
+              0xc7: "differential lossless", 0xc9: "arithmetic", 0xca: "arithmetic progressive", 0xcb: "arithmetic lossless",
+              0xcd: "arithmetic differential", 0xce: "arithmetic differential progressive", 0xcf: "arithmetic differential lossless"}
+
+
+class JpegInfo:
+  """parse()'s result.  refused: None, or why the device decoder does not take the file (the other fields are then unset)."""
+  refused = None
+
+  def __init__(self, **kw):
+    self.__dict__.update(kw)
+
+
+@functools.lru_cache(maxsize=256)
+def _huff_table(bits, vals):
+  """BITS / HUFFVAL (bytes) -> the 1424 bytes of include/vp_hip.h's look-up form, or None for an impossible table.  Cached: the files of
+  a dataset share a handful of tables, and building one is the costly part of parsing a header."""
+  if sum(bits) > 256 or sum(bits) != len(vals):
+    return None
+  lut = np.zeros(512, np.uint16)
+  maxcode = np.full(18, -1, np.int32)
+  valoff = np.zeros(18, np.int32)
+  v = np.zeros(256, np.uint8)
+  v[:len(vals)] = np.frombuffer(vals, np.uint8)
+  code, k = 0, 0
+  for length in range(1, 17):
+    n = bits[length - 1]
+    if n:
+      if code + n > 1 << length:
+        return None
+      valoff[length] = k - code
+      maxcode[length] = code + n - 1
+      if length <= LOOKUP_BITS:
+        for i in range(n):
+          lo = (code + i) << (LOOKUP_BITS - length)
+          lut[lo:lo + (1 << (LOOKUP_BITS - length))] = (length << 8) | vals[k + i]
+      code += n
+      k += n
+    code <<= 1
+  return lut.tobytes() + maxcode.tobytes() + valoff.tobytes() + v.tobytes()
+
+
+def parse(data, max_height=None, max_width=None):
+  """bytes of a .jpg -> JpegInfo: height, width, sampling (2: 4:2:0, 1: 4:4:4), mcux, mcuy, dri, scan (offset of the entropy-coded data),
+  rst (offsets of the RSTn markers), tq / td / ta per component, segments int32 [n, 6] (one per restart interval, else one), tables (the
+  quantisation and Huffman part of the meta blob).  .refused names the reason for a file outside the subset."""
+  def no(why):
+    r = JpegInfo()
+    r.refused = why
+    return r
+  data = bytes(data)
+  if data[:2] != b"\xff\xd8":
+    return no("not a JPEG file (no SOI)")
+  quant, huff, dri, sof, p = {}, {}, 0, None, 2
+  while True:
+    if p + 4 > len(data):
+      return no("truncated header")
+    if data[p] != 0xff:
+      return no("no marker at byte %d" % p)
+    m = data[p + 1]
+    if m == 0xff:
+      p += 1
+      continue
+    n = int.from_bytes(data[p + 2:p + 4], "big")
+    if n < 2 or p + 2 + n > len(data):
+      return no("truncated header")
+    body = data[p + 4:p + 2 + n]
+    if m in _SOF_OTHER:
+      return no("%s (SOF%d): only baseline sequential Huffman files" % (_SOF_OTHER[m], m - 0xc0))
+    if m == 0xdb:
+      q = 0
+      while q < len(body):
+        if body[q] >> 4:
+          return no("16-bit quantisation table")
+        if (body[q] & 15) > 3 or q + 65 > len(body):
+          return no("bad DQT segment")
+        t = np.zeros(64, np.uint16)
+        t[_ZIGZAG] = np.frombuffer(body[q + 1:q + 65], np.uint8)
+        quant[body[q] & 15] = t
+        q += 65
+    elif m == 0xc4:
+      q = 0
+      while q < len(body):
+        if q + 17 > len(body):
+          return no("bad DHT segment")
+        tc, th, bits = body[q] >> 4, body[q] & 15, bytes(body[q + 1:q + 17])
+        vals = bytes(body[q + 17:q + 17 + sum(bits)])
+        if tc > 1 or th > 1:
+          return no("Huffman table %d / %d: baseline has two DC and two AC tables" % (tc, th))
+        t = _huff_table(bits, vals)
+        if t is None:
+          return no("bad DHT segment")
+        huff[(tc, th)] = t
+        q += 17 + sum(bits)
+    elif m == 0xc0:
+      if len(body) < 6:
+        return no("truncated header")
+      if body[0] != 8:
+        return no("%d-bit samples" % body[0])
+      if body[5] != 3:
+        return no("%d components (grey or CMYK): only three" % body[5])
+      if len(body) < 15:
+        return no("truncated header")
+      comps = [(body[6 + 3 * i], body[7 + 3 * i] >> 4, body[7 + 3 * i] & 15, body[8 + 3 * i]) for i in range(3)]
+      samp = [(h, v) for _, h, v, _ in comps]
+      if samp not in ([(2, 2), (1, 1), (1, 1)], [(1, 1), (1, 1), (1, 1)]):
+        return no("sampling %s: only 4:2:0 and 4:4:4" % "".join("%dx%d " % s for s in samp).strip())
+      sof = (int.from_bytes(body[1:3], "big"), int.from_bytes(body[3:5], "big"), samp[0][0], comps)
+    elif m == 0xdd:
+      dri = int.from_bytes(body[:2], "big")
+    elif m == 0xda:
+      if sof is None:
+        return no("SOS before SOF0")
+      if len(body) < 1:
+        return no("truncated header")
+      if body[0] != 3 or len(body) < 10:
+        return no("a scan of %d components: only one interleaved scan" % body[0])
+      if tuple(body[7:10]) != (0, 63, 0):
+        return no("not a sequential scan")
+      sel = {body[1 + 2 * i]: (body[2 + 2 * i] >> 4, body[2 + 2 * i] & 15) for i in range(3)}
+      p += 2 + n
+      break
+    p += 2 + n
+  H, W, s, comps = sof
+  if H < 1 or W < 1:
+    return no("empty image")
+  if (max_height is not None and H > max_height) or (max_width is not None and W > max_width):
+    return no("oversize: %d x %d, up to %d x %d" % (W, H, max_width, max_height))
+  try:
+    tq, td, ta = [c[3] for c in comps], [sel[c[0]][0] for c in comps], [sel[c[0]][1] for c in comps]
+  except KeyError:
+    return no("the scan names a component the frame does not have")
+  if any(t not in quant for t in tq) or any((0, t) not in huff for t in td) or any((1, t) not in huff for t in ta):
+    return no("a table the scan uses is missing")
+  # restart markers: in entropy-coded data 0xff is followed only by 0x00 or RSTn; the first other follower ends the scan
+  a = np.frombuffer(data, np.uint8)[p:]
+  ff = np.flatnonzero(a[:-1] == 0xff)
+  nxt = a[ff + 1]
+  is_rst = (nxt & 0xf8) == 0xd0
+  other = np.flatnonzero((nxt != 0) & ~is_rst)
+  if other.size:
+    ff, is_rst = ff[:other[0]], is_rst[:other[0]]
+  rst = (ff[is_rst] + p).astype(np.int64)
+  mcux, mcuy = -(-W // (8 * s)), -(-H // (8 * s))
+  total = mcux * mcuy
+  if dri:
+    nseg = -(-total // dri)
+    if len(rst) + 1 < nseg:           # a scan cut short or damaged: no lane would own the MCUs behind the last marker found
+      return no("restart markers missing: %d found, %d intervals" % (len(rst), nseg))
+    seg = np.zeros((nseg, 6), np.int32)
+    seg[0, 0] = p
+    seg[1:, 0] = rst[:nseg - 1] + 2
+    seg[:, 4] = np.arange(nseg) * dri
+    seg[:, 5] = np.minimum(dri, total - seg[:, 4])
+  else:
+    seg = np.array([[p, 0, 0, 0, 0, total]], np.int32)
+  zero = bytes(1424)
+  tables = b"".join(quant.get(i, np.zeros(64, np.uint16)).tobytes() for i in range(4)) + b"".join(huff.get(k, zero) for k in ((0, 0), (0, 1), (1, 0), (1, 1)))
+  return JpegInfo(height=H, width=W, sampling=s, mcux=mcux, mcuy=mcuy, dri=dri, scan=p, rst=rst, tq=tq, td=td, ta=ta, segments=seg, tables=tables,
+                  bytes=len(data))
+
+
+def index_segments(info, entries):
+  """entries int32 [mcuy, 4] (a decode's record of the file) -> the segment table of one lane per MCU row"""
+  seg = np.zeros((info.mcuy, 6), np.int32)
+  seg[:, :4] = entries[:info.mcuy]
+  seg[:, 4] = np.arange(info.mcuy) * info.mcux
+  seg[:, 5] = info.mcux
+  return seg
+
+
+def meta_blob(info, segments=None):
+  seg = info.segments if segments is None else segments
+  head = np.zeros(32, np.int32)
+  head[:8] = (1, info.width, info.height, info.sampling, info.mcux, info.mcuy, info.dri, len(seg))
+  return head.tobytes() + info.tables + np.ascontiguousarray(seg, np.int32).tobytes()
+
+
+def _ptr(t):
+  return ctypes.c_void_p(t.data_ptr())
+
+
+def _stream():
+  return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _key(path):
+  st = os.stat(path)
+  return (os.path.abspath(path), st.st_size, st.st_mtime_ns)
+
+
+class JpegDecoder:
+  """decode(files) -> (uint8 [n, max_height, max_width, 3] device, status int32 [n] device), files being bytes or paths.  A path's decode
+  feeds the index cache and uses it from its second decode on.  last_segments: the segment count of every file of the last call."""
+
+  RING = 3          # staging buffers: one stays untouched until two calls later (the prefetcher's contract for pinned memory)
+
+  def __init__(self, max_files, max_height, max_width, bgr=True, max_file_bytes=1 << 22, max_segments_per_file=1 << 16):
+    if not torch.cuda.is_available():
+      raise RuntimeError("JpegDecoder needs an MI355X (no CPU fallback)")
+    self.L = _lib.lib()
+    self.desc = _lib.JpegDecDesc(ctypes.sizeof(_lib.JpegDecDesc), int(max_files), int(max_height), int(max_width), int(max_file_bytes),
+                                 int(max_segments_per_file), int(bool(bgr)))
+    ws = self.L.vp_jpegdec_workspace_bytes(ctypes.byref(self.desc))
+    if ws == 0:
+      raise ValueError("invalid JPEG decoder descriptor: " + self.L.vp_last_error().decode())
+    self.max_files, self.max_height, self.max_width, self.bgr = int(max_files), int(max_height), int(max_width), bool(bgr)
+    self.workspace = torch.empty(ws, dtype=torch.uint8, device="cuda")
+    h = ctypes.c_void_p()
+    _lib.check(self.L.vp_jpegdec_create(ctypes.byref(self.desc), _ptr(self.workspace), ws, ctypes.byref(h)), "vp_jpegdec_create")
+    self.h = h
+    self.index = {}                 # (path, size, mtime_ns) -> int32 [mcuy, 4]
+    self.last_segments = []
+    self._ring = [None] * self.RING
+    self._turn = 0
+    self._pending = [None] * self.RING
+
+  # ---- the index ----
+  def save_index(self, path):
+    self.harvest()
+    keys = sorted(self.index)
+    np.savez(path, paths=np.array([k[0] for k in keys], dtype=str), sizes=np.array([k[1] for k in keys], np.int64),
+             mtimes=np.array([k[2] for k in keys], np.int64), rows=np.array([len(self.index[k]) for k in keys], np.int64),
+             entries=np.concatenate([self.index[k] for k in keys]).astype(np.int32) if keys else np.zeros((0, 4), np.int32))
+
+  def load_index(self, path):
+    z = np.load(path if str(path).endswith(".npz") else str(path) + ".npz")
+    at = 0
+    for p, s, m, r in zip(z["paths"], z["sizes"], z["mtimes"], z["rows"]):
+      self.index[(str(p), int(s), int(m))] = z["entries"][at:at + int(r)].copy()
+      at += int(r)
+
+  def harvest(self, slot=None):
+    """Reads the status and entries earlier decode_into calls left in pinned memory (of staging slot `slot`, or of all: waits for their
+    events, long completed when a slot is refilled) -> the names of the files whose status was not 0.  Their entries are dropped, the
+    others fill the index cache."""
+    bad = []
+    for k in (range(self.RING) if slot is None else [slot]):
+      if self._pending[k] is None:
+        continue
+      event, status, entries, keys, rows, names = self._pending[k]
+      self._pending[k] = None
+      event.synchronize()
+      st, en = status.numpy(), entries.numpy()
+      for i, key in enumerate(keys):
+        if names[i] is None:
+          continue
+        if st[i] != 0:
+          bad.append(names[i])
+        elif key is not None and key not in self.index:
+          self.index[key] = en[i, :rows[i]].copy()
+    return bad
+
+  # ---- decoding ----
+  def tensor(self, name):
+    """'coefficients' int16 [max_files, blocks, 64], 'entries' int32 [max_files, rows, 4], 'planes' uint8 [max_files, 3, Hp, Wp]: views of
+    the workspace, rows in the order of the last decode."""
+    p, shp = ctypes.c_void_p(), (ctypes.c_int64 * 4)()
+    _lib.check(self.L.vp_jpegdec_tensor(self.h, name.encode(), ctypes.byref(p), shp), "vp_jpegdec_tensor")
+    shape = [int(v) for v in shp]
+    dtype = {"coefficients": torch.int16, "entries": torch.int32, "planes": torch.uint8}[name]
+    off = p.value - self.workspace.data_ptr()
+    n = int(np.prod(shape)) * torch.empty(0, dtype=dtype).element_size()
+    t = self.workspace[off:off + n].view(dtype)
+    return t.view(*(shape if name == "planes" else shape[:3]))
+
+  def pack(self, items):
+    """Host half of a decode.  items: [(bytes, JpegInfo, key or None, segments or None, name) or None (a gap: that row of the output is
+    left alone)] -> what enqueue() takes: the per-file table and the metas and files in one pinned staging buffer (a ring of RING: a
+    buffer stays untouched until two calls later).  Before it reuses a staging slot it reads the status and entries the decode RING
+    calls ago left there."""
+    n = len(items)
+    if not 1 <= n <= self.max_files:
+      raise ValueError("decode: %d files, 1 .. %d" % (n, self.max_files))
+    slot = self._turn
+    self._turn = (self._turn + 1) % self.RING
+    bad = self.harvest(slot)                # of the call RING calls ago: its event has long completed
+    table = (_lib.JpegDecFile * n)()
+    parts, at, segments = [], 0, []
+    for i, item in enumerate(items):
+      if item is None:                      # a gap: n_segments 0, the caller fills the row
+        segments.append(0)
+        continue
+      data, info, key, seg, _ = item
+      if seg is None and key is not None and key in self.index and not info.dri:
+        seg = index_segments(info, self.index[key])
+      meta = meta_blob(info, seg)
+      f = table[i]
+      f.meta_offset, f.file_offset = at, at + len(meta)
+      f.file_bytes, f.width, f.height, f.sampling, f.restart_interval = len(data), info.width, info.height, info.sampling, info.dri
+      f.n_segments = len(info.segments if seg is None else seg)
+      segments.append(int(f.n_segments))
+      for c in range(3):
+        f.tq[c], f.td[c], f.ta[c] = info.tq[c], info.td[c], info.ta[c]
+      pad = -(len(meta) + len(data)) % 16
+      parts += [meta, data, bytes(pad)]
+      at += len(meta) + len(data) + pad
+    ring = self._ring[slot]
+    if ring is None or ring[0].numel() < at:
+      cap = max(at, 1 << 16) * 3 // 2
+      ring = (torch.empty(cap, dtype=torch.uint8).pin_memory(), torch.empty(cap, dtype=torch.uint8, device="cuda"),
+              torch.empty(self.max_files, dtype=torch.int32).pin_memory(),
+              torch.empty(self.tensor("entries").shape, dtype=torch.int32).pin_memory())
+      self._ring[slot] = ring
+    ring[0].numpy()[:at] = np.frombuffer(b"".join(parts), np.uint8)
+    return slot, table, at, segments, items, bad
+
+  def enqueue(self, packed, out, row_pitch, frame_stride, status, raise_bad=True):
+    """Device half: one H2D copy of the staging buffer, vp_jpegdec_decode into out (device uint8 the caller owns), and the copies of status
+    and entries back to pinned memory, all on the current stream; no wait."""
+    slot, table, at, segments, items, bad = packed
+    n = len(items)
+    pinned, dev, st_host, en_host = self._ring[slot]
+    self.last_segments = segments
+    dev[:at].copy_(pinned[:at], non_blocking=True)
+    _lib.check(self.L.vp_jpegdec_decode(self.h, _ptr(dev), table, n, _ptr(out), int(row_pitch), int(frame_stride), _ptr(status), _stream()),
+               "vp_jpegdec_decode")
+    st_host[:n].copy_(status[:n], non_blocking=True)
+    en_host[:n].copy_(self.tensor("entries")[:n], non_blocking=True)
+    event = torch.cuda.Event()
+    event.record()
+    self._pending[slot] = (event, st_host, en_host, [it and it[2] for it in items], [it and it[1].mcuy for it in items],
+                           [it and it[4] for it in items])
+    if bad and raise_bad:
+      raise RuntimeError("corrupt JPEG data in %s" % ", ".join(str(b) for b in bad))
+
+  def decode_into(self, items, out, row_pitch, frame_stride, status, raise_bad=True):
+    """pack() then enqueue().  A file's status is looked at RING calls later, when its staging slot is packed again, and only there: one
+    with status != 0 then raises RuntimeError naming it (raise_bad).  The files of the last RING calls before a decoder is dropped are
+    therefore never reported unless the caller ends with harvest(), which waits for them and returns the names."""
+    self.enqueue(self.pack(items), out, row_pitch, frame_stride, status, raise_bad)
+
+  def items(self, files, indexes=None):
+    """bytes or paths -> decode_into's items (read and parsed; a file parse() refuses raises ValueError naming the reason)."""
+    items = []
+    for i, f in enumerate(files):
+      key = None
+      if isinstance(f, (bytes, bytearray, memoryview)):
+        data, name = bytes(f), "file %d" % i
+      else:
+        key, name = _key(f), str(f)
+        with open(f, "rb") as fh:
+          data = fh.read()
+      info = parse(data, self.max_height, self.max_width)
+      if info.refused:
+        raise ValueError("%s: %s" % (name, info.refused))
+      seg = index_segments(info, np.asarray(indexes[i], np.int32)) if indexes is not None and indexes[i] is not None else None
+      items.append((data, info, key, seg, name))
+    return items
+
+  def decode(self, files, out=None, indexes=None):
+    """files: bytes or paths.  indexes: per file None or int32 [mcuy, 4] entries to decode from (paths use the cache on their own).  A
+    file parse() refuses raises ValueError naming the reason."""
+    self.harvest()                          # this convenience call may wait: the index of every earlier call is used
+    items = self.items(files, indexes)
+    if out is None:
+      out = torch.zeros(len(items), self.max_height, self.max_width, 3, dtype=torch.uint8, device="cuda")
+    assert out.dtype == torch.uint8 and out.is_cuda and out.dim() == 4 and out.shape[0] >= len(items) and out.stride(3) == 1 and out.stride(2) == 3
+    status = torch.empty(len(items), dtype=torch.int32, device="cuda")
+    self.decode_into(items, out, out.stride(1), out.stride(0), status, raise_bad=False)
+    return out[:len(items)], status
+
+  def __del__(self):
+    try:
+      if getattr(self, "h", None):
+        self.L.vp_jpegdec_destroy(self.h)
+        self.h = None
+    except Exception:
+      pass

@@ -45,6 +45,8 @@ def main(argv=None):
   cmd_parser.add_option('--batch_size', type="int", dest="batch_size", default=2, help='per-GPU batch (reference: 2)')
   cmd_parser.add_option('--img_size', type="int", dest="img_size", default=None, help='override amd.img_size')
   cmd_parser.add_option('--resume', action="store_true", dest="resume", default=False, help='restore the latest checkpoint of save_dir')
+  cmd_parser.add_option('--device_jpeg_decode', action="store_true", dest="device_jpeg_decode", default=False,
+                        help='decode the training .jpg files on the device (overrides amd.device_jpeg_decode)')
   opts, _ = cmd_parser.parse_args(argv)
 
   if (opts.config_path is None):
@@ -73,6 +75,8 @@ def main(argv=None):
   params.batch_size = batch_size
   if opts.img_size:
     params.img_size = opts.img_size
+  if opts.device_jpeg_decode:
+    train_generator.force_device_jpeg_decode = True
   train_generator.set_params(params)
   # the per-sample crop / resize / packing on the device, decoded uint8 frames copied under the previous step;
   # amd: {device_input_pipeline: false} in params.yml restores the reference's host pipeline
