@@ -860,6 +860,21 @@ int vp_jpegdec_decode(vp_jpegdec_t* h, const unsigned char* blob, const vp_jpegd
  * "entries": int32 [max_files, mcu rows, 4].  "planes": uint8 [max_files, 3, padded height, padded width] (Y, Cb, Cr; chroma of a 4:2:0
  * file fills the top left quarter).  Rows of the first axis are positions in the last decode call. */
 int vp_jpegdec_tensor(vp_jpegdec_t* h, const char* name, void** ptr, int64_t shape[4]);
+/* Device index scan (opt-in): finds the MCU-row entry points of a file without restart markers inside the decode call that first sees
+ * it, so that this very call already runs one lane per MCU row.  One workgroup per file cuts the entropy-coded segment into chunks of
+ * chunk_bytes raw file bytes, decodes every chunk from a guessed state, and repeats "chunk i from the exit state of chunk i - 1" until a
+ * round changes nothing (Huffman streams self-synchronise; Weissenberger & Schmidt, ICPP 2018); a prefix sum over block counts and DC
+ * differences then gives the block index and the predictors at every chunk start, and one more walk writes "entries".
+ * chunk_bytes: a power of two, 32 .. 4096.  max_rounds: 1 .. 1024, the bound on the fixed-point rounds of one sweep (a sweep: as many
+ * chunks as the workgroup has lanes).  vp_jpegdec_scan_workspace_bytes returns 0 on a refused value (vp_last_error names it).
+ * vp_jpegdec_enable_scan is host only; scan_workspace is DEVICE memory the caller keeps alive as long as the decoder.  Without this call
+ * vp_jpegdec_decode is unchanged.  With it, a file is scanned when n_segments == 1, restart_interval == 0, it has at least two MCU rows
+ * and its one segment starts at MCU 0 and covers every MCU; every other file of the call takes the usual path.  The scan holds
+ * ("scan_ok" 1) only if the rounds settled, no settled lane met an invalid code and the block total is the file's; otherwise one lane
+ * decodes the file's single segment as without the scan.  Two more names of vp_jpegdec_tensor, both int32 [max_files] and 0 for a file
+ * that was not scanned: "scan_ok", and "scan_rounds", the most rounds a sweep of the file took (the last, unchanged round included). */
+size_t vp_jpegdec_scan_workspace_bytes(const vp_jpegdec_desc* d, int chunk_bytes);
+int vp_jpegdec_enable_scan(vp_jpegdec_t* h, void* scan_workspace, size_t scan_workspace_bytes, int chunk_bytes, int max_rounds);
 
 /* Host helper: CRC-32C (Castagnoli, the checksum of TensorFlow checkpoint bundles) of `n` bytes, continuing from `crc` (0 to start). */
 unsigned vp_crc32c(const void* data, size_t n, unsigned crc);

@@ -1,9 +1,10 @@
 """Decode rate of the device JPEG decoder (voicepuppet_amd.jpeg_dec.JpegDecoder) against the host expression it replaces: one JSON line
 into profiles/jpeg_decode.json.  Needs an MI355X; no fallback.
 
-  (a) 64 triptychs of 256 x 768 at quality 95, three forms alternating in one process, medians after warm-up: no restart markers and no
-      index (one lane per file), the same files from their index (one lane per MCU row), and their restart_marker_rows=1 re-saves (one
-      lane per interval).  Three figures per form, each its own: host_parse_ms (reading nothing: jpeg_dec.parse of the 64 byte strings
+  (a) 64 triptychs of 256 x 768 at quality 95, four forms alternating in one process, medians after warm-up: no restart markers and no
+      index (one lane per file), the same files at first sight through a decoder with the index scan (scan_chunk_bytes=--scan_chunk: the
+      scan kernel, then one lane per MCU row), the same files from their index (one lane per MCU row), and their restart_marker_rows=1
+      re-saves (one lane per interval).  Three figures per form, each its own: host_parse_ms (reading nothing: jpeg_dec.parse of the 64 byte strings
       on one thread), host_pack_ms (JpegDecoder.pack: meta blobs, the per-file table, the copy into the pinned staging buffer) and
       device_ms (events around JpegDecoder.enqueue alone, parsed and packed before the first event: the H2D copy of the blob, the three
       kernels per 32 files, the copies of status and entries back).
@@ -15,6 +16,9 @@ into profiles/jpeg_decode.json.  Needs an MI355X; no fallback.
       beside them: of the dataset iterator alone (PixReferDataGenerator.get_device_dataset, nothing consuming the batches but a stream
       wait), and of the train_pixrefer.py loop, each variant a child process, from the launcher's own log (its cumulative frames/s
       every 50 iterations, differenced into per-interval rates; an epoch is 100 iterations).
+  --scan_out PATH merges the scan's figures (device_ms of one-lane, scan and indexed of this run and their ratios, the rounds, the
+  first-epoch iterator rate with and without the scan) into PATH's "measured" key (profiles/jpeg_scan.json); --only picks the parts
+  (iterator_scan: one more first epoch of the iterator, through the index scan).
 """
 import argparse
 import io
@@ -83,16 +87,16 @@ def loop_rates(tmp, N=32, S=256):
           "intervals": {"flag_off": off, "flag_on": on, "synthetic": syn}, "batch": N, "img_size": S, "files": FOLDER_FILES}
 
 
-def iterator_rates(tmp, paths, N=32, S=256):
+def iterator_rates(tmp, paths, N=32, S=256, scan_chunk=128, plain=True, scan=True):
   import torch
   from voicepuppet_amd.generator.generator import PixReferDataGenerator
   lst, count = os.path.join(tmp, "train.txt"), FOLDER_FILES
-  def run(dataset_path, on, spans):
+  def run(dataset_path, on, spans, scan=0):
     g = PixReferDataGenerator(os.path.join(ROOT, "config", "params.yml"))
     p = g.params
     p.dataset_path, p.batch_size, p.img_size = dataset_path, N, S
     amd = dict(p.get("amd") or {})
-    amd["device_jpeg_decode"] = on
+    amd["device_jpeg_decode"], amd["device_jpeg_scan"] = on, scan
     p.amd = amd
     g.set_params(p)
     it = g.get_device_dataset().make_one_shot_iterator()
@@ -108,11 +112,17 @@ def iterator_rates(tmp, paths, N=32, S=256):
       rates.append(N * batches / (time.perf_counter() - t0))
     return rates, (list(it._pf.segments_used[:2]) if on else None)
   epoch = count // N
-  off, _ = run(lst, False, [(4, 40)])
-  on, segs = run(lst, True, [(4, epoch - 8), (epoch + 8, 40)])
-  syn, _ = run(os.path.join(tmp, "absent.txt"), False, [(4, 40)])
-  return {"flag_off_pil": off[0], "flag_on_first_epoch": on[0], "flag_on_indexed": on[1], "flag_on_indexed_segments_per_file": segs,
-          "synthetic_pool": syn[0], "batch": N, "img_size": S, "files": count}
+  res = {"batch": N, "img_size": S, "files": count}
+  if plain:
+    off, _ = run(lst, False, [(4, 40)])
+    on, segs = run(lst, True, [(4, epoch - 8), (epoch + 8, 40)])
+    syn, _ = run(os.path.join(tmp, "absent.txt"), False, [(4, 40)])
+    res.update({"flag_off_pil": off[0], "flag_on_first_epoch": on[0], "flag_on_indexed": on[1], "flag_on_indexed_segments_per_file": segs,
+                "synthetic_pool": syn[0]})
+  if scan:
+    rates, scan_segs = run(lst, True, [(4, epoch - 8)], scan_chunk)
+    res.update({"flag_on_scan_first_epoch": rates[0], "flag_on_scan_first_epoch_segments_per_file": scan_segs, "scan_chunk_bytes": scan_chunk})
+  return res
 
 
 def main():
@@ -121,6 +131,10 @@ def main():
   ap.add_argument("--repeats", type=int, default=30)
   ap.add_argument("--warmup", type=int, default=5)
   ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "jpeg_decode.json"))
+  ap.add_argument("--scan_chunk", type=int, default=128)
+  ap.add_argument("--scan_out", default=None)
+  ap.add_argument("--only", default="decode,host,iterator,iterator_scan,loop",
+                  help="comma list of: decode (always), host, iterator, iterator_scan, loop")
   a = ap.parse_args()
   import torch
   from PIL import Image
@@ -140,12 +154,15 @@ def main():
   want = out.cpu().numpy().copy()
   assert st.cpu().tolist() == [0] * a.files
   index = [e.cpu().numpy().copy() for e in dec.tensor("entries")[:a.files, :16]]
-  forms = {"one_lane_per_file": (plain, None), "indexed": (plain, index), "restart_markers": (marked, None)}
+  dec_scan = JpegDecoder(a.files, 256, 768, bgr=True, scan_chunk_bytes=a.scan_chunk)      # byte strings have no key: always first sight
+  forms = {"one_lane_per_file": (plain, None), "scan": (plain, None), "indexed": (plain, index), "restart_markers": (marked, None)}
+  base, scan_rounds = dec, None
   times = {k: {"device": [], "parse": [], "pack": []} for k in forms}
   segs = {}
   status = torch.empty(a.files, dtype=torch.int32, device="cuda")
   for r in range(a.warmup + a.repeats):
     for name, (files, idx) in forms.items():          # alternating
+      dec = dec_scan if name == "scan" else base
       t0 = time.perf_counter()
       items = dec.items(files, idx)                   # host: parse the headers
       t1 = time.perf_counter()
@@ -164,6 +181,9 @@ def main():
       elif r == 0:
         assert status.cpu().tolist() == [0] * a.files
         segs[name] = dec.last_segments[0]
+        if name == "scan":
+          assert dec.tensor("scan_ok")[:a.files].cpu().tolist() == [1] * a.files
+          scan_rounds = dec.tensor("scan_rounds")[:a.files].cpu().tolist()
         if files is plain:
           assert np.array_equal(out.cpu().numpy(), want)
   res = {"metric": "jpeg_decode", "device": torch.cuda.get_device_name(0), "files": a.files, "shape": [256, 768, 3], "quality": 95,
@@ -175,6 +195,11 @@ def main():
          "note": "device_ms: events around JpegDecoder.enqueue alone (H2D copy of the blob, kernels, status / entries copies back); "
                  "parse and pack are host wall time on one thread, outside the events"}
 
+  dec = base
+  med = {k: res["decode"][k]["device_ms_median"] for k in res["decode"]}
+  res["scan"] = {"chunk_bytes": a.scan_chunk, "max_rounds": dec_scan.scan_max_rounds, "rounds_per_file_max": max(scan_rounds), "rounds_per_file_median": float(np.median(scan_rounds)),
+                 "device_ms_scan_over_one_lane": med["scan"] / med["one_lane_per_file"], "device_ms_scan_over_indexed": med["scan"] / med["indexed"]}
+  only = set(a.only.split(","))
   tmp = tempfile.mkdtemp(prefix="jpeg_decode_rate_")
   paths = []
   for i, f in enumerate(plain):
@@ -184,29 +209,42 @@ def main():
 
   def host(p):
     return np.ascontiguousarray(np.asarray(Image.open(p).convert("RGB"))[..., ::-1])
-  one, pool = [], []
-  with ThreadPoolExecutor(16) as ex:
-    for r in range(3 + 10):
-      t0 = time.perf_counter()
-      for p in paths:
-        host(p)
-      t1 = time.perf_counter()
-      list(ex.map(host, paths))
-      t2 = time.perf_counter()
-      if r >= 3:
-        one.append((t1 - t0) / len(paths) * 1e3)
-        pool.append((t2 - t1) / len(paths) * 1e3)
-  res["host_pil"] = {"one_thread_ms_per_file": float(np.median(one)), "pool16_wall_ms_per_file": float(np.median(pool))}
+  if "host" in only:
+    one, pool = [], []
+    with ThreadPoolExecutor(16) as ex:
+      for r in range(3 + 10):
+        t0 = time.perf_counter()
+        for p in paths:
+          host(p)
+        t1 = time.perf_counter()
+        list(ex.map(host, paths))
+        t2 = time.perf_counter()
+        if r >= 3:
+          one.append((t1 - t0) / len(paths) * 1e3)
+          pool.append((t2 - t1) / len(paths) * 1e3)
+    res["host_pil"] = {"one_thread_ms_per_file": float(np.median(one)), "pool16_wall_ms_per_file": float(np.median(pool))}
   make_folder(tmp, paths)
-  res["iterator_frames_per_second"] = iterator_rates(tmp, paths)
-  del dec, out
+  if only & {"iterator", "iterator_scan"}:
+    res["iterator_frames_per_second"] = iterator_rates(tmp, paths, scan_chunk=a.scan_chunk, plain="iterator" in only, scan="iterator_scan" in only)
+  del dec, base, dec_scan, out
   torch.cuda.empty_cache()
-  res["train_loop_frames_per_second"] = loop_rates(tmp)
+  if "loop" in only:
+    res["train_loop_frames_per_second"] = loop_rates(tmp)
   shutil.rmtree(tmp)
   line = json.dumps(res)
   print(line)
   with open(a.out, "w") as f:
     f.write(line + "\n")
+  if a.scan_out:
+    rec = json.load(open(a.scan_out)) if os.path.exists(a.scan_out) else {}
+    it = res.get("iterator_frames_per_second", {})
+    rec.pop("note", None)
+    rec["measured"] = {"device": res["device"], "files": a.files, "shape": [256, 768, 3], "quality": 95, "mean_file_bytes": res["mean_file_bytes"],
+                       "repeats": a.repeats, "warmup": a.warmup, "device_ms_median": med, "segments_per_file": segs, "scan": res["scan"],
+                       "iterator_first_epoch_frames_per_second": {"scan": it.get("flag_on_scan_first_epoch"), "one_lane": it.get("flag_on_first_epoch"),
+                                                                  "indexed": it.get("flag_on_indexed"), "pil": it.get("flag_off_pil")}}
+    with open(a.scan_out, "w") as f:
+      f.write(json.dumps(rec, indent=1) + "\n")
 
 
 if __name__ == "__main__":

@@ -214,6 +214,8 @@ _SIGNATURES = {
     "vp_jpegdec_destroy": (None, [_P]),
     "vp_jpegdec_decode": (ctypes.c_int, [_P, _P, ctypes.POINTER(JpegDecFile), ctypes.c_int, _P, ctypes.c_size_t, ctypes.c_size_t, _P, _P]),
     "vp_jpegdec_tensor": (ctypes.c_int, [_P, ctypes.c_char_p, ctypes.POINTER(_P), ctypes.POINTER(ctypes.c_int64)]),
+    "vp_jpegdec_scan_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(JpegDecDesc), ctypes.c_int]),
+    "vp_jpegdec_enable_scan": (ctypes.c_int, [_P, _P, ctypes.c_size_t, ctypes.c_int, ctypes.c_int]),
     "vp_pcmin_desc_size": (ctypes.c_size_t, []),
     "vp_pcmin_ratio": (ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [ctypes.POINTER(ctypes.c_int)] * 4),
     "vp_pcmin_bank": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _P]),

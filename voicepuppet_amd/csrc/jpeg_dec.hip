@@ -8,6 +8,9 @@
 //        coefficients row-major to the workspace (the block zeroed first).  At every MCU-row start it records where it stands (byte, bit,
 //        predictors) in `entries`.  Reads are bounded by the file's length, writes by the segment's MCU range clamped to the file's MCU
 //        count, both taken from the kernel arguments the host validated against the descriptor, never from the blob.
+//   jpegdec_scan_kernel     (opt-in, vp_jpegdec_enable_scan) one workgroup per file without restart markers and without an index: finds the
+//        file's MCU-row entry points in parallel, chunk by chunk, by the self-synchronisation of Huffman streams, and writes `entries`
+//        before the entropy kernel of the same call runs, which then takes one lane per MCU row.  See the comment at the kernel.
 //   jpegdec_planes_kernel   one thread per 8 x 8 block: dequantise, libjpeg's "islow" inverse DCT in registers, uint8 to the padded plane.
 //   jpegdec_rgb_kernel      one thread per 4 pixels of a row: fancy up-sampling of chroma (4:2:0), YCbCr -> RGB, three dword stores where
 //        the row is dword aligned (a wave writes 768 contiguous bytes), bytes at a ragged right edge or on an unaligned row.
@@ -28,12 +31,14 @@ constexpr int kLookupBits = 9;
 constexpr int kHuffBytes = 1424;             // uint16 lut[512], int32 maxcode[18], int32 valoff[18], uint8 vals[256]
 constexpr int kQuantAt = 128, kHuffAt = 640, kSegAt = VP_JPEGDEC_META_BYTES;
 constexpr int kLanes = 64;
+constexpr int kScanLanes = 1024;             // chunks of one sweep of the index scan
 
 struct DecFile {                             // one file of a launch, as kernel argument
   uint32_t meta, file;                       // offsets in the blob
   uint32_t bytes, nseg, dri;
   uint16_t W, H, mcux, mcuy;
-  uint8_t sampling, tq[3], td[3], ta[3], pad[2];
+  uint8_t sampling, tq[3], td[3], ta[3];
+  uint8_t scan, pad;                         // scan: the index scan runs on this file and the entropy kernel asks scan_ok
 };
 
 struct DecArgs {
@@ -46,6 +51,10 @@ struct DecArgs {
   size_t row_pitch, frame_stride;
   int first;                                 // slot of f[0]
   int blocks_cap, rows_cap, Hp, Wp, bgr;
+  uint2* scan_state;                         // [file of the launch][chunks_cap]: exit state per chunk (null: no scan)
+  int* scan_ok;                              // [slot]
+  int* scan_rounds;                          // [slot]
+  int chunk_bytes, chunks_cap, max_rounds;
   DecFile f[VP_JPEGDEC_FILES_PER_LAUNCH];
 };
 
@@ -135,7 +144,10 @@ __global__ __launch_bounds__(kLanes) void jpegdec_entropy_kernel(const DecArgs a
   __shared__ HuffLds huff[4];
   const DecFile& f = a.f[blockIdx.y];
   const int seg = blockIdx.x * kLanes + threadIdx.x;
-  if ((uint32_t)(blockIdx.x * kLanes) >= f.nseg) return;        // the whole workgroup
+  // a scanned file whose scan held: one lane per MCU row from `entries`; one that did not hold: its single segment, as without the scan
+  const bool by_row = f.scan && a.scan_ok[a.first + blockIdx.y] == 1;
+  const uint32_t nseg = by_row ? (uint32_t)f.mcuy : f.nseg;
+  if ((uint32_t)(blockIdx.x * kLanes) >= nseg) return;          // the whole workgroup
   const unsigned char* meta = a.blob + f.meta;
   {
     const uint32_t* src = reinterpret_cast<const uint32_t*>(meta + kHuffAt);
@@ -143,9 +155,18 @@ __global__ __launch_bounds__(kLanes) void jpegdec_entropy_kernel(const DecArgs a
     for (int i = threadIdx.x; i < 4 * kHuffBytes / 4; i += kLanes) dst[i] = src[i];
   }
   __syncthreads();
-  if ((uint32_t)seg >= f.nseg) return;
+  if ((uint32_t)seg >= nseg) return;
   const int slot = a.first + blockIdx.y;
-  const int* sg = reinterpret_cast<const int*>(meta + kSegAt) + 6 * seg;
+  int* entries = a.entries + (size_t)slot * a.rows_cap * 4;    // mcuy <= rows_cap: checked by the host against the descriptor
+  int sg[6];
+  if (by_row) {
+    const int4 e = *reinterpret_cast<const int4*>(entries + 4 * seg);
+    sg[0] = e.x; sg[1] = e.y; sg[2] = e.z; sg[3] = e.w; sg[4] = seg * (int)f.mcux; sg[5] = f.mcux;
+  } else {
+    const int* src = reinterpret_cast<const int*>(meta + kSegAt) + 6 * seg;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) sg[i] = src[i];
+  }
   const int bpm = f.sampling == 2 ? 6 : 3;
   const int total = (int)f.mcux * f.mcuy;
   int mcu0 = sg[4], count = sg[5];
@@ -157,8 +178,7 @@ __global__ __launch_bounds__(kLanes) void jpegdec_entropy_kernel(const DecArgs a
   r.p = a.blob + f.file;
   r.end = f.bytes;
   r.start((uint32_t)sg[0], sg[1]);
-  short* coef = a.coef + (size_t)slot * a.blocks_cap * 64;     // total * bpm <= blocks_cap: checked by the host against the descriptor
-  int* entries = a.entries + (size_t)slot * a.rows_cap * 4;    // mcuy <= rows_cap: likewise
+  short* coef = a.coef + (size_t)slot * a.blocks_cap * 64;     // total * bpm <= blocks_cap: likewise
   bool bad = false;
   for (int mcu = mcu0; mcu < mcu0 + count && !bad; ++mcu) {
     if (f.dri && mcu > mcu0 && mcu % (int)f.dri == 0) {         // a restart inside the segment: the marker, predictors zero
@@ -208,6 +228,229 @@ __global__ __launch_bounds__(kLanes) void jpegdec_entropy_kernel(const DecArgs a
     }
   }
   if (bad) a.status[slot] = -1;
+}
+
+
+// ---- index scan ------------------------------------------------------------------------------------------------------------------------
+// The entropy-coded segment of a file, from the byte its one segment starts at to the end of the file, is cut into chunks of chunk_bytes
+// raw file bytes; lane i of the workgroup owns chunk i (a file with more than kScanLanes chunks is handled in sweeps of kScanLanes).  A
+// decoder state is (position of the next symbol as BitReader::where() names it, block-in-MCU j, zig-zag position k; k == 0: a DC
+// symbol comes next), packed as (byte, bit | j << 3 | k << 8).  decode(chunk, state) decodes symbols from `state` while the next symbol
+// starts in front of the chunk's end and returns the state it then stands in.
+//
+//   cold pass   exit[i] = decode(chunk i, guess): the guess of lane 0 is the true state (the segment's start; in a later sweep the settled
+//               exit of the chunk before), the guess of every other lane its chunk's first byte - one further if that byte is the stuffed
+//               0x00 of an 0xff 0x00 pair - bit 0, j = 0, k = 0.
+//   rounds      exit[i] = decode(chunk i, exit[i - 1]) for all i >= 1 at once (every lane reads its neighbour's state of the round before),
+//               until a round changes nothing or max_rounds is reached.  A lane whose input did not change since it last decoded does
+//               not decode again: decode() is a function of its input.
+//   Why the fixed point is the serial decode: in a round without change exit[i] == decode(chunk i, exit[i - 1]) holds for every i >= 1,
+//   and exit[-1], lane 0's input, is the true state.  The serial decoder's state at the end of chunk 0 is decode(chunk 0, true) = exit[0];
+//   if its state at the end of chunk i - 1 is exit[i - 1], its state at the end of chunk i is decode(chunk i, exit[i - 1]) = exit[i].  By
+//   induction every exit[i] is the serial decoder's state.  That it is reached in few rounds is the self-synchronisation of Huffman
+//   codes (Weissenberger & Schmidt, "Massively Parallel Huffman Decoding on GPUs", ICPP 2018); that it was reached is checked, never assumed.
+//   count pass  from its settled input every lane counts the blocks that start in its chunk and sums their DC differences per component;
+//               an exclusive prefix sum over the workgroup, carried across sweeps, gives the block index and the three predictors
+//               (modulo 2^16 in the end, as `entries` stores them) at every chunk start.
+//   entry pass  one more walk; where a block with index % (blocks per MCU) == 0 and MCU % mcux == 0 starts, entries[row] is written from
+//               BitReader::where(), the form the entropy kernel records.
+//
+// Rules for states no valid stream reaches (only determinism matters, a wrong guess is only ever a starting point):
+//   - a symbol (code and extra bits) that takes bits from behind the data (the end of the file or a marker) is void, and so is an
+//     invalid code with fewer than 16 bits of data left (zeros fed behind the data took part in calling it invalid): the walk ends in the
+//     state in front of it.  The padding behind the last block, up to seven ones, ends the true walk this way: no code of a table built
+//     by the standard's procedure is all ones, so the padding either starts a code that runs into the zeros or starts none;
+//   - an invalid code, a DC category above 15, a run past coefficient 63: the reader goes back in front of the symbol, drops one bit, and
+//     a DC symbol of the same block-in-MCU is expected (k = 0).
+// scan_ok = the rounds of every sweep settled, no lane met the second rule from its settled input, every counted block's j agreed with
+// its index, and the block total is mcux * mcuy * blocks per MCU.  Reads are bounded by the file's length (BitReader), the walk by the
+// chunk's end (every step consumes at least one bit), the writes to `entries` by mcuy, the state writes by the chunk count of the file's
+// length, which the host checked against the descriptor the workspace was sized for.
+__device__ __forceinline__ bool same(uint2 a, uint2 b) { return a.x == b.x && a.y == b.y; }
+
+// MODE 0: states only.  1: acc += (blocks, DC differences per component).  2: acc runs as (block index, predictors), entries are written.
+// -> the exit state; *err: the drop-one-bit rule was used (MODE 2: or a block's j disagrees with its index)
+template <int MODE>
+__device__ __forceinline__ uint2 scan_walk(const unsigned char* file, uint32_t bytes, const HuffLds* huff, const DecFile& f, int bpm, uint2 in,
+                                           uint32_t chunk_end, int4& acc, bool& err, int* entries) {
+  BitReader r;
+  r.p = file;
+  r.end = bytes;
+  r.start(in.x, (int)(in.y & 7u));
+  int j = (int)(in.y >> 3) & 7, k = (int)(in.y >> 8);
+  for (;;) {
+    const BitReader s = r;                                      // in front of the next symbol
+    int byte = 0, bit = 0;
+    bool stop = false;
+    // where() lies at least the buffer's data bytes in front of pos: only then can it have reached the chunk's end (and is worth its walk)
+    if (r.pos >= chunk_end + (uint32_t)(r.real > 0 ? (r.real + 7) >> 3 : 0)) {
+      s.where(&byte, &bit);
+      stop = (uint32_t)byte >= chunk_end;
+    }
+    bool bad = false;
+    int c = 0, diff = 0;
+    if (!stop) {
+      if (k == 0) {
+        c = bpm == 6 ? (j < 4 ? 0 : j - 3) : j;
+        const int sy = huff_symbol(r, huff[f.td[c]]);
+        if (sy < 0 || sy > 15) bad = true;
+        else diff = extend(r.take(sy), sy);
+        c = sy < 0 ? -1 : c;
+      } else {
+        const int rs = huff_symbol(r, huff[2 + f.ta[bpm == 6 ? (j < 4 ? 0 : j - 3) : j]]);
+        if (rs < 0) bad = true;
+        else if (rs & 15) r.take(rs & 15);
+        c = rs;
+      }
+      if (r.real < 0 || (c < 0 && r.real < 16)) {               // void: bits from behind the data
+        stop = true;
+        s.where(&byte, &bit);
+      }
+    }
+    if (stop) return make_uint2((uint32_t)byte, (uint32_t)(bit | (j << 3) | (k << 8)));
+    if (!bad) {
+      if (k == 0) {
+        if (MODE == 1) {
+          acc.x += 1;
+          if (c == 0) acc.y += diff; else if (c == 1) acc.z += diff; else acc.w += diff;
+        }
+        if (MODE == 2) {
+          const int mcu = acc.x / bpm;
+          if (acc.x - mcu * bpm != j) err = true;
+          else if (j == 0 && mcu % (int)f.mcux == 0 && mcu / (int)f.mcux < (int)f.mcuy) {
+            int4 e;
+            s.where(&e.x, &e.y);
+            e.z = (int)(((uint32_t)acc.y & 0xffffu) | ((uint32_t)acc.z << 16));
+            e.w = (int)((uint32_t)acc.w & 0xffffu);
+            *reinterpret_cast<int4*>(entries + 4 * (mcu / (int)f.mcux)) = e;
+          }
+          acc.x += 1;
+          if (c == 0) acc.y += diff; else if (c == 1) acc.z += diff; else acc.w += diff;
+        }
+        k = 1;
+      } else {
+        const int run = c >> 4;
+        if ((c & 15) == 0) {
+          if (run == 15) { k += 16; bad = k > 64; }
+          else k = 64;                                          // EOB
+        } else {
+          k += run;
+          if (k > 63) bad = true; else ++k;
+        }
+      }
+    }
+    if (bad) {
+      err = true;
+      r = s;
+      r.refill();
+      r.skip(1);
+      k = 0;
+    } else if (k >= 64) {
+      k = 0;
+      j = j + 1 == bpm ? 0 : j + 1;
+    }
+  }
+}
+
+__global__ __launch_bounds__(kScanLanes) void jpegdec_scan_kernel(const DecArgs a) {
+  __shared__ HuffLds huff[4];
+  __shared__ int4 pre[kScanLanes];
+  __shared__ int4 carry;                                        // block index and predictors at the sweep's first chunk
+  __shared__ int changed, failed;
+  const DecFile& f = a.f[blockIdx.x];
+  if (!f.scan) return;
+  const int lane = threadIdx.x, slot = a.first + blockIdx.x;
+  const unsigned char* meta = a.blob + f.meta;
+  const unsigned char* file = a.blob + f.file;
+  {
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(meta + kHuffAt);
+    uint32_t* dst = reinterpret_cast<uint32_t*>(huff);
+    for (int i = lane; i < 4 * kHuffBytes / 4; i += kScanLanes) dst[i] = src[i];
+  }
+  const int* sg = reinterpret_cast<const int*>(meta + kSegAt);
+  const int bpm = f.sampling == 2 ? 6 : 3;
+  const int total = (int)f.mcux * f.mcuy;
+  const uint32_t start = (uint32_t)sg[0];
+  // the one segment must be the whole scan from MCU 0, and start inside the file behind its first byte (the cold start looks one back)
+  bool ok = sg[4] == 0 && sg[5] >= total && sg[0] >= 1 && start < f.bytes && (uint32_t)sg[1] < 8u;
+  const uint32_t shift = 31 - __clz(a.chunk_bytes);
+  const int nchunks = ok ? (int)((f.bytes - start + (uint32_t)a.chunk_bytes - 1) >> shift) : 0;
+  if (nchunks > a.chunks_cap) ok = false;
+  if (lane == 0) {
+    carry = make_int4(0, (int)(short)(sg[2] & 0xffff), (int)(short)((uint32_t)sg[2] >> 16), (int)(short)(sg[3] & 0xffff));
+    changed = 0;
+    failed = 0;
+  }
+  __syncthreads();
+  uint2* state = a.scan_state + (size_t)blockIdx.x * a.chunks_cap;
+  int* entries = a.entries + (size_t)slot * a.rows_cap * 4;
+  int rounds_max = 0;
+  for (int base = 0; ok && base < nchunks; base += kScanLanes) {
+    const int chunk = base + lane;
+    const bool active = chunk < nchunks;
+    const uint32_t first = start + ((uint32_t)chunk << shift);
+    const uint32_t chunk_end = active && first + (uint32_t)a.chunk_bytes < f.bytes ? first + (uint32_t)a.chunk_bytes : f.bytes;
+    uint2 in = make_uint2(0, 0), mine = make_uint2(0, 0);
+    if (active) {
+      if (lane == 0) in = base == 0 ? make_uint2(start, (uint32_t)sg[1]) : state[chunk - 1];
+      else in = make_uint2(first + (file[first] == 0 && file[first - 1] == 0xff ? 1u : 0u), 0u);
+    }
+    int4 acc = make_int4(0, 0, 0, 0);
+    bool err = false, redo = active;
+    int round = 0;
+    for (;; ++round) {                                          // round 0 is the cold pass
+      if (redo) {
+        bool e = false;
+        const uint2 out = scan_walk<0>(file, f.bytes, huff, f, bpm, in, chunk_end, acc, e, entries);
+        if (round == 0 || !same(out, mine)) {
+          state[chunk] = out;
+          mine = out;
+          if (round) changed = 1;
+        }
+      }
+      __syncthreads();
+      const bool ch = changed != 0;
+      if (round > 0 && (!ch || round >= a.max_rounds)) {
+        if (ch) ok = false;                                     // max_rounds rounds and the last still changed a state
+        break;
+      }
+      __syncthreads();
+      if (lane == 0) changed = 0;
+      redo = false;
+      if (active && lane > 0) {
+        const uint2 n = state[chunk - 1];
+        redo = !same(n, in);
+        in = n;
+      }
+      __syncthreads();
+    }
+    if (round > rounds_max) rounds_max = round;
+    if (!ok) break;
+    // every lane's `in` is now the serial decoder's state at its chunk's start
+    if (active) scan_walk<1>(file, f.bytes, huff, f, bpm, in, chunk_end, acc, err, entries);
+    pre[lane] = acc;
+    __syncthreads();
+    for (int d = 1; d < kScanLanes; d <<= 1) {
+      int4 v = make_int4(0, 0, 0, 0);
+      if (lane >= d) v = pre[lane - d];
+      __syncthreads();
+      int4 w = pre[lane];
+      w.x += v.x; w.y += v.y; w.z += v.z; w.w += v.w;
+      pre[lane] = w;
+      __syncthreads();
+    }
+    const int4 incl = pre[lane], c0 = carry;
+    int4 at = make_int4(c0.x + incl.x - acc.x, c0.y + incl.y - acc.y, c0.z + incl.z - acc.z, c0.w + incl.w - acc.w);
+    __syncthreads();
+    if (lane == kScanLanes - 1) carry = make_int4(c0.x + incl.x, c0.y + incl.y, c0.z + incl.z, c0.w + incl.w);
+    if (active) scan_walk<2>(file, f.bytes, huff, f, bpm, in, chunk_end, at, err, entries);
+    if (err) failed = 1;
+    __syncthreads();                                            // carry, failed and this sweep's states are in place
+  }
+  if (lane == 0) {
+    a.scan_ok[slot] = ok && !failed && carry.x == total * bpm ? 1 : 0;
+    a.scan_rounds[slot] = rounds_max;
+  }
 }
 
 // ---- pixels ------------------------------------------------------------------------------------------------------------------------------
@@ -377,12 +620,38 @@ static int dec_layout(const vp_jpegdec_desc* d, DecLayout* L) {
   return VP_OK;
 }
 
+struct ScanLayout {
+  int chunks_cap, slots;                     // chunks of the largest file; files of one launch group
+  size_t state, ok, rounds, total;
+};
+
+static int scan_layout(const vp_jpegdec_desc* d, int chunk_bytes, ScanLayout* S) {
+  DecLayout L;
+  const int rc = dec_layout(d, &L);
+  if (rc) return rc;
+  if (chunk_bytes < 32 || chunk_bytes > 4096 || (chunk_bytes & (chunk_bytes - 1))) {
+    set_err("vp_jpegdec: bad scan chunk_bytes %d (a power of two, 32 .. 4096)", chunk_bytes);
+    return VP_ERR_ARG;
+  }
+  S->chunks_cap = (d->max_file_bytes + chunk_bytes - 1) / chunk_bytes;
+  S->slots = d->max_files < VP_JPEGDEC_FILES_PER_LAUNCH ? d->max_files : VP_JPEGDEC_FILES_PER_LAUNCH;
+  size_t o = 0;
+  S->state = o; o += dec_align((size_t)S->slots * S->chunks_cap * sizeof(uint2));     // launch groups run one after another on the stream
+  S->ok = o; o += dec_align((size_t)d->max_files * sizeof(int));
+  S->rounds = o; o += dec_align((size_t)d->max_files * sizeof(int));
+  S->total = o + 256;
+  return VP_OK;
+}
+
 }  // namespace vp
 
 struct vp_jpegdec {
   vp_jpegdec_desc d;
   vp::DecLayout L;
   char* base;
+  vp::ScanLayout S;                          // the index scan: scan_base null until vp_jpegdec_enable_scan
+  char* scan_base;
+  int chunk_bytes, max_rounds;
 };
 
 using namespace vp;
@@ -407,7 +676,27 @@ int vp_jpegdec_create(const vp_jpegdec_desc* d, void* workspace, size_t bytes, v
   if (!h) { set_err("vp_jpegdec_create: out of host memory"); return VP_ERR_STATE; }
   h->d = *d; h->L = L;
   h->base = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  h->scan_base = nullptr;
   *out = h;
+  return VP_OK;
+}
+
+size_t vp_jpegdec_scan_workspace_bytes(const vp_jpegdec_desc* d, int chunk_bytes) {
+  ScanLayout S;
+  return scan_layout(d, chunk_bytes, &S) ? 0 : S.total;
+}
+
+int vp_jpegdec_enable_scan(vp_jpegdec_t* h, void* scan_workspace, size_t bytes, int chunk_bytes, int max_rounds) {
+  if (!h) { set_err("vp_jpegdec_enable_scan: bad argument"); return VP_ERR_ARG; }
+  ScanLayout S;
+  const int rc = scan_layout(&h->d, chunk_bytes, &S);
+  if (rc) return rc;
+  if (max_rounds < 1 || max_rounds > 1024) { set_err("vp_jpegdec_enable_scan: bad max_rounds %d (1 .. 1024)", max_rounds); return VP_ERR_ARG; }
+  if (!scan_workspace || bytes < S.total) { set_err("vp_jpegdec_enable_scan: workspace too small (%zu of %zu bytes)", bytes, S.total); return VP_ERR_WORKSPACE; }
+  h->S = S;
+  h->scan_base = (char*)(((uintptr_t)scan_workspace + 255) & ~(uintptr_t)255);
+  h->chunk_bytes = chunk_bytes;
+  h->max_rounds = max_rounds;
   return VP_OK;
 }
 
@@ -440,6 +729,10 @@ int vp_jpegdec_decode(vp_jpegdec_t* h, const unsigned char* blob, const vp_jpegd
   const DecLayout& L = h->L;
   hipStream_t st = (hipStream_t)stream;
   VP_HIP_CHECK(hipMemsetAsync(status, 0, (size_t)n * sizeof(int), st));
+  if (h->scan_base) {                             // 0 for every file the scan does not run on
+    VP_HIP_CHECK(hipMemsetAsync(h->scan_base + h->S.ok, 0, (size_t)n * sizeof(int), st));
+    VP_HIP_CHECK(hipMemsetAsync(h->scan_base + h->S.rounds, 0, (size_t)n * sizeof(int), st));
+  }
   for (int i0 = 0; i0 < n; i0 += VP_JPEGDEC_FILES_PER_LAUNCH) {
     const int m = n - i0 < VP_JPEGDEC_FILES_PER_LAUNCH ? n - i0 : VP_JPEGDEC_FILES_PER_LAUNCH;
     DecArgs a;
@@ -450,7 +743,13 @@ int vp_jpegdec_decode(vp_jpegdec_t* h, const unsigned char* blob, const vp_jpegd
     a.planes = (unsigned char*)(h->base + L.planes);
     a.out = out; a.status = status; a.row_pitch = row_pitch; a.frame_stride = frame_stride;
     a.first = i0; a.blocks_cap = L.blocks_cap; a.rows_cap = L.rows_cap; a.Hp = L.Hp; a.Wp = L.Wp; a.bgr = d.bgr;
-    int max_seg = 1, max_blocks = 1, max_groups = 1;
+    if (h->scan_base) {
+      a.scan_state = (uint2*)(h->scan_base + h->S.state);
+      a.scan_ok = (int*)(h->scan_base + h->S.ok);
+      a.scan_rounds = (int*)(h->scan_base + h->S.rounds);
+      a.chunk_bytes = h->chunk_bytes; a.chunks_cap = h->S.chunks_cap; a.max_rounds = h->max_rounds;
+    }
+    int max_seg = 1, max_blocks = 1, max_groups = 1, scans = 0;
     for (int i = 0; i < m; ++i) {
       const vp_jpegdec_file& f = files[i0 + i];
       DecFile& g = a.f[i];
@@ -464,9 +763,18 @@ int vp_jpegdec_decode(vp_jpegdec_t* h, const unsigned char* blob, const vp_jpegd
       for (int c = 0; c < 3; ++c) { g.tq[c] = f.tq[c]; g.td[c] = f.td[c]; g.ta[c] = f.ta[c]; }
       const int blocks = (int)g.mcux * g.mcuy * (f.sampling == 2 ? 6 : 3);
       const int groups = ((f.width + 3) / 4) * f.height;
+      if (h->scan_base && f.n_segments == 1 && f.restart_interval == 0 && g.mcuy >= 2) {      // whether its segment is the whole scan: the kernel
+        g.scan = 1;
+        ++scans;
+        if (g.mcuy > max_seg) max_seg = g.mcuy;
+      }
       if (f.n_segments > max_seg) max_seg = f.n_segments;
       if (blocks > max_blocks) max_blocks = blocks;
       if (groups > max_groups) max_groups = groups;
+    }
+    if (scans) {
+      hipLaunchKernelGGL(jpegdec_scan_kernel, dim3(m), dim3(kScanLanes), 0, st, a);
+      VP_HIP_CHECK(hipGetLastError());
     }
     hipLaunchKernelGGL(jpegdec_entropy_kernel, dim3((max_seg + kLanes - 1) / kLanes, m), dim3(kLanes), 0, st, a);
     VP_HIP_CHECK(hipGetLastError());
@@ -486,7 +794,11 @@ int vp_jpegdec_tensor(vp_jpegdec_t* h, const char* name, void** ptr, int64_t sha
   if (s == "coefficients") { *ptr = h->base + L.coef; shp[1] = L.blocks_cap; shp[2] = 64; }
   else if (s == "entries") { *ptr = h->base + L.entries; shp[1] = L.rows_cap; shp[2] = 4; }
   else if (s == "planes") { *ptr = h->base + L.planes; shp[1] = 3; shp[2] = L.Hp; shp[3] = L.Wp; }
-  else { set_err("vp_jpegdec_tensor: no tensor '%s' (coefficients, entries, planes)", name); return VP_ERR_ARG; }
+  else if (s == "scan_ok" || s == "scan_rounds") {
+    if (!h->scan_base) { set_err("vp_jpegdec_tensor: '%s' needs vp_jpegdec_enable_scan", name); return VP_ERR_ARG; }
+    *ptr = h->scan_base + (s == "scan_ok" ? h->S.ok : h->S.rounds); shp[1] = 1; shp[2] = 1;
+  }
+  else { set_err("vp_jpegdec_tensor: no tensor '%s' (coefficients, entries, planes, scan_ok, scan_rounds)", name); return VP_ERR_ARG; }
   if (shape) for (int i = 0; i < 4; ++i) shape[i] = shp[i];
   return VP_OK;
 }

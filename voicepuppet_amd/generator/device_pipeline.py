@@ -70,9 +70,12 @@ class FramePrefetcher:
   follows.  The decoder's status and entry points are copied to pinned memory behind it and looked at three batches later (when the
   decoder's staging buffer is reused, long after they arrived): a file that did not decode raises RuntimeError naming it; no host wait
   is added.  segments_used: the segment count per file of the last compressed batch filled (0: a frame that came decoded).
+  device_jpeg_scan: None, or the chunk bytes of the decoder's index scan (JpegDecoder(scan_chunk_bytes=...)): a file then runs one
+  lane per MCU row in the batch that first sees it.  segments_used is then a lazy read-only property: it is resolved from the decoder's
+  last call when it is read (a host wait for that call), not a snapshot taken when the batch was filled.
   """
 
-  def __init__(self, source, batch, img_size, depth=2, device=None):
+  def __init__(self, source, batch, img_size, depth=2, device=None, device_jpeg_scan=None):
     self.source = iter(source)
     self.device = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
     # the process's fourth executor stream (include/vp_hip.h vp_host_stream): the training engine beside this prefetcher keeps to three
@@ -92,7 +95,8 @@ class FramePrefetcher:
     self.head = self.tail = 0
     self.batch, self.img_size = batch, img_size
     self.decoder = None                               # JpegDecoder of 2 * batch files, made by the first CompressedBatch
-    self.segments_used = []
+    self.device_jpeg_scan = device_jpeg_scan
+    self._segments_used = []
     self._copied = []                                 # copy-done events of the last batches whose sources were read in place
     for _ in range(depth):
       self._fill()
@@ -148,7 +152,7 @@ class FramePrefetcher:
     N, S = self.batch, self.img_size
     if self.decoder is None:
       from ..jpeg_dec import JpegDecoder
-      self.decoder = JpegDecoder(2 * N, S, 3 * S, bgr=True)
+      self.decoder = JpegDecoder(2 * N, S, 3 * S, bgr=True, scan_chunk_bytes=self.device_jpeg_scan)
       self._status = torch.empty(2 * N, dtype=torch.int32, device=self.device)
     if "frames" not in slot:                          # ex and cur as the two halves of one tensor: one decode call fills both
       slot["frames"] = torch.empty(2, N, S, 3 * S, 3, dtype=torch.uint8, device=self.device)
@@ -174,15 +178,19 @@ class FramePrefetcher:
       if any(it is not None for it in items):
         flat = frames.view(2 * N, S, 3 * S, 3)
         self.decoder.decode_into(items, flat, flat.stride(1), flat.stride(0), self._status)
-        self.segments_used = list(self.decoder.last_segments)
+        self._segments_used = None                    # the decoder's last call: resolved when asked for
       else:
-        self.segments_used = [0] * (2 * N)
+        self._segments_used = [0] * (2 * N)
       ev = torch.cuda.Event()
       ev.record(self.stream)
       self._copied = self._copied[-2:] + [ev]
       slot["src"] = [crops]
       slot["packer"](frames[0], frames[1], slot["dev"][2])
       slot["ready"].record(self.stream)
+
+  @property
+  def segments_used(self):
+    return list(self.decoder.last_segments) if self._segments_used is None else self._segments_used
 
   def next(self):
     if self.tail == self.head:

@@ -374,6 +374,10 @@ class PixReferDataGenerator(DataGenerator):
     # amd: {device_jpeg_decode: true}: the device pipeline hands over the .jpg files themselves (voicepuppet_amd/jpeg_dec.py)
     # (force_device_jpeg_decode: the launcher's --device_jpeg_decode, which overrides the key)
     self.device_jpeg_decode = getattr(self, 'force_device_jpeg_decode', False) or amd.get('device_jpeg_decode', False) in (True, 'true', 'yes', 1)
+    # amd: {device_jpeg_scan: <chunk bytes>}: the decoder's index scan; 0: off.  force_device_jpeg_scan (the launcher's
+    # --device_jpeg_scan) overrides the key whenever it is given, a 0 included
+    forced = getattr(self, 'force_device_jpeg_scan', None)
+    self.device_jpeg_scan = int((forced if forced is not None else amd.get('device_jpeg_scan', 0)) or 0)
 
   def _load_triptych(self, image_loader, path):
     """jpg (S x 3S BGR) -> random square crop + resize of the three panels -> [S, 3S, 3] RGB float."""
@@ -537,7 +541,8 @@ class _DeviceFrameIterator(object):
   def next_batch(self):
     if self._pf is None:
       from .device_pipeline import FramePrefetcher
-      self._pf = FramePrefetcher(self._batches(), self.ds.batch_size, self.ds.owner.img_size)
+      self._pf = FramePrefetcher(self._batches(), self.ds.batch_size, self.ds.owner.img_size,
+                                 device_jpeg_scan=self.ds.owner.device_jpeg_scan or None)
     return self._pf.next()
 
 

@@ -8,6 +8,12 @@ one pinned buffer, copies it once and enqueues the decode; it never waits in dec
 Segments.  A file with restart markers is decoded one lane per interval, a file without them by one lane - and every decode records, per
 MCU row, where the lane stood (`entries`).  Those records are the file's entry-point index: pure data, kept in a cache keyed by (path,
 size, mtime); the next decode of the file runs one lane per MCU row.  save_index / load_index keep the cache in one .npz.
+
+Index scan (JpegDecoder(scan_chunk_bytes=N), off by default).  The first decode of a file without restart markers then finds the entry
+points on the device, in the same call and in front of the entropy kernel (vp_jpegdec_enable_scan, include/vp_hip.h): one workgroup per
+file decodes chunks of N file bytes from guessed states and repeats "chunk i from the exit of chunk i - 1" until nothing changes.  A
+file whose scan held is decoded one lane per MCU row at first sight; one whose scan did not hold (rounds exhausted, damaged data) by one
+lane as before.  The entries recorded are the same either way, so the cache and the .npz are filled as before.
 """
 import ctypes
 import functools
@@ -215,11 +221,20 @@ def _key(path):
 
 class JpegDecoder:
   """decode(files) -> (uint8 [n, max_height, max_width, 3] device, status int32 [n] device), files being bytes or paths.  A path's decode
-  feeds the index cache and uses it from its second decode on.  last_segments: the segment count of every file of the last call."""
+  feeds the index cache and uses it from its second decode on.  last_segments: the segment count of every file of the last call.  It is
+  a read-only property and, with the index scan enabled, a lazy one: the count of a scanned file (its MCU rows, or 1) is the device's
+  verdict, so reading it waits for that call's event, and it speaks of whatever call is the last when it is read.  Without the scan
+  it is the list the host packed, as before.  Nothing on the training path reads it.
+  scan_chunk_bytes: None, or the chunk size of the device index scan (a power of two, 32 .. 4096; 128 suits training triptychs);
+  scan_max_rounds bounds its fixed-point rounds per sweep.  The default is 512, not the 32 first pencilled in: files of dense noise
+  synchronise slowly (tests/test_jpeg_scan_host.py counts up to 209 rounds at 32-byte chunks, profiles/jpeg_scan.json), and a lane
+  whose input did not change does not decode again, so late rounds cost little.  last_scan_rounds: the rounds per file of the last
+  harvested call (0: not scanned)."""
 
   RING = 3          # staging buffers: one stays untouched until two calls later (the prefetcher's contract for pinned memory)
 
-  def __init__(self, max_files, max_height, max_width, bgr=True, max_file_bytes=1 << 22, max_segments_per_file=1 << 16):
+  def __init__(self, max_files, max_height, max_width, bgr=True, max_file_bytes=1 << 22, max_segments_per_file=1 << 16,
+               scan_chunk_bytes=None, scan_max_rounds=512):
     if not torch.cuda.is_available():
       raise RuntimeError("JpegDecoder needs an MI355X (no CPU fallback)")
     self.L = _lib.lib()
@@ -233,8 +248,18 @@ class JpegDecoder:
     h = ctypes.c_void_p()
     _lib.check(self.L.vp_jpegdec_create(ctypes.byref(self.desc), _ptr(self.workspace), ws, ctypes.byref(h)), "vp_jpegdec_create")
     self.h = h
+    self.scan_chunk_bytes, self.scan_max_rounds, self.scan_workspace = None, None, None
+    if scan_chunk_bytes is not None:
+      sws = self.L.vp_jpegdec_scan_workspace_bytes(ctypes.byref(self.desc), int(scan_chunk_bytes))
+      if sws == 0:
+        raise ValueError("invalid JPEG index scan setting: " + self.L.vp_last_error().decode())
+      self.scan_workspace = torch.empty(sws, dtype=torch.uint8, device="cuda")
+      _lib.check(self.L.vp_jpegdec_enable_scan(self.h, _ptr(self.scan_workspace), sws, int(scan_chunk_bytes), int(scan_max_rounds)),
+                 "vp_jpegdec_enable_scan")
+      self.scan_chunk_bytes, self.scan_max_rounds = int(scan_chunk_bytes), int(scan_max_rounds)
     self.index = {}                 # (path, size, mtime_ns) -> int32 [mcuy, 4]
-    self.last_segments = []
+    self.last_scan_rounds = []
+    self._last = ([], None)         # the last call's segment counts as packed, and (event, pinned scan_ok, MCU rows) with the scan
     self._ring = [None] * self.RING
     self._turn = 0
     self._pending = [None] * self.RING
@@ -254,6 +279,15 @@ class JpegDecoder:
       self.index[(str(p), int(s), int(m))] = z["entries"][at:at + int(r)].copy()
       at += int(r)
 
+  @property
+  def last_segments(self):
+    segs, scan = self._last
+    if scan is None:
+      return segs
+    event, ok, rows = scan
+    event.synchronize()
+    return [rows[i] if ok[i] else s for i, s in enumerate(segs)]
+
   def harvest(self, slot=None):
     """Reads the status and entries earlier decode_into calls left in pinned memory (of staging slot `slot`, or of all: waits for their
     events, long completed when a slot is refilled) -> the names of the files whose status was not 0.  Their entries are dropped, the
@@ -262,9 +296,11 @@ class JpegDecoder:
     for k in (range(self.RING) if slot is None else [slot]):
       if self._pending[k] is None:
         continue
-      event, status, entries, keys, rows, names = self._pending[k]
+      event, status, entries, keys, rows, names, scan_rounds = self._pending[k]
       self._pending[k] = None
       event.synchronize()
+      if scan_rounds is not None:
+        self.last_scan_rounds = scan_rounds.numpy()[:len(keys)].tolist()
       st, en = status.numpy(), entries.numpy()
       for i, key in enumerate(keys):
         if names[i] is None:
@@ -278,10 +314,13 @@ class JpegDecoder:
   # ---- decoding ----
   def tensor(self, name):
     """'coefficients' int16 [max_files, blocks, 64], 'entries' int32 [max_files, rows, 4], 'planes' uint8 [max_files, 3, Hp, Wp]: views of
-    the workspace, rows in the order of the last decode."""
+    the workspace, rows in the order of the last decode.  With the index scan 'scan_ok' and 'scan_rounds', int32 [max_files]."""
     p, shp = ctypes.c_void_p(), (ctypes.c_int64 * 4)()
     _lib.check(self.L.vp_jpegdec_tensor(self.h, name.encode(), ctypes.byref(p), shp), "vp_jpegdec_tensor")
     shape = [int(v) for v in shp]
+    if name in ("scan_ok", "scan_rounds"):
+      off = p.value - self.scan_workspace.data_ptr()
+      return self.scan_workspace[off:off + 4 * shape[0]].view(torch.int32)
     dtype = {"coefficients": torch.int16, "entries": torch.int32, "planes": torch.uint8}[name]
     off = p.value - self.workspace.data_ptr()
     n = int(np.prod(shape)) * torch.empty(0, dtype=dtype).element_size()
@@ -324,7 +363,8 @@ class JpegDecoder:
       cap = max(at, 1 << 16) * 3 // 2
       ring = (torch.empty(cap, dtype=torch.uint8).pin_memory(), torch.empty(cap, dtype=torch.uint8, device="cuda"),
               torch.empty(self.max_files, dtype=torch.int32).pin_memory(),
-              torch.empty(self.tensor("entries").shape, dtype=torch.int32).pin_memory())
+              torch.empty(self.tensor("entries").shape, dtype=torch.int32).pin_memory(),
+              torch.empty(2, self.max_files, dtype=torch.int32).pin_memory())          # scan_ok, scan_rounds
       self._ring[slot] = ring
     ring[0].numpy()[:at] = np.frombuffer(b"".join(parts), np.uint8)
     return slot, table, at, segments, items, bad
@@ -334,17 +374,22 @@ class JpegDecoder:
     and entries back to pinned memory, all on the current stream; no wait."""
     slot, table, at, segments, items, bad = packed
     n = len(items)
-    pinned, dev, st_host, en_host = self._ring[slot]
-    self.last_segments = segments
+    pinned, dev, st_host, en_host, scan_host = self._ring[slot]
     dev[:at].copy_(pinned[:at], non_blocking=True)
     _lib.check(self.L.vp_jpegdec_decode(self.h, _ptr(dev), table, n, _ptr(out), int(row_pitch), int(frame_stride), _ptr(status), _stream()),
                "vp_jpegdec_decode")
     st_host[:n].copy_(status[:n], non_blocking=True)
     en_host[:n].copy_(self.tensor("entries")[:n], non_blocking=True)
+    scan = self.scan_chunk_bytes is not None
+    if scan:
+      scan_host[0, :n].copy_(self.tensor("scan_ok")[:n], non_blocking=True)
+      scan_host[1, :n].copy_(self.tensor("scan_rounds")[:n], non_blocking=True)
     event = torch.cuda.Event()
     event.record()
-    self._pending[slot] = (event, st_host, en_host, [it and it[2] for it in items], [it and it[1].mcuy for it in items],
-                           [it and it[4] for it in items])
+    rows = [it and it[1].mcuy for it in items]
+    self._last = (segments, (event, scan_host[0].numpy(), rows) if scan else None)
+    self._pending[slot] = (event, st_host, en_host, [it and it[2] for it in items], rows, [it and it[4] for it in items],
+                           scan_host[1] if scan else None)
     if bad and raise_bad:
       raise RuntimeError("corrupt JPEG data in %s" % ", ".join(str(b) for b in bad))
 

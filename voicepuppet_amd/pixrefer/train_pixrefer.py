@@ -38,7 +38,8 @@ def save_image(path, arr):
   Image.fromarray((np.clip(arr, 0, 1) * 255).astype(np.uint8)).save(path)
 
 
-def main(argv=None):
+def parse_options(argv=None):
+  """the command line -> optparse's options"""
   cmd_parser = OptionParser(usage="usage: %prog [options] --config_path <>")
   cmd_parser.add_option('--config_path', type="string", dest="config_path", help='the config yaml file')
   cmd_parser.add_option('--steps', type="int", dest="steps", default=None, help='iterations to run (default: training.epochs)')
@@ -47,7 +48,18 @@ def main(argv=None):
   cmd_parser.add_option('--resume', action="store_true", dest="resume", default=False, help='restore the latest checkpoint of save_dir')
   cmd_parser.add_option('--device_jpeg_decode', action="store_true", dest="device_jpeg_decode", default=False,
                         help='decode the training .jpg files on the device (overrides amd.device_jpeg_decode)')
-  opts, _ = cmd_parser.parse_args(argv)
+  cmd_parser.add_option('--device_jpeg_scan', type="int", dest="device_jpeg_scan", default=None, metavar="N",
+                        help='with --device_jpeg_decode: find a file\'s MCU-row entry points on the device at first sight, in chunks '
+                             'of N bytes, 128 when no N follows (overrides amd.device_jpeg_scan)')
+  argv = list(sys.argv[1:] if argv is None else argv)
+  for i, a in enumerate(argv):                     # --device_jpeg_scan [N]: the bare flag means 128
+    if a == '--device_jpeg_scan' and not (i + 1 < len(argv) and argv[i + 1].isdigit()):
+      argv[i] = '--device_jpeg_scan=128'
+  return cmd_parser.parse_args(argv)[0]
+
+
+def main(argv=None):
+  opts = parse_options(argv)
 
   if (opts.config_path is None):
     logger.error('Please check your parameters.')
@@ -77,6 +89,8 @@ def main(argv=None):
     params.img_size = opts.img_size
   if opts.device_jpeg_decode:
     train_generator.force_device_jpeg_decode = True
+  if opts.device_jpeg_scan is not None:
+    train_generator.force_device_jpeg_scan = opts.device_jpeg_scan
   train_generator.set_params(params)
   # the per-sample crop / resize / packing on the device, decoded uint8 frames copied under the previous step;
   # amd: {device_input_pipeline: false} in params.yml restores the reference's host pipeline
