@@ -19,6 +19,7 @@
  *   vp_jpeg_*          replaces  infer_bfmvid.py:243-244 (cv2.imwrite per frame) with a baseline JPEG encode on the device
  *   vp_jpegdec_*       replaces  generator/generator.py:956-1019 (cv2.imread per sample) and loader.py ImageLoader with a baseline JPEG decode on the device
  *   vp_pcmin_*         replaces  generator/loader.py:39-54 (WavLoader: scale, channel mean, resample_poly over a whole file) for live PCM
+ *   vp_frame_metrics_* replaces  nothing: the reference has no image-quality measure (L1, PSNR and SSIM per frame pair, on the device)
  *
  * Conventions: every function returns 0 on success and a negative vp_status otherwise (never throws);
  * all tensor pointers are DEVICE pointers owned by the caller (NHWC, row-major); nothing is allocated
@@ -875,6 +876,59 @@ int vp_jpegdec_tensor(vp_jpegdec_t* h, const char* name, void** ptr, int64_t sha
  * that was not scanned: "scan_ok", and "scan_rounds", the most rounds a sweep of the file took (the last, unchanged round included). */
 size_t vp_jpegdec_scan_workspace_bytes(const vp_jpegdec_desc* d, int chunk_bytes);
 int vp_jpegdec_enable_scan(vp_jpegdec_t* h, void* scan_workspace, size_t scan_workspace_bytes, int chunk_bytes, int max_rounds);
+
+/* ------------------------------------------------------------------------------------------------
+ * Frame quality metrics on the device: per frame pair mean |a - b|, mean (a - b)^2, PSNR and SSIM of two batches of three-channel NHWC
+ * (interleaved) frames that are already on the device (decoded dataset frames, generator output, emitted uint8 frames).  The reference has
+ * no counterpart.  csrc/frame_metrics.hip; tests/frame_metrics_ref.py restates the definition in float64 numpy.
+ *
+ * Values are in [0, 255]: uint8 as is; float32 x mapped v = min(max(x * scale + offset, 0), 255) in double, no rounding (scale = offset =
+ * 127.5 takes the generator's [-1, 1] output; a NaN maps to 0).
+ *   L1    sum |a - b| / (3 H W)
+ *   MSE   sum (a - b)^2 / (3 H W)
+ *   PSNR  10 log10(255^2 / MSE) dB, +inf at MSE == 0
+ *   SSIM  Wang, Bovik, Sheikh & Simoncelli 2004, per channel on the values in [0, 255].  Window: 11 x 11 Gaussian of sigma 1.5, the outer
+ *         product of the 11-tap vector g[i] = exp(-(i - 5)^2 / (2 sigma^2)) normalised to sum 1 (computed in double on the host and
+ *         handed to the kernel).  Per window, with E[.] the weighted mean: mu_a = E[a], mu_b = E[b], var_a = E[a^2] - mu_a^2,
+ *         var_b = E[b^2] - mu_b^2, cov = E[a b] - mu_a mu_b (weighted population moments, no Bessel factor);
+ *         S = (2 mu_a mu_b + C1)(2 cov + C2) / ((mu_a^2 + mu_b^2 + C1)(var_a + var_b + C2)), C1 = (0.01 * 255)^2, C2 = (0.03 * 255)^2.
+ *         Only the (H - 10) x (W - 10) windows that lie wholly inside the image; SSIM is the mean of S over those windows and the three
+ *         channels.  This is skimage.metrics.structural_similarity(a, b, gaussian_weights=True, use_sample_covariance=False,
+ *         data_range=255, channel_axis=-1).  height < 11 or width < 11 is refused.
+ * Arithmetic: all moments and S in float64 (E[x^2] - mu^2 cancels at 65025 against C2 = 58.5).  For uint8 input sum |a - b| and
+ * sum (a - b)^2 are integers and exact.  No floating-point atomics: one workgroup per tile of 16 x 16 windows and frame writes its partial
+ * sums to the workspace, a second kernel adds a frame's tiles in a fixed order (lane l of 256 adds tiles l, l + 256, ... in index order,
+ * then a fixed tree over the lanes), so a frame's numbers depend on neither scheduling nor the other frames of the call.
+ * ---------------------------------------------------------------------------------------------- */
+#define VP_FRAME_METRICS_MAX_FRAMES 4096
+typedef struct vp_frame_metrics_desc {
+  uint32_t struct_bytes;          /* sizeof(vp_frame_metrics_desc) of the caller's build: must equal vp_frame_metrics_desc_size() */
+  int32_t max_frames;             /* frame pairs per call: 1 .. VP_FRAME_METRICS_MAX_FRAMES */
+  int32_t max_height;             /* 11 .. 8192 */
+  int32_t max_width;              /* 11 .. 8192 */
+} vp_frame_metrics_desc;
+size_t vp_frame_metrics_desc_size(void);
+typedef struct vp_frame_metrics vp_frame_metrics_t;
+/* 0 on a refused descriptor (vp_last_error names the field) */
+size_t vp_frame_metrics_workspace_bytes(const vp_frame_metrics_desc* d);
+/* Host only: touches no device memory.  workspace: DEVICE memory the caller keeps alive as long as the handle. */
+int vp_frame_metrics_create(const vp_frame_metrics_desc* d, void* workspace, size_t workspace_bytes, vp_frame_metrics_t** out);
+void vp_frame_metrics_destroy(vp_frame_metrics_t* h);
+/* a, b: DEVICE uint8, frame f's value (y, x, c) at p + f * frame_stride + y * row_pitch + 3 x + c; pitches and strides in bytes and
+ * independent for the two operands (a padded vp_jpegdec_decode output against a dense tensor).  Only the n x height x width x 3 values
+ * are read.  out: DEVICE float64 [n][4]: L1, MSE, PSNR, SSIM.  Refused, before anything is enqueued (vp_last_error names the reason):
+ * n outside 1 .. max_frames, height or width under 11 or over the descriptor's, row_pitch < 3 * width, frame_stride <
+ * (height - 1) * row_pitch + 3 * width, more than 2^23 tiles of 16 x 16 windows in one call (64 frames of 8192 x 8192: split the batch).
+ * Also refused: out off an 8-byte boundary, a row_pitch over 2^40 or a frame_stride over 2^48 bytes.
+ * Two launches on `stream`; never waits, never allocates. */
+int vp_frame_metrics_u8(vp_frame_metrics_t* h, const unsigned char* a, size_t a_row_pitch, size_t a_frame_stride, const unsigned char* b,
+                        size_t b_row_pitch, size_t b_frame_stride, int n, int height, int width, double* out, void* stream);
+/* The same for float32 elements (pointers, pitches and strides multiples of 4 bytes, a row 12 * width bytes), mapped as above. */
+int vp_frame_metrics_f32(vp_frame_metrics_t* h, const float* a, size_t a_row_pitch, size_t a_frame_stride, const float* b, size_t b_row_pitch,
+                         size_t b_frame_stride, int n, int height, int width, double scale, double offset, double* out, void* stream);
+/* "abs_sum", "sq_sum": int64 [max_frames], sum |a - b| and sum (a - b)^2 of the frames of the last vp_frame_metrics_u8 call (a
+ * vp_frame_metrics_f32 call leaves them alone).  shape[0] = max_frames. */
+int vp_frame_metrics_tensor(vp_frame_metrics_t* h, const char* name, void** ptr, int64_t shape[4]);
 
 /* Host helper: CRC-32C (Castagnoli, the checksum of TensorFlow checkpoint bundles) of `n` bytes, continuing from `crc` (0 to start). */
 unsigned vp_crc32c(const void* data, size_t n, unsigned crc);

@@ -82,6 +82,13 @@ PCMIN_MAX_SLOTS, PCMIN_MAX_CHANNELS = 128, 8      # include/vp_hip.h VP_PCMIN_MA
 PCM_S16, PCM_F32 = 0, 1
 
 
+class FrameMetricsDesc(ctypes.Structure):
+  _fields_ = [("struct_bytes", ctypes.c_uint32), ("max_frames", ctypes.c_int32), ("max_height", ctypes.c_int32), ("max_width", ctypes.c_int32)]
+
+
+FRAME_METRICS_MAX_FRAMES = 4096      # include/vp_hip.h VP_FRAME_METRICS_MAX_FRAMES
+
+
 class BfmModel(ctypes.Structure):
   _fields_ = [("nver", ctypes.c_int), ("ntri", ctypes.c_int), ("meanshape", ctypes.c_void_p), ("idBase", ctypes.c_void_p),
               ("exBase", ctypes.c_void_p), ("meantex", ctypes.c_void_p), ("texBase", ctypes.c_void_p), ("tri", ctypes.c_void_p),
@@ -226,6 +233,15 @@ _SIGNATURES = {
     "vp_pcmin_open_slot": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P]),
     "vp_pcmin_ready": (ctypes.c_longlong, [_P, ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_longlong)]),
     "vp_pcmin_push": (ctypes.c_int, [_P, _P, ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_int), _P, _P]),
+    "vp_frame_metrics_desc_size": (ctypes.c_size_t, []),
+    "vp_frame_metrics_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(FrameMetricsDesc)]),
+    "vp_frame_metrics_create": (ctypes.c_int, [ctypes.POINTER(FrameMetricsDesc), _P, ctypes.c_size_t, ctypes.POINTER(_P)]),
+    "vp_frame_metrics_destroy": (None, [_P]),
+    "vp_frame_metrics_u8": (ctypes.c_int, [_P, _P, ctypes.c_size_t, ctypes.c_size_t, _P, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int, ctypes.c_int,
+                                           ctypes.c_int, _P, _P]),
+    "vp_frame_metrics_f32": (ctypes.c_int, [_P, _P, ctypes.c_size_t, ctypes.c_size_t, _P, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int, ctypes.c_int,
+                                            ctypes.c_int, ctypes.c_double, ctypes.c_double, _P, _P]),
+    "vp_frame_metrics_tensor": (ctypes.c_int, [_P, ctypes.c_char_p, ctypes.POINTER(_P), ctypes.POINTER(ctypes.c_int64)]),
     "vp_bfm_reconstruct_rows": (ctypes.c_int, [ctypes.POINTER(BfmModel), _P, _P, ctypes.c_int, _P, ctypes.c_int, _P, _P, _P, _P, ctypes.c_size_t, _P]),
     "vp_bfmstream_group_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(BfmStreamGroupDesc)]),
     "vp_bfmstream_group_plan_info": (ctypes.c_int, [ctypes.POINTER(BfmStreamGroupDesc), ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
@@ -345,6 +361,10 @@ def lib():
       want = int(l.vp_pcmin_desc_size())
       if want != ctypes.sizeof(PcmInDesc):
         raise RuntimeError("%s: vp_pcmin_desc is %d bytes in the library, %d in this binding" % (LIB_PATH, want, ctypes.sizeof(PcmInDesc)))
+    if hasattr(l, "vp_frame_metrics_desc_size") and l.vp_frame_metrics_desc_size.argtypes is not None:
+      want = int(l.vp_frame_metrics_desc_size())
+      if want != ctypes.sizeof(FrameMetricsDesc):
+        raise RuntimeError("%s: vp_frame_metrics_desc is %d bytes in the library, %d in this binding" % (LIB_PATH, want, ctypes.sizeof(FrameMetricsDesc)))
     _lib = l
   return _lib
 

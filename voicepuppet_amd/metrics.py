@@ -1,0 +1,99 @@
+"""Frame quality metrics on the device (libvp_hip.so: vp_frame_metrics_*, csrc/frame_metrics.hip): per frame pair L1, MSE, PSNR and SSIM of
+two batches of three-channel NHWC frames that are already on the device.  include/vp_hip.h defines the numbers (SSIM: Wang et al. 2004,
+skimage's structural_similarity with gaussian_weights=True, use_sample_covariance=False, data_range=255, channel_axis=-1).
+
+compare only enqueues on the current stream and returns a device float64 [n, 4] tensor; compare(...).cpu() is the host read.
+"""
+import ctypes
+
+import torch
+
+from . import _lib
+
+L1, MSE, PSNR, SSIM = 0, 1, 2, 3
+COLUMNS = ("L1", "MSE", "PSNR", "SSIM")
+# value_range -> (scale, offset) of v = x * scale + offset; (0, 1) is the deprocessed generator output (bench.py --dump-outputs)
+VALUE_RANGES = {(-1, 1): (127.5, 127.5), (0, 255): (1.0, 0.0), (0, 1): (255.0, 0.0)}
+
+
+def _ptr(t):
+  return ctypes.c_void_p(t.data_ptr())
+
+
+def _stream():
+  return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def frame_metrics_desc(max_frames, max_height, max_width):
+  return _lib.FrameMetricsDesc(ctypes.sizeof(_lib.FrameMetricsDesc), int(max_frames), int(max_height), int(max_width))
+
+
+class FrameMetrics:
+  """compare(a, b) for device tensors [n, H, W, 3], both uint8 or both float32, n <= max_frames, 11 <= H <= max_height, 11 <= W <= max_width
+  -> device float64 [n, 4], columns L1, MSE, PSNR, SSIM (the module's constants).  Strided views are taken as they are when a pixel's three
+  values and a row's pixels are adjacent (stride 1 and 3 on the last two axes): a padded decoder output against a dense tensor."""
+
+  def __init__(self, max_frames, max_height, max_width):
+    if not torch.cuda.is_available():
+      raise RuntimeError("FrameMetrics needs an MI355X (no CPU fallback)")
+    self.L = _lib.lib()
+    self.desc = frame_metrics_desc(max_frames, max_height, max_width)
+    ws = self.L.vp_frame_metrics_workspace_bytes(ctypes.byref(self.desc))
+    if ws == 0:
+      raise ValueError("invalid frame metrics descriptor: " + self.L.vp_last_error().decode())
+    self.max_frames, self.max_height, self.max_width = int(max_frames), int(max_height), int(max_width)
+    self.workspace = torch.empty(ws, dtype=torch.uint8, device="cuda")
+    h = ctypes.c_void_p()
+    _lib.check(self.L.vp_frame_metrics_create(ctypes.byref(self.desc), _ptr(self.workspace), ws, ctypes.byref(h)), "vp_frame_metrics_create")
+    self.h = h
+
+  @staticmethod
+  def _layout(t, name):
+    """(row pitch, frame stride) in bytes of a [n, H, W, 3] view"""
+    n, H, W, C = t.shape
+    e = t.element_size()
+    if t.stride(3) != 1 or t.stride(2) != 3 or t.stride(1) < 3 * W or (n > 1 and t.stride(0) < (H - 1) * t.stride(1) + 3 * W):
+      raise ValueError("compare: %s has strides %s: a pixel's values and a row's pixels must be adjacent, rows and frames must not overlap"
+                       % (name, tuple(t.stride())))
+    pitch = t.stride(1) * e
+    return pitch, max(t.stride(0) * e, (H - 1) * pitch + 3 * W * e)       # a single frame's stride(0) is arbitrary
+
+  def compare(self, a, b, value_range=(-1, 1), out=None):
+    """value_range: of float32 operands, (-1, 1) (the generator's output), (0, 255) or (0, 1); values outside are clamped.  uint8 ignores it.
+    out: a contiguous device float64 [>= n, 4] to write into; allocated when None."""
+    if a.dim() != 4 or a.shape[3] != 3 or a.shape != b.shape or a.dtype != b.dtype or not (a.is_cuda and b.is_cuda) \
+       or a.dtype not in (torch.uint8, torch.float32):
+      raise ValueError("compare: two device tensors [n, H, W, 3] of the same shape, both uint8 or both float32")
+    n, H, W = int(a.shape[0]), int(a.shape[1]), int(a.shape[2])
+    ap, as_ = self._layout(a, "a")
+    bp, bs = self._layout(b, "b")
+    if out is None:
+      out = torch.empty(max(n, 1), 4, dtype=torch.float64, device="cuda")
+    if out.dtype != torch.float64 or not out.is_cuda or not out.is_contiguous() or out.dim() != 2 or out.shape[1] != 4 or out.shape[0] < n:
+      raise ValueError("compare: out must be a contiguous device float64 [>= %d, 4]" % n)
+    if a.dtype == torch.uint8:
+      rc = self.L.vp_frame_metrics_u8(self.h, _ptr(a), ap, as_, _ptr(b), bp, bs, n, H, W, _ptr(out), _stream())
+      _lib.check(rc, "vp_frame_metrics_u8")
+    else:
+      try:
+        scale, offset = VALUE_RANGES[tuple(value_range)]
+      except (KeyError, TypeError):
+        raise ValueError("compare: value_range %r, (-1, 1), (0, 255) or (0, 1)" % (value_range,))
+      rc = self.L.vp_frame_metrics_f32(self.h, _ptr(a), ap, as_, _ptr(b), bp, bs, n, H, W, scale, offset, _ptr(out), _stream())
+      _lib.check(rc, "vp_frame_metrics_f32")
+    return out[:n]
+
+  def tensor(self, name):
+    """'abs_sum', 'sq_sum': int64 [max_frames] views of the workspace, the integer sums of the frames of the last uint8 compare."""
+    p, shp = ctypes.c_void_p(), (ctypes.c_int64 * 4)()
+    _lib.check(self.L.vp_frame_metrics_tensor(self.h, name.encode(), ctypes.byref(p), shp), "vp_frame_metrics_tensor")
+    off = p.value - self.workspace.data_ptr()
+    return self.workspace[off:off + 8 * int(shp[0])].view(torch.int64)
+
+  def __del__(self):
+    try:
+      if getattr(self, "h", None):
+        self.L.vp_frame_metrics_destroy(self.h)
+        self.h = None
+    except Exception:
+      pass

@@ -6,7 +6,8 @@
 
 One process per GPU; under torch.distributed.run (WORLD_SIZE > 1) the G/D gradient arenas are
 all-reduced over RCCL every step (plain data parallel, per-replica batch statistics).
-Extra, optional flags (defaults reproduce the reference run): --steps, --batch_size, --img_size, --resume (continue from the
+Extra, optional flags (defaults reproduce the reference run): --steps, --batch_size, --img_size, --eval_list / --eval_step /
+--eval_frames (held-out PSNR, SSIM and L1 next to the losses: pixrefer/heldout.py), --resume (continue from the
 latest checkpoint in ckpt_pixrefer - the block the reference keeps commented out at train_pixrefer.py:93-99; what a restart after a
 lost rank does: a FRESH process from the last checkpoint, never a re-exec of one that touched the GPU).
 """
@@ -51,6 +52,14 @@ def parse_options(argv=None):
   cmd_parser.add_option('--device_jpeg_scan', type="int", dest="device_jpeg_scan", default=None, metavar="N",
                         help='with --device_jpeg_decode: find a file\'s MCU-row entry points on the device at first sight, in chunks '
                              'of N bytes, 128 when no N follows (overrides amd.device_jpeg_scan)')
+  cmd_parser.add_option('--eval_list', type="string", dest="eval_list", default=None, metavar="FILE",
+                        help='held-out evaluation: a dataset list whose first --eval_frames triptychs are run through the generator '
+                             'every --eval_step steps; mean PSNR, SSIM and L1 are logged next to the losses (overrides amd.eval_list; '
+                             'absent: no evaluation)')
+  cmd_parser.add_option('--eval_step', type="int", dest="eval_step", default=None, metavar="N",
+                        help='with --eval_list: evaluate every N steps (default: on the steps that print the losses; overrides amd.eval_step)')
+  cmd_parser.add_option('--eval_frames', type="int", dest="eval_frames", default=None, metavar="K",
+                        help='with --eval_list: the number of held-out triptychs (default 8; overrides amd.eval_frames)')
   argv = list(sys.argv[1:] if argv is None else argv)
   for i, a in enumerate(argv):                     # --device_jpeg_scan [N]: the bare flag means 128
     if a == '--device_jpeg_scan' and not (i + 1 < len(argv) and argv[i + 1].isdigit()):
@@ -124,6 +133,18 @@ def main(argv=None):
   train_nodes = vid2vidnet.build_train_op(*train_iter.get_next())
   if use_device_pipeline:
     vid2vidnet.engine.use_streams(3)      # the input prefetcher's stream is the fourth busy one (include/vp_hip.h vp_pixrefer_use_streams)
+  # --eval_list / amd: {eval_list:, eval_step:, eval_frames:}: held-out evaluation (pixrefer/heldout.py), on rank 0.  Absent by default, and
+  # then nothing here changes.  It reads the training weights into an inference engine of its own and only enqueues; its numbers are read
+  # on the steps that read the losses anyway
+  held_out, eval_step = None, None
+  amd_keys = params.get('amd') or {}
+  eval_list = opts.eval_list or amd_keys.get('eval_list')
+  if eval_list and rank == 0:
+    from voicepuppet_amd.pixrefer.heldout import HeldOutEval
+    held_out = HeldOutEval(vid2vidnet.engine, eval_list, frames=opts.eval_frames or amd_keys.get('eval_frames', 8),
+                           crop_ratio=train_generator.crop_ratio, device_jpeg_decode=train_generator.device_jpeg_decode)
+    eval_step = int(opts.eval_step or amd_keys.get('eval_step') or max(1, params.summary_step // 2))
+    logger.info('held-out evaluation: %d frames of %s every %d steps', held_out.frames, eval_list, eval_step)
   # --resume / amd: {resume: true}: continue from the latest checkpoint of save_dir.  `epochs` stays the TOTAL number of iterations of
   # the run (the learning-rate schedule is a function of global_step, which the checkpoint restores), so a run restarted at
   # global_step 120000 of 200000 trains the remaining 40000 iterations, not another 100000.  The data pipeline is NOT part of a
@@ -189,11 +210,16 @@ def main(argv=None):
       ev = torch.cuda.Event()
       ev.record()
       dog.beat(ev)
+    if held_out is not None and (global_step // 2) % eval_step == 0:
+      held_out.run()                    # enqueued behind this step's update; no wait
     if summary:
       gen_loss_GAN, gen_loss_L1, discrim_loss = vals[3:6]
     if (summary and rank == 0):
       print('Step {}, Lr= {:.2e}: \n\tgen_loss_GAN= {:.3f}, \n\tgen_loss_L1= {:.3f}, \n\tdiscrim_loss= {:.3f}'.format(
           global_step, lr, gen_loss_GAN, gen_loss_L1, discrim_loss))
+      if held_out is not None and held_out.last is not None:
+        m = held_out.read()
+        print('\theld-out ({} frames): PSNR= {:.3f} dB, SSIM= {:.4f}, L1= {:.3f}'.format(m['frames'], m['PSNR'], m['SSIM'], m['L1']))
       fps = (i + 1) * batch_size * world / (time.time() - t0)
       logger.info('%.1f frames/s', fps)
       eng = vid2vidnet.engine
