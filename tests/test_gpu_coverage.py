@@ -32,7 +32,7 @@ IN_STEP = {
     "cout1wgrad_bf16_16x512": "layer_5 weight gradient (a wave per pixel, 16 x 8 sums per lane): "
                               "tests/test_gpu_step.py::test_one_output_channel_backward_kernel_in_situ against the generic kernels, test_gpu_fullwidth.py against the oracle",
     "cout4_bf16_16x16": "decoder_1 forward (128 -> 4 channels, f32 output): tests/test_gpu_step.py::test_step_parity[bf16], "
-                        "test_thin_decoder_tile_kernel_in_situ, test_gpu_fullwidth.py",
+                        "test_decoder_1_four_channel_kernel_in_situ, test_gpu_fullwidth.py",
 }
 
 

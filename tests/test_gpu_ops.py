@@ -100,17 +100,26 @@ def ref_input(x, sc, sh, in_act, dtype):
   return gu.rounded(xa, dtype) if dtype == "bf16" else xa
 
 
-@pytest.mark.parametrize("dtype", ["f32", "bf16"])
-@pytest.mark.parametrize("case", FWD_CASES)
-def test_conv_fwd(case, dtype):
+def fwd_device(case, dtype):
   kind, n, h, w, cin, cout, k, s, p, in_act, out_act, affine = case
   x, wt, b, sc, sh = make_case(case)
   d = gu.conv_desc(kind, n, h, w, cin, cout, k, s, p, dtype, in_act, out_act)
-  y = gu.conv_fwd(d, x, sc, sh, wt, b, dtype)
+  return gu.conv_fwd(d, x, sc, sh, wt, b, dtype)
+
+
+def fwd_oracle(case, dtype):
+  kind, n, h, w, cin, cout, k, s, p, in_act, out_act, affine = case
+  x, wt, b, sc, sh = make_case(case)
   xa = ref_input(x, sc, sh, in_act, dtype)
   wr = gu.rounded(wt, dtype)
   yr = ops.conv2d_fwd(xa, wr, np.float32(b).astype(np.float64), s, p) if kind == 0 else ops.deconv4s2_fwd(xa, wr, np.float32(b).astype(np.float64))
-  yr = ACTS[out_act](yr)
+  return ACTS[out_act](yr)
+
+
+@pytest.mark.parametrize("dtype", ["f32", "bf16"])
+@pytest.mark.parametrize("case", FWD_CASES)
+def test_conv_fwd(case, dtype):
+  y, yr = fwd_device(case, dtype), fwd_oracle(case, dtype)
   assert np.isfinite(y).all()
   assert gu.rel_l2(y, yr) < TOL[dtype], gu.rel_l2(y, yr)
 
@@ -133,20 +142,32 @@ def test_patch_kernel_tile_variants(case, small, dtype):
 BWD_CASES = [c for c in FWD_CASES if c[5] >= 8 and (c[5] & (c[5] - 1)) == 0]
 
 
-@pytest.mark.parametrize("dtype", ["f32", "bf16"])
-@pytest.mark.parametrize("case", BWD_CASES)
-def test_conv_bwd_data(case, dtype):
+def bwd_data_device(case, dtype):
   kind, n, h, w, cin, cout, k, s, p, in_act, out_act, affine = case
   x, wt, b, sc, sh = make_case(case)
   d = gu.conv_desc(kind, n, h, w, cin, cout, k, s, p, dtype)
   ho, wo = gu.out_hw(d)
   dy = np.random.default_rng(7).normal(size=(n, ho, wo, cout))
-  dx = gu.conv_bwd_data(d, dy, wt, dtype)
+  return gu.conv_bwd_data(d, dy, wt, dtype)
+
+
+def bwd_data_oracle(case, dtype):
+  kind, n, h, w, cin, cout, k, s, p, in_act, out_act, affine = case
+  x, wt, b, sc, sh = make_case(case)
+  ho, wo = gu.out_hw(gu.conv_desc(kind, n, h, w, cin, cout, k, s, p, dtype))
+  dy = np.random.default_rng(7).normal(size=(n, ho, wo, cout))
   dyr, wr = gu.rounded(dy, dtype), gu.rounded(wt, dtype)
   if kind == 0:
     dxr, _, _ = ops.conv2d_bwd(np.zeros((n, h, w, cin)), wr, dyr, s, p, need_dw=False)
   else:
     dxr, _, _ = ops.deconv4s2_bwd(np.zeros((n, h, w, cin)), wr, dyr)
+  return dxr
+
+
+@pytest.mark.parametrize("dtype", ["f32", "bf16"])
+@pytest.mark.parametrize("case", BWD_CASES)
+def test_conv_bwd_data(case, dtype):
+  dx, dxr = bwd_data_device(case, dtype), bwd_data_oracle(case, dtype)
   assert gu.rel_l2(dx, dxr) < TOL[dtype], gu.rel_l2(dx, dxr)
 
 
@@ -267,3 +288,34 @@ def test_thin_layer_cases_run_on_their_dedicated_kernels():
   c11 = (0, 4, 64, 128, 8, 64, 3, 1, 1, 0, 2, False)
   assert any(c.startswith("cout8_") for c in _profile_classes(lambda: test_conv_bwd_data(c11, "bf16")))
   assert any(c.startswith("cin8_") for c in _profile_classes(lambda: test_conv_fwd(c11, "bf16")))
+
+
+CONV1_1 = (0, 4, 64, 128, 8, 64, 3, 1, 1, 0, 2, False)
+LAYER_1 = (0, 4, 128, 128, 8, 64, 4, 2, 1, 0, 0, False)
+
+
+# (profile class, grid-cap knob, its default (conv_ops.h thin_blocks_knob), the lowered cap, device run, oracle, case)
+@pytest.mark.parametrize("cls,knob,default,blocks,device,oracle,case", [
+    ("cout8", b"thin_blocks_cout8", 1024, 5, bwd_data_device, bwd_data_oracle, CONV1_1),    # 512 tiles on 5 blocks: 103 / 102 tiles per block
+    ("dcout8", b"thin_blocks_dcout8", 512, 5, bwd_data_device, bwd_data_oracle, LAYER_1),   # 256 tiles on 5 blocks: 52 / 51
+    ("cin8", b"thin_blocks_cin8", 512, 3, fwd_device, fwd_oracle, CONV1_1),                 # 2048 tiles on 12 waves: 171 / 170, no multiple of the 4-tile trip
+])
+def test_thin_kernels_on_a_small_grid(cls, knob, default, blocks, device, oracle, case):
+  """At their default grid caps the thin cases give every block (every wave of cin8) one tile.  Under a lowered cap the persistent tile
+  loop takes many trips, blocks own unequal tile counts and the clamped trips past a block's last tile run: parity with the oracle as
+  test_conv_fwd / test_conv_bwd_data, the same bits as the default grid (which block computes a pixel does not enter its arithmetic),
+  and the dedicated kernel is what ran both times."""
+  L = _lib.lib()
+  want = oracle(case, "bf16")
+  got = {}
+  try:
+    for cap in (default, blocks):
+      L.vp_tune(knob, cap)
+      classes = _profile_classes(lambda: got.__setitem__(cap, device(case, "bf16")))
+      assert any(c.startswith(cls + "_") for c in classes), classes
+  finally:
+    L.vp_tune(knob, default)
+  for cap in (default, blocks):
+    assert np.isfinite(got[cap]).all()
+    assert gu.rel_l2(got[cap], want) < TOL["bf16"], (cap, gu.rel_l2(got[cap], want))
+  assert np.array_equal(got[default], got[blocks])

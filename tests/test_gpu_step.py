@@ -265,11 +265,8 @@ def test_staged_generator_backward_equals_monolithic():
   assert torch.equal(eng.grads_g, want)
 
 
-@pytest.mark.gpu
-def test_decoder_1_four_channel_kernel_in_situ():
-  """decoder_1 at a width where the dedicated 4-channel transposed-conv kernel runs (Cin = 64 = 2 MFMA steps per tap):
-  its f32 output against the float64 deconvolution of the SAME bf16 inputs the device fed it (teacher forcing)."""
-  from oracle import nn_ops as ops
+def decoder_1_in_situ():
+  """One bf16 forward pass at ngf = 32: decoder_1's two inputs as the device fed them, its f32 output, its weights."""
   ngf = 32
   p = ref.init_params(ngf, ngf, seed=11, dtype=np.float32)
   rng = np.random.default_rng(2)
@@ -284,9 +281,36 @@ def test_decoder_1_four_channel_kernel_in_situ():
   x_c2 = torch.relu(torch.addcmul(sh, sc, c2)).to(torch.bfloat16).float()          # act_apply: relu(fma(scale, y, shift)) -> bf16
   x_e1 = torch.relu(eng.tensor("g/encoder_1").float())
   x = torch.cat([x_c2, x_e1], dim=-1).cpu().numpy().astype(np.float64)
+  return p, x, eng.tensor("g/decoder_1").cpu().numpy()
+
+
+@pytest.fixture(scope="module")
+def decoder_1_default_grid():
+  """decoder_1_in_situ at the default grid cap, with the float64 deconvolution of the inputs the device fed the layer."""
+  from oracle import nn_ops as ops
+  p, x, got = decoder_1_in_situ()
   w = gu.rounded(p["generator/decoder_1/conv2d_transpose/kernel"], "bf16")
   want = ops.deconv4s2_fwd(x, w, p["generator/decoder_1/conv2d_transpose/bias"].astype(np.float64))
-  got = eng.tensor("g/decoder_1").cpu().numpy()
+  return dict(x=x, got=got, want=want)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("blocks", [None, 7])     # the default cap (one tile per block); 256 tiles on 7 blocks (37 / 36 tiles each)
+def test_decoder_1_four_channel_kernel_in_situ(decoder_1_default_grid, blocks):
+  """decoder_1 at a width where the dedicated 4-channel transposed-conv kernel runs (Cin = 64 = 2 MFMA steps per tap):
+  its f32 output against the float64 deconvolution of the SAME bf16 inputs the device fed it (teacher forcing).  Under a lowered grid
+  cap (vp_tune "thin_blocks_cout4") the blocks walk many tiles, unequally many: the same bound, and the same bits as the default grid."""
+  ref0 = decoder_1_default_grid
+  want, got = ref0["want"], ref0["got"]
+  if blocks is not None:
+    L = _lib.lib()
+    L.vp_tune(b"thin_blocks_cout4", blocks)
+    try:
+      _, x, got = decoder_1_in_situ()
+    finally:
+      L.vp_tune(b"thin_blocks_cout4", 512)        # (conv_ops.h thin_blocks_knob: the default)
+    assert np.array_equal(x, ref0["x"])           # the layers in front are deterministic: one oracle serves both grids
+    assert np.array_equal(got, ref0["got"])
   assert got.shape == want.shape == (1, 256, 256, 4)
   assert gu.rel_l2(got, want) < 2e-3, gu.rel_l2(got, want)       # fma-vs-float64 activation rounding flips a few bf16 ulps
 

@@ -33,7 +33,7 @@ enum ConvKernel {
   CK_CIN8,        // 8-channel image inputs (conv_cin8_kernel)          - igemm plans
   CK_COUT8,       // 3x3, 64 -> <= 8 channels (conv3x3_cout8_tile_kernel)
   CK_DCOUT8,      // 4x4 / stride-2 transposed, 64 -> <= 8 channels (deconv_cout8_tile_kernel)
-  CK_COUT4,       // 4-channel float32 transposed conv (deconv_cout4_kernel)
+  CK_COUT4,       // 4-channel float32 transposed conv (deconv_cout4_tile_kernel)
   CK_C64,         // 3x3, 64 / 128 -> 64 / 128 channels (conv_c64.hip)  - patch plans
   CK_PATCH3,      // unrolled 3x3 patch schedule (conv_patch3.hip)
   CK_PATCH4,      // unrolled 4x4 patch schedule (conv_patch3.hip, KW = 4)

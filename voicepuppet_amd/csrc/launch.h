@@ -14,12 +14,16 @@ bool patch3_eligible(const IgemmArgs& a, int is_bf16);                          
 hipError_t launch_igemm_patch3(const IgemmArgs& a, int is_bf16, int bc, int bp, hipStream_t st);                   // conv_patch3.hip
 bool patch4_eligible(const IgemmArgs& a, int is_bf16);                                                               // conv_patch3.hip (KW = 4)
 hipError_t launch_igemm_patch4(const IgemmArgs& a, hipStream_t st);
-bool conv_cin8_eligible(const IgemmArgs& a, int is_bf16);                                                           // conv_kernels.hip
-bool conv_cout8_eligible(const IgemmArgs& a, int is_bf16);
-bool conv_dcout8_eligible(const IgemmArgs& a, int is_bf16);
-bool conv_cout4_eligible(const IgemmArgs& a, int is_bf16);
 bool conv_kernel_ok(const IgemmArgs& a, int is_bf16);          // the preconditions of the plan's kernel (a.kern) hold for these arguments
 const char* conv_kernel_name(int kern);
+bool conv_cin8_eligible(const IgemmArgs& a, int is_bf16);                                                           // conv_thin.hip
+hipError_t launch_conv_cin8(const IgemmArgs& a, hipStream_t st);
+bool conv_cout8_eligible(const IgemmArgs& a, int is_bf16);
+hipError_t launch_conv_cout8(const IgemmArgs& a, hipStream_t st);
+bool conv_dcout8_eligible(const IgemmArgs& a, int is_bf16);
+hipError_t launch_conv_dcout8(const IgemmArgs& a, hipStream_t st);
+bool conv_cout4_eligible(const IgemmArgs& a, int is_bf16);
+hipError_t launch_conv_cout4(const IgemmArgs& a, hipStream_t st);
 bool conv_c64_eligible(const IgemmArgs& a, int is_bf16);                                                            // conv_c64.hip
 hipError_t launch_conv_c64(const IgemmArgs& a, hipStream_t st);
 bool conv_dc64_eligible(const IgemmArgs& a, int is_bf16);                                                           // conv_dc64.hip
