@@ -17,6 +17,7 @@
  *   vp_bfm_reconstruct replaces  utils/reconstruct_mesh.py:198-223 Reconstruction_rotation + infer_bfmvid.py:92-99
  *   vp_puppet_*        replaces  infer_bfmvid.py:110-121, :223-224, :229-238 for the rows of many talkers (stream groups)
  *   vp_jpeg_*          replaces  infer_bfmvid.py:243-244 (cv2.imwrite per frame) with a baseline JPEG encode on the device
+ *   vp_avimux_*        replaces  infer_bfmvid.py:245 (ffmpeg over the .jpg files and the wav) with Motion-JPEG + PCM AVI segments built on the device
  *   vp_jpegdec_*       replaces  generator/generator.py:956-1019 (cv2.imread per sample) and loader.py ImageLoader with a baseline JPEG decode on the device
  *   vp_pcmin_*         replaces  generator/loader.py:39-54 (WavLoader: scale, channel mean, resample_poly over a whole file) for live PCM
  *   vp_frame_metrics_* replaces  nothing: the reference has no image-quality measure (L1, PSNR and SSIM per frame pair, on the device)
@@ -929,6 +930,59 @@ int vp_frame_metrics_f32(vp_frame_metrics_t* h, const float* a, size_t a_row_pit
 /* "abs_sum", "sq_sum": int64 [max_frames], sum |a - b| and sum (a - b)^2 of the frames of the last vp_frame_metrics_u8 call (a
  * vp_frame_metrics_f32 call leaves them alone).  shape[0] = max_frames. */
 int vp_frame_metrics_tensor(vp_frame_metrics_t* h, const char* name, void** ptr, int64_t shape[4]);
+
+/* ------------------------------------------------------------------------------------------------
+ * AVI segments on the device: replaces infer_bfmvid.py:245 (ffmpeg over output/%d.jpg and the wav) for the JPEG rows of vp_jpeg_encode and
+ * the 16 kHz float32 samples of a push.  The container is AVI 1.0 (RIFF 'AVI '): Motion-JPEG video chunks `00dc`, 16-bit PCM audio chunks
+ * `01wb`, an `idx1` index; the host writes the headers and the index (voicepuppet_amd/avi.py AviWriter), the device the chunks.
+ * csrc/avi_mux.hip.
+ *
+ * A call writes one blob, little-endian throughout:
+ *   uint32 head[4]             table_bytes, used_bytes (table and every status-0 segment: the prefix worth copying), chunks, worst status
+ *   uint32 slot[slots][4]      offset of the slot's segment from the start of the blob, its bytes, its chunks, its status
+ *   uint32 entry[chunks][4]    AVIOLDINDEX entries in segment order (slot s's entries follow those of the slots before it): ckid, flags
+ *                              0x10, offset of the chunk header from the start of the slot's segment, payload bytes
+ *   (table_bytes = 16 + 16 * slots + 16 * (frames + slots) of the call: vp_avimux_table_bytes)
+ *   the segments, in slot order.  A slot with samples or frames in the call has one contiguous segment: a `01wb` chunk first when it has
+ *   samples (fourcc, uint32 payload bytes, int16 samples), then one `00dc` chunk per frame of the slot in row order (fourcc, uint32
+ *   lengths[r], the bytes, one zero byte when lengths[r] is odd).  A segment's bytes and its entries do not depend on the other slots.
+ * A sample x becomes clamp(rintf(x * 32768.0f), -32768, 32767), round half to even, NaN 0: what arrived as int16 / 32768 leaves as it came.
+ * Status: 0 ok; 1 a frame of the slot has lengths[r] < 0 (vp_jpeg_encode's capacity rule): nothing is written for the slot (0 bytes, 0
+ * chunks) and the host builds its segment; 2 the segment would end past out_capacity: offset, bytes, chunks and entries are what they
+ * would be, and nothing of the segment is written.
+ * Bounds: a row is read up to min(lengths[r], row_bytes); the samples of all slots together inside [0, samples) (counts are cut, in slot
+ * order, to what is left of `samples`; offsets moved inside); writes inside [0, out_capacity).  Rows whose frame_slot is outside 0 ..
+ * slots - 1 are left out; frame_slot must be non-decreasing (an unsorted one loses rows but breaks no bound).
+ * ---------------------------------------------------------------------------------------------- */
+#define VP_AVIMUX_MAX_FRAMES 4096
+#define VP_AVIMUX_MAX_SLOTS 128
+typedef struct vp_avimux_desc {
+  uint32_t struct_bytes;  /* sizeof(vp_avimux_desc) of the caller's build: must equal vp_avimux_desc_size() */
+  int32_t max_frames;     /* JPEG rows per call: 1 .. VP_AVIMUX_MAX_FRAMES */
+  int32_t row_bytes;      /* the largest row pitch a call may pass (vp_jpeg_frame_capacity) */
+  int32_t slots;          /* 1 .. VP_AVIMUX_MAX_SLOTS */
+  int32_t max_samples;    /* samples of all slots per call */
+} vp_avimux_desc;
+size_t vp_avimux_desc_size(void);
+typedef struct vp_avimux vp_avimux_t;
+/* 0 on a refused descriptor (vp_last_error says why; one whose vp_avimux_out_capacity is 4 GiB or more is refused: offsets are 32 bits) */
+size_t vp_avimux_workspace_bytes(const vp_avimux_desc* d);
+/* table + max_frames * (8 + row_bytes + 1) + slots * 8 + 2 * max_samples: a blob of that many bytes never has status 2 */
+size_t vp_avimux_out_capacity(const vp_avimux_desc* d);
+/* the table's bytes for a call of `frames` rows (0 .. max_frames): where the first segment starts */
+size_t vp_avimux_table_bytes(const vp_avimux_desc* d, int frames);
+/* Host only: touches no device memory.  workspace: DEVICE memory the caller keeps alive as long as the handle. */
+int vp_avimux_create(const vp_avimux_desc* d, void* workspace, size_t workspace_bytes, vp_avimux_t** out);
+/* data [frames, row_bytes] bytes, lengths [frames] int, as vp_jpeg_encode writes them; frame_slot [frames] int, non-decreasing; pcm
+ * [samples] float32 on a 4-byte boundary, slot s's samples at sample_offset[s] .. + sample_count[s] (int [slots] each; the packed layout
+ * of vp_bfmstream_group_push); out: the blob, on a 4-byte boundary, out_capacity bytes.  All of these DEVICE memory; frames (0 ..
+ * max_frames) and samples (0 .. max_samples) are host counts and may be 0, the pointers of an empty half NULL.  Two launches on `stream`
+ * (the table and the chunk list; the copies and the sample conversion); never waits, never allocates.  Calls on one handle must be
+ * ordered (one stream, or events): the chunk list lives in the workspace. */
+int vp_avimux_segment(vp_avimux_t* h, const unsigned char* data, size_t row_bytes, const int* lengths, const int* frame_slot, int frames,
+                      const float* pcm, const int* sample_offset, const int* sample_count, int samples, unsigned char* out, size_t out_capacity,
+                      void* stream);
+void vp_avimux_destroy(vp_avimux_t* h);
 
 /* Host helper: CRC-32C (Castagnoli, the checksum of TensorFlow checkpoint bundles) of `n` bytes, continuing from `crc` (0 to start). */
 unsigned vp_crc32c(const void* data, size_t n, unsigned crc);

@@ -89,6 +89,14 @@ class FrameMetricsDesc(ctypes.Structure):
 FRAME_METRICS_MAX_FRAMES = 4096      # include/vp_hip.h VP_FRAME_METRICS_MAX_FRAMES
 
 
+class AviMuxDesc(ctypes.Structure):
+  _fields_ = [("struct_bytes", ctypes.c_uint32), ("max_frames", ctypes.c_int32), ("row_bytes", ctypes.c_int32), ("slots", ctypes.c_int32),
+              ("max_samples", ctypes.c_int32)]
+
+
+AVIMUX_MAX_FRAMES, AVIMUX_MAX_SLOTS = 4096, 128   # include/vp_hip.h VP_AVIMUX_MAX_FRAMES, VP_AVIMUX_MAX_SLOTS
+
+
 class BfmModel(ctypes.Structure):
   _fields_ = [("nver", ctypes.c_int), ("ntri", ctypes.c_int), ("meanshape", ctypes.c_void_p), ("idBase", ctypes.c_void_p),
               ("exBase", ctypes.c_void_p), ("meantex", ctypes.c_void_p), ("texBase", ctypes.c_void_p), ("tri", ctypes.c_void_p),
@@ -242,6 +250,13 @@ _SIGNATURES = {
     "vp_frame_metrics_f32": (ctypes.c_int, [_P, _P, ctypes.c_size_t, ctypes.c_size_t, _P, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int, ctypes.c_int,
                                             ctypes.c_int, ctypes.c_double, ctypes.c_double, _P, _P]),
     "vp_frame_metrics_tensor": (ctypes.c_int, [_P, ctypes.c_char_p, ctypes.POINTER(_P), ctypes.POINTER(ctypes.c_int64)]),
+    "vp_avimux_desc_size": (ctypes.c_size_t, []),
+    "vp_avimux_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(AviMuxDesc)]),
+    "vp_avimux_out_capacity": (ctypes.c_size_t, [ctypes.POINTER(AviMuxDesc)]),
+    "vp_avimux_table_bytes": (ctypes.c_size_t, [ctypes.POINTER(AviMuxDesc), ctypes.c_int]),
+    "vp_avimux_create": (ctypes.c_int, [ctypes.POINTER(AviMuxDesc), _P, ctypes.c_size_t, ctypes.POINTER(_P)]),
+    "vp_avimux_segment": (ctypes.c_int, [_P, _P, ctypes.c_size_t, _P, _P, ctypes.c_int, _P, _P, _P, ctypes.c_int, _P, ctypes.c_size_t, _P]),
+    "vp_avimux_destroy": (None, [_P]),
     "vp_bfm_reconstruct_rows": (ctypes.c_int, [ctypes.POINTER(BfmModel), _P, _P, ctypes.c_int, _P, ctypes.c_int, _P, _P, _P, _P, ctypes.c_size_t, _P]),
     "vp_bfmstream_group_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(BfmStreamGroupDesc)]),
     "vp_bfmstream_group_plan_info": (ctypes.c_int, [ctypes.POINTER(BfmStreamGroupDesc), ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
@@ -365,6 +380,10 @@ def lib():
       want = int(l.vp_frame_metrics_desc_size())
       if want != ctypes.sizeof(FrameMetricsDesc):
         raise RuntimeError("%s: vp_frame_metrics_desc is %d bytes in the library, %d in this binding" % (LIB_PATH, want, ctypes.sizeof(FrameMetricsDesc)))
+    if hasattr(l, "vp_avimux_desc_size") and l.vp_avimux_desc_size.argtypes is not None:
+      want = int(l.vp_avimux_desc_size())
+      if want != ctypes.sizeof(AviMuxDesc):
+        raise RuntimeError("%s: vp_avimux_desc is %d bytes in the library, %d in this binding" % (LIB_PATH, want, ctypes.sizeof(AviMuxDesc)))
     _lib = l
   return _lib
 

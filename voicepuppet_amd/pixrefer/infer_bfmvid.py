@@ -166,7 +166,8 @@ def render_faces(renderer, center_x, center_y, ratio, bfm_coeff_seq, img_shape, 
   return out if on_device else out.cpu().numpy()      # on_device: the clip loop consumes the frames where they are (no PCIe round trip)
 
 
-def main(argv=None):
+def parse_options(argv=None):
+  """(options, positional arguments) of the command line."""
   cmd_parser = OptionParser(usage="usage: %prog [options] --config_path <> image audio")
   cmd_parser.add_option('--config_path', type="string", dest="config_path", help='the config yaml file')
   cmd_parser.add_option('--frame_batch', type="int", dest="frame_batch", default=8, help='frames per device batch')
@@ -176,7 +177,18 @@ def main(argv=None):
                         help='frame directory (the reference always writes output/; infer_clips.py gives every clip its own)')
   cmd_parser.add_option('--device_jpeg', action="store_true", dest="device_jpeg", default=False,
                         help='encode the .jpg files on the device (quality 75) instead of PIL on the host pool')
-  opts, argv = cmd_parser.parse_args(argv)
+  cmd_parser.add_option('--avi', action="store_true", dest="avi", default=False,
+                        help='also write <output_dir>.avi (Motion-JPEG + 16-bit PCM, built on the device; implies --device_jpeg)')
+  cmd_parser.add_option('--avi_only', action="store_true", dest="avi_only", default=False,
+                        help='--avi without the per-frame .jpg files and without the ffmpeg call')
+  return cmd_parser.parse_args(argv)
+
+
+def main(argv=None):
+  opts, argv = parse_options(argv)
+  avi = opts.avi or opts.avi_only
+  if avi:
+    opts.device_jpeg = True           # the video chunks are the device encoder's files
 
   if (opts.config_path is None):
     logger.error('Please check your parameters.')
@@ -269,6 +281,17 @@ def main(argv=None):
       # the frames never leave the device raw: voicepuppet_amd.jpeg encodes Outputs_u8 where it is, the pool only writes the files
       from voicepuppet_amd.jpeg import JpegEncoder
       encoder = JpegEncoder(img_size, img_size, nb, quality=75)
+    muxer = writer = None
+    if avi:
+      # the clip's 16 kHz signal goes up once; every batch's call takes its frames and the samples of their 40 ms each (the last one the rest)
+      from voicepuppet_amd.avi import AviMuxer, AviWriter
+      spf = infer_generator.frame_wav_scale
+      pcm_d = torch.from_numpy(np.ascontiguousarray(pcm, dtype=np.float32)).to(dev)
+      n_pcm = int(pcm_d.numel())
+      muxer = AviMuxer(nb, encoder.capacity, 1, n_pcm, quality=75)
+      writer = AviWriter(out_dir.rstrip('/') + '.avi', img_size, img_size, frame_us=int(round(1e6 * spf / infer_generator.sample_rate)),
+                         sample_rate=infer_generator.sample_rate)
+      slot0 = torch.zeros(nb, dtype=torch.int32, device=dev)
     try:
       for i0 in range(0, T, nb):
         idx = [min(i0 + k, T - 1) for k in range(nb)]
@@ -288,7 +311,16 @@ def main(argv=None):
           eng.forward(inputs, fg_inputs, targets)
           u8 = eng.fetch('Outputs_u8')
           n = min(nb, T - i0)
-          files = encoder.to_host(*encoder.encode(u8[:n]), u8)
+          data, lengths = encoder.encode(u8[:n])
+          if muxer is not None:
+            a = min(i0 * spf, n_pcm)
+            b = n_pcm if i0 + n >= T else min((i0 + n) * spf, n_pcm)
+            seg = muxer.segment(data, lengths, slot0[:n], pcm_d if n_pcm else None, [a], [b - a])
+            for segment, entries in muxer.to_host(seg, u8).values():
+              writer.append(segment, entries)
+            if opts.avi_only:
+              continue
+          files = encoder.to_host(data, lengths, u8)
           for k in range(n):
             pending.append(pool.submit(write_bytes, files[k], os.path.join(out_dir, '{}.jpg'.format(i0 + k))))
           continue
@@ -301,6 +333,12 @@ def main(argv=None):
         f.result()           # every frame is on disk (and any write error surfaces) before ffmpeg reads the directory
     finally:
       pool.shutdown()        # (also on an error in the loop: the writer threads must not outlive the call)
+      if writer is not None:
+        writer.close()
+    if writer is not None:
+      logger.info('wrote %s', ', '.join(writer.paths))
+    if opts.avi_only:
+      return
 
     if shutil.which('ffmpeg'):
       # same command line as infer_bfmvid.py:245, as an argument vector (no shell: the audio path is user input)

@@ -40,7 +40,8 @@ def rank_commands(opts, clip_list, world):
   for r in range(world):
     argv = [sys.executable, '-m', 'voicepuppet_amd.pixrefer.infer_clips', '--config_path', opts.config_path,
             '--frame_batch', str(opts.frame_batch), '--out_root', opts.out_root, '--gpus', str(world)] + \
-           (['--device_jpeg'] if getattr(opts, 'device_jpeg', False) else []) + [clip_list]
+           (['--device_jpeg'] if getattr(opts, 'device_jpeg', False) else []) + (['--avi'] if getattr(opts, 'avi', False) else []) + \
+           (['--avi_only'] if getattr(opts, 'avi_only', False) else []) + [clip_list]
     env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(world))
     env.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')
     out.append((argv, env))
@@ -62,11 +63,15 @@ def run_rank(opts, clips, rank, world):
       argv += ['--bfmcoeff', clip[2]]
     if getattr(opts, 'device_jpeg', False):
       argv += ['--device_jpeg']
+    for flag in ('avi', 'avi_only'):       # <out_root>/clip_<i>.avi beside the clip's directory
+      if getattr(opts, flag, False):
+        argv += ['--' + flag]
     infer_bfmvid.main(argv + [clip[0], clip[1]])
   return len(mine)
 
 
-def main(argv=None):
+def parse_options(argv=None):
+  """(options, positional arguments) of the command line."""
   cmd_parser = OptionParser(usage="usage: %prog [options] --config_path <> clips.txt")
   cmd_parser.add_option('--config_path', type="string", dest="config_path", help='the config yaml file')
   cmd_parser.add_option('--gpus', type="int", dest="gpus", default=1, help='ranks (one per GPU)')
@@ -74,7 +79,15 @@ def main(argv=None):
   cmd_parser.add_option('--out_root', type="string", dest="out_root", default='output_clips', help='clip_<i>/ directories go here')
   cmd_parser.add_option('--device_jpeg', action="store_true", dest="device_jpeg", default=False,
                         help='passed to infer_bfmvid: encode the .jpg files on the device')
-  opts, args = cmd_parser.parse_args(argv)
+  cmd_parser.add_option('--avi', action="store_true", dest="avi", default=False,
+                        help='passed to infer_bfmvid: also write <out_root>/clip_<i>.avi (Motion-JPEG + 16-bit PCM, built on the device)')
+  cmd_parser.add_option('--avi_only', action="store_true", dest="avi_only", default=False,
+                        help='passed to infer_bfmvid: --avi without the per-frame .jpg files and without the ffmpeg call')
+  return cmd_parser.parse_args(argv)
+
+
+def main(argv=None):
+  opts, args = parse_options(argv)
   if (opts.config_path is None or len(args) != 1):
     logger.error('Please check your parameters.')
     exit(0)

@@ -31,7 +31,8 @@ logging.basicConfig(level=logging.INFO, format='%(asctime)s - %(name)s - %(level
 logger = logging.getLogger(__name__)
 
 
-def main(argv=None):
+def parse_options(argv=None):
+  """(options, positional arguments) of the command line."""
   cmd_parser = OptionParser(usage="usage: %prog [options] --config_path <> image audio")
   cmd_parser.add_option('--config_path', type="string", dest="config_path", help='the config yaml file')
   cmd_parser.add_option('--frame_batch', type="int", dest="frame_batch", default=8, help='frames per device batch')
@@ -43,7 +44,18 @@ def main(argv=None):
                         help='encode the .jpg files on the device (quality 75) instead of PIL on the host pool')
   cmd_parser.add_option('--native_pcm', action="store_true", dest="native_pcm", default=False,
                         help='push the wav as it is (its rate, channels and sample type): converted and resampled on the device, chunk by chunk')
-  opts, argv = cmd_parser.parse_args(argv)
+  cmd_parser.add_option('--avi', action="store_true", dest="avi", default=False,
+                        help='also write <output_dir>.avi (Motion-JPEG + 16-bit PCM, built on the device; implies --device_jpeg)')
+  cmd_parser.add_option('--avi_only', action="store_true", dest="avi_only", default=False,
+                        help='--avi without the per-frame .jpg files and without the ffmpeg call')
+  return cmd_parser.parse_args(argv)
+
+
+def main(argv=None):
+  opts, argv = parse_options(argv)
+  avi = opts.avi or opts.avi_only
+  if avi:
+    opts.device_jpeg = True           # the video chunks are the device encoder's files
 
   if (opts.config_path is None):
     logger.error('Please check your parameters.')
@@ -84,7 +96,10 @@ def main(argv=None):
   # a window emits at most the frames one chunk completes (a catch-up push runs several windows)
   stream = PuppetStream(config_path, img, bfmcoeff=opts.bfmcoeff, frame_batch=opts.frame_batch,
                         max_chunk_frames=max(1, int(math.ceil(opts.chunk_ms / frame_ms))),
-                        **({'jpeg_quality': 75} if opts.device_jpeg else {}), **({'pcm_format': pcm_format} if pcm_format else {}))
+                        **({'jpeg_quality': 75} if opts.device_jpeg else {}), **({'pcm_format': pcm_format} if pcm_format else {}),
+                        **({'avi': True} if avi else {}))
+  if avi:
+    stream.record(out_dir.rstrip('/') + '.avi', frame_us=int(round(1000.0 * frame_ms)))
   logger.info('streaming %d samples in chunks of %d (%.0f ms), lookahead %.0f ms', pcm.shape[0], chunk, opts.chunk_ms,
               stream.audio.lookahead_ms)
 
@@ -101,6 +116,8 @@ def main(argv=None):
     Image.fromarray(arr_u8).save(path)
 
   def emit(frames):
+    if opts.avi_only:                  # the frames are in the .avi (PuppetStream appends every push to the open recording)
+      return
     for i, f in frames:
       pending.append(pool.submit(write_jpg, f, os.path.join(out_dir, '{}.jpg'.format(i))))
 
@@ -122,6 +139,10 @@ def main(argv=None):
     logger.info('%d pushes: latency median %.2f ms, max %.2f ms (frames included); finish %.2f ms; %d frames', len(lat),
                 float(np.median(lat)), float(np.max(lat)), fin_ms, stream.frame)
 
+  if avi:
+    logger.info('wrote %s', ', '.join(stream.stop()))
+  if opts.avi_only:
+    return
   if shutil.which('ffmpeg'):
     # infer_bfmvid's mux (infer_bfmvid.py:245), as an argument vector
     subprocess.call(['ffmpeg', '-i', os.path.join(out_dir, '%d.jpg'), '-i', audio_file, '-c:v', 'libx264', '-c:a', 'aac',

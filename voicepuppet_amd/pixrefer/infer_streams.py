@@ -49,7 +49,8 @@ def read_list(path):
   return talkers
 
 
-def main(argv=None):
+def parse_options(argv=None):
+  """(options, positional arguments) of the command line."""
   cmd_parser = OptionParser(usage="usage: %prog [options] --config_path <> list_file")
   cmd_parser.add_option('--config_path', type="string", dest="config_path", help='the config yaml file')
   cmd_parser.add_option('--frame_batch', type="int", dest="frame_batch", default=8, help='frames per generator launch')
@@ -60,7 +61,18 @@ def main(argv=None):
                         help='encode the .jpg files on the device (quality 75) instead of PIL on the host pool')
   cmd_parser.add_option('--native_pcm', action="store_true", dest="native_pcm", default=False,
                         help='push every wav as it is (its rate, channels and sample type): converted and resampled on the device, chunk by chunk')
-  opts, argv = cmd_parser.parse_args(argv)
+  cmd_parser.add_option('--avi', action="store_true", dest="avi", default=False,
+                        help='also write <output_dir>/<s>.avi per talker (Motion-JPEG + 16-bit PCM, built on the device; implies --device_jpeg)')
+  cmd_parser.add_option('--avi_only', action="store_true", dest="avi_only", default=False,
+                        help='--avi without the per-frame .jpg files and without the ffmpeg call')
+  return cmd_parser.parse_args(argv)
+
+
+def main(argv=None):
+  opts, argv = parse_options(argv)
+  avi = opts.avi or opts.avi_only
+  if avi:
+    opts.device_jpeg = True           # the video chunks are the device encoder's files
 
   if (opts.config_path is None or len(argv) != 1):
     logger.error('Please check your parameters.')
@@ -105,9 +117,11 @@ def main(argv=None):
   frame_ms = 1000.0 * gen.frame_wav_scale / gen.sample_rate
   group = PuppetStreamGroup(config_path, S, frame_batch=opts.frame_batch, max_chunk_frames=max(1, int(math.ceil(opts.chunk_ms / frame_ms))),
                             **({'jpeg_quality': 75} if opts.device_jpeg else {}),
-                            **({'ingest_rates': sorted(set(f[0] for f in formats))} if formats else {}))
+                            **({'ingest_rates': sorted(set(f[0] for f in formats))} if formats else {}), **({'avi': True} if avi else {}))
   for s, (image, _, npz) in enumerate(talkers):
     group.attach(s, ImageLoader().get_data(image)[:, :, ::-1], npz, *(formats[s] if formats else ()))      # RGB float in [0,1], 512 x 1536
+    if avi:
+      group.record(s, out_dirs[s] + '.avi', frame_us=int(round(1000.0 * frame_ms)))
   rngs = [np.random.RandomState(opts.seed) for _ in range(S)] if opts.seed is not None else None
   logger.info('streaming %d talkers in chunks of %d samples (%.0f ms), lookahead %.0f ms', S, chunk, opts.chunk_ms, group.audio.lookahead_ms)
 
@@ -135,6 +149,12 @@ def main(argv=None):
     t = time.perf_counter()
     res = (group.push_raw if formats is not None else group.push)(chunks, finish=finish, ears=ears)
     n = sum(len(v) for v in res.values())
+    if avi:
+      group.write_avi()                                                # every push: its audio goes to the file before its frames exist
+    if opts.avi_only:
+      lat.append(1000.0 * (time.perf_counter() - t))
+      logger.debug('push %d: %d frames, %.2f ms', len(lat), n, lat[-1])
+      return n
     if opts.device_jpeg:
       files = group.last_jpeg() if n else {}                           # the one wait of the push: the encoded bytes
       lat.append(1000.0 * (time.perf_counter() - t))
@@ -171,6 +191,11 @@ def main(argv=None):
   logger.info('%d pushes: latency median %.2f ms, max %.2f ms (frames included); %d frames of %d talkers', len(lat), float(np.median(lat)),
               float(np.max(lat)), total, S)
 
+  if avi:
+    for s in range(S):
+      logger.info('wrote %s', ', '.join(group.stop(s)))
+  if opts.avi_only:
+    return
   for s, (_, audio, _) in enumerate(talkers):
     if shutil.which('ffmpeg'):
       subprocess.call(['ffmpeg', '-i', os.path.join(out_dirs[s], '%d.jpg'), '-i', audio, '-c:v', 'libx264', '-c:a', 'aac',

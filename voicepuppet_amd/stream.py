@@ -199,6 +199,8 @@ class AudioStreamGroup:
     _lib.check(self.L.vp_bfmstream_group_create(d, _ptr(self.workspace), ws, _ptr(self.params), _stream(), ctypes.byref(h)),
                "vp_bfmstream_group_create")
     self.h = h
+    self.keep_pcm = False           # a PuppetStreamGroup that writes AVI: last_pcm is the packed device samples of the last push (or None)
+    self.last_pcm = None
     if params is not None:
       self.load_params(load_bfmnet_params(params) if isinstance(params, str) else params)
 
@@ -281,6 +283,8 @@ class AudioStreamGroup:
         raise ValueError("push_device_packed: a contiguous f32 device tensor of %d samples" % total)
     else:
       pcm = None
+    if self.keep_pcm:
+      self.last_pcm = pcm
     k = self.ready(sizes, finish)
     K = sum(k)
     out = torch.empty(K, 64, dtype=torch.float32, device="cuda")
@@ -447,9 +451,16 @@ class PuppetStreamGroup:
   jpeg_quality=Q (1 .. 100; None, the default: no encoder exists and push is what it is without the keyword): the group owns a
   voicepuppet_amd.jpeg.JpegEncoder of frame_batch frames, a push also enqueues the JPEG encode of last_frames in launches of at most
   frame_batch rows, and last_jpeg() -> {slot: [(global frame index, bytes of the .jpg file)]} for the frames of the last push (the one
-  wait: the lengths, then the used part of the byte rows; the raw frames stay on the device)."""
+  wait: the lengths, then the used part of the byte rows; the raw frames stay on the device).
 
-  def __init__(self, config_path, slots, frame_batch=8, max_chunk_frames=1, dtype="f32", img_size=512, jpeg_quality=None, ingest_rates=None):
+  avi=True (with jpeg_quality): the group owns a voicepuppet_amd.avi.AviMuxer and a push also enqueues, behind its JPEG encodes, the
+  AVI segments of the push: per slot the 16-bit PCM of the samples pushed and the frames emitted, as RIFF chunks.  last_avi() -> {slot:
+  (segment bytes, index entries)} of the last push (AviMuxer.to_host: one wait).  record(slot, path) opens a voicepuppet_amd.avi.AviWriter
+  for the slot, write_avi() appends last_avi() to the writers that are open, stop(slot) closes the slot's file and returns its paths;
+  attach and reset_slot stop a recording.  Without the keyword nothing of this exists and a push is what it was."""
+
+  def __init__(self, config_path, slots, frame_batch=8, max_chunk_frames=1, dtype="f32", img_size=512, jpeg_quality=None, ingest_rates=None,
+               avi=False):
     import os
     from .pixrefer import infer_bfmvid as ib
     if not torch.cuda.is_available():
@@ -493,6 +504,16 @@ class PuppetStreamGroup:
     if jpeg_quality is not None:
       from .jpeg import JpegEncoder
       self.jpeg = JpegEncoder(self.img_size, self.img_size, self.nb, quality=jpeg_quality)
+    self.avi = None
+    self._avi_seg = None
+    self._writers = {}
+    if avi:
+      if self.jpeg is None:
+        raise ValueError("PuppetStreamGroup: avi=True needs jpeg_quality (the video chunks are the device encoder's files)")
+      from .avi import AviMuxer
+      # a finishing push flushes the lookahead and a catch-up push carries any number of samples: the ABI's limits, not a guess
+      self.avi = AviMuxer(_lib.AVIMUX_MAX_FRAMES, self.jpeg.capacity, self.slots, 1 << 24, quality=jpeg_quality)
+      self.audio.keep_pcm = True
     self.ingest = None
     self._ingest_fmt = {}
     if ingest_rates is not None:
@@ -529,6 +550,8 @@ class PuppetStreamGroup:
 
   def reset_slot(self, slot):
     """Slot `slot` starts a new clip (audio session, head sway, frame counter, ingest filter state); its photo stays."""
+    if int(slot) in self._writers:
+      self.stop(slot)
     self.audio.reset_slot(slot)
     self.plan.reset_slot(int(slot))
     if self.ingest is not None and int(slot) in self._ingest_fmt:
@@ -583,7 +606,10 @@ class PuppetStreamGroup:
     res = {s: [] for s in sizes}
     self.last_frames, self.last_conditioning = None, None
     self._jpeg_rows = None
+    self._avi_seg = None
     if K == 0:
+      if self.avi is not None and self.audio.last_pcm is not None:      # audio without a frame yet (the lookahead): a segment all the same
+        self._avi_segment(None, None, None, sizes)
       return res
     render, tex_src, tex_row, cond = launch_tables(slot, g, self.has_coeff, self.bg_row, nb)
     R = int(render.shape[0])
@@ -617,6 +643,8 @@ class PuppetStreamGroup:
         n = min(nb, K - i0)
         self.jpeg.encode(out[i0:i0 + n], data[i0:i0 + n], lengths[i0:i0 + n])
       self._jpeg_rows = (data, lengths, slot, g)
+      if self.avi is not None:
+        self._avi_segment(data, lengths, cond_d[:K, 0].contiguous(), sizes)
     if kept is not None:
       self.last_conditioning = {"slot": slot, "frame": g,
                                 **{name: torch.cat([b[i] for b in kept]) for i, name in enumerate(("inputs", "fg_inputs", "targets", "Outputs"))}}
@@ -637,8 +665,57 @@ class PuppetStreamGroup:
       res.setdefault(int(slot[r]), []).append((int(g[r]), f))
     return res
 
+  def _avi_segment(self, data, lengths, slot_d, sizes):
+    """Enqueues the AVI segments of this push: the JPEG rows (or none) and the samples AudioStreamGroup packed, in slot order."""
+    pcm = self.audio.last_pcm
+    counts = np.zeros(self.slots, np.int32)
+    for s, n in sizes.items():
+      counts[s] = n
+    offsets = (np.cumsum(counts) - counts).astype(np.int32)
+    self._avi_seg = self.avi.segment(data, lengths, slot_d, pcm, offsets, counts)
+
+  def last_avi(self):
+    """{slot: (the slot's chunks of the last push, their uint32 [n, 4] index entries)} (avi=True groups); waits for them."""
+    if self.avi is None:
+      raise RuntimeError("last_avi: the group was created without avi=True")
+    if self._avi_seg is None:
+      return {}
+    return self.avi.to_host(self._avi_seg, self.last_frames)
+
+  def record(self, slot, path, **writer_args):
+    """Slot `slot`'s pushes from now on go to an AVI file at `path` (write_avi appends, stop closes); writer_args: AviWriter's keywords."""
+    from .avi import AviWriter
+    if self.avi is None:
+      raise RuntimeError("record: the group was created without avi=True")
+    slot = int(slot)
+    if not 0 <= slot < self.slots:
+      raise IndexError("slot %d of %d" % (slot, self.slots))
+    if slot in self._writers:
+      self.stop(slot)
+    writer_args.setdefault("frame_us", 1000000 * SAMPLES_PER_FRAME // self.audio.desc.sample_rate)
+    writer_args.setdefault("sample_rate", self.audio.desc.sample_rate)
+    self._writers[slot] = AviWriter(path, self.img_size, self.img_size, **writer_args)
+
+  def write_avi(self):
+    """last_avi() appended to the writers that are open; returns it."""
+    segs = self.last_avi()
+    for s, (segment, entries) in segs.items():
+      if s in self._writers:
+        self._writers[s].append(segment, entries)
+    return segs
+
+  def stop(self, slot):
+    """Closes slot `slot`'s recording; the paths of its files (more than one when it passed max_bytes), or None when none was open."""
+    w = self._writers.pop(int(slot), None)
+    if w is None:
+      return None
+    w.close()
+    return w.paths
+
   def __del__(self):
     try:
+      for s in list(getattr(self, "_writers", {})):
+        self.stop(s)
       if getattr(self, "h", None):
         self.L.vp_puppet_destroy(self.h)
         self.h = None
@@ -655,10 +732,12 @@ class PuppetStream:
   encoded on the device (PuppetStreamGroup), and no raw frame crosses to the host."""
 
   def __init__(self, config_path, image, bfmcoeff=None, frame_batch=8, max_chunk_frames=1, dtype="f32", img_size=512, jpeg_quality=None,
-               pcm_format=None):
-    """pcm_format=(rate, channels, fmt): the stream also takes client PCM of that form through push_raw (PuppetStreamGroup.push_raw)."""
+               pcm_format=None, avi=False):
+    """pcm_format=(rate, channels, fmt): the stream also takes client PCM of that form through push_raw (PuppetStreamGroup.push_raw).
+    avi=True (with jpeg_quality): as PuppetStreamGroup; record(path) / stop() hold the file, and every push and finish appends to it."""
     self.group = PuppetStreamGroup(config_path, 1, frame_batch=frame_batch, max_chunk_frames=max_chunk_frames, dtype=dtype, img_size=img_size,
-                                   jpeg_quality=jpeg_quality, **({'ingest_rates': (pcm_format[0],)} if pcm_format else {}))
+                                   jpeg_quality=jpeg_quality, **({'ingest_rates': (pcm_format[0],)} if pcm_format else {}),
+                                   **({'avi': True} if avi else {}))
     self.jpeg_quality = jpeg_quality
     self.group.attach(0, image, bfmcoeff, *(pcm_format or ()))
     self.audio = self.group.audio
@@ -681,7 +760,15 @@ class PuppetStream:
       return self._host(self.group.push_raw({}, finish=(0,)))
     return self._host(self.group.push({}, finish=(0,)))
 
+  def record(self, path, **writer_args):
+    self.group.record(0, path, **writer_args)
+
+  def stop(self):
+    return self.group.stop(0)
+
   def _host(self, res):
+    if self.group._writers:
+      self.group.write_avi()
     if not res[0]:
       return []
     if self.jpeg_quality is not None:      # the device's .jpg bytes in place of host arrays; no raw frame is copied
