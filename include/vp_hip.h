@@ -15,6 +15,10 @@
  *   vp_bfmnet_*     replaces  voicepuppet/bfmnet/bfmnet.py:189-213,325-333 + tinynet.py:159-212
  *   vp_render_colors   replaces  utils/cython/mesh_core.h:63 _render_colors_core (mesh_core.cpp:169-231)
  *   vp_bfm_reconstruct replaces  utils/reconstruct_mesh.py:198-223 Reconstruction_rotation + infer_bfmvid.py:92-99
+ *   vp_bfm_reconstruct_view replaces utils/reconstruct_mesh.py:172-194 Reconstruction + the packing of utils/bfm_visual.py:100-112 (view 0)
+ *                             and voicepuppet/bfmnet/infer_bfmnet.py:212-216 (view 1)
+ *   vp_sheet_tile_u8   replaces  utils/bfm_visual.py:125-128 (cvtColor + the numpy paste of a tile into big_img)
+ *   vp_landmark_distance replaces nothing: the reference judges BFMNet by the montage alone (68-landmark distance, on the device)
  *   vp_puppet_*        replaces  infer_bfmvid.py:110-121, :223-224, :229-238 for the rows of many talkers (stream groups)
  *   vp_jpeg_*          replaces  infer_bfmvid.py:243-244 (cv2.imwrite per frame) with a baseline JPEG encode on the device
  *   vp_avimux_*        replaces  infer_bfmvid.py:245 (ffmpeg over the .jpg files and the wav) with Motion-JPEG + PCM AVI segments built on the device
@@ -545,6 +549,33 @@ int vp_bfm_reconstruct(const vp_bfm_model* m, const float* coeff, const double* 
  * vp_bfm_reconstruct(shared_texture = 1) returns for that identity's frames alone.  Same workspace query; never waits. */
 int vp_bfm_reconstruct_rows(const vp_bfm_model* m, const float* coeff, const double* rotation, int frames, const int* tex_src, int textures,
                             const int* tex_row, float* vertices, float* colors, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Reconstruction(coeff, facemodel) (utils/reconstruct_mesh.py:172-194), the form plot_bfm_coeff_seq (utils/bfm_visual.py:97) and
+ * voicepuppet/bfmnet/infer_bfmnet.py:209 call: the pose is the coefficients' own, rotation [frames,9] = Compute_rotation_matrix(coeff[:, 224:227])
+ * (evaluated by the host in double, as above).  The normals are rotated by it, the projection is shape . R + t (ONE rotation, inside
+ * Projection_layer), and face_shape is returned UNROTATED; lighting and colour packing are those of vp_bfm_reconstruct.  No choice of
+ * angles turns vp_bfm_reconstruct into this.  Same model, same workspace query, same optional float64 outputs.
+ *   view 0 (montage, bfm_visual.py:100-112):  vertices = float32(x, 224 - y, z_buffer); scale is ignored
+ *   view 1 (mesh video, infer_bfmnet.py:212-216): vertices = float32((112 - sx*112)*scale, (112 - sy*112)*scale, sz*scale) from the
+ *          unrotated face_shape, evaluated in double in that order; the reference's scale is 3 (a 672 x 672 image); 0 < scale <= 1024 */
+int vp_bfm_reconstruct_view(const vp_bfm_model* m, const float* coeff, const double* rotation, int frames, int shared_texture, int view, double scale,
+                            double* face_shape, double* face_texture, double* face_color, double* face_projection, double* z_buffer,
+                            float* vertices, float* colors, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Visual evaluation of BFMNet: the mesh montage of utils/bfm_visual.py plot_bfm_coeff_seq (:88-154) and a number to go with it.
+ * vp_sheet_tile_u8: tile i of tiles [n,h,w,3] uint8 (vp_render_colors' images) goes to cell first_cell + i of sheet
+ * [sheet_rows*h, sheet_cols*w, 3] uint8: cell c is row c / sheet_cols, column c % sheet_cols (:127-128).  swap_rb != 0 exchanges the
+ * first and third channel on the way (:125).  Cells that are not written keep their contents: the caller zeroes the sheet.  A cell
+ * outside the sheet is refused with VP_ERR_ARG before anything is enqueued.
+ * vp_landmark_distance: for frame f of two projected sequences proj_a, proj_b [frames,nver,2] float64 (face_projection of view 0: pixels
+ * of the 224 image) and keypoints [68] int32 (0-based vertex indices, facemodel.keypoints), out[f] = { mean over the 68 landmarks of the
+ * Euclidean distance, the same over landmarks 48..67 (the mouth) }.  One wavefront per frame and a fixed summation order: a frame's two
+ * numbers are the same bits alone and in any batch.  A keypoint outside 0 .. nver-1 is not read; the frame's numbers are NaN.
+ * ---------------------------------------------------------------------------------------------- */
+int vp_sheet_tile_u8(const unsigned char* tiles, int n, int h, int w, unsigned char* sheet, int sheet_rows, int sheet_cols, int first_cell,
+                     int swap_rb, void* stream);
+int vp_landmark_distance(const double* proj_a, const double* proj_b, const int* keypoints, int frames, int nver, double* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * BFMNet TRAINING step (voicepuppet/bfmnet/bfmnet.py:215-323, tinynet.py:7-212): the non-GEMM kernels, float32 NHWC,

@@ -5,8 +5,10 @@
     python voicepuppet/bfmnet/train_bfmnet.py --config_path config/params.yml
 
 Single GPU, as the reference (it pins CUDA_VISIBLE_DEVICES to one device).  Extra, optional flags (defaults reproduce the reference
-run): --steps, --batch_size, --eval_step, --save_step.  The evaluation plot of the reference (plot_bfm_coeff_seq, a matplotlib
-figure of the mesh) is outside the path; the evaluation loss is printed.
+run): --steps, --batch_size, --eval_step, --save_step.  The evaluation loss is printed.  The reference's mesh montage of every
+evaluation step (train_bfmnet.py:79,138: plot_bfm_coeff_seq into log/eval_bfmnet) is written with --eval_visual (that directory) or
+--eval_visual_dir DIR, on the device (voicepuppet_amd/bfmnet/visual.py), with the 68-landmark distance printed beside the loss; it needs
+BFM/BFM_model_front.mat and is off by default.
 """
 import logging
 import os
@@ -29,14 +31,44 @@ def mkdir(path):
     os.makedirs(path)
 
 
-def main(argv=None):
+BFM_MAT = os.path.join('BFM', 'BFM_model_front.mat')
+
+
+def parse_options(argv=None):
   cmd_parser = OptionParser(usage="usage: %prog [options] --config_path <>")
   cmd_parser.add_option('--config_path', type="string", dest="config_path", help='the config yaml file')
   cmd_parser.add_option('--steps', type="int", dest="steps", default=None, help='iterations to run (default: training.epochs)')
   cmd_parser.add_option('--batch_size', type="int", dest="batch_size", default=4, help='clips per step (reference: 4)')
   cmd_parser.add_option('--eval_step', type="int", dest="eval_step", default=1000)
   cmd_parser.add_option('--save_step', type="int", dest="save_step", default=5000)
-  opts, _ = cmd_parser.parse_args(argv)
+  cmd_parser.add_option('--eval_visual_dir', type="string", dest="eval_visual_dir", default=None,
+                        help='write the mesh montage bfmnet_<step>.jpg of every evaluation step into this directory')
+  cmd_parser.add_option('--eval_visual', action="store_true", dest="eval_visual", default=False,
+                        help='--eval_visual_dir log/eval_bfmnet (the reference\'s directory)')
+  return cmd_parser.parse_args(argv)
+
+
+def visual_dir(opts):
+  """Where the evaluation montage goes, or None (the default): --eval_visual_dir wins over --eval_visual."""
+  return opts.eval_visual_dir or ('log/eval_bfmnet' if opts.eval_visual else None)
+
+
+def mesh_sheet(directory):
+  """The MeshSheet of BFM/BFM_model_front.mat for `directory`, or None (with one warning) when the face model is not there: the random
+  stand-in the generator trains against has no triangles to draw."""
+  if directory is None:
+    return None
+  if not os.path.exists(BFM_MAT):
+    logger.warning('%s not found: no evaluation montage is written', BFM_MAT)
+    return None
+  from voicepuppet_amd.bfmnet.visual import MeshSheet
+  from voicepuppet_amd.pixrefer.infer_bfmvid import clip_renderer
+  mkdir(directory)
+  return MeshSheet(clip_renderer())
+
+
+def main(argv=None):
+  opts, _ = parse_options(argv)
 
   if (opts.config_path is None):
     logger.error('Please check your parameters.')
@@ -80,6 +112,8 @@ def main(argv=None):
   bfmnet.set_params(params)
 
   mkdir(params.save_dir)
+  eval_visual_dir = visual_dir(opts)
+  sheet = mesh_sheet(eval_visual_dir)
 
   train_nodes = bfmnet.build_train_op(*train_iter.get_next())
   eval_nodes = bfmnet.build_eval_op(*eval_iter.get_next())
@@ -101,6 +135,10 @@ def main(argv=None):
       loss, seq_len, real_bfm_coeff_seq, bfm_coeff_seq = sess.run([eval_nodes['Loss'], eval_nodes['Seq_len'], eval_nodes['BFM_coeff_seq'],
                                                                    eval_nodes['BFMCoeffDecoder']])
       print('\r\nEvaluation >>> Loss= {:.3f}'.format(loss))
+      if sheet is not None:
+        from voicepuppet_amd.bfmnet.visual import plot_bfm_coeff_seq
+        lmd = plot_bfm_coeff_seq(eval_visual_dir, sheet, global_step, seq_len, real_bfm_coeff_seq, bfm_coeff_seq)      # train_bfmnet.py:138
+        print('LMD= %.3f px, mouth %.3f px' % lmd)
       logger.info('%.1f clips/s', (i + 1) * batch_size / (time.time() - t0))
 
     ### Save checkpoint

@@ -1,6 +1,7 @@
 // BFM reconstruction for a clip: [T,257] coefficients -> projected vertices + per-vertex colours for the rasteriser.
 // Device form of utils/reconstruct_mesh.py `Reconstruction_rotation` (:198-223) + the packing of infer_bfmvid.py:92-99,
-// batched over the T frames of a clip.  float64 arithmetic like the reference's numpy (the model bases are promoted to
+// batched over the T frames of a clip; and of `Reconstruction` (:172-194), the pose the coefficients carry themselves, packed
+// for the mesh montage (utils/bfm_visual.py:100-112) or the 672 x 672 mesh video (bfmnet/infer_bfmnet.py:212-216).  float64 arithmetic like the reference's numpy (the model bases are promoted to
 // float64 once, at model load), so the float32 vertices / integer colours handed to the rasteriser agree with the
 // reference's; the work is HBM-bound on the three basis matrices, which are read ONCE per clip instead of once per frame.
 //
@@ -106,8 +107,16 @@ struct VertexArgs {
   const int* tex_row;        // optional [T]: the texture row of each frame (rows of several identities)
   double focal, center;
   double sh[9];              // a_i*c_i products of Illumination_layer (:138-143), evaluated on the host in double
+  double scale;              // kOwnPoseFlat only: the image scale of infer_bfmnet.py:216
 };
 
+// What the vertex kernel computes, fixed at compile time (the first is the code it always was):
+//   kExternalPose  Reconstruction_rotation: shape rotated for face_shape and once more in Projection_layer; vertices (x, 224-y, z_buffer)
+//   kOwnPose       Reconstruction: normals rotated, shape rotated ONCE (in Projection_layer), face_shape unrotated; vertices as above
+//   kOwnPoseFlat   Reconstruction, vertices from the unrotated shape: ((112 - sx*112)*scale, (112 - sy*112)*scale, sz*scale)
+enum VertexMode { kExternalPose = 0, kOwnPose = 1, kOwnPoseFlat = 2 };
+
+template <int kMode>
 __global__ __launch_bounds__(256) void bfm_vertex_kernel(VertexArgs a) {
   const int v = blockIdx.x * 256 + threadIdx.x;
   const int f = blockIdx.y;
@@ -130,7 +139,10 @@ __global__ __launch_bounds__(256) void bfm_vertex_kernel(VertexArgs a) {
   // shape: rotated once for the returned face_shape, and once more inside Projection_layer (:211,:214 -> :113)
   const size_t vi = ((size_t)f * a.nver + v) * 3;
   const double sx = a.shape[vi], sy = a.shape[vi + 1], sz = a.shape[vi + 2];
-  const double px = sx * r00 + sy * r10 + sz * r20, py = sx * r01 + sy * r11 + sz * r21, pz = sx * r02 + sy * r12 + sz * r22;
+  double px = sx, py = sy, pz = sz;            // what Projection_layer is handed: kOwnPose* pass the unrotated shape (:185)
+  if constexpr (kMode == kExternalPose) {
+    px = sx * r00 + sy * r10 + sz * r20; py = sx * r01 + sy * r11 + sz * r21; pz = sx * r02 + sy * r12 + sz * r22;
+  }
   if (a.face_shape) { a.face_shape[vi] = px; a.face_shape[vi + 1] = py; a.face_shape[vi + 2] = pz; }
   const float* C = a.coeff + (size_t)f * 257;
   const double qx = (px * r00 + py * r10 + pz * r20) + (double)C[254];
@@ -140,7 +152,12 @@ __global__ __launch_bounds__(256) void bfm_vertex_kernel(VertexArgs a) {
   const double prx = ux / qz, pry = 224.0 - uy / qz, zb = -qz;
   if (a.face_projection) { a.face_projection[((size_t)f * a.nver + v) * 2] = prx; a.face_projection[((size_t)f * a.nver + v) * 2 + 1] = pry; }
   if (a.z_buffer) a.z_buffer[(size_t)f * a.nver + v] = zb;
-  a.vertices[vi] = (float)prx; a.vertices[vi + 1] = (float)pry; a.vertices[vi + 2] = (float)zb;
+  if constexpr (kMode == kOwnPoseFlat) {
+    a.vertices[vi] = (float)((112.0 - sx * 112.0) * a.scale); a.vertices[vi + 1] = (float)((112.0 - sy * 112.0) * a.scale);
+    a.vertices[vi + 2] = (float)(sz * a.scale);
+  } else {
+    a.vertices[vi] = (float)prx; a.vertices[vi + 1] = (float)pry; a.vertices[vi + 2] = (float)zb;
+  }
   // SH lighting on the rotated normal
   double Y[9];
   Y[0] = a.sh[0];
@@ -170,8 +187,8 @@ size_t vp_bfm_reconstruct_workspace_bytes(int nver, int ntri, int frames) {
   return ((size_t)frames * nver * 3 * 2 + (size_t)frames * (ntri + 1) * 3) * sizeof(double) + 512;
 }
 
-static int reconstruct_impl(const char* who, const vp_bfm_model* m, const float* coeff, const double* rotation, int frames, int tex_frames,
-                            const int* tex_src, const int* tex_row,
+static int reconstruct_impl(const char* who, int mode, double scale, const vp_bfm_model* m, const float* coeff, const double* rotation, int frames,
+                            int tex_frames, const int* tex_src, const int* tex_row,
                             double* face_shape, double* face_texture, double* face_color, double* face_projection, double* z_buffer,
                             float* vertices, float* colors, void* workspace, size_t workspace_bytes, void* stream) {
   if (!m || !coeff || !rotation || !vertices || !colors || !workspace || frames < 1 || m->nver < 1 || m->ntri < 1 || !m->idBase ||
@@ -205,7 +222,11 @@ static int reconstruct_impl(const char* who, const vp_bfm_model* m, const float*
   va.vertices = vertices; va.colors = colors; va.nver = m->nver; va.ntri = m->ntri; va.frames = frames; va.tex_frames = tex_frames; va.tex_row = tex_row;
   va.focal = m->focal; va.center = m->image_center;
   for (int i = 0; i < 5; ++i) va.sh[i] = m->sh[i];
-  hipLaunchKernelGGL(vp::bfm_vertex_kernel, dim3((m->nver + 255) / 256, frames), dim3(256), 0, st, va);
+  va.scale = scale;
+  const dim3 vgrid((m->nver + 255) / 256, frames);
+  if (mode == vp::kOwnPose) hipLaunchKernelGGL(vp::bfm_vertex_kernel<vp::kOwnPose>, vgrid, dim3(256), 0, st, va);
+  else if (mode == vp::kOwnPoseFlat) hipLaunchKernelGGL(vp::bfm_vertex_kernel<vp::kOwnPoseFlat>, vgrid, dim3(256), 0, st, va);
+  else hipLaunchKernelGGL(vp::bfm_vertex_kernel<vp::kExternalPose>, vgrid, dim3(256), 0, st, va);
   VP_HIP_CHECK(hipGetLastError());
   return VP_OK;
 }
@@ -213,8 +234,25 @@ static int reconstruct_impl(const char* who, const vp_bfm_model* m, const float*
 int vp_bfm_reconstruct(const vp_bfm_model* m, const float* coeff, const double* rotation, int frames, int shared_texture,
                        double* face_shape, double* face_texture, double* face_color, double* face_projection, double* z_buffer,
                        float* vertices, float* colors, void* workspace, size_t workspace_bytes, void* stream) {
-  return reconstruct_impl("vp_bfm_reconstruct", m, coeff, rotation, frames, shared_texture ? 1 : frames, nullptr, nullptr, face_shape, face_texture,
-                          face_color, face_projection, z_buffer, vertices, colors, workspace, workspace_bytes, stream);
+  return reconstruct_impl("vp_bfm_reconstruct", vp::kExternalPose, 1.0, m, coeff, rotation, frames, shared_texture ? 1 : frames, nullptr, nullptr,
+                          face_shape, face_texture, face_color, face_projection, z_buffer, vertices, colors, workspace, workspace_bytes, stream);
+}
+
+// Reconstruction (:172-194): rotation = Compute_rotation_matrix(coeff[:, 224:227]); view 0 packs for the montage, view 1 for the mesh video
+int vp_bfm_reconstruct_view(const vp_bfm_model* m, const float* coeff, const double* rotation, int frames, int shared_texture, int view, double scale,
+                            double* face_shape, double* face_texture, double* face_color, double* face_projection, double* z_buffer,
+                            float* vertices, float* colors, void* workspace, size_t workspace_bytes, void* stream) {
+  if (view != 0 && view != 1) {
+    vp::set_err("vp_bfm_reconstruct_view: bad argument (view %d: 0 montage, 1 mesh video)", view);
+    return VP_ERR_ARG;
+  }
+  if (view == 1 && !(scale > 0.0 && scale <= 1024.0)) {      // (also refuses NaN)
+    vp::set_err("vp_bfm_reconstruct_view: bad argument (scale %g outside (0, 1024])", scale);
+    return VP_ERR_ARG;
+  }
+  return reconstruct_impl("vp_bfm_reconstruct_view", view ? vp::kOwnPoseFlat : vp::kOwnPose, scale, m, coeff, rotation, frames,
+                          shared_texture ? 1 : frames, nullptr, nullptr, face_shape, face_texture, face_color, face_projection, z_buffer, vertices,
+                          colors, workspace, workspace_bytes, stream);
 }
 
 // rows of several identities: texture t from coefficient row tex_src[t], row r lit with texture tex_row[r] (include/vp_hip.h)
@@ -224,8 +262,8 @@ int vp_bfm_reconstruct_rows(const vp_bfm_model* m, const float* coeff, const dou
     vp::set_err("vp_bfm_reconstruct_rows: bad argument (1 .. frames textures, device tables)");
     return VP_ERR_ARG;
   }
-  return reconstruct_impl("vp_bfm_reconstruct_rows", m, coeff, rotation, frames, textures, tex_src, tex_row, nullptr, nullptr, nullptr, nullptr,
-                          nullptr, vertices, colors, workspace, workspace_bytes, stream);
+  return reconstruct_impl("vp_bfm_reconstruct_rows", vp::kExternalPose, 1.0, m, coeff, rotation, frames, textures, tex_src, tex_row, nullptr, nullptr,
+                          nullptr, nullptr, nullptr, vertices, colors, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -1,6 +1,8 @@
 """Drop-in for the reference's utils/reconstruct_mesh.py on the MI355X (libvp_hip.so: vp_bfm_reconstruct): BFM coefficients ->
 face shape / texture / colour / projection, batched over the frames of a clip, plus `ClipRenderer`, which chains it with the
 rasteriser (utils.mesh_core) the way render_face does per frame (voicepuppet/pixrefer/infer_bfmvid.py:79-108).
+`reconstruct_view` / `Reconstruction` / `ClipRenderer.render_view` are the same for `Reconstruction` (:172-194), the pose the
+coefficients carry themselves (vp_bfm_reconstruct_view): what utils/bfm_visual.py and voicepuppet/bfmnet/infer_bfmnet.py call.
 
 Host work kept here on purpose: the one-time promotion of the face model to float64 device arrays, the mean-shape centre and
 SH constants (model load), and the 3x3 rotation matrices of the clip (numpy, same libm as the reference).  No CPU fallback.
@@ -115,6 +117,36 @@ def reconstruct_clip(coeff, model, angles, shared_texture=False, full=True):
   return out
 
 
+def reconstruct_view(coeff, model, view=0, scale=1.0, shared_texture=False, full=True):
+  """Batched Reconstruction (reconstruct_mesh.py:172-194): the angles are coeff[:, 224:227].  view 0: vertices = (x, 224-y, z_buffer), the
+  montage's packing (utils/bfm_visual.py:100-112); view 1: ((112 - sx*112)*scale, (112 - sy*112)*scale, sz*scale) from the unrotated shape
+  (infer_bfmnet.py:212-216).  Returns reconstruct_clip's dict; face_shape is UNROTATED, and full=True adds `translation` [T,3]."""
+  dev = model.device
+  coeff_d = (torch.from_numpy(np.ascontiguousarray(coeff, np.float32)) if isinstance(coeff, np.ndarray) else coeff).to(dev).contiguous()
+  T = coeff_d.shape[0]
+  if coeff_d.dtype != torch.float32 or coeff_d.dim() != 2 or coeff_d.shape[1] != 257 or T < 1:
+    raise ValueError("coeff must be float32 [T,257]")
+  if view not in (0, 1):
+    raise ValueError("view must be 0 (montage) or 1 (mesh video)")
+  angles = coeff_d[:, 224:227].cpu().numpy()                                                  # float32, as Split_coeff hands them (:173)
+  rot = torch.from_numpy(Compute_rotation_matrix(angles)).to(dev)
+  N = model.nver
+  out = {"vertices": torch.empty(T, N, 3, dtype=torch.float32, device=dev), "colors": torch.empty(T, N, 3, dtype=torch.float32, device=dev)}
+  if full:
+    for k, shp in (("face_shape", (T, N, 3)), ("face_texture", (1 if shared_texture else T, N, 3)), ("face_color", (T, N, 3)),
+                   ("face_projection", (T, N, 2)), ("z_buffer", (T, N, 1))):
+      out[k] = torch.empty(*shp, dtype=torch.float64, device=dev)
+  ws = model.workspace(T)
+  _lib.check(_lib.lib().vp_bfm_reconstruct_view(ctypes.byref(model.c), _ptr(coeff_d), _ptr(rot), T, 1 if shared_texture else 0, int(view), float(scale),
+                                                _ptr(out.get("face_shape")), _ptr(out.get("face_texture")), _ptr(out.get("face_color")),
+                                                _ptr(out.get("face_projection")), _ptr(out.get("z_buffer")), _ptr(out["vertices"]), _ptr(out["colors"]),
+                                                _ptr(ws), ws.numel(), _stream()), "vp_bfm_reconstruct_view")
+  if full:
+    out["landmarks_2d"] = out["face_projection"][:, torch.from_numpy(model.keypoints).to(dev)]
+    out["translation"] = coeff_d[:, 254:]
+  return out
+
+
 def reconstruct_rows(coeff, rot, tex_src, textures, tex_row, model):
   """Rows of several identities in one call (vp_bfm_reconstruct_rows; stream groups): coeff [R,257] f32, rot [R,3,3] f64, tex_src
   [textures] / tex_row [R] int32 - all DEVICE tensors, so the call only enqueues.  Returns (vertices, colors) [R,N,3] f32."""
@@ -141,6 +173,15 @@ def Reconstruction_rotation(coeff, facemodel, angles):
   return tuple(o[k].cpu().numpy() for k in ("face_shape", "face_texture", "face_color", "face_projection", "z_buffer", "landmarks_2d"))
 
 
+def Reconstruction(coeff, facemodel):
+  """reconstruct_mesh.py:172-194, same arguments and 7-tuple (face_shape, face_texture, face_color, face_projection, z_buffer,
+  landmarks_2d, translation): numpy float64 except translation, which the reference returns as the slice of `coeff` it is."""
+  model = facemodel if isinstance(facemodel, DeviceFaceModel) else DeviceFaceModel(facemodel)
+  o = reconstruct_view(coeff, model)
+  res = tuple(o[k].cpu().numpy() for k in ("face_shape", "face_texture", "face_color", "face_projection", "z_buffer", "landmarks_2d"))
+  return res + (np.asarray(coeff)[:, 254:] if isinstance(coeff, np.ndarray) else o["translation"].cpu().numpy(),)
+
+
 class ClipRenderer:
   """render_face's reconstruction + rasterisation (infer_bfmvid.py:79-108) for all frames of a clip in four launches + one:
   images uint8 [T,h,w,3] in the reference's channel order BEFORE its cvtColor (:110), masks uint8 [T,h,w]."""
@@ -158,6 +199,13 @@ class ClipRenderer:
     __call__ gives for that identity's frames alone."""
     vertices, colors = reconstruct_rows(coeff, rot, tex_src, textures, tex_row, self.model)
     return self._raster(vertices, colors)
+
+  def render_view(self, coeff, view=0, scale=1.0, shared_texture=False, full=False):
+    """__call__ for Reconstruction's own pose (reconstruct_view), rasterised at this renderer's h x w: (images, masks), and with
+    full=True the reconstruction's dict as a third value (its face_projection is what the landmark distance reads)."""
+    o = reconstruct_view(coeff, self.model, view=view, scale=scale, shared_texture=shared_texture, full=full)
+    image, mask = self._raster(o["vertices"], o["colors"])
+    return (image, mask, o) if full else (image, mask)
 
   def _raster(self, vertices, colors):
     T, dev = vertices.shape[0], self.model.device
