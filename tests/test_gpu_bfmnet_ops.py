@@ -51,10 +51,10 @@ from oracle import audio_ref as ar
 from voicepuppet_amd import _lib
 
 import gpu_util as gu
+from gpu_util import SENTINEL, assert_guards, guarded      # (re-exported: test_gpu_bfmnet_train_ops.py imports them from here)
 
 gpu = pytest.mark.gpu
 U = 2.0 ** -24
-SENTINEL = -1536.0                      # exact in bf16 and f32
 VP_ERR_ARG = -1                         # enum vp_status of include/vp_hip.h
 CLIP_SCALES = (1.0, 0.6, 1.6)
 
@@ -246,23 +246,6 @@ def test_dwproj_reference_on_cpu():
 # ---------------------------------------------------------------------------------------------------------------------------------
 # GPU side
 # ---------------------------------------------------------------------------------------------------------------------------------
-def guarded(shape, row_elems, dtype="f32", fill=None):
-  """(whole buffer, view of `shape` inside it, guard length): the view starts after a guard band of >= one image row of SENTINEL."""
-  g = -(-max(row_elems, 64) // 64) * 64
-  n = int(np.prod(shape))
-  whole = torch.full((n + 2 * g,), SENTINEL, dtype=gu.tdtype(dtype), device="cuda")
-  view = whole[g:g + n].view(*shape)
-  if fill is None:
-    view.fill_(float("nan"))
-  else:
-    view.copy_(torch.as_tensor(fill, dtype=torch.float32).to(gu.tdtype(dtype)))
-  return whole, view, g
-
-
-def assert_guards(whole, g):
-  assert bool((whole[:g] == SENTINEL).all()) and bool((whole[-g:] == SENTINEL).all()), "guard band written"
-
-
 def check(name, got, ref, bound):
   """Per-element bound; prints the worst ratio and the rel-L2 first, names the worst elements on failure."""
   got = np.asarray(got, np.float64)

@@ -1,7 +1,40 @@
 """-m gpu: single-op parity of the HIP kernels against the numpy oracle (oracle/nn_ops.py),
 called through the C ABI.  Tolerances: f32 path 1e-5 relative L2 (f32 MFMA == fmaf chain);
-bf16 path 1e-2 on bf16-rounded operands (bf16 storage of the result, f32 accumulate)."""
+bf16 path 1e-2 on bf16-rounded operands (bf16 storage of the result, f32 accumulate).
+
+The relative L2 is one number per tensor: a pixel with every channel wrong, a dropped border tap or a lost K slab moves it by a few
+1e-3 and passes.  So test_conv_fwd, test_conv_bwd_data and test_conv_bwd_weight (and every test that calls them under other knobs) also
+compare PER ELEMENT against a forward-error bound computed next to the float64 reference (fwd_reference / bwd_data_reference /
+bwd_weight_reference), u = 2^-24:
+
+    |got - ref| <= r_out |ref| + (1 + r_out) (gamma(K + c) S + |w| (*) D),      gamma(n) = n u / (1 - n u)
+
+  S      the same convolution of the absolute values of the operands, plus |bias| (computed in float32 and raised by its own error
+         2 K u: it is a magnitude)
+  K      the number of products that can be non-zero in one output element: k^2 cin forward (4 cin for the 4x4 / stride-2 transposed
+         convolution: a 2 x 2 subset of the taps reaches an output pixel), (k / s)^2 cout backward-data (16 cout transposed), the output
+         pixels n ho wo for the weight gradient (n h w transposed).  Every product is exact in float32 on the bf16 path (8 x 8 bits) and
+         is rounded once with its addition on the float32 path (fmaf / MFMA), so K counts every rounding of the sum.  Sums with an exact 0
+         (padding taps, the channels an 8-channel input is padded with, a zeroed split-K slab) round nothing.
+  c      forward: 1, the bias add.  Backward: 0.  Split-K adds nothing: the slabs are float32 sums that start from 0 and are combined by
+         float32 additions (a combine kernel or atomics) - the same K terms in another order, and the bound n u S on a sum of n terms holds
+         for any order (each term passes through at most n - 1 additions).  A slab stored in less than float32 would break that, and is
+         what the bound is there to catch.  (The planner's split factor has no entry point; none is needed for this.)
+  r_out  2^-8 (half an ulp of bf16) where the output is stored in bf16, u where it is float32 (the bf16 weight gradient is float32).
+         (1 + r_out): the stored value is the rounding of the DEVICE's float32 value, not of the reference.
+  act    ReLU is 1-Lipschitz: the bound passes through.  tanh (1-Lipschitz) adds K_TANH u |ref|, the measured constant of
+         test_gpu_bfmnet_train_ops.py for tanhf on the MI355X.  No case uses the sigmoid.
+  D      the one ambiguity of the reference: the float32 value the loader hands on as the activated input.  scale * x + shift may be
+         fused (prologue_piece, conv_kernels.hip: fmaf) or not, and act_apply's leaky ReLU 0.6f v + 0.4f |v| is contracted by the
+         compiler into either product's fma or left alone; on the bf16 path the result is then rounded to bf16 (Elem<bf16>::pack).  All
+         six float32 evaluations are computed in numpy (input_candidates); the reference uses the MIDPOINT of their range and D is half
+         the range, so |w| (*) D covers whichever the kernel computes.  D is zero almost everywhere on the bf16 path (a flipped bf16
+         rounding) and a few u |xa| on the float32 path.  For the weight gradient the term is D against |dy|.
+
+Measured worst |got - ref| / bound per (op, dtype): the docstring of test_gpu_ops_exact.py, which holds the exact (integer operand)
+counterpart of these tests and the CPU tests of this bound."""
 import ctypes
+import functools
 
 import numpy as np
 import pytest
@@ -11,9 +44,13 @@ from oracle import nn_ops as ops
 from voicepuppet_amd import _lib
 
 import gpu_util as gu
+from test_gpu_bfmnet_ops import check
+from test_gpu_bfmnet_train_ops import K_TANH, fma32
 
 pytestmark = pytest.mark.gpu
 TOL = {"f32": 2e-5, "bf16": 1e-2}
+U = 2.0 ** -24
+R_OUT = {"f32": U, "bf16": 2.0 ** -8}
 ACTS = {0: lambda v: v, 1: lambda v: ops.lrelu(v, 0.2), 2: ops.relu, 3: np.tanh, 4: ops.sigmoid}
 
 # (kind, n, h, w, cin, cout, k, s, p, in_act, out_act, affine)
@@ -92,12 +129,91 @@ def make_case(case, seed=0):
   return x, wt, b, sc, sh
 
 
-def ref_input(x, sc, sh, in_act, dtype):
+def bf16_round(a):
+  return torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(torch.bfloat16).float().numpy()
+
+
+def input_candidates(x, sc, sh, in_act, dtype):
+  """Every float32 array the loader may hand on as the activated input (module docstring, D): the affine fused or not, the leaky ReLU
+  plain or contracted into either product, then the bf16 rounding of the bf16 path."""
+  f = np.float32
   xr = gu.rounded(x, dtype)
+  pres = [xr.astype(f)]
   if sc is not None:
-    xr = np.float32(sc) * xr + np.float32(sh)
-  xa = ACTS[in_act](xr)
-  return gu.rounded(xa, dtype) if dtype == "bf16" else xa
+    sc64, sh64 = np.float32(sc).astype(np.float64), np.float32(sh).astype(np.float64)
+    pres = [fma32(sc64, xr, sh64), f(sc) * xr.astype(f) + f(sh)]
+  out = []
+  for v in pres:
+    if in_act == 1:
+      p6, p4 = f(0.6) * v, f(0.4) * np.abs(v)
+      v64 = v.astype(np.float64)
+      out += [p6 + p4, fma32(float(f(0.6)), v64, p4.astype(np.float64)), fma32(float(f(0.4)), np.abs(v64), p6.astype(np.float64))]
+    else:
+      out.append(ACTS[in_act](v).astype(f))
+  return [bf16_round(v) for v in out] if dtype == "bf16" else out
+
+
+def ref_operand(x, sc, sh, in_act, dtype):
+  """(activated input, D) in float64: the midpoint and the half range of input_candidates (D is None where there is one candidate)."""
+  cand = input_candidates(x, sc, sh, in_act, dtype)
+  if len(cand) == 1:
+    return cand[0].astype(np.float64), None
+  lo, hi = np.minimum.reduce(cand).astype(np.float64), np.maximum.reduce(cand).astype(np.float64)
+  return 0.5 * (lo + hi), 0.5 * (hi - lo)
+
+
+def ref_input(x, sc, sh, in_act, dtype):
+  return ref_operand(x, sc, sh, in_act, dtype)[0]
+
+
+def gamma(n):
+  return n * U / (1.0 - n * U)
+
+
+def contraction(case, op):
+  """K of the module docstring."""
+  kind, n, h, w, cin, cout, k, s, p = case[:9]
+  if op == "fwd":
+    return k * k * cin if kind == 0 else 4 * cin
+  if op == "bwd_data":
+    return (k // s) ** 2 * cout if kind == 0 else 16 * cout
+  ho, wo = gu.out_hw(gu.conv_desc(kind, n, h, w, cin, cout, k, s, p, "f32"))
+  return n * ho * wo if kind == 0 else n * h * w
+
+
+def conv_op(case, op, a, b, bias=None):
+  """The convolution `op` of the case on numpy arrays in their own dtype (oracle/nn_ops.py): fwd (x, w, bias) -> y, bwd_data (dy, w) -> dx,
+  bwd_weight (x, dy) -> dw."""
+  kind, n, h, w, cin, cout, k, s, p = case[:9]
+  if op == "fwd":
+    return ops.conv2d_fwd(a, b, bias, s, p) if kind == 0 else ops.deconv4s2_fwd(a, b, bias)
+  if op == "bwd_data":
+    z = np.zeros((n, h, w, cin), a.dtype)
+    return ops.conv2d_bwd(z, b, a, s, p, need_dw=False)[0] if kind == 0 else ops.deconv4s2_bwd(z, b, a)[0]
+  z = np.zeros((k, k, cin, cout) if kind == 0 else (4, 4, cout, cin), a.dtype)
+  return ops.conv2d_bwd(a, z, b, s, p, need_dx=False)[1] if kind == 0 else ops.deconv4s2_bwd(a, z, b, need_dx=False)[1]
+
+
+def element_bound(case, op, dtype, ref, a, b, bias=None, delta=None, out_act=0):
+  """The bound of the module docstring for ref = act(conv_op(a, b, bias)) (float64); delta: D of operand a."""
+  f = np.float32
+  kk = contraction(case, op)
+  aa = np.abs(a) if delta is None else np.abs(a) + delta
+  mag = conv_op(case, op, aa.astype(f), np.abs(b).astype(f), None if bias is None else np.abs(bias).astype(f)).astype(np.float64) * (1 + 2 * kk * U)
+  inner = gamma(kk + (1 if bias is not None else 0)) * mag
+  if delta is not None:
+    inner = inner + conv_op(case, op, delta.astype(f), np.abs(b).astype(f)).astype(np.float64) * (1 + 2 * kk * U)
+  if out_act == 3:
+    inner = inner + K_TANH * U * np.abs(ref)
+  else:
+    assert out_act in (0, 2), "no bound is derived for output activation %d" % out_act
+  r = U if op == "bwd_weight" else R_OUT[dtype]
+  return r * np.abs(ref) + (1 + r) * inner + 1e-300
+
+
+def check_elements(name, got, ref, bound):
+  """Per element; prints the worst |got - ref| / bound first and names the first elements outside it (test_gpu_bfmnet_ops.check)."""
+  return check(name, got, ref, bound)
 
 
 def fwd_device(case, dtype):
@@ -107,21 +223,28 @@ def fwd_device(case, dtype):
   return gu.conv_fwd(d, x, sc, sh, wt, b, dtype)
 
 
-def fwd_oracle(case, dtype):
+@functools.lru_cache(maxsize=2)
+def fwd_reference(case, dtype):
+  """(float64 reference, per-element bound)"""
   kind, n, h, w, cin, cout, k, s, p, in_act, out_act, affine = case
   x, wt, b, sc, sh = make_case(case)
-  xa = ref_input(x, sc, sh, in_act, dtype)
-  wr = gu.rounded(wt, dtype)
-  yr = ops.conv2d_fwd(xa, wr, np.float32(b).astype(np.float64), s, p) if kind == 0 else ops.deconv4s2_fwd(xa, wr, np.float32(b).astype(np.float64))
-  return ACTS[out_act](yr)
+  xa, delta = ref_operand(x, sc, sh, in_act, dtype)
+  wr, b64 = gu.rounded(wt, dtype), np.float32(b).astype(np.float64)
+  yr = ACTS[out_act](conv_op(case, "fwd", xa, wr, b64))
+  return yr, element_bound(case, "fwd", dtype, yr, xa, wr, b64, delta, out_act)
+
+
+def fwd_oracle(case, dtype):
+  return fwd_reference(case, dtype)[0]
 
 
 @pytest.mark.parametrize("dtype", ["f32", "bf16"])
 @pytest.mark.parametrize("case", FWD_CASES)
 def test_conv_fwd(case, dtype):
-  y, yr = fwd_device(case, dtype), fwd_oracle(case, dtype)
+  y, (yr, bound) = fwd_device(case, dtype), fwd_reference(case, dtype)
   assert np.isfinite(y).all()
   assert gu.rel_l2(y, yr) < TOL[dtype], gu.rel_l2(y, yr)
+  check_elements("fwd %s %s" % (dtype, case), y, yr, bound)
 
 
 @pytest.mark.parametrize("dtype", ["f32", "bf16"])
@@ -151,24 +274,41 @@ def bwd_data_device(case, dtype):
   return gu.conv_bwd_data(d, dy, wt, dtype)
 
 
-def bwd_data_oracle(case, dtype):
+@functools.lru_cache(maxsize=2)
+def bwd_data_reference(case, dtype):
+  """(float64 reference, per-element bound)"""
   kind, n, h, w, cin, cout, k, s, p, in_act, out_act, affine = case
   x, wt, b, sc, sh = make_case(case)
   ho, wo = gu.out_hw(gu.conv_desc(kind, n, h, w, cin, cout, k, s, p, dtype))
   dy = np.random.default_rng(7).normal(size=(n, ho, wo, cout))
   dyr, wr = gu.rounded(dy, dtype), gu.rounded(wt, dtype)
-  if kind == 0:
-    dxr, _, _ = ops.conv2d_bwd(np.zeros((n, h, w, cin)), wr, dyr, s, p, need_dw=False)
-  else:
-    dxr, _, _ = ops.deconv4s2_bwd(np.zeros((n, h, w, cin)), wr, dyr)
-  return dxr
+  dxr = conv_op(case, "bwd_data", dyr, wr)
+  return dxr, element_bound(case, "bwd_data", dtype, dxr, dyr, wr)
+
+
+def bwd_data_oracle(case, dtype):
+  return bwd_data_reference(case, dtype)[0]
 
 
 @pytest.mark.parametrize("dtype", ["f32", "bf16"])
 @pytest.mark.parametrize("case", BWD_CASES)
 def test_conv_bwd_data(case, dtype):
-  dx, dxr = bwd_data_device(case, dtype), bwd_data_oracle(case, dtype)
+  dx, (dxr, bound) = bwd_data_device(case, dtype), bwd_data_reference(case, dtype)
   assert gu.rel_l2(dx, dxr) < TOL[dtype], gu.rel_l2(dx, dxr)
+  check_elements("bwd_data %s %s" % (dtype, case), dx, dxr, bound)
+
+
+@functools.lru_cache(maxsize=2)
+def bwd_weight_reference(case, dtype):
+  """(float64 reference, per-element bound)"""
+  kind, n, h, w, cin, cout, k, s, p, in_act, out_act, affine = case
+  x, wt, b, sc, sh = make_case(case)
+  ho, wo = gu.out_hw(gu.conv_desc(kind, n, h, w, cin, cout, k, s, p, dtype))
+  dy = np.random.default_rng(7).normal(size=(n, ho, wo, cout))
+  xa, delta = ref_operand(x, sc, sh, in_act, dtype)
+  dyr = gu.rounded(dy, dtype)
+  dwr = conv_op(case, "bwd_weight", xa, dyr)
+  return dwr, element_bound(case, "bwd_weight", dtype, dwr, xa, dyr, None, delta)
 
 
 @pytest.mark.parametrize("dtype", ["f32", "bf16"])
@@ -180,13 +320,9 @@ def test_conv_bwd_weight(case, dtype):
   ho, wo = gu.out_hw(d)
   dy = np.random.default_rng(7).normal(size=(n, ho, wo, cout))
   dw = gu.conv_bwd_weight(d, x, sc, sh, dy, wt.shape, dtype)
-  xa = ref_input(x, sc, sh, in_act, dtype)
-  dyr = gu.rounded(dy, dtype)
-  if kind == 0:
-    _, dwr, _ = ops.conv2d_bwd(xa, np.zeros_like(wt), dyr, s, p, need_dx=False)
-  else:
-    _, dwr, _ = ops.deconv4s2_bwd(xa, np.zeros_like(wt), dyr, need_dx=False)
+  dwr, bound = bwd_weight_reference(case, dtype)
   assert gu.rel_l2(dw, dwr) < TOL[dtype], gu.rel_l2(dw, dwr)
+  check_elements("bwd_weight %s %s" % (dtype, case), dw, dwr, bound)
 
 
 @pytest.mark.parametrize("dtype", ["f32", "bf16"])
