@@ -21,6 +21,7 @@
  *   vp_landmark_distance replaces nothing: the reference judges BFMNet by the montage alone (68-landmark distance, on the device)
  *   vp_puppet_*        replaces  infer_bfmvid.py:110-121, :223-224, :229-238 for the rows of many talkers (stream groups)
  *   vp_jpeg_*          replaces  infer_bfmvid.py:243-244 (cv2.imwrite per frame) with a baseline JPEG encode on the device
+ *   vp_png_*           replaces  train_pixrefer.py:105-118 (five tf.summary.image calls: PNG through zlib on the host) with a PNG encode on the device
  *   vp_avimux_*        replaces  infer_bfmvid.py:245 (ffmpeg over the .jpg files and the wav) with Motion-JPEG + PCM AVI segments built on the device
  *   vp_jpegdec_*       replaces  generator/generator.py:956-1019 (cv2.imread per sample) and loader.py ImageLoader with a baseline JPEG decode on the device
  *   vp_pcmin_*         replaces  generator/loader.py:39-54 (WavLoader: scale, channel mean, resample_poly over a whole file) for live PCM
@@ -823,6 +824,61 @@ long long vp_pcmin_ready(const vp_pcmin_t* h, const long long* in_frames, const 
  * bytes long and starts at the next 16-byte boundary after the previous one.  pcm_out: DEVICE float32, the slots' new samples packed in
  * slot order - the pcm argument of vp_bfmstream_group_push with n[s] = out_samples[s].  One launch on `stream`; never waits, never allocates. */
 int vp_pcmin_push(vp_pcmin_t* h, const void* raw, const long long* in_frames, const int* finish, float* pcm_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * PNG encoding of device tensors: replaces the host PNG encode behind the reference's image summaries (train_pixrefer.py:105-118: five
+ * tf.summary.image calls, up to three images each, every summary step) for the frames of a whole launch.  csrc/png_enc.hip; the byte
+ * stream is restated in tests/png_ref.py, which is its definition.
+ *
+ * Source: a DEVICE tensor [frames, height, width, pixel_stride], uint8 or float32, of which `channels` components starting at
+ * channel_offset are encoded in place (Inputs[..., 3:6] of the 6-channel training input needs no slice copy).  uint8 passes through.
+ * float32 follows tf.image.convert_image_dtype(x, tf.uint8): (uint8) trunc(x * 255.5f).  Outside [0, 1] the reference's unsaturated cast
+ * is undefined; here values below 0 and NaN give 0, values from 255 / 255.5 up give 255.
+ *
+ * The file is PNG 1.2, bit depth 8, colour type 0 / 2 / 6 (1 / 3 / 4 channels), no interlace: signature, IHDR, IDAT(78 01), one IDAT
+ * per strip, IDAT(03 00, Adler-32), IEND.  A strip is R = vp_png_rows_per_strip rows: the largest R <= 16 with
+ * (2 R + 1) * width * channels + R + 32 <= 53248, so that a strip's raw rows, filtered bytes and bit buffer fit one workgroup's LDS;
+ * width * channels is therefore at most VP_PNG_MAX_ROW_BYTES (R = 1).  Per strip: PNG filters (filter -1: per row the one with the
+ * smallest sum of absolute signed residuals, the lowest number on a tie; 0 .. 4: that filter on every row), literals and runs (matches
+ * at distance 1, 3 .. 258 long; no other LZ77), one dynamic-Huffman block (length limits 15 / 7, no repeat symbols, one distance code)
+ * closed by an empty stored block as zlib's sync flush writes it, or, when that is not shorter, one stored block and the empty one.
+ *
+ * Capacity.  A stored strip takes its filtered bytes + 22, so a file's size has a bound that depends on the descriptor alone:
+ * vp_png_frame_capacity (47 + sum over strips (rows * (1 + width * channels) + 22) + 30, rounded up to 256).  There is no "did not fit".
+ * ---------------------------------------------------------------------------------------------- */
+#define VP_PNG_MAX_FRAMES 4096
+#define VP_PNG_MAX_HEIGHT 65535
+#define VP_PNG_MAX_ROW_BYTES 17738
+#define VP_PNG_MAX_PIXEL_STRIDE 64
+enum vp_png_dtype { VP_PNG_U8 = 0, VP_PNG_F32 = 1 };
+typedef struct vp_png_desc {
+  uint32_t struct_bytes;  /* sizeof(vp_png_desc) of the caller's build: must equal vp_png_desc_size() */
+  int32_t max_frames;     /* frames per vp_png_encode: 1 .. VP_PNG_MAX_FRAMES */
+  int32_t height;         /* 1 .. VP_PNG_MAX_HEIGHT */
+  int32_t width;          /* width * channels: 1 .. VP_PNG_MAX_ROW_BYTES */
+  int32_t channels;       /* 1 (grey), 3 (RGB) or 4 (RGBA) */
+  int32_t filter;         /* -1 adaptive (the default), 0 None, 1 Sub, 2 Up, 3 Average, 4 Paeth on every row */
+} vp_png_desc;
+size_t vp_png_desc_size(void);
+typedef struct vp_png vp_png_t;
+/* 0 on a refused descriptor (vp_last_error says why) */
+size_t vp_png_workspace_bytes(const vp_png_desc* d);
+size_t vp_png_frame_capacity(const vp_png_desc* d);
+int vp_png_rows_per_strip(const vp_png_desc* d);
+/* Host only apart from one upload (the 47 bytes before the strips); may wait, once per encoder */
+int vp_png_create(const vp_png_desc* d, void* workspace, size_t workspace_bytes, void* stream, vp_png_t** out);
+/* src: see above (src_dtype a vp_png_dtype; float32 on a 4-byte boundary; channel_offset + channels <= pixel_stride <=
+ * VP_PNG_MAX_PIXEL_STRIDE), 1 .. max_frames frames.  out: DEVICE bytes, frame f's file starts at out + f * out_row_bytes, out_row_bytes
+ * at least the capacity rule's bound; out_bytes: DEVICE int [frames], the file's length (rows f >= frames are not touched).  Two launches
+ * on `stream`; never waits, never allocates; a bad argument is refused with VP_ERR_ARG before anything is enqueued.  Replaces the PNG
+ * encodes of train_pixrefer.py:105-118. */
+int vp_png_encode(vp_png_t* h, const void* src, int src_dtype, int pixel_stride, int channel_offset, int frames, unsigned char* out,
+                  size_t out_row_bytes, int* out_bytes, void* stream);
+/* "strips": int32 [max_frames, strips, 4, 1] of the last encode: the strip's IDAT chunk bytes, its Adler-32 a and b, 1 when stored */
+int vp_png_tensor(vp_png_t* h, const char* name, void** ptr, int64_t shape[4]);
+/* Host only: the bytes before the first strip (signature, IHDR, IDAT(78 01)), *n their count; host_out may be NULL to ask for the count */
+int vp_png_header(const vp_png_t* h, unsigned char* host_out, size_t cap, size_t* n);
+void vp_png_destroy(vp_png_t* h);
 
 /* ------------------------------------------------------------------------------------------------
  * JPEG decoding of training frames on the device: replaces the two cv2.imread calls per sample of generator/generator.py:956-1019 and

@@ -59,6 +59,14 @@ class JpegDesc(ctypes.Structure):
               ("quality", ctypes.c_int32)]
 
 
+class PngDesc(ctypes.Structure):
+  _fields_ = [("struct_bytes", ctypes.c_uint32), ("max_frames", ctypes.c_int32), ("height", ctypes.c_int32), ("width", ctypes.c_int32),
+              ("channels", ctypes.c_int32), ("filter", ctypes.c_int32)]
+
+
+PNG_U8, PNG_F32 = 0, 1               # include/vp_hip.h vp_png_dtype
+
+
 class JpegDecDesc(ctypes.Structure):
   _fields_ = [("struct_bytes", ctypes.c_uint32), ("max_files", ctypes.c_int32), ("max_height", ctypes.c_int32), ("max_width", ctypes.c_int32),
               ("max_file_bytes", ctypes.c_int32), ("max_segments_per_file", ctypes.c_int32), ("bgr", ctypes.c_int32)]
@@ -223,6 +231,15 @@ _SIGNATURES = {
     "vp_jpeg_tensor": (ctypes.c_int, [_P, ctypes.c_char_p, ctypes.POINTER(_P), ctypes.POINTER(ctypes.c_int64)]),
     "vp_jpeg_header": (ctypes.c_int, [_P, _P, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]),
     "vp_jpeg_destroy": (None, [_P]),
+    "vp_png_desc_size": (ctypes.c_size_t, []),
+    "vp_png_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(PngDesc)]),
+    "vp_png_frame_capacity": (ctypes.c_size_t, [ctypes.POINTER(PngDesc)]),
+    "vp_png_rows_per_strip": (ctypes.c_int, [ctypes.POINTER(PngDesc)]),
+    "vp_png_create": (ctypes.c_int, [ctypes.POINTER(PngDesc), _P, ctypes.c_size_t, _P, ctypes.POINTER(_P)]),
+    "vp_png_encode": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, ctypes.c_size_t, _P, _P]),
+    "vp_png_tensor": (ctypes.c_int, [_P, ctypes.c_char_p, ctypes.POINTER(_P), ctypes.POINTER(ctypes.c_int64)]),
+    "vp_png_header": (ctypes.c_int, [_P, _P, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]),
+    "vp_png_destroy": (None, [_P]),
     "vp_jpegdec_desc_size": (ctypes.c_size_t, []),
     "vp_jpegdec_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(JpegDecDesc)]),
     "vp_jpegdec_create": (ctypes.c_int, [ctypes.POINTER(JpegDecDesc), _P, ctypes.c_size_t, ctypes.POINTER(_P)]),
@@ -372,6 +389,10 @@ def lib():
       want = int(l.vp_jpeg_desc_size())
       if want != ctypes.sizeof(JpegDesc):
         raise RuntimeError("%s: vp_jpeg_desc is %d bytes in the library, %d in this binding" % (LIB_PATH, want, ctypes.sizeof(JpegDesc)))
+    if hasattr(l, "vp_png_desc_size") and l.vp_png_desc_size.argtypes is not None:
+      want = int(l.vp_png_desc_size())
+      if want != ctypes.sizeof(PngDesc):
+        raise RuntimeError("%s: vp_png_desc is %d bytes in the library, %d in this binding" % (LIB_PATH, want, ctypes.sizeof(PngDesc)))
     if hasattr(l, "vp_jpegdec_desc_size") and l.vp_jpegdec_desc_size.argtypes is not None:
       want = int(l.vp_jpegdec_desc_size())
       if want != ctypes.sizeof(JpegDecDesc):

@@ -7,7 +7,8 @@
 One process per GPU; under torch.distributed.run (WORLD_SIZE > 1) the G/D gradient arenas are
 all-reduced over RCCL every step (plain data parallel, per-replica batch statistics).
 Extra, optional flags (defaults reproduce the reference run): --steps, --batch_size, --img_size, --eval_list / --eval_step /
---eval_frames (held-out PSNR, SSIM and L1 next to the losses: pixrefer/heldout.py), --resume (continue from the
+--eval_frames (held-out PSNR, SSIM and L1 next to the losses: pixrefer/heldout.py), --tensorboard (the reference's scalar and image
+summaries as an event file in log/summary_pixrefer, the images PNG-encoded on the device: pixrefer/summaries.py), --resume (continue from the
 latest checkpoint in ckpt_pixrefer - the block the reference keeps commented out at train_pixrefer.py:93-99; what a restart after a
 lost rank does: a FRESH process from the last checkpoint, never a re-exec of one that touched the GPU).
 """
@@ -60,6 +61,9 @@ def parse_options(argv=None):
                         help='with --eval_list: evaluate every N steps (default: on the steps that print the losses; overrides amd.eval_step)')
   cmd_parser.add_option('--eval_frames', type="int", dest="eval_frames", default=None, metavar="K",
                         help='with --eval_list: the number of held-out triptychs (default 8; overrides amd.eval_frames)')
+  cmd_parser.add_option('--tensorboard', action="store_true", dest="tensorboard", default=False,
+                        help='write the reference\'s summaries (three losses, five image summaries) to an event file in summary_dir on '
+                             'the steps that print the losses (overrides amd.tensorboard; absent: no event file)')
   argv = list(sys.argv[1:] if argv is None else argv)
   for i, a in enumerate(argv):                     # --device_jpeg_scan [N]: the bare flag means 128
     if a == '--device_jpeg_scan' and not (i + 1 < len(argv) and argv[i + 1].isdigit()):
@@ -145,6 +149,13 @@ def main(argv=None):
                            crop_ratio=train_generator.crop_ratio, device_jpeg_decode=train_generator.device_jpeg_decode)
     eval_step = int(opts.eval_step or amd_keys.get('eval_step') or max(1, params.summary_step // 2))
     logger.info('held-out evaluation: %d frames of %s every %d steps', held_out.frames, eval_list, eval_step)
+  # --tensorboard / amd: {tensorboard: true}: the reference's summaries (train_pixrefer.py:101-132, 146) on rank 0.  Off by default, and
+  # then nothing here changes
+  tb = None
+  if (opts.tensorboard or amd_keys.get('tensorboard', False) in (True, 'true', 'yes', 1)) and rank == 0:
+    from voicepuppet_amd.pixrefer.summaries import TrainSummaries
+    tb = TrainSummaries(params.summary_dir, batch_size, vid2vidnet.engine.desc.height)
+    logger.info('summaries: %s', tb.writer.path)
   # --resume / amd: {resume: true}: continue from the latest checkpoint of save_dir.  `epochs` stays the TOTAL number of iterations of
   # the run (the learning-rate schedule is a function of global_step, which the checkpoint restores), so a run restarted at
   # global_step 120000 of 200000 trains the remaining 40000 iterations, not another 100000.  The data pipeline is NOT part of a
@@ -206,6 +217,8 @@ def main(argv=None):
       fetch += [train_nodes['Gen_loss_GAN'], train_nodes['Gen_loss_L1'], train_nodes['Discrim_loss']]
     vals = sess.run(fetch)
     lr, global_step = vals[1], vals[2]
+    # the five image summaries read the step's own tensors: enqueued behind the step, before the next batch is drawn
+    tb_pending = tb.enqueue(vid2vidnet.engine) if (tb is not None and summary) else None
     if dog is not None:
       ev = torch.cuda.Event()
       ev.record()
@@ -224,6 +237,8 @@ def main(argv=None):
       logger.info('%.1f frames/s', fps)
       eng = vid2vidnet.engine
       save_image(os.path.join(params.summary_dir, 'outputs_%d.png' % global_step), ((eng.tensor('Outputs_raw')[0] + 1) / 2).cpu().numpy())
+      if tb is not None:
+        tb.write(global_step, (discrim_loss, gen_loss_GAN, gen_loss_L1), tb_pending)
 
     ### Save checkpoint
     if (global_step % params.save_step == 0 and rank == 0):
@@ -240,6 +255,8 @@ def main(argv=None):
         for suffix in ('.index', '.data-00000-of-00001'):
           if os.path.exists(old + suffix):
             os.remove(old + suffix)
+  if tb is not None:
+    tb.close()
   if dog is not None:
     dog.close()
   if world > 1:
