@@ -19,6 +19,8 @@
  *                             and voicepuppet/bfmnet/infer_bfmnet.py:212-216 (view 1)
  *   vp_sheet_tile_u8   replaces  utils/bfm_visual.py:125-128 (cvtColor + the numpy paste of a tile into big_img)
  *   vp_landmark_distance replaces nothing: the reference judges BFMNet by the montage alone (68-landmark distance, on the device)
+ *   vp_bfmfit_*        replaces  infer_bfmvid.py:47-74 and datasets/make_data_from_GRID.py:193-214 (FaceReconModel.pb, a frozen TF1 ResNet) for the
+ *                             identity, expression and pose of the 257 coefficients: a float64 fit to 68 landmarks, batched over frames
  *   vp_puppet_*        replaces  infer_bfmvid.py:110-121, :223-224, :229-238 for the rows of many talkers (stream groups)
  *   vp_jpeg_*          replaces  infer_bfmvid.py:243-244 (cv2.imwrite per frame) with a baseline JPEG encode on the device
  *   vp_png_*           replaces  train_pixrefer.py:105-118 (five tf.summary.image calls: PNG through zlib on the host) with a PNG encode on the device
@@ -577,6 +579,42 @@ int vp_bfm_reconstruct_view(const vp_bfm_model* m, const float* coeff, const dou
 int vp_sheet_tile_u8(const unsigned char* tiles, int n, int h, int w, unsigned char* sheet, int sheet_rows, int sheet_cols, int first_cell,
                      int swap_rb, void* stream);
 int vp_landmark_distance(const double* proj_a, const double* proj_b, const int* keypoints, int frames, int nver, double* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Fit of BFM coefficients to 68 landmarks: the inverse of `Reconstruction` (utils/reconstruct_mesh.py:172-194) for its landmarks_2d.
+ * Replaces the coefficient regression of FaceReconModel.pb (voicepuppet/pixrefer/infer_bfmvid.py:47-74, datasets/make_data_from_GRID.py:193-214)
+ * for identity 0:80, expression 80:144, angles 224:227 and translation 254:257; texture 144:224 and lighting 227:254 are NOT fitted and keep
+ * the template's values.  Unknowns p[150] = [alpha | beta | angles | t]; cost E = sum_k w_k |pi_k(p) - l_k|^2 + lam_id |alpha|^2 + lam_ex |beta|^2,
+ * pi = the forward model above (re-centred shape, ONE rotation (Rz Ry Rx)^T, + t, z -> 10 - z, focal / image_center of the model, y -> 224 - y,
+ * taken at the keypoints).  Levenberg-Marquardt in float64: A = J^T W J + Lambda, g = J^T W r + Lambda p on the free parameters; status 0 when
+ * |g|_inf <= gtol; (A + mu diag A) d = -g by Cholesky; E(p + d) < E(p) accepts and mu <- max(mu / 3, 1e-9), anything else (a non-finite cost
+ * included) rejects and mu <- 4 mu; mu > 1e8: status 2; max_iters accepted steps: status 1; non-finite landmarks or start values: status 3 and
+ * the start values go back.  mu0 = 1e-3.  Every loop is bounded by these rules.
+ * The two costs of that comparison leave out the regularisation of the blocks that are not free (the same number on both sides; it would only
+ * set their rounding); the reported E is the whole cost.
+ *   keypoints [68]    HOST int array, 0-based vertex indices (facemodel.keypoints); one outside 0 .. nver-1 is refused before any launch
+ *   table_ready       0: the keypoint rows of the model are gathered into the workspace first (one more launch); != 0: the caller
+ *                     states that an earlier call with this model, these keypoints and this workspace has done that
+ *   landmarks         [frames,68,2] float64 (x, y) pixels of the 224 image
+ *   weights           NULL (all 1), [68] (weights_per_frame = 0) or [frames,68]; w <= 0 drops the landmark
+ *   init              [frames,257] float32: start values and template
+ *   params            optional [frames,150] float64: p as float64 on return; with params_in != 0 also the start values (instead of init's)
+ *   free_mask         bits 1 identity, 2 expression, 4 angles, 8 translation: 15 full fit, 14 tracking, 12 pose only
+ *   coeff             [frames,257] float32 (may be init): the template with the fitted blocks overwritten; other blocks bit-equal to init
+ *   report            [frames,4] float64 = { status, accepted iterations, final E, final |g|_inf }
+ * One workgroup per frame, fixed summation order: a frame's coeff, params and report are the same bits alone and in any batch.
+ * vp_bfmfit_identity_step: one Gauss-Newton step on an alpha shared by all frames (row 0's alpha is taken as the current one), beta and pose of
+ * every frame fixed: A = sum_t J_a^T W J_a + T lam_id I, g = sum_t J_a^T W r_t + T lam_id alpha, summed over blocks of 64 consecutive frames
+ * and then over the blocks, both in frame order (no atomics); alpha + d goes to columns 0:80 of every row of params (and of coeff, when
+ * non-NULL, as float32).  Frames with non-finite landmarks or parameters take no part (T counts the others).  Neither call waits.
+ * ---------------------------------------------------------------------------------------------- */
+size_t vp_bfmfit_workspace_bytes(int frames);
+int vp_bfmfit_fit(const vp_bfm_model* m, const int* keypoints, int table_ready, const double* landmarks, const double* weights, int weights_per_frame,
+                  const float* init, double* params, int params_in, int frames, double lam_id, double lam_ex, double gtol, int max_iters, int free_mask,
+                  float* coeff, double* report, void* workspace, size_t workspace_bytes, void* stream);
+int vp_bfmfit_identity_step(const vp_bfm_model* m, const int* keypoints, int table_ready, const double* landmarks, const double* weights,
+                            int weights_per_frame, double* params, float* coeff, int frames, double lam_id, void* workspace, size_t workspace_bytes,
+                            void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * BFMNet TRAINING step (voicepuppet/bfmnet/bfmnet.py:215-323, tinynet.py:7-212): the non-GEMM kernels, float32 NHWC,

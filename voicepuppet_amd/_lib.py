@@ -304,6 +304,10 @@ _SIGNATURES = {
                                                ctypes.c_size_t, _P]),
     "vp_sheet_tile_u8": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P]),
     "vp_landmark_distance": (ctypes.c_int, [_P, _P, _P, ctypes.c_int, ctypes.c_int, _P, _P]),
+    "vp_bfmfit_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int]),
+    "vp_bfmfit_fit": (ctypes.c_int, [_P, _P, ctypes.c_int, _P, _P, ctypes.c_int, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double,
+                                     ctypes.c_double, ctypes.c_int, ctypes.c_int, _P, _P, _P, ctypes.c_size_t, _P]),
+    "vp_bfmfit_identity_step": (ctypes.c_int, [_P, _P, ctypes.c_int, _P, _P, ctypes.c_int, _P, _P, ctypes.c_int, ctypes.c_double, _P, ctypes.c_size_t, _P]),
     "vp_render_colors_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "vp_render_colors": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                         ctypes.c_int, _P, _P]),
