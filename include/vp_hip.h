@@ -20,7 +20,8 @@
  *   vp_sheet_tile_u8   replaces  utils/bfm_visual.py:125-128 (cvtColor + the numpy paste of a tile into big_img)
  *   vp_landmark_distance replaces nothing: the reference judges BFMNet by the montage alone (68-landmark distance, on the device)
  *   vp_bfmfit_*        replaces  infer_bfmvid.py:47-74 and datasets/make_data_from_GRID.py:193-214 (FaceReconModel.pb, a frozen TF1 ResNet) for the
- *                             identity, expression and pose of the 257 coefficients: a float64 fit to 68 landmarks, batched over frames
+ *                             identity, expression and pose of the 257 coefficients: a float64 fit to 68 landmarks, batched over frames;
+ *                             vp_bfmfit_observe / vp_bfmfit_appearance for texture and lighting: a float64 fit to the photo's pixels
  *   vp_puppet_*        replaces  infer_bfmvid.py:110-121, :223-224, :229-238 for the rows of many talkers (stream groups)
  *   vp_jpeg_*          replaces  infer_bfmvid.py:243-244 (cv2.imwrite per frame) with a baseline JPEG encode on the device
  *   vp_png_*           replaces  train_pixrefer.py:105-118 (five tf.summary.image calls: PNG through zlib on the host) with a PNG encode on the device
@@ -583,8 +584,8 @@ int vp_landmark_distance(const double* proj_a, const double* proj_b, const int* 
 /* ------------------------------------------------------------------------------------------------
  * Fit of BFM coefficients to 68 landmarks: the inverse of `Reconstruction` (utils/reconstruct_mesh.py:172-194) for its landmarks_2d.
  * Replaces the coefficient regression of FaceReconModel.pb (voicepuppet/pixrefer/infer_bfmvid.py:47-74, datasets/make_data_from_GRID.py:193-214)
- * for identity 0:80, expression 80:144, angles 224:227 and translation 254:257; texture 144:224 and lighting 227:254 are NOT fitted and keep
- * the template's values.  Unknowns p[150] = [alpha | beta | angles | t]; cost E = sum_k w_k |pi_k(p) - l_k|^2 + lam_id |alpha|^2 + lam_ex |beta|^2,
+ * for identity 0:80, expression 80:144, angles 224:227 and translation 254:257; texture 144:224 and lighting 227:254 are NOT fitted by these two calls and keep
+ * the template's values (vp_bfmfit_appearance, below, fits them to a photo).  Unknowns p[150] = [alpha | beta | angles | t]; cost E = sum_k w_k |pi_k(p) - l_k|^2 + lam_id |alpha|^2 + lam_ex |beta|^2,
  * pi = the forward model above (re-centred shape, ONE rotation (Rz Ry Rx)^T, + t, z -> 10 - z, focal / image_center of the model, y -> 224 - y,
  * taken at the keypoints).  Levenberg-Marquardt in float64: A = J^T W J + Lambda, g = J^T W r + Lambda p on the free parameters; status 0 when
  * |g|_inf <= gtol; (A + mu diag A) d = -g by Cholesky; E(p + d) < E(p) accepts and mu <- max(mu / 3, 1e-9), anything else (a non-finite cost
@@ -615,6 +616,61 @@ int vp_bfmfit_fit(const vp_bfm_model* m, const int* keypoints, int table_ready, 
 int vp_bfmfit_identity_step(const vp_bfm_model* m, const int* keypoints, int table_ready, const double* landmarks, const double* weights,
                             int weights_per_frame, double* params, float* coeff, int frames, double lam_id, void* workspace, size_t workspace_bytes,
                             void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Photometric fit of texture (coefficients 144:224) and lighting (227:254) to a photo's pixels, the geometry fixed at what vp_bfmfit_fit
+ * returned: the inverse of face_color = Illumination_layer(Texture_formation(tex_coeff), face_norm . rotation, gamma)
+ * (utils/reconstruct_mesh.py:58-62, :129-168, as Reconstruction :172-194 calls them; render_face rasterises that colour,
+ * voicepuppet/pixrefer/infer_bfmvid.py:91-108).  Replaces, for those 107 coefficients, FaceReconModel.pb (infer_bfmvid.py:47-74).
+ * For frame f, vertex v, channel c (RGB, :57), unknowns p[107] = [delta(80) | gamma(27)]:
+ *   T_vc = meantex_vc + sum_j texBase[3v+c, j] delta_j                                   (:59)
+ *   L_vc = sum_k Y_vk (gamma_ck + init_k),  init = (0.8, 0, ..., 0), gamma viewed as [3,9]  (:133-135, :159-161)
+ *   Y_v  = the nine SH terms (:137-155) of the ROTATED normal n_v . R (:182)
+ *   r_vc = T_vc L_vc - I_vc,  I_v the photo sampled at the vertex's projection;  colours in the reference's 0 .. 255 units
+ *   E    = (1/W) sum_v w_v sum_c r_vc^2 + lam_tex |delta|^2 + lam_gamma |gamma|^2,   W = 3 sum_v w_v
+ * (1/W keeps lam meaningful at any vertex count.)  lam_tex = lam_gamma = 1 are the callers' defaults and are UNTUNED on real photos.
+ *
+ * vp_bfmfit_observe (inverts :179-186, the geometry half of Reconstruction): face_shape, the one-ring normals, n . R and face_projection
+ * exactly as vp_bfm_reconstruct_view computes them (the same device code), then
+ *   sh [frames,nver,9]       Y_v
+ *   observed [frames,nver,3] the photo sampled bilinearly, in float64, at (a x + bx, a y + by), (x, y) = face_projection, integer
+ *                            coordinates = pixel centres; 0 where the position is outside
+ *   weight [frames,nver]     vertex_weights_v max(0, (n_v . R)_z) inside: the camera sits at z = +10 (:103), normals facing it have positive z;
+ *                            inside = 1 iff 0 <= px <= W-1 and 0 <= py <= H-1
+ * coeff [frames,257] float32; rotation [frames,9] float64 = Compute_rotation_matrix(coeff[:, 224:227]) from the host, as for
+ * vp_bfm_reconstruct_view; frames <= 65535; photo [photo_frames,H,W,3] uint8 RGB, photo_frames 1 (shared) or frames, H, W >= 2; affine [frames,3] float64
+ * (a, bx, by): 224-image pixels -> photo pixels; vertex_weights NULL (ones) or [nver] float64 (a skin mask).  All device pointers.
+ * Left out: self-occlusion (no z-buffer test; the facing weight is smooth, so no threshold can flip) and any pre-filter when a > 1.
+ *
+ * vp_bfmfit_appearance (inverts :58-62 and :129-168): Levenberg-Marquardt in float64 on p, the rule of vp_bfmfit_fit with
+ *   A = J^T W J / W + Lambda, g = J^T W r / W + Lambda p;  d r_vc / d delta_j = L_vc texBase[3v+c, j];  d r_vc / d gamma_ck = Y_vk T_vc
+ *   (A + mu diag A) d = -g by Cholesky;  E(p + d) < E(p) accepts and mu <- max(mu / 3, 1e-9); anything else rejects and mu <- 4 mu;
+ *   mu > 1e8: status 2;  mu0 = 1e-3;  a factorisation that fails raises mu the same way without an evaluation
+ *   status 0 when |g|_inf <= gtol E, or E = 0: a RELATIVE test, because the float64 floor of the accept test scales with E
+ * A fit is a fixed chain of max_trials rounds (accumulate, step) and nothing is read back.  The accumulate stage evaluates (A, g, E) at
+ * the trial point: blocks own vertex slabs (the partition a function of nver alone) and write partial systems per (frame, slab); a second
+ * launch adds them in slab order, no atomics.  The step kernel (one workgroup per frame) applies the rule, keeps the system of the last accepted point, solves for the next
+ * trial point and sets the status; both leave a frame with a status alone.  A frame's coeff, params and report are therefore the same
+ * bits alone and in any batch.  Status 1: max_trials evaluations were used up; status 3: a non-finite sh / weight / observed / start
+ * value or sum_v w_v = 0, and the start values go back.
+ *   sh, weight, observed   vp_bfmfit_observe's outputs (weight <= 0 drops a vertex)
+ *   coeff_in               [frames,257] float32: template, and start values unless params_in
+ *   params                 optional [frames,107] float64: p on return; with params_in != 0 also the start values
+ *   stages                 3 in every use but timing.  1 / 2 enqueue only the accumulate stage / only the step launches of the chain, so that
+ *                          the two can be timed apart: with 1, coeff, report and params are NOT written (undefined on return); with 2 they
+ *                          come from whatever partial sums the workspace holds
+ *   coeff                  [frames,257] float32 (may be coeff_in): columns 144:224 and 227:254 fitted, every other column copied
+ *   report                 [frames,4] float64 = { status, accepted steps, E, |g|_inf } at the returned point
+ * Neither call waits.
+ * ---------------------------------------------------------------------------------------------- */
+size_t vp_bfmfit_observe_workspace_bytes(int nver, int ntri, int frames);
+int vp_bfmfit_observe(const vp_bfm_model* m, const float* coeff, const double* rotation, int frames, const unsigned char* photo, int photo_frames,
+                      int height, int width, const double* affine, const double* vertex_weights, double* sh, double* weight, double* observed,
+                      void* workspace, size_t workspace_bytes, void* stream);
+size_t vp_bfmfit_appearance_workspace_bytes(int nver, int frames);
+int vp_bfmfit_appearance(const vp_bfm_model* m, const double* sh, const double* weight, const double* observed, const float* coeff_in, double* params,
+                         int params_in, int frames, double lam_tex, double lam_gamma, double gtol, int max_trials, int stages, float* coeff,
+                         double* report, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * BFMNet TRAINING step (voicepuppet/bfmnet/bfmnet.py:215-323, tinynet.py:7-212): the non-GEMM kernels, float32 NHWC,

@@ -3,13 +3,20 @@
 The reference obtains a photo's 257 coefficients and the `bfmcoeff.txt` rows BFMNet is trained on from FaceReconModel.pb, a frozen
 TensorFlow 1 ResNet (voicepuppet/pixrefer/infer_bfmvid.py:47-74, datasets/make_data_from_GRID.py:193-214).  This module gets identity
 (0:80), expression (80:144), angles (224:227) and translation (254:257) from a landmark file instead: it inverts `Reconstruction`
-(utils/reconstruct_mesh.py:172-194) for the 68 landmarks that function returns.  Texture (144:224) and lighting (227:254) are NOT fitted:
-they stay at the caller's template, zeros by default, i.e. the mean albedo under ambient light.
+(utils/reconstruct_mesh.py:172-194) for the 68 landmarks that function returns.  Texture (144:224) and lighting (227:254) come from the
+photo's pixels (`observe`, `fit_appearance`, `enroll(image=...)`; libvp_hip.so: vp_bfmfit_observe, vp_bfmfit_appearance; csrc/bfm_appear.hip),
+with the geometry fixed at the landmark fit's; without a photo they stay at the caller's template, zeros by default, i.e. the mean albedo
+under ambient light.
 
   E(p) = sum_k w_k |pi_k(p) - l_k|^2 + lam_id |alpha|^2 + lam_ex |beta|^2        p = [alpha(80) | beta(64) | angles(3) | t(3)]
 
 minimised per frame by Levenberg-Marquardt in float64, one workgroup per frame (include/vp_hip.h states the rule).
 `report` [frames,4] = (status, accepted iterations, final E, final |g|_inf); status 0 converged, 1 max_iters, 2 stalled, 3 non-finite input.
+
+Appearance: p = [delta(80) | gamma(27)], r_vc = T_vc(delta) L_vc(gamma) - I_vc at the vertices, I the photo sampled at their projections,
+  E(p) = (1/W) sum_v w_v sum_c r_vc^2 + lam_tex |delta|^2 + lam_gamma |gamma|^2,  W = 3 sum_v w_v,  w_v = mask_v max(0, (n_v . R)_z) inside
+by the same rule with a relative stopping test (|g|_inf <= gtol E), as a fixed chain of `max_trials` launch pairs; report as above with
+status 1 = max_trials used up, 3 = non-finite input or no visible vertex.  lam_tex = lam_gamma = 1 are untuned on real photos.
 
 `FaceFitter.fit_sequence` is a FIXED SCHEDULE of block-coordinate descent for a clip of one person (per-frame fits, then identity steps
 alternating with tracking fits), not a minimiser: it stops after `rounds` rounds whatever the cost does.
@@ -23,6 +30,7 @@ import numpy as np
 from . import _lib
 
 NP = 150
+NA = 107                                                    # appearance unknowns: texture 80 | lighting 27
 FREE_ID, FREE_EX, FREE_ANGLES, FREE_T = 1, 2, 4, 8
 FREE = {"all": 15, "tracking": FREE_EX | FREE_ANGLES | FREE_T, "pose": FREE_ANGLES | FREE_T}
 
@@ -46,10 +54,8 @@ def five_points(lm):
   return five[[1, 2, 0, 3, 4]]
 
 
-def crop_alignment(landmarks_xy, img_h, img_w, out_img_size=224, ratio=1.3):
-  """The landmark arithmetic of crop_expand_alignment (utils/utils.py:78-110): the square crop around the landmarks' bounding box, expanded
-  by `ratio` (less where the image ends), resized to out_img_size.  landmarks_xy [68,2] image pixels -> (landmarks in the crop [68,2],
-  center_x, center_y, ratio = out_img_size / crop width)."""
+def _crop_box(landmarks_xy, img_h, img_w, ratio=1.3):
+  """crop_expand_alignment's square (utils/utils.py:78-104): (xy [68,2], center_x, center_y, left, top, width)."""
   xy = np.array(landmarks_xy, np.float64).reshape(-1, 2)
   max_x, max_y = xy[:, 0].max(), xy[:, 1].max()
   min_x, min_y = xy[:, 0].min(), xy[:, 1].min()
@@ -68,6 +74,15 @@ def crop_alignment(landmarks_xy, img_h, img_w, out_img_size=224, ratio=1.3):
     raise ValueError("crop_alignment: the landmarks' centre lies outside the %d x %d image" % (img_w, img_h))
   left = int(round(center_x - width / 2))
   top = int(round(center_y - height / 2))
+  return xy, center_x, center_y, left, top, width
+
+
+def crop_alignment(landmarks_xy, img_h, img_w, out_img_size=224, ratio=1.3):
+  """The landmark arithmetic of crop_expand_alignment (utils/utils.py:78-110): the square crop around the landmarks' bounding box, expanded
+  by `ratio` (less where the image ends), resized to out_img_size.  landmarks_xy [68,2] image pixels -> (landmarks in the crop [68,2],
+  center_x, center_y, ratio = out_img_size / crop width)."""
+  xy, center_x, center_y, left, top, width = _crop_box(landmarks_xy, img_h, img_w, ratio)
+  height = width
   out = np.stack([(xy[:, 0] - left) * out_img_size / width, (xy[:, 1] - top) * out_img_size / height], axis=1)
   return out, center_x, center_y, float(out_img_size) / width
 
@@ -77,6 +92,16 @@ def preprocess_landmarks(lm, lm3D, w0=224, h0=224):
   standard landmarks, [68,3] (BFM/similarity_Lm3D_all.mat's `lm`) or the five points load_lm3d returns.  The five points of both are
   load_lm3d's (:122-127).  Returns (lm_new [68,2]: all 68 in the 224 image the network would have seen, trans_params [5] =
   (w0, h0, 102 / s, t0 - w0/2, h0/2 - t1))."""
+  lm, s, t0, t1, w, h = _similarity(lm, lm3D, w0, h0)
+  flip = np.stack([lm[:, 0], h0 - 1 - lm[:, 1]], axis=1)                                          # :201
+  new = np.stack([flip[:, 0] - t0 + w0 / 2, flip[:, 1] - t1 + h0 / 2], axis=1) / s * 102          # :179
+  new = new - np.array([w / 2 - 112, h / 2 - 112]).reshape(1, 2)                                  # :191
+  lm_new = np.stack([new[:, 0], 223 - new[:, 1]], axis=1)                                         # :209
+  return lm_new, np.array([w0, h0, 102.0 / s, t0 - w0 / 2, h0 / 2 - t1], np.float64)
+
+
+def _similarity(lm, lm3D, w0=224, h0=224):
+  """POS (utils/bfm_load_data.py:148-170) on the five points and process_img's image size (:176-177): (lm [68,2], s, t0, t1, w, h)."""
   lm = np.asarray(lm, np.float64).reshape(68, 2)
   lm3D = np.asarray(lm3D, np.float64)
   x = five_points(lm3D) if lm3D.shape[0] == 68 else lm3D.reshape(5, 3)
@@ -92,10 +117,21 @@ def preprocess_landmarks(lm, lm3D, w0=224, h0=224):
   t0, t1 = k[3], k[7]
   w = np.int32(w0 / s * 102)                                                                      # process_img :176-177
   h = np.int32(h0 / s * 102)
-  new = np.stack([flip[:, 0] - t0 + w0 / 2, flip[:, 1] - t1 + h0 / 2], axis=1) / s * 102          # :179
-  new = new - np.array([w / 2 - 112, h / 2 - 112]).reshape(1, 2)                                  # :191
-  lm_new = np.stack([new[:, 0], 223 - new[:, 1]], axis=1)                                         # :209
-  return lm_new, np.array([w0, h0, 102.0 / s, t0 - w0 / 2, h0 / 2 - t1], np.float64)
+  return lm, s, t0, t1, w, h
+
+
+def photo_affine(landmarks_xy, img_h, img_w, lm3D):
+  """The inverse of preprocess_landmarks o crop_alignment as an affine map, float64: (a, bx, by) with photo (x, y) = (a u + bx, a v + by)
+  for a point (u, v) of the 224 image the fit works in (face_projection's pixels).  One uniform scale: the crop is square and both resizes
+  are isotropic.  Forward, from the two functions: c = (xy - (left, top)) 224 / width;  u = (c_x - t0 + 112) k - (w/2 - 112),
+  v = 223 - ((223 - c_y - t1 + 112) k - (h/2 - 112)),  k = 102 / s (two y flips).  Solved for xy:
+    a = width / (224 k);  bx = left + ((w/2 - 112) / k + t0 - 112) width / 224;  by = top + (335 - t1 - (111 + h/2) / k) width / 224."""
+  xy, _, _, left, top, width = _crop_box(landmarks_xy, img_h, img_w)
+  crop = np.stack([(xy[:, 0] - left) * 224 / width, (xy[:, 1] - top) * 224 / width], axis=1)
+  _, s, t0, t1, w, h = _similarity(crop, lm3D)
+  k = 102.0 / s
+  g = width / 224.0
+  return np.array([g / k, left + ((w / 2 - 112) / k + t0 - 112) * g, top + (335 - t1 - (111 + h / 2) / k) * g], np.float64)
 
 
 def params_of(coeff):
@@ -118,6 +154,10 @@ class FaceFitter:
     self._ws = None
     self._table_ready = False
     self.last_params = None                                 # float64 [frames,150] of the last call
+    self._ws_obs = self._ws_app = None
+    self.last_appearance = None                             # float64 [frames,107] of the last fit_appearance
+    self.last_appearance_report = None                      # enroll(image=...): fit_appearance's report [1,4]
+    self.last_appearance_lams = None                        # (lam_tex, lam_gamma) of the last fit_appearance
     self._torch = torch
 
   def _workspace(self, frames):
@@ -220,13 +260,106 @@ class FaceFitter:
       p = self.last_params
     return coeff, report
 
-  def enroll(self, landmarks_xy, img_h, img_w, lm3D, **fit_args):
+  def _photo(self, photo, T):
+    torch = self._torch
+    t = torch.from_numpy(np.ascontiguousarray(photo)) if isinstance(photo, np.ndarray) else photo
+    if t.dtype != torch.uint8 or t.dim() not in (3, 4) or t.shape[-1] != 3 or (t.dim() == 4 and t.shape[0] not in (1, T)):
+      raise ValueError("photo must be uint8 RGB [H,W,3] or [frames,H,W,3]")
+    t = t.to(self.model.device).contiguous()
+    return t, (1 if t.dim() == 3 else int(t.shape[0])), int(t.shape[-3]), int(t.shape[-2])
+
+  def observe(self, coeff, photo, affine, vertex_weights=None):
+    """What the photo shows at the vertices of Reconstruction(coeff) (vp_bfmfit_observe).  coeff [frames,257] float32; photo [H,W,3] (shared)
+    or [frames,H,W,3] uint8 RGB; affine [3] or [frames,3] float64 (a, bx, by), 224-image pixels -> photo pixels (`photo_affine`);
+    vertex_weights None or [N] float64 (a skin mask).  Returns device float64 (sh [frames,N,9], weight [frames,N], observed [frames,N,3]):
+    the SH terms of the rotated normals, mask x max(0, (n . R)_z) x inside, and the bilinear samples.  The rotation matrices are made on
+    the host from coeff's angles, as reconstruct_view makes them (a device coeff is read back for that); everything else only enqueues.
+    No self-occlusion test and no pre-filter for a > 1."""
+    torch, dev = self._torch, self.model.device
+    from .utils.reconstruct_mesh import Compute_rotation_matrix
+    c = (torch.from_numpy(np.ascontiguousarray(coeff, np.float32)) if isinstance(coeff, np.ndarray) else coeff).to(dev).contiguous()
+    if c.dtype != torch.float32 or c.dim() != 2 or c.shape[1] != 257 or c.shape[0] < 1:
+      raise ValueError("coeff must be float32 [frames,257]")
+    T, N = int(c.shape[0]), self.model.nver
+    angles = coeff[:, 224:227] if isinstance(coeff, np.ndarray) else c[:, 224:227].cpu().numpy()
+    rot = torch.from_numpy(Compute_rotation_matrix(np.asarray(angles, np.float32))).to(dev)
+    img, photo_frames, H, W = self._photo(photo, T)
+    if not isinstance(affine, np.ndarray) and not torch.is_tensor(affine):
+      affine = np.asarray(affine, np.float64)
+    if affine.ndim == 1:
+      affine = (torch.from_numpy(np.tile(affine, (T, 1))) if isinstance(affine, np.ndarray) else affine.reshape(1, 3).repeat(T, 1))
+    aff = self._device(affine, torch.float64, (T, 3), "affine")
+    vw = None if vertex_weights is None else self._device(vertex_weights, torch.float64, (N,), "vertex_weights")
+    sh = torch.empty(T, N, 9, dtype=torch.float64, device=dev)
+    weight = torch.empty(T, N, dtype=torch.float64, device=dev)
+    observed = torch.empty(T, N, 3, dtype=torch.float64, device=dev)
+    n = _lib.lib().vp_bfmfit_observe_workspace_bytes(N, self.model.ntri, T)
+    if self._ws_obs is None or self._ws_obs.numel() < n:
+      self._ws_obs = torch.empty(n, dtype=torch.uint8, device=dev)
+    P = ctypes.c_void_p
+    _lib.check(_lib.lib().vp_bfmfit_observe(ctypes.byref(self.model.c), P(c.data_ptr()), P(rot.data_ptr()), T, P(img.data_ptr()), photo_frames, H, W,
+                                            P(aff.data_ptr()), P(vw.data_ptr() if vw is not None else 0), P(sh.data_ptr()), P(weight.data_ptr()),
+                                            P(observed.data_ptr()), P(self._ws_obs.data_ptr()), self._ws_obs.numel(),
+                                            P(torch.cuda.current_stream().cuda_stream)), "vp_bfmfit_observe")
+    return sh, weight, observed
+
+  def fit_appearance(self, coeff, photo=None, affine=None, observation=None, vertex_weights=None, init=None, params=None, lam_tex=1.0,
+                     lam_gamma=1.0, gtol=1e-6, max_trials=32, _stages=3):
+    """Texture and lighting of coeff [frames,257] float32 (the landmark fit's output: its geometry is kept) from the photo's pixels
+    (vp_bfmfit_appearance).  Either photo + affine (see `observe`) or a ready observation = (sh, weight, observed).  init [frames,257]:
+    start values of columns 144:224 and 227:254 (default: coeff's own); params [frames,107] float64: start from these instead.  Returns
+    (coeff [frames,257] float32 with those columns fitted and every other column coeff's, report [frames,4] float64), device tensors; the
+    float64 solution is kept in `self.last_appearance`.  A fixed chain of `max_trials` rounds; the call only enqueues.  `_stages` is for
+    timing only (scripts/bfm_appearance_latency.py): 1 / 2 enqueue only the accumulate / only the step launches, and what is returned is then
+    undefined."""
+    torch, dev = self._torch, self.model.device
+    if (observation is None) == (photo is None) or (photo is not None and affine is None):
+      raise ValueError("fit_appearance: either photo and affine, or observation = (sh, weight, observed)")
+    c = (torch.from_numpy(np.ascontiguousarray(coeff, np.float32)) if isinstance(coeff, np.ndarray) else coeff).to(dev).contiguous()
+    if c.dtype != torch.float32 or c.dim() != 2 or c.shape[1] != 257 or c.shape[0] < 1:
+      raise ValueError("coeff must be float32 [frames,257]")
+    T, N = int(c.shape[0]), self.model.nver
+    if observation is None:
+      observation = self.observe(coeff, photo, affine, vertex_weights)
+    sh, weight, observed = observation
+    sh = self._device(sh, torch.float64, (T, N, 9), "sh")
+    weight = self._device(weight, torch.float64, (T, N), "weight")
+    observed = self._device(observed, torch.float64, (T, N, 3), "observed")
+    tmpl = c
+    if init is not None:
+      start = self._device(init, torch.float32, (T, 257), "init")
+      tmpl = c.clone()
+      tmpl[:, 144:224], tmpl[:, 227:254] = start[:, 144:224], start[:, 227:254]
+    params_in = params is not None
+    p = self._device(params, torch.float64, (T, NA), "params").clone() if params_in else torch.empty(T, NA, dtype=torch.float64, device=dev)
+    out = torch.empty(T, 257, dtype=torch.float32, device=dev)
+    report = torch.empty(T, 4, dtype=torch.float64, device=dev)
+    n = _lib.lib().vp_bfmfit_appearance_workspace_bytes(N, T)
+    if self._ws_app is None or self._ws_app.numel() < n:
+      self._ws_app = torch.empty(n, dtype=torch.uint8, device=dev)
+    P = ctypes.c_void_p
+    _lib.check(_lib.lib().vp_bfmfit_appearance(ctypes.byref(self.model.c), P(sh.data_ptr()), P(weight.data_ptr()), P(observed.data_ptr()),
+                                               P(tmpl.data_ptr()), P(p.data_ptr()), 1 if params_in else 0, T, float(lam_tex), float(lam_gamma),
+                                               float(gtol), int(max_trials), int(_stages), P(out.data_ptr()), P(report.data_ptr()),
+                                               P(self._ws_app.data_ptr()), self._ws_app.numel(), P(torch.cuda.current_stream().cuda_stream)),
+               "vp_bfmfit_appearance")
+    self.last_appearance, self.last_appearance_lams = p, (float(lam_tex), float(lam_gamma))
+    return out, report
+
+  def enroll(self, landmarks_xy, img_h, img_w, lm3D, image=None, lam_tex=1.0, lam_gamma=1.0, **fit_args):
     """A photo's landmarks [68,2] (image pixels) -> the dictionary infer_bfmvid.py --bfmcoeff reads (np.savez(path, **d)): bfmcoeff [1,257]
     float32, transform_params [5], center_x, center_y, ratio.  crop_alignment, preprocess_landmarks and one full fit; the fit's report
-    [1,4] (device) and the landmarks it was given [68,2] stay in `self.last_report` / `self.last_landmarks`."""
+    [1,4] (device) and the landmarks it was given [68,2] stay in `self.last_report` / `self.last_landmarks`.  With `image` ([img_h,img_w,3]
+    uint8 RGB, numpy or device) texture and lighting are then fitted to it (`photo_affine`, `fit_appearance`; its report in
+    `self.last_appearance_report`); without, they stay zeros."""
     crop, center_x, center_y, ratio = crop_alignment(landmarks_xy, img_h, img_w)
     lm_new, trans_params = preprocess_landmarks(crop, lm3D)
     coeff, report = self.fit(lm_new.reshape(1, 68, 2), **fit_args)
     self.last_report, self.last_landmarks = report, lm_new
+    if image is not None:
+      if tuple(image.shape) != (img_h, img_w, 3):
+        raise ValueError("enroll: image must be [img_h,img_w,3], got %s" % (tuple(image.shape),))
+      coeff, self.last_appearance_report = self.fit_appearance(coeff, photo=image, affine=photo_affine(landmarks_xy, img_h, img_w, lm3D),
+                                                               lam_tex=lam_tex, lam_gamma=lam_gamma)
     return {"bfmcoeff": coeff.cpu().numpy().reshape(1, 257), "transform_params": trans_params, "center_x": center_x, "center_y": center_y,
             "ratio": ratio}

@@ -3,17 +3,21 @@
 """BFM coefficients from a 68-landmark file (voicepuppet_amd.bfmfit.FaceFitter), in place of the reference's FaceReconModel.pb:
 
     python voicepuppet/bfmnet/fit_landmarks.py --photo landmarks.txt --size H W --out photo.npz
+    python voicepuppet/bfmnet/fit_landmarks.py --photo landmarks.txt --image photo.jpg --out photo.npz
     python voicepuppet/bfmnet/fit_landmarks.py --clip landmarks.txt --size H W --out bfmcoeff.txt
 
 --photo: the first line of the landmarks file is enrolled; photo.npz is what infer_bfmvid.py / infer_bfmnet.py take as --bfmcoeff
-         (bfmcoeff [1,257], transform_params [5], center_x, center_y, ratio).
+         (bfmcoeff [1,257], transform_params [5], center_x, center_y, ratio).  With --image (read with PIL as RGB; --size is then the
+         image's own) texture and lighting (coefficients 144:224, 227:254) are fitted to the photo's pixels, with weights --lam_tex and
+         --lam_gamma on their squared norms (defaults 1, untuned on real photos); without it they stay zeros.
 --clip:  every line is a frame of ONE person; the frames are aligned one by one as the reference's data preparation does
          (datasets/make_data_from_GRID.py:193-214), fitted with FaceFitter.fit_sequence, and written as one row of 257 comma-separated
          values per frame: the bfmcoeff.txt that BFMCoeffLoader reads and train_bfmnet.py learns from.
 A landmarks file has one frame per line: 136 comma-separated values x0,y0,...,x67,y67 in pixels of the H x W image (any landmark model
 with the 68-point layout; the reference's README names dlib).  Needs BFM/BFM_model_front.mat and BFM/similarity_Lm3D_all.mat, as the
-reference does.  Texture and lighting coefficients are not fitted (zeros: mean albedo, ambient light).  One line per clip is printed:
-frames, statuses, mean and worst reprojection error in pixels of the 224 image."""
+reference does.  --clip never fits texture and lighting (zeros: mean albedo, ambient light): BFMNet learns expression only.  One line
+per clip is printed: frames, statuses, mean and worst reprojection error in pixels of the 224 image, and with --image the appearance fit's
+status and the RMS colour residual in grey levels."""
 import logging
 import os
 import sys
@@ -70,11 +74,24 @@ def summary_line(name, report, err):
   return '%s: %d frames, status %s, reprojection mean %.3f px, worst %.3f px' % (name, status.shape[0], counts, float(err.mean()), float(err.max()))
 
 
+def appearance_summary(fitter):
+  """', appearance status S, colour RMS R grey levels': R^2 = the report's E without its two regularisation terms (the weighted mean of
+  the squared colour residuals at the fitted point; the lambdas are read back from E's definition: E - lam |p|^2)."""
+  rep = fitter.last_appearance_report.cpu().numpy()[0]
+  p = fitter.last_appearance.cpu().numpy()[0]
+  lam_tex, lam_gamma = fitter.last_appearance_lams
+  data = rep[2] - lam_tex * float(np.sum(p[:80] ** 2)) - lam_gamma * float(np.sum(p[80:] ** 2))
+  return ', appearance status %d, colour RMS %.2f grey levels' % (int(rep[0]), float(np.sqrt(max(data, 0.0))))
+
+
 def parse_options(argv=None):
-  cmd_parser = OptionParser(usage="usage: %prog (--photo LANDMARKS | --clip LANDMARKS) --size H W --out FILE")
+  cmd_parser = OptionParser(usage="usage: %prog (--photo LANDMARKS [--image PHOTO] | --clip LANDMARKS) [--size H W] --out FILE")
   cmd_parser.add_option('--photo', type="string", dest="photo", default=None, help='landmarks file; its first line is enrolled -> npz')
   cmd_parser.add_option('--clip', type="string", dest="clip", default=None, help='landmarks file of one person\'s clip -> bfmcoeff.txt')
-  cmd_parser.add_option('--size', type="int", nargs=2, dest="size", default=None, help='image height and width in pixels')
+  cmd_parser.add_option('--size', type="int", nargs=2, dest="size", default=None, help='image height and width in pixels (optional with --image)')
+  cmd_parser.add_option('--image', type="string", dest="image", default=None, help='--photo: the photo itself; fits texture and lighting to it')
+  cmd_parser.add_option('--lam_tex', type="float", dest="lam_tex", default=1.0, help='--image: weight of |texture coefficients|^2')
+  cmd_parser.add_option('--lam_gamma', type="float", dest="lam_gamma", default=1.0, help='--image: weight of |lighting coefficients|^2')
   cmd_parser.add_option('--out', type="string", dest="out", default=None, help='output file')
   cmd_parser.add_option('--rounds', type="int", dest="rounds", default=3, help='--clip: rounds of (identity steps, tracking fit)')
   cmd_parser.add_option('--id_steps', type="int", dest="id_steps", default=3, help='--clip: identity steps per round')
@@ -83,8 +100,8 @@ def parse_options(argv=None):
 
 def main(argv=None):
   opts, _ = parse_options(argv)
-  if (opts.photo is None) == (opts.clip is None) or opts.size is None or opts.out is None:
-    logger.error('Please check your parameters: one of --photo / --clip, --size H W and --out are needed.')
+  if (opts.photo is None) == (opts.clip is None) or (opts.size is None and opts.image is None) or opts.out is None or (opts.image and opts.clip):
+    logger.error('Please check your parameters: one of --photo / --clip, --size H W (or --photo with --image) and --out are needed.')
     exit(0)
   if not (os.path.exists(BFM_MAT) and os.path.exists(LM3D_MAT)):
     logger.error('%s and %s are needed', BFM_MAT, LM3D_MAT)
@@ -93,14 +110,24 @@ def main(argv=None):
   from voicepuppet_amd.bfmfit import FaceFitter, crop_alignment, preprocess_landmarks
   fitter = FaceFitter(_BFM(loadmat(BFM_MAT)))
   lm3D = loadmat(LM3D_MAT)['lm']
-  img_h, img_w = opts.size
+  image = None
+  if opts.image:
+    from PIL import Image
+    image = np.array(Image.open(opts.image).convert('RGB'), np.uint8)                     # (a writable copy)
+    if opts.size is not None and tuple(opts.size) != image.shape[:2]:
+      logger.error('--size %d %d does not match %s (%d x %d)', opts.size[0], opts.size[1], opts.image, image.shape[0], image.shape[1])
+      exit(0)
+  img_h, img_w = opts.size if image is None else image.shape[:2]
   if opts.photo:
     lms = read_landmarks(opts.photo)
-    photo = fitter.enroll(lms[0], img_h, img_w, lm3D)
+    photo = fitter.enroll(lms[0], img_h, img_w, lm3D, image=image, lam_tex=opts.lam_tex, lam_gamma=opts.lam_gamma)
     np.savez(opts.out, **photo)
     import torch
     coeff = torch.from_numpy(photo['bfmcoeff']).to(fitter.model.device)
-    print(summary_line(opts.photo, fitter.last_report, reprojection_error(fitter, coeff, fitter.last_landmarks.reshape(1, 68, 2))))
+    line = summary_line(opts.photo, fitter.last_report, reprojection_error(fitter, coeff, fitter.last_landmarks.reshape(1, 68, 2)))
+    if image is not None:
+      line += appearance_summary(fitter)
+    print(line)
     return
   lms = read_landmarks(opts.clip)
   aligned = np.stack([preprocess_landmarks(crop_alignment(lm, img_h, img_w)[0], lm3D)[0] for lm in lms])

@@ -21,6 +21,7 @@
 #include <stdint.h>
 
 #include "errors.h"
+#include "fit_device.h"
 
 namespace vp {
 
@@ -30,7 +31,6 @@ constexpr int FIT_NQ = 144;        // alpha | beta
 constexpr int FIT_NL = 68;         // landmarks
 constexpr int FIT_NR = 204;        // table rows: 3 per landmark
 constexpr int FIT_TC = 145;        // table columns: 144 bases + the centred mean
-constexpr int FIT_THREADS = 256;
 constexpr int FIT_SLICE = 16;      // rows of J per LDS slice (8 landmarks)
 constexpr int FIT_TRI = 151 * 152 / 2;           // packed lower triangle of 151 rows
 constexpr int ID_N = 80;
@@ -39,8 +39,6 @@ constexpr int ID_PART = ID_TRI + 1;              // + the number of frames that 
 constexpr int ID_FRAMES = 64;      // frames per block of the identity accumulation
 
 struct FitKeypoints { int v[FIT_NL]; };
-
-__device__ __forceinline__ int tri_idx(int i, int j) { return i * (i + 1) / 2 + j; }
 
 __global__ __launch_bounds__(256) void bfm_fit_table_kernel(const double* __restrict__ meanshape, const double* __restrict__ idBase,
                                                             const double* __restrict__ exBase, int nver, double c0, double c1, double c2,
@@ -68,31 +66,6 @@ struct FrameLds {
   double* jp;      // [68][12] d pi / d (angles, t) for the x and the y row
   double* red;     // [256]
 };
-
-// fixed-order tree over the block's 256 values; every thread gets the result
-__device__ __forceinline__ double block_sum(double v, double* red) {
-  const int t = threadIdx.x;
-  __syncthreads();
-  red[t] = v;
-  __syncthreads();
-  for (int s = FIT_THREADS / 2; s > 0; s >>= 1) {
-    if (t < s) red[t] += red[t + s];
-    __syncthreads();
-  }
-  return red[0];
-}
-
-__device__ __forceinline__ double block_max(double v, double* red) {
-  const int t = threadIdx.x;
-  __syncthreads();
-  red[t] = v;
-  __syncthreads();
-  for (int s = FIT_THREADS / 2; s > 0; s >>= 1) {
-    if (t < s) red[t] = (red[t + s] > red[t] || red[t + s] != red[t + s]) ? red[t + s] : red[t];      // a NaN wins
-    __syncthreads();
-  }
-  return red[0];
-}
 
 // One coordinate of the shape: mean + sum_j base_j p_j as a compensated dot product (error-free product and sum, the small terms first,
 // the mean last).  The plain 144-term sum leaves 1e-15 in the shape, 1e-13 px in every residual and 1e-12 in E, which is what a step
@@ -186,37 +159,6 @@ __device__ __forceinline__ void tile_of(int t, int& bi, int& bj) {
   bi = 0;
   while ((bi + 1) * (bi + 2) / 2 <= t && bi < 64) ++bi;
   bj = t - bi * (bi + 1) / 2;
-}
-
-// In-place Cholesky of the packed lower triangle a (rows 0 .. n; row n is a right-hand side that takes the forward substitution along),
-// pivots to piv [n], then the back substitution: d [n] = solution of (L L^T) d = row n.  False (for every thread) when a pivot is not > 0.
-__device__ bool chol_solve(double* a, double* piv, double* d, int n) {
-  const int t = threadIdx.x, ty = t >> 4, tx = t & 15;
-  __syncthreads();
-  for (int k = 0; k < n; ++k) {
-    const double akk = a[tri_idx(k, k)];
-    if (!(akk > 0.0)) return false;                 // the same value for every thread: a uniform exit
-    const double pv = sqrt(akk);
-    for (int i = k + 1 + t; i <= n; i += FIT_THREADS) a[tri_idx(i, k)] /= pv;
-    if (t == 0) piv[k] = pv;
-    __syncthreads();
-    for (int i = k + 1 + ty; i <= n; i += 16) {
-      const double lik = a[tri_idx(i, k)];
-      const int jend = i < n ? i : n - 1;
-      for (int j = k + 1 + tx; j <= jend; j += 16) a[tri_idx(i, j)] -= lik * a[tri_idx(j, k)];
-    }
-    __syncthreads();
-  }
-  if (t < n) d[t] = a[tri_idx(n, t)];
-  __syncthreads();
-  for (int k = n - 1; k >= 0; --k) {
-    const double dk = d[k] / piv[k];
-    __syncthreads();
-    if (t < k) d[t] -= a[tri_idx(k, t)] * dk;
-    else if (t == k) d[k] = dk;
-    __syncthreads();
-  }
-  return true;
 }
 
 struct FitArgs {

@@ -12,6 +12,7 @@
 #include <stdint.h>
 
 #include "errors.h"
+#include "bfm_device.h"
 
 #pragma clang fp contract(off)
 
@@ -124,32 +125,21 @@ __global__ __launch_bounds__(256) void bfm_vertex_kernel(VertexArgs a) {
   int tr = a.tex_frames == 1 ? 0 : f;
   if (a.tex_row) { tr = a.tex_row[f]; if (tr < 0 || tr >= a.tex_frames) return; }
   const double* R = a.rot + f * 9;
-  const double r00 = R[0], r01 = R[1], r02 = R[2], r10 = R[3], r11 = R[4], r12 = R[5], r20 = R[6], r21 = R[7], r22 = R[8];
-  // one-ring vertex normal
-  const double* FN = a.fn + (size_t)f * (a.ntri + 1) * 3;
-  double nx = 0, ny = 0, nz = 0;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int t = a.point_buf[v * 8 + j];
-    nx += FN[3 * t]; ny += FN[3 * t + 1]; nz += FN[3 * t + 2];
-  }
-  const double len = sqrt((nx * nx + ny * ny) + nz * nz);
-  nx /= len; ny /= len; nz /= len;
-  const double mx = nx * r00 + ny * r10 + nz * r20, my = nx * r01 + ny * r11 + nz * r21, mz = nx * r02 + ny * r12 + nz * r22;
+  // one-ring vertex normal, rotated
+  double nx, ny, nz, mx, my, mz;
+  bfm_vertex_normal(a.fn + (size_t)f * (a.ntri + 1) * 3, a.point_buf, v, nx, ny, nz);
+  bfm_rotate(R, nx, ny, nz, mx, my, mz);
   // shape: rotated once for the returned face_shape, and once more inside Projection_layer (:211,:214 -> :113)
   const size_t vi = ((size_t)f * a.nver + v) * 3;
   const double sx = a.shape[vi], sy = a.shape[vi + 1], sz = a.shape[vi + 2];
   double px = sx, py = sy, pz = sz;            // what Projection_layer is handed: kOwnPose* pass the unrotated shape (:185)
   if constexpr (kMode == kExternalPose) {
-    px = sx * r00 + sy * r10 + sz * r20; py = sx * r01 + sy * r11 + sz * r21; pz = sx * r02 + sy * r12 + sz * r22;
+    bfm_rotate(R, sx, sy, sz, px, py, pz);
   }
   if (a.face_shape) { a.face_shape[vi] = px; a.face_shape[vi + 1] = py; a.face_shape[vi + 2] = pz; }
   const float* C = a.coeff + (size_t)f * 257;
-  const double qx = (px * r00 + py * r10 + pz * r20) + (double)C[254];
-  const double qy = (px * r01 + py * r11 + pz * r21) + (double)C[255];
-  const double qz = -((px * r02 + py * r12 + pz * r22) + (double)C[256]) + 10.0;
-  const double ux = a.focal * qx + a.center * qz, uy = a.focal * qy + a.center * qz;
-  const double prx = ux / qz, pry = 224.0 - uy / qz, zb = -qz;
+  double prx, pry, zb;
+  bfm_project(R, px, py, pz, (double)C[254], (double)C[255], (double)C[256], a.focal, a.center, prx, pry, zb);
   if (a.face_projection) { a.face_projection[((size_t)f * a.nver + v) * 2] = prx; a.face_projection[((size_t)f * a.nver + v) * 2 + 1] = pry; }
   if (a.z_buffer) a.z_buffer[(size_t)f * a.nver + v] = zb;
   if constexpr (kMode == kOwnPoseFlat) {
@@ -160,12 +150,7 @@ __global__ __launch_bounds__(256) void bfm_vertex_kernel(VertexArgs a) {
   }
   // SH lighting on the rotated normal
   double Y[9];
-  Y[0] = a.sh[0];
-  Y[1] = -a.sh[1] * my; Y[2] = a.sh[1] * mz; Y[3] = -a.sh[1] * mx;
-  Y[4] = a.sh[2] * mx * my; Y[5] = -a.sh[2] * my * mz;
-  Y[6] = a.sh[3] * (3.0 * (mz * mz) - 1.0);
-  Y[7] = -a.sh[2] * mx * mz;
-  Y[8] = a.sh[4] * (mx * mx - my * my);
+  bfm_sh_terms(a.sh, mx, my, mz, Y);
   const double* TX = a.tex + ((size_t)tr * a.nver + v) * 3;
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
@@ -176,6 +161,20 @@ __global__ __launch_bounds__(256) void bfm_vertex_kernel(VertexArgs a) {
     if (a.face_color) a.face_color[vi + c] = col;
     a.colors[vi + c] = (float)(int)fmin(fmax(col, 0.0), 255.0);
   }
+}
+
+void bfm_launch_shape(const vp_bfm_model* m, const float* coeff, int frames, double* shape, hipStream_t st) {
+  const int rows = 3 * m->nver;
+  LinearArgs la{};
+  la.b1 = m->idBase; la.k1 = 80; la.o1 = 0; la.b2 = m->exBase; la.k2 = 64; la.o2 = 80;
+  la.mean = m->meanshape; la.sub[0] = m->center[0]; la.sub[1] = m->center[1]; la.sub[2] = m->center[2];
+  la.coeff = coeff; la.out = shape; la.rows = rows; la.frames = frames;
+  const int nb = (rows + BFM_LIN_THREADS - 1) / BFM_LIN_THREADS;
+  hipLaunchKernelGGL(bfm_linear_kernel, dim3(nb, (frames + BFM_FT - 1) / BFM_FT), dim3(BFM_LIN_THREADS), 0, st, la);
+}
+
+void bfm_launch_fnormal(const vp_bfm_model* m, const double* shape, int frames, double* fn, hipStream_t st) {
+  hipLaunchKernelGGL(bfm_fnormal_kernel, dim3((m->ntri + 1 + 255) / 256, frames), dim3(256), 0, st, shape, m->tri, fn, m->nver, m->ntri);
 }
 
 }  // namespace vp
@@ -205,17 +204,13 @@ static int reconstruct_impl(const char* who, int mode, double scale, const vp_bf
   double* shape = (double*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
   double* tex = face_texture ? face_texture : shape + (size_t)frames * rows;
   double* fn = shape + (size_t)frames * rows * 2;
-  vp::LinearArgs la{};
-  la.b1 = m->idBase; la.k1 = 80; la.o1 = 0; la.b2 = m->exBase; la.k2 = 64; la.o2 = 80;
-  la.mean = m->meanshape; la.sub[0] = m->center[0]; la.sub[1] = m->center[1]; la.sub[2] = m->center[2];
-  la.coeff = coeff; la.out = shape; la.rows = rows; la.frames = frames;
+  vp::bfm_launch_shape(m, coeff, frames, shape, st);
   const int nb = (rows + vp::BFM_LIN_THREADS - 1) / vp::BFM_LIN_THREADS;
-  hipLaunchKernelGGL(vp::bfm_linear_kernel, dim3(nb, (frames + vp::BFM_FT - 1) / vp::BFM_FT), dim3(vp::BFM_LIN_THREADS), 0, st, la);
   vp::LinearArgs lt{};
   lt.b1 = m->texBase; lt.k1 = 80; lt.o1 = 144; lt.b2 = nullptr; lt.k2 = 0; lt.o2 = 0; lt.mean = m->meantex;
   lt.coeff = coeff; lt.out = tex; lt.rows = rows; lt.frames = tex_frames; lt.src_row = tex_src; lt.src_rows = frames;
   hipLaunchKernelGGL(vp::bfm_linear_kernel, dim3(nb, (tex_frames + vp::BFM_FT - 1) / vp::BFM_FT), dim3(vp::BFM_LIN_THREADS), 0, st, lt);
-  hipLaunchKernelGGL(vp::bfm_fnormal_kernel, dim3((m->ntri + 1 + 255) / 256, frames), dim3(256), 0, st, shape, m->tri, fn, m->nver, m->ntri);
+  vp::bfm_launch_fnormal(m, shape, frames, fn, st);
   vp::VertexArgs va{};
   va.shape = shape; va.tex = tex; va.fn = fn; va.point_buf = m->point_buf; va.rot = rotation; va.coeff = coeff;
   va.face_shape = face_shape; va.face_color = face_color; va.face_projection = face_projection; va.z_buffer = z_buffer;
