@@ -104,7 +104,7 @@ for mode in modes:
     f1 = lambda: eng.forward(*b)
     (m_g, v_g), (m_d, v_d) = eng.adam["g"], eng.adam["d"]
     from voicepuppet_amd import _lib
-    from voicepuppet_amd.engine import _ptr, _stream
+    from voicepuppet_amd._handle import ptr as _ptr, stream as _stream
     f2 = lambda: _lib.check(eng.L.vp_pixrefer_backward_update(eng.h, _ptr(m_g), _ptr(v_g), _ptr(m_d), _ptr(v_d), 1, 1, 3e-4, 0.5, 0.999, 1e-8, _stream()))
     both = lambda: (f1(), f2())
     eager = timed(both)

@@ -100,8 +100,9 @@ def ingest_alone(rate, S, frames, pushes, warmup):
   # the span includes the packing copies of the wrapper's device path (one per slot); launch_ms is the C call alone, packed input
   import ctypes
   from voicepuppet_amd import _lib
+  from voicepuppet_amd._handle import slot_arrays
   packed = torch.zeros(S * ((frames * 4 + 15) // 16 * 16), dtype=torch.uint8, device="cuda")
-  n, fin = ing._arrays({s: frames for s in range(S)}, ())
+  n, fin = slot_arrays(S, {s: frames for s in range(S)}, ())
   out = torch.empty(sum(ing.ready({s: frames for s in range(S)})), dtype=torch.float32, device="cuda")
   st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
   launch = []

@@ -127,6 +127,44 @@ def test_library_exports_every_declared_symbol():
   assert lib.vp_bfmnet_param_count() > 7_000_000
 
 
+def test_every_descriptor_size_query_has_its_layout_check():
+  """_lib.lib() compares vp_X_desc_size() with the ctypes structure of _lib.DESC_SIZE_QUERIES (include/vp_hip.h, "ABI rule"): every such
+  query the binding knows has its line there, and every structure but vp_pixrefer_desc, which predates the field, starts with the
+  struct_bytes the library checks per call."""
+  from voicepuppet_amd import _lib
+  queries = [s for s in _lib.exported_symbols() if re.fullmatch(r"vp_\w+_desc_size", s)]
+  assert len(queries) >= 10
+  assert set(queries) == set(_lib.DESC_SIZE_QUERIES), set(queries) ^ set(_lib.DESC_SIZE_QUERIES)
+  for query, struct in _lib.DESC_SIZE_QUERIES.items():
+    assert issubclass(struct, ctypes.Structure), query
+    if query != "vp_pixrefer_desc_size":
+      assert struct._fields_[0][0] == "struct_bytes", query
+
+
+def test_workspace_view_aliases_the_bytes_and_refuses_what_lies_outside():
+  """_handle.workspace_view is a function of a uint8 tensor and an address: on a 64-byte CPU tensor an int16 [2, 3] view at offset 8 is
+  bytes 8..19; a view that starts in front of the tensor or ends behind it raises, one that ends at its last byte does not."""
+  import torch
+  from voicepuppet_amd._handle import workspace_view
+  ws = torch.zeros(64, dtype=torch.uint8)
+  base = ws.data_ptr()
+  v = workspace_view(ws, base + 8, (2, 3), torch.int16)
+  assert v.dtype == torch.int16 and tuple(v.shape) == (2, 3)
+  v.copy_(torch.tensor([[0x0102, 0x0304, 0x0506], [0x0708, 0x090a, 0x0b0c]], dtype=torch.int16))
+  got = ws.numpy()
+  assert got[8:20].tolist() == [2, 1, 4, 3, 6, 5, 8, 7, 10, 9, 12, 11] and not got[:8].any() and not got[20:].any()
+  with pytest.raises(ValueError):
+    workspace_view(ws, base - 1, (2, 3), torch.int16)
+  with pytest.raises(ValueError):
+    workspace_view(ws, base + 53, (2, 3), torch.int16)          # 53 + 12 = 65: one byte behind the end
+  with pytest.raises(ValueError):
+    workspace_view(ws, base + 62, (1, 3), torch.uint8)
+  last = workspace_view(ws, base + 52, (2, 3), torch.int16)     # ends exactly at byte 64
+  last.fill_(-1)
+  assert (ws.numpy()[52:] == 255).all() and not ws.numpy()[20:52].any()
+  assert tuple(workspace_view(ws, base + 60, (4,), torch.uint8).shape) == (4,)
+
+
 def test_missing_config_exits_with_status_zero(tmp_path):
   """train_pixrefer.py:24-32: logger.error + exit(0)."""
   from voicepuppet_amd.pixrefer import train_pixrefer

@@ -348,6 +348,21 @@ _SIGNATURES = {
     "vp_bn_bwd": (ctypes.c_int, [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P, _P, _P, _P, _P, _P]),
 }
 
+# vp_X_desc_size -> the structure that restates vp_X_desc here: lib() compares the two sizes.  A new descriptor gets its line
+# (tests/test_host_logic.py lists the exported queries against this table).
+DESC_SIZE_QUERIES = {
+    "vp_pixrefer_desc_size": PixReferDesc,
+    "vp_bfmstream_desc_size": BfmStreamDesc,
+    "vp_bfmstream_group_desc_size": BfmStreamGroupDesc,
+    "vp_puppet_desc_size": PuppetDesc,
+    "vp_jpeg_desc_size": JpegDesc,
+    "vp_png_desc_size": PngDesc,
+    "vp_jpegdec_desc_size": JpegDecDesc,
+    "vp_pcmin_desc_size": PcmInDesc,
+    "vp_frame_metrics_desc_size": FrameMetricsDesc,
+    "vp_avimux_desc_size": AviMuxDesc,
+}
+
 _lib = None
 
 
@@ -376,48 +391,14 @@ def lib():
         continue                             # an A/B build of an older tree (scripts/ab.sh): entry points added since are simply absent
       fn.restype = res
       fn.argtypes = args
-    # the descriptor is declared twice (include/vp_hip.h, PixReferDesc above): a library built from another header must not be handed
-    # this layout (include/vp_hip.h, "ABI rule"); an older A/B build (VP_LIB) without the query is the 48-byte round-5 layout
-    if hasattr(l, "vp_pixrefer_desc_size") and l.vp_pixrefer_desc_size.argtypes is not None:
-      want = int(l.vp_pixrefer_desc_size())
-      if want != ctypes.sizeof(PixReferDesc):
-        raise RuntimeError("%s: vp_pixrefer_desc is %d bytes in the library, %d in this binding" % (LIB_PATH, want, ctypes.sizeof(PixReferDesc)))
-    if hasattr(l, "vp_bfmstream_desc_size") and l.vp_bfmstream_desc_size.argtypes is not None:
-      want = int(l.vp_bfmstream_desc_size())
-      if want != ctypes.sizeof(BfmStreamDesc):
-        raise RuntimeError("%s: vp_bfmstream_desc is %d bytes in the library, %d in this binding" % (LIB_PATH, want, ctypes.sizeof(BfmStreamDesc)))
-    if hasattr(l, "vp_bfmstream_group_desc_size") and l.vp_bfmstream_group_desc_size.argtypes is not None:
-      want = int(l.vp_bfmstream_group_desc_size())
-      if want != ctypes.sizeof(BfmStreamGroupDesc):
-        raise RuntimeError("%s: vp_bfmstream_group_desc is %d bytes in the library, %d in this binding" % (LIB_PATH, want, ctypes.sizeof(BfmStreamGroupDesc)))
-    if hasattr(l, "vp_puppet_desc_size") and l.vp_puppet_desc_size.argtypes is not None:
-      want = int(l.vp_puppet_desc_size())
-      if want != ctypes.sizeof(PuppetDesc):
-        raise RuntimeError("%s: vp_puppet_desc is %d bytes in the library, %d in this binding" % (LIB_PATH, want, ctypes.sizeof(PuppetDesc)))
-    if hasattr(l, "vp_jpeg_desc_size") and l.vp_jpeg_desc_size.argtypes is not None:
-      want = int(l.vp_jpeg_desc_size())
-      if want != ctypes.sizeof(JpegDesc):
-        raise RuntimeError("%s: vp_jpeg_desc is %d bytes in the library, %d in this binding" % (LIB_PATH, want, ctypes.sizeof(JpegDesc)))
-    if hasattr(l, "vp_png_desc_size") and l.vp_png_desc_size.argtypes is not None:
-      want = int(l.vp_png_desc_size())
-      if want != ctypes.sizeof(PngDesc):
-        raise RuntimeError("%s: vp_png_desc is %d bytes in the library, %d in this binding" % (LIB_PATH, want, ctypes.sizeof(PngDesc)))
-    if hasattr(l, "vp_jpegdec_desc_size") and l.vp_jpegdec_desc_size.argtypes is not None:
-      want = int(l.vp_jpegdec_desc_size())
-      if want != ctypes.sizeof(JpegDecDesc):
-        raise RuntimeError("%s: vp_jpegdec_desc is %d bytes in the library, %d in this binding" % (LIB_PATH, want, ctypes.sizeof(JpegDecDesc)))
-    if hasattr(l, "vp_pcmin_desc_size") and l.vp_pcmin_desc_size.argtypes is not None:
-      want = int(l.vp_pcmin_desc_size())
-      if want != ctypes.sizeof(PcmInDesc):
-        raise RuntimeError("%s: vp_pcmin_desc is %d bytes in the library, %d in this binding" % (LIB_PATH, want, ctypes.sizeof(PcmInDesc)))
-    if hasattr(l, "vp_frame_metrics_desc_size") and l.vp_frame_metrics_desc_size.argtypes is not None:
-      want = int(l.vp_frame_metrics_desc_size())
-      if want != ctypes.sizeof(FrameMetricsDesc):
-        raise RuntimeError("%s: vp_frame_metrics_desc is %d bytes in the library, %d in this binding" % (LIB_PATH, want, ctypes.sizeof(FrameMetricsDesc)))
-    if hasattr(l, "vp_avimux_desc_size") and l.vp_avimux_desc_size.argtypes is not None:
-      want = int(l.vp_avimux_desc_size())
-      if want != ctypes.sizeof(AviMuxDesc):
-        raise RuntimeError("%s: vp_avimux_desc is %d bytes in the library, %d in this binding" % (LIB_PATH, want, ctypes.sizeof(AviMuxDesc)))
+    # every descriptor is declared twice (include/vp_hip.h, the structures above): a library built from another header must not be handed
+    # this layout (include/vp_hip.h, "ABI rule"); an older A/B build (VP_LIB) without a query is skipped (vp_pixrefer_desc: it is the
+    # 48-byte round-5 layout)
+    for query, struct in DESC_SIZE_QUERIES.items():
+      if hasattr(l, query) and getattr(l, query).argtypes is not None:
+        want = int(getattr(l, query)())
+        if want != ctypes.sizeof(struct):
+          raise RuntimeError("%s: %s is %d bytes in the library, %d in this binding" % (LIB_PATH, query[:-len("_size")], want, ctypes.sizeof(struct)))
     _lib = l
   return _lib
 

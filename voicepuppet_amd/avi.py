@@ -21,6 +21,8 @@ import struct
 
 import numpy as np
 
+from ._handle import Handle, ptr, stream
+
 FCC_00DC, FCC_01WB = 0x63643030, 0x62773130      # '00dc', '01wb' as little-endian uint32
 AVIIF_KEYFRAME = 0x10
 AVIF_HASINDEX, AVIF_ISINTERLEAVED = 0x10, 0x100
@@ -203,7 +205,7 @@ class AviSegments:
     self.data, self.lengths, self.frame_slot, self.pcm, self.offsets, self.counts = data, lengths, frame_slot, pcm, offsets, counts
 
 
-class AviMuxer:
+class AviMuxer(Handle):
   """segment(data, lengths, frame_slot, pcm, offsets, counts) enqueues one vp_avimux_segment on the current stream and returns an
   AviSegments; to_host(seg[, frames]) -> {slot: (uint8 array with the slot's chunks, uint32 [n, 4] entries)} for the slots that have any.
   max_frames / max_samples: the most rows / samples (all slots together) one call may carry; row_bytes: the widest row
@@ -214,17 +216,10 @@ class AviMuxer:
     from . import _lib
     if not torch.cuda.is_available():
       raise RuntimeError("AviMuxer needs an MI355X (host_segment is the layout without one)")
-    self.L = _lib.lib()
-    self.desc = _lib.AviMuxDesc(ctypes.sizeof(_lib.AviMuxDesc), int(max_frames), int(row_bytes), int(slots), int(max_samples))
-    ws = self.L.vp_avimux_workspace_bytes(ctypes.byref(self.desc))
-    if ws == 0:
-      raise ValueError("invalid AVI muxer descriptor: " + self.L.vp_last_error().decode())
+    desc = _lib.AviMuxDesc(ctypes.sizeof(_lib.AviMuxDesc), int(max_frames), int(row_bytes), int(slots), int(max_samples))
+    self._open("avimux", desc, invalid="invalid AVI muxer descriptor")
     self.max_frames, self.row_bytes, self.slots, self.max_samples, self.quality = int(max_frames), int(row_bytes), int(slots), int(max_samples), int(quality)
     self.capacity = int(self.L.vp_avimux_out_capacity(ctypes.byref(self.desc)))
-    self.workspace = torch.empty(ws, dtype=torch.uint8, device="cuda")
-    h = ctypes.c_void_p()
-    _lib.check(self.L.vp_avimux_create(ctypes.byref(self.desc), ctypes.c_void_p(self.workspace.data_ptr()), ws, ctypes.byref(h)), "vp_avimux_create")
-    self.h = h
 
   def table_bytes(self, frames):
     return int(self.L.vp_avimux_table_bytes(ctypes.byref(self.desc), int(frames)))
@@ -264,10 +259,9 @@ class AviMuxer:
     if out is None:
       out = torch.empty(self.call_capacity(K, row, n), dtype=torch.uint8, device="cuda")
     assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous()
-    p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
-    _lib.check(self.L.vp_avimux_segment(self.h, p(data) if K else None, row, p(lengths) if K else None, p(frame_slot) if K else None, K,
-                                        p(pcm) if n else None, p(offsets) if n else None, p(counts) if n else None, n, p(out), int(out.numel()),
-                                        ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "vp_avimux_segment")
+    _lib.check(self.L.vp_avimux_segment(self.h, ptr(data) if K else None, row, ptr(lengths) if K else None, ptr(frame_slot) if K else None, K,
+                                        ptr(pcm) if n else None, ptr(offsets) if n else None, ptr(counts) if n else None, n, ptr(out),
+                                        int(out.numel()), stream()), "vp_avimux_segment")
     return AviSegments(out, self.table_bytes(K), K, data if K else None, lengths if K else None, frame_slot if K else None,
                        pcm if n else None, offsets if n else None, counts if n else None)
 
@@ -319,11 +313,3 @@ class AviMuxer:
       o, c = int(seg.offsets.cpu()[s]), int(seg.counts.cpu()[s])
       pcm = seg.pcm[o:o + c].cpu().numpy()
     return host_segment(jpegs, pcm)
-
-  def __del__(self):
-    try:
-      if getattr(self, "h", None):
-        self.L.vp_avimux_destroy(self.h)
-        self.h = None
-    except Exception:
-      pass

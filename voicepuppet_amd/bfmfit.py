@@ -28,6 +28,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
+from ._handle import grow, ptr, stream
 
 NP = 150
 NA = 107                                                    # appearance unknowns: texture 80 | lighting 27
@@ -162,8 +163,9 @@ class FaceFitter:
 
   def _workspace(self, frames):
     n = _lib.lib().vp_bfmfit_workspace_bytes(frames)
-    if self._ws is None or self._ws.numel() < n:
-      self._ws = self._torch.empty(n, dtype=self._torch.uint8, device=self.model.device)
+    ws = grow(self._ws, n, self.model.device)
+    if ws is not self._ws:
+      self._ws = ws
       self._table_ready = False                             # the gathered keypoint table lives at the head of the workspace
     return self._ws
 
@@ -207,11 +209,9 @@ class FaceFitter:
     report = torch.empty(T, 4, dtype=torch.float64, device=dev)
     ws = self._workspace(T)
     P = ctypes.c_void_p
-    _lib.check(_lib.lib().vp_bfmfit_fit(ctypes.byref(self.model.c), self._kp.ctypes.data_as(P), 1 if self._table_ready else 0, P(lm.data_ptr()),
-                                        P(w.data_ptr() if w is not None else 0), per_frame, P(tmpl.data_ptr()), P(p.data_ptr()), 1 if params_in else 0, T,
-                                        float(lam_id), float(lam_ex), float(gtol), int(max_iters), _free_mask(free), P(coeff.data_ptr()),
-                                        P(report.data_ptr()), P(ws.data_ptr()), ws.numel(), P(torch.cuda.current_stream().cuda_stream)),
-               "vp_bfmfit_fit")
+    _lib.check(_lib.lib().vp_bfmfit_fit(ctypes.byref(self.model.c), self._kp.ctypes.data_as(P), 1 if self._table_ready else 0, ptr(lm), ptr(w),
+                                        per_frame, ptr(tmpl), ptr(p), 1 if params_in else 0, T, float(lam_id), float(lam_ex), float(gtol),
+                                        int(max_iters), _free_mask(free), ptr(coeff), ptr(report), ptr(ws), ws.numel(), stream()), "vp_bfmfit_fit")
     self._table_ready = True
     self.last_params = p
     return coeff, report
@@ -229,9 +229,8 @@ class FaceFitter:
     ws = self._workspace(T)
     P = ctypes.c_void_p
     _lib.check(_lib.lib().vp_bfmfit_identity_step(ctypes.byref(self.model.c), self._kp.ctypes.data_as(P), 1 if self._table_ready else 0,
-                                                  P(lm.data_ptr()), P(w.data_ptr() if w is not None else 0), per_frame, P(params.data_ptr()),
-                                                  P(coeff.data_ptr() if coeff is not None else 0), T, float(lam_id), P(ws.data_ptr()), ws.numel(),
-                                                  P(torch.cuda.current_stream().cuda_stream)), "vp_bfmfit_identity_step")
+                                                  ptr(lm), ptr(w), per_frame, ptr(params), ptr(coeff), T, float(lam_id), ptr(ws), ws.numel(),
+                                                  stream()), "vp_bfmfit_identity_step")
     self._table_ready = True
     return params
 
@@ -294,13 +293,10 @@ class FaceFitter:
     weight = torch.empty(T, N, dtype=torch.float64, device=dev)
     observed = torch.empty(T, N, 3, dtype=torch.float64, device=dev)
     n = _lib.lib().vp_bfmfit_observe_workspace_bytes(N, self.model.ntri, T)
-    if self._ws_obs is None or self._ws_obs.numel() < n:
-      self._ws_obs = torch.empty(n, dtype=torch.uint8, device=dev)
-    P = ctypes.c_void_p
-    _lib.check(_lib.lib().vp_bfmfit_observe(ctypes.byref(self.model.c), P(c.data_ptr()), P(rot.data_ptr()), T, P(img.data_ptr()), photo_frames, H, W,
-                                            P(aff.data_ptr()), P(vw.data_ptr() if vw is not None else 0), P(sh.data_ptr()), P(weight.data_ptr()),
-                                            P(observed.data_ptr()), P(self._ws_obs.data_ptr()), self._ws_obs.numel(),
-                                            P(torch.cuda.current_stream().cuda_stream)), "vp_bfmfit_observe")
+    self._ws_obs = grow(self._ws_obs, n, dev)
+    _lib.check(_lib.lib().vp_bfmfit_observe(ctypes.byref(self.model.c), ptr(c), ptr(rot), T, ptr(img), photo_frames, H, W, ptr(aff), ptr(vw),
+                                            ptr(sh), ptr(weight), ptr(observed), ptr(self._ws_obs), self._ws_obs.numel(), stream()),
+               "vp_bfmfit_observe")
     return sh, weight, observed
 
   def fit_appearance(self, coeff, photo=None, affine=None, observation=None, vertex_weights=None, init=None, params=None, lam_tex=1.0,
@@ -335,13 +331,10 @@ class FaceFitter:
     out = torch.empty(T, 257, dtype=torch.float32, device=dev)
     report = torch.empty(T, 4, dtype=torch.float64, device=dev)
     n = _lib.lib().vp_bfmfit_appearance_workspace_bytes(N, T)
-    if self._ws_app is None or self._ws_app.numel() < n:
-      self._ws_app = torch.empty(n, dtype=torch.uint8, device=dev)
-    P = ctypes.c_void_p
-    _lib.check(_lib.lib().vp_bfmfit_appearance(ctypes.byref(self.model.c), P(sh.data_ptr()), P(weight.data_ptr()), P(observed.data_ptr()),
-                                               P(tmpl.data_ptr()), P(p.data_ptr()), 1 if params_in else 0, T, float(lam_tex), float(lam_gamma),
-                                               float(gtol), int(max_trials), int(_stages), P(out.data_ptr()), P(report.data_ptr()),
-                                               P(self._ws_app.data_ptr()), self._ws_app.numel(), P(torch.cuda.current_stream().cuda_stream)),
+    self._ws_app = grow(self._ws_app, n, dev)
+    _lib.check(_lib.lib().vp_bfmfit_appearance(ctypes.byref(self.model.c), ptr(sh), ptr(weight), ptr(observed), ptr(tmpl), ptr(p),
+                                               1 if params_in else 0, T, float(lam_tex), float(lam_gamma), float(gtol), int(max_trials),
+                                               int(_stages), ptr(out), ptr(report), ptr(self._ws_app), self._ws_app.numel(), stream()),
                "vp_bfmfit_appearance")
     self.last_appearance, self.last_appearance_lams = p, (float(lam_tex), float(lam_gamma))
     return out, report

@@ -26,11 +26,11 @@ import numpy as np
 import torch
 
 from .. import _lib
+from .._handle import ptr, stream
 from ..audio import bfmnet_manifest
 
 ACT_NONE, ACT_LRELU, ACT_RELU, ACT_RELU6 = 0, 1, 2, 5
 BN_EPS, BN_DECAY, L2_SCALE = 1e-3, 0.999, 1e-4
-_P = ctypes.c_void_p
 
 # (scope, out_channels, expansion, pool_after)   tinynet.py:172-203
 BLOCKS = [("block1_0", 64, 1, False), ("block2_0", 64, 6, True), ("block2_1", 64, 6, False), ("block3_0", 128, 6, True),
@@ -40,14 +40,6 @@ BLOCKS = [("block1_0", 64, 1, False), ("block2_0", 64, 6, True), ("block2_1", 64
           ("block7_0", 256, 6, False)]
 PREFIX = "mfcc_encoder/MfccNet/"
 GRU = "rnn_module/rnn/multi_rnn_cell/cell_0/gru_cell/"
-
-
-def _ptr(t):
-  return _P(t.data_ptr()) if t is not None else _P(0)
-
-
-def _stream():
-  return _P(torch.cuda.current_stream().cuda_stream)
 
 
 def trainable(name):
@@ -150,8 +142,8 @@ class BFMNetTrainEngine:
     mean, var = self.bs[scope + "/BatchNorm/moving_mean"], self.bs[scope + "/BatchNorm/moving_variance"]
     rs = torch.empty(3, C, dtype=torch.float32, device=self.dev)
     ws = self._work("bn", self.L.vp_bn_train_workspace_bytes(P, C))
-    _lib.check(self.L.vp_bn_train_fwd(_ptr(y), P, C, _ptr(self.p[scope + "/BatchNorm/beta"]), BN_EPS, _ptr(mean), _ptr(var), _ptr(rs[0]), _ptr(rs[1]),
-                                      _ptr(rs[2]), _ptr(ws), _stream()), "vp_bn_train_fwd")
+    _lib.check(self.L.vp_bn_train_fwd(ptr(y), P, C, ptr(self.p[scope + "/BatchNorm/beta"]), BN_EPS, ptr(mean), ptr(var), ptr(rs[0]), ptr(rs[1]),
+                                      ptr(rs[2]), ptr(ws), stream()), "vp_bn_train_fwd")
     return mean, rs[0], rs[2]
 
   def _bn_act_bwd(self, da, y, mean, rstd, shift, act, scope):
@@ -159,8 +151,8 @@ class BFMNetTrainEngine:
     P, C = y.shape
     dx = torch.empty_like(y)
     ws = self._work("bn", self.L.vp_bn_train_workspace_bytes(P, C))
-    _lib.check(self.L.vp_bn_act_train_bwd(_ptr(y), _ptr(da), P, C, _ptr(mean), _ptr(rstd), _ptr(shift), act, _ptr(dx),
-                                          _ptr(self.g[scope + "/BatchNorm/beta"]), _ptr(ws), _stream()), "vp_bn_act_train_bwd")
+    _lib.check(self.L.vp_bn_act_train_bwd(ptr(y), ptr(da), P, C, ptr(mean), ptr(rstd), ptr(shift), act, ptr(dx),
+                                          ptr(self.g[scope + "/BatchNorm/beta"]), ptr(ws), stream()), "vp_bn_act_train_bwd")
     return dx
 
   def _act(self, x, scale, shift, act, mask=None, add=None):
@@ -168,14 +160,14 @@ class BFMNetTrainEngine:
     P, C = x.shape
     y = torch.empty_like(x)
     if add is not None:
-      _lib.check(self.L.vp_affine_act_add_fwd(_ptr(x), _ptr(scale), _ptr(shift), _ptr(mask), _ptr(add), P, C, act, _ptr(y), _stream()), "vp_affine_act_add_fwd")
+      _lib.check(self.L.vp_affine_act_add_fwd(ptr(x), ptr(scale), ptr(shift), ptr(mask), ptr(add), P, C, act, ptr(y), stream()), "vp_affine_act_add_fwd")
     else:
-      _lib.check(self.L.vp_affine_act_fwd(_ptr(x), _ptr(scale), _ptr(shift), _ptr(mask), P, C, act, _ptr(y), _stream()), "vp_affine_act_fwd")
+      _lib.check(self.L.vp_affine_act_fwd(ptr(x), ptr(scale), ptr(shift), ptr(mask), P, C, act, ptr(y), stream()), "vp_affine_act_fwd")
     return y
 
   def _act_bwd(self, dy, ya, act, mask=None):
     dx = torch.empty_like(dy)
-    _lib.check(self.L.vp_act_bwd(_ptr(dy), _ptr(ya), _ptr(mask), dy.numel(), act, _ptr(dx), _stream()), "vp_act_bwd")
+    _lib.check(self.L.vp_act_bwd(ptr(dy), ptr(ya), ptr(mask), dy.numel(), act, ptr(dx), stream()), "vp_act_bwd")
     return dx
 
   def _dw(self, x2d, w21, H, W, backward=False):
@@ -183,25 +175,25 @@ class BFMNetTrainEngine:
     C = x2d.shape[1]
     y = torch.empty_like(x2d)
     fn = self.L.vp_dwconv7x3_bwd_data if backward else self.L.vp_dwconv7x3_raw
-    _lib.check(fn(_ptr(x2d), _ptr(w21), _ptr(y), self.B, H, W, C, _stream()), "vp_dwconv7x3")
+    _lib.check(fn(ptr(x2d), ptr(w21), ptr(y), self.B, H, W, C, stream()), "vp_dwconv7x3")
     return y
 
   def _dw_wgrad(self, x2d, dy2d, H, W, out):
     C = x2d.shape[1]
     ws = self._work("dw", self.L.vp_dwconv7x3_wgrad_workspace_bytes(self.B, H, W, C))
-    _lib.check(self.L.vp_dwconv7x3_wgrad(_ptr(x2d), _ptr(dy2d), _ptr(out), self.B, H, W, C, _ptr(ws), _stream()), "vp_dwconv7x3_wgrad")
+    _lib.check(self.L.vp_dwconv7x3_wgrad(ptr(x2d), ptr(dy2d), ptr(out), self.B, H, W, C, ptr(ws), stream()), "vp_dwconv7x3_wgrad")
 
   def _pool(self, x2d, H, W, k, s):
     C = x2d.shape[1]
     Ho, Wo = -(-H // s[0]), -(-W // s[1])
     y = torch.empty(self.B * Ho * Wo, C, dtype=torch.float32, device=self.dev)
-    _lib.check(self.L.vp_maxpool_hw(_ptr(x2d), _ptr(y), self.B, H, W, C, k[0], k[1], s[0], s[1], _stream()), "vp_maxpool_hw")
+    _lib.check(self.L.vp_maxpool_hw(ptr(x2d), ptr(y), self.B, H, W, C, k[0], k[1], s[0], s[1], stream()), "vp_maxpool_hw")
     return y, Ho, Wo
 
   def _pool_bwd(self, x2d, dy2d, H, W, k, s):
     C = x2d.shape[1]
     dx = torch.empty_like(x2d)
-    _lib.check(self.L.vp_maxpool_hw_bwd(_ptr(x2d), _ptr(dy2d), _ptr(dx), self.B, H, W, C, k[0], k[1], s[0], s[1], _stream()), "vp_maxpool_hw_bwd")
+    _lib.check(self.L.vp_maxpool_hw_bwd(ptr(x2d), ptr(dy2d), ptr(dx), self.B, H, W, C, k[0], k[1], s[0], s[1], stream()), "vp_maxpool_hw_bwd")
     return dx
 
   # ---- matrix products: the repo's own float32 MFMA kernels behind vp_mm_* (include/vp_hip.h), no vendor GEMM library --------------------
@@ -279,7 +271,7 @@ class BFMNetTrainEngine:
         # constants: pack now, once (each against its own base pointer: one launch per matrix)
         for i, (key, wconst) in enumerate(items):
           one = dev[i * dsz:(i + 1) * dsz].clone()
-          _lib.check(L.vp_mm_pack_table(_ptr(one), 1, _ptr(wconst), _ptr(self._packed), _stream()), "vp_mm_pack_table")
+          _lib.check(L.vp_mm_pack_table(ptr(one), 1, ptr(wconst), ptr(self._packed), stream()), "vp_mm_pack_table")
           self._keep_const = getattr(self, "_keep_const", []) + [one]
     self._pk_pending = {}
     self._pk_ready = True
@@ -288,7 +280,7 @@ class BFMNetTrainEngine:
     """One launch: every arena matrix of the step, both layouts, from the current parameters."""
     if self._pk_ready and self._pk_arena[1] > 0:
       dev, n = self._pk_arena
-      _lib.check(self.L.vp_mm_pack_table(_ptr(dev), n, _ptr(self.arena), _ptr(self._packed), _stream()), "vp_mm_pack_table")
+      _lib.check(self.L.vp_mm_pack_table(ptr(dev), n, ptr(self.arena), ptr(self._packed), stream()), "vp_mm_pack_table")
 
   def _mm(self, x, w, bias=None, w_t=False, out=None):
     """x [P, K] . w [K, N] (+ bias) -> [P, N];  w_t: w is stored [N, K].  Row strides are taken from the tensors."""
@@ -298,11 +290,11 @@ class BFMNetTrainEngine:
     y = out if out is not None else torch.empty(P, N, dtype=torch.float32, device=self.dev)
     pk = self._packed_for(w, w_t, P, K, N, 0)
     if pk is not None:
-      _lib.check(self.L.vp_mm_fwd_f32_packed(_ptr(x), x.stride(0), pk, _ptr(bias), _ptr(y), y.stride(0), P, K, N, _ptr(self._mm_ws(P, K, N)), _stream()),
+      _lib.check(self.L.vp_mm_fwd_f32_packed(ptr(x), x.stride(0), pk, ptr(bias), ptr(y), y.stride(0), P, K, N, ptr(self._mm_ws(P, K, N)), stream()),
                  "vp_mm_fwd_f32_packed")
     else:
-      _lib.check(self.L.vp_mm_fwd_f32(_ptr(x), x.stride(0), _ptr(w), w.stride(0), 1 if w_t else 0, _ptr(bias), _ptr(y), y.stride(0), P, K, N,
-                                      _ptr(self._mm_ws(P, K, N)), _stream()), "vp_mm_fwd_f32")
+      _lib.check(self.L.vp_mm_fwd_f32(ptr(x), x.stride(0), ptr(w), w.stride(0), 1 if w_t else 0, ptr(bias), ptr(y), y.stride(0), P, K, N,
+                                      ptr(self._mm_ws(P, K, N)), stream()), "vp_mm_fwd_f32")
     return y
 
   def _mm_dx(self, dy, w, w_t=False, out=None, accumulate=False, n=None):
@@ -315,22 +307,22 @@ class BFMNetTrainEngine:
     dx = out if out is not None else torch.empty(P, K, dtype=torch.float32, device=self.dev)
     pk = self._packed_for(w, w_t, P, K, N, 1)
     if pk is not None:
-      _lib.check(self.L.vp_mm_bwd_data_f32_packed(_ptr(dy), dy.stride(0), pk, _ptr(dx), dx.stride(0), 1 if accumulate else 0, P, K, N,
-                                                  _ptr(self._mm_ws(P, K, N)), _stream()), "vp_mm_bwd_data_f32_packed")
+      _lib.check(self.L.vp_mm_bwd_data_f32_packed(ptr(dy), dy.stride(0), pk, ptr(dx), dx.stride(0), 1 if accumulate else 0, P, K, N,
+                                                  ptr(self._mm_ws(P, K, N)), stream()), "vp_mm_bwd_data_f32_packed")
     else:
-      _lib.check(self.L.vp_mm_bwd_data_f32(_ptr(dy), dy.stride(0), _ptr(w), w.stride(0), 1 if w_t else 0, _ptr(dx), dx.stride(0), 1 if accumulate else 0,
-                                           P, K, N, _ptr(self._mm_ws(P, K, N)), _stream()), "vp_mm_bwd_data_f32")
+      _lib.check(self.L.vp_mm_bwd_data_f32(ptr(dy), dy.stride(0), ptr(w), w.stride(0), 1 if w_t else 0, ptr(dx), dx.stride(0), 1 if accumulate else 0,
+                                           P, K, N, ptr(self._mm_ws(P, K, N)), stream()), "vp_mm_bwd_data_f32")
     return dx
 
   def _colsum(self, x, out):
     """out[c] = sum over rows of x: the bias gradients (vp_colsum_f32; it was torch.sum, an at::native reduction)"""
     assert x.is_contiguous() and out.is_contiguous() and out.numel() == x.shape[1]
-    _lib.check(self.L.vp_colsum_f32(_ptr(x), int(x.shape[0]), int(x.shape[1]), _ptr(out), _stream()), "vp_colsum_f32")
+    _lib.check(self.L.vp_colsum_f32(ptr(x), int(x.shape[0]), int(x.shape[1]), ptr(out), stream()), "vp_colsum_f32")
 
   def _mul(self, a, b):
     out = torch.empty_like(a)
     assert a.is_contiguous() and b.is_contiguous() and a.numel() == b.numel()
-    _lib.check(self.L.vp_mul_f32(_ptr(a), _ptr(b), _ptr(out), a.numel(), _stream()), "vp_mul_f32")
+    _lib.check(self.L.vp_mul_f32(ptr(a), ptr(b), ptr(out), a.numel(), stream()), "vp_mul_f32")
     return out
 
   def _mm_dw(self, x, dy, out, k_real=None):
@@ -339,20 +331,20 @@ class BFMNetTrainEngine:
     N = dy.shape[1]
     kr = K if k_real is None else int(k_real)
     assert x.stride(1) == 1 and dy.stride(1) == 1 and out.is_contiguous() and out.numel() == kr * N, (x.shape, dy.shape, out.shape)
-    _lib.check(self.L.vp_mm_bwd_weight_f32(_ptr(x), x.stride(0), _ptr(dy), dy.stride(0), _ptr(out), P, K, kr, N, _ptr(self._mm_ws(P, K, N)), _stream()),
+    _lib.check(self.L.vp_mm_bwd_weight_f32(ptr(x), x.stride(0), ptr(dy), dy.stride(0), ptr(out), P, K, kr, N, ptr(self._mm_ws(P, K, N)), stream()),
                "vp_mm_bwd_weight_f32")
     return out
 
   def _sumsq(self, x):
     n = self.L.vp_sumsq_partials(x.numel())
     part = torch.empty(n, dtype=torch.float64, device=self.dev)
-    _lib.check(self.L.vp_sumsq(_ptr(x), x.numel(), _ptr(part), _stream()), "vp_sumsq")
+    _lib.check(self.L.vp_sumsq(ptr(x), x.numel(), ptr(part), stream()), "vp_sumsq")
     return self._sum64(part)
 
   def _sum64(self, part, scale=1.0, add=None):
     """Float64 device scalar = (add or 0) + scale * sum(part), by the library's one-block kernel (no framework reduction on the path)."""
     out = torch.empty((), dtype=torch.float64, device=self.dev)
-    _lib.check(self.L.vp_sum_f64(_ptr(part), part.numel(), float(scale), _ptr(add) if add is not None else None, _ptr(out), _stream()), "vp_sum_f64")
+    _lib.check(self.L.vp_sum_f64(ptr(part), part.numel(), float(scale), ptr(add) if add is not None else None, ptr(out), stream()), "vp_sum_f64")
     return out
 
   # ---- conv + batch-norm + activation, forward / backward -----------------------------------------------------------------------
@@ -454,7 +446,7 @@ class BFMNetTrainEngine:
     # stem: 9x5 stride (1,2) as im2col + GEMM
     Wo = (W + 1) // 2
     col = torch.empty(B * H * Wo, 48, dtype=torch.float32, device=self.dev)
-    _lib.check(L.vp_stem_im2col(_ptr(mfccs.contiguous()), _ptr(col), B, H, W, _stream()), "vp_stem_im2col")
+    _lib.check(L.vp_stem_im2col(ptr(mfccs.contiguous()), ptr(col), B, H, W, stream()), "vp_stem_im2col")
     s0 = PREFIX + "block0_0/conv2d"
     k0 = torch.zeros(48, 32, dtype=torch.float32, device=self.dev)
     k0[:45] = p[s0 + "/conv2d/kernel"].reshape(45, 32)
@@ -503,17 +495,17 @@ class BFMNetTrainEngine:
     # the recurrent halves of the two GRUCell kernels, as they are (forward) and transposed (backward): one launch, no at::native copies
     whg, whg_t = (torch.empty(256, 512, dtype=torch.float32, device=self.dev), torch.empty(512, 256, dtype=torch.float32, device=self.dev))
     whc, whc_t = (torch.empty(256, 256, dtype=torch.float32, device=self.dev), torch.empty(256, 256, dtype=torch.float32, device=self.dev))
-    _lib.check(L.vp_gru_split_recurrent(_ptr(wg), _ptr(wc), _ptr(whg), _ptr(whc), _ptr(whg_t), _ptr(whc_t), _stream()), "vp_gru_split_recurrent")
+    _lib.check(L.vp_gru_split_recurrent(ptr(wg), ptr(wc), ptr(whg), ptr(whc), ptr(whg_t), ptr(whc_t), stream()), "vp_gru_split_recurrent")
     rnn, sr, su, scand, shp = (torch.empty(B * T, 256, dtype=torch.float32, device=self.dev) for _ in range(5))
-    _lib.check(L.vp_gru_train_fwd(_ptr(xg), _ptr(xc), _ptr(whg), _ptr(whc), _ptr(seq), _ptr(rnn), _ptr(sr), _ptr(su), _ptr(scand), _ptr(shp), B, T,
-                                  _stream()), "vp_gru_train_fwd")
+    _lib.check(L.vp_gru_train_fwd(ptr(xg), ptr(xc), ptr(whg), ptr(whc), ptr(seq), ptr(rnn), ptr(sr), ptr(su), ptr(scand), ptr(shp), B, T,
+                                  stream()), "vp_gru_train_fwd")
     mr = mk("rnn", 256)
     rnn_m = rnn if mr is None else self._act(rnn, None, None, ACT_NONE, mr)
     d0 = dense(rnn_m, "bfm_coeff_decoder/dense/kernel", "bfm_coeff_decoder/dense/bias", ACT_LRELU, mk("d0", 128))
     d1 = dense(d0, "bfm_coeff_decoder/dense_1/kernel", "bfm_coeff_decoder/dense_1/bias", ACT_LRELU, mk("d1", 64))
     o = dense(d1, "bfm_coeff_decoder/dense_2/kernel", "bfm_coeff_decoder/dense_2/bias", ACT_NONE, None)
     # + tf.pad(ears * [-2,-2,-2,-4], [16, 44]), in place (the last dense layer has no activation: its backward never reads its output)
-    _lib.check(L.vp_add_ears_f32(_ptr(o), _ptr(ears.reshape(B * T).contiguous()), B * T, _stream()), "vp_add_ears_f32")
+    _lib.check(L.vp_add_ears_f32(ptr(o), ptr(ears.reshape(B * T).contiguous()), B * T, stream()), "vp_add_ears_f32")
     self.last_out = o.view(B, T, 64)
 
     loss_data, do = self._vertex_loss(o, bfm_coeffs, seq)
@@ -535,8 +527,8 @@ class BFMNetTrainEngine:
     if mr is not None:
       d = self._mul(d, mr)
     dag, dac = torch.empty(B * T, 512, dtype=torch.float32, device=self.dev), torch.empty(B * T, 256, dtype=torch.float32, device=self.dev)
-    _lib.check(L.vp_gru_train_bwd(_ptr(d.contiguous()), _ptr(whg_t), _ptr(whc_t), _ptr(seq), _ptr(sr), _ptr(su), _ptr(scand), _ptr(shp), _ptr(dag), _ptr(dac),
-                                  B, T, _stream()), "vp_gru_train_bwd")
+    _lib.check(L.vp_gru_train_bwd(ptr(d.contiguous()), ptr(whg_t), ptr(whc_t), ptr(seq), ptr(sr), ptr(su), ptr(scand), ptr(shp), ptr(dag), ptr(dac),
+                                  B, T, stream()), "vp_gru_train_bwd")
     srh = self._mul(sr, shp)
     def gru_wg():
       self._mm_dw(c1, dag, g[GRU + "gates/kernel"][:256])
@@ -588,21 +580,21 @@ class BFMNetTrainEngine:
     self._join()                                                                     # every weight gradient is in the arena
     # ---- regulariser, clip_by_global_norm, Adam, moving averages ------------------------------------------------------------------------
     part = torch.empty(L.vp_sumsq_partials(self.ntrain), dtype=torch.float64, device=self.dev)
-    _lib.check(L.vp_l2_regulariser(_ptr(self.arena), _ptr(self.l2mask), _ptr(self.grads), self.ntrain, L2_SCALE, _ptr(part), _stream()), "vp_l2_regulariser")
+    _lib.check(L.vp_l2_regulariser(ptr(self.arena), ptr(self.l2mask), ptr(self.grads), self.ntrain, L2_SCALE, ptr(part), stream()), "vp_l2_regulariser")
     reg = self._sum64(part)
     ss = self._sumsq(self.grads)
     self._last_ss = ss
     if apply:
-      _lib.check(L.vp_adam_tf_clipped(_ptr(self.arena), _ptr(self.grads), _ptr(self.m), _ptr(self.v), self.ntrain, _ptr(self.lr_t), _ptr(ss), self.clip,
-                                      0.9, 0.999, 1e-8, _stream()), "vp_adam_tf_clipped")
-      _lib.check(L.vp_moving_update(_ptr(self.arena[self.ntrain:]), _ptr(self.bstats), _ptr(self._moving_factor()), self.bstats.numel(), BN_DECAY,
-                                    _stream()), "vp_moving_update")
+      _lib.check(L.vp_adam_tf_clipped(ptr(self.arena), ptr(self.grads), ptr(self.m), ptr(self.v), self.ntrain, ptr(self.lr_t), ptr(ss), self.clip,
+                                      0.9, 0.999, 1e-8, stream()), "vp_adam_tf_clipped")
+      _lib.check(L.vp_moving_update(ptr(self.arena[self.ntrain:]), ptr(self.bstats), ptr(self._moving_factor()), self.bstats.numel(), BN_DECAY,
+                                    stream()), "vp_moving_update")
     else:
-      _lib.check(L.vp_clip_scale_f32(_ptr(self.grads), self.ntrain, _ptr(ss), self.clip, _stream()), "vp_clip_scale_f32")
+      _lib.check(L.vp_clip_scale_f32(ptr(self.grads), self.ntrain, ptr(ss), self.clip, stream()), "vp_clip_scale_f32")
     if self._pk_pending and not torch.cuda.is_current_stream_capturing():
       self._build_pack_table()                                                       # after the first eager step: the products are known
     rep = torch.empty(3, dtype=torch.float64, device=self.dev)
-    _lib.check(L.vp_bfm_step_report(_ptr(loss_data), _ptr(reg), 0.5 * L2_SCALE, _ptr(ss), _ptr(rep), _stream()), "vp_bfm_step_report")
+    _lib.check(L.vp_bfm_step_report(ptr(loss_data), ptr(reg), 0.5 * L2_SCALE, ptr(ss), ptr(rep), stream()), "vp_bfm_step_report")
     return rep
 
   def _vertex_loss(self, o, bfm_coeffs, seq):
@@ -615,7 +607,7 @@ class BFMNetTrainEngine:
     gD = torch.empty_like(D)
     npart = L.vp_vertex_loss_partials(B, J)
     part = torch.empty(npart, dtype=torch.float64, device=self.dev)
-    _lib.check(L.vp_bfm_vertex_loss(_ptr(D), _ptr(self.vmask), _ptr(seq), B, T, J, _ptr(gD), _ptr(part), _stream()), "vp_bfm_vertex_loss")
+    _lib.check(L.vp_bfm_vertex_loss(ptr(D), ptr(self.vmask), ptr(seq), B, T, J, ptr(gD), ptr(part), stream()), "vp_bfm_vertex_loss")
     # gD . exBase contracts over the 3n vertex coordinates (not a multiple of the kernels' 16-float K chunk): a zero-padded copy
     gp = self._gdpad
     if gp is None or gp.shape[0] != B * T:
@@ -628,7 +620,7 @@ class BFMNetTrainEngine:
     for n in self.p:
       if regularised(n):
         part = torch.empty(self.L.vp_sumsq_partials(self.p[n].numel()), dtype=torch.float64, device=self.dev)
-        _lib.check(self.L.vp_sumsq(_ptr(self.p[n]), self.p[n].numel(), _ptr(part), _stream()), "vp_sumsq")
+        _lib.check(self.L.vp_sumsq(ptr(self.p[n]), self.p[n].numel(), ptr(part), stream()), "vp_sumsq")
         reg = self._sum64(part, add=reg)
     return float(reg) * 0.5 * L2_SCALE if reg is not None else 0.0
 

@@ -16,7 +16,6 @@ MeshSheet(swap_rb=True) gives the reference's in-memory big_img instead.
 
 No CPU fallback: without a GPU MeshSheet raises.  sheet_cells, splice_predicted and clip_time are plain arithmetic and need none.
 """
-import ctypes
 import os
 import re
 
@@ -59,15 +58,15 @@ def sheet_tile(tiles, sheet, first_cell=0, swap_rb=False):
   contiguous), on the current stream.  A cell outside the sheet raises before anything is enqueued."""
   import torch
   from .. import _lib
+  from .._handle import ptr, stream
   n, h, w = (int(v) for v in tiles.shape[:3])
   for t in (tiles, sheet):
     if not (t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.dim() == (4 if t is tiles else 3) and t.shape[-1] == 3):
       raise ValueError("sheet_tile: contiguous uint8 device tensors, tiles [n,h,w,3] and sheet [rows*h, cols*w, 3]")
   if sheet.shape[0] % h or sheet.shape[1] % w:
     raise ValueError("sheet_tile: a sheet of %d x %d is no whole number of %d x %d tiles" % (sheet.shape[0], sheet.shape[1], h, w))
-  _lib.check(_lib.lib().vp_sheet_tile_u8(ctypes.c_void_p(tiles.data_ptr()), n, h, w, ctypes.c_void_p(sheet.data_ptr()), int(sheet.shape[0]) // h,
-                                         int(sheet.shape[1]) // w, int(first_cell), 1 if swap_rb else 0,
-                                         ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "vp_sheet_tile_u8")
+  _lib.check(_lib.lib().vp_sheet_tile_u8(ptr(tiles), n, h, w, ptr(sheet), int(sheet.shape[0]) // h, int(sheet.shape[1]) // w, int(first_cell),
+                                         1 if swap_rb else 0, stream()), "vp_sheet_tile_u8")
   return sheet
 
 
@@ -76,6 +75,7 @@ def landmark_distance(proj_a, proj_b, keypoints):
   proj_a and proj_b float64 [F,N,2] (device, contiguous); keypoints int32 [68] device."""
   import torch
   from .. import _lib
+  from .._handle import ptr, stream
   F, N = int(proj_a.shape[0]), int(proj_a.shape[1])
   for t in (proj_a, proj_b):
     if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == (F, N, 2)):
@@ -83,9 +83,7 @@ def landmark_distance(proj_a, proj_b, keypoints):
   if not (keypoints.is_cuda and keypoints.dtype == torch.int32 and keypoints.is_contiguous() and keypoints.numel() == 68):
     raise ValueError("landmark_distance: keypoints int32 [68] on the device")
   out = torch.empty(F, 2, dtype=torch.float64, device=proj_a.device)
-  _lib.check(_lib.lib().vp_landmark_distance(ctypes.c_void_p(proj_a.data_ptr()), ctypes.c_void_p(proj_b.data_ptr()), ctypes.c_void_p(keypoints.data_ptr()),
-                                             F, N, ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)),
-             "vp_landmark_distance")
+  _lib.check(_lib.lib().vp_landmark_distance(ptr(proj_a), ptr(proj_b), ptr(keypoints), F, N, ptr(out), stream()), "vp_landmark_distance")
   return out
 
 

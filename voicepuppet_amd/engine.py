@@ -10,15 +10,8 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._handle import Handle, ptr, stream, workspace_view
 from ._lib import VP_BF16, VP_F32, PixReferDesc
-
-
-def _ptr(t):
-  return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
-
-
-def _stream():
-  return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def manifest(desc, which):
@@ -36,8 +29,12 @@ def manifest(desc, which):
   return out
 
 
-class PixReferEngine:
-  """One replica of the PixReferNet graph (pixrefer.py:356-438) on the current device."""
+class PixReferEngine(Handle):
+  """One replica of the PixReferNet graph (pixrefer.py:356-438) on the current device.
+
+  close() destroys the plan NOW and returns its 7 GB workspace's owner to the collector.  (The executor's HIP streams are process-wide and
+  stay: until they were, an engine created while an earlier one's streams existed ran slow - scripts/exp_engine_sequence.py,
+  profiles/r06_exp_engine_sequence.txt.)"""
 
   def __init__(self, batch, height, ngf=64, ndf=64, dtype="bf16", training=True, l1_weight=500.0, gan_weight=1.0,
                device=None, per_sample_bn=False, streams=0, d_backward_fork=0, d_beside_vgg=0):
@@ -67,30 +64,9 @@ class PixReferEngine:
     self.grad_transport = "f32"          # data parallel: 'bf16' halves the bytes of the gradient all-reduce (parallel.GradExchange)
     self._exchange = None
     self.fused_update = True             # single-GPU train_step: vp_pixrefer_backward_update (backward + Adam x 2 + re-pack in one call)
-    ws = self.L.vp_pixrefer_workspace_bytes(d)
-    if ws == 0:
-      raise ValueError("invalid PixReferNet descriptor: %s" % self.L.vp_last_error().decode())
-    self.workspace = torch.zeros(ws, dtype=torch.uint8, device=self.device)
-    h = ctypes.c_void_p()
-    _lib.check(self.L.vp_pixrefer_create(d, _ptr(self.workspace), ws, _ptr(self.params_g), _ptr(self.params_d),
-                                         _ptr(self.params_vgg), _ptr(self.grads_g), _ptr(self.grads_d), _stream(),
-                                         ctypes.byref(h)), "vp_pixrefer_create")
-    self.h = h
+    self._open("pixrefer", self.desc, (ptr(self.params_g), ptr(self.params_d), ptr(self.params_vgg), ptr(self.grads_g), ptr(self.grads_d), stream()),
+               zero=True, invalid="invalid PixReferNet descriptor", device=self.device)
     self._keep = None
-
-  def close(self):
-    """Destroys the plan NOW and returns its 7 GB workspace's owner to the collector.  (The executor's HIP streams are process-wide and
-    stay: until they were, an engine created while an earlier one's streams existed ran slow - scripts/exp_engine_sequence.py,
-    profiles/r06_exp_engine_sequence.txt.)"""
-    if getattr(self, "h", None):
-      self.L.vp_pixrefer_destroy(self.h)
-      self.h = None
-
-  def __del__(self):
-    try:
-      self.close()
-    except Exception:
-      pass
 
   # ---- parameters -------------------------------------------------------------------------------
   def arena(self, which):
@@ -168,24 +144,24 @@ class PixReferEngine:
     self._keep = (ts, m)   # the backward reads targets/masks again
     if fg_inputs.shape[-1] == 3:   # infer_bfmvid.py:203 feeds a 3-channel foreground reference: the library reads it as it is
       assert fg_inputs.shape == (N, H, H, 3) and not self.training
-      _lib.check(self.L.vp_pixrefer_forward_fg3(self.h, _ptr(ts[0]), _ptr(ts[1]), _ptr(ts[2]), _stream()), "vp_pixrefer_forward_fg3")
+      _lib.check(self.L.vp_pixrefer_forward_fg3(self.h, ptr(ts[0]), ptr(ts[1]), ptr(ts[2]), stream()), "vp_pixrefer_forward_fg3")
       return
     assert fg_inputs.shape == (N, H, H, 6)
-    _lib.check(self.L.vp_pixrefer_forward(self.h, _ptr(ts[0]), _ptr(ts[1]), _ptr(ts[2]), _ptr(m), _stream()),
+    _lib.check(self.L.vp_pixrefer_forward(self.h, ptr(ts[0]), ptr(ts[1]), ptr(ts[2]), ptr(m), stream()),
                "vp_pixrefer_forward")
 
   def backward(self):
-    _lib.check(self.L.vp_pixrefer_backward(self.h, _stream()), "vp_pixrefer_backward")
+    _lib.check(self.L.vp_pixrefer_backward(self.h, stream()), "vp_pixrefer_backward")
 
   def backward_d(self):
-    _lib.check(self.L.vp_pixrefer_backward_d(self.h, _stream()), "vp_pixrefer_backward_d")
+    _lib.check(self.L.vp_pixrefer_backward_d(self.h, stream()), "vp_pixrefer_backward_d")
 
   def backward_g(self):
-    _lib.check(self.L.vp_pixrefer_backward_g(self.h, _stream()), "vp_pixrefer_backward_g")
+    _lib.check(self.L.vp_pixrefer_backward_g(self.h, stream()), "vp_pixrefer_backward_g")
 
   def backward_g_stage(self, stage):
     """Stage `stage` of backward_g (0 .. backward_g_stages()-1); see grad_buckets_g."""
-    _lib.check(self.L.vp_pixrefer_backward_g_stage(self.h, int(stage), _stream()), "vp_pixrefer_backward_g_stage")
+    _lib.check(self.L.vp_pixrefer_backward_g_stage(self.h, int(stage), stream()), "vp_pixrefer_backward_g_stage")
 
   def grad_buckets_g(self):
     """[(lo, hi)] float ranges of the generator gradient arena that are final after stage 0, 1, 2 of backward_g:
@@ -212,8 +188,8 @@ class PixReferEngine:
       self.t_d += 1
       self.t_g += 1
       (m_g, v_g), (m_d, v_d) = self.adam["g"], self.adam["d"]
-      _lib.check(self.L.vp_pixrefer_backward_update(self.h, _ptr(m_g), _ptr(v_g), _ptr(m_d), _ptr(v_d), self.t_g, self.t_d, lr, beta1,
-                                                    0.999, 1e-8, _stream()), "vp_pixrefer_backward_update")
+      _lib.check(self.L.vp_pixrefer_backward_update(self.h, ptr(m_g), ptr(v_g), ptr(m_d), ptr(v_d), self.t_g, self.t_d, lr, beta1,
+                                                    0.999, 1e-8, stream()), "vp_pixrefer_backward_update")
       return
     if group is None:
       self.backward()          # both passes, the discriminator-loss pass on the executor's side stream
@@ -241,10 +217,10 @@ class PixReferEngine:
 
       def update(which, bucket):
         m, v, t = (m_d, v_d, self.t_d) if which else (m_g, v_g, self.t_g)
-        return lambda sp: _lib.check(self.L.vp_pixrefer_update_bucket(self.h, which, bucket, _ptr(m), _ptr(v), t, lr, beta1, 0.999, 1e-8, sp),
+        return lambda sp: _lib.check(self.L.vp_pixrefer_update_bucket(self.h, which, bucket, ptr(m), ptr(v), t, lr, beta1, 0.999, 1e-8, sp),
                                      "vp_pixrefer_update_bucket")
       ex.begin_step()
-      _lib.check(self.L.vp_pixrefer_backward_d_fork(self.h, _stream()), "vp_pixrefer_backward_d_fork")
+      _lib.check(self.L.vp_pixrefer_backward_d_fork(self.h, stream()), "vp_pixrefer_backward_d_fork")
       d_early = not self.dp_own_stream
       for stage, (lo, hi) in enumerate(self.grad_buckets_g()):
         self.backward_g_stage(stage)
@@ -255,7 +231,7 @@ class PixReferEngine:
           # all-reduce -> Adam -> re-pack chain was the tail of every data-parallel step
           ex.start(self.grads_d, then=update(1, 0), name="discriminator")
         ex.start(self.grads_g[lo:hi], then=update(0, stage), name="generator stage %d" % stage)
-      _lib.check(self.L.vp_pixrefer_backward_d_join(self.h, _stream()), "vp_pixrefer_backward_d_join")
+      _lib.check(self.L.vp_pixrefer_backward_d_join(self.h, stream()), "vp_pixrefer_backward_d_join")
       if not d_early:
         # a communication stream of the exchange's own: the discriminator-loss pass has to be joined first; its bucket goes last
         ex.start(self.grads_d, then=update(1, 0), name="discriminator")       # (an event on this stream covers the joined pass: include/vp_hip.h)
@@ -269,7 +245,7 @@ class PixReferEngine:
     self.t_g += 1
     for key, p, g, t in (("d", self.params_d, self.grads_d, self.t_d), ("g", self.params_g, self.grads_g, self.t_g)):
       m, v = self.adam[key]
-      _lib.check(self.L.vp_adam_tf(_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), t, lr, beta1, beta2, eps, _stream()),
+      _lib.check(self.L.vp_adam_tf(ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), t, lr, beta1, beta2, eps, stream()),
                  "vp_adam_tf")
     _lib.check(self.L.vp_pixrefer_optimizer_stepped(self.h))      # generator / discriminator moved; the frozen vgg_16 trunk did not
 
@@ -281,12 +257,7 @@ class PixReferEngine:
     dt = ctypes.c_int()
     _lib.check(self.L.vp_pixrefer_tensor(self.h, name.encode(), ctypes.byref(p), shp, ctypes.byref(dt)),
                "vp_pixrefer_tensor(%s)" % name)
-    shape = tuple(int(s) for s in shp)
-    tdt = torch.bfloat16 if dt.value == VP_BF16 else torch.float32
-    nbytes = int(np.prod(shape)) * (2 if dt.value == VP_BF16 else 4)
-    off = p.value - self.workspace.data_ptr()
-    assert 0 <= off and off + nbytes <= self.workspace.numel(), name
-    return self.workspace[off:off + nbytes].view(tdt).view(shape)
+    return workspace_view(self.workspace, p.value, shp, torch.bfloat16 if dt.value == VP_BF16 else torch.float32)
 
   FETCH = {"Outputs": 0, "Outputs_u8": 1, "Alphas": 2, "Outputs_FG": 3}
 
@@ -296,7 +267,7 @@ class PixReferEngine:
     pixrefer.py:436 quirk on an inference plan).  [N, H, H, 3] device tensor."""
     n, hgt = self.desc.batch, self.desc.height
     out = torch.empty((n, hgt, hgt, 3), dtype=torch.uint8 if name == "Outputs_u8" else torch.float32, device=self.device)
-    _lib.check(self.L.vp_pixrefer_fetch(self.h, self.FETCH[name], _ptr(out), _stream()), "vp_pixrefer_fetch(%s)" % name)
+    _lib.check(self.L.vp_pixrefer_fetch(self.h, self.FETCH[name], ptr(out), stream()), "vp_pixrefer_fetch(%s)" % name)
     return out
 
   def profile(self, on):

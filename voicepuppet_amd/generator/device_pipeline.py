@@ -7,13 +7,13 @@ uint8 frames (2 * 9 * S * S bytes per sample: 8x fewer bytes over PCIe) and thre
 vp_pixrefer_pack_frames does the rest in one kernel, and `FramePrefetcher` overlaps the copies of batch k+1 with step k on a
 second HIP stream (pinned staging buffers, event hand-off).
 """
-import ctypes
 import random
 
 import numpy as np
 import torch
 
 from .. import _lib
+from .._handle import ptr, stream
 
 
 def draw_crop(img_size, crop_ratio, rng=random):
@@ -42,10 +42,8 @@ class DeviceFramePacker:
     assert ex_u8.shape == (N, S, 3 * S, 3) and cur_u8.shape == ex_u8.shape and ex_u8.dtype == torch.uint8 and cur_u8.dtype == torch.uint8
     assert crops.shape == (N, 2, 3) and crops.dtype == torch.int32
     ex_u8, cur_u8, crops = ex_u8.contiguous(), cur_u8.contiguous(), crops.contiguous()
-    p = lambda t: ctypes.c_void_p(t.data_ptr())
-    _lib.check(self.L.vp_pixrefer_pack_frames(p(ex_u8), p(cur_u8), p(crops), N, S, p(self.out[0]), p(self.out[1]), p(self.out[2]),
-                                              p(self.out[3]), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)),
-               "vp_pixrefer_pack_frames")
+    _lib.check(self.L.vp_pixrefer_pack_frames(ptr(ex_u8), ptr(cur_u8), ptr(crops), N, S, ptr(self.out[0]), ptr(self.out[1]), ptr(self.out[2]),
+                                              ptr(self.out[3]), stream()), "vp_pixrefer_pack_frames")
     return self.out
 
 

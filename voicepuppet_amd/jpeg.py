@@ -13,23 +13,16 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._handle import Handle, ptr, rows_to_host, stream
 
 logger = logging.getLogger(__name__)
-
-
-def _ptr(t):
-  return ctypes.c_void_p(t.data_ptr())
-
-
-def _stream():
-  return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def jpeg_desc(height, width, max_frames, quality=75):
   return _lib.JpegDesc(ctypes.sizeof(_lib.JpegDesc), int(max_frames), int(height), int(width), int(quality))
 
 
-class JpegEncoder:
+class JpegEncoder(Handle):
   """encode(frames uint8 [K, H, W, 3] device, K <= max_frames) -> (bytes uint8 [K, cap] device, lengths int32 [K] device), enqueued on the
   current stream; to_host(bytes, lengths[, frames]) -> list of K bytes objects, each a complete .jpg file."""
 
@@ -38,17 +31,9 @@ class JpegEncoder:
   def __init__(self, height, width, max_frames, quality=75):
     if not torch.cuda.is_available():
       raise RuntimeError("JpegEncoder needs an MI355X (no CPU fallback)")
-    self.L = _lib.lib()
-    self.desc = jpeg_desc(height, width, max_frames, quality)
-    ws = self.L.vp_jpeg_workspace_bytes(ctypes.byref(self.desc))
-    if ws == 0:
-      raise ValueError("invalid JPEG encoder descriptor: " + self.L.vp_last_error().decode())
+    self._open("jpeg", jpeg_desc(height, width, max_frames, quality), (stream(),), invalid="invalid JPEG encoder descriptor")
     self.height, self.width, self.max_frames, self.quality = int(height), int(width), int(max_frames), int(quality)
     self.capacity = int(self.L.vp_jpeg_frame_capacity(ctypes.byref(self.desc)))
-    self.workspace = torch.empty(ws, dtype=torch.uint8, device="cuda")
-    h = ctypes.c_void_p()
-    _lib.check(self.L.vp_jpeg_create(ctypes.byref(self.desc), _ptr(self.workspace), ws, _stream(), ctypes.byref(h)), "vp_jpeg_create")
-    self.h = h
 
   def encode(self, frames, out=None, lengths=None):
     """out / lengths: rows of a larger [*, cap] / [*] pair to write into (a push that encodes in several launches); allocated when None."""
@@ -61,7 +46,7 @@ class JpegEncoder:
       out = torch.empty(K, self.capacity, dtype=torch.uint8, device="cuda")
       lengths = torch.empty(K, dtype=torch.int32, device="cuda")
     assert out.is_contiguous() and lengths.is_contiguous() and out.shape[0] >= K and lengths.shape[0] >= K
-    _lib.check(self.L.vp_jpeg_encode(self.h, _ptr(frames), K, _ptr(out), int(out.shape[1]), _ptr(lengths), _stream()), "vp_jpeg_encode")
+    _lib.check(self.L.vp_jpeg_encode(self.h, ptr(frames), K, ptr(out), int(out.shape[1]), ptr(lengths), stream()), "vp_jpeg_encode")
     return out[:K], lengths[:K]
 
   def header(self):
@@ -73,30 +58,14 @@ class JpegEncoder:
 
   def coefficients(self):
     """int16 [max_frames, H/16, 6 * W/16, 64] view of the quantised coefficients (tests; encodes store them from this call on)."""
-    p = ctypes.c_void_p()
-    shp = (ctypes.c_int64 * 4)()
-    _lib.check(self.L.vp_jpeg_tensor(self.h, b"coefficients", ctypes.byref(p), shp), "vp_jpeg_tensor")
-    n = 2 * int(shp[0]) * int(shp[1]) * int(shp[2]) * int(shp[3])
-    off = p.value - self.workspace.data_ptr()
-    return self.workspace[off:off + n].view(torch.int16).view(*[int(v) for v in shp])
+    return self._tensor("coefficients", torch.int16, 4)
 
   def to_host(self, data, lengths, frames=None):
-    """One pinned copy of the lengths (the wait), then one of the used prefix of the rows.  frames: the raw frames, for the rows the
-    device gave up on (length -1); without them such a row raises."""
-    K = int(lengths.shape[0])
-    pinned = torch.empty(K, dtype=torch.int32).pin_memory()
-    pinned.copy_(lengths, non_blocking=True)
-    torch.cuda.current_stream().synchronize()
-    n = pinned.numpy().copy()
-    used = int(n.max()) if K else 0
-    host = None
-    if used > 0:
-      host = torch.empty(K, used, dtype=torch.uint8).pin_memory()
-      host.copy_(data[:K, :used], non_blocking=True)
-      torch.cuda.current_stream().synchronize()
-      host = host.numpy()
+    """One pinned copy of the lengths (the wait), then one of the used prefix of the rows (rows_to_host).  frames: the raw frames, for
+    the rows the device gave up on (length -1); without them such a row raises."""
+    (host, n), = rows_to_host([(data, lengths)])
     files = []
-    for i in range(K):
+    for i in range(len(n)):
       if n[i] >= 0:
         files.append(host[i, :n[i]].tobytes())
         continue
@@ -107,14 +76,6 @@ class JpegEncoder:
         logger.warning("a frame did not fit the device JPEG encoder's slots: encoded on the host (logged once)")
       files.append(host_jpeg(frames[i].cpu().numpy(), self.quality))
     return files
-
-  def __del__(self):
-    try:
-      if getattr(self, "h", None):
-        self.L.vp_jpeg_destroy(self.h)
-        self.h = None
-    except Exception:
-      pass
 
 
 def host_jpeg(frame_u8, quality=75):

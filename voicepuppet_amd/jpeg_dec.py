@@ -23,6 +23,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._handle import Handle, ptr, stream
 
 LOOKUP_BITS = 9
 META_BYTES = _lib.JPEGDEC_META_BYTES
@@ -206,20 +207,12 @@ def meta_blob(info, segments=None):
   return head.tobytes() + info.tables + np.ascontiguousarray(seg, np.int32).tobytes()
 
 
-def _ptr(t):
-  return ctypes.c_void_p(t.data_ptr())
-
-
-def _stream():
-  return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def _key(path):
   st = os.stat(path)
   return (os.path.abspath(path), st.st_size, st.st_mtime_ns)
 
 
-class JpegDecoder:
+class JpegDecoder(Handle):
   """decode(files) -> (uint8 [n, max_height, max_width, 3] device, status int32 [n] device), files being bytes or paths.  A path's decode
   feeds the index cache and uses it from its second decode on.  last_segments: the segment count of every file of the last call.  It is
   a read-only property and, with the index scan enabled, a lazy one: the count of a scanned file (its MCU rows, or 1) is the device's
@@ -237,24 +230,17 @@ class JpegDecoder:
                scan_chunk_bytes=None, scan_max_rounds=512):
     if not torch.cuda.is_available():
       raise RuntimeError("JpegDecoder needs an MI355X (no CPU fallback)")
-    self.L = _lib.lib()
-    self.desc = _lib.JpegDecDesc(ctypes.sizeof(_lib.JpegDecDesc), int(max_files), int(max_height), int(max_width), int(max_file_bytes),
-                                 int(max_segments_per_file), int(bool(bgr)))
-    ws = self.L.vp_jpegdec_workspace_bytes(ctypes.byref(self.desc))
-    if ws == 0:
-      raise ValueError("invalid JPEG decoder descriptor: " + self.L.vp_last_error().decode())
+    desc = _lib.JpegDecDesc(ctypes.sizeof(_lib.JpegDecDesc), int(max_files), int(max_height), int(max_width), int(max_file_bytes),
+                            int(max_segments_per_file), int(bool(bgr)))
+    self._open("jpegdec", desc, invalid="invalid JPEG decoder descriptor")
     self.max_files, self.max_height, self.max_width, self.bgr = int(max_files), int(max_height), int(max_width), bool(bgr)
-    self.workspace = torch.empty(ws, dtype=torch.uint8, device="cuda")
-    h = ctypes.c_void_p()
-    _lib.check(self.L.vp_jpegdec_create(ctypes.byref(self.desc), _ptr(self.workspace), ws, ctypes.byref(h)), "vp_jpegdec_create")
-    self.h = h
     self.scan_chunk_bytes, self.scan_max_rounds, self.scan_workspace = None, None, None
     if scan_chunk_bytes is not None:
       sws = self.L.vp_jpegdec_scan_workspace_bytes(ctypes.byref(self.desc), int(scan_chunk_bytes))
       if sws == 0:
         raise ValueError("invalid JPEG index scan setting: " + self.L.vp_last_error().decode())
       self.scan_workspace = torch.empty(sws, dtype=torch.uint8, device="cuda")
-      _lib.check(self.L.vp_jpegdec_enable_scan(self.h, _ptr(self.scan_workspace), sws, int(scan_chunk_bytes), int(scan_max_rounds)),
+      _lib.check(self.L.vp_jpegdec_enable_scan(self.h, ptr(self.scan_workspace), sws, int(scan_chunk_bytes), int(scan_max_rounds)),
                  "vp_jpegdec_enable_scan")
       self.scan_chunk_bytes, self.scan_max_rounds = int(scan_chunk_bytes), int(scan_max_rounds)
     self.index = {}                 # (path, size, mtime_ns) -> int32 [mcuy, 4]
@@ -315,17 +301,10 @@ class JpegDecoder:
   def tensor(self, name):
     """'coefficients' int16 [max_files, blocks, 64], 'entries' int32 [max_files, rows, 4], 'planes' uint8 [max_files, 3, Hp, Wp]: views of
     the workspace, rows in the order of the last decode.  With the index scan 'scan_ok' and 'scan_rounds', int32 [max_files]."""
-    p, shp = ctypes.c_void_p(), (ctypes.c_int64 * 4)()
-    _lib.check(self.L.vp_jpegdec_tensor(self.h, name.encode(), ctypes.byref(p), shp), "vp_jpegdec_tensor")
-    shape = [int(v) for v in shp]
-    if name in ("scan_ok", "scan_rounds"):
-      off = p.value - self.scan_workspace.data_ptr()
-      return self.scan_workspace[off:off + 4 * shape[0]].view(torch.int32)
+    if name in ("scan_ok", "scan_rounds"):          # the index scan's buffers lie in its own workspace
+      return self._tensor(name, torch.int32, 1, self.scan_workspace)
     dtype = {"coefficients": torch.int16, "entries": torch.int32, "planes": torch.uint8}[name]
-    off = p.value - self.workspace.data_ptr()
-    n = int(np.prod(shape)) * torch.empty(0, dtype=dtype).element_size()
-    t = self.workspace[off:off + n].view(dtype)
-    return t.view(*(shape if name == "planes" else shape[:3]))
+    return self._tensor(name, dtype, 4 if name == "planes" else 3)
 
   def pack(self, items):
     """Host half of a decode.  items: [(bytes, JpegInfo, key or None, segments or None, name) or None (a gap: that row of the output is
@@ -376,7 +355,7 @@ class JpegDecoder:
     n = len(items)
     pinned, dev, st_host, en_host, scan_host = self._ring[slot]
     dev[:at].copy_(pinned[:at], non_blocking=True)
-    _lib.check(self.L.vp_jpegdec_decode(self.h, _ptr(dev), table, n, _ptr(out), int(row_pitch), int(frame_stride), _ptr(status), _stream()),
+    _lib.check(self.L.vp_jpegdec_decode(self.h, ptr(dev), table, n, ptr(out), int(row_pitch), int(frame_stride), ptr(status), stream()),
                "vp_jpegdec_decode")
     st_host[:n].copy_(status[:n], non_blocking=True)
     en_host[:n].copy_(self.tensor("entries")[:n], non_blocking=True)
@@ -428,11 +407,3 @@ class JpegDecoder:
     status = torch.empty(len(items), dtype=torch.int32, device="cuda")
     self.decode_into(items, out, out.stride(1), out.stride(0), status, raise_bad=False)
     return out[:len(items)], status
-
-  def __del__(self):
-    try:
-      if getattr(self, "h", None):
-        self.L.vp_jpegdec_destroy(self.h)
-        self.h = None
-    except Exception:
-      pass

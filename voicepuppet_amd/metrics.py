@@ -9,6 +9,7 @@ import ctypes
 import torch
 
 from . import _lib
+from ._handle import Handle, ptr, stream
 
 L1, MSE, PSNR, SSIM = 0, 1, 2, 3
 COLUMNS = ("L1", "MSE", "PSNR", "SSIM")
@@ -16,19 +17,11 @@ COLUMNS = ("L1", "MSE", "PSNR", "SSIM")
 VALUE_RANGES = {(-1, 1): (127.5, 127.5), (0, 255): (1.0, 0.0), (0, 1): (255.0, 0.0)}
 
 
-def _ptr(t):
-  return ctypes.c_void_p(t.data_ptr())
-
-
-def _stream():
-  return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def frame_metrics_desc(max_frames, max_height, max_width):
   return _lib.FrameMetricsDesc(ctypes.sizeof(_lib.FrameMetricsDesc), int(max_frames), int(max_height), int(max_width))
 
 
-class FrameMetrics:
+class FrameMetrics(Handle):
   """compare(a, b) for device tensors [n, H, W, 3], both uint8 or both float32, n <= max_frames, 11 <= H <= max_height, 11 <= W <= max_width
   -> device float64 [n, 4], columns L1, MSE, PSNR, SSIM (the module's constants).  Strided views are taken as they are when a pixel's three
   values and a row's pixels are adjacent (stride 1 and 3 on the last two axes): a padded decoder output against a dense tensor."""
@@ -36,16 +29,8 @@ class FrameMetrics:
   def __init__(self, max_frames, max_height, max_width):
     if not torch.cuda.is_available():
       raise RuntimeError("FrameMetrics needs an MI355X (no CPU fallback)")
-    self.L = _lib.lib()
-    self.desc = frame_metrics_desc(max_frames, max_height, max_width)
-    ws = self.L.vp_frame_metrics_workspace_bytes(ctypes.byref(self.desc))
-    if ws == 0:
-      raise ValueError("invalid frame metrics descriptor: " + self.L.vp_last_error().decode())
+    self._open("frame_metrics", frame_metrics_desc(max_frames, max_height, max_width), invalid="invalid frame metrics descriptor")
     self.max_frames, self.max_height, self.max_width = int(max_frames), int(max_height), int(max_width)
-    self.workspace = torch.empty(ws, dtype=torch.uint8, device="cuda")
-    h = ctypes.c_void_p()
-    _lib.check(self.L.vp_frame_metrics_create(ctypes.byref(self.desc), _ptr(self.workspace), ws, ctypes.byref(h)), "vp_frame_metrics_create")
-    self.h = h
 
   @staticmethod
   def _layout(t, name):
@@ -72,28 +57,17 @@ class FrameMetrics:
     if out.dtype != torch.float64 or not out.is_cuda or not out.is_contiguous() or out.dim() != 2 or out.shape[1] != 4 or out.shape[0] < n:
       raise ValueError("compare: out must be a contiguous device float64 [>= %d, 4]" % n)
     if a.dtype == torch.uint8:
-      rc = self.L.vp_frame_metrics_u8(self.h, _ptr(a), ap, as_, _ptr(b), bp, bs, n, H, W, _ptr(out), _stream())
+      rc = self.L.vp_frame_metrics_u8(self.h, ptr(a), ap, as_, ptr(b), bp, bs, n, H, W, ptr(out), stream())
       _lib.check(rc, "vp_frame_metrics_u8")
     else:
       try:
         scale, offset = VALUE_RANGES[tuple(value_range)]
       except (KeyError, TypeError):
         raise ValueError("compare: value_range %r, (-1, 1), (0, 255) or (0, 1)" % (value_range,))
-      rc = self.L.vp_frame_metrics_f32(self.h, _ptr(a), ap, as_, _ptr(b), bp, bs, n, H, W, scale, offset, _ptr(out), _stream())
+      rc = self.L.vp_frame_metrics_f32(self.h, ptr(a), ap, as_, ptr(b), bp, bs, n, H, W, scale, offset, ptr(out), stream())
       _lib.check(rc, "vp_frame_metrics_f32")
     return out[:n]
 
   def tensor(self, name):
     """'abs_sum', 'sq_sum': int64 [max_frames] views of the workspace, the integer sums of the frames of the last uint8 compare."""
-    p, shp = ctypes.c_void_p(), (ctypes.c_int64 * 4)()
-    _lib.check(self.L.vp_frame_metrics_tensor(self.h, name.encode(), ctypes.byref(p), shp), "vp_frame_metrics_tensor")
-    off = p.value - self.workspace.data_ptr()
-    return self.workspace[off:off + 8 * int(shp[0])].view(torch.int64)
-
-  def __del__(self):
-    try:
-      if getattr(self, "h", None):
-        self.L.vp_frame_metrics_destroy(self.h)
-        self.h = None
-    except Exception:
-      pass
+    return self._tensor(name, torch.int64, 1)

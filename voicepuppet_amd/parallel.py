@@ -232,6 +232,7 @@ class GradExchange(object):
     stream (the bucket's Adam update)."""
     import ctypes
     from . import _lib
+    from ._handle import ptr
     ready = torch.cuda.Event()
     ready.record()                                   # on the stream the executor was driven from
     with torch.cuda.stream(self.stream):
@@ -243,10 +244,9 @@ class GradExchange(object):
       # (a blocking-style call: with RCCL it only orders the communication stream behind the collective, the host does not wait)
       if self.transport == "bf16":
         buf = self._buffer(t)
-        _lib.check(_lib.lib().vp_grad_pack_bf16(ctypes.c_void_p(t.data_ptr()), ctypes.c_void_p(buf.data_ptr()), t.numel(), sp), "vp_grad_pack_bf16")
+        _lib.check(_lib.lib().vp_grad_pack_bf16(ptr(t), ptr(buf), t.numel(), sp), "vp_grad_pack_bf16")
         dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=self.group)
-        _lib.check(_lib.lib().vp_grad_unpack_bf16(ctypes.c_void_p(buf.data_ptr()), ctypes.c_void_p(t.data_ptr()), t.numel(), 1.0 / self.world, sp),
-                   "vp_grad_unpack_bf16")
+        _lib.check(_lib.lib().vp_grad_unpack_bf16(ptr(buf), ptr(t), t.numel(), 1.0 / self.world, sp), "vp_grad_unpack_bf16")
       elif self.backend == "nccl":
         dist.all_reduce(t, op=dist.ReduceOp.AVG, group=self.group)
       else:

@@ -11,17 +11,10 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._handle import Handle, ptr, slot_arrays, stream
 
 COMMON_RATES = (8000, 16000, 22050, 24000, 32000, 44100, 48000, 96000)     # a default for PcmIngest(rates=): at most 8 per handle
 FORMATS = {"s16": (_lib.PCM_S16, np.int16), "f32": (_lib.PCM_F32, np.float32)}
-
-
-def _ptr(t):
-  return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
-
-
-def _stream():
-  return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def pcmin_desc(slots, rates, out_rate=16000, max_in_frames=1 << 20):
@@ -64,7 +57,7 @@ def read_wav(path):
   return int(rate), np.ascontiguousarray(data.reshape(data.shape[0], -1)), fmt
 
 
-class PcmIngest:
+class PcmIngest(Handle):
   """`slots` independent ingest sessions behind one handle.
 
   open_slot(slot, rate, channels=1, fmt="s16") starts (or restarts) a slot's clip.  push({slot: frames}, finish=()) -> (float32 device
@@ -75,16 +68,8 @@ class PcmIngest:
   def __init__(self, slots, rates=COMMON_RATES, out_rate=16000, max_in_frames=1 << 20):
     if not torch.cuda.is_available():
       raise RuntimeError("PcmIngest needs an MI355X (no CPU fallback)")
-    self.L = _lib.lib()
     self.slots, self.out_rate, self.max_in_frames = int(slots), int(out_rate), int(max_in_frames)
-    self.desc = pcmin_desc(slots, rates, out_rate, max_in_frames)
-    ws = self.L.vp_pcmin_workspace_bytes(ctypes.byref(self.desc))
-    if ws == 0:
-      raise ValueError("invalid ingest descriptor: " + self.L.vp_last_error().decode())
-    self.workspace = torch.empty(ws, dtype=torch.uint8, device="cuda")
-    h = ctypes.c_void_p()
-    _lib.check(self.L.vp_pcmin_create(ctypes.byref(self.desc), _ptr(self.workspace), ws, _stream(), ctypes.byref(h)), "vp_pcmin_create")
-    self.h = h
+    self._open("pcmin", pcmin_desc(slots, rates, out_rate, max_in_frames), (stream(),), invalid="invalid ingest descriptor")
     self.fmt = [None] * self.slots        # per open slot: (channels, numpy sample type)
 
   def open_slot(self, slot, rate, channels=1, fmt="s16"):
@@ -94,23 +79,13 @@ class PcmIngest:
     if fmt not in FORMATS:
       raise ValueError("fmt %r: one of %s" % (fmt, sorted(FORMATS)))
     code, dt = FORMATS[fmt]
-    _lib.check(self.L.vp_pcmin_open_slot(self.h, slot, int(rate), int(channels), code, _stream()), "vp_pcmin_open_slot")
+    _lib.check(self.L.vp_pcmin_open_slot(self.h, slot, int(rate), int(channels), code, stream()), "vp_pcmin_open_slot")
     self.fmt[slot] = (int(channels), np.dtype(dt))
-
-  def _arrays(self, n_by_slot, finish):
-    n = (ctypes.c_longlong * self.slots)()
-    fin = (ctypes.c_int * self.slots)()
-    items = n_by_slot.items() if isinstance(n_by_slot, dict) else enumerate(n_by_slot or ())
-    for s, v in items:
-      n[int(s)] = int(v)
-    for s in finish or ():
-      fin[int(s)] = 1
-    return n, fin
 
   def ready(self, frames_by_slot, finish=()):
     """Samples per slot (a list of `slots` counts) that a push of frames_by_slot ({slot: input frames} or a sequence) emits, the slots in
     `finish` ending their clips after them.  Host only.  (One launch: more than max_in_frames for a slot is refused; push splits.)"""
-    n, fin = self._arrays(frames_by_slot, finish)
+    n, fin = slot_arrays(self.slots, frames_by_slot, finish)
     k = (ctypes.c_longlong * self.slots)()
     if self.L.vp_pcmin_ready(self.h, n, fin, k) < 0:
       raise ValueError(self.L.vp_last_error().decode())
@@ -163,8 +138,8 @@ class PcmIngest:
           raw[offs[s]:offs[s] + v.numel()].copy_(v, non_blocking=True)
     total = sum(k)
     out = torch.empty(total, dtype=torch.float32, device="cuda")
-    n, fin = self._arrays(frames, finish)
-    _lib.check(self.L.vp_pcmin_push(self.h, _ptr(raw), n, fin, _ptr(out if total else None), _stream()), "vp_pcmin_push")
+    n, fin = slot_arrays(self.slots, frames, finish)
+    _lib.check(self.L.vp_pcmin_push(self.h, ptr(raw), n, fin, ptr(out if total else None), stream()), "vp_pcmin_push")
     return out, k
 
   def push(self, raw_by_slot, finish=()):
@@ -199,11 +174,3 @@ class PcmIngest:
     k = [sum(int(p.numel()) for p in pieces[s]) for s in range(self.slots)]
     flat = [p for s in range(self.slots) for p in pieces[s]]
     return (torch.cat(flat) if flat else torch.empty(0, dtype=torch.float32, device="cuda")), k
-
-  def __del__(self):
-    try:
-      if getattr(self, "h", None):
-        self.L.vp_pcmin_destroy(self.h)
-        self.h = None
-    except Exception:
-      pass

@@ -5,8 +5,7 @@ summaries of up to three images each, under the tags tf.summary.image gives them
 sources are the step's own device tensors; the encodes (voicepuppet_amd/png.py) are enqueued on the step's stream, and the host copies
 only the PNG bytes.
 """
-import torch
-
+from .._handle import rows_to_host
 from ..png import PngEncoder
 from ..utils.tb_events import EventFileWriter
 
@@ -40,23 +39,10 @@ class TrainSummaries:
 
   def collect(self, pending):
     """One wait for the 5 k lengths, then one for the used part of the rows -> {tag: (height, width, 3, png bytes)}"""
-    lengths = torch.cat([n for _, _, n in pending])
-    host_n = torch.empty(lengths.shape, dtype=torch.int32).pin_memory()
-    host_n.copy_(lengths, non_blocking=True)
-    torch.cuda.current_stream().synchronize()
-    n = host_n.numpy().reshape(len(pending), self.k)
-    host = []
-    for j, (_, rows, _) in enumerate(pending):
-      used = int(n[j].max())
-      h = torch.empty(self.k, used, dtype=torch.uint8).pin_memory()
-      h.copy_(rows[:, :used], non_blocking=True)
-      host.append(h)
-    torch.cuda.current_stream().synchronize()
     images = {}
-    for j, (name, _, _) in enumerate(pending):
-      a = host[j].numpy()
+    for (name, _, _), (a, n) in zip(pending, rows_to_host([(rows, lengths) for _, rows, lengths in pending])):
       for i in range(self.k):
-        images[image_tag(name, i)] = (self.size, self.size, 3, a[i, :n[j, i]].tobytes())
+        images[image_tag(name, i)] = (self.size, self.size, 3, a[i, :n[i]].tobytes())
     return images
 
   def write(self, step, scalars, pending):

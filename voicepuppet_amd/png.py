@@ -10,21 +10,14 @@ import ctypes
 import torch
 
 from . import _lib
-
-
-def _ptr(t):
-  return ctypes.c_void_p(t.data_ptr())
-
-
-def _stream():
-  return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+from ._handle import Handle, ptr, rows_to_host, stream
 
 
 def png_desc(max_frames, height, width, channels=3, filter=-1):
   return _lib.PngDesc(ctypes.sizeof(_lib.PngDesc), int(max_frames), int(height), int(width), int(channels), int(filter))
 
 
-class PngEncoder:
+class PngEncoder(Handle):
   """encode(t [K, H, W, P] device, uint8 or float32, K <= max_frames; channels [channel_offset, channel_offset + channels) of the P
   per pixel) -> (bytes uint8 [K, cap] device, lengths int32 [K] device), enqueued on the current stream; files(...) -> K bytes objects,
   each a complete .png file."""
@@ -32,18 +25,10 @@ class PngEncoder:
   def __init__(self, max_frames, height, width, channels=3, filter=-1):
     if not torch.cuda.is_available():
       raise RuntimeError("PngEncoder needs an MI355X (no CPU fallback)")
-    self.L = _lib.lib()
-    self.desc = png_desc(max_frames, height, width, channels, filter)
-    ws = self.L.vp_png_workspace_bytes(ctypes.byref(self.desc))
-    if ws == 0:
-      raise ValueError("invalid PNG encoder descriptor: " + self.L.vp_last_error().decode())
+    self._open("png", png_desc(max_frames, height, width, channels, filter), (stream(),), invalid="invalid PNG encoder descriptor")
     self.max_frames, self.height, self.width, self.channels, self.filter = int(max_frames), int(height), int(width), int(channels), int(filter)
     self.capacity = int(self.L.vp_png_frame_capacity(ctypes.byref(self.desc)))
     self.rows_per_strip = int(self.L.vp_png_rows_per_strip(ctypes.byref(self.desc)))
-    self.workspace = torch.empty(ws, dtype=torch.uint8, device="cuda")
-    h = ctypes.c_void_p()
-    _lib.check(self.L.vp_png_create(ctypes.byref(self.desc), _ptr(self.workspace), ws, _stream(), ctypes.byref(h)), "vp_png_create")
-    self.h = h
     self._frames = 0
 
   def encode(self, t, channel_offset=0, frames=None):
@@ -58,23 +43,15 @@ class PngEncoder:
     out = torch.empty(K, self.capacity, dtype=torch.uint8, device="cuda")
     lengths = torch.empty(K, dtype=torch.int32, device="cuda")
     dtype = _lib.PNG_U8 if t.dtype == torch.uint8 else _lib.PNG_F32
-    _lib.check(self.L.vp_png_encode(self.h, _ptr(t), dtype, int(t.shape[3]), int(channel_offset), K, _ptr(out), self.capacity, _ptr(lengths),
-                                    _stream()), "vp_png_encode")
+    _lib.check(self.L.vp_png_encode(self.h, ptr(t), dtype, int(t.shape[3]), int(channel_offset), K, ptr(out), self.capacity, ptr(lengths),
+                                    stream()), "vp_png_encode")
     self._frames = K
     return out, lengths
 
   def to_host(self, rows, lengths):
-    """One pinned copy of the lengths (the wait), then one of the used prefix of the rows -> list of bytes."""
-    K = int(lengths.shape[0])
-    pinned = torch.empty(K, dtype=torch.int32).pin_memory()
-    pinned.copy_(lengths, non_blocking=True)
-    torch.cuda.current_stream().synchronize()
-    n = pinned.numpy().copy()
-    host = torch.empty(K, int(n.max()), dtype=torch.uint8).pin_memory()
-    host.copy_(rows[:K, :int(n.max())], non_blocking=True)
-    torch.cuda.current_stream().synchronize()
-    host = host.numpy()
-    return [host[i, :n[i]].tobytes() for i in range(K)]
+    """One pinned copy of the lengths (the wait), then one of the used prefix of the rows (rows_to_host) -> list of bytes."""
+    (host, n), = rows_to_host([(rows, lengths)])
+    return [host[i, :n[i]].tobytes() for i in range(len(n))]
 
   def files(self, t, channel_offset=0, frames=None):
     return self.to_host(*self.encode(t, channel_offset, frames))
@@ -88,18 +65,5 @@ class PngEncoder:
 
   def last_strips(self):
     """int32 [K, strips, 2] on the host: per strip of the last encode its IDAT chunk's bytes and 1 when it was stored (tests)."""
-    p = ctypes.c_void_p()
-    shp = (ctypes.c_int64 * 4)()
-    _lib.check(self.L.vp_png_tensor(self.h, b"strips", ctypes.byref(p), shp), "vp_png_tensor")
-    n = 4 * int(shp[0]) * int(shp[1]) * int(shp[2])
-    off = p.value - self.workspace.data_ptr()
-    m = self.workspace[off:off + n].view(torch.int32).view(int(shp[0]), int(shp[1]), 4)
+    m = self._tensor("strips", torch.int32, 3)            # [max_frames, strips, 4]
     return m[:self._frames, :, [0, 3]].cpu().numpy()
-
-  def __del__(self):
-    try:
-      if getattr(self, "h", None):
-        self.L.vp_png_destroy(self.h)
-        self.h = None
-    except Exception:
-      pass

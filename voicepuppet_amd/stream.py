@@ -16,18 +16,11 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._handle import Handle, ptr, slot_arrays, stream
 from ._lib import BfmStreamDesc, BfmStreamGroupDesc
-from .audio import bfmnet_manifest
+from .audio import bfmnet_manifest, write_params
 
 SAMPLES_PER_FRAME = 640          # 16 kHz / 25 frames per second (config/params.yml)
-
-
-def _ptr(t):
-  return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
-
-
-def _stream():
-  return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def stream_desc(max_chunk_frames=1, dtype="f32", num_mel_bins=80, sample_rate=16000, lower_hz=80.0, upper_hz=7600.0):
@@ -51,22 +44,11 @@ def load_bfmnet_params(path):
   return tf_checkpoint.read_checkpoint(path)
 
 
-def _write_params(arena, manifest, params):
-  """The named arrays of `params` into their places of the device parameter arena (names it does not hold are left as they are)."""
-  host = arena.cpu().numpy()
-  for name, off, shape in manifest:
-    if name in params:
-      v = np.asarray(params[name], dtype=np.float32)
-      assert v.shape == shape, (name, v.shape, shape)
-      host[off:off + v.size] = v.reshape(-1)
-  arena.copy_(torch.from_numpy(host))
-
-
 def _lookahead_ms(right_mel, sample_rate):
   return 1000.0 * (right_mel * 128 + (512 - 128)) / sample_rate
 
 
-class AudioStream:
+class AudioStream(Handle):
   """One streaming session of BFMNet inference.
 
   push(pcm) / finish() return [k, 64] f32 device tensors, k = ready(len(pcm)) / ready_finish(); finish zero-pads the clip the way
@@ -76,19 +58,11 @@ class AudioStream:
   def __init__(self, params=None, max_chunk_frames=1, dtype="f32", num_mel_bins=80, sample_rate=16000, lower_hz=80.0, upper_hz=7600.0):
     if not torch.cuda.is_available():
       raise RuntimeError("AudioStream needs an MI355X (no CPU fallback)")
-    self.L = _lib.lib()
-    self.desc = stream_desc(max_chunk_frames, dtype, num_mel_bins, sample_rate, lower_hz, upper_hz)
-    d = ctypes.byref(self.desc)
-    ws = self.L.vp_bfmstream_workspace_bytes(d)
-    if ws == 0:
-      raise ValueError("invalid stream descriptor")
+    ws = self._query("bfmstream", stream_desc(max_chunk_frames, dtype, num_mel_bins, sample_rate, lower_hz, upper_hz), "invalid stream descriptor")
     self.left_mel, self.right_mel, self.left_frames, self.right_frames, self.window_frames = stream_context(self.desc)
     self.manifest = bfmnet_manifest()
     self.params = torch.zeros(self.L.vp_bfmnet_param_count(), dtype=torch.float32, device="cuda")
-    self.workspace = torch.zeros(ws, dtype=torch.uint8, device="cuda")
-    h = ctypes.c_void_p()
-    _lib.check(self.L.vp_bfmstream_create(d, _ptr(self.workspace), ws, _ptr(self.params), _stream(), ctypes.byref(h)), "vp_bfmstream_create")
-    self.h = h
+    self._create(ws, (ptr(self.params), stream()), zero=True)
     self.samples = 0
     if params is not None:
       self.load_params(load_bfmnet_params(params) if isinstance(params, str) else params)
@@ -100,7 +74,7 @@ class AudioStream:
     return _lookahead_ms(self.right_mel, self.desc.sample_rate)
 
   def load_params(self, params):
-    _write_params(self.params, self.manifest, params)
+    write_params(self.params, self.manifest, params)
     _lib.check(self.L.vp_bfmstream_params_changed(self.h), "vp_bfmstream_params_changed")
 
   def ready(self, n_samples):
@@ -135,7 +109,7 @@ class AudioStream:
     k = self.ready(n)
     out = torch.empty(k, 64, dtype=torch.float32, device="cuda")
     e = self._ears(k, ears) if k else None
-    _lib.check(self.L.vp_bfmstream_push(self.h, _ptr(pcm), n, _ptr(e), _ptr(out if k else None), _stream()), "vp_bfmstream_push")
+    _lib.check(self.L.vp_bfmstream_push(self.h, ptr(pcm), n, ptr(e), ptr(out if k else None), stream()), "vp_bfmstream_push")
     self.samples += n
     return out
 
@@ -143,29 +117,16 @@ class AudioStream:
     k = self.ready_finish()
     out = torch.empty(k, 64, dtype=torch.float32, device="cuda")
     e = self._ears(k, ears)
-    _lib.check(self.L.vp_bfmstream_finish(self.h, _ptr(e), _ptr(out), _stream()), "vp_bfmstream_finish")
+    _lib.check(self.L.vp_bfmstream_finish(self.h, ptr(e), ptr(out), stream()), "vp_bfmstream_finish")
     return out
 
   def reset(self):
-    _lib.check(self.L.vp_bfmstream_reset(self.h, _stream()), "vp_bfmstream_reset")
+    _lib.check(self.L.vp_bfmstream_reset(self.h, stream()), "vp_bfmstream_reset")
     self.samples = 0
 
   def mel_history(self):
     """The device mel history: [rows, num_mel_bins]; mel frame r of the clip sits at row r % rows while it is kept."""
-    p = ctypes.c_void_p()
-    shp = (ctypes.c_int64 * 4)()
-    _lib.check(self.L.vp_bfmstream_tensor(self.h, b"mel", ctypes.byref(p), shp), "vp_bfmstream_tensor")
-    rows, nmel = int(shp[0]), int(shp[1])
-    off = p.value - self.workspace.data_ptr()
-    return self.workspace[off:off + 4 * rows * nmel].view(torch.float32).view(rows, nmel)
-
-  def __del__(self):
-    try:
-      if getattr(self, "h", None):
-        self.L.vp_bfmstream_destroy(self.h)
-        self.h = None
-    except Exception:
-      pass
+    return self._tensor("mel", torch.float32, 2)
 
 
 def group_desc(slots, max_chunk_frames=1, dtype="f32", num_mel_bins=80, sample_rate=16000, lower_hz=80.0, upper_hz=7600.0):
@@ -173,7 +134,7 @@ def group_desc(slots, max_chunk_frames=1, dtype="f32", num_mel_bins=80, sample_r
                             {"f32": _lib.VP_F32, "bf16": _lib.VP_BF16}[dtype], sample_rate, lower_hz, upper_hz)
 
 
-class AudioStreamGroup:
+class AudioStreamGroup(Handle):
   """`slots` independent AudioStream sessions behind one handle (libvp_hip.so: vp_bfmstream_group_*), for serving many talkers at once.
 
   One push advances any subset of the slots by any number of samples each and runs one kernel chain per round for all of them.  Every
@@ -183,22 +144,14 @@ class AudioStreamGroup:
   def __init__(self, params=None, slots=1, max_chunk_frames=1, dtype="f32", num_mel_bins=80, sample_rate=16000, lower_hz=80.0, upper_hz=7600.0):
     if not torch.cuda.is_available():
       raise RuntimeError("AudioStreamGroup needs an MI355X (no CPU fallback)")
-    self.L = _lib.lib()
     self.slots = int(slots)
-    self.desc = group_desc(self.slots, max_chunk_frames, dtype, num_mel_bins, sample_rate, lower_hz, upper_hz)
-    d = ctypes.byref(self.desc)
-    ws = self.L.vp_bfmstream_group_workspace_bytes(d)
-    if ws == 0:
-      raise ValueError("invalid stream group descriptor: " + self.L.vp_last_error().decode())
+    ws = self._query("bfmstream_group", group_desc(self.slots, max_chunk_frames, dtype, num_mel_bins, sample_rate, lower_hz, upper_hz),
+                     "invalid stream group descriptor")
     self.left_mel, self.right_mel, self.left_frames, self.right_frames, self.window_frames = stream_context(
         stream_desc(max_chunk_frames, dtype, num_mel_bins, sample_rate, lower_hz, upper_hz))
     self.manifest = bfmnet_manifest()
     self.params = torch.zeros(self.L.vp_bfmnet_param_count(), dtype=torch.float32, device="cuda")
-    self.workspace = torch.zeros(ws, dtype=torch.uint8, device="cuda")
-    h = ctypes.c_void_p()
-    _lib.check(self.L.vp_bfmstream_group_create(d, _ptr(self.workspace), ws, _ptr(self.params), _stream(), ctypes.byref(h)),
-               "vp_bfmstream_group_create")
-    self.h = h
+    self._create(ws, (ptr(self.params), stream()), zero=True)
     self.keep_pcm = False           # a PuppetStreamGroup that writes AVI: last_pcm is the packed device samples of the last push (or None)
     self.last_pcm = None
     if params is not None:
@@ -210,23 +163,13 @@ class AudioStreamGroup:
     return _lookahead_ms(self.right_mel, self.desc.sample_rate)
 
   def load_params(self, params):
-    _write_params(self.params, self.manifest, params)
+    write_params(self.params, self.manifest, params)
     _lib.check(self.L.vp_bfmstream_group_params_changed(self.h), "vp_bfmstream_group_params_changed")
-
-  def _arrays(self, n_by_slot, finish_by_slot):
-    n = (ctypes.c_longlong * self.slots)()
-    fin = (ctypes.c_int * self.slots)()
-    items = n_by_slot.items() if isinstance(n_by_slot, dict) else enumerate(n_by_slot or ())
-    for s, v in items:
-      n[int(s)] = int(v)
-    for s in finish_by_slot or ():
-      fin[int(s)] = 1
-    return n, fin
 
   def ready(self, n_by_slot, finish_by_slot=()):
     """Frames per slot (a list of `slots` counts) that a push of n_by_slot ({slot: samples} or a sequence) new samples emits, the slots
     in finish_by_slot ending their clips after them.  Host only."""
-    n, fin = self._arrays(n_by_slot, finish_by_slot)
+    n, fin = slot_arrays(self.slots, n_by_slot, finish_by_slot)
     k = (ctypes.c_int * self.slots)()
     if self.L.vp_bfmstream_group_ready(self.h, n, fin, k) < 0:
       raise ValueError("bad ready query (negative count, or samples / finish for a finished slot)")
@@ -295,31 +238,18 @@ class AudioStreamGroup:
       else:
         e = np.concatenate([np.asarray(ears[s], dtype=np.float32).reshape(k[s], 1) for s in range(self.slots) if k[s]])
       e = AudioStream._to_device(e)
-    n, fin = self._arrays(sizes, finish)
-    _lib.check(self.L.vp_bfmstream_group_push(self.h, _ptr(pcm), n, fin, _ptr(e), _ptr(out if K else None), _stream()),
+    n, fin = slot_arrays(self.slots, sizes, finish)
+    _lib.check(self.L.vp_bfmstream_group_push(self.h, ptr(pcm), n, fin, ptr(e), ptr(out if K else None), stream()),
                "vp_bfmstream_group_push")
     return out, k, sizes
 
   def reset_slot(self, slot):
     """Slot `slot` starts a new clip; the other slots are untouched."""
-    _lib.check(self.L.vp_bfmstream_group_reset_slot(self.h, int(slot), _stream()), "vp_bfmstream_group_reset_slot")
+    _lib.check(self.L.vp_bfmstream_group_reset_slot(self.h, int(slot), stream()), "vp_bfmstream_group_reset_slot")
 
   def mel_history(self):
     """The device mel rings: [slots, rows, num_mel_bins]."""
-    p = ctypes.c_void_p()
-    shp = (ctypes.c_int64 * 4)()
-    _lib.check(self.L.vp_bfmstream_group_tensor(self.h, b"mel", ctypes.byref(p), shp), "vp_bfmstream_group_tensor")
-    S, rows, nmel = int(shp[0]), int(shp[1]), int(shp[2])
-    off = p.value - self.workspace.data_ptr()
-    return self.workspace[off:off + 4 * S * rows * nmel].view(torch.float32).view(S, rows, nmel)
-
-  def __del__(self):
-    try:
-      if getattr(self, "h", None):
-        self.L.vp_bfmstream_group_destroy(self.h)
-        self.h = None
-    except Exception:
-      pass
+    return self._tensor("mel", torch.float32, 3)
 
 
 class HeadSway:
@@ -434,7 +364,7 @@ def background_bank(img_size):
   return _BANKS[key]
 
 
-class PuppetStreamGroup:
+class PuppetStreamGroup(Handle):
   """Streaming infer_bfmvid for `slots` talkers behind one handle: one AudioStreamGroup, one generator plan (infer_bfmvid's cache, batch
   frame_batch, per-sample batch norm), one ClipRenderer; per slot a photo, its coefficients, a head-sway state and a frame counter.
 
@@ -465,12 +395,9 @@ class PuppetStreamGroup:
     from .pixrefer import infer_bfmvid as ib
     if not torch.cuda.is_available():
       raise RuntimeError("PuppetStreamGroup needs an MI355X (no CPU fallback)")
-    self.ib, self.L = ib, _lib.lib()
+    self.ib = ib
     self.slots, self.nb, self.img_size = int(slots), int(frame_batch), int(img_size)
-    self.desc = puppet_desc(self.slots, self.nb, self.img_size)
-    ws = self.L.vp_puppet_workspace_bytes(ctypes.byref(self.desc))
-    if ws == 0:
-      raise ValueError("invalid puppet group descriptor: " + self.L.vp_last_error().decode())
+    ws = self._query("puppet", puppet_desc(self.slots, self.nb, self.img_size), "invalid puppet group descriptor")
     bfm_file = next((f for f in (ib.BFMNET_CKPT + '.index', ib.BFMNET_CKPT + '.npz') if os.path.exists(f)), None)
     if bfm_file is None:
       from .bfmnet.bfmnet import random_variables
@@ -482,12 +409,9 @@ class PuppetStreamGroup:
     self.net = ib.load_generator(config_path, self.nb, self.img_size)[0]
     self.engine = self.net.engine
     self.renderer = ib.clip_renderer() if os.path.exists(os.path.join('BFM', 'BFM_model_front.mat')) else None
-    self.workspace = torch.empty(ws, dtype=torch.uint8, device="cuda")
-    h = ctypes.c_void_p()
-    _lib.check(self.L.vp_puppet_create(ctypes.byref(self.desc), _ptr(self.workspace), ws, _stream(), ctypes.byref(h)), "vp_puppet_create")
-    self.h = h
+    self._create(ws, (stream(),))
     self.bank, self.bg_row = background_bank(self.img_size)
-    _lib.check(self.L.vp_puppet_set_backgrounds(self.h, _ptr(self.bank), 0 if self.bank is None else int(self.bank.shape[0])),
+    _lib.check(self.L.vp_puppet_set_backgrounds(self.h, ptr(self.bank), 0 if self.bank is None else int(self.bank.shape[0])),
                "vp_puppet_set_backgrounds")
     nb, H = self.nb, self.img_size
     self.inputs = torch.empty([nb, H, H, 6], dtype=torch.float32, device="cuda")
@@ -540,8 +464,8 @@ class PuppetStreamGroup:
       side, y0, x0 = ib.paste_geometry(int(p['center_x']), int(p['center_y']), float(p['ratio']), p['transform_params'], self.desc.face_size)
     else:
       ib.logger.warning('BFM assets unavailable: conditioning every frame on the reference 3-D face panel')
-    _lib.check(self.L.vp_puppet_attach(self.h, slot, _ptr(refer_t), _ptr(fg_t), coeff.ctypes.data_as(ctypes.c_void_p) if coeff is not None else None,
-                                       int(side), int(y0), int(x0), _stream()), "vp_puppet_attach")
+    _lib.check(self.L.vp_puppet_attach(self.h, slot, ptr(refer_t), ptr(fg_t), coeff.ctypes.data_as(ctypes.c_void_p) if coeff is not None else None,
+                                       int(side), int(y0), int(x0), stream()), "vp_puppet_attach")
     self.has_coeff[slot] = coeff is not None
     self.attached[slot] = True
     if self.ingest is not None:
@@ -618,7 +542,7 @@ class PuppetStreamGroup:
       rot = Compute_rotation_matrix(angles[render[:, 1]])
       rot_d, render_d, tex_src_d, tex_row_d, cond_d = self._upload([rot, render, tex_src, tex_row, cond])
       spliced = torch.empty(R, 257, dtype=torch.float32, device="cuda")
-      _lib.check(L.vp_puppet_splice(self.h, _ptr(coeff), K, _ptr(render_d), R, _ptr(spliced), _stream()), "vp_puppet_splice")
+      _lib.check(L.vp_puppet_splice(self.h, ptr(coeff), K, ptr(render_d), R, ptr(spliced), stream()), "vp_puppet_splice")
       faces, _ = self.renderer.render_rows(spliced, rot_d, tex_src_d, int(tex_src.shape[0]), tex_row_d)
     else:
       cond_d, = self._upload([cond])
@@ -627,10 +551,10 @@ class PuppetStreamGroup:
     kept = [] if self.keep_conditioning else None
     eng = self.engine
     for i0 in range(0, Kp, nb):
-      _lib.check(L.vp_puppet_condition(self.h, _ptr(faces), R, _ptr(cond_d[i0:i0 + nb]), nb, _ptr(self.inputs), _ptr(self.fg_inputs),
-                                       _ptr(self.targets), _stream()), "vp_puppet_condition")
+      _lib.check(L.vp_puppet_condition(self.h, ptr(faces), R, ptr(cond_d[i0:i0 + nb]), nb, ptr(self.inputs), ptr(self.fg_inputs),
+                                       ptr(self.targets), stream()), "vp_puppet_condition")
       eng.forward(self.inputs, self.fg_inputs, self.targets)
-      _lib.check(L.vp_pixrefer_fetch(eng.h, eng.FETCH["Outputs_u8"], _ptr(out[i0:i0 + nb]), _stream()), "vp_pixrefer_fetch(Outputs_u8)")
+      _lib.check(L.vp_pixrefer_fetch(eng.h, eng.FETCH["Outputs_u8"], ptr(out[i0:i0 + nb]), stream()), "vp_pixrefer_fetch(Outputs_u8)")
       if kept is not None:
         n = min(nb, K - i0)
         kept.append([t[:n].clone() for t in (self.inputs, self.fg_inputs, self.targets, eng.fetch("Outputs"))])
@@ -716,11 +640,9 @@ class PuppetStreamGroup:
     try:
       for s in list(getattr(self, "_writers", {})):
         self.stop(s)
-      if getattr(self, "h", None):
-        self.L.vp_puppet_destroy(self.h)
-        self.h = None
     except Exception:
       pass
+    Handle.__del__(self)
 
 
 class PuppetStream:

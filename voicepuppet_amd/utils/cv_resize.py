@@ -1,10 +1,9 @@
 """cv2.resize(uint8 image, dsize) [INTER_LINEAR] + paste on the device (csrc/resize.hip): the last step of the reference's
 render_face (voicepuppet/pixrefer/infer_bfmvid.py:110-121), byte for byte OpenCV's fixed-point bilinear."""
-import ctypes
-
 import torch
 
 from .. import _lib
+from .._handle import ptr, stream
 
 
 def resize_paste_u8(src, dst_h, dst_w, canvas_shape, y0, x0, swap_rb=False, canvas=None):
@@ -19,8 +18,6 @@ def resize_paste_u8(src, dst_h, dst_w, canvas_shape, y0, x0, swap_rb=False, canv
   if canvas is None:
     canvas = torch.zeros((T, H, W, 3), dtype=torch.uint8, device=src.device)
   ws = torch.empty(int(L.vp_resize_paste_workspace_bytes(int(dst_h), int(dst_w))), dtype=torch.uint8, device=src.device)
-  st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-  _lib.check(L.vp_resize_paste_u8(ctypes.c_void_p(src.data_ptr()), T, h, w, int(dst_h), int(dst_w), 1 if swap_rb else 0,
-                                  ctypes.c_void_p(canvas.data_ptr()), H, W, int(y0), int(x0), ctypes.c_void_p(ws.data_ptr()), st),
-             "vp_resize_paste_u8")
+  _lib.check(L.vp_resize_paste_u8(ptr(src), T, h, w, int(dst_h), int(dst_w), 1 if swap_rb else 0, ptr(canvas), H, W, int(y0), int(x0), ptr(ws),
+                                  stream()), "vp_resize_paste_u8")
   return canvas

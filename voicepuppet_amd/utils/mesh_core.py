@@ -6,20 +6,11 @@ z-buffer rasteriser that turns BFMNet's reconstructed mesh into PixReferNet's co
 through HBM (the reference's calling convention); CUDA tensors are rasterised where they lie.  `render_colors` is the
 batched form for a clip: F frames sharing one triangle list in ONE launch.  No CPU fallback.
 """
-import ctypes
-
 import numpy as np
 import torch
 
 from .. import _lib
-
-
-def _ptr(t):
-  return ctypes.c_void_p(t.data_ptr())
-
-
-def _stream():
-  return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+from .._handle import grow, ptr, stream
 
 
 _workspaces = {}
@@ -27,10 +18,7 @@ _workspaces = {}
 
 def _workspace(nbytes, device):
   key = (device.index if device.index is not None else torch.cuda.current_device())
-  ws = _workspaces.get(key)
-  if ws is None or ws.numel() < nbytes:
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
-    _workspaces[key] = ws
+  ws = _workspaces[key] = grow(_workspaces.get(key), nbytes, device)
   return ws
 
 
@@ -52,8 +40,8 @@ def render_colors(image, face_mask, vertices, triangles, colors, depth_buffer):
   L = _lib.lib()
   nbytes = L.vp_render_colors_workspace_bytes(F, h, w)
   ws = _workspace(nbytes, image.device)
-  _lib.check(L.vp_render_colors(_ptr(image), _ptr(face_mask), _ptr(vertices), _ptr(triangles), _ptr(colors), _ptr(depth_buffer),
-                                ntri, nver, h, w, c, F, _ptr(ws), _stream()), "vp_render_colors")
+  _lib.check(L.vp_render_colors(ptr(image), ptr(face_mask), ptr(vertices), ptr(triangles), ptr(colors), ptr(depth_buffer),
+                                ntri, nver, h, w, c, F, ptr(ws), stream()), "vp_render_colors")
   return image, face_mask, depth_buffer
 
 

@@ -13,15 +13,8 @@ import numpy as np
 import torch
 
 from .. import _lib
+from .._handle import grow, ptr, stream
 from . import mesh_core
-
-
-def _ptr(t):
-  return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
-
-
-def _stream():
-  return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def Split_coeff(coeff):
@@ -85,8 +78,7 @@ class DeviceFaceModel:
 
   def workspace(self, frames):
     n = _lib.lib().vp_bfm_reconstruct_workspace_bytes(self.nver, self.ntri, frames)
-    if self._ws is None or self._ws.numel() < n:
-      self._ws = torch.empty(n, dtype=torch.uint8, device=self.device)
+    self._ws = grow(self._ws, n, self.device)
     return self._ws
 
 
@@ -108,9 +100,9 @@ def reconstruct_clip(coeff, model, angles, shared_texture=False, full=True):
       out[k] = torch.empty(*shp, dtype=torch.float64, device=dev)
   ws = model.workspace(T)
   L = _lib.lib()
-  _lib.check(L.vp_bfm_reconstruct(ctypes.byref(model.c), _ptr(coeff_d), _ptr(rot), T, 1 if shared_texture else 0, _ptr(out.get("face_shape")),
-                                  _ptr(out.get("face_texture")), _ptr(out.get("face_color")), _ptr(out.get("face_projection")),
-                                  _ptr(out.get("z_buffer")), _ptr(out["vertices"]), _ptr(out["colors"]), _ptr(ws), ws.numel(), _stream()),
+  _lib.check(L.vp_bfm_reconstruct(ctypes.byref(model.c), ptr(coeff_d), ptr(rot), T, 1 if shared_texture else 0, ptr(out.get("face_shape")),
+                                  ptr(out.get("face_texture")), ptr(out.get("face_color")), ptr(out.get("face_projection")),
+                                  ptr(out.get("z_buffer")), ptr(out["vertices"]), ptr(out["colors"]), ptr(ws), ws.numel(), stream()),
              "vp_bfm_reconstruct")
   if full:
     out["landmarks_2d"] = out["face_projection"][:, torch.from_numpy(model.keypoints).to(dev)]
@@ -137,10 +129,10 @@ def reconstruct_view(coeff, model, view=0, scale=1.0, shared_texture=False, full
                    ("face_projection", (T, N, 2)), ("z_buffer", (T, N, 1))):
       out[k] = torch.empty(*shp, dtype=torch.float64, device=dev)
   ws = model.workspace(T)
-  _lib.check(_lib.lib().vp_bfm_reconstruct_view(ctypes.byref(model.c), _ptr(coeff_d), _ptr(rot), T, 1 if shared_texture else 0, int(view), float(scale),
-                                                _ptr(out.get("face_shape")), _ptr(out.get("face_texture")), _ptr(out.get("face_color")),
-                                                _ptr(out.get("face_projection")), _ptr(out.get("z_buffer")), _ptr(out["vertices"]), _ptr(out["colors"]),
-                                                _ptr(ws), ws.numel(), _stream()), "vp_bfm_reconstruct_view")
+  _lib.check(_lib.lib().vp_bfm_reconstruct_view(ctypes.byref(model.c), ptr(coeff_d), ptr(rot), T, 1 if shared_texture else 0, int(view), float(scale),
+                                                ptr(out.get("face_shape")), ptr(out.get("face_texture")), ptr(out.get("face_color")),
+                                                ptr(out.get("face_projection")), ptr(out.get("z_buffer")), ptr(out["vertices"]), ptr(out["colors"]),
+                                                ptr(ws), ws.numel(), stream()), "vp_bfm_reconstruct_view")
   if full:
     out["landmarks_2d"] = out["face_projection"][:, torch.from_numpy(model.keypoints).to(dev)]
     out["translation"] = coeff_d[:, 254:]
@@ -160,8 +152,8 @@ def reconstruct_rows(coeff, rot, tex_src, textures, tex_row, model):
   vertices = torch.empty(R, N, 3, dtype=torch.float32, device=dev)
   colors = torch.empty(R, N, 3, dtype=torch.float32, device=dev)
   ws = model.workspace(R)
-  _lib.check(_lib.lib().vp_bfm_reconstruct_rows(ctypes.byref(model.c), _ptr(coeff), _ptr(rot), R, _ptr(tex_src), int(textures), _ptr(tex_row),
-                                                _ptr(vertices), _ptr(colors), _ptr(ws), ws.numel(), _stream()), "vp_bfm_reconstruct_rows")
+  _lib.check(_lib.lib().vp_bfm_reconstruct_rows(ctypes.byref(model.c), ptr(coeff), ptr(rot), R, ptr(tex_src), int(textures), ptr(tex_row),
+                                                ptr(vertices), ptr(colors), ptr(ws), ws.numel(), stream()), "vp_bfm_reconstruct_rows")
   return vertices, colors
 
 
