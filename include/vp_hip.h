@@ -28,6 +28,8 @@
  *   vp_avimux_*        replaces  infer_bfmvid.py:245 (ffmpeg over the .jpg files and the wav) with Motion-JPEG + PCM AVI segments built on the device
  *   vp_jpegdec_*       replaces  generator/generator.py:956-1019 (cv2.imread per sample) and loader.py ImageLoader with a baseline JPEG decode on the device
  *   vp_pcmin_*         replaces  generator/loader.py:39-54 (WavLoader: scale, channel mean, resample_poly over a whole file) for live PCM
+ *   vp_triptych_*      replaces  datasets/make_data_from_GRID.py:430-469 (step 5: binary_fill_holes, cv2.resize, erode, GaussianBlur, the paste and the
+ *                             three panels of a training triptych) and :690-695 (step 6's layout with an alpha matte)
  *   vp_frame_metrics_* replaces  nothing: the reference has no image-quality measure (L1, PSNR and SSIM per frame pair, on the device)
  *
  * Conventions: every function returns 0 on success and a negative vp_status otherwise (never throws);
@@ -1164,6 +1166,65 @@ int vp_avimux_segment(vp_avimux_t* h, const unsigned char* data, size_t row_byte
                       const float* pcm, const int* sample_offset, const int* sample_count, int samples, unsigned char* out, size_t out_capacity,
                       void* stream);
 void vp_avimux_destroy(vp_avimux_t* h);
+
+/* ------------------------------------------------------------------------------------------------
+ * PixReferNet training triptychs on the device: [frame | 3-D face on the frame | mask], the file generator/generator.py:924-1040 reads.
+ * Replaces the image part of step 5 of datasets/make_data_from_GRID.py (deep_video_portraits, :430-469) and, with an alpha matte, the
+ * layout of step 6 (:690-695), for all frames of a call.  csrc/triptych.hip.  Per frame, with face = face_size:
+ *   a  filled = scipy.ndimage.binary_fill_holes(face_mask > 0), default structuring element (:431-433): a zero pixel is filled unless a
+ *      4-connected path of zero pixels joins it to the image border.
+ *   b  cv2.resize(filled as 0/1 float32, (side, side)), INTER_LINEAR (:435-436): f = (d + 0.5) * (face / side) - 0.5 in double, s = floor(f),
+ *      fraction f - s; s < 0: s = 0, fraction 0; s >= face - 1: s = face - 1, fraction 0; the coefficients (1 - fraction, fraction) cast to
+ *      float32; the horizontal pass, then the vertical pass, each v0 * c0 + v1 * c1 in float32, every product and sum rounded on its own.
+ *   c  cv2.erode with np.ones((5, 5)) (:438-439): the minimum over the 5 x 5 window centred on the pixel, pixels outside the image left out.
+ *   d  u = (uint8)(m * 255), truncated, then cv2.GaussianBlur(u, (21, 21), cv2.BORDER_DEFAULT) (:441): the reference passes the constant 4
+ *      in the sigma position, so sigmaX = sigmaY = 4 and the border is the default REFLECT_101.  Defined here in integers: q[k] =
+ *      round(65536 * g[k]) with g the normalised exp(-(k - 10)^2 / 32) in double, the centre tap adjusted so that the taps sum to 65536
+ *      (vp_triptych_blur_taps); the horizontal sums in 32 bits, the vertical sums in 64, the result (v + 2^31) >> 32.  OpenCV's own
+ *      uint8 Gaussian has coarser fixed-point taps: about +-1 grey level from this one (equality with cv2 is not claimed for b-d).
+ *   e  paste at rows y0.., columns x0.. of a size x size canvas of zeros: the mask as float32(u) / 255 (:442, :457-458), and the render
+ *      behind cv2.cvtColor(BGR2RGB) and cv2.resize(uint8, (side, side)) (:444-446, :449-455) - the bytes of vp_resize_paste_u8 with swap_rb.
+ *   f  panels in float32, every operation rounded on its own, truncated to uint8 (:460-469): the frame; (frame * (1 - m) + face * m) *
+ *      (m > 0); m * 255 on the three channels.
+ *   g  with alpha: the frame; the pasted render on black; alpha on the three channels (:692-695).  Stages a-d are skipped.
+ * Geometry (side, y0, x0) is the caller's; the Python layer takes it from infer_bfmvid.paste_geometry, that is step 6's and inference's
+ * int() (infer_bfmvid.py:83-86), NOT step 5's int(round()) (:397-398): training sees the paste that inference produces.
+ * Status per frame: 0 built; 1 side < 11 (REFLECT_101 of 21 taps); 2 side > max_side; 3 the paste rectangle is not wholly inside the canvas
+ * (the reference's numpy assignment raises there).  A frame with a nonzero status leaves its triptych bytes untouched; nothing is read or
+ * written out of bounds for any table contents.
+ * ---------------------------------------------------------------------------------------------- */
+#define VP_TRIPTYCH_MAX_FRAMES 4096
+#define VP_TRIPTYCH_MAX_SIZE 1024
+typedef struct vp_triptych_desc {
+  uint32_t struct_bytes;  /* sizeof(vp_triptych_desc) of the caller's build: must equal vp_triptych_desc_size() */
+  int32_t max_frames;     /* frames per call: 1 .. VP_TRIPTYCH_MAX_FRAMES */
+  int32_t size;           /* the square canvas S: 11 .. VP_TRIPTYCH_MAX_SIZE */
+  int32_t face_size;      /* the render and its mask: 2 .. 256 (224) */
+  int32_t max_side;       /* the largest side a frame may ask for: 11 .. size */
+} vp_triptych_desc;
+size_t vp_triptych_desc_size(void);
+typedef struct vp_triptych vp_triptych_t;
+/* 0 on a refused descriptor (vp_last_error says why) */
+size_t vp_triptych_workspace_bytes(const vp_triptych_desc* d);
+/* Builds the resize tables of every side 1 .. max_side and uploads them; may wait, once per builder */
+int vp_triptych_create(const vp_triptych_desc* d, void* workspace, size_t workspace_bytes, void* stream, vp_triptych_t** out);
+/* All DEVICE pointers, n = 1 .. max_frames frames: frames uint8 [n,size,size,3] RGB; render uint8 [n,face,face,3] in the rasteriser's channel
+ * order (vp_bfm_reconstruct_view); face_mask uint8 [n,face,face] (may be NULL with alpha); geometry int32 [n,3] = (side, y0, x0); alpha
+ * NULL or uint8 [n,size,size]; triptych uint8 [n,size,3*size,3]; status int32 [n].  Six launches on `stream` (one with alpha); never waits,
+ * never allocates.  Replaces make_data_from_GRID.py:430-469 per frame (:692-695 with alpha). */
+int vp_triptych_build(vp_triptych_t* h, const unsigned char* frames, const unsigned char* render, const unsigned char* face_mask, const int* geometry,
+                      const unsigned char* alpha, int n, unsigned char* triptych, int* status, void* stream);
+/* Stages a-d alone (fill != 0) or b-d on face_mask > 0 as it is (fill == 0), into the "mask" planes; frames with a nonzero status are skipped */
+int vp_triptych_mask(vp_triptych_t* h, const unsigned char* face_mask, const int* geometry, int n, int fill, void* stream);
+/* Stage a alone, no handle: masks uint8 [n,height,width] (DEVICE, height and width 1 .. 256) -> out uint8 [n,height,width] of 0 / 1.
+ * One workgroup per mask, rounds of row and column passes over two bitmaps in LDS until nothing changes (:431-433). */
+int vp_triptych_fill_holes(const unsigned char* masks, int n, int height, int width, unsigned char* out, void* stream);
+/* Host only: the 21 integer taps of stage d */
+int vp_triptych_blur_taps(int q[21]);
+/* "mask": uint8 [max_frames, max_side, max_side], the blurred mask u of the last build or vp_triptych_mask in its top-left side x side
+ * corner; "filled": uint8 [max_frames, face_size, face_size], stage a's 0 / 1 */
+int vp_triptych_tensor(vp_triptych_t* h, const char* name, void** ptr, int64_t shape[4]);
+void vp_triptych_destroy(vp_triptych_t* h);
 
 /* Host helper: CRC-32C (Castagnoli, the checksum of TensorFlow checkpoint bundles) of `n` bytes, continuing from `crc` (0 to start). */
 unsigned vp_crc32c(const void* data, size_t n, unsigned crc);

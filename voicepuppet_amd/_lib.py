@@ -105,6 +105,14 @@ class AviMuxDesc(ctypes.Structure):
 AVIMUX_MAX_FRAMES, AVIMUX_MAX_SLOTS = 4096, 128   # include/vp_hip.h VP_AVIMUX_MAX_FRAMES, VP_AVIMUX_MAX_SLOTS
 
 
+class TriptychDesc(ctypes.Structure):
+  _fields_ = [("struct_bytes", ctypes.c_uint32), ("max_frames", ctypes.c_int32), ("size", ctypes.c_int32), ("face_size", ctypes.c_int32),
+              ("max_side", ctypes.c_int32)]
+
+
+TRIPTYCH_MAX_FRAMES, TRIPTYCH_MAX_SIZE = 4096, 1024   # include/vp_hip.h VP_TRIPTYCH_MAX_FRAMES, VP_TRIPTYCH_MAX_SIZE
+
+
 class BfmModel(ctypes.Structure):
   _fields_ = [("nver", ctypes.c_int), ("ntri", ctypes.c_int), ("meanshape", ctypes.c_void_p), ("idBase", ctypes.c_void_p),
               ("exBase", ctypes.c_void_p), ("meantex", ctypes.c_void_p), ("texBase", ctypes.c_void_p), ("tri", ctypes.c_void_p),
@@ -274,6 +282,15 @@ _SIGNATURES = {
     "vp_avimux_create": (ctypes.c_int, [ctypes.POINTER(AviMuxDesc), _P, ctypes.c_size_t, ctypes.POINTER(_P)]),
     "vp_avimux_segment": (ctypes.c_int, [_P, _P, ctypes.c_size_t, _P, _P, ctypes.c_int, _P, _P, _P, ctypes.c_int, _P, ctypes.c_size_t, _P]),
     "vp_avimux_destroy": (None, [_P]),
+    "vp_triptych_desc_size": (ctypes.c_size_t, []),
+    "vp_triptych_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(TriptychDesc)]),
+    "vp_triptych_create": (ctypes.c_int, [ctypes.POINTER(TriptychDesc), _P, ctypes.c_size_t, _P, ctypes.POINTER(_P)]),
+    "vp_triptych_build": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, ctypes.c_int, _P, _P, _P]),
+    "vp_triptych_mask": (ctypes.c_int, [_P, _P, _P, ctypes.c_int, ctypes.c_int, _P]),
+    "vp_triptych_fill_holes": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P]),
+    "vp_triptych_blur_taps": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int)]),
+    "vp_triptych_tensor": (ctypes.c_int, [_P, ctypes.c_char_p, ctypes.POINTER(_P), ctypes.POINTER(ctypes.c_int64)]),
+    "vp_triptych_destroy": (None, [_P]),
     "vp_bfm_reconstruct_rows": (ctypes.c_int, [ctypes.POINTER(BfmModel), _P, _P, ctypes.c_int, _P, ctypes.c_int, _P, _P, _P, _P, ctypes.c_size_t, _P]),
     "vp_bfmstream_group_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(BfmStreamGroupDesc)]),
     "vp_bfmstream_group_plan_info": (ctypes.c_int, [ctypes.POINTER(BfmStreamGroupDesc), ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
@@ -361,6 +378,7 @@ DESC_SIZE_QUERIES = {
     "vp_pcmin_desc_size": PcmInDesc,
     "vp_frame_metrics_desc_size": FrameMetricsDesc,
     "vp_avimux_desc_size": AviMuxDesc,
+    "vp_triptych_desc_size": TriptychDesc,
 }
 
 _lib = None

@@ -13,59 +13,17 @@
 // (oracle/cv_resize_ref.py, tests/test_cv_resize.py), not by cv2 itself: "unpinned by cv2".
 // The coefficient tables are built on the host in the same C float / double arithmetic as OpenCV (this file is compiled with
 // -ffp-contract=off); the per-pixel work is integer and runs on the device, all frames of a clip in one launch.
+// The tables and the arithmetic of one output byte live in resize_core.h, which csrc/triptych.hip shares (one side per frame there).
 #include <math.h>
 #include <string.h>
 
 #include <vector>
 
 #include "errors.h"
+#include "resize_core.h"
 #include "vp_common.h"
 
 namespace vp {
-
-struct ResizeTab { int ofs; short a0, a1; };      // source index, the two 11-bit coefficients (a1 = 0 and ofs clipped beyond xmax)
-
-static void build_table(int ssize, int dsize, ResizeTab* tab) {
-  const double inv_scale = (double)dsize / ssize;
-  const double scale = 1.0 / inv_scale;
-  for (int d = 0; d < dsize; ++d) {
-    float f = (float)((d + 0.5) * scale - 0.5);
-    int s = (int)floorf(f);
-    f -= s;
-    bool single = false;                             // beyond xmax: only S[s] is read (weight 2048)
-    if (s < 0) { f = 0.f; s = 0; }
-    if (s + 1 >= ssize) {
-      single = true;
-      if (s >= ssize - 1) { f = 0.f; s = ssize - 1; }
-    }
-    const float c0 = 1.f - f, c1 = f;
-    long a0 = lrintf(c0 * 2048.f), a1 = lrintf(c1 * 2048.f);
-    a0 = a0 < -32768 ? -32768 : (a0 > 32767 ? 32767 : a0);
-    a1 = a1 < -32768 ? -32768 : (a1 > 32767 ? 32767 : a1);
-    tab[d].ofs = s;
-    tab[d].a0 = single ? (short)2048 : (short)a0;
-    tab[d].a1 = single ? (short)0 : (short)a1;
-  }
-}
-
-// rows: OpenCV keeps the (possibly negative) floor and clips the two source ROWS instead of the coefficient
-static void build_row_table(int ssize, int dsize, ResizeTab* tab, int* row1) {
-  const double inv_scale = (double)dsize / ssize;
-  const double scale = 1.0 / inv_scale;
-  for (int d = 0; d < dsize; ++d) {
-    float f = (float)((d + 0.5) * scale - 0.5);
-    const int s = (int)floorf(f);
-    f -= s;
-    const float c0 = 1.f - f, c1 = f;
-    long b0 = lrintf(c0 * 2048.f), b1 = lrintf(c1 * 2048.f);
-    b0 = b0 < -32768 ? -32768 : (b0 > 32767 ? 32767 : b0);
-    b1 = b1 < -32768 ? -32768 : (b1 > 32767 ? 32767 : b1);
-    const int r0 = s < 0 ? 0 : (s > ssize - 1 ? ssize - 1 : s);
-    const int r1 = s + 1 < 0 ? 0 : (s + 1 > ssize - 1 ? ssize - 1 : s + 1);
-    tab[d].ofs = r0; tab[d].a0 = (short)b0; tab[d].a1 = (short)b1;
-    row1[d] = r1;
-  }
-}
 
 struct ResizeArgs {
   const unsigned char* src;   // [T][hs][ws][3]
@@ -89,22 +47,7 @@ __global__ __launch_bounds__(256) void resize_paste_kernel(const ResizeArgs a) {
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       const int sc = a.swap_rb ? 2 - c : c;
-      int v;
-      if (a.mode == 1) {
-        v = s[((size_t)dy * a.ws + dx) * 3 + sc];
-      } else if (a.mode == 2) {
-        const unsigned char* p = s + ((size_t)(2 * dy) * a.ws + 2 * dx) * 3 + sc;
-        v = (p[0] + p[3] + p[(size_t)a.ws * 3] + p[(size_t)a.ws * 3 + 3] + 2) >> 2;
-      } else {
-        const ResizeTab xt = a.xt[dx], yt = a.yt[dy];
-        const int r1 = a.yrow1[dy];
-        const int x1 = xt.a1 ? xt.ofs + 1 : xt.ofs;            // (a1 == 0: the second tap is never read by OpenCV either)
-        const unsigned char* p0 = s + (size_t)yt.ofs * a.ws * 3;
-        const unsigned char* p1 = s + (size_t)r1 * a.ws * 3;
-        const int d0 = p0[xt.ofs * 3 + sc] * xt.a0 + p0[x1 * 3 + sc] * xt.a1;
-        const int d1 = p1[xt.ofs * 3 + sc] * xt.a0 + p1[x1 * 3 + sc] * xt.a1;
-        v = ((((int)yt.a0 * (d0 >> 4)) >> 16) + (((int)yt.a1 * (d1 >> 4)) >> 16) + 2) >> 2;
-      }
+      const int v = resize_px(s, a.ws, a.mode, a.xt, a.yt, a.yrow1, dy, dx, sc);
       o[c] = (unsigned char)v;
     }
   }
@@ -135,7 +78,7 @@ int vp_resize_paste_u8(const unsigned char* src, int frames, int src_h, int src_
   memset(&a, 0, sizeof(a));
   a.src = src; a.dst = canvas; a.T = frames; a.hs = src_h; a.ws = src_w; a.dh = dst_h; a.dw = dst_w;
   a.H = canvas_h; a.W = canvas_w; a.y0 = y0; a.x0 = x0; a.swap_rb = swap_rb ? 1 : 0;
-  a.mode = (dst_h == src_h && dst_w == src_w) ? 1 : ((src_h == 2 * dst_h && src_w == 2 * dst_w) ? 2 : 0);
+  a.mode = resize_mode(src_h, src_w, dst_h, dst_w);
   if (a.mode == 0) {
     std::vector<ResizeTab> tab((size_t)dst_w + dst_h);
     std::vector<int> r1((size_t)dst_h);

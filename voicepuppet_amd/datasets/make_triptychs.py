@@ -1,0 +1,247 @@
+#!/usr/bin/env python
+# -*- encoding: utf-8 -*-
+"""A PixReferNet training folder from a clip's frames and a 68-landmark file, on the MI355X:
+
+    python voicepuppet/datasets/make_triptychs.py --clip_dir frames/ --landmarks frames/_landmark.txt --out_dir data/clip0 --list train.txt
+
+In place of steps 5 and 6 of the reference's datasets/make_data_from_GRID.py (deep_video_portraits, :408-471; the layout of
+deep_video_portraits_v2, :690-695), which need TensorFlow 1, MXNet, OpenCV and FaceReconModel.pb.
+
+--clip_dir DIR     0.jpg, 1.jpg, ... (read with JpegDecoder; a file outside its subset is read with PIL)
+--landmarks FILE   one frame per line, 136 comma-separated values x0,y0,...,x67,y67 in pixels of those frames (the _landmark.txt of the
+                   reference's step 3; any landmark model with the 68-point layout)
+--out_dir DIR      gets <i>.jpg (S x 3S: frame | 3-D face on the frame | mask), bfmcoeff.txt (one row of 257 per frame), ear.txt
+                   (ear_compute's formula, :96-102, on the landmark values as given)
+--size S           the triptych's panel size; the (cropped) frames are resized to S x S with the OpenCV-exact uint8 bilinear.  Default: the
+                   frames' own size, which must then be square
+--crop X0 Y0 SIDE  the square of the frame to keep, before the resize (the landmarks follow)
+--alpha_dir DIR    <i>.jpg or <i>.png mattes, S x S after the same crop and resize: step 6's layout (render on black | matte) instead of step 5's
+--bfmcoeff FILE    rows of 257 coefficients to use instead of fitting them (fit_landmarks.py --clip writes such a file)
+--appearance first|none   first (default): texture and lighting are fitted to frame 0's pixels and shared by the clip; none: zeros
+--frame_batch N    frames per device batch (default 32)
+--list FILE        gets the line "out_dir|count" appended: the list train_pixrefer.py reads
+
+The paste geometry is infer_bfmvid.paste_geometry for every frame, i.e. step 6's and inference's int(), not step 5's int(round()).  A frame
+that cannot be built (TriptychBuilder's status) repeats the frame before it, as step 6 does; a clip whose first frame cannot be built is
+refused.  Needs BFM/BFM_model_front.mat and BFM/similarity_Lm3D_all.mat, like fit_landmarks.py.  One line is printed: frames, statuses,
+repeated frames, and the reprojection error in pixels of the 224 image as fit_landmarks.py prints it."""
+import logging
+import math
+import os
+import sys
+from optparse import OptionParser
+
+import numpy as np
+
+sys.path.append(os.getcwd())
+
+logging.basicConfig(level=logging.INFO, format='%(asctime)s - %(name)s - %(levelname)s - %(message)s')
+logger = logging.getLogger(__name__)
+
+
+def ear_value(ps):
+  """ear_compute (make_data_from_GRID.py:96-102) for one line of 136 values: the mean of the two eyes' aspect ratios, landmarks 36..41 and
+  42..47 (0-based): (|p1 - p5| + |p2 - p4|) / |p0 - p3|."""
+  def dist(a, b):
+    return math.sqrt((ps[a] - ps[b]) ** 2 + (ps[a + 1] - ps[b + 1]) ** 2)
+  ear1 = (dist(74, 82) + dist(76, 80)) / dist(72, 78)
+  ear2 = (dist(86, 94) + dist(88, 92)) / dist(84, 90)
+  return (ear1 + ear2) / 2
+
+
+def count_frames(clip_dir):
+  n = 0
+  while os.path.exists(os.path.join(clip_dir, '%d.jpg' % n)):
+    n += 1
+  return n
+
+
+def _pil_rgb(path):
+  from PIL import Image
+  return np.array(Image.open(path).convert('RGB'), np.uint8)
+
+
+class FrameReader(object):
+  """<i>.jpg of a folder -> uint8 RGB device tensors [n, S, S, 3], cropped and resized.  All files have the size of the first."""
+
+  def __init__(self, clip_dir, batch, crop, size):
+    import torch
+    from PIL import Image
+    from voicepuppet_amd.jpeg_dec import JpegDecoder
+    self.torch, self.dir = torch, clip_dir
+    with Image.open(os.path.join(clip_dir, '0.jpg')) as im:
+      self.w, self.h = im.size
+    x0, y0, side = crop if crop is not None else (0, 0, self.h)
+    if crop is None and self.h != self.w:
+      raise ValueError('%s: the frames are %d x %d; --crop X0 Y0 SIDE must name a square' % (clip_dir, self.w, self.h))
+    if x0 < 0 or y0 < 0 or side < 1 or x0 + side > self.w or y0 + side > self.h:
+      raise ValueError('--crop %d %d %d does not lie inside the %d x %d frames' % (x0, y0, side, self.w, self.h))
+    self.crop = (int(x0), int(y0), int(side))
+    self.size = int(size) if size else int(side)
+    self.decoder = JpegDecoder(batch, self.h, self.w, bgr=False)
+    self.fallbacks = 0
+
+  def _decode(self, paths):
+    torch = self.torch
+    try:
+      out, status = self.decoder.decode(paths)
+      bad = np.flatnonzero(status.cpu().numpy() != 0).tolist()
+    except ValueError as e:                                       # a file outside the decoder's subset (progressive, 4:4:4, another size...)
+      logger.info('%s: read with PIL', e)
+      out, bad = torch.zeros(len(paths), self.h, self.w, 3, dtype=torch.uint8, device='cuda'), list(range(len(paths)))
+    for i in bad:
+      img = _pil_rgb(paths[i])
+      if img.shape != (self.h, self.w, 3):
+        raise ValueError('%s is %d x %d, the clip\'s first frame %d x %d' % (paths[i], img.shape[1], img.shape[0], self.w, self.h))
+      out[i] = torch.from_numpy(img).cuda()
+      self.fallbacks += 1
+    return out
+
+  def fit_to_panel(self, frames):
+    """[n, h, w, 3] device -> the crop, resized to S x S as cv2.resize(uint8) does."""
+    from voicepuppet_amd.utils.cv_resize import resize_paste_u8
+    x0, y0, side = self.crop
+    frames = frames[:, y0:y0 + side, x0:x0 + side].contiguous()
+    if side == self.size:
+      return frames
+    return resize_paste_u8(frames, self.size, self.size, (self.size, self.size), 0, 0)
+
+  def read(self, first, n):
+    return self.fit_to_panel(self._decode([os.path.join(self.dir, '%d.jpg' % i) for i in range(first, first + n)]))
+
+  def landmarks_to_panel(self, lms):
+    x0, y0, side = self.crop
+    return (np.asarray(lms, np.float64) - np.array([x0, y0], np.float64)) * (float(self.size) / side)
+
+
+def read_alpha(reader, alpha_dir, first, n):
+  """<i>.jpg / <i>.png mattes of the frames' size -> uint8 device [n, S, S] (PIL, grey), through the frames' crop and resize."""
+  import torch
+  planes = []
+  for i in range(first, first + n):
+    path = next((p for p in (os.path.join(alpha_dir, '%d.%s' % (i, e)) for e in ('png', 'jpg')) if os.path.exists(p)), None)
+    if path is None:
+      raise ValueError('%s: no %d.png or %d.jpg' % (alpha_dir, i, i))
+    from PIL import Image
+    a = np.array(Image.open(path).convert('L'), np.uint8)
+    if a.shape != (reader.h, reader.w):
+      raise ValueError('%s is %d x %d, the frames %d x %d' % (path, a.shape[1], a.shape[0], reader.w, reader.h))
+    planes.append(a)
+  a = torch.from_numpy(np.stack(planes)).cuda()
+  return reader.fit_to_panel(a[..., None].expand(-1, -1, -1, 3))[..., 0].contiguous()
+
+
+def parse_options(argv=None):
+  p = OptionParser(usage='usage: %prog --clip_dir DIR --landmarks FILE --out_dir DIR [--size S] [--crop X0 Y0 SIDE] [--alpha_dir DIR] '
+                         '[--bfmcoeff FILE] [--appearance first|none] [--frame_batch N] [--list FILE]')
+  p.add_option('--clip_dir', type='string', dest='clip_dir', default=None, help='folder of 0.jpg, 1.jpg, ...')
+  p.add_option('--landmarks', type='string', dest='landmarks', default=None, help='68 landmarks per frame, 136 comma-separated values per line')
+  p.add_option('--out_dir', type='string', dest='out_dir', default=None, help='the dataset folder to write')
+  p.add_option('--size', type='int', dest='size', default=None, help='panel size S (default: the frames\' own)')
+  p.add_option('--crop', type='int', nargs=3, dest='crop', default=None, help='X0 Y0 SIDE: the square of each frame to keep')
+  p.add_option('--alpha_dir', type='string', dest='alpha_dir', default=None, help='mattes <i>.png / <i>.jpg: step 6\'s layout')
+  p.add_option('--bfmcoeff', type='string', dest='bfmcoeff', default=None, help='rows of 257 coefficients instead of a fit')
+  p.add_option('--appearance', type='choice', choices=['first', 'none'], dest='appearance', default='first',
+               help='first: texture and lighting fitted to frame 0 and shared; none: zeros')
+  p.add_option('--frame_batch', type='int', dest='frame_batch', default=32, help='frames per device batch')
+  p.add_option('--list', type='string', dest='list', default=None, help='dataset list to append "out_dir|count" to')
+  p.add_option('--rounds', type='int', dest='rounds', default=3, help='fit_sequence: rounds of (identity steps, tracking fit)')
+  p.add_option('--id_steps', type='int', dest='id_steps', default=3, help='fit_sequence: identity steps per round')
+  return p.parse_args(argv)
+
+
+def main(argv=None):
+  opts, _ = parse_options(argv)
+  if opts.clip_dir is None or opts.landmarks is None or opts.out_dir is None:
+    logger.error('Please check your parameters: --clip_dir, --landmarks and --out_dir are needed.')
+    exit(0)
+  from voicepuppet_amd.bfmnet.fit_landmarks import BFM_MAT, LM3D_MAT, _BFM, read_landmarks, reprojection_error, summary_line
+  if not (os.path.exists(BFM_MAT) and os.path.exists(LM3D_MAT)):
+    logger.error('%s and %s are needed', BFM_MAT, LM3D_MAT)
+    exit(0)
+  if opts.frame_batch < 1:
+    raise SystemExit('--frame_batch must be at least 1')
+  import torch
+  from scipy.io import loadmat
+  from voicepuppet_amd.bfmfit import FaceFitter, crop_alignment, photo_affine, preprocess_landmarks
+  from voicepuppet_amd.pixrefer.infer_bfmvid import paste_geometry
+  from voicepuppet_amd.triptych import STATUS, TriptychBuilder
+  from voicepuppet_amd.utils.reconstruct_mesh import ClipRenderer
+
+  frames_n = count_frames(opts.clip_dir)
+  if frames_n < 1:
+    raise SystemExit('%s: no 0.jpg' % opts.clip_dir)
+  with open(opts.landmarks) as f:
+    raw_lines = [line for line in f if line.strip()]
+  lms = read_landmarks(opts.landmarks)
+  if lms.shape[0] < frames_n:
+    raise SystemExit('%s has %d lines for the %d frames of %s' % (opts.landmarks, lms.shape[0], frames_n, opts.clip_dir))
+  lms, raw_lines = lms[:frames_n], raw_lines[:frames_n]
+  batch = min(opts.frame_batch, frames_n)
+  try:
+    reader = FrameReader(opts.clip_dir, batch, opts.crop, opts.size)
+  except ValueError as e:
+    raise SystemExit(str(e))
+  S = reader.size
+  lms = reader.landmarks_to_panel(lms)
+
+  # alignment and paste geometry per frame (host, float64): datasets/make_data_from_GRID.py:193-214 and infer_bfmvid.py:83-86
+  fitter = FaceFitter(_BFM(loadmat(BFM_MAT)))
+  lm3D = loadmat(LM3D_MAT)['lm']
+  aligned, geometry = [], []
+  for lm in lms:
+    crop, center_x, center_y, ratio = crop_alignment(lm, S, S)
+    lm_new, trans_params = preprocess_landmarks(crop, lm3D)
+    aligned.append(lm_new)
+    geometry.append(paste_geometry(center_x, center_y, ratio, trans_params, 224))
+  aligned, geometry = np.stack(aligned), np.array(geometry, np.int64)
+
+  if opts.bfmcoeff:
+    rows = np.loadtxt(opts.bfmcoeff, delimiter=',', dtype=np.float32, ndmin=2)
+    if rows.shape[0] < frames_n or rows.shape[1] != 257:
+      raise SystemExit('%s: %s, expected at least %d rows of 257' % (opts.bfmcoeff, rows.shape, frames_n))
+    coeff, report = torch.from_numpy(rows[:frames_n]).cuda(), torch.zeros(frames_n, 4, dtype=torch.float64, device='cuda')
+  else:
+    coeff, report = fitter.fit_sequence(aligned, rounds=opts.rounds, id_steps=opts.id_steps)
+  extra = ''
+  if opts.appearance == 'first':
+    frame0 = reader.read(0, 1)[0]
+    first, rep = fitter.fit_appearance(coeff[:1], photo=frame0, affine=photo_affine(lms[0], S, S, lm3D))
+    coeff = coeff.clone()
+    coeff[:, 144:224], coeff[:, 227:254] = first[:, 144:224], first[:, 227:254]
+    extra = ', appearance status %d' % int(rep[0, 0].item())
+
+  os.makedirs(opts.out_dir, exist_ok=True)
+  renderer = ClipRenderer(fitter.model)
+  builder = TriptychBuilder(S, batch)
+  status, repeated = [], []
+  try:
+    for first in range(0, frames_n, batch):
+      n = min(batch, frames_n - first)
+      frames = reader.read(first, n)
+      render, face_mask = renderer.render_view(coeff[first:first + n], view=0)
+      alpha = read_alpha(reader, opts.alpha_dir, first, n) if opts.alpha_dir else None
+      trip, st = builder.build(frames, render, face_mask, geometry[first:first + n], alpha=alpha)
+      repeated += builder.write(trip, st, opts.out_dir, first)
+      status.append(st.cpu().numpy())
+  except ValueError as e:
+    raise SystemExit('%s: %s' % (opts.clip_dir, e))
+  status = np.concatenate(status)
+
+  np.savetxt(os.path.join(opts.out_dir, 'bfmcoeff.txt'), coeff.cpu().numpy(), delimiter=',', fmt='%.8g')
+  with open(os.path.join(opts.out_dir, 'ear.txt'), 'w') as f:
+    for line in raw_lines:
+      f.write('{}\n'.format(ear_value([float(v) for v in line.strip().split(',')])))
+  if opts.list:
+    with open(opts.list, 'a') as f:
+      f.write('%s|%d\n' % (opts.out_dir, frames_n))
+  counts = ' '.join('%d:%d' % (s, int((status == s).sum())) for s in sorted(set(status.tolist())))
+  for s in sorted(set(status.tolist()) - {0}):
+    logger.warning('triptych status %d: %s', s, STATUS.get(s, '?'))
+  fit = summary_line(opts.clip_dir, report, reprojection_error(fitter, coeff, aligned))
+  print('%s; triptych status %s, %d repeated, %d read with PIL%s' % (fit, counts, len(repeated), reader.fallbacks, extra))
+  return {'frames': frames_n, 'status': status, 'repeated': repeated, 'geometry': geometry}
+
+
+if (__name__ == '__main__'):
+  main()
