@@ -62,6 +62,7 @@ struct Tens {
   bool is_f32 = false;
   bool has_bn = false;
   bool is_input = false;
+  int pool = -1, pool_src = -1;   // VGG: this tensor is pool 0 / 1 (pool1 / pool2) of the conv tensor pool_src
   bool dz_written = false;
   void* dz2 = nullptr;    // discriminator tensors: gradient buffer of the generator-loss pass (fake group only), so that pass can run
   bool dz2_written = false;   // concurrently with the discriminator-loss pass, which owns dz
@@ -95,6 +96,8 @@ struct Layer {
   int out_act = ACT_NONE;  // VGG: relu in the epilogue
   int out = -1;
   bool has_bn = false;
+  bool fg = false;               // generator: one of encoder_fg_1 .. 4 (the chain that runs beside encoder_1 .. 4 on a stream of its own)
+  int pool = -1, pool_t = -1;    // VGG: this conv (conv1_2 / conv2_2) feeds pool 0 / 1, the tensor pool_t
   size_t w_off = 0, b_off = 0, gamma_off = 0, beta_off = 0;
   size_t pk_fwd = 0, pk_bwd[2] = {0, 0}, pk_bwd_alt[2] = {0, 0};   // pk_bwd_alt == pk_bwd unless the two batch sizes run different kernel families
   bool need_bwd[2] = {false, false};
@@ -127,6 +130,7 @@ struct Net {
   std::vector<ParamInfo> manifest;
   size_t nparams = 0;
   int batch = 0, groups = 1;
+  int i_md5 = -1, i_me2 = -1;   // generator: layers merged_decoder_5 / merged_encoder_2, where the gradient buckets of the backward pass begin
   float* params = nullptr;
   float* grads = nullptr;
   char* packed = nullptr;       // packed weights of this net (compute dtype)
@@ -136,6 +140,15 @@ struct Net {
   unsigned* sp_cnt = nullptr;   // arrival counters of the few-pixel launches of this net (zeroed at create, left zero by every launch)
   size_t sp_cnt_n = 0;
 };
+
+// A stream of the executor with the split-K / slab scratch and the batch-norm partials of the work enqueued on it: two streams never
+// share either, so whatever runs on a lane takes both from that lane
+struct Lane { hipStream_t s; char* scratch; double* bn_partial; };
+enum { LANE_CALLER = 0, LANE_SIDE = 1, LANE_BRANCH = 2, LANE_BRANCH2 = 3 };
+
+// the samples a backward launch covers: the whole batch, or (alt: the plans for batch N, gpass: the dz2 buffers) the fake group of the
+// discriminator on the generator-loss pass
+struct Sub { int sample0, nb; bool alt, gpass; };
 
 }  // namespace vp
 
@@ -160,17 +173,13 @@ struct vp_pixrefer {
   bool pool_fuse_ok[2];
   bool pool_bwd_fused;        // the last backward pass took that path (vp_pixrefer_counter("pool_bwd_fused"))
   bool pool_dz_stale[2];      // ... and the conv's :dy tensor has not been materialised since (vp_pixrefer_tensor does it on demand)
-  double *comp_partial, *perc_partial, *bn_partial;
-  char* scratch;
-  char* scratch2;             // split-K / slab scratch and batch-norm partials of the side stream (backward_d when overlapped)
-  double* bn_partial2;
-  char* scratch3;             // ... and of the branch stream (the generator's foreground encoder branch, forward and backward)
-  double* bn_partial3;
-  char* scratch4;             // ... and of the second branch stream (the foreground encoder branch of the BACKWARD pass, see branch2)
-  double* bn_partial4;
-  hipStream_t side, branch;
-  hipStream_t branch2;             // backward: the foreground encoder chain, so that it does not queue behind the weight-gradient backlog of `branch`
-                                   // (== branch with vp_pixrefer_desc::streams = 3 / vp_pixrefer_use_streams(h, 3): a host that brings streams of its own wants three)
+  double *comp_partial, *perc_partial;
+  // [LANE_CALLER]: the caller's stream - it differs per call, so .s stays null here and every entry point binds it (caller_lane);
+  // [LANE_SIDE]: the low-priority side stream (backward_d when overlapped); [LANE_BRANCH]: the generator's foreground encoder branch of the
+  // forward pass, the weight gradients of the backward pass; [LANE_BRANCH2]: backward: the foreground encoder chain, so that it does not
+  // queue behind the weight-gradient backlog of the branch lane (.s created on first use; with vp_pixrefer_desc::streams = 3 /
+  // vp_pixrefer_use_streams(h, 3) the chain stays on the branch lane: a host that brings streams of its own wants three)
+  Lane lane[4];
   hipEvent_t ev_b2join;
   bool use_b2;                     // vp_pixrefer_use_streams: false = the backward pass keeps to three streams (the host runs a stream of its own)
   hipEvent_t ev_fork, ev_join, ev_bfork, ev_bjoin;
@@ -281,7 +290,10 @@ static void build_generator(Net& n, int N, int H, int ngf, int groups = 1) {
   int c4 = add_layer(n, P, "merged2_decoder_4", 1, 4, 2, 1, {d2, e4}, ngf * 8, ngf * 2, true, ACT_RELU, ACT_NONE, DK, DB);
   int c3 = add_layer(n, P, "merged2_decoder_3", 1, 4, 2, 1, {c4, e3}, ngf * 4, ngf * 2, true, ACT_RELU, ACT_NONE, DK, DB);
   int c2 = add_layer(n, P, "merged2_decoder_2", 1, 4, 2, 1, {c3, e2}, ngf * 4, ngf, true, ACT_RELU, ACT_NONE, DK, DB);
-  add_layer(n, P, "decoder_1", 1, 4, 2, 1, {c2, e1}, ngf * 2, 4, false, ACT_RELU, ACT_NONE, DK, DB);
+  int d1 = add_layer(n, P, "decoder_1", 1, 4, 2, 1, {c2, e1}, ngf * 2, 4, false, ACT_RELU, ACT_NONE, DK, DB);
+  n.t[d1].is_f32 = true;        // thin float32 output (a plan-level buffer)
+  for (int f : {f1, f2, f3, f4}) n.l[n.t[f].producer].fg = true;
+  n.i_me2 = n.t[m2].producer; n.i_md5 = n.t[d5].producer;
 }
 
 static void build_discriminator(Net& n, int N, int H, int ndf) {
@@ -294,7 +306,8 @@ static void build_discriminator(Net& n, int N, int H, int ndf) {
   int l2 = add_layer(n, P, "layer_2", 0, 4, 2, 1, {l1}, ndf, ndf * 2, true, ACT_LRELU, ACT_NONE, CK, CB);
   int l3 = add_layer(n, P, "layer_3", 0, 4, 2, 1, {l2}, ndf * 2, ndf * 4, true, ACT_LRELU, ACT_NONE, CK, CB);
   int l4 = add_layer(n, P, "layer_4", 0, 4, 1, 1, {l3}, ndf * 4, ndf * 8, true, ACT_LRELU, ACT_NONE, CK, CB);
-  add_layer(n, P, "layer_5", 0, 4, 1, 1, {l4}, ndf * 8, 1, false, ACT_LRELU, ACT_NONE, CK, CB);
+  int l5 = add_layer(n, P, "layer_5", 0, 4, 1, 1, {l4}, ndf * 8, 1, false, ACT_LRELU, ACT_NONE, CK, CB);
+  n.t[l5].is_f32 = true;        // thin float32 output (a plan-level buffer)
 }
 
 static void build_vgg(Net& n, int N, int H) {
@@ -302,12 +315,19 @@ static void build_vgg(Net& n, int N, int H) {
   const int tin = add_tensor(n, "v_inputs", 2 * N, H, H, 8, false, true);
   const std::string P = "vgg_16/";
   // vgg_simple.py:138-151: conv3x3 s1 SAME + bias + relu; pools are separate ops between the blocks
+  auto add_pool = [&](int k, int conv) {
+    const Tens tc = n.t[conv];
+    const int p = add_tensor(n, k ? "pool2" : "pool1", tc.N, tc.H / 2, tc.W / 2, tc.C, false, false);
+    n.t[p].pool = k; n.t[p].pool_src = conv;
+    n.l[tc.producer].pool = k; n.l[tc.producer].pool_t = p;
+    return p;
+  };
   int c11 = add_layer(n, P, "conv1/conv1_1", 0, 3, 1, 1, {tin}, 3, 64, false, ACT_NONE, ACT_RELU, "weights", "biases");
-  add_layer(n, P, "conv1/conv1_2", 0, 3, 1, 1, {c11}, 64, 64, false, ACT_NONE, ACT_RELU, "weights", "biases");
-  const int p1 = add_tensor(n, "pool1", 2 * N, H / 2, H / 2, 64, false, false);
+  int c12 = add_layer(n, P, "conv1/conv1_2", 0, 3, 1, 1, {c11}, 64, 64, false, ACT_NONE, ACT_RELU, "weights", "biases");
+  const int p1 = add_pool(0, c12);
   int c21 = add_layer(n, P, "conv2/conv2_1", 0, 3, 1, 1, {p1}, 64, 128, false, ACT_NONE, ACT_RELU, "weights", "biases");
-  add_layer(n, P, "conv2/conv2_2", 0, 3, 1, 1, {c21}, 128, 128, false, ACT_NONE, ACT_RELU, "weights", "biases");
-  const int p2 = add_tensor(n, "pool2", 2 * N, H / 4, H / 4, 128, false, false);
+  int c22 = add_layer(n, P, "conv2/conv2_2", 0, 3, 1, 1, {c21}, 128, 128, false, ACT_NONE, ACT_RELU, "weights", "biases");
+  const int p2 = add_pool(1, c22);
   int c31 = add_layer(n, P, "conv3/conv3_1", 0, 3, 1, 1, {p2}, 128, 256, false, ACT_NONE, ACT_RELU, "weights", "biases");
   int c32 = add_layer(n, P, "conv3/conv3_2", 0, 3, 1, 1, {c31}, 256, 256, false, ACT_NONE, ACT_RELU, "weights", "biases");
   add_layer(n, P, "conv3/conv3_3", 0, 3, 1, 1, {c32}, 256, 256, false, ACT_NONE, ACT_RELU, "weights", "biases");
@@ -332,7 +352,6 @@ static void plan_net(Net& n, int bf16, bool training, bool want_wgrad, int alt_b
     n.descs.push_back(p.pack);
     if (p.partial_bytes > *scratch_max) *scratch_max = p.partial_bytes;
   };
-  for (Tens& t : n.t) t.is_f32 = t.name == "decoder_1" || t.name == "layer_5";   // thin float32 outputs (plan-level buffers)
   for (Layer& L : n.l) {
     L.desc0 = n.descs.size();
     Tens& to = n.t[L.out];
@@ -586,33 +605,24 @@ static size_t carve_all(vp_pixrefer* h, char* base, size_t cap, std::vector<std:
     carve_net(h->D, ar, es, true);
     carve_net(h->V, ar, es, true);
     // gradient buffers.  generator + discriminator: one per non-input tensor.
-    for (Tens& t : h->G.t) if (!t.is_input && t.name != "decoder_1") { t.dz = ar.alloc(t.elems() * es); if (t.hi) t.dz32 = ar.alloc(t.elems() * sizeof(float)); }
-    for (Tens& t : h->D.t) if (!t.is_input && t.name != "layer_5") { t.dz = ar.alloc(t.elems() * es); t.dz2 = ar.alloc(t.elems() / 3 * es); }
+    for (Tens& t : h->G.t) if (!t.is_input && !t.is_f32) { t.dz = ar.alloc(t.elems() * es); if (t.hi) t.dz32 = ar.alloc(t.elems() * sizeof(float)); }
+    for (Tens& t : h->D.t) if (!t.is_input && !t.is_f32) { t.dz = ar.alloc(t.elems() * es); t.dz2 = ar.alloc(t.elems() / 3 * es); }
     // 64-channel tensors without batch-norm (encoder_1, encoder_fg_1, layer_1): partial rows of the producer's bias gradient (conv_dc64.hip CSUM)
     for (Net* n : {&h->G, &h->D})
       for (Tens& t : n->t) if (h->bf16 && !t.is_input && !t.has_bn && t.C == 64) t.cs_part = (double*)ar.alloc((size_t)512 * 2 * 64 * sizeof(double));
     // VGG backward runs on the fake half only
     for (Tens& t : h->V.t) if (!t.is_input) t.dz = ar.alloc(t.elems() / 2 * es);
     // ... and the arg-max codes of its two pools (one byte per pooled element of the fake half)
-    for (const Tens& t : h->V.t) {
-      if (t.name == "pool1") h->vpool_code[0] = (unsigned char*)ar.alloc(t.elems() / 2);
-      if (t.name == "pool2") h->vpool_code[1] = (unsigned char*)ar.alloc(t.elems() / 2);
-    }
+    for (const Tens& t : h->V.t) if (t.pool >= 0) h->vpool_code[t.pool] = (unsigned char*)ar.alloc(t.elems() / 2);
     h->n_comp = composite_nblocks(N, H * H);
     h->n_perc = perceptual_nblocks((size_t)N * (H / 4) * (H / 4) * 256, h->bf16);
     h->comp_partial = (double*)ar.alloc((size_t)h->n_comp * 2 * sizeof(double));
     h->perc_partial = (double*)ar.alloc((size_t)h->n_perc * sizeof(double));
   }
   h->zeros = ar.alloc(256);
-  h->bn_partial = (double*)ar.alloc((size_t)1024 * 2 * 512 * sizeof(double));
-  h->scratch = (char*)ar.alloc(h->scratch_bytes);
-  if (d.training) {
-    h->bn_partial2 = (double*)ar.alloc((size_t)1024 * 2 * 512 * sizeof(double));
-    h->scratch2 = (char*)ar.alloc(h->scratch_bytes);
-    h->bn_partial3 = (double*)ar.alloc((size_t)1024 * 2 * 512 * sizeof(double));
-    h->scratch3 = (char*)ar.alloc(h->scratch_bytes);
-    h->bn_partial4 = (double*)ar.alloc((size_t)1024 * 2 * 512 * sizeof(double));
-    h->scratch4 = (char*)ar.alloc(h->scratch_bytes);
+  for (int k = 0; k < (d.training ? 4 : 1); ++k) {      // (an inference plan runs on the caller's lane only)
+    h->lane[k].bn_partial = (double*)ar.alloc((size_t)1024 * 2 * 512 * sizeof(double));
+    h->lane[k].scratch = (char*)ar.alloc(h->scratch_bytes);
   }
   return ar.off + 256;
 }
@@ -641,11 +651,11 @@ static void init_handle(vp_pixrefer* h, const vp_pixrefer_desc* d) {
     for (Layer& L : h->V.l) L.g.N = 2 * d->batch;
     plan_net(h->V, h->bf16, true, false, d->batch, &smax, true);
     for (const Layer& L : h->V.l) {
-      if (L.scope != "conv1/conv1_2" && L.scope != "conv2/conv2_2") continue;
+      if (L.pool < 0) continue;
       // knob 1: pool1 always; pool2 from 4096 tiles of the conv2_2 launch (16 frames at 256 x 256) - below that its pooled-source form
       // measured +0.01 .. 0.02 ms on the 8-frame step against pool1 alone, from 16 frames up it gains (EXPERIMENTS.md 0.Q).  2 / 3: pool1 /
       // pool2 only, 4: both at every size (experiments and tests)
-      const int k = L.scope == "conv2/conv2_2", knob = pool_bwd_fused_knob();
+      const int k = L.pool, knob = pool_bwd_fused_knob();
       const IgemmArgs& ba = L.bwd_alt[0].a;
       const bool big = !k || (long long)ba.N * (ba.Hg / 4) * (ba.Wg / 16) >= 4096;
       h->pool_fuse_ok[k] = ((knob == 1 && big) || knob == 2 + k || knob == 4) && h->bf16 && conv_kernel_ok(pool_fused_view(L.bwd_alt[0]), h->bf16);
@@ -676,19 +686,34 @@ static bool valid_desc(const vp_pixrefer_desc* d) {
 // ------------------------------------------------------------------------------------------------
 // execution helpers
 // ------------------------------------------------------------------------------------------------
-static void fill_src(const Net& n, const Layer& L, PixSrc& x, int group_n, int sample0, int group0, int es) {
+// sample `sample0` of tensor t in the buffer `base` (one of t's own: y, an activation copy) of `es`-byte elements
+static char* at_sample(const Tens& t, const void* base, int sample0, int es) {
+  return (char*)base + (size_t)sample0 * t.H * t.W * t.C * es;
+}
+
+static void fill_src(const Net& n, const Layer& L, PixSrc& x, int group_n, int sample0, int es) {
   for (int s = 0; s < 2; ++s) {
     x.ptr[s] = nullptr; x.C[s] = 0; x.aff_a[s] = nullptr; x.aff_b[s] = nullptr;
   }
   for (int s = 0; s < L.nsrc; ++s) {
     const Tens& t = n.t[L.src[s]];
-    const void* base = (L.in_act != ACT_NONE) ? t.xa[L.in_act] : t.y;   // act(bn(y)) was materialised by the producer
-    x.ptr[s] = (const char*)base + (size_t)sample0 * t.H * t.W * t.C * es;
+    x.ptr[s] = at_sample(t, (L.in_act != ACT_NONE) ? t.xa[L.in_act] : t.y, sample0, es);   // act(bn(y)) was materialised by the producer
     x.C[s] = t.C;
   }
   x.act = ACT_NONE;
   x.group_n = group_n;
-  (void)group0;
+}
+
+// the caller's lane for this call: its stream with the first scratch set
+static Lane caller_lane(const vp_pixrefer* h, void* stream) {
+  return Lane{(hipStream_t)stream, h->lane[LANE_CALLER].scratch, h->lane[LANE_CALLER].bn_partial};
+}
+
+// record-then-wait: what is enqueued on `to` from here on runs after everything enqueued on `from` so far
+static int after(hipEvent_t ev, hipStream_t from, hipStream_t to) {
+  VP_HIP_CHECK(hipEventRecord(ev, from));
+  VP_HIP_CHECK(hipStreamWaitEvent(to, ev, 0));
+  return VP_OK;
 }
 
 static int run_pack(vp_pixrefer* h, Net& n, hipStream_t st) {
@@ -697,18 +722,15 @@ static int run_pack(vp_pixrefer* h, Net& n, hipStream_t st) {
   return VP_OK;
 }
 
-// scratch set of a stream: 0 = the caller's stream, 1 = side stream, 2 = branch stream
-static char* scratch_of(vp_pixrefer* h, int ss) { return ss == 3 ? h->scratch4 : ss == 2 ? h->scratch3 : ss == 1 ? h->scratch2 : h->scratch; }
-static double* bnp_of(vp_pixrefer* h, int ss) { return ss == 3 ? h->bn_partial4 : ss == 2 ? h->bn_partial3 : ss == 1 ? h->bn_partial2 : h->bn_partial; }
-
 // fused_chunks > 0: the conv epilogue already wrote that many partial chunks per group; only the finalize pass runs
-static int run_bn_stats(vp_pixrefer* h, Net& n, Layer& L, int fused_chunks, hipStream_t st, int ss = 0) {
+static int run_bn_stats(vp_pixrefer* h, Net& n, Layer& L, int fused_chunks, const Lane& ln) {
+  hipStream_t st = ln.s;
   Tens& t = n.t[L.out];
   BnArgs b;
   memset(&b, 0, sizeof(b));
   b.y = t.y; b.C = t.C; b.G = n.groups; b.Pg = (n.batch / n.groups) * t.H * t.W;
   b.nchunk = bn_nchunk(b.Pg, b.C, b.G, h->bf16);
-  b.partial = bnp_of(h, ss);
+  b.partial = ln.bn_partial;
   b.gamma = n.params + L.gamma_off; b.beta = n.params + L.beta_off;
   b.aff_a = t.bn.a; b.aff_b = t.bn.b; b.mu = t.bn.mu; b.rstd = t.bn.rstd;
   b.eps = 1e-5f;   // pixrefer.py:100
@@ -750,22 +772,22 @@ static int epi_stat_chunks(const IgemmPlan& p, int batch, int groups) {
 
 // forward of one half of the batch of a plain conv layer (VGG: no batch-norm, activation in the epilogue): half 0 / 1
 // (pool_code: with pool_only, the epilogue also records the pool's arg-max codes for the backward pass)
-static int run_layer_fwd_half(vp_pixrefer* h, Net& n, Layer& L, int half, hipStream_t st, void* pool_out = nullptr, bool pool_only = false,
+static int run_layer_fwd_half(vp_pixrefer* h, Net& n, Layer& L, int half, const Lane& ln, void* pool_out = nullptr, bool pool_only = false,
                               unsigned char* pool_code = nullptr) {
   IgemmArgs a = L.fwd_half.a;
   a.pool_out = pool_out;
   a.pool_only = pool_out && pool_only ? 1 : 0;
   a.pool_code = a.pool_only ? pool_code : nullptr;
   const int nb = a.N;
-  fill_src(n, L, a.x, nb, half * nb, 0, h->es);
+  fill_src(n, L, a.x, nb, half * nb, h->es);
   a.Wp = n.packed + L.pk_fwd_half * h->es;
   Tens& to = n.t[L.out];
-  a.Y = (char*)to.y + (size_t)half * nb * to.H * to.W * to.C * h->es;      // (ldY, out_act: the plan's)
+  a.Y = at_sample(to, to.y, half * nb, h->es);      // (ldY, out_act: the plan's)
   a.bias = n.params + L.b_off;
   a.partial = nullptr;        // (no K split on this path)
   a.zeros = h->zeros;
   profile_tag((L.scope + (half ? ":fwd1" : ":fwd0")).c_str());
-  VP_HIP_CHECK(launch_igemm(a, h->bf16, L.fwd_half.cfg, st));
+  VP_HIP_CHECK(launch_igemm(a, h->bf16, L.fwd_half.cfg, ln.s));
   return VP_OK;
 }
 
@@ -777,25 +799,44 @@ static bool first_layer_acts_fused(const vp_pixrefer* h, const Net& n, const Lay
   return first_layer_shape(h->bf16, n, L) && L.fwd.a.kern == CK_CIN8;
 }
 
+// the few-pixel kernel's argument block around the filled launch `a` (mode SP_PLAIN): arrival counters `cnt`, slab and partials of the lane
+static SmallPArgs smallp_args(const IgemmArgs& a, unsigned* cnt, const Lane& ln) {
+  SmallPArgs sp;
+  memset(&sp, 0, sizeof(sp));
+  sp.g = a;
+  sp.g.sp_cnt = cnt;
+  for (int c = 0; c < 4; ++c) sp.tap_mask[c] = a.sp_mask[c];
+  sp.slab = a.partial; sp.cnt = cnt; sp.part = ln.bn_partial;
+  return sp;
+}
+
+// ... whose launch completes the gradient of the batch-normalised tensor t: the batch-norm backward of t (sums, c1 / c2, dgamma / dbeta, dy
+// in place; Tens::hi: dz32 / y in float32, dL/dy out as T into dz) runs in the same launch, run_bn_bwd then skips it
+static void smallp_bn_bwd(SmallPArgs& sp, Net& n, Tens& t) {
+  const Layer& Lp = n.l[t.producer];
+  sp.mode = SP_BWD_BN;
+  if (t.hi) { sp.hi = 1; sp.dy_out = t.dz; }
+  sp.bn_y = t.y; sp.bn_mu = t.bn.mu; sp.bn_rstd = t.bn.rstd; sp.bn_gamma = n.params + Lp.gamma_off;
+  sp.c1 = t.bn.c1; sp.c2 = t.bn.c2;
+  sp.dgamma = n.grads + Lp.gamma_off; sp.dbeta = n.grads + Lp.beta_off; sp.dbias_zero = n.grads + Lp.b_off;
+  t.bn_bwd_done = true;
+}
+
 // forward of one conv layer (+ its batch statistics)
-static int run_layer_fwd(vp_pixrefer* h, Net& n, Layer& L, hipStream_t st, void* pool_out = nullptr, int ss = 0) {
+static int run_layer_fwd(vp_pixrefer* h, Net& n, Layer& L, const Lane& ln, void* pool_out = nullptr) {
+  hipStream_t st = ln.s;
   IgemmArgs a = L.fwd.a;
   a.pool_out = pool_out;
-  fill_src(n, L, a.x, n.batch / n.groups, 0, 0, h->es);
+  fill_src(n, L, a.x, n.batch / n.groups, 0, h->es);
   a.Wp = n.packed + L.pk_fwd * h->es;
   Tens& to = n.t[L.out];
   a.Y = L.tapgemm ? L.tap_S : to.y;      // (ldY, y_f32, out_act: the plan's)
   a.bias = L.has_bn || L.tapgemm ? nullptr : n.params + L.b_off;   // a bias in front of batch-norm cancels exactly
-  a.partial = (float*)scratch_of(h, ss);
+  a.partial = (float*)ln.scratch;
   a.zeros = h->zeros;
   if (a.kern == CK_SMALLP) {
     // few-pixel layer: convolution, K-split combine, batch statistics, affine and the consumers' activations in ONE launch
-    SmallPArgs sp;
-    memset(&sp, 0, sizeof(sp));
-    a.sp_cnt = L.sp_cnt_fwd;
-    sp.g = a;
-    for (int c = 0; c < 4; ++c) sp.tap_mask[c] = a.sp_mask[c];
-    sp.slab = a.partial; sp.cnt = a.sp_cnt; sp.part = bnp_of(h, ss);
+    SmallPArgs sp = smallp_args(a, L.sp_cnt_fwd, ln);
     sp.mode = L.has_bn ? SP_FWD_BN : SP_PLAIN;
     sp.hi = to.hi ? 1 : 0;               // float32 raw output + statistics of the unrounded values (Tens::hi)
     if (L.has_bn) {
@@ -818,19 +859,19 @@ static int run_layer_fwd(vp_pixrefer* h, Net& n, Layer& L, hipStream_t st, void*
   if (L.has_bn && a.kern == CK_DC256 && n.groups == 1) {
     // conv_dc64.hip conv_dc256_kernel: one partial row per block and column parity
     stat_chunks = 2 * conv_dc256_grid(a);
-    a.bn_part = bnp_of(h, ss); a.bn_tpg = 1 << 30; a.bn_nchunk = stat_chunks;
+    a.bn_part = ln.bn_partial; a.bn_tpg = 1 << 30; a.bn_nchunk = stat_chunks;
     fused_stats = true;
   } else if (L.has_bn && a.kern == CK_S2C64) {
     // conv_s2c64.hip: one partial row per block and group
     const int grid = conv_s2c64_grid(a);
     if ((size_t)n.groups * grid * 2 * to.C <= (size_t)1024 * 2 * 512 && n.groups <= 32) {
       stat_chunks = grid;
-      a.bn_part = bnp_of(h, ss); a.bn_tpg = (n.batch / n.groups) * conv_s2c64_tiles_per_image(a); a.bn_nchunk = grid;
+      a.bn_part = ln.bn_partial; a.bn_tpg = (n.batch / n.groups) * conv_s2c64_tiles_per_image(a); a.bn_nchunk = grid;
       fused_stats = true;
     }
   } else if (L.fwd_stats) {       // one row per pixel tile and class
     stat_chunks = epi_stat_chunks(L.fwd, n.batch, n.groups);
-    a.bn_part = bnp_of(h, ss); a.bn_tpg = stat_chunks / a.nclass; a.bn_nchunk = stat_chunks;
+    a.bn_part = ln.bn_partial; a.bn_tpg = stat_chunks / a.nclass; a.bn_nchunk = stat_chunks;
     fused_stats = true;
   }
   // first layers (8-channel image inputs, no batch-norm: encoder_1, encoder_fg_1, discriminator layer_1): the direct kernel's epilogue
@@ -853,7 +894,7 @@ static int run_layer_fwd(vp_pixrefer* h, Net& n, Layer& L, hipStream_t st, void*
   }
   bool acts_done = acts_fused;
   if (L.has_bn) {
-    const int rc = run_bn_stats(h, n, L, fused_stats ? stat_chunks : 0, st, ss);
+    const int rc = run_bn_stats(h, n, L, fused_stats ? stat_chunks : 0, ln);
     if (rc < 0) return rc;
     acts_done = rc == 1;
   }
@@ -865,174 +906,154 @@ static int run_layer_fwd(vp_pixrefer* h, Net& n, Layer& L, hipStream_t st, void*
   return VP_OK;
 }
 
-// backward of one layer given dL/dy in `dy` (dtype T, channel stride g.CoutT):
-//   weight/bias/BN gradients (when grads != null) and dz of every source tensor.
-// sample0/nb/group0/ng select a sub-batch (discriminator G-loss pass: the fake group only).
-// ss: scratch set of the stream the call runs on; gpass: generator-loss pass through the discriminator (dz2 buffers)
-static int run_layer_bwd(vp_pixrefer* h, Net& n, Layer& L, const void* dy, bool want_dw, bool alt,
-                         int sample0, int nb, int group0, hipStream_t st, int ss = 0, bool gpass = false, int parts = 7) {
-  // parts: bit 0 = weight / bias gradients, bit 1 = data gradient of source 0, bit 2 = data gradient of source 1 (so a host can put
-  // them on different streams: only source 0's gradient - the decoder chain - is on the critical path of the generator backward)
-  const int es = h->es;
-  if (!(parts & 1)) want_dw = false;
-  char* scratch = scratch_of(h, ss);
-  double* bn_partial = bnp_of(h, ss);
-  const int group_n = n.batch / n.groups;
-  if (want_dw) {
-    WgradArgs w = L.wg.a;
-    PixSrc xs;
-    fill_src(n, L, xs, group_n, sample0, group0, es);
-    PixSrc ds;
-    set_single_src(ds, dy, L.g.CoutT, nullptr, nullptr, ACT_NONE, 0);
-    if (L.g.kind == 0) { w.g = xs; w.d = ds; } else { w.g = ds; w.d = xs; }
-    bool own_wgrad = false;
-    if (L.tapgemm && h->bf16 && cout1_knob() > 0 && L.nsrc == 1 && !n.t[L.src[0]].is_input && !n.t[L.src[0]].hi && n.t[L.src[0]].xa[L.in_act] &&
-        L.g.ks == 4 && L.g.stride == 1) {
-      // the one-output-channel layer's weight gradient on its own kernel (conv_cout1.hip): no tap spreading, no transposes
-      Tens& tx = n.t[L.src[0]];
-      Cout1Args c;
-      memset(&c, 0, sizeof(c));
-      c.dy = dy; c.ld_dy = L.g.CoutT;
-      c.ref = (const char*)tx.xa[L.in_act] + (size_t)sample0 * tx.H * tx.W * tx.C * es;
-      c.N = nb; c.H = tx.H; c.W = tx.W; c.C = tx.C; c.Ho = L.g.Hout; c.Wo = L.g.Wout; c.ks = L.g.ks; c.pad = L.g.pad;
-      c.slabs = (float*)scratch; c.dW = n.grads + L.w_off;
-      const long long px = (long long)nb * tx.H * tx.W;
-      const size_t cap = h->scratch_bytes / ((size_t)16 * 512 * sizeof(float));
-      c.rows = (int)(px / 96 < wgrad1_rows_knob() ? px / 96 : wgrad1_rows_knob());            // >= 24 pixels per wave
-      if ((size_t)c.rows > cap) c.rows = (int)cap;
-      if (c.rows >= 1 && L.g.Cin == 512 && conv_cout1_wgrad_eligible(c)) {
-        profile_tag((L.scope + ":wgrad").c_str());
-        VP_HIP_CHECK(launch_cout1_wgrad_prof(c, st));
-        own_wgrad = true;
-      }
-    }
-    if (L.tapgemm && !own_wgrad) {
-      TapArgs ta;
-      memset(&ta, 0, sizeof(ta));
-      ta.dy = dy; ta.dyS = L.tap_dyS; ta.ld_dy = L.g.CoutT;
-      ta.N = nb; ta.Hin = L.g.Hin; ta.Win = L.g.Win; ta.Hout = L.g.Hout; ta.Wout = L.g.Wout; ta.ks = L.g.ks; ta.pad = L.g.pad;
-      VP_HIP_CHECK(launch_tap_spread(ta, h->bf16, st));
-      set_single_src(w.g, L.tap_dyS, 16, nullptr, nullptr, ACT_NONE, 0);
-      w.d = xs;
-    }
-    w.partial = (float*)scratch;
-    w.dW = n.grads + L.w_off;
-    w.accumulate = 0;
-    w.zeros = h->zeros;
-    if (!own_wgrad) {
+// Backward of one layer given dL/dy in `dy` (dtype T, channel stride g.CoutT), in two parts a caller can put on different lanes (only
+// the data gradient - the decoder chain - is on the critical path of the generator backward).  This one: the weight / bias gradients
+static int run_layer_wgrad(vp_pixrefer* h, Net& n, Layer& L, const void* dy, const Sub& sub, const Lane& ln) {
+  hipStream_t st = ln.s;
+  const int es = h->es, sample0 = sub.sample0, nb = sub.nb;
+  WgradArgs w = L.wg.a;
+  PixSrc xs;
+  fill_src(n, L, xs, n.batch / n.groups, sample0, es);
+  PixSrc ds;
+  set_single_src(ds, dy, L.g.CoutT, nullptr, nullptr, ACT_NONE, 0);
+  if (L.g.kind == 0) { w.g = xs; w.d = ds; } else { w.g = ds; w.d = xs; }
+  bool own_wgrad = false;
+  if (L.tapgemm && h->bf16 && cout1_knob() > 0 && L.nsrc == 1 && !n.t[L.src[0]].is_input && !n.t[L.src[0]].hi && n.t[L.src[0]].xa[L.in_act] &&
+      L.g.ks == 4 && L.g.stride == 1) {
+    // the one-output-channel layer's weight gradient on its own kernel (conv_cout1.hip): no tap spreading, no transposes
+    Tens& tx = n.t[L.src[0]];
+    Cout1Args c;
+    memset(&c, 0, sizeof(c));
+    c.dy = dy; c.ld_dy = L.g.CoutT;
+    c.ref = at_sample(tx, tx.xa[L.in_act], sample0, es);
+    c.N = nb; c.H = tx.H; c.W = tx.W; c.C = tx.C; c.Ho = L.g.Hout; c.Wo = L.g.Wout; c.ks = L.g.ks; c.pad = L.g.pad;
+    c.slabs = (float*)ln.scratch; c.dW = n.grads + L.w_off;
+    const long long px = (long long)nb * tx.H * tx.W;
+    const size_t cap = h->scratch_bytes / ((size_t)16 * 512 * sizeof(float));
+    c.rows = (int)(px / 96 < wgrad1_rows_knob() ? px / 96 : wgrad1_rows_knob());            // >= 24 pixels per wave
+    if ((size_t)c.rows > cap) c.rows = (int)cap;
+    if (c.rows >= 1 && L.g.Cin == 512 && conv_cout1_wgrad_eligible(c)) {
       profile_tag((L.scope + ":wgrad").c_str());
-      VP_HIP_CHECK(launch_wgrad(w, h->bf16, L.wg.cfg, st));
-    }
-    float* db = n.grads + L.b_off;
-    if (L.has_bn) {
-      // analytically zero: written by this layer's batch-norm backward (run_bn_bwd, dbias_zero) - no separate memset launch
-    } else {
-      BnArgs b;
-      memset(&b, 0, sizeof(b));
-      b.y = dy; b.C = L.g.CoutT; b.G = 1; b.Pg = nb * L.g.Hout * L.g.Wout;
-      b.nchunk = bn_nchunk(b.Pg, b.C, 1, h->bf16);
-      b.partial = bn_partial;
-      Tens& to = n.t[L.out];
-      if (to.cs_chunks > 0 && dy == to.dz) {     // the launch that completed dy left its column sums behind (conv_dc64.hip CSUM): finalize only
-        b.partial = to.cs_part; b.nchunk = to.cs_chunks;
-        to.cs_chunks = 0;
-        VP_HIP_CHECK(launch_colsum_tail(b, L.g.Cout, db, 0, st));
-      } else {
-        VP_HIP_CHECK(launch_colsum(b, L.g.Cout, db, 0, h->bf16, st));
-      }
+      VP_HIP_CHECK(launch_cout1_wgrad_prof(c, st));
+      own_wgrad = true;
     }
   }
-  // Backward sums of a batch-normalised tensor from the epilogue of the launch that completes its gradient (IgemmArgs::bst_*, staged_epilogue
-  // STATS == 2): the tensor's batch-norm backward then starts at its finalize - bn_reduce_kernel<T, 1> never re-reads y and dz.  `which`:
-  // output 0 / 1 of a two-output launch.  Not for tensors the one-launch batch-norm backward handles (<= 2048 pixels per group), not for
-  // launches on the few-pixel / register-resident-weights kernels (no such epilogue), not when a pixel tile would straddle two groups.
-  auto try_bst = [&](IgemmArgs& a, const IgemmPlan& p, Tens& ts, int which, bool last) {
-    if (!h->bst_on || !last || !ts.has_bn || ts.hi || ts.producer < 0 || ts.is_input) return;
-    const int groups = (gpass || alt) ? 1 : n.groups;
-    if ((nb / groups) * ts.H * ts.W <= 2048) return;                       // bn_small
-    if (a.y_f32 || a.ldY % 8 || a.Cout % 8 || a.ldY != ts.C) return;
-    // bwd_sums_in_epilogue = 1 (default): only where the A/B said it pays (profiles/r06_bwd_sums_per_layer.txt) - single-output launches of the
-    // 2x2-tap patch kernel and the plain implicit GEMM.  The sixteen accumulators do not fit beside the staged tile's registers in the
-    // 128-register kernels: on the two-output launches (decoder_1: 0.090 -> 0.178 ms), the 4x4 patch kernel (layer_4: +0.063 ms) and the
-    // 16-deep tap product of the generator-loss pass (layer_5: +0.010 ms against a 0.010 ms reduce) the spills cost as much or more than the reduce pass they replace.  2: every launch that can.
-    // Kernels with the staged epilogue: the plain implicit GEMM, the 2x2-tap patch kernel (single source) and the 4x4 patch kernel.
-    if (h->bst_on < 2 && (a.split_c || conv_staging(a.kern) == CK_PATCH || (L.tapgemm && gpass))) return;
-    if (a.kern != CK_IGEMM && a.kern != CK_PATCH4 && !(a.kern == CK_PATCH2 && a.x.C[1] == 0)) return;
-    const int chunks = epi_stat_chunks(p, nb, groups);
-    if (chunks <= 0 || chunks > (gpass ? ts.pbg_cap : ts.pb_cap)) return;
-    double* part = gpass ? ts.bn.pbg : ts.bn.pb;
-    const void* y = (const char*)ts.y + (size_t)sample0 * ts.H * ts.W * ts.C * es;
-    if (which == 0) { a.bn_part = part; a.bst_y = y; }
-    else { a.bn_part2 = part; a.bst_y2 = y; }
-    a.bn_tpg = chunks / a.nclass; a.bn_nchunk = chunks;
-    (gpass ? ts.bst_chunks_g : ts.bst_chunks) = chunks;
-    h->bst_count++;
-  };
+  if (L.tapgemm && !own_wgrad) {
+    TapArgs ta;
+    memset(&ta, 0, sizeof(ta));
+    ta.dy = dy; ta.dyS = L.tap_dyS; ta.ld_dy = L.g.CoutT;
+    ta.N = nb; ta.Hin = L.g.Hin; ta.Win = L.g.Win; ta.Hout = L.g.Hout; ta.Wout = L.g.Wout; ta.ks = L.g.ks; ta.pad = L.g.pad;
+    VP_HIP_CHECK(launch_tap_spread(ta, h->bf16, st));
+    set_single_src(w.g, L.tap_dyS, 16, nullptr, nullptr, ACT_NONE, 0);
+    w.d = xs;
+  }
+  w.partial = (float*)ln.scratch;
+  w.dW = n.grads + L.w_off;
+  w.accumulate = 0;
+  w.zeros = h->zeros;
+  if (!own_wgrad) {
+    profile_tag((L.scope + ":wgrad").c_str());
+    VP_HIP_CHECK(launch_wgrad(w, h->bf16, L.wg.cfg, st));
+  }
+  float* db = n.grads + L.b_off;
+  if (L.has_bn) {
+    // analytically zero: written by this layer's batch-norm backward (run_bn_bwd, dbias_zero) - no separate memset launch
+  } else {
+    BnArgs b;
+    memset(&b, 0, sizeof(b));
+    b.y = dy; b.C = L.g.CoutT; b.G = 1; b.Pg = nb * L.g.Hout * L.g.Wout;
+    b.nchunk = bn_nchunk(b.Pg, b.C, 1, h->bf16);
+    b.partial = ln.bn_partial;
+    Tens& to = n.t[L.out];
+    if (to.cs_chunks > 0 && dy == to.dz) {     // the launch that completed dy left its column sums behind (conv_dc64.hip CSUM): finalize only
+      b.partial = to.cs_part; b.nchunk = to.cs_chunks;
+      to.cs_chunks = 0;
+      VP_HIP_CHECK(launch_colsum_tail(b, L.g.Cout, db, 0, st));
+    } else {
+      VP_HIP_CHECK(launch_colsum(b, L.g.Cout, db, 0, h->bf16, st));
+    }
+  }
+  return VP_OK;
+}
+
+// Backward sums of a batch-normalised tensor from the epilogue of the launch that completes its gradient (IgemmArgs::bst_*, staged_epilogue
+// STATS == 2): the tensor's batch-norm backward then starts at its finalize - bn_reduce_kernel<T, 1> never re-reads y and dz.  `which`:
+// output 0 / 1 of a two-output launch.  Not for tensors the one-launch batch-norm backward handles (<= 2048 pixels per group), not for
+// launches on the few-pixel / register-resident-weights kernels (no such epilogue), not when a pixel tile would straddle two groups.
+static void try_bst(vp_pixrefer* h, const Net& n, const Layer& L, const Sub& sub, IgemmArgs& a, const IgemmPlan& p, Tens& ts, int which, bool last) {
+  const bool gpass = sub.gpass;
+  if (!h->bst_on || !last || !ts.has_bn || ts.hi || ts.producer < 0 || ts.is_input) return;
+  const int groups = (gpass || sub.alt) ? 1 : n.groups;
+  if ((sub.nb / groups) * ts.H * ts.W <= 2048) return;                       // bn_small
+  if (a.y_f32 || a.ldY % 8 || a.Cout % 8 || a.ldY != ts.C) return;
+  // bwd_sums_in_epilogue = 1 (default): only where the A/B said it pays (profiles/r06_bwd_sums_per_layer.txt) - single-output launches of the
+  // 2x2-tap patch kernel and the plain implicit GEMM.  The sixteen accumulators do not fit beside the staged tile's registers in the
+  // 128-register kernels: on the two-output launches (decoder_1: 0.090 -> 0.178 ms), the 4x4 patch kernel (layer_4: +0.063 ms) and the
+  // 16-deep tap product of the generator-loss pass (layer_5: +0.010 ms against a 0.010 ms reduce) the spills cost as much or more than the reduce pass they replace.  2: every launch that can.
+  // Kernels with the staged epilogue: the plain implicit GEMM, the 2x2-tap patch kernel (single source) and the 4x4 patch kernel.
+  if (h->bst_on < 2 && (a.split_c || conv_staging(a.kern) == CK_PATCH || (L.tapgemm && gpass))) return;
+  if (a.kern != CK_IGEMM && a.kern != CK_PATCH4 && !(a.kern == CK_PATCH2 && a.x.C[1] == 0)) return;
+  const int chunks = epi_stat_chunks(p, sub.nb, groups);
+  if (chunks <= 0 || chunks > (gpass ? ts.pbg_cap : ts.pb_cap)) return;
+  double* part = gpass ? ts.bn.pbg : ts.bn.pb;
+  const void* y = at_sample(ts, ts.y, sub.sample0, h->es);
+  if (which == 0) { a.bn_part = part; a.bst_y = y; }
+  else { a.bn_part2 = part; a.bst_y2 = y; }
+  a.bn_tpg = chunks / a.nclass; a.bn_nchunk = chunks;
+  (gpass ? ts.bst_chunks_g : ts.bst_chunks) = chunks;
+  h->bst_count++;
+}
+
+// ... and this one: the data gradients, dz of every source tensor
+static int run_layer_dgrad(vp_pixrefer* h, Net& n, Layer& L, const void* dy, const Sub& sub, const Lane& ln) {
+  hipStream_t st = ln.s;
+  const int es = h->es, sample0 = sub.sample0, nb = sub.nb;
+  const bool alt = sub.alt, gpass = sub.gpass;
+  const int group_n = n.batch / n.groups;
   // few-pixel pairs: only the usual case - this launch is the LAST contribution to the first tensor (its batch-norm backward runs in
   // the launch) and NOT the last one to the second (the skip tensor's own encoder consumer comes later)
   const bool pair_sp = L.has_pair && L.bwd_pair.a.kern == CK_SMALLP;
   const bool pair_sp_ok = pair_sp && n.t[L.src[0]].has_bn && n.t[L.src[0]].dz_writes + 1 == n.t[L.src[0]].n_bwd_consumers &&
                           n.t[L.src[1]].dz_writes + 1 < n.t[L.src[1]].n_bwd_consumers;
-  if (L.has_pair && (parts & 6) == 6 && !alt && !gpass && (!pair_sp || pair_sp_ok)) {
+  if (L.has_pair && !alt && !gpass && (!pair_sp || pair_sp_ok)) {
     // both sources' data gradients in one two-output launch (Layer::bwd_pair)
     Tens &t0 = n.t[L.src[0]], &t1 = n.t[L.src[1]];
     IgemmArgs a = L.bwd_pair.a;
-    if (pair_sp) {
-      set_single_src(a.x, dy, L.g.CoutT, nullptr, nullptr, ACT_NONE, 0);
-      a.Wp = n.packed + L.pk_bwd_pair * es;
-      a.partial = (float*)scratch;
-      a.zeros = h->zeros;
-      a.ref = (const char*)t0.xa[L.in_act] + (size_t)sample0 * t0.H * t0.W * t0.C * es;
-      a.ref2 = (const char*)t1.xa[L.in_act] + (size_t)sample0 * t1.H * t1.W * t1.C * es;
-      a.ref_act = L.in_act;
-      a.ref_group_n = group_n;
-      a.Y = t0.hi ? t0.dz32 : t0.dz; a.accumulate = t0.dz_written ? 1 : 0;
-      a.Y2 = t1.hi ? t1.dz32 : t1.dz; a.accumulate2 = t1.dz_written ? 1 : 0; a.y2_f32 = t1.hi ? 1 : 0;
-      t0.dz_written = t1.dz_written = true;
-      t0.dz_writes++; t1.dz_writes++;
-      SmallPArgs sp;
-      memset(&sp, 0, sizeof(sp));
-      a.sp_cnt = L.sp_cnt_pair;
-      sp.g = a;
-      for (int c = 0; c < 4; ++c) sp.tap_mask[c] = a.sp_mask[c];
-      sp.slab = a.partial; sp.cnt = a.sp_cnt; sp.part = bn_partial;
-      const Layer& Lp = n.l[t0.producer];
-      sp.mode = SP_BWD_BN;
-      if (t0.hi) { sp.hi = 1; sp.dy_out = t0.dz; }
-      sp.bn_y = t0.y; sp.bn_mu = t0.bn.mu; sp.bn_rstd = t0.bn.rstd; sp.bn_gamma = n.params + Lp.gamma_off;
-      sp.c1 = t0.bn.c1; sp.c2 = t0.bn.c2;
-      sp.dgamma = n.grads + Lp.gamma_off; sp.dbeta = n.grads + Lp.beta_off; sp.dbias_zero = n.grads + Lp.b_off;
-      t0.bn_bwd_done = true;
-      profile_tag((L.scope + ":bwd").c_str());
-      VP_HIP_CHECK(launch_smallp_fused(sp, h->bf16, st));
-      return VP_OK;
-    }
     set_single_src(a.x, dy, L.g.CoutT, nullptr, nullptr, ACT_NONE, 0);
     a.Wp = n.packed + L.pk_bwd_pair * es;
-    a.partial = (float*)scratch;
+    a.partial = (float*)ln.scratch;
+    a.zeros = h->zeros;
     a.Y = t0.dz; a.accumulate = t0.dz_written ? 1 : 0;
     a.Y2 = t1.dz; a.accumulate2 = t1.dz_written ? 1 : 0;
-    t0.dz_written = t1.dz_written = true;
-    t0.dz_writes++; t1.dz_writes++;
-    a.ref = (const char*)t0.xa[L.in_act] + (size_t)sample0 * t0.H * t0.W * t0.C * es;
-    a.ref2 = (const char*)t1.xa[L.in_act] + (size_t)sample0 * t1.H * t1.W * t1.C * es;
+    a.ref = at_sample(t0, t0.xa[L.in_act], sample0, es);
+    a.ref2 = at_sample(t1, t1.xa[L.in_act], sample0, es);
     a.ref_act = L.in_act;
     a.ref_group_n = group_n;
-    a.zeros = h->zeros;
-    try_bst(a, L.bwd_pair, t0, 0, t0.dz_writes == t0.n_bwd_consumers);
-    try_bst(a, L.bwd_pair, t1, 1, t1.dz_writes == t1.n_bwd_consumers);
+    t0.dz_written = t1.dz_written = true;
+    t0.dz_writes++; t1.dz_writes++;
     profile_tag((L.scope + ":bwd").c_str());
-    VP_HIP_CHECK(launch_igemm(a, h->bf16, L.bwd_pair.cfg, st));
+    if (pair_sp) {
+      // float32 few-pixel tensors (Tens::hi) accumulate in dz32; the first one's batch-norm backward runs in the launch
+      if (t0.hi) a.Y = t0.dz32;
+      if (t1.hi) a.Y2 = t1.dz32;
+      a.y2_f32 = t1.hi ? 1 : 0;
+      SmallPArgs sp = smallp_args(a, L.sp_cnt_pair, ln);
+      smallp_bn_bwd(sp, n, t0);
+      VP_HIP_CHECK(launch_smallp_fused(sp, h->bf16, st));
+    } else {
+      try_bst(h, n, L, sub, a, L.bwd_pair, t0, 0, t0.dz_writes == t0.n_bwd_consumers);
+      try_bst(h, n, L, sub, a, L.bwd_pair, t1, 1, t1.dz_writes == t1.n_bwd_consumers);
+      VP_HIP_CHECK(launch_igemm(a, h->bf16, L.bwd_pair.cfg, st));
+    }
     return VP_OK;
   }
   for (int s = 0; s < L.nsrc; ++s) {
-    if (!(parts & (2 << s))) continue;
     if (!L.need_bwd[s]) continue;
     Tens& ts = n.t[L.src[s]];
     IgemmArgs a = alt ? L.bwd_alt[s].a : L.bwd[s].a;
     set_single_src(a.x, dy, L.g.CoutT, nullptr, nullptr, ACT_NONE, 0);
     a.Wp = n.packed + (alt ? L.pk_bwd_alt[s] : L.pk_bwd[s]) * es;
-    a.partial = (float*)scratch;
+    a.partial = (float*)ln.scratch;
     if (ts.is_input) {
       a.Y = (n.groups == 3) ? h->d_din : h->d_vin;
       a.accumulate = 0;
@@ -1050,7 +1071,7 @@ static int run_layer_bwd(vp_pixrefer* h, Net& n, Layer& L, const void* dy, bool 
       }
       // chain rule through the consumer's activation and (for BN tensors) up to the normalised value
       // lrelu'/relu' only depend on the sign of the pre-activation == the sign of the materialised x~
-      a.ref = (const char*)ts.xa[L.in_act] + (size_t)sample0 * ts.H * ts.W * ts.C * es;
+      a.ref = at_sample(ts, ts.xa[L.in_act], sample0, es);
       a.ref_act = L.in_act;
       a.ref_group_n = group_n;
     }
@@ -1058,25 +1079,13 @@ static int run_layer_bwd(vp_pixrefer* h, Net& n, Layer& L, const void* dy, bool 
     profile_tag((L.scope + (alt ? ":bwdG" : ":bwd")).c_str());
     if (a.kern == CK_SMALLP && !alt) {
       // few-pixel layer: K-split combine in the launch; when this is the last gradient contribution to a batch-normalised tensor, the
-      // batch-norm backward of that tensor (sums, c1 / c2, dgamma / dbeta, dy in place) runs in the same launch
-      SmallPArgs sp;
-      memset(&sp, 0, sizeof(sp));
-      a.sp_cnt = L.sp_cnt_bwd[s];
-      sp.g = a;
-      for (int c = 0; c < 4; ++c) sp.tap_mask[c] = a.sp_mask[c];
-      sp.slab = a.partial; sp.cnt = a.sp_cnt; sp.part = bn_partial;
+      // batch-norm backward of that tensor runs in the same launch
+      SmallPArgs sp = smallp_args(a, L.sp_cnt_bwd[s], ln);
       const bool last = !ts.is_input && !gpass && ts.has_bn && ts.producer >= 0 && ts.dz_writes == ts.n_bwd_consumers && n.groups == 1;
       if (ts.hi && !last && ts.dz_writes == ts.n_bwd_consumers) { set_err("%s: float32 tensor %s needs its batch-norm backward in the launch", L.scope.c_str(), ts.name.c_str()); return VP_ERR_STATE; }
       if (last) {
-        const Layer& Lp = n.l[ts.producer];
-        sp.mode = SP_BWD_BN;
-        if (ts.hi) { sp.hi = 1; sp.dy_out = ts.dz; sp.g.y_f32 = 0; }      // dz32 / y in float32, dL/dy out as T into dz
-        sp.bn_y = ts.y; sp.bn_mu = ts.bn.mu; sp.bn_rstd = ts.bn.rstd; sp.bn_gamma = n.params + Lp.gamma_off;
-        sp.c1 = ts.bn.c1; sp.c2 = ts.bn.c2;
-        sp.dgamma = n.grads + Lp.gamma_off; sp.dbeta = n.grads + Lp.beta_off; sp.dbias_zero = n.grads + Lp.b_off;
-        ts.bn_bwd_done = true;
-      } else {
-        sp.mode = SP_PLAIN;
+        smallp_bn_bwd(sp, n, ts);
+        if (ts.hi) sp.g.y_f32 = 0;       // (a plain contribution to a float32 tensor says so in g.y_f32, this mode in `hi`)
       }
       VP_HIP_CHECK(launch_smallp_fused(sp, h->bf16, st));
       continue;
@@ -1102,7 +1111,7 @@ static int run_layer_bwd(vp_pixrefer* h, Net& n, Layer& L, const void* dy, bool 
       if (c.rows > 512 / groups) c.rows = 512 / groups;          // 512 resident blocks in all (two per compute unit): three groups x 170 rows 0.059 ms, x 256 0.065
       if (sums && c.rows > cap) c.rows = cap;
       if ((long long)nb * ts.H * ts.W < 16384 || c.rows < 1) c.rows = 0;
-      if (sums) { c.part = gpass ? ts.bn.pbg : ts.bn.pb; c.y = (const char*)ts.y + (size_t)sample0 * ts.H * ts.W * ts.C * es; }
+      if (sums) { c.part = gpass ? ts.bn.pbg : ts.bn.pb; c.y = at_sample(ts, ts.y, sample0, es); }
       if (tiles > 0 && c.rows > 0 && conv_cout1_bwd_eligible(c)) {
         if (sums) { (gpass ? ts.bst_chunks_g : ts.bst_chunks) = c.rows; h->bst_count++; }
         VP_HIP_CHECK(launch_cout1_bwd_prof(c, st));
@@ -1117,25 +1126,33 @@ static int run_layer_bwd(vp_pixrefer* h, Net& n, Layer& L, const void* dy, bool 
       ts.cs_chunks = conv_dc64_grid(a);
     }
     // (the discriminator's tensors have one consumer each and no write counter: every gradient launch completes its tensor)
-    if (!ts.is_input) try_bst(a, alt ? L.bwd_alt[s] : L.bwd[s], ts, 0, (gpass || n.groups != 1) ? true : ts.dz_writes == ts.n_bwd_consumers);
+    if (!ts.is_input) try_bst(h, n, L, sub, a, alt ? L.bwd_alt[s] : L.bwd[s], ts, 0, (gpass || n.groups != 1) ? true : ts.dz_writes == ts.n_bwd_consumers);
     VP_HIP_CHECK(launch_igemm(a, h->bf16, alt ? L.bwd_alt[s].cfg : L.bwd[s].cfg, st));
   }
   return VP_OK;
 }
 
-// dz -> dy through the training-mode batch norm of tensor t (in place), + dgamma/dbeta
-static int run_bn_bwd(vp_pixrefer* h, Net& n, Layer& L, bool want_dw, int sample0, int nb, int group0, int ng, hipStream_t st,
-                      int ss = 0, bool gpass = false) {
+static int run_layer_bwd(vp_pixrefer* h, Net& n, Layer& L, const void* dy, bool want_dw, const Sub& sub, const Lane& ln) {
+  int rc;
+  if (want_dw && (rc = run_layer_wgrad(h, n, L, dy, sub, ln))) return rc;
+  return run_layer_dgrad(h, n, L, dy, sub, ln);
+}
+
+// dz -> dy through the training-mode batch norm of tensor t (in place), + dgamma/dbeta.  group0 / ng: the first batch-norm group of
+// the samples `sub` and how many they span
+static int run_bn_bwd(vp_pixrefer* h, Net& n, Layer& L, bool want_dw, const Sub& sub, int group0, int ng, const Lane& ln) {
+  hipStream_t st = ln.s;
+  const bool gpass = sub.gpass;
   Tens& t = n.t[L.out];
   if (!gpass && t.bn_bwd_done) { t.bn_bwd_done = false; return VP_OK; }   // done inside the last gradient contribution's launch (conv_smallp.hip)
   if (t.hi) { set_err("%s: the batch-norm backward of a float32 few-pixel tensor runs inside the few-pixel launch only", L.scope.c_str()); return VP_ERR_STATE; }
   BnArgs b;
   memset(&b, 0, sizeof(b));
-  b.y = (const char*)t.y + (size_t)sample0 * t.H * t.W * t.C * h->es;
+  b.y = at_sample(t, t.y, sub.sample0, h->es);
   b.dy = gpass ? t.dz2 : t.dz; b.dz = b.dy;
-  b.C = t.C; b.G = ng; b.Pg = (nb / ng) * t.H * t.W;
+  b.C = t.C; b.G = ng; b.Pg = (sub.nb / ng) * t.H * t.W;
   b.nchunk = bn_nchunk(b.Pg, b.C, b.G, h->bf16);
-  b.partial = bnp_of(h, ss);
+  b.partial = ln.bn_partial;
   b.gamma = n.params + L.gamma_off;
   b.mu = t.bn.mu + (size_t)group0 * t.C; b.rstd = t.bn.rstd + (size_t)group0 * t.C;
   b.c1 = gpass ? t.bn.c1g : t.bn.c1; b.c2 = gpass ? t.bn.c2g : t.bn.c2;
@@ -1151,6 +1168,95 @@ static int run_bn_bwd(vp_pixrefer* h, Net& n, Layer& L, bool want_dw, int sample
   }
   if (bn_small(b)) { VP_HIP_CHECK(launch_bn_small_bwd(b, h->bf16, st)); return VP_OK; }
   VP_HIP_CHECK(launch_bn_bwd(b, h->bf16, st));
+  return VP_OK;
+}
+
+// Forward of the VGG trunk on one lane.  half == -1: the whole [real | fake] batch (Layer::fwd); 0 / 1: that half (Layer::fwd_half).
+// conv1_2 / conv2_2 write their 2x2 max pool from the epilogue where the plan's kernel can (a maxpool launch otherwise).  The real half
+// has no backward pass: of those two layers only the pooled image is ever read, the full-resolution store is skipped.  The fake half
+// skips it when `codes` holds, and records the pool's arg-max codes for the backward pass instead
+static int vgg_forward(vp_pixrefer* h, int half, const Lane& ln, bool codes) {
+  Net& V = h->V;
+  const int N = h->d.batch, s0 = half > 0 ? N : 0;
+  int rc;
+  for (Layer& L : V.l) {
+    const bool fuse = L.pool >= 0 && plan_can_pool(half < 0 ? L.fwd : L.fwd_half);
+    const Tens& ti = V.t[L.out];
+    void* pool_y = L.pool >= 0 ? at_sample(V.t[L.pool_t], V.t[L.pool_t].y, s0, h->es) : nullptr;
+    if (half < 0) {
+      rc = run_layer_fwd(h, V, L, ln, fuse ? pool_y : nullptr);
+    } else {
+      const bool code = fuse && codes && half == 1;
+      rc = run_layer_fwd_half(h, V, L, half, ln, fuse ? pool_y : nullptr, half == 0 || code, code ? h->vpool_code[L.pool] : nullptr);
+    }
+    if (rc) return rc;
+    if (L.pool >= 0 && !fuse) VP_HIP_CHECK(launch_maxpool_fwd(at_sample(ti, ti.y, s0, h->es), pool_y, half < 0 ? ti.N : N, ti.H, ti.W, ti.C, h->bf16, ln.s));
+  }
+  return VP_OK;
+}
+
+// Generator-loss pass, GAN term: through the fake application of the discriminator (dX only, pre-update weights)
+static int discriminator_gpass(vp_pixrefer* h, const Lane& ln) {
+  Net& D = h->D;
+  const int N = h->d.batch;
+  const Sub fake{2 * N, N, true, true};
+  int rc;
+  for (Tens& t : D.t) { t.dz2_written = false; t.bst_chunks_g = 0; }
+  for (int i = (int)D.l.size() - 1; i >= 0; --i) {
+    Layer& L = D.l[i];
+    if (L.has_bn) if ((rc = run_bn_bwd(h, D, L, false, fake, 2, 1, ln))) return rc;
+    const void* dy = (i == (int)D.l.size() - 1) ? h->dl_g : D.t[L.out].dz2;
+    if ((rc = run_layer_bwd(h, D, L, dy, false, fake, ln))) return rc;
+  }
+  return VP_OK;
+}
+
+// Generator-loss pass, perceptual term: through the VGG trunk, fake half only (dX only: VGG is frozen)
+static int vgg_backward(vp_pixrefer* h, const Lane& ln) {
+  Net& V = h->V;
+  const int N = h->d.batch, bf = h->bf16, es = h->es;
+  for (Tens& t : V.t) t.dz_written = false;
+  h->pool_bwd_fused = false;
+  h->pool_dz_stale[0] = h->pool_dz_stale[1] = false;
+  for (int i = (int)V.l.size() - 1; i >= 0; --i) {
+    Layer& L = V.l[i];
+    Tens& to = V.t[L.out];
+    Tens& ti = V.t[L.src[0]];
+    // dz of a conv output here is already w.r.t. the pre-relu value (perceptual seed / epilogue / pool bwd)
+    IgemmArgs a = L.bwd_alt[0].a;
+    set_single_src(a.x, to.dz, L.g.CoutT, nullptr, nullptr, ACT_NONE, 0);
+    if (L.pool >= 0 && h->pool_dz_stale[L.pool]) {
+      // the pool behind this conv left its gradient unexpanded (below): the launch reads the pooled gradient and the codes
+      a.x.ptr[0] = V.t[L.pool_t].dz;
+      a.pool_code = h->vpool_code[L.pool];
+      a.pool_src = 1;
+    }
+    a.Wp = V.packed + L.pk_bwd_alt[0] * es;
+    a.partial = (float*)ln.scratch;
+    if (ti.is_input) {
+      a.Y = h->d_vin;
+    } else {
+      a.Y = ti.dz;
+      if (ti.pool < 0) {   // producer is a conv+relu: multiply by relu'(stored output of the fake half)
+        a.ref = (const char*)ti.y + ti.elems() / 2 * es;
+        a.ref_act = ACT_RELU;
+      }
+    }
+    a.zeros = h->zeros;
+    profile_tag((L.scope + ":bwd").c_str());
+    VP_HIP_CHECK(launch_igemm(a, bf, L.bwd_alt[0].cfg, ln.s));
+    if (ti.pool >= 0) {
+      Tens& tc = V.t[ti.pool_src];      // the conv tensor under the pool
+      const char* xin = (const char*)tc.y + tc.elems() / 2 * es;
+      const int k = ti.pool;
+      if (h->pool_codes_written && h->pool_fuse_ok[k]) {
+        // the conv below the pool expands the gradient in its loader (the next trip of this loop): nothing to launch, tc.dz stays unwritten
+        h->pool_dz_stale[k] = true;
+        h->pool_bwd_fused = true;
+      } else if (h->pool_codes_written) VP_HIP_CHECK(launch_maxpool_bwd_code(h->vpool_code[k], ti.dz, tc.dz, N, tc.H, tc.W, tc.C, bf, ln.s));
+      else VP_HIP_CHECK(launch_maxpool_bwd(xin, ti.dz, tc.dz, N, tc.H, tc.W, tc.C, bf, ln.s));
+    }
+  }
   return VP_OK;
 }
 
@@ -1265,7 +1371,7 @@ int vp_pixrefer_validate_plan(const vp_pixrefer_desc* d) {
     if (n->t.empty()) continue;
     for (const Tens& t : n->t) {
       const std::string nm = t.name;
-      if (t.name == "decoder_1" || t.name == "layer_5") continue;       // thin f32 outputs live in handle-level buffers (checked below)
+      if (t.is_f32) continue;       // thin f32 outputs live in handle-level buffers (checked below)
       region_of(t.y, t.elems() * (t.hi ? 4 : es), (nm + ".y").c_str());
       for (int k = 1; k < 3; ++k) if (t.need_act[k]) region_of(t.xa[k], t.elems() * es, (nm + ".xa").c_str());
       if (t.has_bn) {
@@ -1318,7 +1424,12 @@ int vp_pixrefer_validate_plan(const vp_pixrefer_desc* d) {
   region_of(h->gin, px * 8 * es, "gin"); region_of(h->gfg, px * 8 * es, "gfg");
   region_of(h->y4, px * 4 * 4, "y4"); region_of(h->o4, px * 4 * 4, "o4");
   region_of(h->outputs, px * 3 * 4, "outputs"); region_of(h->outputs_fg, px * 3 * 4, "outputs_fg");
-  region_of(h->scratch, h->scratch_bytes, "scratch"); region_of(h->bn_partial, (size_t)1024 * 2 * 512 * 8, "bn_partial");
+  static const char* const lane_scratch[4] = {"scratch", "scratch2", "scratch3", "scratch4"};
+  static const char* const lane_bnp[4] = {"bn_partial", "bn_partial2", "bn_partial3", "bn_partial4"};
+  for (int k = 0; k < (d->training ? 4 : 1); ++k) {
+    region_of(h->lane[k].scratch, h->scratch_bytes, lane_scratch[k]);
+    region_of(h->lane[k].bn_partial, (size_t)1024 * 2 * 512 * 8, lane_bnp[k]);
+  }
   if (d->training) {
     const int hd = d->height / 8 - 2;
     const size_t M = (size_t)d->batch * hd * hd;
@@ -1326,24 +1437,18 @@ int vp_pixrefer_validate_plan(const vp_pixrefer_desc* d) {
     region_of(h->logits, 3 * M * 4, "logits"); region_of(h->predict, 2 * M * 4, "predict");
     region_of(h->dl_d, 3 * M * 8 * es, "dl_d"); region_of(h->dl_g, M * 8 * es, "dl_g");
     region_of(h->d_din, px * 8 * es, "d_din"); region_of(h->d_vin, px * 8 * es, "d_vin"); region_of(h->dy4, px * 8 * es, "dy4");
-    for (const Tens& t : h->V.t) {
-      if (t.name == "pool1") region_of(h->vpool_code[0], t.elems() / 2, "pool1 codes");
-      if (t.name == "pool2") region_of(h->vpool_code[1], t.elems() / 2, "pool2 codes");
-    }
+    for (const Tens& t : h->V.t) if (t.pool >= 0) region_of(h->vpool_code[t.pool], t.elems() / 2, (t.name + " codes").c_str());
     // the pooled-source backward-data launches: the plan's kernel takes that form, and what its loader reads instead of the conv's own
     // gradient - the fake half of the pool's gradient and one code byte per element of it - is carved
     for (const Layer& L : h->V.l) {
-      const int k = L.scope == "conv2/conv2_2";
-      if ((L.scope != "conv1/conv1_2" && !k) || !h->pool_fuse_ok[k]) continue;
-      const Tens& tp = h->V.t[L.out + 1];
-      if (tp.name != (k ? "pool2" : "pool1") || tp.H * 2 != h->V.t[L.out].H || tp.C != h->V.t[L.out].C) fail("%s: the tensor behind it is not its 2x2 pool", L.scope.c_str());
+      const int k = L.pool;
+      if (k < 0 || !h->pool_fuse_ok[k]) continue;
+      const Tens& tp = h->V.t[L.pool_t];
+      if (tp.pool != k || tp.pool_src != L.out || tp.H * 2 != h->V.t[L.out].H || tp.C != h->V.t[L.out].C) fail("%s: the tensor behind it is not its 2x2 pool", L.scope.c_str());
       if (L.bwd_alt[0].a.kern != CK_C64 || !conv_kernel_ok(pool_fused_view(L.bwd_alt[0]), h->bf16)) fail("%s bwd_alt: no pooled-source form of kernel %s", L.scope.c_str(), conv_kernel_name(L.bwd_alt[0].a.kern));
       region_of(tp.dz, tp.elems() / 2 * es, (tp.name + ".dz (pooled-source read)").c_str());
       region_of(h->vpool_code[k], tp.elems() / 2, (tp.name + " codes (pooled-source read)").c_str());
     }
-    region_of(h->scratch2, h->scratch_bytes, "scratch2"); region_of(h->scratch3, h->scratch_bytes, "scratch3");
-    region_of(h->scratch4, h->scratch_bytes, "scratch4"); region_of(h->bn_partial4, (size_t)1024 * 2 * 512 * 8, "bn_partial4");
-    region_of(h->bn_partial2, (size_t)1024 * 2 * 512 * 8, "bn_partial2"); region_of(h->bn_partial3, (size_t)1024 * 2 * 512 * 8, "bn_partial3");
   }
   delete h;
   return rc;
@@ -1409,10 +1514,10 @@ int vp_pixrefer_create(const vp_pixrefer_desc* d, void* workspace, size_t worksp
   h->D.params = params_d; h->D.grads = grads_d;
   h->V.params = const_cast<float*>(params_vgg);
   // thin f32 outputs
-  for (Tens& t : h->G.t) if (t.name == "decoder_1") { t.y = h->y4; t.dz = h->dy4; }
+  for (Tens& t : h->G.t) if (t.is_f32) { t.y = h->y4; t.dz = h->dy4; }
   hipStream_t st = (hipStream_t)stream;
   VP_HIP_CHECK(hipMemsetAsync(h->zeros, 0, 256, st));
-  if (d->training) for (Tens& t : h->D.t) if (t.name == "layer_5") { t.y = h->logits; t.dz = h->dl_d; }
+  if (d->training) for (Tens& t : h->D.t) if (t.is_f32) { t.y = h->logits; t.dz = h->dl_d; }
   for (Net* n : {&h->G, &h->D, &h->V}) {
     if (n->descs.empty()) continue;
     VP_HIP_CHECK(hipMemcpyAsync(n->d_descs, n->descs.data(), n->descs.size() * sizeof(PackDesc), hipMemcpyHostToDevice, st));
@@ -1425,7 +1530,7 @@ int vp_pixrefer_create(const vp_pixrefer_desc* d, void* workspace, size_t worksp
   h->ov_on = true; h->store_first_raw = false; h->dfork_point = d->d_backward_fork ? d->d_backward_fork - 1 : 2; h->dsplit_on = d->d_beside_vgg != 1;
   if (d->training && d->streams != 1) {
     // the process-wide executor streams (StreamPool above); the fourth one on first use unless vp_reserve_streams() made it already
-    { const int rc = pool_streams(false, &h->side, &h->branch, &h->branch2); if (rc) { delete h; return rc; } }
+    { const int rc = pool_streams(false, &h->lane[LANE_SIDE].s, &h->lane[LANE_BRANCH].s, &h->lane[LANE_BRANCH2].s); if (rc) { delete h; return rc; } }
     VP_HIP_CHECK(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
     VP_HIP_CHECK(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
     h->use_b2 = d->streams != 3;
@@ -1445,16 +1550,8 @@ void vp_pixrefer_destroy(vp_pixrefer_t* h) {
   if (h->marks_made) for (int i = 0; i < 64; ++i) (void)hipEventDestroy(h->mark[i]);
   if (h->overlap) {
     // the streams belong to the process (StreamPool): this plan's work on them is waited for, they live on
-    (void)hipStreamSynchronize(h->side);
-    (void)hipEventDestroy(h->ev_fork);
-    (void)hipEventDestroy(h->ev_join);
-    (void)hipStreamSynchronize(h->branch);
-    (void)hipEventDestroy(h->ev_bfork);
-    (void)hipEventDestroy(h->ev_bjoin);
-    (void)hipEventDestroy(h->ev_b2join);
-    if (h->branch2) (void)hipStreamSynchronize(h->branch2);
-    (void)hipEventDestroy(h->ev_upd_b);
-    (void)hipEventDestroy(h->ev_upd_m);
+    for (int k = LANE_SIDE; k <= LANE_BRANCH2; ++k) if (h->lane[k].s) (void)hipStreamSynchronize(h->lane[k].s);
+    for (hipEvent_t ev : {h->ev_fork, h->ev_join, h->ev_bfork, h->ev_bjoin, h->ev_b2join, h->ev_upd_b, h->ev_upd_m}) (void)hipEventDestroy(ev);
   }
   delete h;
 }
@@ -1492,7 +1589,9 @@ static int forward_impl(vp_pixrefer_t* h, const float* inputs, const float* fg_i
   if (!h || !inputs || !fg_inputs || !targets) { set_err("vp_pixrefer_forward: null argument"); return VP_ERR_ARG; }
   const vp_pixrefer_desc& d = h->d;
   if (d.training && !masks) { set_err("vp_pixrefer_forward: masks required when training"); return VP_ERR_ARG; }
-  hipStream_t st = (hipStream_t)stream;
+  const Lane me = caller_lane(h, stream);
+  const Lane &side = h->lane[LANE_SIDE], &branch = h->lane[LANE_BRANCH];
+  hipStream_t st = me.s;
   const int N = d.batch, H = d.height, bf = h->bf16;
   int rc;
   if (h->params_dirty) {
@@ -1517,46 +1616,34 @@ static int forward_impl(vp_pixrefer_t* h, const float* inputs, const float* fg_i
   if (split_vgg) for (Layer& L : h->V.l) split_vgg = split_vgg && L.has_fwd_half;
   // (vp_pixrefer_set_option("vgg_real_fork", k): the side stream starts it in front of generator layer k instead of at once - the
   // encoders then share the device with one stream less and the real half fills the few-pixel section of the generator: EXPERIMENTS.md)
+  bool vgg_real_pending = split_vgg;
   auto vgg_real_half = [&]() -> int {
-    VP_HIP_CHECK(hipEventRecord(h->ev_fork, st));
-    VP_HIP_CHECK(hipStreamWaitEvent(h->side, h->ev_fork, 0));
-    Net& Vs = h->V;
-    for (size_t i = 0; i < Vs.l.size(); ++i) {
-      Layer& L = Vs.l[i];
-      const bool pooled = L.scope == "conv1/conv1_2" || L.scope == "conv2/conv2_2";
-      const bool fuse = pooled && plan_can_pool(L.fwd_half);
-      // the real half has no backward pass: of conv1_2 / conv2_2 only the pooled image is ever read, the full-resolution store is skipped
-      if ((rc = run_layer_fwd_half(h, Vs, L, 0, h->side, fuse ? Vs.t[L.out + 1].y : nullptr, true))) return rc;
-      if (pooled && !fuse) {
-        const Tens& ti = Vs.t[L.out];
-        Tens& tp = Vs.t[L.out + 1];
-        VP_HIP_CHECK(launch_maxpool_fwd(ti.y, tp.y, N, ti.H, ti.W, ti.C, bf, h->side));
-      }
-    }
-    VP_HIP_CHECK(hipEventRecord(h->ev_join, h->side));
+    vgg_real_pending = false;
+    if ((rc = after(h->ev_fork, st, side.s))) return rc;
+    if ((rc = vgg_forward(h, 0, side, false))) return rc;
+    VP_HIP_CHECK(hipEventRecord(h->ev_join, side.s));
     return VP_OK;
   };
-  bool vgg_real_started = false;
-  if (split_vgg && h->vgg_fork_layer <= 0) { if ((rc = vgg_real_half())) return rc; vgg_real_started = true; }
+  if (vgg_real_pending && h->vgg_fork_layer <= 0 && (rc = vgg_real_half())) return rc;
 
   // generator: the two encoder branches (encoder_1..4 on `inputs`, encoder_fg_1..4 on `fg_inputs`, pixrefer.py:169-213) are
   // independent chains of small kernels until merged_encoder_2: the foreground branch runs on the branch stream
   const bool split_enc = d.training && h->overlap && h->ov_on;
   if (split_enc) {
-    VP_HIP_CHECK(hipEventRecord(h->ev_bfork, st));
-    VP_HIP_CHECK(hipStreamWaitEvent(h->branch, h->ev_bfork, 0));
-    for (Layer& L : h->G.l) if (L.scope.rfind("encoder_fg_", 0) == 0) if ((rc = run_layer_fwd(h, h->G, L, h->branch, nullptr, 2))) return rc;
-    VP_HIP_CHECK(hipEventRecord(h->ev_bjoin, h->branch));
+    if ((rc = after(h->ev_bfork, st, branch.s))) return rc;
+    for (Layer& L : h->G.l) if (L.fg) if ((rc = run_layer_fwd(h, h->G, L, branch))) return rc;
+    VP_HIP_CHECK(hipEventRecord(h->ev_bjoin, branch.s));
   }
-  for (Layer& L : h->G.l) {
-    if (split_enc && L.scope.rfind("encoder_fg_", 0) == 0) continue;
-    if (split_enc && L.scope == "merged_encoder_2") VP_HIP_CHECK(hipStreamWaitEvent(st, h->ev_bjoin, 0));
-    if (split_vgg && !vgg_real_started && (int)(&L - &h->G.l[0]) >= h->vgg_fork_layer) { if ((rc = vgg_real_half())) return rc; vgg_real_started = true; }
-    if (g_phase_detail) phase_mark(h, st, 8 + (int)(&L - &h->G.l[0]));          // per-layer marks: [8 + layer] = before the layer's forward
-    if ((rc = run_layer_fwd(h, h->G, L, st))) return rc;
+  for (int i = 0; i < (int)h->G.l.size(); ++i) {
+    Layer& L = h->G.l[i];
+    if (split_enc && L.fg) continue;
+    if (split_enc && i == h->G.i_me2) VP_HIP_CHECK(hipStreamWaitEvent(st, h->ev_bjoin, 0));
+    if (vgg_real_pending && i >= h->vgg_fork_layer && (rc = vgg_real_half())) return rc;
+    if (g_phase_detail) phase_mark(h, st, 8 + i);          // per-layer marks: [8 + layer] = before the layer's forward
+    if ((rc = run_layer_fwd(h, h->G, L, me))) return rc;
   }
 
-  if (split_vgg && !vgg_real_started) { if ((rc = vgg_real_half())) return rc; vgg_real_started = true; }
+  if (vgg_real_pending && (rc = vgg_real_half())) return rc;
   CompositeArgs ca;
   memset(&ca, 0, sizeof(ca));
   ca.y4 = h->y4; ca.targets = targets; ca.masks = masks; ca.o4 = h->o4; ca.outputs = h->outputs; ca.outputs_fg = h->outputs_fg;
@@ -1568,62 +1655,29 @@ static int forward_impl(vp_pixrefer_t* h, const float* inputs, const float* fg_i
   // discriminator on [real1 | real2 | fake] (pixrefer.py:295-306).  It and the fake half of the VGG trunk both hang off the
   // composite only: the discriminator (conv + batch-norm glue, HBM-bound in between) runs on the branch stream under the VGG convs
   const bool split_d = h->overlap && h->ov_on && h->dsplit_on;
-  hipStream_t sd = split_d ? h->branch : st;
-  const int ssd = split_d ? 2 : 0;
-  if (split_d) {
-    VP_HIP_CHECK(hipEventRecord(h->ev_bfork, st));
-    VP_HIP_CHECK(hipStreamWaitEvent(h->branch, h->ev_bfork, 0));
-  }
-  for (Layer& L : h->D.l) if ((rc = run_layer_fwd(h, h->D, L, sd, nullptr, ssd))) return rc;
+  const Lane& ld = split_d ? branch : me;
+  if (split_d && (rc = after(h->ev_bfork, st, branch.s))) return rc;
+  for (Layer& L : h->D.l) if ((rc = run_layer_fwd(h, h->D, L, ld))) return rc;
   const int hd = H / 8 - 2;
   GanLossArgs ga;
   memset(&ga, 0, sizeof(ga));
   ga.logits = h->logits; ga.dl_d = h->dl_d; ga.dl_g = h->dl_g; ga.predict = h->predict; ga.losses = h->losses;
   ga.M = N * hd * hd; ga.gan_weight = d.gan_weight;
-  VP_HIP_CHECK(launch_gan_loss(ga, bf, sd));
-  if (split_d) VP_HIP_CHECK(hipEventRecord(h->ev_bjoin, h->branch));
+  VP_HIP_CHECK(launch_gan_loss(ga, bf, ld.s));
+  if (split_d) VP_HIP_CHECK(hipEventRecord(h->ev_bjoin, branch.s));
 
   // VGG trunk on [real fg | Outputs_FG] (pixrefer.py:321).  The real half does not depend on the generator: when every layer has
-  // a half-batch plan it was started on the side stream right after pack_inputs (below, `vgg_half`) and only the fake half runs here
+  // a half-batch plan it was started on the side stream (above, `vgg_real_half`) and only the fake half runs here
   Net& V = h->V;
   // The fake half of conv1_2 / conv2_2: after the fused pool only the pool's backward pass reads the full-resolution output, and only for
   // the first arg-max of a window and the sign of its maximum.  The epilogue records that as one byte per pooled element and the output
   // is not stored (as for the real half).  bf16 plans whose two layers can fuse the pool; store_first_raw = 1 keeps the stored tensors
   bool codes = split_vgg && bf && !h->store_first_raw && h->vpool_code[0] && h->vpool_code[1];
   for (Layer& L : V.l)
-    if (L.scope == "conv1/conv1_2" || L.scope == "conv2/conv2_2") codes = codes && plan_can_pool(L.fwd_half);
+    if (L.pool >= 0) codes = codes && plan_can_pool(L.fwd_half);
   h->pool_codes_written = codes;
-  auto vgg_half = [&](int half, hipStream_t s2) -> int {
-    for (size_t i = 0; i < V.l.size(); ++i) {
-      Layer& L = V.l[i];
-      int rc2;
-      const bool pooled = L.scope == "conv1/conv1_2" || L.scope == "conv2/conv2_2";
-      const bool fuse = pooled && plan_can_pool(L.fwd_half);
-      const Tens& ti = V.t[L.out];
-      Tens& tp = V.t[pooled ? L.out + 1 : L.out];   // pool tensor follows in creation order
-      const size_t oi = (size_t)half * N * ti.H * ti.W * ti.C * h->es, op = (size_t)half * N * tp.H * tp.W * tp.C * h->es;
-      const bool code = fuse && codes && half == 1;
-      if ((rc2 = run_layer_fwd_half(h, V, L, half, s2, fuse ? (char*)tp.y + op : nullptr, code, code ? h->vpool_code[L.scope == "conv2/conv2_2"] : nullptr))) return rc2;
-      if (pooled && !fuse) VP_HIP_CHECK(launch_maxpool_fwd((const char*)ti.y + oi, (char*)tp.y + op, N, ti.H, ti.W, ti.C, bf, s2));
-    }
-    return VP_OK;
-  };
-  if (split_vgg) {
-    if ((rc = vgg_half(1, st))) return rc;
-    VP_HIP_CHECK(hipStreamWaitEvent(st, h->ev_join, 0));      // the real half (side stream) is complete
-  } else {
-    for (size_t i = 0; i < V.l.size(); ++i) {
-      Layer& L = V.l[i];
-      const bool pooled = L.scope == "conv1/conv1_2" || L.scope == "conv2/conv2_2";
-      const bool fuse = pooled && plan_can_pool(L.fwd);
-      if ((rc = run_layer_fwd(h, V, L, st, fuse ? V.t[L.out + 1].y : nullptr))) return rc;
-      if (pooled && !fuse) {
-        const Tens& ti = V.t[L.out];
-        Tens& tp = V.t[L.out + 1];   // pool tensor follows in creation order
-        VP_HIP_CHECK(launch_maxpool_fwd(ti.y, tp.y, ti.N, ti.H, ti.W, ti.C, bf, st));
-      }
-    }
-  }
+  if ((rc = vgg_forward(h, split_vgg ? 1 : -1, me, codes))) return rc;
+  if (split_vgg) VP_HIP_CHECK(hipStreamWaitEvent(st, h->ev_join, 0));      // the real half (side stream) is complete
   const Tens& f3 = V.t.back();
   PerceptualArgs pa;
   memset(&pa, 0, sizeof(pa));
@@ -1641,8 +1695,23 @@ static int forward_impl(vp_pixrefer_t* h, const float* inputs, const float* fg_i
   return VP_OK;
 }
 
-static int backward_d_on(vp_pixrefer_t* h, hipStream_t st, bool side);
+static int backward_d_on(vp_pixrefer_t* h, const Lane& ln);
 static int fork_d(vp_pixrefer_t* h, hipStream_t st);
+
+// tf.train.AdamOptimizer's step size at step t
+static float adam_lr_t(float lr, float beta1, float beta2, int t) {
+  return (float)((double)lr * sqrt(1.0 - pow((double)beta2, t)) / (1.0 - pow((double)beta1, t)));
+}
+
+// Bucket 0 .. 2 of the generator's arenas = what stage `bucket` of the backward pass completes (vp_pixrefer_backward_g_stage): its
+// layers l0 .. l1 and their range [off0, off1) of the flat parameter / gradient arena
+static void bucket_range(const Net& G, int bucket, int* l0, int* l1, size_t* off0, size_t* off1) {
+  const int last = (int)G.l.size() - 1;
+  *l0 = bucket == 0 ? G.i_md5 : (bucket == 1 ? G.i_me2 : 0);
+  *l1 = bucket == 0 ? last : (bucket == 1 ? G.i_md5 - 1 : G.i_me2 - 1);
+  *off0 = G.l[*l0].w_off;
+  *off1 = *l1 < last ? G.l[*l1 + 1].w_off : G.nparams;
+}
 
 // tf.train.AdamOptimizer on the arena range [off0, off1) of a net (= its layers l0 .. l1) followed by the re-pack of those layers'
 // weights for the next step, both on stream s
@@ -1688,14 +1757,14 @@ int vp_pixrefer_backward(vp_pixrefer_t* h, void* stream) {
 }
 
 static int fork_d(vp_pixrefer_t* h, hipStream_t st) {
+  const Lane& side = h->lane[LANE_SIDE];
   h->dfork_pending = 0;
-  VP_HIP_CHECK(hipEventRecord(h->ev_fork, st));
-  VP_HIP_CHECK(hipStreamWaitEvent(h->side, h->ev_fork, 0));
-  int rc = backward_d_on(h, h->side, true);
+  int rc = after(h->ev_fork, st, side.s);
   if (rc) return rc;
+  if ((rc = backward_d_on(h, side))) return rc;
   // forked behind the generator-loss pass through the discriminator (point 2): nobody reads the discriminator's weights any more
-  if (h->upd.active && h->dfork_point == 2 && (rc = update_d(h, h->side))) return rc;
-  VP_HIP_CHECK(hipEventRecord(h->ev_join, h->side));
+  if (h->upd.active && h->dfork_point == 2 && (rc = update_d(h, side.s))) return rc;
+  VP_HIP_CHECK(hipEventRecord(h->ev_join, side.s));
   return VP_OK;
 }
 
@@ -1708,10 +1777,9 @@ int vp_pixrefer_backward_update(vp_pixrefer_t* h, float* m_g, float* v_g, float*
                                 float lr, float beta1, float beta2, float eps, void* stream) {
   if (!h || !h->d.training) { set_err("vp_pixrefer_backward_update: needs a training plan"); return VP_ERR_STATE; }
   if (!m_g || !v_g || !m_d || !v_d || step_t_g < 1 || step_t_d < 1) { set_err("vp_pixrefer_backward_update: bad argument"); return VP_ERR_ARG; }
-  auto lr_t = [&](int t) { return (float)((double)lr * sqrt(1.0 - pow((double)beta2, t)) / (1.0 - pow((double)beta1, t))); };
   h->upd.active = true; h->upd.d_done = false;
   h->upd.m_g = m_g; h->upd.v_g = v_g; h->upd.m_d = m_d; h->upd.v_d = v_d;
-  h->upd.lr_t_g = lr_t(step_t_g); h->upd.lr_t_d = lr_t(step_t_d); h->upd.beta1 = beta1; h->upd.beta2 = beta2; h->upd.eps = eps;
+  h->upd.lr_t_g = adam_lr_t(lr, beta1, beta2, step_t_g); h->upd.lr_t_d = adam_lr_t(lr, beta1, beta2, step_t_d); h->upd.beta1 = beta1; h->upd.beta2 = beta2; h->upd.eps = eps;
   int rc = vp_pixrefer_backward(h, stream);
   if (!rc && !h->upd.d_done) rc = update_d(h, (hipStream_t)stream);
   h->upd.active = false;
@@ -1731,23 +1799,17 @@ int vp_pixrefer_update_bucket(vp_pixrefer_t* h, int which, int bucket, float* m,
     set_err("vp_pixrefer_update_bucket: bad argument");
     return VP_ERR_ARG;
   }
-  const float lr_t = (float)((double)lr * sqrt(1.0 - pow((double)beta2, step_t)) / (1.0 - pow((double)beta1, step_t)));
+  const float lr_t = adam_lr_t(lr, beta1, beta2, step_t);
   h->upd.beta1 = beta1; h->upd.beta2 = beta2; h->upd.eps = eps;
   int rc;
   if (which == 1) {
     rc = update_range(h, h->D, m, v, lr_t, 0, h->D.nparams, 0, (int)h->D.l.size() - 1, (hipStream_t)stream);
     h->upd_mask |= 8;
   } else {
-    Net& G = h->G;
-    int i_md5 = -1, i_me2 = -1;
-    for (int i = 0; i < (int)G.l.size(); ++i) {
-      if (G.l[i].scope == "merged_decoder_5") i_md5 = i;
-      if (G.l[i].scope == "merged_encoder_2") i_me2 = i;
-    }
-    const int l0 = bucket == 0 ? i_md5 : (bucket == 1 ? i_me2 : 0);
-    const int l1 = bucket == 0 ? (int)G.l.size() - 1 : (bucket == 1 ? i_md5 - 1 : i_me2 - 1);
-    const size_t off0 = G.l[l0].w_off, off1 = l1 + 1 < (int)G.l.size() ? G.l[l1 + 1].w_off : G.nparams;
-    rc = update_range(h, G, m, v, lr_t, off0, off1, l0, l1, (hipStream_t)stream);
+    int l0, l1;
+    size_t off0, off1;
+    bucket_range(h->G, bucket, &l0, &l1, &off0, &off1);
+    rc = update_range(h, h->G, m, v, lr_t, off0, off1, l0, l1, (hipStream_t)stream);
     h->upd_mask |= 1 << bucket;
   }
   if (rc) return rc;
@@ -1757,7 +1819,7 @@ int vp_pixrefer_update_bucket(vp_pixrefer_t* h, int which, int bucket, float* m,
 
 int vp_pixrefer_backward_d(vp_pixrefer_t* h, void* stream) {
   if (!h || !h->d.training) { set_err("vp_pixrefer_backward_d: needs a training plan"); return VP_ERR_STATE; }
-  return backward_d_on(h, (hipStream_t)stream, false);
+  return backward_d_on(h, caller_lane(h, stream));
 }
 
 // The two halves of vp_pixrefer_backward for a host that has work of its own between them (data parallel: the staged generator
@@ -1767,7 +1829,7 @@ int vp_pixrefer_backward_d_fork(vp_pixrefer_t* h, void* stream) {
   if (!h || !h->d.training) { set_err("vp_pixrefer_backward_d_fork: needs a training plan"); return VP_ERR_STATE; }
   hipStream_t st = (hipStream_t)stream;
   h->forked = h->overlap && h->ov_on;
-  if (!h->forked) return backward_d_on(h, st, false);
+  if (!h->forked) return backward_d_on(h, caller_lane(h, stream));
   // the pass starts where vp_pixrefer_backward starts it (vp_tune "d_backward_fork", default: inside stage 0 of the generator
   // backward, behind the generator-loss pass through D and the VGG trunk, i.e. under the generator's own layers); 0: at once
   h->dfork_pending = h->dfork_point;
@@ -1778,7 +1840,7 @@ int vp_pixrefer_backward_d_fork(vp_pixrefer_t* h, void* stream) {
 // The executor's low-priority side stream (the discriminator-loss pass and the fused optimiser run there), for a data-parallel host that
 // wants to issue its collectives on it instead of creating one more stream: the GPU exposes a handful of hardware queues, and every
 // extra stream beyond them shares one with another stream (false serialisation).  NULL when the plan does not overlap.
-void* vp_pixrefer_side_stream(vp_pixrefer_t* h) { return (h && h->overlap) ? (void*)h->side : nullptr; }
+void* vp_pixrefer_side_stream(vp_pixrefer_t* h) { return (h && h->overlap) ? (void*)h->lane[LANE_SIDE].s : nullptr; }
 
 // Streams the executor spreads a training step over: 4 (default: the caller's, side, branch and the foreground chain's own in the backward
 // pass) or 3.  The device schedules a handful of hardware queues; a host that keeps a busy stream of its own next to the step (an input
@@ -1830,8 +1892,8 @@ int vp_pixrefer_backward_d_join(vp_pixrefer_t* h, void* stream) {
   return VP_OK;
 }
 
-static int backward_d_on(vp_pixrefer_t* h, hipStream_t st, bool side) {
-  const int N = h->d.batch;
+static int backward_d_on(vp_pixrefer_t* h, const Lane& ln) {
+  const Sub all{0, 3 * h->d.batch, false, false};
   int rc;
   Net& D = h->D;
 
@@ -1840,10 +1902,10 @@ static int backward_d_on(vp_pixrefer_t* h, hipStream_t st, bool side) {
   for (int i = (int)D.l.size() - 1; i >= 0; --i) {
     Layer& L = D.l[i];
     Tens& to = D.t[L.out];
-    if (L.has_bn) if ((rc = run_bn_bwd(h, D, L, true, 0, 3 * N, 0, 3, st, side ? 1 : 0))) return rc;
+    if (L.has_bn) if ((rc = run_bn_bwd(h, D, L, true, all, 0, 3, ln))) return rc;
     const bool save = L.need_bwd[0];
     if (i == 0) L.need_bwd[0] = false;          // no gradient w.r.t. the images for the D loss
-    rc = run_layer_bwd(h, D, L, to.dz, true, false, 0, 3 * N, 0, st, side ? 1 : 0);
+    rc = run_layer_bwd(h, D, L, to.dz, true, all, ln);
     L.need_bwd[0] = save;
     if (rc) return rc;
   }
@@ -1855,6 +1917,34 @@ int vp_pixrefer_backward_g(vp_pixrefer_t* h, void* stream) { return vp_pixrefer_
 
 int vp_pixrefer_backward_g_stages(void) { return 3; }
 
+// Stage 0's prologue: Gen_loss -> the gradient w.r.t. the generator's output (pixrefer.py:402-407), and the generator's run-time state reset
+static int backward_g_head(vp_pixrefer_t* h, const Lane& me) {
+  const vp_pixrefer_desc& d = h->d;
+  hipStream_t st = me.s;
+  int rc;
+  // (a) GAN term through the fake application of the discriminator
+  // ... on the branch stream: independent of the VGG pass (b) until the composite (c) adds the two image gradients
+  const bool split_d = h->overlap && h->ov_on && h->dsplit_on;
+  const Lane& ld = split_d ? h->lane[LANE_BRANCH] : me;
+  if (split_d && (rc = after(h->ev_bfork, st, ld.s))) return rc;
+  if ((rc = discriminator_gpass(h, ld))) return rc;
+  if (split_d) VP_HIP_CHECK(hipEventRecord(h->ev_bjoin, ld.s));
+  if (h->dfork_pending == 1 && (rc = fork_d(h, st))) return rc;
+  // (b) perceptual term through the VGG trunk
+  if ((rc = vgg_backward(h, me))) return rc;
+  if (split_d) VP_HIP_CHECK(hipStreamWaitEvent(st, h->ev_bjoin, 0));
+  if (h->dfork_pending == 2 && (rc = fork_d(h, st))) return rc;
+  // (c) composite + L1 / matte terms -> gradient w.r.t. the pre-tanh generator output
+  CompositeArgs ca;
+  memset(&ca, 0, sizeof(ca));
+  ca.targets = h->in_targets; ca.masks = h->in_masks; ca.o4 = h->o4; ca.outputs = h->outputs;
+  ca.d_din = h->d_din; ca.d_vin = h->d_vin; ca.dy4 = h->dy4; ca.N = d.batch; ca.HW = d.height * d.height; ca.l1_weight = d.l1_weight;
+  VP_HIP_CHECK(launch_composite_bwd(ca, h->bf16, st));
+  phase_mark(h, st, 3);
+  for (Tens& t : h->G.t) { t.dz_written = false; t.dz_writes = 0; t.bn_bwd_done = false; t.bst_chunks = 0; t.cs_chunks = 0; }
+  return VP_OK;
+}
+
 // Stage s of the generator-loss backward pass; stage boundaries are where a contiguous range of the generator's flat
 // gradient arena becomes final, so a data-parallel host can start that bucket's all-reduce while the next stage computes:
 //   0: D(fake) + VGG + composite, then decoder_1 .. merged_decoder_5   -> arena [merged_decoder_5 .. end) final
@@ -1864,182 +1954,89 @@ int vp_pixrefer_backward_g_stages(void) { return 3; }
 int vp_pixrefer_backward_g_stage(vp_pixrefer_t* h, int stage, void* stream) {
   if (!h || !h->d.training) { set_err("vp_pixrefer_backward_g: needs a training plan"); return VP_ERR_STATE; }
   if (stage > 2) { set_err("vp_pixrefer_backward_g_stage: stage must be < 3"); return VP_ERR_ARG; }
-  hipStream_t st = (hipStream_t)stream;
-  const vp_pixrefer_desc& d = h->d;
-  const int N = d.batch, H = d.height, bf = h->bf16, es = h->es;
+  const Lane me = caller_lane(h, stream);
+  const Lane &side = h->lane[LANE_SIDE], &branch = h->lane[LANE_BRANCH], &b2 = h->lane[LANE_BRANCH2];
+  hipStream_t st = me.s;
+  const Sub all{0, h->d.batch, false, false};
   int rc;
-  Net &G = h->G, &D = h->D, &V = h->V;
-  // generator layers are walked last to first; l_hi / l_lo = the layer range of this stage
-  int i_md5 = -1, i_me2 = -1;
-  for (int i = 0; i < (int)G.l.size(); ++i) {
-    if (G.l[i].scope == "merged_decoder_5") i_md5 = i;
-    if (G.l[i].scope == "merged_encoder_2") i_me2 = i;
-  }
-  const int l_hi = stage <= 0 ? (int)G.l.size() - 1 : (stage == 1 ? i_md5 - 1 : i_me2 - 1);
-  const int l_lo = stage < 0 ? 0 : (stage == 0 ? i_md5 : (stage == 1 ? i_me2 : 0));
-  if (stage <= 0) {
-  // ---- Gen_loss -> generator* (pixrefer.py:402-407) ----
-  // (a) GAN term through the fake application of the discriminator (dX only, pre-update weights)
-  // ... on the branch stream: independent of the VGG pass (b) until the composite (c) adds the two image gradients
-  const bool split_d = h->overlap && h->ov_on && h->dsplit_on;
-  hipStream_t sd = split_d ? h->branch : st;
-  const int ssd = split_d ? 2 : 0;
-  if (split_d) {
-    VP_HIP_CHECK(hipEventRecord(h->ev_bfork, st));
-    VP_HIP_CHECK(hipStreamWaitEvent(h->branch, h->ev_bfork, 0));
-  }
-  for (Tens& t : D.t) { t.dz2_written = false; t.bst_chunks_g = 0; }
-  for (int i = (int)D.l.size() - 1; i >= 0; --i) {
-    Layer& L = D.l[i];
-    Tens& to = D.t[L.out];
-    if (L.has_bn) if ((rc = run_bn_bwd(h, D, L, false, 2 * N, N, 2, 1, sd, ssd, true))) return rc;
-    const void* dy = (i == (int)D.l.size() - 1) ? h->dl_g : to.dz2;
-    if ((rc = run_layer_bwd(h, D, L, dy, false, true, 2 * N, N, 2, sd, ssd, true))) return rc;
-  }
-  if (split_d) VP_HIP_CHECK(hipEventRecord(h->ev_bjoin, h->branch));
-  if (h->dfork_pending == 1 && (rc = fork_d(h, st))) return rc;
-  // (b) perceptual term through the VGG trunk, fake half only (dX only: VGG is frozen)
-  for (Tens& t : V.t) t.dz_written = false;
-  h->pool_bwd_fused = false;
-  h->pool_dz_stale[0] = h->pool_dz_stale[1] = false;
-  for (int i = (int)V.l.size() - 1; i >= 0; --i) {
-    Layer& L = V.l[i];
-    Tens& to = V.t[L.out];
-    Tens& ti = V.t[L.src[0]];
-    // dz of a conv output here is already w.r.t. the pre-relu value (perceptual seed / epilogue / pool bwd)
-    IgemmArgs a = L.bwd_alt[0].a;
-    set_single_src(a.x, to.dz, L.g.CoutT, nullptr, nullptr, ACT_NONE, 0);
-    const int pk = L.scope == "conv2/conv2_2";
-    if ((pk || L.scope == "conv1/conv1_2") && h->pool_dz_stale[pk]) {
-      // the pool behind this conv left its gradient unexpanded (below): the launch reads the pooled gradient and the codes
-      a.x.ptr[0] = V.t[L.out + 1].dz;
-      a.pool_code = h->vpool_code[pk];
-      a.pool_src = 1;
-    }
-    a.Wp = V.packed + L.pk_bwd_alt[0] * es;
-    a.partial = (float*)h->scratch;
-    const bool from_pool = (ti.name == "pool1" || ti.name == "pool2");
-    if (ti.is_input) {
-      a.Y = h->d_vin;
-    } else {
-      a.Y = ti.dz;
-      if (!from_pool) {   // producer is a conv+relu: multiply by relu'(stored output of the fake half)
-        a.ref = (const char*)ti.y + ti.elems() / 2 * es;
-        a.ref_act = ACT_RELU;
-      }
-    }
-    a.zeros = h->zeros;
-    profile_tag((L.scope + ":bwd").c_str());
-    VP_HIP_CHECK(launch_igemm(a, bf, L.bwd_alt[0].cfg, st));
-    if (from_pool) {
-      // ti = pool output; its input is the conv tensor created just before it
-      const int ci = L.src[0] - 1;
-      Tens& tc = V.t[ci];
-      const char* xin = (const char*)tc.y + tc.elems() / 2 * es;
-      const int k = ti.name == "pool2";
-      if (h->pool_codes_written && h->pool_fuse_ok[k]) {
-        // the conv below the pool expands the gradient in its loader (the next trip of this loop): nothing to launch, tc.dz stays unwritten
-        h->pool_dz_stale[k] = true;
-        h->pool_bwd_fused = true;
-      } else if (h->pool_codes_written) VP_HIP_CHECK(launch_maxpool_bwd_code(h->vpool_code[k], ti.dz, tc.dz, N, tc.H, tc.W, tc.C, bf, st));
-      else VP_HIP_CHECK(launch_maxpool_bwd(xin, ti.dz, tc.dz, N, tc.H, tc.W, tc.C, bf, st));
-    }
-  }
-  if (split_d) VP_HIP_CHECK(hipStreamWaitEvent(st, h->ev_bjoin, 0));
-  if (h->dfork_pending == 2 && (rc = fork_d(h, st))) return rc;
-  // (c) composite + L1 / matte terms -> gradient w.r.t. the pre-tanh generator output
-  CompositeArgs ca;
-  memset(&ca, 0, sizeof(ca));
-  ca.targets = h->in_targets; ca.masks = h->in_masks; ca.o4 = h->o4; ca.outputs = h->outputs;
-  ca.d_din = h->d_din; ca.d_vin = h->d_vin; ca.dy4 = h->dy4; ca.N = N; ca.HW = H * H; ca.l1_weight = d.l1_weight;
-  VP_HIP_CHECK(launch_composite_bwd(ca, bf, st));
-  phase_mark(h, st, 3);
-  for (Tens& t : G.t) { t.dz_written = false; t.dz_writes = 0; t.bn_bwd_done = false; t.bst_chunks = 0; t.cs_chunks = 0; }
-  }
+  Net& G = h->G;
+  // generator layers are walked last to first; l_hi .. l_lo = the layer range of this stage
+  int l_lo = 0, l_hi = (int)G.l.size() - 1;
+  size_t off0, off1;
+  if (stage >= 0) bucket_range(G, stage, &l_lo, &l_hi, &off0, &off1);
+  if (stage <= 0 && (rc = backward_g_head(h, me))) return rc;
   // (d) generator, last layer first.  Below merged_encoder_2 the two encoder branches are independent again: the foreground
   // branch (encoder_fg_4 .. encoder_fg_1) runs on the branch stream, joined before this call returns control of `st`
   const bool split_enc = h->overlap && h->ov_on && l_lo == 0;
   const bool wsplit = h->overlap && h->ov_on;
-  bool forked = false, fg_forked = false;
-  bool b2_used = false;            // something of this call runs on the second branch stream (joined wherever `branch` is)
+  bool forked = false;
+  const Lane* fgl = nullptr;       // the foreground chain's lane, once forked: the second branch stream's (then joined wherever `branch` is) or `branch`
   for (int i = l_hi; i >= l_lo; --i) {
     Layer& L = G.l[i];
     Tens& to = G.t[L.out];
-    const bool fg = split_enc && L.scope.rfind("encoder_fg_", 0) == 0;
-    if (fg && !fg_forked) {      // the branch's first layer needs merged_encoder_2's data gradient, enqueued on `st` just before
+    const bool fg = split_enc && L.fg;
+    if (fg && !fgl) {      // the branch's first layer needs merged_encoder_2's data gradient, enqueued on `st` just before
       VP_HIP_CHECK(hipEventRecord(h->ev_bfork, st));
-      if (h->use_b2 && !h->branch2) { const int rc2 = pool_streams(true, nullptr, nullptr, &h->branch2); if (rc2) return rc2; }
-      VP_HIP_CHECK(hipStreamWaitEvent(h->use_b2 ? h->branch2 : h->branch, h->ev_bfork, 0));
-      forked = fg_forked = true;
-      b2_used = h->use_b2;
+      if (h->use_b2 && !b2.s && (rc = pool_streams(true, nullptr, nullptr, &h->lane[LANE_BRANCH2].s))) return rc;
+      fgl = h->use_b2 ? &b2 : &branch;
+      VP_HIP_CHECK(hipStreamWaitEvent(fgl->s, h->ev_bfork, 0));
+      forked = true;
     }
     // (the foreground chain has a stream of its own: on `branch` it queued behind the weight gradients of every layer before it and
     // ended the step 0.2-0.6 ms after the caller's chain)
-    hipStream_t s2 = fg ? (h->use_b2 ? h->branch2 : h->branch) : st;
-    const int ss = fg ? (h->use_b2 ? 3 : 2) : 0;
-    if (i == i_md5 - 1) phase_mark(h, st, 4);
-    if (i == i_me2 - 1) phase_mark(h, st, 5);
+    const Lane& ln = fg ? *fgl : me;
+    if (i == G.i_md5 - 1) phase_mark(h, st, 4);
+    if (i == G.i_me2 - 1) phase_mark(h, st, 5);
     if (g_phase_detail && !fg) phase_mark(h, st, 32 + i);                         // [32 + layer] = before the layer's backward on `st`
-    if (L.has_bn) if ((rc = run_bn_bwd(h, G, L, true, 0, N, 0, 1, s2, ss))) return rc;
+    if (L.has_bn) if ((rc = run_bn_bwd(h, G, L, true, all, 0, 1, ln))) return rc;
     if (wsplit && !fg) {
       // the weight gradient of a layer hangs off the chain (only its data gradient feeds the next layer): branch stream
       // (alternating the weight gradients between the two branch streams was measured: slower - they then sit in front of the
       // foreground chain again; batch 4 2.55 vs 2.50 ms)
-      VP_HIP_CHECK(hipEventRecord(h->ev_bfork, st));
-      VP_HIP_CHECK(hipStreamWaitEvent(h->branch, h->ev_bfork, 0));
+      if ((rc = after(h->ev_bfork, st, branch.s))) return rc;
       forked = true;
       // (the data gradient of a decoder's skip-connection source on the branch stream too was measured slower - EXPERIMENTS.md - and
       // raced with the fourth stream: removed.  Stage 0's weight gradients alternating between `branch` and the then idle `branch2`:
       // +0.01 .. 0.05 ms at batch 4 / 8 / 32 - the weight gradients, the optimiser and the weight-streaming layers share HBM, a second
       // stream adds contention, not throughput; EXPERIMENTS.md 0.2)
-      if ((rc = run_layer_bwd(h, G, L, to.dz, true, false, 0, N, 0, h->branch, 2, false, 1))) return rc;
-      if ((rc = run_layer_bwd(h, G, L, to.dz, true, false, 0, N, 0, st, 0, false, 6))) return rc;
+      if ((rc = run_layer_wgrad(h, G, L, to.dz, all, branch))) return rc;
+      if ((rc = run_layer_dgrad(h, G, L, to.dz, all, me))) return rc;
     } else {
-      if ((rc = run_layer_bwd(h, G, L, to.dz, true, false, 0, N, 0, s2, ss))) return rc;
+      if ((rc = run_layer_bwd(h, G, L, to.dz, true, all, ln))) return rc;
     }
     // a bucket of the gradient arena is final (stage boundaries above): its Adam update + re-pack, on the side stream
     // (holding the first bucket's update back until the end of stage 1, so that it does not run beside the weight-streaming few-pixel
     // layers of that stage, was measured: +0.02 .. 0.08 ms at batch 4, +-0 at 8 / 32 - EXPERIMENTS.md)
-    if (h->upd.active && (i == i_md5 || i == i_me2 || i == 0)) {
-      const int l0 = i, l1 = i == i_md5 ? (int)G.l.size() - 1 : (i == i_me2 ? i_md5 - 1 : i_me2 - 1);
-      const size_t off0 = G.l[l0].w_off, off1 = l1 + 1 < (int)G.l.size() ? G.l[l1 + 1].w_off : G.nparams;
+    const int bucket = i == G.i_md5 ? 0 : (i == G.i_me2 ? 1 : (i == 0 ? 2 : -1));
+    if (h->upd.active && bucket >= 0) {
+      int l0, l1;
+      bucket_range(G, bucket, &l0, &l1, &off0, &off1);
       hipStream_t su = st;
-      const bool on_side = h->overlap && h->ov_on && h->dfork_pending == 0 && h->dfork_point >= 0;
-      if (h->overlap && h->ov_on && on_side) {
+      const bool on_side = wsplit && h->dfork_pending == 0;      // the discriminator-loss pass has been started there
+      if (on_side) {
         // the (HBM-bound) optimiser + re-pack of the bucket go to the SIDE stream, behind the discriminator-loss pass that runs there:
         // on the branch stream they sat between the weight gradients of the layers still to come and delayed the end of the step.
         // The bucket is final when its weight gradients (branch stream) and its data gradients (this stream: they read the packed
         // weights the re-pack overwrites) are done; vp_pixrefer_backward's closing wait on ev_join covers the updates.
-        VP_HIP_CHECK(hipEventRecord(h->ev_upd_b, h->branch));
+        VP_HIP_CHECK(hipEventRecord(h->ev_upd_b, branch.s));
         VP_HIP_CHECK(hipEventRecord(h->ev_upd_m, st));
-        VP_HIP_CHECK(hipStreamWaitEvent(h->side, h->ev_upd_b, 0));
-        VP_HIP_CHECK(hipStreamWaitEvent(h->side, h->ev_upd_m, 0));
-        if (b2_used) {                                   // weight gradients / the foreground encoders' chain on the second branch stream
-          VP_HIP_CHECK(hipEventRecord(h->ev_b2join, h->branch2));
-          VP_HIP_CHECK(hipStreamWaitEvent(h->side, h->ev_b2join, 0));
-        }
-        su = h->side;
-      } else if (h->overlap && h->ov_on) {
-        VP_HIP_CHECK(hipEventRecord(h->ev_bfork, st));
-        VP_HIP_CHECK(hipStreamWaitEvent(h->branch, h->ev_bfork, 0));
-        if (b2_used) {
-          VP_HIP_CHECK(hipEventRecord(h->ev_b2join, h->branch2));
-          VP_HIP_CHECK(hipStreamWaitEvent(h->branch, h->ev_b2join, 0));
-        }
-        su = h->branch; forked = true;
+        VP_HIP_CHECK(hipStreamWaitEvent(side.s, h->ev_upd_b, 0));
+        VP_HIP_CHECK(hipStreamWaitEvent(side.s, h->ev_upd_m, 0));
+        if (fgl == &b2 && (rc = after(h->ev_b2join, b2.s, side.s))) return rc;
+        su = side.s;
+      } else if (wsplit) {
+        if ((rc = after(h->ev_bfork, st, branch.s))) return rc;
+        if (fgl == &b2 && (rc = after(h->ev_b2join, b2.s, branch.s))) return rc;
+        su = branch.s; forked = true;
       }
       if ((rc = update_range(h, G, h->upd.m_g, h->upd.v_g, h->upd.lr_t_g, off0, off1, l0, l1, su))) return rc;
-      if (h->overlap && h->ov_on && on_side) VP_HIP_CHECK(hipEventRecord(h->ev_join, h->side));
+      if (on_side) VP_HIP_CHECK(hipEventRecord(h->ev_join, side.s));
     }
   }
   if (forked) {
     if (g_phase_detail && (stage < 0 || stage == 2)) phase_mark(h, st, 60);      // [60] the caller's chain is done, [6] the branch stream's weight gradients too
-    VP_HIP_CHECK(hipEventRecord(h->ev_bjoin, h->branch));
-    VP_HIP_CHECK(hipStreamWaitEvent(st, h->ev_bjoin, 0));
-    if (b2_used) {
-      VP_HIP_CHECK(hipEventRecord(h->ev_b2join, h->branch2));
-      VP_HIP_CHECK(hipStreamWaitEvent(st, h->ev_b2join, 0));
-    }
+    if ((rc = after(h->ev_bjoin, branch.s, st))) return rc;
+    if (fgl == &b2 && (rc = after(h->ev_b2join, b2.s, st))) return rc;
   }
   if (stage < 0 || stage == 2) phase_mark(h, st, 6);
   return VP_OK;
@@ -2148,7 +2145,7 @@ int vp_adam_tf(float* params, const float* grads, float* m, float* v, size_t n, 
   if (!params || !grads || !m || !v || step_t < 1) { set_err("vp_adam_tf: bad argument"); return VP_ERR_ARG; }
   AdamArgs a;
   a.p = params; a.g = grads; a.m = m; a.v = v; a.n = n;
-  a.lr_t = (float)((double)lr * sqrt(1.0 - pow((double)beta2, step_t)) / (1.0 - pow((double)beta1, step_t)));
+  a.lr_t = adam_lr_t(lr, beta1, beta2, step_t);
   a.beta1 = beta1; a.beta2 = beta2; a.eps = eps;
   VP_HIP_CHECK(launch_adam(a, (hipStream_t)stream));
   return VP_OK;
