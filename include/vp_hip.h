@@ -14,6 +14,8 @@
  *   vp_logmel_*     replaces  generator/generator.py:60-80              (DataGenerator.extract_mfcc)
  *   vp_bfmnet_*     replaces  voicepuppet/bfmnet/bfmnet.py:189-213,325-333 + tinynet.py:159-212
  *   vp_render_colors   replaces  utils/cython/mesh_core.h:63 _render_colors_core (mesh_core.cpp:169-231)
+ *   vp_rasterize_triangles, vp_render_texture, vp_vertex_normals replace the rest of mesh_core.h:53-77 (_rasterize_triangles_core,
+ *                             _render_texture_core, _get_normal_core: mesh_core.cpp:85-166, :234-333); vp_raster_interpolate goes with them
  *   vp_bfm_reconstruct replaces  utils/reconstruct_mesh.py:198-223 Reconstruction_rotation + infer_bfmvid.py:92-99
  *   vp_bfm_reconstruct_view replaces utils/reconstruct_mesh.py:172-194 Reconstruction + the packing of utils/bfm_visual.py:100-112 (view 0)
  *                             and voicepuppet/bfmnet/infer_bfmnet.py:212-216 (view 1)
@@ -514,6 +516,53 @@ size_t vp_render_colors_workspace_bytes(int batch, int h, int w);
 int vp_render_colors(unsigned char* image, unsigned char* face_mask, const float* vertices, const int* triangles,
                      const float* colors, float* depth_buffer, int ntri, int nver, int h, int w, int c, int batch,
                      void* workspace, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The rest of mesh_core_cython (utils/cython/mesh_core_cython.pyx:40-99): the dense correspondence of a frame - which triangle
+ * each pixel sees, with which barycentric weights, at which interpolated depth - bit-exact with mesh_core.cpp, batched over frames
+ * that share `triangles` like vp_render_colors (vertices [batch,nver,3], buffers [batch,h,w,...]).  All pointers are device pointers,
+ * the calls only enqueue, ntri == 0 is legal, h * w < 2^31.
+ *
+ * Visibility (both rasterisers): a pixel of a triangle's clamped bounding box is a candidate when it lies inside the triangle
+ * (isPointInTri, mesh_core.cpp:23-50) or in the two-pixel border ring x < 2, x > w-3, y < 2, y > h-3 (:148, :292: no inside test
+ * there, so the weights may leave [0, 1] and the depth is extrapolated).  Its depth is p_depth = w0*d0 + w1*d1 + w2*d2 with
+ * get_point_weight's w0 = 1 - u - v, w1 = v, w2 = u (:53-82), in float32, left to right.  The reference overwrites on a strictly
+ * greater depth in index order, so the survivor is the greatest p_depth and, among equal ones, the lowest index; a NaN p_depth never
+ * wins, and a pixel that no candidate beats keeps every buffer as given (a second call over the same buffers changes nothing).
+ * A triangle with a vertex index outside 0 .. nver-1 is skipped (the reference reads out of bounds).
+ *
+ * vp_rasterize_triangles: _rasterize_triangles_core(vertices, triangles, depth_buffer, triangle_buffer, barycentric_weight, nver, ntri,
+ *   h, w) (mesh_core.h:57, mesh_core.cpp:108-166).  depth_buffer f32 [batch,h,w], triangle_buffer i32 [batch,h,w], barycentric_weight
+ *   f32 [batch,h,w,3] are read-modify-write: winning pixels get the winner's depth, index and weights.
+ * vp_render_texture: _render_texture_core(image, vertices, triangles, texture, tex_coords, tex_triangles, depth_buffer, nver, tex_nver,
+ *   ntri, h, w, c, tex_h, tex_w, tex_c, mapping_type) (mesh_core.h:70, mesh_core.cpp:234-333).  image f32 [batch,h,w,c] and depth_buffer
+ *   are read-modify-write; texture f32 [tex_h,tex_w,tex_c], tex_coords f32 [tex_rows,3] and tex_triangles i32 [ntri,3] are shared by the
+ *   frames.  The indexing is the reference's as written (:270-272): x of corner k is tex_coords[3*tex_triangles[3i+k]], y is
+ *   tex_coords[3*triangles[3i+k] + 1]; tex_p = tex_p0*w0 + tex_p1*w1 + tex_p2*w2, clamped to the texture; mapping_type 0 reads the
+ *   nearest texel through round() (half away from zero), any other value the four-term bilinear sum in the written order (:322).
+ *   Refused: c > tex_c, tex_rows < max(nver, tex_nver).  A triangle with a tex_triangles index outside 0 .. tex_nver-1 is skipped.
+ * vp_raster_interpolate: no compiled form in the reference (its callers do this in numpy): out[f,y,x,:] = w0*a[i0] + w1*a[i1] + w2*a[i2]
+ *   in float32, left to right, for the pixel's triangle (i0,i1,i2) and weights; attributes f32 [batch,nver,k], out f32 [batch,h,w,k].
+ *   Pixels whose triangle_buffer entry is negative (or not below ntri) are left as given.
+ * vp_vertex_normals: _get_normal_core(normal, tri_normal, triangles, ntri) (mesh_core.h:53, mesh_core.cpp:85-105): normal [batch,nver,3]
+ *   += tri_normal [batch,ntri,3] of the incident triangles, added in ascending triangle order and within a triangle in corner order (a
+ *   repeated index adds twice), onto the values given: the bits of the serial loop.  The order comes from an adjacency (vertex ->
+ *   sorted list of 3*triangle + corner) that depends on `triangles` alone: vp_vertex_adjacency_build fills `adjacency`
+ *   (vp_vertex_adjacency_bytes(nver, ntri) bytes, 0 for bad sizes) once, vp_vertex_normals takes it with the same nver and ntri.
+ *   Corners with an index outside 0 .. nver-1 are left out of it.
+ * ---------------------------------------------------------------------------------------------- */
+size_t vp_rasterize_triangles_workspace_bytes(int batch, int h, int w);
+int vp_rasterize_triangles(const float* vertices, const int* triangles, float* depth_buffer, int* triangle_buffer, float* barycentric_weight,
+                           int nver, int ntri, int h, int w, int batch, void* workspace, void* stream);
+size_t vp_render_texture_workspace_bytes(int batch, int h, int w);
+int vp_render_texture(float* image, const float* vertices, const int* triangles, const float* texture, const float* tex_coords,
+                      const int* tex_triangles, float* depth_buffer, int nver, int tex_nver, int tex_rows, int ntri, int h, int w, int c, int tex_h,
+                      int tex_w, int tex_c, int mapping_type, int batch, void* workspace, void* stream);
+int vp_raster_interpolate(float* out, const int* triangle_buffer, const float* barycentric_weight, const int* triangles, const float* attributes,
+                          int nver, int ntri, int k, int h, int w, int batch, void* stream);
+size_t vp_vertex_adjacency_bytes(int nver, int ntri);
+int vp_vertex_adjacency_build(const int* triangles, int nver, int ntri, void* adjacency, size_t adjacency_bytes, void* stream);
+int vp_vertex_normals(float* normal, const float* tri_normal, const void* adjacency, int nver, int ntri, int batch, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * BFM reconstruction for a clip ("next" row): replaces the per-frame numpy of

@@ -333,7 +333,15 @@ _SIGNATURES = {
     "vp_render_colors_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "vp_render_colors": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                         ctypes.c_int, _P, _P]),
-    "vp_bn_train_workspace_bytes": (ctypes.c_size_t, [ctypes.c_size_t, ctypes.c_int]),
+    "vp_rasterize_triangles_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "vp_rasterize_triangles": (ctypes.c_int, [_P] * 5 + [ctypes.c_int] * 5 + [_P, _P]),
+    "vp_render_texture_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "vp_render_texture": (ctypes.c_int, [_P] * 7 + [ctypes.c_int] * 12 + [_P, _P]),
+    "vp_raster_interpolate": (ctypes.c_int, [_P] * 5 + [ctypes.c_int] * 6 + [_P]),
+    "vp_vertex_adjacency_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
+    "vp_vertex_adjacency_build": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _P, ctypes.c_size_t, _P]),
+    "vp_vertex_normals": (ctypes.c_int, [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P]),
+    "vp_bn_train_workspace_bytes":(ctypes.c_size_t, [ctypes.c_size_t, ctypes.c_int]),
     "vp_bn_train_fwd": (ctypes.c_int, [_P, ctypes.c_size_t, ctypes.c_int, _P, ctypes.c_float, _P, _P, _P, _P, _P, _P, _P]),
     "vp_bn_train_bwd": (ctypes.c_int, [_P, _P, ctypes.c_size_t, ctypes.c_int, _P, _P, _P, _P, _P, _P]),
     "vp_affine_act_fwd": (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, _P, _P]),

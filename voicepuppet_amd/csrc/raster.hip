@@ -11,31 +11,11 @@
 #include <stdint.h>
 
 #include "errors.h"
+#include "raster_common.h"   // depth_bits, point_in_tri: shared with raster_dense.hip
 
 #pragma clang fp contract(off)
 
 namespace vp {
-
-__device__ __forceinline__ unsigned int depth_bits(float d) {
-  const unsigned int u = __float_as_uint(d + 0.f);           // -0 -> +0: the reference compares floats, where they are equal
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);      // monotone float -> uint
-}
-
-__device__ __forceinline__ bool point_in_tri(float px, float py, float p0x, float p0y, float p1x, float p1y, float p2x, float p2y) {
-  const float v0x = p2x - p0x, v0y = p2y - p0y;
-  const float v1x = p1x - p0x, v1y = p1y - p0y;
-  const float v2x = px - p0x, v2y = py - p0y;
-  const float dot00 = ((v0x * v0x) + (v0y * v0y));
-  const float dot01 = ((v0x * v1x) + (v0y * v1y));
-  const float dot02 = ((v0x * v2x) + (v0y * v2y));
-  const float dot11 = ((v1x * v1x) + (v1y * v1y));
-  const float dot12 = ((v1x * v2x) + (v1y * v2y));
-  const float den = ((dot00 * dot11) - (dot01 * dot01));
-  const float inv = (den == 0.f) ? 0.f : (1.f / den);
-  const float u = ((dot11 * dot02) - (dot01 * dot12)) * inv;
-  const float v = ((dot00 * dot12) - (dot01 * dot02)) * inv;
-  return (u >= 0.f) && (v >= 0.f) && ((u + v) < 1.f);
-}
 
 __global__ __launch_bounds__(256) void raster_init_kernel(const float* __restrict__ depth, unsigned long long* __restrict__ keys, size_t n) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
