@@ -15,9 +15,7 @@
 #include <stdint.h>
 #include <string.h>
 
-#include <new>
-
-#include "errors.h"
+#include "workspace.h"
 
 namespace vp {
 
@@ -254,12 +252,19 @@ __global__ __launch_bounds__(kAviLanes) void avi_gather_kernel(AviArgs a) {
 
 static size_t avi_table_bytes(int slots, int frames) { return 16 + 16 * (size_t)slots + 16 * ((size_t)frames + slots); }
 
-static int avi_check(const vp_avimux_desc* d, const char* who) {
-  if (!d) { set_err("%s: bad descriptor (null)", who); return VP_ERR_ARG; }
-  if (d->struct_bytes != (uint32_t)sizeof(vp_avimux_desc)) {
-    set_err("%s: bad descriptor (struct_bytes %u, this library's vp_avimux_desc is %d bytes)", who, d->struct_bytes, (int)sizeof(vp_avimux_desc));
-    return VP_ERR_ARG;
-  }
+}  // namespace vp
+
+struct vp_avimux {
+  vp_avimux_desc d;
+  uint32_t* nchunks;
+  vp::AviChunk* chunks;
+};
+
+using namespace vp;
+
+// (this family's refusals name the entry point, `who`)
+static int avi_check(const vp_avimux_desc* d, const char* who, vp_avimux* h) {
+  if (const int rc = check_desc(d, "vp_avimux", who)) return rc;
   if (d->max_frames < 1 || d->max_frames > VP_AVIMUX_MAX_FRAMES) {
     set_err("%s: bad descriptor (max_frames %d, 1 .. %d)", who, d->max_frames, VP_AVIMUX_MAX_FRAMES);
     return VP_ERR_ARG;
@@ -273,51 +278,42 @@ static int avi_check(const vp_avimux_desc* d, const char* who) {
     set_err("%s: bad descriptor (%d frames of %d bytes and %d samples are %llu bytes: offsets are 32 bits)", who, d->max_frames, d->row_bytes, d->max_samples, cap);
     return VP_ERR_ARG;
   }
+  h->d = *d;
   return VP_OK;
 }
 
-}  // namespace vp
-
-struct vp_avimux {
-  vp_avimux_desc d;
-  char* base;
-};
-
-using namespace vp;
+static size_t avi_carve(vp_avimux* h, void* base) {
+  Arena ar(base);
+  h->nchunks = ar.take<uint32_t>(1);
+  h->chunks = ar.take<AviChunk>((size_t)h->d.max_frames + h->d.slots);
+  return ar.total();
+}
 
 extern "C" {
 
 size_t vp_avimux_desc_size(void) { return sizeof(vp_avimux_desc); }
 
 size_t vp_avimux_workspace_bytes(const vp_avimux_desc* d) {
-  if (avi_check(d, "vp_avimux_workspace_bytes")) return 0;
-  return 256 + 256 + sizeof(AviChunk) * ((size_t)d->max_frames + d->slots);
+  vp_avimux h;
+  return avi_check(d, "vp_avimux_workspace_bytes", &h) ? 0 : avi_carve(&h, nullptr);
 }
 
 size_t vp_avimux_table_bytes(const vp_avimux_desc* d, int frames) {
-  if (avi_check(d, "vp_avimux_table_bytes")) return 0;
+  vp_avimux h;
+  if (avi_check(d, "vp_avimux_table_bytes", &h)) return 0;
   if (frames < 0 || frames > d->max_frames) { set_err("vp_avimux_table_bytes: frames %d outside 0 .. max_frames %d", frames, d->max_frames); return 0; }
   return avi_table_bytes(d->slots, frames);
 }
 
 size_t vp_avimux_out_capacity(const vp_avimux_desc* d) {
-  if (avi_check(d, "vp_avimux_out_capacity")) return 0;
+  vp_avimux h;
+  if (avi_check(d, "vp_avimux_out_capacity", &h)) return 0;
   return avi_table_bytes(d->slots, d->max_frames) + (size_t)d->max_frames * (8 + (size_t)d->row_bytes + 1) + 8 * (size_t)d->slots + 2 * (size_t)d->max_samples;
 }
 
 int vp_avimux_create(const vp_avimux_desc* d, void* workspace, size_t workspace_bytes, vp_avimux_t** out) {
-  if (!out) { set_err("vp_avimux_create: bad argument"); return VP_ERR_ARG; }
-  *out = nullptr;
-  const int rc = avi_check(d, "vp_avimux_create");
-  if (rc) return rc;
-  const size_t want = vp_avimux_workspace_bytes(d);
-  if (!workspace || workspace_bytes < want) { set_err("vp_avimux_create: workspace too small (%zu of %zu bytes)", workspace_bytes, want); return VP_ERR_WORKSPACE; }
-  vp_avimux* h = new (std::nothrow) vp_avimux();
-  if (!h) { set_err("vp_avimux_create: out of host memory"); return VP_ERR_STATE; }
-  h->d = *d;
-  h->base = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-  *out = h;
-  return VP_OK;
+  const auto check = [](const vp_avimux_desc* d, vp_avimux* h) { return avi_check(d, "vp_avimux_create", h); };
+  return open_handle("vp_avimux_create", d, check, avi_carve, workspace, workspace_bytes, out);
 }
 
 void vp_avimux_destroy(vp_avimux_t* h) { delete h; }
@@ -345,8 +341,8 @@ int vp_avimux_segment(vp_avimux_t* h, const unsigned char* data, size_t row_byte
   a.data = data; a.row_bytes = frames > 0 ? row_bytes : 1; a.lengths = lengths; a.frame_slot = frame_slot; a.K = frames;
   a.pcm = pcm; a.s_off = sample_offset; a.s_cnt = sample_count; a.samples = samples;
   a.out = out; a.cap = (uint32_t)(out_capacity > 0xFFFFFFFFull ? 0xFFFFFFFFull : out_capacity); a.table_bytes = (uint32_t)table; a.slots = d.slots;
-  a.nchunks = (uint32_t*)h->base;
-  a.chunks = (AviChunk*)(h->base + 256);
+  a.nchunks = h->nchunks;
+  a.chunks = h->chunks;
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(avi_layout_kernel, dim3(1), dim3(kAviLanes), 0, st, a);
   VP_HIP_CHECK(hipGetLastError());

@@ -25,7 +25,7 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "errors.h"
+#include "workspace.h"
 #include "fit_device.h"
 #include "bfm_device.h"      // (switches FMA contraction off from here on: the observation repeats bfm_recon.hip's bits)
 
@@ -437,7 +437,7 @@ int vp_bfmfit_observe(const vp_bfm_model* m, const float* coeff, const double* r
     return VP_ERR_ARG;
   }
   hipStream_t st = (hipStream_t)stream;
-  double* shape = (double*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  double* shape = vp::align256((double*)workspace);
   double* fn = shape + (size_t)frames * m->nver * 3;
   vp::bfm_launch_shape(m, coeff, frames, shape, st);
   vp::bfm_launch_fnormal(m, shape, frames, fn, st);
@@ -481,7 +481,7 @@ int vp_bfmfit_appearance(const vp_bfm_model* m, const double* sh, const double* 
     attr_done = true;
   }
   const int slabs = vp::ap_slabs(m->nver);
-  double* state = (double*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  double* state = vp::align256((double*)workspace);
   double* sum = state + (size_t)frames * vp::AP_STATE;
   double* part = sum + (size_t)frames * vp::AP_PART;
   vp::InitArgs ia{state, coeff_in, params, params_in ? 1 : 0, frames};

@@ -20,7 +20,7 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "errors.h"
+#include "workspace.h"
 #include "fit_device.h"
 
 namespace vp {
@@ -464,7 +464,7 @@ static bool check_common(const char* who, const vp_bfm_model* m, const int* keyp
 }
 
 static double* fit_tables(const vp_bfm_model* m, const int* keypoints, int table_ready, void* workspace, hipStream_t st) {
-  double* tbl = (double*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  double* tbl = vp::align256((double*)workspace);
   if (!table_ready) {
     FitKeypoints kp;
     for (int k = 0; k < FIT_NL; ++k) kp.v[k] = keypoints[k];

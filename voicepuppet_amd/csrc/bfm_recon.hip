@@ -11,7 +11,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "errors.h"
+#include "workspace.h"
 #include "bfm_device.h"
 
 #pragma clang fp contract(off)
@@ -201,7 +201,7 @@ static int reconstruct_impl(const char* who, int mode, double scale, const vp_bf
   }
   hipStream_t st = (hipStream_t)stream;
   const int rows = 3 * m->nver;
-  double* shape = (double*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  double* shape = vp::align256((double*)workspace);
   double* tex = face_texture ? face_texture : shape + (size_t)frames * rows;
   double* fn = shape + (size_t)frames * rows * 2;
   vp::bfm_launch_shape(m, coeff, frames, shape, st);

@@ -20,10 +20,9 @@
 #include <string.h>
 
 #include <cmath>
-#include <new>
 #include <string>
 
-#include "errors.h"
+#include "workspace.h"
 
 namespace vp {
 
@@ -190,47 +189,39 @@ __global__ __launch_bounds__(kFmLanes) void frame_metrics_final_kernel(const FmA
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------------------------
-static size_t fm_align(size_t n) { return (n + 255) & ~(size_t)255; }
-
-struct FmLayout {
-  size_t tiles_cap;                          // per frame
-  size_t part, abs_sum, sq_sum, total;
-};
-
 static int fm_tiles(int size) { return (size - (kFmTaps - 1) + kFmTile - 1) / kFmTile; }
 
-static int fm_layout(const vp_frame_metrics_desc* d, FmLayout* L) {
-  if (!d) { set_err("vp_frame_metrics: bad descriptor (null)"); return VP_ERR_ARG; }
-  if (d->struct_bytes != (uint32_t)sizeof(vp_frame_metrics_desc)) {
-    set_err("vp_frame_metrics: bad descriptor (struct_bytes %u, this library's vp_frame_metrics_desc is %d bytes)", d->struct_bytes,
-            (int)sizeof(vp_frame_metrics_desc));
-    return VP_ERR_ARG;
-  }
+}  // namespace vp
+
+struct vp_frame_metrics {
+  vp_frame_metrics_desc d;
+  vp::FmPartial* part;                       // [max_frames][tiles of the largest frame]
+  long long *abs_sum, *sq_sum;
+  double w[vp::kFmTaps];
+};
+
+using namespace vp;
+
+static int fm_check(const vp_frame_metrics_desc* d, vp_frame_metrics* h) {
+  if (const int rc = check_desc(d, "vp_frame_metrics")) return rc;
   if (d->max_frames < 1 || d->max_frames > VP_FRAME_METRICS_MAX_FRAMES) {
     set_err("vp_frame_metrics: bad descriptor (max_frames %d, 1 .. %d)", d->max_frames, VP_FRAME_METRICS_MAX_FRAMES);
     return VP_ERR_ARG;
   }
   if (d->max_height < kFmTaps || d->max_height > 8192) { set_err("vp_frame_metrics: bad descriptor (max_height %d, 11 .. 8192)", d->max_height); return VP_ERR_ARG; }
   if (d->max_width < kFmTaps || d->max_width > 8192) { set_err("vp_frame_metrics: bad descriptor (max_width %d, 11 .. 8192)", d->max_width); return VP_ERR_ARG; }
-  L->tiles_cap = (size_t)fm_tiles(d->max_height) * fm_tiles(d->max_width);
-  size_t o = 0;
-  L->part = o; o += fm_align((size_t)d->max_frames * L->tiles_cap * sizeof(FmPartial));
-  L->abs_sum = o; o += fm_align((size_t)d->max_frames * sizeof(long long));
-  L->sq_sum = o; o += fm_align((size_t)d->max_frames * sizeof(long long));
-  L->total = o + 256;
+  h->d = *d;
   return VP_OK;
 }
 
-}  // namespace vp
-
-struct vp_frame_metrics {
-  vp_frame_metrics_desc d;
-  vp::FmLayout L;
-  char* base;
-  double w[vp::kFmTaps];
-};
-
-using namespace vp;
+static size_t fm_carve(vp_frame_metrics* h, void* base) {
+  Arena ar(base);
+  const size_t frames = h->d.max_frames, tiles_cap = (size_t)fm_tiles(h->d.max_height) * fm_tiles(h->d.max_width);
+  h->part = ar.take<FmPartial>(frames * tiles_cap);
+  h->abs_sum = ar.take<long long>(frames);
+  h->sq_sum = ar.take<long long>(frames);
+  return align256(ar.total());
+}
 
 static int fm_run(vp_frame_metrics* h, const char* who, int elem, const void* a, size_t a_pitch, size_t a_stride, const void* b, size_t b_pitch,
                   size_t b_stride, int n, int H, int W, double scale, double offset, double* out, void* stream) {
@@ -263,9 +254,9 @@ static int fm_run(vp_frame_metrics* h, const char* who, int elem, const void* a,
   FmArgs g;
   memset(&g, 0, sizeof(g));
   g.a = a; g.b = b; g.a_pitch = a_pitch; g.a_stride = a_stride; g.b_pitch = b_pitch; g.b_stride = b_stride;
-  g.part = (FmPartial*)(h->base + h->L.part);
-  g.abs_sum = (long long*)(h->base + h->L.abs_sum);
-  g.sq_sum = (long long*)(h->base + h->L.sq_sum);
+  g.part = h->part;
+  g.abs_sum = h->abs_sum;
+  g.sq_sum = h->sq_sum;
   g.out = out;
   for (int k = 0; k < kFmTaps; ++k) g.w[k] = h->w[k];
   g.scale = scale; g.offset = offset;
@@ -285,25 +276,16 @@ extern "C" {
 size_t vp_frame_metrics_desc_size(void) { return sizeof(vp_frame_metrics_desc); }
 
 size_t vp_frame_metrics_workspace_bytes(const vp_frame_metrics_desc* d) {
-  FmLayout L;
-  return fm_layout(d, &L) ? 0 : L.total;
+  vp_frame_metrics h;
+  return fm_check(d, &h) ? 0 : fm_carve(&h, nullptr);
 }
 
 int vp_frame_metrics_create(const vp_frame_metrics_desc* d, void* workspace, size_t bytes, vp_frame_metrics_t** out) {
-  FmLayout L;
-  if (!out) { set_err("vp_frame_metrics_create: bad argument"); return VP_ERR_ARG; }
-  *out = nullptr;
-  const int rc = fm_layout(d, &L);
-  if (rc) return rc;
-  if (!workspace || bytes < L.total) { set_err("vp_frame_metrics_create: workspace too small (%zu of %zu bytes)", bytes, L.total); return VP_ERR_WORKSPACE; }
-  vp_frame_metrics* h = new (std::nothrow) vp_frame_metrics();
-  if (!h) { set_err("vp_frame_metrics_create: out of host memory"); return VP_ERR_STATE; }
-  h->d = *d; h->L = L;
-  h->base = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  if (const int rc = open_handle("vp_frame_metrics_create", d, fm_check, fm_carve, workspace, bytes, out)) return rc;
+  vp_frame_metrics* h = *out;
   double sum = 0.0;
   for (int i = 0; i < kFmTaps; ++i) { h->w[i] = exp(-(double)((i - 5) * (i - 5)) / (2.0 * 1.5 * 1.5)); sum += h->w[i]; }
   for (int i = 0; i < kFmTaps; ++i) h->w[i] /= sum;
-  *out = h;
   return VP_OK;
 }
 
@@ -323,8 +305,8 @@ int vp_frame_metrics_f32(vp_frame_metrics_t* h, const float* a, size_t a_row_pit
 int vp_frame_metrics_tensor(vp_frame_metrics_t* h, const char* name, void** ptr, int64_t shape[4]) {
   if (!h || !name || !ptr) { set_err("vp_frame_metrics_tensor: bad argument"); return VP_ERR_ARG; }
   const std::string s(name);
-  if (s == "abs_sum") *ptr = h->base + h->L.abs_sum;
-  else if (s == "sq_sum") *ptr = h->base + h->L.sq_sum;
+  if (s == "abs_sum") *ptr = h->abs_sum;
+  else if (s == "sq_sum") *ptr = h->sq_sum;
   else { set_err("vp_frame_metrics_tensor: no tensor '%s' (abs_sum, sq_sum)", name); return VP_ERR_ARG; }
   if (shape) { shape[0] = h->d.max_frames; shape[1] = shape[2] = shape[3] = 1; }
   return VP_OK;

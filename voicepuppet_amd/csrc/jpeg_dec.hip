@@ -20,10 +20,9 @@
 #include <stdint.h>
 #include <string.h>
 
-#include <new>
 #include <string>
 
-#include "errors.h"
+#include "workspace.h"
 
 namespace vp {
 
@@ -586,19 +585,24 @@ __global__ __launch_bounds__(256) void jpegdec_rgb_kernel(const DecArgs a) {
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------------------------
-static size_t dec_align(size_t n) { return (n + 255) & ~(size_t)255; }
+}  // namespace vp
 
-struct DecLayout {
+struct vp_jpegdec {
+  vp_jpegdec_desc d;
   int Hp, Wp, blocks_cap, rows_cap;
-  size_t coef, entries, planes, total;
+  short* coef;
+  int* entries;
+  unsigned char* planes;
+  // the index scan: scan_state null until vp_jpegdec_enable_scan
+  int chunk_bytes, max_rounds, chunks_cap, scan_slots;      // chunks of the largest file; files of one launch group
+  uint2* scan_state;
+  int *scan_ok, *scan_rounds;
 };
 
-static int dec_layout(const vp_jpegdec_desc* d, DecLayout* L) {
-  if (!d) { set_err("vp_jpegdec: bad descriptor (null)"); return VP_ERR_ARG; }
-  if (d->struct_bytes != (uint32_t)sizeof(vp_jpegdec_desc)) {
-    set_err("vp_jpegdec: bad descriptor (struct_bytes %u, this library's vp_jpegdec_desc is %d bytes)", d->struct_bytes, (int)sizeof(vp_jpegdec_desc));
-    return VP_ERR_ARG;
-  }
+using namespace vp;
+
+static int dec_check(const vp_jpegdec_desc* d, vp_jpegdec* h) {
+  if (const int rc = check_desc(d, "vp_jpegdec")) return rc;
   if (d->max_files < 1 || d->max_files > VP_JPEGDEC_MAX_FILES) { set_err("vp_jpegdec: bad descriptor (max_files %d, 1 .. %d)", d->max_files, VP_JPEGDEC_MAX_FILES); return VP_ERR_ARG; }
   if (d->max_height < 1 || d->max_height > 8192) { set_err("vp_jpegdec: bad descriptor (max_height %d, 1 .. 8192)", d->max_height); return VP_ERR_ARG; }
   if (d->max_width < 1 || d->max_width > 8192) { set_err("vp_jpegdec: bad descriptor (max_width %d, 1 .. 8192)", d->max_width); return VP_ERR_ARG; }
@@ -608,95 +612,71 @@ static int dec_layout(const vp_jpegdec_desc* d, DecLayout* L) {
     return VP_ERR_ARG;
   }
   if (d->bgr != 0 && d->bgr != 1) { set_err("vp_jpegdec: bad descriptor (bgr %d, 0 or 1)", d->bgr); return VP_ERR_ARG; }
-  L->Hp = (d->max_height + 15) & ~15;
-  L->Wp = (d->max_width + 15) & ~15;
-  L->blocks_cap = 3 * (L->Hp / 8) * (L->Wp / 8);         // 4:4:4; 4:2:0 needs half of it
-  L->rows_cap = L->Hp / 8;
-  size_t o = 0;
-  L->coef = o; o += dec_align((size_t)d->max_files * L->blocks_cap * 64 * sizeof(short));
-  L->entries = o; o += dec_align((size_t)d->max_files * L->rows_cap * 4 * sizeof(int));
-  L->planes = o; o += dec_align((size_t)d->max_files * 3 * L->Hp * L->Wp);
-  L->total = o + 256;
+  h->d = *d;
+  h->Hp = (d->max_height + 15) & ~15;
+  h->Wp = (d->max_width + 15) & ~15;
+  h->blocks_cap = 3 * (h->Hp / 8) * (h->Wp / 8);         // 4:4:4; 4:2:0 needs half of it
+  h->rows_cap = h->Hp / 8;
   return VP_OK;
 }
 
-struct ScanLayout {
-  int chunks_cap, slots;                     // chunks of the largest file; files of one launch group
-  size_t state, ok, rounds, total;
-};
+static size_t dec_carve(vp_jpegdec* h, void* base) {
+  Arena ar(base);
+  const size_t files = h->d.max_files;
+  h->coef = ar.take<short>(files * h->blocks_cap * 64);
+  h->entries = ar.take<int>(files * h->rows_cap * 4);
+  h->planes = ar.take<unsigned char>(files * 3 * h->Hp * h->Wp);
+  return align256(ar.total());
+}
 
-static int scan_layout(const vp_jpegdec_desc* d, int chunk_bytes, ScanLayout* S) {
-  DecLayout L;
-  const int rc = dec_layout(d, &L);
-  if (rc) return rc;
+static int scan_check(const vp_jpegdec_desc* d, int chunk_bytes, vp_jpegdec* h) {
+  if (const int rc = dec_check(d, h)) return rc;
   if (chunk_bytes < 32 || chunk_bytes > 4096 || (chunk_bytes & (chunk_bytes - 1))) {
     set_err("vp_jpegdec: bad scan chunk_bytes %d (a power of two, 32 .. 4096)", chunk_bytes);
     return VP_ERR_ARG;
   }
-  S->chunks_cap = (d->max_file_bytes + chunk_bytes - 1) / chunk_bytes;
-  S->slots = d->max_files < VP_JPEGDEC_FILES_PER_LAUNCH ? d->max_files : VP_JPEGDEC_FILES_PER_LAUNCH;
-  size_t o = 0;
-  S->state = o; o += dec_align((size_t)S->slots * S->chunks_cap * sizeof(uint2));     // launch groups run one after another on the stream
-  S->ok = o; o += dec_align((size_t)d->max_files * sizeof(int));
-  S->rounds = o; o += dec_align((size_t)d->max_files * sizeof(int));
-  S->total = o + 256;
+  h->chunk_bytes = chunk_bytes;
+  h->chunks_cap = (d->max_file_bytes + chunk_bytes - 1) / chunk_bytes;
+  h->scan_slots = d->max_files < VP_JPEGDEC_FILES_PER_LAUNCH ? d->max_files : VP_JPEGDEC_FILES_PER_LAUNCH;
   return VP_OK;
 }
 
-}  // namespace vp
-
-struct vp_jpegdec {
-  vp_jpegdec_desc d;
-  vp::DecLayout L;
-  char* base;
-  vp::ScanLayout S;                          // the index scan: scan_base null until vp_jpegdec_enable_scan
-  char* scan_base;
-  int chunk_bytes, max_rounds;
-};
-
-using namespace vp;
+static size_t scan_carve(vp_jpegdec* h, void* base) {
+  Arena ar(base);
+  h->scan_state = ar.take<uint2>((size_t)h->scan_slots * h->chunks_cap);     // launch groups run one after another on the stream
+  h->scan_ok = ar.take<int>(h->d.max_files);
+  h->scan_rounds = ar.take<int>(h->d.max_files);
+  return align256(ar.total());
+}
 
 extern "C" {
 
 size_t vp_jpegdec_desc_size(void) { return sizeof(vp_jpegdec_desc); }
 
 size_t vp_jpegdec_workspace_bytes(const vp_jpegdec_desc* d) {
-  DecLayout L;
-  return dec_layout(d, &L) ? 0 : L.total;
+  vp_jpegdec h;
+  return dec_check(d, &h) ? 0 : dec_carve(&h, nullptr);
 }
 
 int vp_jpegdec_create(const vp_jpegdec_desc* d, void* workspace, size_t bytes, vp_jpegdec_t** out) {
-  DecLayout L;
-  if (!out) { set_err("vp_jpegdec_create: bad argument"); return VP_ERR_ARG; }
-  *out = nullptr;
-  const int rc = dec_layout(d, &L);
-  if (rc) return rc;
-  if (!workspace || bytes < L.total) { set_err("vp_jpegdec_create: workspace too small (%zu of %zu bytes)", bytes, L.total); return VP_ERR_WORKSPACE; }
-  vp_jpegdec* h = new (std::nothrow) vp_jpegdec();
-  if (!h) { set_err("vp_jpegdec_create: out of host memory"); return VP_ERR_STATE; }
-  h->d = *d; h->L = L;
-  h->base = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-  h->scan_base = nullptr;
-  *out = h;
-  return VP_OK;
+  return open_handle("vp_jpegdec_create", d, dec_check, dec_carve, workspace, bytes, out);
 }
 
 size_t vp_jpegdec_scan_workspace_bytes(const vp_jpegdec_desc* d, int chunk_bytes) {
-  ScanLayout S;
-  return scan_layout(d, chunk_bytes, &S) ? 0 : S.total;
+  vp_jpegdec h;
+  return scan_check(d, chunk_bytes, &h) ? 0 : scan_carve(&h, nullptr);
 }
 
 int vp_jpegdec_enable_scan(vp_jpegdec_t* h, void* scan_workspace, size_t bytes, int chunk_bytes, int max_rounds) {
   if (!h) { set_err("vp_jpegdec_enable_scan: bad argument"); return VP_ERR_ARG; }
-  ScanLayout S;
-  const int rc = scan_layout(&h->d, chunk_bytes, &S);
-  if (rc) return rc;
+  vp_jpegdec s = *h;                                        // (a refusal leaves the handle as it was)
+  if (const int rc = scan_check(&h->d, chunk_bytes, &s)) return rc;
   if (max_rounds < 1 || max_rounds > 1024) { set_err("vp_jpegdec_enable_scan: bad max_rounds %d (1 .. 1024)", max_rounds); return VP_ERR_ARG; }
-  if (!scan_workspace || bytes < S.total) { set_err("vp_jpegdec_enable_scan: workspace too small (%zu of %zu bytes)", bytes, S.total); return VP_ERR_WORKSPACE; }
-  h->S = S;
-  h->scan_base = (char*)(((uintptr_t)scan_workspace + 255) & ~(uintptr_t)255);
-  h->chunk_bytes = chunk_bytes;
-  h->max_rounds = max_rounds;
+  const size_t need = scan_carve(&s, nullptr);
+  if (!scan_workspace || bytes < need) { set_err("vp_jpegdec_enable_scan: workspace too small (%zu of %zu bytes)", bytes, need); return VP_ERR_WORKSPACE; }
+  scan_carve(&s, scan_workspace);
+  s.max_rounds = max_rounds;
+  *h = s;
   return VP_OK;
 }
 
@@ -726,28 +706,27 @@ int vp_jpegdec_decode(vp_jpegdec_t* h, const unsigned char* blob, const vp_jpegd
       if (f.tq[c] > 3 || f.td[c] > 1 || f.ta[c] > 1) what = "table selector (tq 0 .. 3, td / ta 0 .. 1)";
     if (what) { set_err("vp_jpegdec_decode: file %d: %s", i, what); return VP_ERR_ARG; }
   }
-  const DecLayout& L = h->L;
   hipStream_t st = (hipStream_t)stream;
   VP_HIP_CHECK(hipMemsetAsync(status, 0, (size_t)n * sizeof(int), st));
-  if (h->scan_base) {                             // 0 for every file the scan does not run on
-    VP_HIP_CHECK(hipMemsetAsync(h->scan_base + h->S.ok, 0, (size_t)n * sizeof(int), st));
-    VP_HIP_CHECK(hipMemsetAsync(h->scan_base + h->S.rounds, 0, (size_t)n * sizeof(int), st));
+  if (h->scan_state) {                             // 0 for every file the scan does not run on
+    VP_HIP_CHECK(hipMemsetAsync(h->scan_ok, 0, (size_t)n * sizeof(int), st));
+    VP_HIP_CHECK(hipMemsetAsync(h->scan_rounds, 0, (size_t)n * sizeof(int), st));
   }
   for (int i0 = 0; i0 < n; i0 += VP_JPEGDEC_FILES_PER_LAUNCH) {
     const int m = n - i0 < VP_JPEGDEC_FILES_PER_LAUNCH ? n - i0 : VP_JPEGDEC_FILES_PER_LAUNCH;
     DecArgs a;
     memset(&a, 0, sizeof(a));
     a.blob = blob;
-    a.coef = (short*)(h->base + L.coef);
-    a.entries = (int*)(h->base + L.entries);
-    a.planes = (unsigned char*)(h->base + L.planes);
+    a.coef = h->coef;
+    a.entries = h->entries;
+    a.planes = h->planes;
     a.out = out; a.status = status; a.row_pitch = row_pitch; a.frame_stride = frame_stride;
-    a.first = i0; a.blocks_cap = L.blocks_cap; a.rows_cap = L.rows_cap; a.Hp = L.Hp; a.Wp = L.Wp; a.bgr = d.bgr;
-    if (h->scan_base) {
-      a.scan_state = (uint2*)(h->scan_base + h->S.state);
-      a.scan_ok = (int*)(h->scan_base + h->S.ok);
-      a.scan_rounds = (int*)(h->scan_base + h->S.rounds);
-      a.chunk_bytes = h->chunk_bytes; a.chunks_cap = h->S.chunks_cap; a.max_rounds = h->max_rounds;
+    a.first = i0; a.blocks_cap = h->blocks_cap; a.rows_cap = h->rows_cap; a.Hp = h->Hp; a.Wp = h->Wp; a.bgr = d.bgr;
+    if (h->scan_state) {
+      a.scan_state = h->scan_state;
+      a.scan_ok = h->scan_ok;
+      a.scan_rounds = h->scan_rounds;
+      a.chunk_bytes = h->chunk_bytes; a.chunks_cap = h->chunks_cap; a.max_rounds = h->max_rounds;
     }
     int max_seg = 1, max_blocks = 1, max_groups = 1, scans = 0;
     for (int i = 0; i < m; ++i) {
@@ -763,7 +742,7 @@ int vp_jpegdec_decode(vp_jpegdec_t* h, const unsigned char* blob, const vp_jpegd
       for (int c = 0; c < 3; ++c) { g.tq[c] = f.tq[c]; g.td[c] = f.td[c]; g.ta[c] = f.ta[c]; }
       const int blocks = (int)g.mcux * g.mcuy * (f.sampling == 2 ? 6 : 3);
       const int groups = ((f.width + 3) / 4) * f.height;
-      if (h->scan_base && f.n_segments == 1 && f.restart_interval == 0 && g.mcuy >= 2) {      // whether its segment is the whole scan: the kernel
+      if (h->scan_state && f.n_segments == 1 && f.restart_interval == 0 && g.mcuy >= 2) {      // whether its segment is the whole scan: the kernel
         g.scan = 1;
         ++scans;
         if (g.mcuy > max_seg) max_seg = g.mcuy;
@@ -789,14 +768,13 @@ int vp_jpegdec_decode(vp_jpegdec_t* h, const unsigned char* blob, const vp_jpegd
 int vp_jpegdec_tensor(vp_jpegdec_t* h, const char* name, void** ptr, int64_t shape[4]) {
   if (!h || !name || !ptr) { set_err("vp_jpegdec_tensor: bad argument"); return VP_ERR_ARG; }
   const std::string s(name);
-  const DecLayout& L = h->L;
   int64_t shp[4] = {h->d.max_files, 0, 0, 1};
-  if (s == "coefficients") { *ptr = h->base + L.coef; shp[1] = L.blocks_cap; shp[2] = 64; }
-  else if (s == "entries") { *ptr = h->base + L.entries; shp[1] = L.rows_cap; shp[2] = 4; }
-  else if (s == "planes") { *ptr = h->base + L.planes; shp[1] = 3; shp[2] = L.Hp; shp[3] = L.Wp; }
+  if (s == "coefficients") { *ptr = h->coef; shp[1] = h->blocks_cap; shp[2] = 64; }
+  else if (s == "entries") { *ptr = h->entries; shp[1] = h->rows_cap; shp[2] = 4; }
+  else if (s == "planes") { *ptr = h->planes; shp[1] = 3; shp[2] = h->Hp; shp[3] = h->Wp; }
   else if (s == "scan_ok" || s == "scan_rounds") {
-    if (!h->scan_base) { set_err("vp_jpegdec_tensor: '%s' needs vp_jpegdec_enable_scan", name); return VP_ERR_ARG; }
-    *ptr = h->scan_base + (s == "scan_ok" ? h->S.ok : h->S.rounds); shp[1] = 1; shp[2] = 1;
+    if (!h->scan_state) { set_err("vp_jpegdec_tensor: '%s' needs vp_jpegdec_enable_scan", name); return VP_ERR_ARG; }
+    *ptr = s == "scan_ok" ? h->scan_ok : h->scan_rounds; shp[1] = 1; shp[2] = 1;
   }
   else { set_err("vp_jpegdec_tensor: no tensor '%s' (coefficients, entries, planes, scan_ok, scan_rounds)", name); return VP_ERR_ARG; }
   if (shape) for (int i = 0; i < 4; ++i) shape[i] = shp[i];

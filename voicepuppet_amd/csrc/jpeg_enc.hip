@@ -30,11 +30,10 @@
 #include <stdint.h>
 #include <string.h>
 
-#include <new>
 #include <string>
 #include <vector>
 
-#include "errors.h"
+#include "workspace.h"
 
 namespace vp {
 
@@ -358,46 +357,7 @@ __global__ __launch_bounds__(kThreads) void jpeg_gather_kernel(const GatherArgs 
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------------------------
-static size_t align_up(size_t n) { return (n + 255) & ~(size_t)255; }
-
 constexpr int kMaxLds = 64 * 1024 - 64;      // the kernel's few static words beside the dynamic carve
-
-struct JpegLayout {
-  int rows, mcus, nblk, cap, lds_bytes;
-  size_t tables, header, lens, slots, coef, total;
-};
-
-static int jpeg_layout(const vp_jpeg_desc* d, JpegLayout* L) {
-  if (!d) { set_err("vp_jpeg: bad descriptor (null)"); return VP_ERR_ARG; }
-  if (d->struct_bytes != (uint32_t)sizeof(vp_jpeg_desc)) {
-    set_err("vp_jpeg: bad descriptor (struct_bytes %u, this library's vp_jpeg_desc is %d bytes)", d->struct_bytes, (int)sizeof(vp_jpeg_desc));
-    return VP_ERR_ARG;
-  }
-  if (d->max_frames < 1 || d->max_frames > VP_JPEG_MAX_FRAMES) { set_err("vp_jpeg: bad descriptor (max_frames %d, 1 .. %d)", d->max_frames, VP_JPEG_MAX_FRAMES); return VP_ERR_ARG; }
-  if (d->height < 16 || d->height % 16 || d->width < 16 || d->width % 16) {
-    set_err("vp_jpeg: bad descriptor (%d x %d: height and width must be multiples of 16, 4:2:0 MCUs)", d->height, d->width);
-    return VP_ERR_ARG;
-  }
-  if (d->quality < 1 || d->quality > 100) { set_err("vp_jpeg: bad descriptor (quality %d, 1 .. 100)", d->quality); return VP_ERR_ARG; }
-  if (d->height > 4096) { set_err("vp_jpeg: bad descriptor (height %d, up to 4096)", d->height); return VP_ERR_ARG; }
-  L->rows = d->height / 16; L->mcus = d->width / 16; L->nblk = 6 * L->mcus;
-  L->cap = VP_JPEG_SLOT_BYTES(d->width);
-  // the kernel's carve of dynamic LDS: tables, block offsets, coefficients, bit buffer
-  L->lds_bytes = 4 * (128 + kHuffWords + ((L->nblk + 2) & ~1)) + 2 * L->nblk * kBlockStride + 4 * (L->cap / 4 + 1);
-  if (L->lds_bytes > kMaxLds) {
-    set_err("vp_jpeg: bad descriptor (width %d: an MCU row's coefficients and bit buffer need %d bytes of LDS, 65536 at most; up to 832)", d->width, L->lds_bytes);
-    return VP_ERR_ARG;
-  }
-  const size_t n = (size_t)d->max_frames * L->rows;
-  size_t o = 0;
-  L->tables = o; o += align_up(sizeof(JpegTables));
-  L->header = o; o += align_up(1024);
-  L->lens = o; o += align_up(n * sizeof(int));
-  L->slots = o; o += align_up(n * L->cap);
-  L->coef = o; o += align_up(n * L->nblk * 64 * sizeof(short));
-  L->total = o + 256;
-  return VP_OK;
-}
 
 // libjpeg's jpeg_quality_scaling and jpeg_add_quant_table with force_baseline
 static void scaled_quant(const unsigned char* base, int quality, unsigned char* out) {
@@ -450,42 +410,70 @@ static std::vector<unsigned char> jpeg_header(const vp_jpeg_desc* d, const unsig
 
 struct vp_jpeg {
   vp_jpeg_desc d;
-  vp::JpegLayout L;
-  char* base;
+  int rows, mcus, nblk, cap, lds_bytes;
+  vp::JpegTables* tables;
+  unsigned char *header_dev, *slots;
+  int* lens;
+  short* coef;
   std::vector<unsigned char> header;
   bool keep_coef;         // set by the first vp_jpeg_tensor("coefficients"): encodes from then on also store them
 };
 
 using namespace vp;
 
+static int jpeg_check(const vp_jpeg_desc* d, vp_jpeg* h) {
+  if (const int rc = check_desc(d, "vp_jpeg")) return rc;
+  if (d->max_frames < 1 || d->max_frames > VP_JPEG_MAX_FRAMES) { set_err("vp_jpeg: bad descriptor (max_frames %d, 1 .. %d)", d->max_frames, VP_JPEG_MAX_FRAMES); return VP_ERR_ARG; }
+  if (d->height < 16 || d->height % 16 || d->width < 16 || d->width % 16) {
+    set_err("vp_jpeg: bad descriptor (%d x %d: height and width must be multiples of 16, 4:2:0 MCUs)", d->height, d->width);
+    return VP_ERR_ARG;
+  }
+  if (d->quality < 1 || d->quality > 100) { set_err("vp_jpeg: bad descriptor (quality %d, 1 .. 100)", d->quality); return VP_ERR_ARG; }
+  if (d->height > 4096) { set_err("vp_jpeg: bad descriptor (height %d, up to 4096)", d->height); return VP_ERR_ARG; }
+  h->d = *d;
+  h->rows = d->height / 16; h->mcus = d->width / 16; h->nblk = 6 * h->mcus;
+  h->cap = VP_JPEG_SLOT_BYTES(d->width);
+  // the kernel's carve of dynamic LDS: tables, block offsets, coefficients, bit buffer
+  h->lds_bytes = 4 * (128 + kHuffWords + ((h->nblk + 2) & ~1)) + 2 * h->nblk * kBlockStride + 4 * (h->cap / 4 + 1);
+  if (h->lds_bytes > kMaxLds) {
+    set_err("vp_jpeg: bad descriptor (width %d: an MCU row's coefficients and bit buffer need %d bytes of LDS, 65536 at most; up to 832)", d->width, h->lds_bytes);
+    return VP_ERR_ARG;
+  }
+  return VP_OK;
+}
+
+static size_t jpeg_carve(vp_jpeg* h, void* base) {
+  Arena ar(base);
+  const size_t n = (size_t)h->d.max_frames * h->rows;
+  h->tables = ar.take<JpegTables>(1);
+  h->header_dev = ar.take<unsigned char>(1024);
+  h->lens = ar.take<int>(n);
+  h->slots = ar.take<unsigned char>(n * h->cap);
+  h->coef = ar.take<short>(n * h->nblk * 64);
+  return align256(ar.total());
+}
+
 extern "C" {
 
 size_t vp_jpeg_desc_size(void) { return sizeof(vp_jpeg_desc); }
 
 size_t vp_jpeg_workspace_bytes(const vp_jpeg_desc* d) {
-  JpegLayout L;
-  return jpeg_layout(d, &L) ? 0 : L.total;
+  vp_jpeg h;
+  return jpeg_check(d, &h) ? 0 : jpeg_carve(&h, nullptr);
 }
 
 size_t vp_jpeg_frame_capacity(const vp_jpeg_desc* d) {
-  JpegLayout L;
-  if (jpeg_layout(d, &L)) return 0;
+  vp_jpeg h;
+  if (jpeg_check(d, &h)) return 0;
   unsigned char q[64] = {1};
   const size_t header = jpeg_header(d, q, q).size();
-  return align_up(header + (size_t)L.rows * (L.cap + 2));
+  return align256(header + (size_t)h.rows * (h.cap + 2));
 }
 
 int vp_jpeg_create(const vp_jpeg_desc* d, void* workspace, size_t bytes, void* stream, vp_jpeg_t** out) {
-  JpegLayout L;
-  if (!out) { set_err("vp_jpeg_create: bad argument"); return VP_ERR_ARG; }
-  *out = nullptr;
-  const int rc = jpeg_layout(d, &L);
-  if (rc) return rc;
-  if (!workspace || bytes < L.total) { set_err("vp_jpeg_create: workspace too small (%zu of %zu bytes)", bytes, L.total); return VP_ERR_WORKSPACE; }
-  vp_jpeg* h = new (std::nothrow) vp_jpeg();
-  if (!h) { set_err("vp_jpeg_create: out of host memory"); return VP_ERR_STATE; }
-  h->d = *d; h->L = L; h->keep_coef = false;
-  h->base = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  if (const int rc = open_handle("vp_jpeg_create", d, jpeg_check, jpeg_carve, workspace, bytes, out)) return rc;
+  vp_jpeg* h = *out;
+  h->keep_coef = false;
   unsigned char ql[64], qc[64];
   scaled_quant(kQLuma, d->quality, ql);
   scaled_quant(kQChroma, d->quality, qc);
@@ -499,11 +487,10 @@ int vp_jpeg_create(const vp_jpeg_desc* d, void* workspace, size_t bytes, void* s
   huff_codes(kDcChromaBits, kDcVals, tab.huff + 528);
   hipStream_t st = (hipStream_t)stream;
   // create is not an encode: it may wait (pageable sources), once per encoder
-  hipError_t e = hipMemcpyAsync(h->base + L.tables, &tab, sizeof(tab), hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(h->base + L.header, h->header.data(), h->header.size(), hipMemcpyHostToDevice, st);
+  hipError_t e = hipMemcpyAsync(h->tables, &tab, sizeof(tab), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(h->header_dev, h->header.data(), h->header.size(), hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) { set_err("vp_jpeg_create: table upload -> %s", hipGetErrorString(e)); delete h; return VP_ERR_HIP; }
-  *out = h;
+  if (e != hipSuccess) { set_err("vp_jpeg_create: table upload -> %s", hipGetErrorString(e)); delete h; *out = nullptr; return VP_ERR_HIP; }
   return VP_OK;
 }
 
@@ -515,22 +502,21 @@ int vp_jpeg_encode(vp_jpeg_t* h, const unsigned char* rgb, int frames, unsigned 
     return VP_ERR_ARG;
   }
   if ((uintptr_t)rgb & 3) { set_err("vp_jpeg_encode: the frames must start on a 4-byte boundary (the kernel reads them as dwords)"); return VP_ERR_ARG; }
-  const JpegLayout& L = h->L;
   IntervalArgs a{};
   a.rgb = rgb;
-  a.tab = (const JpegTables*)(h->base + L.tables);
-  a.slots = (unsigned char*)(h->base + L.slots);
-  a.lens = (int*)(h->base + L.lens);
-  a.coef = h->keep_coef ? (short*)(h->base + L.coef) : nullptr;
-  a.W = h->d.width; a.H = h->d.height; a.rows = L.rows; a.mcus = L.mcus; a.nblk = L.nblk; a.cap = L.cap;
-  hipLaunchKernelGGL(jpeg_interval_kernel, dim3(L.rows, frames), dim3(kThreads), (size_t)L.lds_bytes, (hipStream_t)stream, a);
+  a.tab = h->tables;
+  a.slots = h->slots;
+  a.lens = h->lens;
+  a.coef = h->keep_coef ? h->coef : nullptr;
+  a.W = h->d.width; a.H = h->d.height; a.rows = h->rows; a.mcus = h->mcus; a.nblk = h->nblk; a.cap = h->cap;
+  hipLaunchKernelGGL(jpeg_interval_kernel, dim3(h->rows, frames), dim3(kThreads), (size_t)h->lds_bytes, (hipStream_t)stream, a);
   VP_HIP_CHECK(hipGetLastError());
   GatherArgs g{};
   g.slots = a.slots; g.lens = a.lens;
-  g.header = (const unsigned char*)(h->base + L.header);
+  g.header = h->header_dev;
   g.out = out; g.out_bytes = out_bytes; g.out_row_bytes = out_row_bytes;
-  g.rows = L.rows; g.cap = L.cap; g.header_len = (int)h->header.size();
-  hipLaunchKernelGGL(jpeg_gather_kernel, dim3(L.rows, frames), dim3(kThreads), 0, (hipStream_t)stream, g);
+  g.rows = h->rows; g.cap = h->cap; g.header_len = (int)h->header.size();
+  hipLaunchKernelGGL(jpeg_gather_kernel, dim3(h->rows, frames), dim3(kThreads), 0, (hipStream_t)stream, g);
   VP_HIP_CHECK(hipGetLastError());
   return VP_OK;
 }
@@ -539,8 +525,8 @@ int vp_jpeg_tensor(vp_jpeg_t* h, const char* name, void** ptr, int64_t shape[4])
   if (!h || !name || !ptr) { set_err("vp_jpeg_tensor: bad argument"); return VP_ERR_ARG; }
   if (std::string(name) != "coefficients") { set_err("vp_jpeg_tensor: no tensor '%s' (coefficients)", name); return VP_ERR_ARG; }
   h->keep_coef = true;
-  *ptr = h->base + h->L.coef;
-  if (shape) { shape[0] = h->d.max_frames; shape[1] = h->L.rows; shape[2] = h->L.nblk; shape[3] = 64; }
+  *ptr = h->coef;
+  if (shape) { shape[0] = h->d.max_frames; shape[1] = h->rows; shape[2] = h->nblk; shape[3] = 64; }
   return VP_OK;
 }
 

@@ -17,12 +17,9 @@
 #include "errors.h"
 #include "launch.h"
 #include "vp_common.h"
+#include "workspace.h"
 
 using namespace vp;
-
-namespace {
-size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
-}
 
 extern "C" {
 
@@ -32,16 +29,16 @@ size_t vp_mm_workspace_bytes(int P, int K, int N) {
   {
     ConvGeomX g = make_geom(0, 1, 1, 0, 1, P, 1, round_up(K, 16), K, N);
     IgemmPlan p = plan_fwd(g, 0, 0);
-    best = al256(p.pack_elems * 4) + al256(p.partial_bytes);
+    best = align256(p.pack_elems * 4) + align256(p.partial_bytes);
   }
   {
     ConvGeomX g = make_geom(0, 1, 1, 0, 1, P, 1, K, K, round_up(N, 16));
     g.CoutT = round_up(N, 16);
     IgemmPlan p = plan_bwd_data(g, 0, 0, K, K, K, 0);
-    const size_t b = al256(p.pack_elems * 4) + al256(p.partial_bytes);
+    const size_t b = align256(p.pack_elems * 4) + align256(p.partial_bytes);
     if (b > best) best = b;
     WgradPlan w = plan_wgrad(g, 0, true);
-    if (al256(w.partial_bytes) > best) best = al256(w.partial_bytes);
+    if (align256(w.partial_bytes) > best) best = align256(w.partial_bytes);
   }
   return best + 1024 + 256;
 }
@@ -92,7 +89,7 @@ int vp_mm_fwd_f32(const float* x, int ldx, const float* w, int ldw, int w_transp
   hipStream_t st = (hipStream_t)stream;
   IgemmPlan p = mm_fwd_plan(P, K, N, ldw, w_transposed);
   // workspace: zero page | split-K slabs | packed copy of w
-  char* pk = (char*)workspace + 256 + al256(p.partial_bytes);
+  char* pk = (char*)workspace + 256 + align256(p.partial_bytes);
   VP_HIP_CHECK(launch_pack_weights_one(p.pack, w, pk, 0, st));
   return mm_fwd_run(p, x, ldx, pk, bias, y, ldy, workspace, st);
 }
@@ -104,7 +101,7 @@ int vp_mm_bwd_data_f32(const float* dy, int lddy, const float* w, int ldw, int w
   if (!dy || !w || !dx || !workspace || P < 1 || K < 1 || N < 1 || lddy < Np || lddy % 4 || lddx < K) { set_err("vp_mm_bwd_data_f32: bad argument"); return VP_ERR_ARG; }
   hipStream_t st = (hipStream_t)stream;
   IgemmPlan p = mm_bwd_plan(P, K, N, ldw, w_transposed, lddx);
-  char* pk = (char*)workspace + 256 + al256(p.partial_bytes);
+  char* pk = (char*)workspace + 256 + align256(p.partial_bytes);
   VP_HIP_CHECK(launch_pack_weights_one(p.pack, w, pk, 0, st));
   return mm_bwd_run(p, dy, lddy, pk, dx, lddx, accumulate, workspace, st);
 }
@@ -114,7 +111,7 @@ int vp_mm_bwd_data_f32(const float* dy, int lddy, const float* w, int ldw, int w
 size_t vp_mm_packed_bytes(int P, int K, int N, int dir) {
   if (P < 1 || K < 1 || N < 1) return 0;
   const IgemmPlan p = dir ? mm_bwd_plan(P, K, N, N, 0, K) : mm_fwd_plan(P, K, N, N, 0);
-  return al256(p.pack_elems * sizeof(float));
+  return align256(p.pack_elems * sizeof(float));
 }
 size_t vp_mm_pack_desc_bytes(void) { return sizeof(PackDesc); }
 // host: descriptor of one matrix for vp_mm_pack_table (w = master + w_off floats; packed block at packed + dst_off floats)

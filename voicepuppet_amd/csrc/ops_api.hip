@@ -8,6 +8,7 @@
 #include "audio_args.h"
 #include "launch.h"
 #include "vp_common.h"
+#include "workspace.h"
 
 using namespace vp;
 
@@ -26,8 +27,6 @@ bool conv_desc_ok(const vp_conv_desc* d) {
 ConvGeomX geom_of(const vp_conv_desc* d) {
   return make_geom(d->kind, d->ksize, d->stride, d->pad, d->n, d->h, d->w, d->cin, d->cin, d->cout);
 }
-
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // 256 zero bytes behind the op's workspace use (padding source of the LDS-DMA loader)
 const void* zero_page(char* ws, size_t used, hipStream_t st) {

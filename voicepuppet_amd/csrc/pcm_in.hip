@@ -23,10 +23,9 @@
 #include <stdint.h>
 #include <string.h>
 
-#include <new>
 #include <vector>
 
-#include "errors.h"
+#include "workspace.h"
 
 namespace vp {
 
@@ -232,17 +231,25 @@ static long long pcm_samples_after(const PcmRatio& r, long long n, int finished)
   return cnt < total ? cnt : total;
 }
 
-struct PcmLayout {
-  int n_rates;
-  PcmRatio ratio[8];
+struct PcmSlot { int rate, channels, format, parity; bool open, finished; long long n_in, n_out; };
+
+}  // namespace vp
+
+struct vp_pcmin {
+  vp_pcmin_desc d;
+  vp::PcmRatio ratio[8];
   int Hn[8], bank_off[8];
   int hist_stride;
-  size_t rates_off, banks_off, hist_off, total;
+  size_t bank_floats;
+  vp::PcmRate* rates;
+  float *banks, *hist;
+  vp::PcmSlot slot[VP_PCMIN_MAX_SLOTS];
 };
 
-static size_t pcm_align(size_t v) { return (v + 255) & ~(size_t)255; }
+using namespace vp;
 
-static int pcm_layout(const vp_pcmin_desc* d, PcmLayout* L) {
+// (this family's null and struct_bytes refusals keep their own wording, which is older than check_desc's)
+static int pcm_check(const vp_pcmin_desc* d, vp_pcmin* h) {
   if (!d) { set_err("vp_pcmin: null descriptor"); return VP_ERR_ARG; }
   if (d->struct_bytes != (int)sizeof(vp_pcmin_desc)) {
     set_err("vp_pcmin_desc: struct_bytes is %d, this library's descriptor has %zu (the struct grows at the tail only)", d->struct_bytes, sizeof(vp_pcmin_desc));
@@ -252,11 +259,11 @@ static int pcm_layout(const vp_pcmin_desc* d, PcmLayout* L) {
   if (d->out_rate < 1000 || d->out_rate > 1000000) { set_err("vp_pcmin_desc: out_rate = %d, 1000 .. 1000000 (the model's is 16000)", d->out_rate); return VP_ERR_ARG; }
   if (d->max_in_frames < 1 || d->max_in_frames > kPcmMaxIn) { set_err("vp_pcmin_desc: max_in_frames = %d, 1 .. %d", d->max_in_frames, kPcmMaxIn); return VP_ERR_ARG; }
   if (d->n_rates < 1 || d->n_rates > 8) { set_err("vp_pcmin_desc: n_rates = %d, 1 .. 8", d->n_rates); return VP_ERR_ARG; }
-  L->n_rates = d->n_rates;
-  size_t bank_floats = 0;
-  int hmax = 4;
+  h->d = *d;
+  h->bank_floats = 0;
+  h->hist_stride = 4;
   for (int i = 0; i < d->n_rates; ++i) {
-    PcmRatio& r = L->ratio[i];
+    PcmRatio& r = h->ratio[i];
     if (pcm_ratio(d->rates[i], d->out_rate, &r)) { set_err("vp_pcmin_desc: rates[%d] = %d is no sample rate (1 .. 1000000 Hz)", i, d->rates[i]); return VP_ERR_ARG; }
     for (int j = 0; j < i; ++j)
       if (d->rates[j] == d->rates[i]) { set_err("vp_pcmin_desc: rates[%d] = %d is listed twice", i, d->rates[i]); return VP_ERR_ARG; }
@@ -267,31 +274,21 @@ static int pcm_layout(const vp_pcmin_desc* d, PcmLayout* L) {
               i, d->rates[i], r.up, r.down, bytes, kPcmBankCap, span, kPcmSpan);
       return VP_ERR_ARG;
     }
-    L->Hn[i] = (r.T + 3) & ~3;
-    L->bank_off[i] = (int)bank_floats;
-    bank_floats += (r.up == r.down) ? 4 : (((size_t)r.up * r.T + 3) & ~(size_t)3);
-    if (L->Hn[i] > hmax) hmax = L->Hn[i];
+    h->Hn[i] = (r.T + 3) & ~3;
+    h->bank_off[i] = (int)h->bank_floats;
+    h->bank_floats += (r.up == r.down) ? 4 : (((size_t)r.up * r.T + 3) & ~(size_t)3);
+    if (h->Hn[i] > h->hist_stride) h->hist_stride = h->Hn[i];
   }
-  L->hist_stride = hmax;
-  L->rates_off = 0;
-  L->banks_off = pcm_align(8 * sizeof(PcmRate));
-  L->hist_off = L->banks_off + pcm_align(bank_floats * sizeof(float));
-  L->total = L->hist_off + pcm_align((size_t)d->slots * 2 * hmax * sizeof(float)) + 256;
   return VP_OK;
 }
 
-struct PcmSlot { int rate, channels, format, parity; bool open, finished; long long n_in, n_out; };
-
-}  // namespace vp
-
-struct vp_pcmin {
-  vp_pcmin_desc d;
-  vp::PcmLayout L;
-  char* base;
-  vp::PcmSlot slot[VP_PCMIN_MAX_SLOTS];
-};
-
-using namespace vp;
+static size_t pcm_carve(vp_pcmin* h, void* base) {
+  Arena ar(base);
+  h->rates = ar.take<PcmRate>(8);
+  h->banks = ar.take<float>(h->bank_floats);
+  h->hist = ar.take<float>((size_t)h->d.slots * 2 * h->hist_stride);
+  return align256(ar.total());
+}
 
 // the counts of one push, host only: 0, or VP_ERR_ARG with the message set
 static int pcm_counts(const vp_pcmin_t* h, const char* who, const long long* in_frames, const int* finish, long long* out_samples, long long* total) {
@@ -306,7 +303,7 @@ static int pcm_counts(const vp_pcmin_t* h, const char* who, const long long* in_
       if (!S.open) { set_err("%s: slot %d is not open (vp_pcmin_open_slot)", who, s); return VP_ERR_ARG; }
       if (S.finished) { set_err("%s: slot %d has finished its clip (vp_pcmin_open_slot restarts it)", who, s); return VP_ERR_ARG; }
       if (S.n_in + n > (1LL << 40)) { set_err("%s: slot %d: more than 2^40 frames in one clip", who, s); return VP_ERR_ARG; }
-      k = pcm_samples_after(h->L.ratio[S.rate], S.n_in + n, fin) - S.n_out;
+      k = pcm_samples_after(h->ratio[S.rate], S.n_in + n, fin) - S.n_out;
     }
     if (out_samples) out_samples[s] = k;
     *total += k;
@@ -346,34 +343,26 @@ long long vp_pcmin_samples_after(int in_rate, int out_rate, long long in_frames,
 }
 
 size_t vp_pcmin_workspace_bytes(const vp_pcmin_desc* d) {
-  PcmLayout L;
-  return pcm_layout(d, &L) ? 0 : L.total;
+  vp_pcmin h;
+  return pcm_check(d, &h) ? 0 : pcm_carve(&h, nullptr);
 }
 
 int vp_pcmin_create(const vp_pcmin_desc* d, void* workspace, size_t bytes, void* stream, vp_pcmin_t** out) {
-  PcmLayout L;
-  if (!out) { set_err("vp_pcmin_create: bad argument"); return VP_ERR_ARG; }
-  *out = nullptr;
-  const int rc = pcm_layout(d, &L);
-  if (rc) return rc;
-  if (!workspace || bytes < L.total) { set_err("vp_pcmin_create: workspace too small (%zu of %zu bytes)", bytes, L.total); return VP_ERR_WORKSPACE; }
-  vp_pcmin* h = new (std::nothrow) vp_pcmin();
-  if (!h) { set_err("vp_pcmin_create: out of host memory"); return VP_ERR_STATE; }
-  h->d = *d; h->L = L;
-  h->base = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  if (const int rc = open_handle("vp_pcmin_create", d, pcm_check, pcm_carve, workspace, bytes, out)) return rc;
+  vp_pcmin* h = *out;
   memset(h->slot, 0, sizeof(h->slot));
   // the rate table and the polyphase banks [phase][tap], from the float32 filter: bank[p][t] = h[p + t up]
   PcmRate rates[8];
   memset(rates, 0, sizeof(rates));
-  std::vector<float> banks((L.hist_off - L.banks_off) / sizeof(float), 0.0f), hf;
-  for (int i = 0; i < L.n_rates; ++i) {
-    const PcmRatio& r = L.ratio[i];
-    rates[i] = PcmRate{r.up, r.down, r.half, r.T, L.Hn[i], L.bank_off[i]};
+  std::vector<float> banks(align256(h->bank_floats * sizeof(float)) / sizeof(float), 0.0f), hf;      // (zeros up to the end of the carve)
+  for (int i = 0; i < d->n_rates; ++i) {
+    const PcmRatio& r = h->ratio[i];
+    rates[i] = PcmRate{r.up, r.down, r.half, r.T, h->Hn[i], h->bank_off[i]};
     if (r.up == r.down) continue;
     const int N = 2 * r.half + 1;
     hf.assign(N, 0.0f);
     pcm_bank(r, hf.data());
-    float* b = banks.data() + L.bank_off[i];
+    float* b = banks.data() + h->bank_off[i];
     for (int p = 0; p < r.up; ++p)
       for (int t = 0; t < r.T; ++t) {
         const long long j = (long long)p + (long long)t * r.up;
@@ -382,12 +371,11 @@ int vp_pcmin_create(const vp_pcmin_desc* d, void* workspace, size_t bytes, void*
   }
   hipStream_t st = (hipStream_t)stream;
   // create is not a push: it may wait (pageable sources), once per handle
-  hipError_t e = hipMemcpyAsync(h->base + L.rates_off, rates, sizeof(rates), hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(h->base + L.banks_off, banks.data(), banks.size() * sizeof(float), hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemsetAsync(h->base + L.hist_off, 0, (size_t)d->slots * 2 * L.hist_stride * sizeof(float), st);
+  hipError_t e = hipMemcpyAsync(h->rates, rates, sizeof(rates), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(h->banks, banks.data(), banks.size() * sizeof(float), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemsetAsync(h->hist, 0, (size_t)d->slots * 2 * h->hist_stride * sizeof(float), st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) { set_err("vp_pcmin_create: table upload -> %s", hipGetErrorString(e)); delete h; return VP_ERR_HIP; }
-  *out = h;
+  if (e != hipSuccess) { set_err("vp_pcmin_create: table upload -> %s", hipGetErrorString(e)); delete h; *out = nullptr; return VP_ERR_HIP; }
   return VP_OK;
 }
 
@@ -404,8 +392,7 @@ int vp_pcmin_open_slot(vp_pcmin_t* h, int slot, int in_rate, int channels, int f
   if (ri < 0) { set_err("vp_pcmin_open_slot: in_rate = %d is not among the rates of the descriptor", in_rate); return VP_ERR_ARG; }
   PcmSlot& S = h->slot[slot];
   // an empty clip has a zero history; the buffer the next push reads is zeroed in stream order
-  VP_HIP_CHECK(hipMemsetAsync(h->base + h->L.hist_off + ((size_t)slot * 2 + S.parity) * h->L.hist_stride * sizeof(float), 0,
-                              h->L.hist_stride * sizeof(float), (hipStream_t)stream));
+  VP_HIP_CHECK(hipMemsetAsync(h->hist + ((size_t)slot * 2 + S.parity) * h->hist_stride, 0, h->hist_stride * sizeof(float), (hipStream_t)stream));
   S.rate = ri; S.channels = channels; S.format = format;
   S.open = true; S.finished = false; S.n_in = 0; S.n_out = 0;
   return VP_OK;
@@ -425,10 +412,10 @@ int vp_pcmin_push(vp_pcmin_t* h, const void* raw, const long long* in_frames, co
   if (total > 0x7fffffffLL) { set_err("vp_pcmin_push: %lld output samples in one push", total); return VP_ERR_ARG; }
   PcmArgs a;
   a.raw = (const unsigned char*)raw; a.out = pcm_out;
-  a.hist = (float*)(h->base + h->L.hist_off);
-  a.banks = (const float*)(h->base + h->L.banks_off);
-  a.rates = (const PcmRate*)(h->base + h->L.rates_off);
-  a.hist_stride = h->L.hist_stride;
+  a.hist = h->hist;
+  a.banks = h->banks;
+  a.rates = h->rates;
+  a.hist_stride = h->hist_stride;
   int ne = 0, tiles = 0, nh = 0;
   size_t raw_bytes = 0;
   long long out_off = 0, in_total = 0;
@@ -436,7 +423,7 @@ int vp_pcmin_push(vp_pcmin_t* h, const void* raw, const long long* in_frames, co
     const long long n = in_frames ? in_frames[s] : 0;
     if (n == 0 && k[s] == 0) continue;
     const PcmSlot& S = h->slot[s];
-    const PcmRatio& r = h->L.ratio[S.rate];
+    const PcmRatio& r = h->ratio[S.rate];
     PcmEntry& e = a.e[ne];
     raw_bytes = (raw_bytes + 15) & ~(size_t)15;
     if ((raw_bytes >> 4) > 0xffffffffull) { set_err("vp_pcmin_push: more than 64 GB of raw samples in one push"); return VP_ERR_ARG; }
@@ -445,7 +432,7 @@ int vp_pcmin_push(vp_pcmin_t* h, const void* raw, const long long* in_frames, co
     e.n_new = (int)n; e.n_out = (int)k[s]; e.out_off = (int)out_off; e.tile0 = tiles;
     // first output m0 = n_out so far: q = m0 down + half, newest input k1 = q / up, as an index into [history (n_in - Hn ..) ++ new]
     const long long q = S.n_out * r.down + r.half;
-    e.kbase = (int)(q / r.up - (S.n_in - h->L.Hn[S.rate]));
+    e.kbase = (int)(q / r.up - (S.n_in - h->Hn[S.rate]));
     e.cfg = (uint32_t)(q % r.up) | (uint32_t)S.rate << 16 | (uint32_t)(S.channels - 1) << 19 | (uint32_t)S.format << 22 | (uint32_t)S.parity << 23 | (uint32_t)s << 24;
     tiles += (int)((k[s] + kPcmThreads - 1) / kPcmThreads);
     if (n) a.hist_entry[nh++] = (unsigned char)ne;

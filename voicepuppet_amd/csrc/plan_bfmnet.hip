@@ -18,15 +18,11 @@
 #include "errors.h"
 #include "launch.h"
 #include "vp_common.h"
+#include "workspace.h"
 
 using namespace vp;
 
 namespace {
-
-struct Bump {
-  char* base; size_t off;
-  void* alloc(size_t bytes) { off = (off + 255) & ~(size_t)255; void* p = base ? base + off : nullptr; off += bytes; return p; }
-};
 
 // a 1x1 conv / dense layer as an igemm over `pixels` rows
 struct Gemm {
@@ -58,7 +54,7 @@ struct vp_logmel {
 };
 
 static size_t logmel_carve(vp_logmel* h, char* base) {
-  Bump ar{base, 0};
+  Arena ar(base);
   const vp_logmel_desc& d = h->d;
   h->frames = 1 + (d.samples - d.win_length) / d.hop_step;
   h->nb = d.fft_length / 2 + 1;
@@ -77,7 +73,7 @@ static size_t logmel_carve(vp_logmel* h, char* base) {
   h->packed = (char*)ar.alloc(h->plan.pack_elems * sizeof(float));
   h->scratch = (char*)ar.alloc(h->plan.partial_bytes + 256);
   h->zeros = ar.alloc(256);
-  return ar.off + 256;
+  return ar.total();
 }
 
 static bool logmel_ok(const vp_logmel_desc* d) {
@@ -287,12 +283,12 @@ void plan_gemm(vp_bfmnet* h, Gemm& g, int pixels, int cin, int cout, int which, 
   g.plan.pack.s_ch = src_ld;      // row stride of the [cin, cout] source matrix (HWIO with H = W = 1)
   g.pk = h->packed_elems;         // (bytes: the arena mixes bf16 and f32 blocks; every block is packed relative to its own base)
   g.plan.pack.dst_off = 0;
-  h->packed_elems += (g.plan.pack_elems * (bf ? 2 : 4) + 255) & ~(size_t)255;
+  h->packed_elems += align256(g.plan.pack_elems * (bf ? 2 : 4));
   if (g.plan.partial_bytes > h->scratch_bytes) h->scratch_bytes = g.plan.partial_bytes;
 }
 
 size_t bfm_carve(vp_bfmnet* h, char* base) {
-  Bump ar{base, 0};
+  Arena ar(base);
   const int B = h->d.batch, T = h->d.frames;
   h->T5 = 5 * T;
   BfmModel& m = h->m;
@@ -344,7 +340,7 @@ size_t bfm_carve(vp_bfmnet* h, char* base) {
   h->dd1 = (float*)ar.alloc((size_t)BT * 64 * 4);
   h->scratch = (char*)ar.alloc(h->scratch_bytes + 256);
   h->zeros = ar.alloc(256);
-  return ar.off + 256;
+  return ar.total();
 }
 
 bool bfm_ok(const vp_bfmnet_desc* d) {
@@ -730,7 +726,7 @@ struct vp_bfmstream_group {
 };
 
 static size_t group_carve(vp_bfmstream_group* G, char* base, vp_logmel_desc* lmd) {
-  Bump ar{base, 0};
+  Arena ar(base);
   const StreamGeo& g = G->g;
   const size_t S = G->d.slots, nmel = G->d.num_mel_bins;
   G->carry = (float*)ar.alloc(S * 2 * kGroupCarry * 4);
@@ -753,7 +749,7 @@ static size_t group_carve(vp_bfmstream_group* G, char* base, vp_logmel_desc* lmd
   for (int t = 1; t < g.Tw; ++t) { const size_t b = bfm_plan_bytes(&tmp, t); if (b > sb) sb = b; }
   G->short_bytes = sb;
   G->short_base = (char*)ar.alloc(sb);
-  return ar.off + 256;
+  return ar.total();
 }
 
 // the layout of a descriptor's group (plans made, nothing carved on memory); VP_ERR_ARG with the reason on a refused descriptor

@@ -23,6 +23,7 @@
 #include "launch.h"
 #include "smallp_args.h"
 #include "vp_common.h"
+#include "workspace.h"
 
 namespace vp {
 
@@ -33,19 +34,6 @@ void set_err(const char* fmt, ...) {
   vsnprintf(g_err, sizeof(g_err), fmt, ap);
   va_end(ap);
 }
-
-struct Arena {
-  char* base;
-  size_t off, cap;
-  std::vector<std::pair<size_t, size_t>>* track = nullptr;   // (offset, bytes) of every carve: vp_pixrefer_validate_plan
-  void* alloc(size_t bytes) {
-    off = (off + 255) & ~(size_t)255;
-    void* p = base ? base + off : nullptr;
-    if (track) track->push_back({off, bytes});
-    off += bytes;
-    return p;
-  }
-};
 
 struct BnBuf {
   float *a, *b, *mu, *rstd, *c1, *c2, *c1g, *c2g;   // c1g / c2g: the generator-loss pass through the discriminator
@@ -575,7 +563,7 @@ static void carve_net(Net& n, Arena& ar, int es, bool training) {
 }
 
 static size_t carve_all(vp_pixrefer* h, char* base, size_t cap, std::vector<std::pair<size_t, size_t>>* track = nullptr) {
-  Arena ar{base, 0, cap};
+  Arena ar(base);
   ar.track = track;
   const vp_pixrefer_desc& d = h->d;
   const int N = d.batch, H = d.height, es = h->es;
@@ -624,7 +612,7 @@ static size_t carve_all(vp_pixrefer* h, char* base, size_t cap, std::vector<std:
     h->lane[k].bn_partial = (double*)ar.alloc((size_t)1024 * 2 * 512 * sizeof(double));
     h->lane[k].scratch = (char*)ar.alloc(h->scratch_bytes);
   }
-  return ar.off + 256;
+  return ar.total();
 }
 
 // the backward-data launch of a VGG conv below a pool in its pooled-source form (see vp_pixrefer::pool_fuse_ok), as launch_view shows it

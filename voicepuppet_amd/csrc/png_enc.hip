@@ -32,11 +32,10 @@
 #include <stdint.h>
 #include <string.h>
 
-#include <new>
 #include <string>
 #include <vector>
 
-#include "errors.h"
+#include "workspace.h"
 
 namespace vp {
 
@@ -541,47 +540,6 @@ __global__ __launch_bounds__(kThreads) void png_gather_kernel(const GatherArgs a
 // ---- host -------------------------------------------------------------------------------------------------------------------------------
 static size_t align_up(size_t n, size_t to) { return (n + to - 1) / to * to; }
 
-struct Layout {
-  int R, strips, WC, RB, slot_bytes, region_a, lds_bytes;
-  size_t header, meta, slots, total, capacity;
-};
-
-static int layout(const vp_png_desc* d, Layout* L) {
-  if (!d) { set_err("vp_png: bad descriptor (null)"); return VP_ERR_ARG; }
-  if (d->struct_bytes != (uint32_t)sizeof(vp_png_desc)) {
-    set_err("vp_png: bad descriptor (struct_bytes %u, this library's vp_png_desc is %d bytes)", d->struct_bytes, (int)sizeof(vp_png_desc));
-    return VP_ERR_ARG;
-  }
-  if (d->max_frames < 1 || d->max_frames > VP_PNG_MAX_FRAMES) { set_err("vp_png: bad descriptor (max_frames %d, 1 .. %d)", d->max_frames, VP_PNG_MAX_FRAMES); return VP_ERR_ARG; }
-  if (d->height < 1 || d->height > VP_PNG_MAX_HEIGHT) { set_err("vp_png: bad descriptor (height %d, 1 .. %d)", d->height, VP_PNG_MAX_HEIGHT); return VP_ERR_ARG; }
-  if (d->channels != 1 && d->channels != 3 && d->channels != 4) { set_err("vp_png: bad descriptor (channels %d: 1, 3 or 4)", d->channels); return VP_ERR_ARG; }
-  if (d->filter < -1 || d->filter > 4) { set_err("vp_png: bad descriptor (filter %d: -1 adaptive, 0 .. 4 forced)", d->filter); return VP_ERR_ARG; }
-  if (d->width < 1 || (long long)d->width * d->channels > VP_PNG_MAX_ROW_BYTES) {
-    set_err("vp_png: bad descriptor (width %d x %d channels: 1 .. %d bytes per row, a strip lives in one workgroup's LDS)", d->width, d->channels, VP_PNG_MAX_ROW_BYTES);
-    return VP_ERR_ARG;
-  }
-  L->WC = d->width * d->channels;
-  L->RB = L->WC + 1;
-  int R = (kLdsBudget - 32 - L->WC) / (2 * L->WC + 1);
-  L->R = R > kMaxRows ? kMaxRows : R;                                     // >= 1 up to VP_PNG_MAX_ROW_BYTES
-  L->strips = (d->height + L->R - 1) / L->R;
-  const int chunk = 12 + L->R * L->RB + 10;
-  L->slot_bytes = (int)align_up((size_t)chunk + 4, 16);
-  const int raw = (L->R + 1) * L->WC;
-  L->region_a = (int)align_up((size_t)(raw > chunk + 12 ? raw : chunk + 12), 16);
-  L->lds_bytes = L->region_a + (int)align_up((size_t)L->R * L->RB, 16);
-  L->capacity = kHeaderBytes + kTrailerBytes;
-  for (int y = 0; y < d->height; y += L->R) L->capacity += 12 + (size_t)(d->height - y < L->R ? d->height - y : L->R) * L->RB + 10;
-  if (L->capacity > 0x7fffffffu) { set_err("vp_png: bad descriptor (%d x %d x %d: a file of up to %zu bytes, lengths are 31 bits)", d->height, d->width, d->channels, L->capacity); return VP_ERR_ARG; }
-  const size_t n = (size_t)d->max_frames * L->strips;
-  size_t o = 0;
-  L->header = o; o += align_up(kHeaderBytes, 256);
-  L->meta = o; o += align_up(n * 4 * sizeof(int), 256);
-  L->slots = o; o += align_up(n * L->slot_bytes, 256);
-  L->total = o + 256;
-  return VP_OK;
-}
-
 static uint32_t host_crc(const unsigned char* p, size_t n) {
   uint32_t c = 0xffffffffu;
   for (size_t i = 0; i < n; ++i) {
@@ -617,51 +575,80 @@ static std::vector<unsigned char> file_header(const vp_png_desc* d) {
 
 struct vp_png {
   vp_png_desc d;
-  vp::png::Layout L;
-  char* base;
+  int R, strips, WC, RB, slot_bytes, region_a, lds_bytes;
+  size_t capacity;
+  unsigned char *header_dev, *slots;
+  int* meta;
   std::vector<unsigned char> header;
 };
 
 using namespace vp;
 using namespace vp::png;
 
+static int png_check(const vp_png_desc* d, vp_png* h) {
+  if (const int rc = check_desc(d, "vp_png")) return rc;
+  if (d->max_frames < 1 || d->max_frames > VP_PNG_MAX_FRAMES) { set_err("vp_png: bad descriptor (max_frames %d, 1 .. %d)", d->max_frames, VP_PNG_MAX_FRAMES); return VP_ERR_ARG; }
+  if (d->height < 1 || d->height > VP_PNG_MAX_HEIGHT) { set_err("vp_png: bad descriptor (height %d, 1 .. %d)", d->height, VP_PNG_MAX_HEIGHT); return VP_ERR_ARG; }
+  if (d->channels != 1 && d->channels != 3 && d->channels != 4) { set_err("vp_png: bad descriptor (channels %d: 1, 3 or 4)", d->channels); return VP_ERR_ARG; }
+  if (d->filter < -1 || d->filter > 4) { set_err("vp_png: bad descriptor (filter %d: -1 adaptive, 0 .. 4 forced)", d->filter); return VP_ERR_ARG; }
+  if (d->width < 1 || (long long)d->width * d->channels > VP_PNG_MAX_ROW_BYTES) {
+    set_err("vp_png: bad descriptor (width %d x %d channels: 1 .. %d bytes per row, a strip lives in one workgroup's LDS)", d->width, d->channels, VP_PNG_MAX_ROW_BYTES);
+    return VP_ERR_ARG;
+  }
+  h->d = *d;
+  h->WC = d->width * d->channels;
+  h->RB = h->WC + 1;
+  int R = (kLdsBudget - 32 - h->WC) / (2 * h->WC + 1);
+  h->R = R > kMaxRows ? kMaxRows : R;                                     // >= 1 up to VP_PNG_MAX_ROW_BYTES
+  h->strips = (d->height + h->R - 1) / h->R;
+  const int chunk = 12 + h->R * h->RB + 10;
+  h->slot_bytes = (int)align_up((size_t)chunk + 4, 16);
+  const int raw = (h->R + 1) * h->WC;
+  h->region_a = (int)align_up((size_t)(raw > chunk + 12 ? raw : chunk + 12), 16);
+  h->lds_bytes = h->region_a + (int)align_up((size_t)h->R * h->RB, 16);
+  h->capacity = kHeaderBytes + kTrailerBytes;
+  for (int y = 0; y < d->height; y += h->R) h->capacity += 12 + (size_t)(d->height - y < h->R ? d->height - y : h->R) * h->RB + 10;
+  if (h->capacity > 0x7fffffffu) { set_err("vp_png: bad descriptor (%d x %d x %d: a file of up to %zu bytes, lengths are 31 bits)", d->height, d->width, d->channels, h->capacity); return VP_ERR_ARG; }
+  return VP_OK;
+}
+
+static size_t png_carve(vp_png* h, void* base) {
+  Arena ar(base);
+  const size_t n = (size_t)h->d.max_frames * h->strips;
+  h->header_dev = ar.take<unsigned char>(kHeaderBytes);
+  h->meta = ar.take<int>(n * 4);
+  h->slots = ar.take<unsigned char>(n * h->slot_bytes);
+  return align256(ar.total());
+}
+
 extern "C" {
 
 size_t vp_png_desc_size(void) { return sizeof(vp_png_desc); }
 
 size_t vp_png_workspace_bytes(const vp_png_desc* d) {
-  Layout L;
-  return layout(d, &L) ? 0 : L.total;
+  vp_png h;
+  return png_check(d, &h) ? 0 : png_carve(&h, nullptr);
 }
 
 size_t vp_png_frame_capacity(const vp_png_desc* d) {
-  Layout L;
-  return layout(d, &L) ? 0 : align_up(L.capacity, 256);
+  vp_png h;
+  return png_check(d, &h) ? 0 : align256(h.capacity);
 }
 
 int vp_png_rows_per_strip(const vp_png_desc* d) {
-  Layout L;
-  return layout(d, &L) ? 0 : L.R;
+  vp_png h;
+  return png_check(d, &h) ? 0 : h.R;
 }
 
 int vp_png_create(const vp_png_desc* d, void* workspace, size_t bytes, void* stream, vp_png_t** out) {
-  Layout L;
-  if (!out) { set_err("vp_png_create: bad argument"); return VP_ERR_ARG; }
-  *out = nullptr;
-  const int rc = layout(d, &L);
-  if (rc) return rc;
-  if (!workspace || bytes < L.total) { set_err("vp_png_create: workspace too small (%zu of %zu bytes)", bytes, L.total); return VP_ERR_WORKSPACE; }
-  vp_png* h = new (std::nothrow) vp_png();
-  if (!h) { set_err("vp_png_create: out of host memory"); return VP_ERR_STATE; }
-  h->d = *d; h->L = L;
-  h->base = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  if (const int rc = open_handle("vp_png_create", d, png_check, png_carve, workspace, bytes, out)) return rc;
+  vp_png* h = *out;
   h->header = file_header(d);
   hipStream_t st = (hipStream_t)stream;
   // create is not an encode: it may wait (a pageable source), once per encoder
-  hipError_t e = hipMemcpyAsync(h->base + L.header, h->header.data(), h->header.size(), hipMemcpyHostToDevice, st);
+  hipError_t e = hipMemcpyAsync(h->header_dev, h->header.data(), h->header.size(), hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) { set_err("vp_png_create: header upload -> %s", hipGetErrorString(e)); delete h; return VP_ERR_HIP; }
-  *out = h;
+  if (e != hipSuccess) { set_err("vp_png_create: header upload -> %s", hipGetErrorString(e)); delete h; *out = nullptr; return VP_ERR_HIP; }
   return VP_OK;
 }
 
@@ -679,23 +666,22 @@ int vp_png_encode(vp_png_t* h, const void* src, int src_dtype, int pixel_stride,
     return VP_ERR_ARG;
   }
   if (src_dtype == VP_PNG_F32 && ((uintptr_t)src & 3)) { set_err("vp_png_encode: a float32 source must start on a 4-byte boundary"); return VP_ERR_ARG; }
-  const Layout& L = h->L;
-  if (out_row_bytes < L.capacity) { set_err("vp_png_encode: out_row_bytes %zu, a file may take %zu (vp_png_frame_capacity)", out_row_bytes, L.capacity); return VP_ERR_ARG; }
+  if (out_row_bytes < h->capacity) { set_err("vp_png_encode: out_row_bytes %zu, a file may take %zu (vp_png_frame_capacity)", out_row_bytes, h->capacity); return VP_ERR_ARG; }
   StripArgs a{};
   a.src = src;
-  a.slots = (unsigned char*)(h->base + L.slots);
-  a.meta = (int*)(h->base + L.meta);
+  a.slots = h->slots;
+  a.meta = h->meta;
   a.f32 = src_dtype == VP_PNG_F32; a.pixel_stride = pixel_stride; a.channel_offset = channel_offset;
-  a.H = h->d.height; a.W = h->d.width; a.C = h->d.channels; a.R = L.R; a.strips = L.strips; a.filter = h->d.filter;
-  a.slot_bytes = L.slot_bytes; a.region_a = L.region_a;
-  hipLaunchKernelGGL(png_strip_kernel, dim3(L.strips, frames), dim3(kThreads), (size_t)L.lds_bytes, (hipStream_t)stream, a);
+  a.H = h->d.height; a.W = h->d.width; a.C = h->d.channels; a.R = h->R; a.strips = h->strips; a.filter = h->d.filter;
+  a.slot_bytes = h->slot_bytes; a.region_a = h->region_a;
+  hipLaunchKernelGGL(png_strip_kernel, dim3(h->strips, frames), dim3(kThreads), (size_t)h->lds_bytes, (hipStream_t)stream, a);
   VP_HIP_CHECK(hipGetLastError());
   GatherArgs g{};
   g.slots = a.slots; g.meta = a.meta;
-  g.header = (const unsigned char*)(h->base + L.header);
+  g.header = h->header_dev;
   g.out = out; g.out_bytes = out_bytes; g.out_row_bytes = out_row_bytes;
-  g.H = a.H; g.R = L.R; g.row_bytes = L.RB; g.strips = L.strips; g.slot_bytes = L.slot_bytes;
-  hipLaunchKernelGGL(png_gather_kernel, dim3(L.strips, frames), dim3(kThreads), 0, (hipStream_t)stream, g);
+  g.H = a.H; g.R = h->R; g.row_bytes = h->RB; g.strips = h->strips; g.slot_bytes = h->slot_bytes;
+  hipLaunchKernelGGL(png_gather_kernel, dim3(h->strips, frames), dim3(kThreads), 0, (hipStream_t)stream, g);
   VP_HIP_CHECK(hipGetLastError());
   return VP_OK;
 }
@@ -703,8 +689,8 @@ int vp_png_encode(vp_png_t* h, const void* src, int src_dtype, int pixel_stride,
 int vp_png_tensor(vp_png_t* h, const char* name, void** ptr, int64_t shape[4]) {
   if (!h || !name || !ptr) { set_err("vp_png_tensor: bad argument"); return VP_ERR_ARG; }
   if (std::string(name) != "strips") { set_err("vp_png_tensor: no tensor '%s' (strips)", name); return VP_ERR_ARG; }
-  *ptr = h->base + h->L.meta;
-  if (shape) { shape[0] = h->d.max_frames; shape[1] = h->L.strips; shape[2] = 4; shape[3] = 1; }
+  *ptr = h->meta;
+  if (shape) { shape[0] = h->d.max_frames; shape[1] = h->strips; shape[2] = 4; shape[3] = 1; }
   return VP_OK;
 }
 

@@ -25,11 +25,10 @@
 #include <stdint.h>
 #include <string.h>
 
-#include <new>
 #include <string>
 #include <vector>
 
-#include "errors.h"
+#include "workspace.h"
 
 #pragma clang fp contract(off)
 
@@ -166,41 +165,15 @@ __global__ __launch_bounds__(256) void puppet_splice_kernel(const float* __restr
   out[i] = (j >= 80 && j < 144) ? expr[(size_t)k * 64 + j - 80] : photo[(size_t)slot * 257 + j];
 }
 
-static size_t align_up(size_t n) { return (n + 255) & ~(size_t)255; }
-
-struct PuppetLayout { size_t slots, coeff, tabs, row1, refer, fg, total; int max_side; };
-
-static int puppet_layout(const vp_puppet_desc* d, PuppetLayout* L) {
-  if (!d) { set_err("vp_puppet: bad descriptor (null)"); return VP_ERR_ARG; }
-  if (d->struct_bytes != (int)sizeof(vp_puppet_desc)) {
-    set_err("vp_puppet: bad descriptor (struct_bytes %d, this library's vp_puppet_desc is %d bytes)", d->struct_bytes, (int)sizeof(vp_puppet_desc));
-    return VP_ERR_ARG;
-  }
-  if (d->slots < 1 || d->slots > VP_PUPPET_MAX_SLOTS) { set_err("vp_puppet: bad descriptor (slots %d, 1 .. %d)", d->slots, VP_PUPPET_MAX_SLOTS); return VP_ERR_ARG; }
-  if (d->frame_batch < 1 || d->frame_batch > 1024) { set_err("vp_puppet: bad descriptor (frame_batch %d, 1 .. 1024)", d->frame_batch); return VP_ERR_ARG; }
-  if (d->img_size < 256 || d->img_size % 256) { set_err("vp_puppet: bad descriptor (img_size %d is not a multiple of 256)", d->img_size); return VP_ERR_ARG; }
-  if (d->face_size < 2 || d->face_size > 4096) { set_err("vp_puppet: bad descriptor (face_size %d, 2 .. 4096)", d->face_size); return VP_ERR_ARG; }
-  // offsets inside one image, one face and one slot's tables are 32-bit in the kernel (rows and slots are widened)
-  if (d->img_size > 4096) { set_err("vp_puppet: bad descriptor (img_size %d: offsets inside an image would leave 32-bit lane offsets)", d->img_size); return VP_ERR_ARG; }
-  const size_t S = d->slots, px = (size_t)d->img_size * d->img_size;
-  L->max_side = 4 * d->img_size;
-  size_t o = 0;
-  L->slots = o; o += align_up(S * sizeof(PuppetSlot));
-  L->coeff = o; o += align_up(S * 257 * sizeof(float));
-  L->tabs = o; o += align_up(S * 2 * L->max_side * sizeof(PuppetTab));
-  L->row1 = o; o += align_up(S * L->max_side * sizeof(int));
-  L->refer = o; o += align_up(S * px * 3 * sizeof(float));
-  L->fg = o; o += align_up(S * px * 3 * sizeof(float));
-  L->total = o + 256;
-  return VP_OK;
-}
-
 }  // namespace vp
 
 struct vp_puppet {
   vp_puppet_desc d;
-  vp::PuppetLayout L;
-  char* base;
+  int max_side;
+  vp::PuppetSlot* slots_dev;
+  float *coeff, *refer, *fg;
+  vp::PuppetTab* tabs;
+  int* row1;
   std::vector<vp::PuppetSlot> slots;
   const unsigned char* bank;
   int n_bg;
@@ -208,32 +181,49 @@ struct vp_puppet {
 
 using namespace vp;
 
+static int puppet_check(const vp_puppet_desc* d, vp_puppet* h) {
+  if (const int rc = check_desc(d, "vp_puppet")) return rc;
+  if (d->slots < 1 || d->slots > VP_PUPPET_MAX_SLOTS) { set_err("vp_puppet: bad descriptor (slots %d, 1 .. %d)", d->slots, VP_PUPPET_MAX_SLOTS); return VP_ERR_ARG; }
+  if (d->frame_batch < 1 || d->frame_batch > 1024) { set_err("vp_puppet: bad descriptor (frame_batch %d, 1 .. 1024)", d->frame_batch); return VP_ERR_ARG; }
+  if (d->img_size < 256 || d->img_size % 256) { set_err("vp_puppet: bad descriptor (img_size %d is not a multiple of 256)", d->img_size); return VP_ERR_ARG; }
+  if (d->face_size < 2 || d->face_size > 4096) { set_err("vp_puppet: bad descriptor (face_size %d, 2 .. 4096)", d->face_size); return VP_ERR_ARG; }
+  // offsets inside one image, one face and one slot's tables are 32-bit in the kernel (rows and slots are widened)
+  if (d->img_size > 4096) { set_err("vp_puppet: bad descriptor (img_size %d: offsets inside an image would leave 32-bit lane offsets)", d->img_size); return VP_ERR_ARG; }
+  h->d = *d;
+  h->max_side = 4 * d->img_size;
+  return VP_OK;
+}
+
+static size_t puppet_carve(vp_puppet* h, void* base) {
+  Arena ar(base);
+  const size_t S = h->d.slots, px = (size_t)h->d.img_size * h->d.img_size;
+  h->slots_dev = ar.take<PuppetSlot>(S);
+  h->coeff = ar.take<float>(S * 257);
+  h->tabs = ar.take<PuppetTab>(S * 2 * h->max_side);
+  h->row1 = ar.take<int>(S * h->max_side);
+  h->refer = ar.take<float>(S * px * 3);
+  h->fg = ar.take<float>(S * px * 3);
+  return align256(ar.total());
+}
+
 extern "C" {
 
 size_t vp_puppet_desc_size(void) { return sizeof(vp_puppet_desc); }
 
 size_t vp_puppet_workspace_bytes(const vp_puppet_desc* d) {
-  PuppetLayout L;
-  return puppet_layout(d, &L) ? 0 : L.total;
+  vp_puppet h;
+  return puppet_check(d, &h) ? 0 : puppet_carve(&h, nullptr);
 }
 
 int vp_puppet_create(const vp_puppet_desc* d, void* workspace, size_t workspace_bytes, void* stream, vp_puppet_t** out) {
-  PuppetLayout L;
-  if (!out) { set_err("vp_puppet_create: bad argument"); return VP_ERR_ARG; }
-  *out = nullptr;
-  const int rc = puppet_layout(d, &L);
-  if (rc) return rc;
-  if (!workspace || workspace_bytes < L.total) { set_err("vp_puppet_create: workspace too small (%zu of %zu bytes)", workspace_bytes, L.total); return VP_ERR_ARG; }
-  vp_puppet* h = new (std::nothrow) vp_puppet();
-  if (!h) { set_err("vp_puppet_create: out of host memory"); return VP_ERR_STATE; }
-  h->d = *d; h->L = L;
-  h->base = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  // (a short workspace is VP_ERR_ARG here, VP_ERR_WORKSPACE in every other family: callers may test for the code, so it stays)
+  if (const int rc = open_handle("vp_puppet_create", d, puppet_check, puppet_carve, workspace, workspace_bytes, out, VP_ERR_ARG)) return rc;
+  vp_puppet* h = *out;
   h->slots.assign(d->slots, PuppetSlot{});
   h->bank = nullptr; h->n_bg = 0;
-  // every slot empty, no coefficients
-  const hipError_t e = hipMemsetAsync(h->base, 0, L.coeff + align_up((size_t)d->slots * 257 * sizeof(float)), (hipStream_t)stream);
-  if (e != hipSuccess) { set_err("vp_puppet_create: hipMemsetAsync -> %s", hipGetErrorString(e)); delete h; return VP_ERR_HIP; }
-  *out = h;
+  // every slot empty, no coefficients: the slot table and the coefficients, up to where the tables start
+  const hipError_t e = hipMemsetAsync(h->slots_dev, 0, (size_t)((char*)h->tabs - (char*)h->slots_dev), (hipStream_t)stream);
+  if (e != hipSuccess) { set_err("vp_puppet_create: hipMemsetAsync -> %s", hipGetErrorString(e)); delete h; *out = nullptr; return VP_ERR_HIP; }
   return VP_OK;
 }
 
@@ -243,7 +233,7 @@ int vp_puppet_attach(vp_puppet_t* h, int slot, const float* refer, const float* 
                      void* stream) {
   if (!h || slot < 0 || slot >= h->d.slots || !refer || !fg_refer) { set_err("vp_puppet_attach: bad argument"); return VP_ERR_ARG; }
   hipStream_t st = (hipStream_t)stream;
-  const int fs = h->d.face_size, ms = h->L.max_side, H = h->d.img_size;
+  const int fs = h->d.face_size, ms = h->max_side, H = h->d.img_size;
   PuppetSlot s{};
   if (!photo_coeff) {
     s.kind = PK_PANEL;
@@ -265,19 +255,19 @@ int vp_puppet_attach(vp_puppet_t* h, int slot, const float* refer, const float* 
     rc = vp_resize_linear_table(fs, side, 1, ofs.data(), a0.data(), a1.data(), r1.data());
     if (rc) return rc;
     for (int i = 0; i < side; ++i) tab[side + i] = PuppetTab{ofs[i], a0[i], a1[i]};
-    PuppetTab* dt = (PuppetTab*)(h->base + h->L.tabs) + (size_t)slot * 2 * ms;
+    PuppetTab* dt = h->tabs + (size_t)slot * 2 * ms;
     VP_HIP_CHECK(hipMemcpyAsync(dt, tab.data(), side * sizeof(PuppetTab), hipMemcpyHostToDevice, st));
     VP_HIP_CHECK(hipMemcpyAsync(dt + ms, tab.data() + side, side * sizeof(PuppetTab), hipMemcpyHostToDevice, st));
-    VP_HIP_CHECK(hipMemcpyAsync((int*)(h->base + h->L.row1) + (size_t)slot * ms, r1.data(), side * sizeof(int), hipMemcpyHostToDevice, st));
+    VP_HIP_CHECK(hipMemcpyAsync(h->row1 + (size_t)slot * ms, r1.data(), side * sizeof(int), hipMemcpyHostToDevice, st));
     VP_HIP_CHECK(hipStreamSynchronize(st));
   }
   if (photo_coeff)
-    VP_HIP_CHECK(hipMemcpyAsync((float*)(h->base + h->L.coeff) + (size_t)slot * 257, photo_coeff, 257 * sizeof(float), hipMemcpyHostToDevice, st));
+    VP_HIP_CHECK(hipMemcpyAsync(h->coeff + (size_t)slot * 257, photo_coeff, 257 * sizeof(float), hipMemcpyHostToDevice, st));
   else
-    VP_HIP_CHECK(hipMemsetAsync((float*)(h->base + h->L.coeff) + (size_t)slot * 257, 0, 257 * sizeof(float), st));
-  VP_HIP_CHECK(hipMemcpyAsync((float*)(h->base + h->L.refer) + (size_t)slot * px, refer, px * sizeof(float), hipMemcpyDeviceToDevice, st));
-  VP_HIP_CHECK(hipMemcpyAsync((float*)(h->base + h->L.fg) + (size_t)slot * px, fg_refer, px * sizeof(float), hipMemcpyDeviceToDevice, st));
-  VP_HIP_CHECK(hipMemcpyAsync((PuppetSlot*)(h->base + h->L.slots) + slot, &s, sizeof(s), hipMemcpyHostToDevice, st));
+    VP_HIP_CHECK(hipMemsetAsync(h->coeff + (size_t)slot * 257, 0, 257 * sizeof(float), st));
+  VP_HIP_CHECK(hipMemcpyAsync(h->refer + (size_t)slot * px, refer, px * sizeof(float), hipMemcpyDeviceToDevice, st));
+  VP_HIP_CHECK(hipMemcpyAsync(h->fg + (size_t)slot * px, fg_refer, px * sizeof(float), hipMemcpyDeviceToDevice, st));
+  VP_HIP_CHECK(hipMemcpyAsync(h->slots_dev + slot, &s, sizeof(s), hipMemcpyHostToDevice, st));
   VP_HIP_CHECK(hipStreamSynchronize(st));
   h->slots[slot] = s;
   return VP_OK;
@@ -292,7 +282,7 @@ int vp_puppet_set_backgrounds(vp_puppet_t* h, const unsigned char* bank, int cou
 int vp_puppet_splice(vp_puppet_t* h, const float* expr, int expr_rows, const int* rows, int count, float* coeff_out, void* stream) {
   if (!h || !expr || !rows || !coeff_out || count < 1 || expr_rows < 1 || count > (1 << 22)) { set_err("vp_puppet_splice: bad argument"); return VP_ERR_ARG; }
   hipLaunchKernelGGL(puppet_splice_kernel, dim3((count * 257 + 255) / 256), dim3(256), 0, (hipStream_t)stream,
-                     (const float*)(h->base + h->L.coeff), expr, rows, coeff_out, count, h->d.slots, expr_rows);
+                     h->coeff, expr, rows, coeff_out, count, h->d.slots, expr_rows);
   VP_HIP_CHECK(hipGetLastError());
   return VP_OK;
 }
@@ -304,14 +294,14 @@ int vp_puppet_condition(vp_puppet_t* h, const unsigned char* faces, int face_row
     return VP_ERR_ARG;
   }
   CondArgs a{};
-  a.slots = (const PuppetSlot*)(h->base + h->L.slots);
-  a.tabs = (const PuppetTab*)(h->base + h->L.tabs);
-  a.row1 = (const int*)(h->base + h->L.row1);
-  a.refer = (const float*)(h->base + h->L.refer);
-  a.fg = (const float*)(h->base + h->L.fg);
+  a.slots = h->slots_dev;
+  a.tabs = h->tabs;
+  a.row1 = h->row1;
+  a.refer = h->refer;
+  a.fg = h->fg;
   a.faces = faces; a.bank = h->bank; a.rows = rows;
   a.inputs = inputs; a.fg_inputs = fg_inputs; a.targets = targets;
-  a.S = h->d.slots; a.B = count; a.H = h->d.img_size; a.fs = h->d.face_size; a.max_side = h->L.max_side; a.n_faces = face_rows; a.n_bg = h->n_bg;
+  a.S = h->d.slots; a.B = count; a.H = h->d.img_size; a.fs = h->d.face_size; a.max_side = h->max_side; a.n_faces = face_rows; a.n_bg = h->n_bg;
   // one wave per image line; 256 CUs x 2 blocks of 4 waves keep every CU streaming without a tail of tiny blocks
   int blocks = (count * a.H + 3) / 4;
   if (blocks > 512) blocks = 512;
@@ -325,9 +315,9 @@ int vp_puppet_tensor(vp_puppet_t* h, const char* name, void** ptr, int64_t shape
   const std::string n(name);
   const int64_t S = h->d.slots, H = h->d.img_size;
   int64_t shp[4] = {S, 1, 1, 1};
-  if (n == "coeff") { *ptr = h->base + h->L.coeff; shp[1] = 257; }
-  else if (n == "refer") { *ptr = h->base + h->L.refer; shp[1] = H; shp[2] = H; shp[3] = 3; }
-  else if (n == "fg") { *ptr = h->base + h->L.fg; shp[1] = H; shp[2] = H; shp[3] = 3; }
+  if (n == "coeff") { *ptr = h->coeff; shp[1] = 257; }
+  else if (n == "refer") { *ptr = h->refer; shp[1] = H; shp[2] = H; shp[3] = 3; }
+  else if (n == "fg") { *ptr = h->fg; shp[1] = H; shp[2] = H; shp[3] = 3; }
   else { set_err("vp_puppet_tensor: no tensor '%s' (coeff, refer, fg)", name); return VP_ERR_ARG; }
   if (shape) for (int i = 0; i < 4; ++i) shape[i] = shp[i];
   return VP_OK;

@@ -16,7 +16,7 @@
 #include <limits.h>
 #include <stdint.h>
 
-#include "errors.h"
+#include "workspace.h"
 #include "raster_common.h"
 
 #pragma clang fp contract(off)
@@ -380,7 +380,7 @@ int vp_raster_interpolate(float* out, const int* triangle_buffer, const float* b
 
 size_t vp_vertex_adjacency_bytes(int nver, int ntri) {
   if (nver < 1 || ntri < 0 || nver > INT_MAX / 3 || ntri > INT_MAX / 3) return 0;
-  return (((size_t)2 * nver + 1 + (size_t)3 * ntri) * sizeof(int) + 255) / 256 * 256;
+  return vp::align256(((size_t)2 * nver + 1 + (size_t)3 * ntri) * sizeof(int));
 }
 
 int vp_vertex_adjacency_build(const int* triangles, int nver, int ntri, void* adjacency, size_t adjacency_bytes, void* stream) {

@@ -20,13 +20,12 @@
 #include <string.h>
 
 #include <algorithm>
-#include <new>
 #include <string>
 #include <vector>
 
-#include "errors.h"
 #include "resize_core.h"
 #include "vp_common.h"
+#include "workspace.h"
 
 namespace vp {
 
@@ -326,16 +325,23 @@ __global__ __launch_bounds__(256) void triptych_compose_kernel(const TrArgs a) {
   }
 }
 
-struct TrLayout { size_t xt, yt, yrow1, ft, filled, qa, er, hb, total, entries; };
+}  // namespace vp
 
-static size_t tr_align(size_t v) { return (v + 255) & ~(size_t)255; }
+struct vp_triptych {
+  vp_triptych_desc d;
+  size_t entries;                            // of the tables: side s at entry s (s - 1) / 2, sides 1 .. max_side
+  vp::ResizeTab *xt, *yt;
+  int* yrow1;
+  vp::FTab* ft;
+  unsigned char *filled, *qa, *er;
+  int* hb;
+  int q[vp::kTrTaps];
+};
 
-static int tr_layout(const vp_triptych_desc* d, TrLayout* L) {
-  if (!d) { set_err("vp_triptych: bad descriptor (null)"); return VP_ERR_ARG; }
-  if (d->struct_bytes != (uint32_t)sizeof(vp_triptych_desc)) {
-    set_err("vp_triptych: bad descriptor (struct_bytes %u, this library's vp_triptych_desc is %d bytes)", d->struct_bytes, (int)sizeof(vp_triptych_desc));
-    return VP_ERR_ARG;
-  }
+using namespace vp;
+
+static int tr_check(const vp_triptych_desc* d, vp_triptych* h) {
+  if (const int rc = check_desc(d, "vp_triptych")) return rc;
   if (d->max_frames < 1 || d->max_frames > VP_TRIPTYCH_MAX_FRAMES) {
     set_err("vp_triptych: bad descriptor (max_frames %d, 1 .. %d)", d->max_frames, VP_TRIPTYCH_MAX_FRAMES);
     return VP_ERR_ARG;
@@ -349,31 +355,25 @@ static int tr_layout(const vp_triptych_desc* d, TrLayout* L) {
     set_err("vp_triptych: bad descriptor (max_side %d, %d .. size %d)", d->max_side, kTrRadius + 1, d->size);
     return VP_ERR_ARG;
   }
-  const size_t n = (size_t)d->max_side * (d->max_side + 1) / 2, plane = (size_t)d->max_frames * d->max_side * d->max_side;
-  size_t o = 0;
-  L->entries = n;
-  L->xt = o; o += tr_align(n * sizeof(ResizeTab));
-  L->yt = o; o += tr_align(n * sizeof(ResizeTab));
-  L->yrow1 = o; o += tr_align(n * sizeof(int));
-  L->ft = o; o += tr_align(n * sizeof(FTab));
-  L->filled = o; o += tr_align((size_t)d->max_frames * d->face_size * d->face_size);
-  L->qa = o; o += tr_align(plane);
-  L->er = o; o += tr_align(plane);
-  L->hb = o; o += tr_align(plane * sizeof(int));
-  L->total = o + 256;
+  h->d = *d;
+  h->entries = (size_t)d->max_side * (d->max_side + 1) / 2;
   return VP_OK;
 }
 
-}  // namespace vp
-
-struct vp_triptych {
-  vp_triptych_desc d;
-  vp::TrLayout L;
-  char* base;
-  int q[vp::kTrTaps];
-};
-
-using namespace vp;
+static size_t tr_carve(vp_triptych* h, void* base) {
+  Arena ar(base);
+  const vp_triptych_desc& d = h->d;
+  const size_t n = h->entries, plane = (size_t)d.max_frames * d.max_side * d.max_side;
+  h->xt = ar.take<ResizeTab>(n);
+  h->yt = ar.take<ResizeTab>(n);
+  h->yrow1 = ar.take<int>(n);
+  h->ft = ar.take<FTab>(n);
+  h->filled = ar.take<unsigned char>((size_t)d.max_frames * d.face_size * d.face_size);
+  h->qa = ar.take<unsigned char>(plane);
+  h->er = ar.take<unsigned char>(plane);
+  h->hb = ar.take<int>(plane);
+  return align256(ar.total());
+}
 
 static int launch_fill(const unsigned char* in, unsigned char* out, int n, int h, int w, const int* geom, int S, int ms, hipStream_t st) {
   FillArgs f;
@@ -385,9 +385,8 @@ static int launch_fill(const unsigned char* in, unsigned char* out, int n, int h
 
 static void tr_args(const vp_triptych* h, TrArgs* a) {
   memset(a, 0, sizeof(*a));
-  a->xt = (const ResizeTab*)(h->base + h->L.xt); a->yt = (const ResizeTab*)(h->base + h->L.yt);
-  a->yrow1 = (const int*)(h->base + h->L.yrow1); a->ft = (const FTab*)(h->base + h->L.ft);
-  a->qa = (unsigned char*)(h->base + h->L.qa); a->er = (unsigned char*)(h->base + h->L.er); a->hb = (int*)(h->base + h->L.hb);
+  a->xt = h->xt; a->yt = h->yt; a->yrow1 = h->yrow1; a->ft = h->ft;
+  a->qa = h->qa; a->er = h->er; a->hb = h->hb;
   for (int k = 0; k < kTrTaps; ++k) a->q[k] = h->q[k];
   a->S = h->d.size; a->face = h->d.face_size; a->ms = h->d.max_side;
 }
@@ -397,10 +396,9 @@ static int run_mask(vp_triptych* h, TrArgs& a, const unsigned char* face_mask, i
   const vp_triptych_desc& d = h->d;
   a.mask_in = face_mask;
   if (fill) {
-    unsigned char* filled = (unsigned char*)(h->base + h->L.filled);
-    const int rc = launch_fill(face_mask, filled, a.T, d.face_size, d.face_size, a.geom, d.size, d.max_side, st);
+    const int rc = launch_fill(face_mask, h->filled, a.T, d.face_size, d.face_size, a.geom, d.size, d.max_side, st);
     if (rc) return rc;
-    a.mask_in = filled;
+    a.mask_in = h->filled;
   }
   const int bx = std::min(((int)d.max_side * d.max_side + 255) / 256, 256);
   const dim3 grid(bx, a.T);
@@ -420,8 +418,8 @@ extern "C" {
 size_t vp_triptych_desc_size(void) { return sizeof(vp_triptych_desc); }
 
 size_t vp_triptych_workspace_bytes(const vp_triptych_desc* d) {
-  TrLayout L;
-  return tr_layout(d, &L) ? 0 : L.total;
+  vp_triptych h;
+  return tr_check(d, &h) ? 0 : tr_carve(&h, nullptr);
 }
 
 int vp_triptych_blur_taps(int q[21]) {
@@ -431,21 +429,13 @@ int vp_triptych_blur_taps(int q[21]) {
 }
 
 int vp_triptych_create(const vp_triptych_desc* d, void* workspace, size_t bytes, void* stream, vp_triptych_t** out) {
-  TrLayout L;
-  if (!out) { set_err("vp_triptych_create: bad argument"); return VP_ERR_ARG; }
-  *out = nullptr;
-  const int rc = tr_layout(d, &L);
-  if (rc) return rc;
-  if (!workspace || bytes < L.total) { set_err("vp_triptych_create: workspace too small (%zu of %zu bytes)", bytes, L.total); return VP_ERR_WORKSPACE; }
-  vp_triptych* h = new (std::nothrow) vp_triptych();
-  if (!h) { set_err("vp_triptych_create: out of host memory"); return VP_ERR_STATE; }
-  h->d = *d; h->L = L;
-  h->base = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  if (const int rc = open_handle("vp_triptych_create", d, tr_check, tr_carve, workspace, bytes, out)) return rc;
+  vp_triptych* h = *out;
   blur_taps(h->q);
   // every frame has its own side: the tables of all sides 1 .. max_side are built here, once, side s at entry s (s - 1) / 2
-  std::vector<ResizeTab> xt(L.entries), yt(L.entries);
-  std::vector<int> r1(L.entries);
-  std::vector<FTab> ft(L.entries);
+  std::vector<ResizeTab> xt(h->entries), yt(h->entries);
+  std::vector<int> r1(h->entries);
+  std::vector<FTab> ft(h->entries);
   for (int s = 1; s <= d->max_side; ++s) {
     const size_t b = tab_base(s);
     build_table(d->face_size, s, xt.data() + b);
@@ -454,13 +444,12 @@ int vp_triptych_create(const vp_triptych_desc* d, void* workspace, size_t bytes,
   }
   hipStream_t st = (hipStream_t)stream;
   // create is not a build: it may wait (pageable sources), once per builder
-  hipError_t e = hipMemcpyAsync(h->base + L.xt, xt.data(), xt.size() * sizeof(ResizeTab), hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(h->base + L.yt, yt.data(), yt.size() * sizeof(ResizeTab), hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(h->base + L.yrow1, r1.data(), r1.size() * sizeof(int), hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(h->base + L.ft, ft.data(), ft.size() * sizeof(FTab), hipMemcpyHostToDevice, st);
+  hipError_t e = hipMemcpyAsync(h->xt, xt.data(), xt.size() * sizeof(ResizeTab), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(h->yt, yt.data(), yt.size() * sizeof(ResizeTab), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(h->yrow1, r1.data(), r1.size() * sizeof(int), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(h->ft, ft.data(), ft.size() * sizeof(FTab), hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) { set_err("vp_triptych_create: table upload -> %s", hipGetErrorString(e)); delete h; return VP_ERR_HIP; }
-  *out = h;
+  if (e != hipSuccess) { set_err("vp_triptych_create: table upload -> %s", hipGetErrorString(e)); delete h; *out = nullptr; return VP_ERR_HIP; }
   return VP_OK;
 }
 
@@ -511,8 +500,8 @@ int vp_triptych_tensor(vp_triptych_t* h, const char* name, void** ptr, int64_t s
   if (!h || !name || !ptr) { set_err("vp_triptych_tensor: bad argument"); return VP_ERR_ARG; }
   const std::string s(name);
   int64_t side;
-  if (s == "mask") { *ptr = h->base + h->L.qa; side = h->d.max_side; }
-  else if (s == "filled") { *ptr = h->base + h->L.filled; side = h->d.face_size; }
+  if (s == "mask") { *ptr = h->qa; side = h->d.max_side; }
+  else if (s == "filled") { *ptr = h->filled; side = h->d.face_size; }
   else { set_err("vp_triptych_tensor: no tensor '%s' (mask, filled)", name); return VP_ERR_ARG; }
   if (shape) { shape[0] = h->d.max_frames; shape[1] = shape[2] = side; shape[3] = 1; }
   return VP_OK;
