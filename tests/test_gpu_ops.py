@@ -25,7 +25,7 @@ bwd_weight_reference), u = 2^-24:
   act    ReLU is 1-Lipschitz: the bound passes through.  tanh (1-Lipschitz) adds K_TANH u |ref|, the measured constant of
          test_gpu_bfmnet_train_ops.py for tanhf on the MI355X.  No case uses the sigmoid.
   D      the one ambiguity of the reference: the float32 value the loader hands on as the activated input.  scale * x + shift may be
-         fused (prologue_piece, conv_kernels.hip: fmaf) or not, and act_apply's leaky ReLU 0.6f v + 0.4f |v| is contracted by the
+         fused (prologue_piece, plane_device.h: fmaf) or not, and act_apply's leaky ReLU 0.6f v + 0.4f |v| is contracted by the
          compiler into either product's fma or left alone; on the bf16 path the result is then rounded to bf16 (Elem<bf16>::pack).  All
          six float32 evaluations are computed in numpy (input_candidates); the reference uses the MIDPOINT of their range and D is half
          the range, so |w| (*) D covers whichever the kernel computes.  D is zero almost everywhere on the bf16 path (a flipped bf16

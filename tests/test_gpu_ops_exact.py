@@ -15,7 +15,7 @@ Operands (exact_operands)
   K < 8 (the weight gradients of the two 2-pixel bottleneck cases, K = 2, where 12 of the 16 taps only ever meet padding): w / dy
   without zeros and the non-negative inputs of the float32 recipe below, or fewer than 20 % of the outputs would be non-zero.
   affine / in_act cases: x in {-15, -10, -5, 0, 1, 2}, scale in {1, 2}, shift in {0, 5, 10}: scale x + shift is an integer of at most
-  five bits, fused or not, and every negative one is a multiple of 5.  The loaders (prologue_piece, conv_kernels.hip) compute
+  five bits, fused or not, and every negative one is a multiple of 5.  The loaders (prologue_piece, plane_device.h) compute
   fmaf(scale, x, shift), then act_apply, then on the bf16 path round to bf16 (Elem<bf16>::pack).  act_apply's leaky ReLU is
   0.6f v + 0.4f |v|, which the compiler is free to contract into either product: for v = -5 m the plain form gives -m, the form
   fma(0.6f, v, 0.4f |v|) gives -m (1 + 2^-23).  Rounded to bf16 both are -m, so on the bf16 path - the benchmark's - the activated

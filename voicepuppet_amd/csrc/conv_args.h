@@ -23,7 +23,8 @@ struct PixSrc {
 };
 
 // The kernel of a convolution launch (IgemmArgs::kern).  The first five are the plan families (how the plan stages its operands and
-// packs its weights: conv_staging); the others run plans of one of those families.
+// packs its weights); the others run plans of one of those families, named by their row of the kernel table (conv_dispatch.hip:
+// conv_staging).  The values are visible outside the library: a new kernel goes at the end.
 enum ConvKernel {
   CK_IGEMM = 0,   // generic implicit GEMM (IgemmPlan::cfg picks the tile)
   CK_PATCH,       // patch kernel, generic schedule (conv_patch.hip)
@@ -40,11 +41,6 @@ enum ConvKernel {
   CK_DC256,       // 2 x 128 -> 64 channel transposed conv (conv_dc64.hip) - patch2 plans
   CK_DC64,        // 128 -> 64 channel transposed conv (conv_dc64.hip)
 };
-// plan family of a kernel: 0 igemm, 1 patch, 2 patch2, 3 smallp, 4 s2c64
-inline int conv_staging(int k) {
-  return k <= CK_S2C64 ? k : (k <= CK_COUT4 ? CK_IGEMM : (k <= CK_PATCH4 ? CK_PATCH : CK_PATCH2));
-}
-
 // Y[pixel, co] = epilogue( sum_{tap, ci} X~[pixel (+) tap, ci] * Wp[co][tap*Cin + ci] )
 // Covers conv fwd, conv bwd-data, transposed-conv fwd (4 output-parity classes) and its bwd-data.
 struct IgemmArgs {

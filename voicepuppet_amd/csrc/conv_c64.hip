@@ -463,6 +463,7 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_c64_kernel(const IgemmArgs a,
 // what the kernel handles: a patch-plan 3x3 (conv_ops.h plan_make_patch: permuted rows, kswap) from ONE tensor of 64 channels to 64 / 128 or
 // of 128 channels to 64 / 128, plain store (no batch statistics, no accumulation, no affine on the reference), relu / no activation,
 // optional fused 2x2 max pool of relu outputs, optional relu'(reference) product, image sides multiples of the 4 x 16 tile
+bool patch3_eligible(const IgemmArgs& a, int is_bf16);      // conv_patch3.hip: the patch schedule this kernel specialises
 bool conv_c64_eligible(const IgemmArgs& a, int is_bf16) {
   if (!is_bf16 || conv_staging(a.kern) != CK_PATCH || !patch3_eligible(a, 1)) return false;
   if ((a.Cin != 64 && a.Cin != 128) || a.x.C[0] != a.Cin || (a.Cout != 64 && a.Cout != 128)) return false;

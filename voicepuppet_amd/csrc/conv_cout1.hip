@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 
 #include "conv_args.h"
+#include "conv_prof.h"
 #include "igemm_device.h"
 #include "launch.h"
 #include "vp_common.h"
@@ -147,6 +148,9 @@ bool conv_cout1_bwd_eligible(const Cout1Args& a) {
 }
 
 hipError_t launch_conv_cout1_bwd(const Cout1Args& a0, hipStream_t st) {
+  const double px = (double)a0.N * a0.H * a0.W;
+  ProfScope prof("cout1bwd", true, 512, 16, 2.0 * px * a0.C * a0.ks * a0.ks,
+                 2.0 * ((double)a0.N * a0.Ho * a0.Wo + (double)a0.ks * a0.ks * a0.C + px * a0.C), st);       // timed like every other conv launch
   Cout1Args a = a0;
   a.pix_per_group = (a.N / a.groups) * a.H * a.W;
   a.tiles_per_group = (a.pix_per_group + 15) >> 4;
@@ -279,6 +283,9 @@ bool conv_cout1_wgrad_eligible(const Cout1Args& a) {
 
 // a.ref = the layer's (materialised, activated) input, a.rows = blocks = slabs, a.slabs >= rows * 16 * 512 floats, a.dW [16][512]
 hipError_t launch_conv_cout1_wgrad(const Cout1Args& a, hipStream_t st) {
+  const double px = (double)a.N * a.H * a.W;
+  ProfScope prof("cout1wgrad", true, 16, 512, 2.0 * px * a.C * a.ks * a.ks,
+                 2.0 * ((double)a.N * a.Ho * a.Wo + px * a.C) + 4.0 * a.ks * a.ks * a.C, st);
   const int smem = 3 * 64 * 64 * 4;
   (void)hipFuncSetAttribute((const void*)cout1_wgrad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
   hipLaunchKernelGGL(cout1_wgrad_kernel, dim3(a.rows), dim3(256), smem, st, a);

@@ -45,17 +45,17 @@ inline int& thin_blocks_knob(int i) { static int v[4] = {1024, 512, 512, 512}; r
 // tile choice for an igemm producing `rows` channels over P pixels
 inline int pick_igemm_cfg(int rows, int P, int Kpad = 0) {
   if (P >= 96) {
-    if (rows % 128 == 0 && igemm_small_grid_knob() > 0 && (long long)((P + 127) / 128) * (rows / 128) <= igemm_small_grid_knob()) return 1;
+    if (rows % 128 == 0 && igemm_small_grid_knob() > 0 && (long long)((P + 127) / 128) * (rows / 128) <= igemm_small_grid_knob()) return IG_64x128;
     // 256x256 (8-wave tile) runs one block per CU: its prologue / epilogue are exposed, only long K loops amortise them
-    if (rows % 256 == 0 && P >= 256 * 256 && Kpad >= 4096) return 7;
-    if (rows % 128 == 0 && P >= 256 * 512) return 6;           // 128x256, 8 waves
-    if (rows % 128 == 0) return 0;
-    if (rows % 64 == 0) return 1;
-    if (rows <= 16) return 2;
-    return rows > 64 ? 0 : 1;
+    if (rows % 256 == 0 && P >= 256 * 256 && Kpad >= 4096) return IG_256x256;
+    if (rows % 128 == 0 && P >= 256 * 512) return IG_128x256;  // 8 waves
+    if (rows % 128 == 0) return IG_128x128;
+    if (rows % 64 == 0) return IG_64x128;
+    if (rows <= 16) return IG_16x128;
+    return rows > 64 ? IG_128x128 : IG_64x128;
   }
-  if (rows <= 64) return 5;
-  return P > 16 ? 3 : 4;
+  if (rows <= 64) return IG_64x32;
+  return P > 16 ? IG_128x32 : IG_128x16;
 }
 
 constexpr int IGEMM_SPLITK_TARGET_DEFAULT = 64;   // rounds 2-5: 128
@@ -112,9 +112,9 @@ inline void finish_igemm(IgemmPlan& p, int rows, int is_bf16, const IgemmPin* pi
   // float32 matrix products (one tap: BFMNet's 1x1 convolutions, the DFT): a 128x128 block is 4x the MFMA time of a bf16 one, so a grid
   // of 257-511 blocks costs two full rounds of the 256 CUs.  64x128 tiles (two resident per CU, half the time each) quantise finer:
   // rounds x rows 3 x 64 against 2 x 128 for 300 blocks (scripts/mm_bench.py: 19200 x 1152 x 256 forward 140 -> 109 us)
-  if (!is_bf16 && a.ntaps == 1 && p.cfg == 0) {
+  if (!is_bf16 && a.ntaps == 1 && p.cfg == IG_128x128) {
     const long long b128 = (long long)((P + 127) / 128) * (rows / 128), b64 = 2 * b128;
-    if (((b64 + 255) / 256) * 64 < ((b128 + 255) / 256) * 128) p.cfg = 1;
+    if (((b64 + 255) / 256) * 64 < ((b128 + 255) / 256) * 128) p.cfg = IG_64x128;
   }
   if (pin) p.cfg = pin->cfg;
   int bc, bp;
@@ -127,7 +127,7 @@ inline void finish_igemm(IgemmPlan& p, int rows, int is_bf16, const IgemmPin* pi
   p.partial_bytes = a.splitk > 1 ? (size_t)a.nclass * a.splitk * P * a.CoutPad * sizeof(float) : 0;
   // row permutation inside 64-row blocks (IgemmArgs::rowperm) where the tile's waves own whole 64-row blocks
   {
-    const bool tc4 = p.cfg == 0 || p.cfg == 1 || p.cfg == 6 || p.cfg == 7 || p.cfg == 8 || p.cfg == 9;
+    const bool tc4 = p.cfg == IG_128x128 || p.cfg == IG_64x128 || p.cfg == IG_128x256 || p.cfg == IG_256x256;
     a.rowperm = (tc4 && rows % 64 == 0) ? 1 : 0;
     p.pack.perm = a.rowperm;
   }
@@ -224,7 +224,7 @@ inline void plan_make_patch(IgemmPlan& p, int rows, int is_bf16) {
   a.p_dhf = a.taps[0].dh[0]; a.p_dwf = a.taps[0].dw[0];
   a.p_dhs = a.taps[0].dh[ks] - a.taps[0].dh[0]; a.p_dws = a.taps[0].dw[1] - a.taps[0].dw[0];
   const int bp = p4 ? 256 : patch_tile_pixels(bc);
-  p.cfg = bc == 256 ? (bp == 128 ? 15 : 10) : (bc == 128 ? (bp == 256 ? 13 : 11) : (bp == 256 ? 14 : 12));
+  p.cfg = bc == 256 ? (bp == 128 ? PATCH_256x128 : PATCH_256x256) : (bc == 128 ? (bp == 256 ? PATCH_128x256 : PATCH_128x512) : (bp == 256 ? PATCH_64x256 : PATCH_64x512));
   a.CoutPad = round_up(rows, bc);
   a.splitk = 1;
   p.partial_bytes = 0;
@@ -256,7 +256,7 @@ inline void plan_make_patch2(IgemmPlan& p, int rows, int is_bf16) {
   IgemmArgs& a = p.a;
   const int bc = rows % 128 == 0 ? 128 : 64;
   a.kern = CK_PATCH2; a.p_kw = 2;
-  p.cfg = bc == 128 ? 13 : 14;
+  p.cfg = bc == 128 ? PATCH_128x256 : PATCH_64x256;
   a.CoutPad = round_up(rows, bc);
   a.splitk = 1;
   p.partial_bytes = 0;
@@ -291,7 +291,7 @@ inline void plan_make_smallp(IgemmPlan& p, int rows, int is_bf16) {
   const int Pc = a.N * a.Hg * a.Wg;
   a.kern = CK_SMALLP;
   a.sp_npt = Pc <= 16 ? 1 : (Pc <= 32 ? 2 : 4);
-  p.cfg = a.sp_npt == 1 ? 16 : (a.sp_npt == 2 ? 17 : 18);
+  p.cfg = a.sp_npt == 1 ? SMALLP_32x16 : (a.sp_npt == 2 ? SMALLP_32x32 : SMALLP_32x64);
   a.sp_lcpt = ilog2(a.Cin / kc);
   a.CoutPad = round_up(rows, 32);
   a.rowperm = 0; p.pack.perm = 0; p.pack.kswap = 0;
@@ -339,7 +339,7 @@ inline bool plan_s2c64_eligible(const IgemmPlan& p, int rows, int is_bf16, int c
 inline void plan_make_s2c64(IgemmPlan& p) {
   IgemmArgs& a = p.a;
   a.kern = CK_S2C64;
-  p.cfg = 0;                 // (128 x 128: the class name's tile; the kernel has its own)
+  p.cfg = IG_128x128;        // (the class name's tile; the kernel has its own)
   a.CoutPad = a.Cout; a.wp_rows = a.Cout; p.pack.rows_pad = a.Cout;
   p.pack_elems = (size_t)a.wp_rows * a.Kpad;
   a.splitk = 1; p.partial_bytes = 0;
@@ -365,29 +365,11 @@ inline IgemmArgs launch_view(const IgemmPlan& p, const LaunchForm& f) {
   return v;
 }
 
-// the specialised kernel for a launch of this family, in priority order (the first whose preconditions hold), else the family's own
-inline int pick_conv_kernel(const IgemmArgs& v, int is_bf16) {
-  const int fam = conv_staging(v.kern);
-  if (fam == CK_SMALLP || fam == CK_S2C64) return fam;
-  if (is_bf16) {
-    if (conv_cin8_eligible(v, 1)) return CK_CIN8;
-    if (conv_cout8_eligible(v, 1)) return CK_COUT8;
-    if (conv_dcout8_eligible(v, 1)) return CK_DCOUT8;
-    if (conv_cout4_eligible(v, 1)) return CK_COUT4;
-    if (c64_knob() && conv_c64_eligible(v, 1)) return CK_C64;
-    if (dc64_knob() && conv_dc256_eligible(v, 1)) return CK_DC256;
-    if (dc64_knob() && conv_dc64_eligible(v, 1)) return CK_DC64;
-    if (patch4_knob() && patch4_eligible(v, 1)) return CK_PATCH4;
-  }
-  if (fam == CK_PATCH && patch3_knob() && patch3_eligible(v, is_bf16)) return CK_PATCH3;
-  return fam;
-}
-
 // plan families a caller allows (plan_kernel)
 enum { FAM_SMALLP = 1, FAM_PATCH = 2, FAM_PATCH2 = 4, FAM_S2C64 = 8, FAM_ALL = 15 };
 
-// The one place a convolution launch's kernel is chosen (and every kernel-selecting knob read): the plan family - how the plan stages
-// its operands and packs its weights - from those the caller allows, then the kernel within it (IgemmArgs::kern).  rows: output channels
+// The one place a convolution launch's kernel is chosen (and, with the kernel table it ends in, every kernel-selecting knob read): the plan family - how the plan stages
+// its operands and packs its weights - from those the caller allows, then the kernel within it (IgemmArgs::kern: pick_conv_kernel, conv_dispatch.hip).  rows: output channels
 // of the GEMM; c0 / c1: channels of the one or two source tensors; any_grid: see plan_patch_eligible.  The plan's ldY / y_f32 / out_act /
 // ref_act / split_c must be those of its launches.
 inline void plan_kernel(IgemmPlan& p, int rows, int is_bf16, int c0, int c1, unsigned fams, const LaunchForm& f, bool any_grid = false) {
@@ -518,16 +500,16 @@ inline WgradPlan plan_wgrad(const ConvGeomX& g, int is_bf16, bool plain_operands
   a.log2Gc = ilog2(a.Gc);
   a.gc_mask = a.Gc - 1;
   if (a.ntaps == 1) { a.log2Gc = 30; a.gc_mask = 0x3fffffff; }   // 1x1: rows are channels, any count (BFMNet's 192 .. 1536-wide layers)
-  p.cfg = (a.Dc % 128 == 0) ? 0 : (a.Dc % 64 == 0 ? 1 : 2);
+  p.cfg = (a.Dc % 128 == 0) ? WG_128x128 : (a.Dc % 64 == 0 ? WG_128x64 : WG_128x16);
   // (256-row 8-wave tiles for the register-transposing kernel measured no faster - one 240-register block per CU, EXPERIMENTS.md 3)
   a.lw = ilog2(a.Wb); a.lh = ilog2(a.Hb);
   const bool tr = is_bf16 && plain_operands && (wgrad_tr_knob() & 1) && (a.ntaps * a.Gc) % 256 == 0 && a.Dc % 128 == 0 &&
                   (((long long)a.N << (a.lw + a.lh)) % 32) == 0;
-  if (tr) p.cfg = 5;
+  if (tr) p.cfg = WG_TR_256x128;
   // thin layers (image inputs: 16 taps x 8 padded channels = 128 rows): the 128 x 128 form of the same kernel, single-source operands
   const bool tr_thin = !tr && is_bf16 && plain_operands && (wgrad_tr_knob() & 2) && (a.ntaps * a.Gc) % 128 == 0 && a.Dc % 8 == 0 && a.Dc <= 128 &&
                        (((long long)a.N << (a.lw + a.lh)) % 32) == 0 && a.lw + a.lh >= 5;
-  if (tr_thin) p.cfg = 6;
+  if (tr_thin) p.cfg = WG_TR_128x128;
   int bm, bn;
   wgrad_tile(p.cfg, &bm, &bn);
   a.Mpad = round_up(a.ntaps * a.Gc, bm);

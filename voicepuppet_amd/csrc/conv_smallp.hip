@@ -21,6 +21,7 @@
 // stand-alone batch-norm kernels (pointwise.hip).
 #include <string.h>
 
+#include "conv_prof.h"
 #include "igemm_device.h"
 #include "launch.h"
 #include "smallp_args.h"
@@ -408,7 +409,7 @@ static hipError_t launch_smallp_t(const SmallPArgs& s, dim3 grid, hipStream_t st
   return hipGetLastError();
 }
 
-hipError_t launch_smallp(const SmallPArgs& s, int is_bf16, hipStream_t st) {
+static hipError_t launch_smallp_mode(const SmallPArgs& s, int is_bf16, hipStream_t st) {
   const IgemmArgs& a = s.g;
   const int npt_t = a.sp_npt, PT = npt_t * 16;
   const int Pc = a.N * a.Hg * a.Wg;
@@ -429,7 +430,17 @@ hipError_t launch_smallp(const SmallPArgs& s, int is_bf16, hipStream_t st) {
   return hipErrorInvalidValue;
 }
 
-// plain-epilogue form behind launch_igemm (IgemmArgs::kern == CK_SMALLP): the stand-alone op entry points and BN-free layers
+// the fused batch-norm forms (SmallPArgs::mode), launched by the step executor; timed like every other conv launch
+hipError_t launch_smallp(const SmallPArgs& s, int is_bf16, hipStream_t st) {
+  const IgemmArgs& a = s.g;
+  const double Pn = (double)a.N * a.Hg * a.Wg * a.nclass, kreal = (double)a.ntaps * a.cin_real, es = is_bf16 ? 2 : 4;
+  ProfScope prof("smallp", is_bf16, 32, a.sp_npt * 16, 2.0 * Pn * a.Cout * kreal,
+                 es * ((double)a.N * a.Hin * a.Win * a.cin_real + kreal * a.nclass * a.Cout + Pn * a.Cout), st);
+  return launch_smallp_mode(s, is_bf16, st);
+}
+
+// plain-epilogue form behind launch_igemm (the CK_SMALLP row of the kernel table, which writes the profile record): the stand-alone op
+// entry points and BN-free layers
 hipError_t launch_igemm_smallp(const IgemmArgs& a, int is_bf16, hipStream_t st) {
   SmallPArgs s;
   memset(&s, 0, sizeof(s));
@@ -438,7 +449,7 @@ hipError_t launch_igemm_smallp(const IgemmArgs& a, int is_bf16, hipStream_t st) 
   s.slab = a.partial;
   s.cnt = a.sp_cnt;
   s.mode = SP_PLAIN;
-  return launch_smallp(s, is_bf16, st);
+  return launch_smallp_mode(s, is_bf16, st);
 }
 
 }  // namespace vp

@@ -1,61 +1,44 @@
-// Host-side launchers implemented in conv_kernels.hip / pointwise.hip.
+// Host-side launchers of the kernels: the convolution entry points (conv_dispatch.hip runs the plan's kernel through its table, the
+// generic implicit GEMM is in conv_kernels.hip, the weight gradients in wgrad_kernels.hip), what the planner and the step executor call
+// by name beside the kernel it belongs to, and the pointwise launchers (pointwise.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "conv_args.h"
+#include "conv_dispatch.h"
 #include "pointwise_args.h"
 
 namespace vp {
 
-hipError_t launch_igemm(const IgemmArgs& a, int is_bf16, int cfg, hipStream_t st);
-void igemm_tile(int cfg, int* bc, int* bp);
-hipError_t launch_igemm_patch(const IgemmArgs& a, int is_bf16, int bc, int bp, hipStream_t st);                    // conv_patch.hip
-bool patch3_eligible(const IgemmArgs& a, int is_bf16);                                                               // conv_patch3.hip
-hipError_t launch_igemm_patch3(const IgemmArgs& a, int is_bf16, int bc, int bp, hipStream_t st);                   // conv_patch3.hip
-bool patch4_eligible(const IgemmArgs& a, int is_bf16);                                                               // conv_patch3.hip (KW = 4)
-hipError_t launch_igemm_patch4(const IgemmArgs& a, hipStream_t st);
-bool conv_kernel_ok(const IgemmArgs& a, int is_bf16);          // the preconditions of the plan's kernel (a.kern) hold for these arguments
-const char* conv_kernel_name(int kern);
-bool conv_cin8_eligible(const IgemmArgs& a, int is_bf16);                                                           // conv_thin.hip
-hipError_t launch_conv_cin8(const IgemmArgs& a, hipStream_t st);
-bool conv_cout8_eligible(const IgemmArgs& a, int is_bf16);
-hipError_t launch_conv_cout8(const IgemmArgs& a, hipStream_t st);
-bool conv_dcout8_eligible(const IgemmArgs& a, int is_bf16);
-hipError_t launch_conv_dcout8(const IgemmArgs& a, hipStream_t st);
-bool conv_cout4_eligible(const IgemmArgs& a, int is_bf16);
-hipError_t launch_conv_cout4(const IgemmArgs& a, hipStream_t st);
-bool conv_c64_eligible(const IgemmArgs& a, int is_bf16);                                                            // conv_c64.hip
-hipError_t launch_conv_c64(const IgemmArgs& a, hipStream_t st);
-bool conv_dc64_eligible(const IgemmArgs& a, int is_bf16);                                                           // conv_dc64.hip
-hipError_t launch_conv_dc64(const IgemmArgs& a, hipStream_t st);
+// tile configs: IgemmPlan::cfg indexes igemm_tile, WgradPlan::cfg wgrad_tile.  The values are visible outside the library
+// (vp_bfmstream_group_plan_info) and must not move; 8, 9 and wgrad 3, 4 are unused
+enum IgemmCfg {
+  IG_128x128 = 0, IG_64x128, IG_16x128, IG_128x32, IG_128x16, IG_64x32, IG_128x256, IG_256x256,                       // generic implicit GEMM (conv_kernels.hip)
+  PATCH_256x256 = 10, PATCH_128x512, PATCH_64x512, PATCH_128x256, PATCH_64x256, PATCH_256x128,                       // patch kernels
+  SMALLP_32x16 = 16, SMALLP_32x32, SMALLP_32x64,                                                                      // few-pixel kernel
+};
+enum WgradCfg { WG_128x128 = 0, WG_128x64, WG_128x16, WG_TR_256x128 = 5, WG_TR_128x128 = 6 };                        // WG_TR_*: wgrad_tr.hip
+void igemm_tile(int cfg, int* bc, int* bp);                                                                          // conv_kernels.hip
+void wgrad_tile(int cfg, int* bm, int* bn);                                                                          // wgrad_kernels.hip
+
+// conv_dc64.hip / conv_s2c64.hip: the blocks of a launch = the partial rows its epilogue writes
 int conv_dc64_grid(const IgemmArgs& a);                        // its blocks = partial rows of IgemmArgs::colsum_part
-bool conv_dc256_eligible(const IgemmArgs& a, int is_bf16);      // conv_dc64.hip: the forward form for 2 x 128 input channels (merged2_decoder_2)
 int conv_dc256_grid(const IgemmArgs& a);                       // its blocks; batch-norm partial rows = 2 per block
-hipError_t launch_conv_dc256(const IgemmArgs& a, hipStream_t st);
-bool conv_s2c64_eligible(const IgemmArgs& a, int is_bf16);                                                          // conv_s2c64.hip
-int conv_s2c64_grid(const IgemmArgs& a);                   // blocks of the launch = partial rows per batch-norm group
+int conv_s2c64_grid(const IgemmArgs& a);                       // blocks of the launch = partial rows per batch-norm group
 int conv_s2c64_tiles_per_image(const IgemmArgs& a);
-hipError_t launch_conv_s2c64(const IgemmArgs& a, hipStream_t st);
-bool conv_cout1_bwd_eligible(const Cout1Args& a);                                                                 // conv_cout1.hip
+// conv_cout1.hip (each launcher writes its own profile record)
+bool conv_cout1_bwd_eligible(const Cout1Args& a);
 hipError_t launch_conv_cout1_bwd(const Cout1Args& a, hipStream_t st);
 bool conv_cout1_wgrad_eligible(const Cout1Args& a);
 hipError_t launch_conv_cout1_wgrad(const Cout1Args& a, hipStream_t st);
-hipError_t launch_cout1_wgrad_prof(const Cout1Args& a, hipStream_t st);
-hipError_t launch_cout1_bwd_prof(const Cout1Args& a, hipStream_t st);                                               // ... with the per-launch profile record (conv_kernels.hip)
-hipError_t launch_igemm_patch2(const IgemmArgs& a, int is_bf16, int bc, int bp, hipStream_t st);                   // conv_patch2.hip
-hipError_t launch_igemm_smallp(const IgemmArgs& a, int is_bf16, hipStream_t st);                                   // conv_smallp.hip (plain epilogue)
+// conv_smallp.hip: the fused batch-norm forms (with its profile record)
 struct SmallPArgs;
-hipError_t launch_smallp(const SmallPArgs& s, int is_bf16, hipStream_t st);                                         // conv_smallp.hip (fused batch-norm forms)
-hipError_t launch_smallp_fused(const SmallPArgs& s, int is_bf16, hipStream_t st);                                   // ... with the per-launch profile record (conv_kernels.hip)
+hipError_t launch_smallp(const SmallPArgs& s, int is_bf16, hipStream_t st);
+// wgrad_kernels.hip / wgrad_mm.hip / wgrad_tr.hip
 hipError_t launch_wgrad(const WgradArgs& a, int is_bf16, int cfg, hipStream_t st);
-bool wgrad_mm_eligible(const WgradArgs& a, int cfg);                                                                                      // wgrad_mm.hip
+bool wgrad_mm_eligible(const WgradArgs& a, int cfg);
 hipError_t launch_wgrad_mm(const WgradArgs& a, int cfg, hipStream_t st);
-hipError_t launch_wgrad_tr(const WgradArgs& a, hipStream_t st, const char** variant = nullptr, int* tile_cols = nullptr);                                          // wgrad_tr.hip
-void wgrad_tile(int cfg, int* bm, int* bn);
-
-void profile_enable(int on);          // 1: per kernel kind, 2: per layer tag
-void profile_tag(const char* tag);
-size_t profile_collect(char* out, size_t cap);
+hipError_t launch_wgrad_tr(const WgradArgs& a, hipStream_t st, const char** variant = nullptr, int* tile_cols = nullptr);
 
 hipError_t launch_pack_weights(const PackDesc* d_descs, int ndesc, const float* master, void* packed, int is_bf16, hipStream_t st);
 hipError_t launch_pack_weights_one(const PackDesc& d, const float* master, void* packed, int is_bf16, hipStream_t st);

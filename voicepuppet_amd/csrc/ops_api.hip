@@ -55,42 +55,59 @@ int vp_pixrefer_pack_frames(const unsigned char* example_frames, const unsigned 
 
 extern "C" void vp_phase_marks_enable(int on);   // plan_pixrefer.hip
 
+// vp_tune: one row per key (the knobs and their defaults: conv_ops.h, audio_args.h)
+enum TuneRule {
+  TUNE_PLAIN,         // store any value
+  TUNE_POSITIVE,      // a non-positive value is refused like an unknown key
+  TUNE_NEG_RESETS,    // a negative value: back to the default
+  TUNE_0_TO_4,        // a value outside 0 .. 4: back to the default
+};
+struct TuneRow { const char* key; int* knob; TuneRule rule; int dflt; };      // dflt: what a reset stores (the resetting rules only)
+
 int vp_tune(const char* key, int value) {
   if (!key) return VP_ERR_ARG;
-  const std::string k(key);
-  if (k == "patch_tiles") { patch_tiles_knob() = value; return VP_OK; }
-  if (k == "patch_min_blocks") { patch_minblk_knob() = value < 0 ? PATCH_MIN_BLOCKS_DEFAULT : value; return VP_OK; }      // (< 0: back to the default)
-  if (k == "patch_small_tiles") { patch_small_knob() = value; return VP_OK; }
-  if (k == "patch_long_k_on_256") { patch_longk_knob() = value; return VP_OK; }
-  if (k == "wgrad_tr") { wgrad_tr_knob() = value; return VP_OK; }
-  if (k == "patch3") { patch3_knob() = value; return VP_OK; }
-  if (k == "c64") { c64_knob() = value; return VP_OK; }
-  if (k == "dc64") { dc64_knob() = value; return VP_OK; }
-  if (k == "pool_bwd_fused") { pool_bwd_fused_knob() = value < 0 || value > 4 ? 1 : value; return VP_OK; }
-  if (k == "cout1_wgrad_rows" && value > 0) { wgrad1_rows_knob() = value; return VP_OK; }
-  if (k == "cout1_bwd") { cout1_knob() = value < 0 ? 256 : value; return VP_OK; }
-  if (k == "s2c64") { s2c64_knob() = value; return VP_OK; }
-  if (k == "wgrad_big") { wgrad_big_knob() = value; return VP_OK; }
-  if (k == "patch4") { patch4_knob() = value; return VP_OK; }
-  if (k == "s2c64_pair") { s2c64_pair_knob() = value; return VP_OK; }
-  if (k == "bfm_dwproj") { bfm_dwproj_knob() = value; return VP_OK; }
-  if (k == "patch2") { patch2_knob() = value; return VP_OK; }
-  if (k == "patch_xcd") { patch_xcd_knob() = value; return VP_OK; }
-  if (k == "smallp_max_pixels") { smallp_knob() = value; return VP_OK; }
-  if (k == "igemm_splitk_target") { igemm_splitk_target_knob() = value < 0 ? IGEMM_SPLITK_TARGET_DEFAULT : value; return VP_OK; }
-  if (k == "wgrad_fixed_x10") { wgrad_cost_knob(0) = value; return VP_OK; }
-  if (k == "wgrad_slab_tile_x1000") { wgrad_cost_knob(2) = value < 0 ? 150 : value; return VP_OK; }      // (< 0: back to the default)
-  if (k == "wgrad_slab_x100") { wgrad_cost_knob(1) = value; return VP_OK; }
-  if (k == "smallp_split_target") { plan_misc_knob(0) = value; return VP_OK; }
-  if (k == "igemm_splitk_cap") { plan_misc_knob(1) = value; return VP_OK; }
-  if (k == "igemm_splitk_minchunk") { plan_misc_knob(2) = value; return VP_OK; }
-  if (k == "wgrad_resident_blocks") { plan_misc_knob(3) = value; return VP_OK; }
-  if (k == "igemm_small_grid") { igemm_small_grid_knob() = value; return VP_OK; }
-  if (k == "thin_blocks_cout8" && value > 0) { thin_blocks_knob(0) = value; return VP_OK; }
-  if (k == "thin_blocks_dcout8" && value > 0) { thin_blocks_knob(1) = value; return VP_OK; }
-  if (k == "thin_blocks_cout4" && value > 0) { thin_blocks_knob(2) = value; return VP_OK; }
-  if (k == "thin_blocks_cin8" && value > 0) { thin_blocks_knob(3) = value; return VP_OK; }
-  if (k == "phase_marks") { vp_phase_marks_enable(value); return VP_OK; }
+  static const TuneRow rows[] = {
+      {"patch_tiles", &patch_tiles_knob(), TUNE_PLAIN},
+      {"patch_min_blocks", &patch_minblk_knob(), TUNE_NEG_RESETS, PATCH_MIN_BLOCKS_DEFAULT},
+      {"patch_small_tiles", &patch_small_knob(), TUNE_PLAIN},
+      {"patch_long_k_on_256", &patch_longk_knob(), TUNE_PLAIN},
+      {"wgrad_tr", &wgrad_tr_knob(), TUNE_PLAIN},
+      {"patch3", &patch3_knob(), TUNE_PLAIN},
+      {"c64", &c64_knob(), TUNE_PLAIN},
+      {"dc64", &dc64_knob(), TUNE_PLAIN},
+      {"pool_bwd_fused", &pool_bwd_fused_knob(), TUNE_0_TO_4, 1},
+      {"cout1_wgrad_rows", &wgrad1_rows_knob(), TUNE_POSITIVE},
+      {"cout1_bwd", &cout1_knob(), TUNE_NEG_RESETS, 256},
+      {"s2c64", &s2c64_knob(), TUNE_PLAIN},
+      {"wgrad_big", &wgrad_big_knob(), TUNE_PLAIN},
+      {"patch4", &patch4_knob(), TUNE_PLAIN},
+      {"s2c64_pair", &s2c64_pair_knob(), TUNE_PLAIN},
+      {"bfm_dwproj", &bfm_dwproj_knob(), TUNE_PLAIN},
+      {"patch2", &patch2_knob(), TUNE_PLAIN},
+      {"patch_xcd", &patch_xcd_knob(), TUNE_PLAIN},
+      {"smallp_max_pixels", &smallp_knob(), TUNE_PLAIN},
+      {"igemm_splitk_target", &igemm_splitk_target_knob(), TUNE_NEG_RESETS, IGEMM_SPLITK_TARGET_DEFAULT},
+      {"wgrad_fixed_x10", &wgrad_cost_knob(0), TUNE_PLAIN},
+      {"wgrad_slab_x100", &wgrad_cost_knob(1), TUNE_PLAIN},
+      {"wgrad_slab_tile_x1000", &wgrad_cost_knob(2), TUNE_NEG_RESETS, 150},
+      {"smallp_split_target", &plan_misc_knob(0), TUNE_PLAIN},
+      {"igemm_splitk_cap", &plan_misc_knob(1), TUNE_PLAIN},
+      {"igemm_splitk_minchunk", &plan_misc_knob(2), TUNE_PLAIN},
+      {"wgrad_resident_blocks", &plan_misc_knob(3), TUNE_PLAIN},
+      {"igemm_small_grid", &igemm_small_grid_knob(), TUNE_PLAIN},
+      {"thin_blocks_cout8", &thin_blocks_knob(0), TUNE_POSITIVE},
+      {"thin_blocks_dcout8", &thin_blocks_knob(1), TUNE_POSITIVE},
+      {"thin_blocks_cout4", &thin_blocks_knob(2), TUNE_POSITIVE},
+      {"thin_blocks_cin8", &thin_blocks_knob(3), TUNE_POSITIVE},
+  };
+  if (!strcmp(key, "phase_marks")) { vp_phase_marks_enable(value); return VP_OK; }
+  for (const TuneRow& r : rows) {
+    if (strcmp(key, r.key)) continue;
+    if (r.rule == TUNE_POSITIVE && value <= 0) break;
+    const bool reset = (r.rule == TUNE_NEG_RESETS && value < 0) || (r.rule == TUNE_0_TO_4 && (value < 0 || value > 4));
+    *r.knob = reset ? r.dflt : value;
+    return VP_OK;
+  }
   set_err("vp_tune: unknown key %s", key);
   return VP_ERR_ARG;
 }

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "conv_ops.h"
+#include "conv_prof.h"
 #include "errors.h"
 #include "launch.h"
 #include "smallp_args.h"
@@ -835,7 +836,7 @@ static int run_layer_fwd(vp_pixrefer* h, Net& n, Layer& L, const Lane& ln, void*
       sp.eps = 1e-5f;   // pixrefer.py:100
     }
     profile_tag((L.scope + ":fwd").c_str());
-    VP_HIP_CHECK(launch_smallp_fused(sp, h->bf16, st));
+    VP_HIP_CHECK(launch_smallp(sp, h->bf16, st));
     if (!L.has_bn && (to.need_act[ACT_LRELU] || to.need_act[ACT_RELU]))
       VP_HIP_CHECK(launch_act_apply(to.y, nullptr, nullptr, to.C, (n.batch / n.groups) * to.H * to.W, (size_t)to.N * to.H * to.W,
                                     to.xa[ACT_LRELU], to.xa[ACT_RELU], h->bf16, st));
@@ -922,7 +923,7 @@ static int run_layer_wgrad(vp_pixrefer* h, Net& n, Layer& L, const void* dy, con
     if ((size_t)c.rows > cap) c.rows = (int)cap;
     if (c.rows >= 1 && L.g.Cin == 512 && conv_cout1_wgrad_eligible(c)) {
       profile_tag((L.scope + ":wgrad").c_str());
-      VP_HIP_CHECK(launch_cout1_wgrad_prof(c, st));
+      VP_HIP_CHECK(launch_conv_cout1_wgrad(c, st));
       own_wgrad = true;
     }
   }
@@ -1027,7 +1028,7 @@ static int run_layer_dgrad(vp_pixrefer* h, Net& n, Layer& L, const void* dy, con
       a.y2_f32 = t1.hi ? 1 : 0;
       SmallPArgs sp = smallp_args(a, L.sp_cnt_pair, ln);
       smallp_bn_bwd(sp, n, t0);
-      VP_HIP_CHECK(launch_smallp_fused(sp, h->bf16, st));
+      VP_HIP_CHECK(launch_smallp(sp, h->bf16, st));
     } else {
       try_bst(h, n, L, sub, a, L.bwd_pair, t0, 0, t0.dz_writes == t0.n_bwd_consumers);
       try_bst(h, n, L, sub, a, L.bwd_pair, t1, 1, t1.dz_writes == t1.n_bwd_consumers);
@@ -1075,7 +1076,7 @@ static int run_layer_dgrad(vp_pixrefer* h, Net& n, Layer& L, const void* dy, con
         smallp_bn_bwd(sp, n, ts);
         if (ts.hi) sp.g.y_f32 = 0;       // (a plain contribution to a float32 tensor says so in g.y_f32, this mode in `hi`)
       }
-      VP_HIP_CHECK(launch_smallp_fused(sp, h->bf16, st));
+      VP_HIP_CHECK(launch_smallp(sp, h->bf16, st));
       continue;
     }
     // the PatchGAN's last layer (4x4, stride 1, ONE output channel over 512): its own kernel (conv_cout1.hip), which also leaves the two
@@ -1102,7 +1103,7 @@ static int run_layer_dgrad(vp_pixrefer* h, Net& n, Layer& L, const void* dy, con
       if (sums) { c.part = gpass ? ts.bn.pbg : ts.bn.pb; c.y = at_sample(ts, ts.y, sample0, es); }
       if (tiles > 0 && c.rows > 0 && conv_cout1_bwd_eligible(c)) {
         if (sums) { (gpass ? ts.bst_chunks_g : ts.bst_chunks) = c.rows; h->bst_count++; }
-        VP_HIP_CHECK(launch_cout1_bwd_prof(c, st));
+        VP_HIP_CHECK(launch_conv_cout1_bwd(c, st));
         continue;
       }
     }

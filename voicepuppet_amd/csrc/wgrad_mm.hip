@@ -4,7 +4,7 @@
 // With v_mfma_f32_16x16x4_f32 a lane's operand is ONE float - A: (row = lane % 16, k = lane / 16), B: (k = lane / 16, column = lane % 16)
 // - and the contraction index k is the PIXEL.  So the [pixel][channel] rows go global -> LDS by LDS-DMA exactly as they lie in memory
 // (16-byte pieces, whole 512 / 256-byte row segments: coalesced), and a fragment is one ds_read_b32 per lane: 4 pixel rows x 16
-// consecutive channels.  The general weight-gradient kernel (conv_kernels.hip wgrad_kernel) loads 16-byte pieces into registers,
+// consecutive channels.  The general weight-gradient kernel (wgrad_kernels.hip wgrad_kernel) loads 16-byte pieces into registers,
 // transposes 4 x 4 blocks and writes them to LDS; here no vector ALU touches the operands.
 // Bank conflicts: a pixel row of the tile is 128 (64) floats = a multiple of the 64 banks, so the 4 rows of a k-step would collide.
 // The DMA lanes fetch the pieces of pixel row r rotated by 4 * (r % 4) pieces (which global piece a lane fetches is free): channel c

@@ -3,7 +3,7 @@
 //   dW[tap][g][d] = sum over pixels k = (n, q, r) of  G[pixel (+) tap, g] * D[pixel, d]
 //
 // The reduction index is the PIXEL - the slow index of both NHWC operands - while an MFMA lane needs 8 consecutive k of one row.
-// wgrad_kernel (conv_kernels.hip) gets there with register loads, 8x8 v_perm transposes and ds_writes in the loop.  Here both tiles
+// wgrad_kernel (wgrad_kernels.hip) gets there with register loads, 8x8 v_perm transposes and ds_writes in the loop.  Here both tiles
 // go global -> LDS by LDS-DMA exactly as they lie in memory ([pixel][channel]: whole 256 / 512-byte rows per pixel, no vector ALU on
 // the data, no ds_write), and the fragments come out of LDS with ds_read_b64_tr_b16: in each 16-lane group, lane a supplies the
 // address of ONE 8-byte chunk (4 channels of one pixel) and lane t receives element t % 4 of the chunks of lanes 4j + t / 4,
@@ -303,7 +303,7 @@ static hipError_t launch_wgrad_tr_t(const WgradArgs& a, hipStream_t st, const ch
   return hipGetLastError();
 }
 
-// wgrad cfg 5: 256 rows x 128 columns; cfg 6: 128 x 128 (the 6- / 3-channel input layers: 16 taps x 8 padded channels = 128 rows,
+// WG_TR_256x128: 256 rows x 128 columns; WG_TR_128x128 (the 6- / 3-channel input layers: 16 taps x 8 padded channels = 128 rows,
 // 64 real columns - HBM-bound, the point is the loader: LDS-DMA instead of register loads + 8x8 transposes)
 hipError_t launch_wgrad_tr(const WgradArgs& a, hipStream_t st, const char** variant, int* tile_cols) {
   if (tile_cols) *tile_cols = 128;
