@@ -15,7 +15,8 @@
  *   vp_bfmnet_*     replaces  voicepuppet/bfmnet/bfmnet.py:189-213,325-333 + tinynet.py:159-212
  *   vp_render_colors   replaces  utils/cython/mesh_core.h:63 _render_colors_core (mesh_core.cpp:169-231)
  *   vp_rasterize_triangles, vp_render_texture, vp_vertex_normals replace the rest of mesh_core.h:53-77 (_rasterize_triangles_core,
- *                             _render_texture_core, _get_normal_core: mesh_core.cpp:85-166, :234-333); vp_raster_interpolate goes with them
+ *                             _render_texture_core, _get_normal_core: mesh_core.cpp:85-166, :234-333); vp_raster_interpolate and
+ *                             vp_raster_vertex_visibility go with them
  *   vp_bfm_reconstruct replaces  utils/reconstruct_mesh.py:198-223 Reconstruction_rotation + infer_bfmvid.py:92-99
  *   vp_bfm_reconstruct_view replaces utils/reconstruct_mesh.py:172-194 Reconstruction + the packing of utils/bfm_visual.py:100-112 (view 0)
  *                             and voicepuppet/bfmnet/infer_bfmnet.py:212-216 (view 1)
@@ -23,7 +24,7 @@
  *   vp_landmark_distance replaces nothing: the reference judges BFMNet by the montage alone (68-landmark distance, on the device)
  *   vp_bfmfit_*        replaces  infer_bfmvid.py:47-74 and datasets/make_data_from_GRID.py:193-214 (FaceReconModel.pb, a frozen TF1 ResNet) for the
  *                             identity, expression and pose of the 257 coefficients: a float64 fit to 68 landmarks, batched over frames;
- *                             vp_bfmfit_observe / vp_bfmfit_appearance for texture and lighting: a float64 fit to the photo's pixels
+ *                             vp_bfmfit_observe(_ex) / vp_bfmfit_appearance for texture and lighting: a float64 fit to the photo's pixels
  *   vp_puppet_*        replaces  infer_bfmvid.py:110-121, :223-224, :229-238 for the rows of many talkers (stream groups)
  *   vp_jpeg_*          replaces  infer_bfmvid.py:243-244 (cv2.imwrite per frame) with a baseline JPEG encode on the device
  *   vp_png_*           replaces  train_pixrefer.py:105-118 (five tf.summary.image calls: PNG through zlib on the host) with a PNG encode on the device
@@ -550,6 +551,15 @@ int vp_render_colors(unsigned char* image, unsigned char* face_mask, const float
  *   sorted list of 3*triangle + corner) that depends on `triangles` alone: vp_vertex_adjacency_build fills `adjacency`
  *   (vp_vertex_adjacency_bytes(nver, ntri) bytes, 0 for bad sizes) once, vp_vertex_normals takes it with the same nver and ntri.
  *   Corners with an index outside 0 .. nver-1 are left out of it.
+ * vp_raster_vertex_visibility: no counterpart in the reference.  Is a vertex of the mesh that was rasterised in front of the surface the
+ *   depth buffer holds?  vertices f32 [batch,nver,3] as the rasteriser was given them, depth_buffer f32 [batch,h,w] as
+ *   vp_rasterize_triangles left it, visible u8 [batch,nver].  In float32, for a vertex (x, y, z): 1 when x, y or z is a NaN or x < 0,
+ *   x > w-1, y < 0, y > h-1 (the buffer says nothing about it); otherwise x0 = min((int)floorf(x), w-2), y0 likewise, m = the minimum
+ *   (fminf: a NaN depth is ignored) of the depths at (y0,x0), (y0,x0+1), (y0+1,x0), (y0+1,x0+1), and visible = (z + tol >= m).  The four
+ *   pixel centres surround the vertex; on its own, locally planar, surface at least one of them is no nearer than the vertex, so no
+ *   slope-dependent tolerance is needed (only a concave dip deeper than tol can fail).  An occluder that covers all four centres hides
+ *   the vertex; a vertex on an occlusion edge stays visible; an empty pixel (the caller's clear value) makes it visible.
+ *   Refused: h or w < 2, nver or batch < 1, tol negative or not finite.
  * ---------------------------------------------------------------------------------------------- */
 size_t vp_rasterize_triangles_workspace_bytes(int batch, int h, int w);
 int vp_rasterize_triangles(const float* vertices, const int* triangles, float* depth_buffer, int* triangle_buffer, float* barycentric_weight,
@@ -563,6 +573,8 @@ int vp_raster_interpolate(float* out, const int* triangle_buffer, const float* b
 size_t vp_vertex_adjacency_bytes(int nver, int ntri);
 int vp_vertex_adjacency_build(const int* triangles, int nver, int ntri, void* adjacency, size_t adjacency_bytes, void* stream);
 int vp_vertex_normals(float* normal, const float* tri_normal, const void* adjacency, int nver, int ntri, int batch, void* stream);
+int vp_raster_vertex_visibility(const float* vertices, const float* depth_buffer, unsigned char* visible, int nver, int h, int w, int batch, float tol,
+                                void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * BFM reconstruction for a clip ("next" row): replaces the per-frame numpy of
@@ -691,7 +703,26 @@ int vp_bfmfit_identity_step(const vp_bfm_model* m, const int* keypoints, int tab
  * coeff [frames,257] float32; rotation [frames,9] float64 = Compute_rotation_matrix(coeff[:, 224:227]) from the host, as for
  * vp_bfm_reconstruct_view; frames <= 65535; photo [photo_frames,H,W,3] uint8 RGB, photo_frames 1 (shared) or frames, H, W >= 2; affine [frames,3] float64
  * (a, bx, by): 224-image pixels -> photo pixels; vertex_weights NULL (ones) or [nver] float64 (a skin mask).  All device pointers.
- * Left out: self-occlusion (no z-buffer test; the facing weight is smooth, so no threshold can flip) and any pre-filter when a > 1.
+ * This call has no self-occlusion test (the facing weight is smooth, so no threshold can flip) and reads ONE bilinear tap whatever a is;
+ * vp_bfmfit_observe_ex adds both as options.
+ *
+ * vp_bfmfit_observe_ex: vp_bfmfit_observe's arguments, refusals and, with visibility = prefilter = 0, its bits (the geometry, sh, the
+ * inside test and the facing weight are the same device code), then `o` and `visible` (NULL or u8 [frames,nver]):
+ *   visibility = 1   per frame, float32 raster vertices (ss x, ss y, z_buffer): (x, y) = face_projection, z_buffer what view 0 of
+ *                    vp_bfm_reconstruct_view packs (greater = nearer), ss = raster_scale, the products in float64 and then rounded;
+ *                    depth cleared to -99999 and triangle ids to -1; vp_rasterize_triangles into a (224 ss)^2 buffer;
+ *                    vp_raster_vertex_visibility with tol = depth_tol (model units, decimetres); weight is multiplied by the 0 / 1 result,
+ *                    which also goes to `visible`.  Frames pass through the raster buffers in chunks of at most 8, so the workspace is
+ *                    frames x (a per-frame size) + a constant.  With visibility = 0, `visible` is not written.
+ *   prefilter = 1    a frame with a > 1 reads k x k bilinear taps per vertex, k = min(ceil(a), 16), at (px + ((i + 0.5) / k - 0.5) a,
+ *                    py + ((j + 0.5) / k - 0.5) a), each coordinate clamped to [0, W-1] x [0, H-1]; observed is their mean, in float64;
+ *                    inside is still the centre's.  Order of the sum: tap t = i + k j (i along x) belongs to lane t % 64 of a wave; a lane
+ *                    adds its taps in ascending t; the 64 lane sums are combined by an xor butterfly, strides 32, 16, 8, 4, 2, 1; the total
+ *                    is divided by k k.  It depends on k alone: a frame's numbers are the same bits in any batch.  A frame with a <= 1 takes
+ *                    vp_bfmfit_observe's single tap, bit for bit.
+ * Refused on the host before anything is enqueued: a struct_bytes other than vp_bfmfit_observe_opts_size(), visibility / prefilter not
+ * 0 or 1, raster_scale not 1, 2 or 4, a negative or non-finite depth_tol, everything vp_bfmfit_observe refuses, a short workspace.
+ * depth_tol = 0.01 (1 mm) is the Python callers' default and is UNTUNED on real photos.
  *
  * vp_bfmfit_appearance (inverts :58-62 and :129-168): Levenberg-Marquardt in float64 on p, the rule of vp_bfmfit_fit with
  *   A = J^T W J / W + Lambda, g = J^T W r / W + Lambda p;  d r_vc / d delta_j = L_vc texBase[3v+c, j];  d r_vc / d gamma_ck = Y_vk T_vc
@@ -718,6 +749,18 @@ size_t vp_bfmfit_observe_workspace_bytes(int nver, int ntri, int frames);
 int vp_bfmfit_observe(const vp_bfm_model* m, const float* coeff, const double* rotation, int frames, const unsigned char* photo, int photo_frames,
                       int height, int width, const double* affine, const double* vertex_weights, double* sh, double* weight, double* observed,
                       void* workspace, size_t workspace_bytes, void* stream);
+typedef struct vp_bfmfit_observe_opts {
+  uint32_t struct_bytes;   /* sizeof(vp_bfmfit_observe_opts) of the caller's build: must equal vp_bfmfit_observe_opts_size() */
+  int32_t visibility;      /* 0 | 1 */
+  int32_t raster_scale;    /* ss: 1, 2 or 4; the depth raster is (224*ss)^2 */
+  int32_t prefilter;       /* 0 | 1 */
+  float depth_tol;         /* model units (decimetres), >= 0 */
+} vp_bfmfit_observe_opts;
+size_t vp_bfmfit_observe_opts_size(void);
+size_t vp_bfmfit_observe_ex_workspace_bytes(int nver, int ntri, int frames, const vp_bfmfit_observe_opts* o);
+int vp_bfmfit_observe_ex(const vp_bfm_model* m, const float* coeff, const double* rotation, int frames, const unsigned char* photo, int photo_frames,
+                         int height, int width, const double* affine, const double* vertex_weights, double* sh, double* weight, double* observed,
+                         void* workspace, size_t workspace_bytes, void* stream, const vp_bfmfit_observe_opts* o, unsigned char* visible);
 size_t vp_bfmfit_appearance_workspace_bytes(int nver, int frames);
 int vp_bfmfit_appearance(const vp_bfm_model* m, const double* sh, const double* weight, const double* observed, const float* coeff_in, double* params,
                          int params_in, int frames, double lam_tex, double lam_gamma, double gtol, int max_trials, int stages, float* coeff,

@@ -113,6 +113,11 @@ class TriptychDesc(ctypes.Structure):
 TRIPTYCH_MAX_FRAMES, TRIPTYCH_MAX_SIZE = 4096, 1024   # include/vp_hip.h VP_TRIPTYCH_MAX_FRAMES, VP_TRIPTYCH_MAX_SIZE
 
 
+class BfmObserveOpts(ctypes.Structure):
+  _fields_ = [("struct_bytes", ctypes.c_uint32), ("visibility", ctypes.c_int32), ("raster_scale", ctypes.c_int32), ("prefilter", ctypes.c_int32),
+              ("depth_tol", ctypes.c_float)]
+
+
 class BfmModel(ctypes.Structure):
   _fields_ = [("nver", ctypes.c_int), ("ntri", ctypes.c_int), ("meanshape", ctypes.c_void_p), ("idBase", ctypes.c_void_p),
               ("exBase", ctypes.c_void_p), ("meantex", ctypes.c_void_p), ("texBase", ctypes.c_void_p), ("tri", ctypes.c_void_p),
@@ -327,6 +332,10 @@ _SIGNATURES = {
     "vp_bfmfit_identity_step": (ctypes.c_int, [_P, _P, ctypes.c_int, _P, _P, ctypes.c_int, _P, _P, ctypes.c_int, ctypes.c_double, _P, ctypes.c_size_t, _P]),
     "vp_bfmfit_observe_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "vp_bfmfit_observe": (ctypes.c_int, [_P, _P, _P, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
+    "vp_bfmfit_observe_opts_size": (ctypes.c_size_t, []),
+    "vp_bfmfit_observe_ex_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _P]),
+    "vp_bfmfit_observe_ex": (ctypes.c_int, [_P, _P, _P, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P, _P, _P, _P, _P,
+                                            ctypes.c_size_t, _P, _P, _P]),
     "vp_bfmfit_appearance_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
     "vp_bfmfit_appearance": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                             ctypes.c_int, ctypes.c_int, _P, _P, _P, ctypes.c_size_t, _P]),
@@ -338,6 +347,7 @@ _SIGNATURES = {
     "vp_render_texture_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "vp_render_texture": (ctypes.c_int, [_P] * 7 + [ctypes.c_int] * 12 + [_P, _P]),
     "vp_raster_interpolate": (ctypes.c_int, [_P] * 5 + [ctypes.c_int] * 6 + [_P]),
+    "vp_raster_vertex_visibility": (ctypes.c_int, [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, _P]),
     "vp_vertex_adjacency_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
     "vp_vertex_adjacency_build": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _P, ctypes.c_size_t, _P]),
     "vp_vertex_normals": (ctypes.c_int, [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P]),

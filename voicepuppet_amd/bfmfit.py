@@ -4,7 +4,8 @@ The reference obtains a photo's 257 coefficients and the `bfmcoeff.txt` rows BFM
 TensorFlow 1 ResNet (voicepuppet/pixrefer/infer_bfmvid.py:47-74, datasets/make_data_from_GRID.py:193-214).  This module gets identity
 (0:80), expression (80:144), angles (224:227) and translation (254:257) from a landmark file instead: it inverts `Reconstruction`
 (utils/reconstruct_mesh.py:172-194) for the 68 landmarks that function returns.  Texture (144:224) and lighting (227:254) come from the
-photo's pixels (`observe`, `fit_appearance`, `enroll(image=...)`; libvp_hip.so: vp_bfmfit_observe, vp_bfmfit_appearance; csrc/bfm_appear.hip),
+photo's pixels (`observe`, `fit_appearance`, `enroll(image=...)`; libvp_hip.so: vp_bfmfit_observe, vp_bfmfit_observe_ex, vp_bfmfit_appearance;
+csrc/bfm_appear.hip, csrc/bfm_observe.hip),
 with the geometry fixed at the landmark fit's; without a photo they stay at the caller's template, zeros by default, i.e. the mean albedo
 under ambient light.
 
@@ -267,13 +268,21 @@ class FaceFitter:
     t = t.to(self.model.device).contiguous()
     return t, (1 if t.dim() == 3 else int(t.shape[0])), int(t.shape[-3]), int(t.shape[-2])
 
-  def observe(self, coeff, photo, affine, vertex_weights=None):
+  def observe(self, coeff, photo, affine, vertex_weights=None, visibility=False, prefilter=False, raster_scale=2, depth_tol=0.01,
+              return_visible=False):
     """What the photo shows at the vertices of Reconstruction(coeff) (vp_bfmfit_observe).  coeff [frames,257] float32; photo [H,W,3] (shared)
     or [frames,H,W,3] uint8 RGB; affine [3] or [frames,3] float64 (a, bx, by), 224-image pixels -> photo pixels (`photo_affine`);
     vertex_weights None or [N] float64 (a skin mask).  Returns device float64 (sh [frames,N,9], weight [frames,N], observed [frames,N,3]):
     the SH terms of the rotated normals, mask x max(0, (n . R)_z) x inside, and the bilinear samples.  The rotation matrices are made on
     the host from coeff's angles, as reconstruct_view makes them (a device coeff is read back for that); everything else only enqueues.
-    No self-occlusion test and no pre-filter for a > 1."""
+    Two options, both off by default (the call is then vp_bfmfit_observe, as it always was; with either on, vp_bfmfit_observe_ex):
+      visibility  self-occlusion: the fitted mesh is rasterised into a depth buffer of (224 raster_scale)^2 pixels (raster_scale 1, 2 or 4)
+                  and a vertex that lies more than depth_tol behind the surface drawn around it gets weight 0
+                  (mesh_core.vertex_visibility states the rule).  depth_tol is in model units, decimetres: 0.01 = 1 mm is a default, not
+                  a tuned value.
+      prefilter   a frame whose a exceeds 1 is observed as the mean of k x k bilinear taps spread over the a x a photo pixels a pixel of
+                  the 224 image covers, k = min(ceil(a), 16); frames with a <= 1 keep their single tap.
+    return_visible: a fourth result, the 0 / 1 mask uint8 [frames,N] (needs visibility)."""
     torch, dev = self._torch, self.model.device
     from .utils.reconstruct_mesh import Compute_rotation_matrix
     c = (torch.from_numpy(np.ascontiguousarray(coeff, np.float32)) if isinstance(coeff, np.ndarray) else coeff).to(dev).contiguous()
@@ -292,17 +301,31 @@ class FaceFitter:
     sh = torch.empty(T, N, 9, dtype=torch.float64, device=dev)
     weight = torch.empty(T, N, dtype=torch.float64, device=dev)
     observed = torch.empty(T, N, 3, dtype=torch.float64, device=dev)
-    n = _lib.lib().vp_bfmfit_observe_workspace_bytes(N, self.model.ntri, T)
+    if return_visible and not visibility:
+      raise ValueError("observe: return_visible needs visibility=True")
+    if not (visibility or prefilter):
+      n = _lib.lib().vp_bfmfit_observe_workspace_bytes(N, self.model.ntri, T)
+      self._ws_obs = grow(self._ws_obs, n, dev)
+      _lib.check(_lib.lib().vp_bfmfit_observe(ctypes.byref(self.model.c), ptr(c), ptr(rot), T, ptr(img), photo_frames, H, W, ptr(aff), ptr(vw),
+                                              ptr(sh), ptr(weight), ptr(observed), ptr(self._ws_obs), self._ws_obs.numel(), stream()),
+                 "vp_bfmfit_observe")
+      return sh, weight, observed
+    opts = _lib.BfmObserveOpts(ctypes.sizeof(_lib.BfmObserveOpts), 1 if visibility else 0, int(raster_scale), 1 if prefilter else 0, float(depth_tol))
+    n = _lib.lib().vp_bfmfit_observe_ex_workspace_bytes(N, self.model.ntri, T, ctypes.byref(opts))
+    if n == 0:
+      raise ValueError("observe: %s" % _lib.lib().vp_last_error().decode())
     self._ws_obs = grow(self._ws_obs, n, dev)
-    _lib.check(_lib.lib().vp_bfmfit_observe(ctypes.byref(self.model.c), ptr(c), ptr(rot), T, ptr(img), photo_frames, H, W, ptr(aff), ptr(vw),
-                                            ptr(sh), ptr(weight), ptr(observed), ptr(self._ws_obs), self._ws_obs.numel(), stream()),
-               "vp_bfmfit_observe")
-    return sh, weight, observed
+    visible = torch.empty(T, N, dtype=torch.uint8, device=dev) if return_visible else None
+    _lib.check(_lib.lib().vp_bfmfit_observe_ex(ctypes.byref(self.model.c), ptr(c), ptr(rot), T, ptr(img), photo_frames, H, W, ptr(aff), ptr(vw),
+                                               ptr(sh), ptr(weight), ptr(observed), ptr(self._ws_obs), self._ws_obs.numel(), stream(),
+                                               ctypes.byref(opts), ptr(visible)), "vp_bfmfit_observe_ex")
+    return (sh, weight, observed, visible) if return_visible else (sh, weight, observed)
 
   def fit_appearance(self, coeff, photo=None, affine=None, observation=None, vertex_weights=None, init=None, params=None, lam_tex=1.0,
-                     lam_gamma=1.0, gtol=1e-6, max_trials=32, _stages=3):
+                     lam_gamma=1.0, gtol=1e-6, max_trials=32, _stages=3, visibility=False, prefilter=False):
     """Texture and lighting of coeff [frames,257] float32 (the landmark fit's output: its geometry is kept) from the photo's pixels
-    (vp_bfmfit_appearance).  Either photo + affine (see `observe`) or a ready observation = (sh, weight, observed).  init [frames,257]:
+    (vp_bfmfit_appearance).  Either photo + affine (see `observe`; `visibility` and `prefilter` are passed on to it, with its defaults for
+    raster_scale and depth_tol) or a ready observation = (sh, weight, observed).  init [frames,257]:
     start values of columns 144:224 and 227:254 (default: coeff's own); params [frames,107] float64: start from these instead.  Returns
     (coeff [frames,257] float32 with those columns fitted and every other column coeff's, report [frames,4] float64), device tensors; the
     float64 solution is kept in `self.last_appearance`.  A fixed chain of `max_trials` rounds; the call only enqueues.  `_stages` is for
@@ -316,7 +339,7 @@ class FaceFitter:
       raise ValueError("coeff must be float32 [frames,257]")
     T, N = int(c.shape[0]), self.model.nver
     if observation is None:
-      observation = self.observe(coeff, photo, affine, vertex_weights)
+      observation = self.observe(coeff, photo, affine, vertex_weights, visibility=visibility, prefilter=prefilter)
     sh, weight, observed = observation
     sh = self._device(sh, torch.float64, (T, N, 9), "sh")
     weight = self._device(weight, torch.float64, (T, N), "weight")
@@ -339,12 +362,13 @@ class FaceFitter:
     self.last_appearance, self.last_appearance_lams = p, (float(lam_tex), float(lam_gamma))
     return out, report
 
-  def enroll(self, landmarks_xy, img_h, img_w, lm3D, image=None, lam_tex=1.0, lam_gamma=1.0, **fit_args):
+  def enroll(self, landmarks_xy, img_h, img_w, lm3D, image=None, lam_tex=1.0, lam_gamma=1.0, visibility=False, prefilter=False,
+             **fit_args):
     """A photo's landmarks [68,2] (image pixels) -> the dictionary infer_bfmvid.py --bfmcoeff reads (np.savez(path, **d)): bfmcoeff [1,257]
     float32, transform_params [5], center_x, center_y, ratio.  crop_alignment, preprocess_landmarks and one full fit; the fit's report
     [1,4] (device) and the landmarks it was given [68,2] stay in `self.last_report` / `self.last_landmarks`.  With `image` ([img_h,img_w,3]
     uint8 RGB, numpy or device) texture and lighting are then fitted to it (`photo_affine`, `fit_appearance`; its report in
-    `self.last_appearance_report`); without, they stay zeros."""
+    `self.last_appearance_report`; `visibility` and `prefilter` are `observe`'s options, off by default); without, they stay zeros."""
     crop, center_x, center_y, ratio = crop_alignment(landmarks_xy, img_h, img_w)
     lm_new, trans_params = preprocess_landmarks(crop, lm3D)
     coeff, report = self.fit(lm_new.reshape(1, 68, 2), **fit_args)
@@ -353,6 +377,7 @@ class FaceFitter:
       if tuple(image.shape) != (img_h, img_w, 3):
         raise ValueError("enroll: image must be [img_h,img_w,3], got %s" % (tuple(image.shape),))
       coeff, self.last_appearance_report = self.fit_appearance(coeff, photo=image, affine=photo_affine(landmarks_xy, img_h, img_w, lm3D),
-                                                               lam_tex=lam_tex, lam_gamma=lam_gamma)
+                                                               lam_tex=lam_tex, lam_gamma=lam_gamma, visibility=visibility,
+                                                               prefilter=prefilter)
     return {"bfmcoeff": coeff.cpu().numpy().reshape(1, 257), "transform_params": trans_params, "center_x": center_x, "center_y": center_y,
             "ratio": ratio}

@@ -9,7 +9,9 @@
 --photo: the first line of the landmarks file is enrolled; photo.npz is what infer_bfmvid.py / infer_bfmnet.py take as --bfmcoeff
          (bfmcoeff [1,257], transform_params [5], center_x, center_y, ratio).  With --image (read with PIL as RGB; --size is then the
          image's own) texture and lighting (coefficients 144:224, 227:254) are fitted to the photo's pixels, with weights --lam_tex and
-         --lam_gamma on their squared norms (defaults 1, untuned on real photos); without it they stay zeros.
+         --lam_gamma on their squared norms (defaults 1, untuned on real photos); without it they stay zeros.  --visibility leaves
+         self-occluded vertices out of that fit and --prefilter area-averages a photo larger than the 224 image (FaceFitter.observe;
+         both off by default).
 --clip:  every line is a frame of ONE person; the frames are aligned one by one as the reference's data preparation does
          (datasets/make_data_from_GRID.py:193-214), fitted with FaceFitter.fit_sequence, and written as one row of 257 comma-separated
          values per frame: the bfmcoeff.txt that BFMCoeffLoader reads and train_bfmnet.py learns from.
@@ -92,6 +94,10 @@ def parse_options(argv=None):
   cmd_parser.add_option('--image', type="string", dest="image", default=None, help='--photo: the photo itself; fits texture and lighting to it')
   cmd_parser.add_option('--lam_tex', type="float", dest="lam_tex", default=1.0, help='--image: weight of |texture coefficients|^2')
   cmd_parser.add_option('--lam_gamma', type="float", dest="lam_gamma", default=1.0, help='--image: weight of |lighting coefficients|^2')
+  cmd_parser.add_option('--visibility', action="store_true", dest="visibility", default=False,
+                        help='--image: drop self-occluded vertices (a depth raster of the fitted mesh) from the observation')
+  cmd_parser.add_option('--prefilter', action="store_true", dest="prefilter", default=False,
+                        help='--image: area-average the photo where it has more than one pixel per pixel of the 224 image')
   cmd_parser.add_option('--out', type="string", dest="out", default=None, help='output file')
   cmd_parser.add_option('--rounds', type="int", dest="rounds", default=3, help='--clip: rounds of (identity steps, tracking fit)')
   cmd_parser.add_option('--id_steps', type="int", dest="id_steps", default=3, help='--clip: identity steps per round')
@@ -120,7 +126,8 @@ def main(argv=None):
   img_h, img_w = opts.size if image is None else image.shape[:2]
   if opts.photo:
     lms = read_landmarks(opts.photo)
-    photo = fitter.enroll(lms[0], img_h, img_w, lm3D, image=image, lam_tex=opts.lam_tex, lam_gamma=opts.lam_gamma)
+    photo = fitter.enroll(lms[0], img_h, img_w, lm3D, image=image, lam_tex=opts.lam_tex, lam_gamma=opts.lam_gamma,
+                          visibility=opts.visibility, prefilter=opts.prefilter)
     np.savez(opts.out, **photo)
     import torch
     coeff = torch.from_numpy(photo['bfmcoeff']).to(fitter.model.device)

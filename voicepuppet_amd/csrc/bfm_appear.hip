@@ -27,7 +27,8 @@
 
 #include "workspace.h"
 #include "fit_device.h"
-#include "bfm_device.h"      // (switches FMA contraction off from here on: the observation repeats bfm_recon.hip's bits)
+#include "bfm_observe_device.h"      // ObserveArgs and the per-vertex steps, shared with bfm_observe.hip (switches FMA contraction off from
+                                     // here on, through bfm_device.h: the observation repeats bfm_recon.hip's bits)
 
 namespace vp {
 
@@ -54,60 +55,18 @@ static int ap_slab_verts(int nver) {
 }
 static int ap_slabs(int nver) { const int sv = ap_slab_verts(nver); return (nver + sv - 1) / sv; }
 
-struct ObserveArgs {
-  const double* shape;       // [frames,N,3] unrotated, centred
-  const double* fn;          // [frames,F+1,3]
-  const int* point_buf;
-  const double* rot;         // [frames,9]
-  const float* coeff;        // [frames,257]
-  const unsigned char* photo;          // [photo_frames,H,W,3]
-  const double* affine;      // [frames,3] (a, bx, by)
-  const double* vertex_weights;        // optional [N]
-  double* sh; double* weight; double* observed;
-  int nver, ntri, photo_frames, height, width;
-  double focal, center;
-  double shc[5];
-};
-
 __global__ __launch_bounds__(256) void bfm_appear_observe_kernel(ObserveArgs a) {
   const int v = blockIdx.x * 256 + threadIdx.x;
   const int f = blockIdx.y;
   if (v >= a.nver) return;
-  const double* R = a.rot + f * 9;
-  double nx, ny, nz, mx, my, mz;
-  bfm_vertex_normal(a.fn + (size_t)f * (a.ntri + 1) * 3, a.point_buf, v, nx, ny, nz);
-  bfm_rotate(R, nx, ny, nz, mx, my, mz);
   const size_t fv = (size_t)f * a.nver + v;
-  const float* C = a.coeff + (size_t)f * 257;
-  double prx, pry, zb;
-  bfm_project(R, a.shape[fv * 3], a.shape[fv * 3 + 1], a.shape[fv * 3 + 2], (double)C[254], (double)C[255], (double)C[256], a.focal, a.center, prx,
-              pry, zb);
-  double Y[9];
-  bfm_sh_terms(a.shc, mx, my, mz, Y);
-#pragma unroll
-  for (int k = 0; k < 9; ++k) a.sh[fv * 9 + k] = Y[k];
-  const double s = a.affine[f * 3], px = s * prx + a.affine[f * 3 + 1], py = s * pry + a.affine[f * 3 + 2];
-  const bool inside = px >= 0.0 && px <= (double)(a.width - 1) && py >= 0.0 && py <= (double)(a.height - 1);      // false for a NaN
+  ObservedVertex ov;
+  observe_vertex(a, f, v, fv, ov);
   double o[3] = {0.0, 0.0, 0.0};
-  if (inside) {
-    int x0 = (int)floor(px), y0 = (int)floor(py);
-    if (x0 > a.width - 2) x0 = a.width - 2;                // px = W-1 is inside: the last cell with fx = 1
-    if (y0 > a.height - 2) y0 = a.height - 2;
-    const double fx = px - (double)x0, fy = py - (double)y0;
-    const unsigned char* img = a.photo + (a.photo_frames == 1 ? 0 : (size_t)f * a.height * a.width * 3);
-    const unsigned char* q0 = img + ((size_t)y0 * a.width + x0) * 3;
-    const unsigned char* q1 = q0 + (size_t)a.width * 3;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const double top = (1.0 - fx) * (double)q0[c] + fx * (double)q0[3 + c];
-      const double bot = (1.0 - fx) * (double)q1[c] + fx * (double)q1[3 + c];
-      o[c] = (1.0 - fy) * top + fy * bot;
-    }
-  }
+  if (ov.inside) observe_tap(observe_image(a, f), a.height, a.width, ov.px, ov.py, o);
 #pragma unroll
   for (int c = 0; c < 3; ++c) a.observed[fv * 3 + c] = o[c];
-  const double vw = a.vertex_weights ? a.vertex_weights[v] : 1.0;
-  a.weight[fv] = inside ? vw * fmax(0.0, mz) : 0.0;
+  a.weight[fv] = observe_weight(a, v, ov);
 }
 
 struct InitArgs {

@@ -2,7 +2,7 @@
 // triangle, its barycentric weights and the interpolated depth), _render_texture_core (:234-333), _get_normal_core (:85-105) and the
 // interpolation of per-vertex attributes through the buffers - bit-exact with the serial C++, batched over frames that share a
 // triangle list.  raster.hip is the flat-shaded quarter (_render_colors_core); the depth key and the barycentric arithmetic are shared
-// (raster_common.h).
+// (raster_common.h).  vp_raster_vertex_visibility, which has no counterpart there, asks the depth buffer which vertices it shows.
 //
 // Visibility.  The reference visits triangles in index order and overwrites a pixel when the candidate's depth is strictly greater
 // than the buffer, so a pixel's survivor is the maximum over its candidates of (p_depth, lowest index).  Parallel form, as in
@@ -13,6 +13,7 @@
 // bounding box holds it (:148, :292: no inside test there).  A NaN depth never wins in the reference ('>' is false); its bit pattern
 // would beat everything here, so it is skipped.
 #include <hip/hip_runtime.h>
+#include <float.h>
 #include <limits.h>
 #include <stdint.h>
 
@@ -289,6 +290,24 @@ __global__ __launch_bounds__(256) void vertex_normals_kernel(float* __restrict__
   N[0] = n0; N[1] = n1; N[2] = n2;
 }
 
+// one lane per (frame, vertex): is the vertex in front of (or on) the surface the depth buffer holds around it?  The four pixel centres
+// that surround (x, y) are compared, the nearest-to-the-back of them decides (fminf: a NaN depth is ignored).
+__global__ __launch_bounds__(256) void vertex_visibility_kernel(const float* __restrict__ vertices, const float* __restrict__ depth,
+                                                                unsigned char* __restrict__ visible, int nver, int h, int w, float tol) {
+  const int v = blockIdx.x * 256 + threadIdx.x;
+  if (v >= nver) return;
+  const size_t bv = (size_t)blockIdx.y * nver + v;
+  const float x = vertices[bv * 3], y = vertices[bv * 3 + 1], z = vertices[bv * 3 + 2];
+  unsigned char vis = 1;                                    // off the buffer or a NaN: the buffer says nothing about the vertex
+  if (x >= 0.f && x <= (float)(w - 1) && y >= 0.f && y <= (float)(h - 1) && z == z) {
+    const int x0 = min((int)floorf(x), w - 2), y0 = min((int)floorf(y), h - 2);
+    const float* D = depth + (size_t)blockIdx.y * h * w + (size_t)y0 * w + x0;
+    const float m = fminf(fminf(D[0], D[1]), fminf(D[w], D[w + 1]));
+    vis = (z + tol >= m) ? 1 : 0;
+  }
+  visible[bv] = vis;
+}
+
 static bool dense_sizes_ok(int nver, int ntri, int h, int w, int batch) {
   return ntri >= 0 && ntri <= INT_MAX / 3 && nver >= 1 && nver <= INT_MAX / 3 && h >= 1 && w >= 1 && (long long)h * w <= INT_MAX && batch >= 1 &&
          batch <= 65535;
@@ -374,6 +393,19 @@ int vp_raster_interpolate(float* out, const int* triangle_buffer, const float* b
   const size_t n = (size_t)batch * h * w;
   hipLaunchKernelGGL(vp::interpolate_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, out, triangle_buffer,
                      barycentric_weight, triangles, attributes, nver, ntri, k, (size_t)h * w, batch);
+  VP_HIP_CHECK(hipGetLastError());
+  return VP_OK;
+}
+
+int vp_raster_vertex_visibility(const float* vertices, const float* depth_buffer, unsigned char* visible, int nver, int h, int w, int batch, float tol,
+                                void* stream) {
+  if (!vertices || !depth_buffer || !visible || !vp::dense_sizes_ok(nver, 0, h, w, batch) || h < 2 || w < 2 || !(tol >= 0.f) || !(tol <= FLT_MAX)) {
+    vp::set_err("vp_raster_vertex_visibility: bad argument (null pointer, or nver %d, h %d, w %d, batch %d out of range (h, w >= 2), or tol %g "
+                "negative or not finite)", nver, h, w, batch, (double)tol);
+    return VP_ERR_ARG;
+  }
+  hipLaunchKernelGGL(vp::vertex_visibility_kernel, dim3((nver + 255) / 256, batch), dim3(256), 0, (hipStream_t)stream, vertices, depth_buffer,
+                     visible, nver, h, w, tol);
   VP_HIP_CHECK(hipGetLastError());
   return VP_OK;
 }

@@ -18,6 +18,7 @@ deep_video_portraits_v2, :690-695), which need TensorFlow 1, MXNet, OpenCV and F
 --alpha_dir DIR    <i>.jpg or <i>.png mattes, S x S after the same crop and resize: step 6's layout (render on black | matte) instead of step 5's
 --bfmcoeff FILE    rows of 257 coefficients to use instead of fitting them (fit_landmarks.py --clip writes such a file)
 --appearance first|none   first (default): texture and lighting are fitted to frame 0's pixels and shared by the clip; none: zeros
+--appearance_visibility, --appearance_prefilter   that fit without self-occluded vertices / on area means of frame 0 (both off by default)
 --frame_batch N    frames per device batch (default 32)
 --list FILE        gets the line "out_dir|count" appended: the list train_pixrefer.py reads
 
@@ -143,6 +144,10 @@ def parse_options(argv=None):
   p.add_option('--bfmcoeff', type='string', dest='bfmcoeff', default=None, help='rows of 257 coefficients instead of a fit')
   p.add_option('--appearance', type='choice', choices=['first', 'none'], dest='appearance', default='first',
                help='first: texture and lighting fitted to frame 0 and shared; none: zeros')
+  p.add_option('--appearance_visibility', action='store_true', dest='appearance_visibility', default=False,
+               help='--appearance first: leave self-occluded vertices out of that fit (FaceFitter.observe)')
+  p.add_option('--appearance_prefilter', action='store_true', dest='appearance_prefilter', default=False,
+               help='--appearance first: area-average frame 0 where it is larger than the 224 image')
   p.add_option('--frame_batch', type='int', dest='frame_batch', default=32, help='frames per device batch')
   p.add_option('--list', type='string', dest='list', default=None, help='dataset list to append "out_dir|count" to')
   p.add_option('--rounds', type='int', dest='rounds', default=3, help='fit_sequence: rounds of (identity steps, tracking fit)')
@@ -206,7 +211,8 @@ def main(argv=None):
   extra = ''
   if opts.appearance == 'first':
     frame0 = reader.read(0, 1)[0]
-    first, rep = fitter.fit_appearance(coeff[:1], photo=frame0, affine=photo_affine(lms[0], S, S, lm3D))
+    first, rep = fitter.fit_appearance(coeff[:1], photo=frame0, affine=photo_affine(lms[0], S, S, lm3D),
+                                       visibility=opts.appearance_visibility, prefilter=opts.appearance_prefilter)
     coeff = coeff.clone()
     coeff[:, 144:224], coeff[:, 227:254] = first[:, 144:224], first[:, 227:254]
     extra = ', appearance status %d' % int(rep[0, 0].item())

@@ -154,6 +154,26 @@ def interpolate(triangle_buffer, barycentric_weight, triangles, attributes, out=
   return out
 
 
+def vertex_visibility(vertices, depth_buffer, tol=0.0, out=None):
+  """Which vertices of the mesh `rasterize_triangles` drew lie in front of the depth buffer it left (vp_raster_vertex_visibility; no
+  counterpart in the reference's module): vertices f32 [F,nver,3], depth_buffer f32 [F,h,w] (h, w >= 2) -> u8 [F,nver].  A vertex is
+  visible when z + tol >= the minimum of the four depths around (x, y), in float32; a vertex off the buffer or with a NaN is visible.
+  tol >= 0, in the units of z."""
+  _check("vertex_visibility", ((vertices, torch.float32), (depth_buffer, torch.float32)))
+  if vertices.dim() != 3 or depth_buffer.dim() != 3 or vertices.shape[2] != 3 or vertices.shape[0] != depth_buffer.shape[0]:
+    raise ValueError("vertex_visibility: inconsistent shapes")
+  F, h, w = depth_buffer.shape
+  nver = vertices.shape[1]
+  if out is None:
+    out = torch.empty(F, nver, dtype=torch.uint8, device=vertices.device)
+  _check("vertex_visibility", ((out, torch.uint8),))
+  if tuple(out.shape) != (F, nver):
+    raise ValueError("vertex_visibility: inconsistent shapes")
+  _lib.check(_lib.lib().vp_raster_vertex_visibility(ptr(vertices), ptr(depth_buffer), ptr(out), nver, h, w, F, float(tol), stream()),
+             "vp_raster_vertex_visibility")
+  return out
+
+
 _adjacencies = {}     # id(triangle tensor) -> (weak reference to it, its version, nver, adjacency); tensors compare elementwise, hence the id
 
 
