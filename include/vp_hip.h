@@ -495,6 +495,70 @@ int vp_composite_fwd(const float* gen_out4, const float* targets, float* out4, f
                      void* stream);
 int vp_gan_loss(const float* logits, void* seed_d, void* seed_g, float* predict, float* losses, int m, float gan_weight, int dtype,
                 void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The PixReferNet training step's pointwise kernels one at a time (csrc/pointwise.hip; tests/test_gpu_pixrefer_pointwise_ops.py): an
+ * argument check and the launcher the step executor calls.  Tensors are [groups * pixels_per_group][c] in `dtype`; per-group vectors are
+ * [groups][c] float32; c is a multiple of the element vector (4 for VP_F32, 8 for VP_BF16); at most 1024 groups.  Every entry point returns VP_ERR_ARG before
+ * anything is enqueued for a null required pointer, a non-positive size or such a channel count; the two-pass batch-norm paths and
+ * vp_colsum_groups also for 256 % (c / vector) != 0 (the reduce kernel's thread layout).
+ *   vp_bn_groups_fwd       training-mode batch norm per group (pixrefer.py:99-101): scale / shift (z = scale * y + shift), mean, rstd, and
+ *                          optionally lrelu(z) / relu(z) (either may be null).  path: VP_BN_PATH_PLANNER takes the step planner's rule
+ *                          (one launch up to 2048 pixels per group), _TWO_PASS forces reduce + finalize (+ vp_act_apply's kernel),
+ *                          _ONE_LAUNCH forces the small-tensor kernel.  workspace: vp_bn_groups_workspace_bytes() (unused in one launch)
+ *   vp_bn_groups_bwd       dy = gamma rstd (dz - c1 - zhat c2) (dy may alias dz), c1 / c2 [groups][c], dgamma / dbeta [c] summed over the
+ *                          groups (accumulate != 0: added to what they hold), dbias_zero [c] (may be null) set to 0.  Same path argument
+ *   vp_bn_groups_bwd_tail  the same from caller-made partial rows [groups][nchunk][2][c] of doubles: (sum dz, sum dz zhat), or with
+ *                          raw = 1 the raw moments (sum dz, sum dz y) a convolution epilogue leaves
+ *   vp_colsum_groups       out[0:creal] (+)= sum over all pixels of x[.][0:creal], creal <= c (bias gradients of the BN-free layers)
+ *   vp_act_apply           out_lrelu / out_relu (either may be null) = act(scale[g] * y + shift[g]); scale and shift both null: act(y)
+ *   vp_relu_bwd            d[i] = y[i] > 0 ? d[i] : 0 in place, n elements
+ *   vp_tap_gather          discriminator layer_5 as a GEMM over taps, gather half: y[n][i][j] = bias[0] + sum over (kh, kw) inside the image
+ *                          of s[n][i + kh - pad][j + kw - pad][kh * ksize + kw], s [n][hin][win][16] float32, ksize <= 4
+ *   vp_tap_spread          its weight-gradient counterpart (ksize 4): dys[n][qi][qj][t] = dy[n][qi - t / 4 + pad][qj - t % 4 + pad][0] (0
+ *                          outside), dy [n][hout][wout][ld_dy], dys [n][hin][win][16], both in dtype
+ *   vp_pack_inputs         pixrefer.py:373-375, 295-306, 321: inputs [n][hw][6], fg_inputs [n][hw][fg_c] (fg_c 3 or 6) in [0, 1] ->
+ *                          gin = (2 in - 1, 0, 0), gfg = (2 fg[0:3] - 1, 0 x 5); train != 0 also din [3n][hw][8] = (in[3:6], fg[3:6], 0, 0) |
+ *                          (in[0:3], fg[0:3], 0, 0) | (in[3:6], 0 x 5) and the real half of vin [2n][hw][8] = (fg[3:6], 0 x 5)
+ *   vp_composite_fwd_train vp_composite_fwd plus what the training step needs: outputs_fg into channels 3:6 of din's fake group (channels
+ *                          0:3 kept, 6:8 zero) and into vin's fake half, and partial[vp_composite_nblocks(n, hw)][2] = per-block
+ *                          (sum |2 t - 1 - outputs|, sum |masks - alpha|); din / vin in dtype
+ *   vp_composite_bwd       gradient of Gen_loss w.r.t. the pre-tanh generator output: dy4 [n][hw][8] (channels 4:8 zero) from out4,
+ *                          outputs, targets, masks, d_din (channels 3:6 used) and d_vin (channels 0:3), both [n][hw][8] in dtype
+ *   vp_perceptual          f3 = real half | fake half of conv3_3 (post-relu), `half` elements each: partial[vp_perceptual_nblocks()] =
+ *                          per-block sum (fa - fb)^2, df3 = fb > 0 ? -(l1_weight / half) (fa - fb) : 0
+ *   vp_loss_final          losses[2] = Gen_loss_L1 = sum comp[.][0] / n_out + sum comp[.][1] / n_out + content, [4] = content =
+ *                          sum perc / 2 / n_feat, [3] = losses[1] gan_weight + losses[2] l1_weight; losses[0:2] are read, not written
+ * ---------------------------------------------------------------------------------------------- */
+enum { VP_BN_PATH_PLANNER = 0, VP_BN_PATH_TWO_PASS = 1, VP_BN_PATH_ONE_LAUNCH = 2 };
+size_t vp_bn_groups_workspace_bytes(int groups, int pixels_per_group, int c, int dtype);
+int vp_bn_groups_fwd(const void* y, int groups, int pixels_per_group, int c, int dtype, const float* gamma, const float* beta, float eps,
+                     float* scale, float* shift, float* mean, float* rstd, void* out_lrelu, void* out_relu, int path, void* workspace,
+                     void* stream);
+int vp_bn_groups_bwd(const void* y, const void* dz, void* dy, int groups, int pixels_per_group, int c, int dtype, const float* gamma,
+                     const float* mean, const float* rstd, float* c1, float* c2, float* dgamma, float* dbeta, float* dbias_zero,
+                     int accumulate, int path, void* workspace, void* stream);
+int vp_bn_groups_bwd_tail(const void* y, const void* dz, void* dy, int groups, int pixels_per_group, int c, int dtype, const float* gamma,
+                          const float* mean, const float* rstd, const double* partial, int nchunk, int raw, float* c1, float* c2,
+                          float* dgamma, float* dbeta, float* dbias_zero, int accumulate, void* stream);
+int vp_colsum_groups(const void* x, int groups, int pixels_per_group, int c, int creal, int dtype, float* out, int accumulate,
+                     void* workspace, void* stream);
+int vp_act_apply(const void* y, const float* scale, const float* shift, int groups, int pixels_per_group, int c, int dtype,
+                 void* out_lrelu, void* out_relu, void* stream);
+int vp_relu_bwd(const void* y, void* d, size_t n, int dtype, void* stream);
+int vp_tap_gather(const float* s, const float* bias, float* y, int n, int hin, int win, int ksize, int pad, void* stream);
+int vp_tap_spread(const void* dy, int ld_dy, void* dys, int n, int hin, int win, int pad, int dtype, void* stream);
+int vp_pack_inputs(const float* inputs, const float* fg_inputs, int fg_c, void* gin, void* gfg, void* din, void* vin, int n, int hw,
+                   int train, int dtype, void* stream);
+int vp_composite_nblocks(int n, int hw);
+int vp_composite_fwd_train(const float* gen_out4, const float* targets, const float* masks, float* out4, float* outputs, float* outputs_fg,
+                           void* din, void* vin, double* partial, int n, int hw, int dtype, void* stream);
+int vp_composite_bwd(const float* out4, const float* targets, const float* masks, const float* outputs, const void* d_din, const void* d_vin,
+                     void* dy4, int n, int hw, float l1_weight, int dtype, void* stream);
+int vp_perceptual_nblocks(size_t half, int dtype);
+int vp_perceptual(const void* f3, void* df3, double* partial, size_t half, float l1_weight, int dtype, void* stream);
+int vp_loss_final(const double* comp_partial, int n_comp, const double* perc_partial, int n_perc, double n_out, double n_feat,
+                  float l1_weight, float gan_weight, float* losses, void* stream);
 int vp_dwconv7x3_bn_act(const float* x, const float* w, const float* bias, float* y, int b, int h, int wd, int c, void* stream);
 int vp_dwconv7x3_bn_act_t(const void* x, const float* w, const float* bias, void* y, int dtype, int b, int h, int wd, int c, void* stream);
 int vp_conv_first_fwd(const float* x, const float* w, const float* bias, float* y, int b, int h, int w_in, int cout, void* stream);

@@ -7,6 +7,7 @@ LIB_PATH = os.environ.get("VP_LIB", os.path.join(_HERE, "libvp_hip.so"))   # VP_
 
 VP_F32, VP_BF16 = 0, 1
 ACT_NONE, ACT_LRELU, ACT_RELU, ACT_TANH, ACT_SIGMOID = 0, 1, 2, 3, 4
+BN_PATH_PLANNER, BN_PATH_TWO_PASS, BN_PATH_ONE_LAUNCH = 0, 1, 2      # include/vp_hip.h VP_BN_PATH_*
 
 
 class PixReferDesc(ctypes.Structure):
@@ -381,6 +382,22 @@ _SIGNATURES = {
     "vp_clip_scale_f32": (ctypes.c_int, [_P, ctypes.c_size_t, _P, ctypes.c_float, _P]),
     "vp_sumsq": (ctypes.c_int, [_P, ctypes.c_size_t, _P, _P]),
     "vp_bn_bwd": (ctypes.c_int, [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P, _P, _P, _P, _P, _P]),
+    "vp_bn_groups_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 4),
+    "vp_bn_groups_fwd": (ctypes.c_int, [_P] + [ctypes.c_int] * 4 + [_P, _P, ctypes.c_float] + [_P] * 6 + [ctypes.c_int, _P, _P]),
+    "vp_bn_groups_bwd": (ctypes.c_int, [_P, _P, _P] + [ctypes.c_int] * 4 + [_P] * 8 + [ctypes.c_int, ctypes.c_int, _P, _P]),
+    "vp_bn_groups_bwd_tail": (ctypes.c_int, [_P, _P, _P] + [ctypes.c_int] * 4 + [_P] * 4 + [ctypes.c_int, ctypes.c_int] + [_P] * 5 + [ctypes.c_int, _P]),
+    "vp_colsum_groups": (ctypes.c_int, [_P] + [ctypes.c_int] * 5 + [_P, ctypes.c_int, _P, _P]),
+    "vp_act_apply": (ctypes.c_int, [_P, _P, _P] + [ctypes.c_int] * 4 + [_P, _P, _P]),
+    "vp_relu_bwd": (ctypes.c_int, [_P, _P, ctypes.c_size_t, ctypes.c_int, _P]),
+    "vp_tap_gather": (ctypes.c_int, [_P, _P, _P] + [ctypes.c_int] * 5 + [_P]),
+    "vp_tap_spread": (ctypes.c_int, [_P, ctypes.c_int, _P] + [ctypes.c_int] * 5 + [_P]),
+    "vp_pack_inputs": (ctypes.c_int, [_P, _P, ctypes.c_int, _P, _P, _P, _P] + [ctypes.c_int] * 4 + [_P]),
+    "vp_composite_nblocks": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
+    "vp_composite_fwd_train": (ctypes.c_int, [_P] * 9 + [ctypes.c_int] * 3 + [_P]),
+    "vp_composite_bwd": (ctypes.c_int, [_P] * 7 + [ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_int, _P]),
+    "vp_perceptual_nblocks": (ctypes.c_int, [ctypes.c_size_t, ctypes.c_int]),
+    "vp_perceptual": (ctypes.c_int, [_P, _P, _P, ctypes.c_size_t, ctypes.c_float, ctypes.c_int, _P]),
+    "vp_loss_final": (ctypes.c_int, [_P, ctypes.c_int, _P, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_float, ctypes.c_float, _P, _P]),
 }
 
 # vp_X_desc_size -> the structure that restates vp_X_desc here: lib() compares the two sizes.  A new descriptor gets its line

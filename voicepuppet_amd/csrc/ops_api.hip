@@ -355,6 +355,234 @@ int vp_gan_loss(const float* logits, void* seed_d, void* seed_g, float* predict,
   return VP_OK;
 }
 
+// ---- the PixReferNet step's pointwise kernels one at a time (tests/test_gpu_pixrefer_pointwise_ops.py): an argument check and the
+// launcher the step executor calls, nothing else ----
+
+static bool dtype_ok(int dtype) { return dtype == VP_F32 || dtype == VP_BF16; }
+static int elem_of(int dtype) { return dtype == VP_BF16 ? 8 : 4; }
+// channels a multiple of the element vector; reduce: the channel groups also divide the 256 threads of bn_reduce_kernel
+static bool chan_ok(int c, int dtype, bool reduce) {
+  if (!dtype_ok(dtype) || c < elem_of(dtype) || c % elem_of(dtype)) return false;
+  return !reduce || 256 % (c / elem_of(dtype)) == 0;
+}
+static bool bn_one_launch(int path, int pg) {
+  BnArgs b;
+  memset(&b, 0, sizeof(b));
+  b.Pg = pg;
+  return path == VP_BN_PATH_ONE_LAUNCH || (path == VP_BN_PATH_PLANNER && bn_small(b));
+}
+static bool bn_groups_ok(int groups, int pg, int c, int dtype, int path) {
+  if (groups < 1 || groups > 1024 || pg < 1 || path < VP_BN_PATH_PLANNER || path > VP_BN_PATH_ONE_LAUNCH) return false;
+  return chan_ok(c, dtype, !bn_one_launch(path, pg));
+}
+
+size_t vp_bn_groups_workspace_bytes(int groups, int pixels_per_group, int c, int dtype) {
+  if (groups < 1 || groups > 1024 || pixels_per_group < 1 || !chan_ok(c, dtype, true)) return 0;
+  const int nch = bn_nchunk(pixels_per_group, c, groups, dtype == VP_BF16);
+  return (size_t)groups * nch * 2 * c * sizeof(double) + 1024;
+}
+
+int vp_bn_groups_fwd(const void* y, int groups, int pixels_per_group, int c, int dtype, const float* gamma, const float* beta, float eps,
+                     float* scale, float* shift, float* mean, float* rstd, void* out_lrelu, void* out_relu, int path, void* workspace,
+                     void* stream) {
+  if (!bn_groups_ok(groups, pixels_per_group, c, dtype, path) || !y || !gamma || !beta || !scale || !shift || !mean || !rstd ||
+      (!workspace && !bn_one_launch(path, pixels_per_group))) {
+    set_err("vp_bn_groups_fwd: bad argument");
+    return VP_ERR_ARG;
+  }
+  const int bf = dtype == VP_BF16;
+  BnArgs b;
+  memset(&b, 0, sizeof(b));
+  b.y = y; b.C = c; b.G = groups; b.Pg = pixels_per_group;
+  b.gamma = gamma; b.beta = beta; b.aff_a = scale; b.aff_b = shift; b.mu = mean; b.rstd = rstd; b.eps = eps;
+  if (bn_one_launch(path, pixels_per_group)) {
+    b.nchunk = 1;
+    VP_HIP_CHECK(launch_bn_small_fwd(b, out_lrelu, out_relu, bf, (hipStream_t)stream));
+    return VP_OK;
+  }
+  b.nchunk = bn_nchunk(pixels_per_group, c, groups, bf);
+  b.partial = (double*)workspace;
+  VP_HIP_CHECK(launch_bn_stats(b, bf, (hipStream_t)stream));
+  if (out_lrelu || out_relu)
+    VP_HIP_CHECK(launch_act_apply(y, scale, shift, c, pixels_per_group, (size_t)groups * pixels_per_group, out_lrelu, out_relu, bf, (hipStream_t)stream));
+  return VP_OK;
+}
+
+int vp_bn_groups_bwd(const void* y, const void* dz, void* dy, int groups, int pixels_per_group, int c, int dtype, const float* gamma,
+                     const float* mean, const float* rstd, float* c1, float* c2, float* dgamma, float* dbeta, float* dbias_zero,
+                     int accumulate, int path, void* workspace, void* stream) {
+  if (!bn_groups_ok(groups, pixels_per_group, c, dtype, path) || !y || !dz || !dy || !gamma || !mean || !rstd || !c1 || !c2 || !dgamma ||
+      !dbeta || (!workspace && !bn_one_launch(path, pixels_per_group))) {
+    set_err("vp_bn_groups_bwd: bad argument");
+    return VP_ERR_ARG;
+  }
+  const int bf = dtype == VP_BF16;
+  BnArgs b;
+  memset(&b, 0, sizeof(b));
+  b.y = y; b.dz = dz; b.dy = dy; b.C = c; b.G = groups; b.Pg = pixels_per_group;
+  b.c1 = c1; b.c2 = c2;
+  b.gamma = gamma; b.mu = const_cast<float*>(mean); b.rstd = const_cast<float*>(rstd);
+  b.dgamma = dgamma; b.dbeta = dbeta; b.dbias_zero = dbias_zero; b.accumulate = accumulate != 0;
+  if (bn_one_launch(path, pixels_per_group)) {
+    b.nchunk = 1;
+    VP_HIP_CHECK(launch_bn_small_bwd(b, bf, (hipStream_t)stream));
+    return VP_OK;
+  }
+  b.nchunk = bn_nchunk(pixels_per_group, c, groups, bf);
+  b.partial = (double*)workspace;
+  VP_HIP_CHECK(launch_bn_bwd(b, bf, (hipStream_t)stream));
+  return VP_OK;
+}
+
+int vp_bn_groups_bwd_tail(const void* y, const void* dz, void* dy, int groups, int pixels_per_group, int c, int dtype, const float* gamma,
+                          const float* mean, const float* rstd, const double* partial, int nchunk, int raw, float* c1, float* c2,
+                          float* dgamma, float* dbeta, float* dbias_zero, int accumulate, void* stream) {
+  if (groups < 1 || pixels_per_group < 1 || !chan_ok(c, dtype, false) || nchunk < 1 || (raw != 0 && raw != 1) || !y || !dz || !dy || !gamma ||
+      !mean || !rstd || !partial || !c1 || !c2 || !dgamma || !dbeta) {
+    set_err("vp_bn_groups_bwd_tail: bad argument");
+    return VP_ERR_ARG;
+  }
+  BnArgs b;
+  memset(&b, 0, sizeof(b));
+  b.y = y; b.dz = dz; b.dy = dy; b.C = c; b.G = groups; b.Pg = pixels_per_group;
+  b.nchunk = nchunk; b.partial = const_cast<double*>(partial); b.raw = raw;
+  b.c1 = c1; b.c2 = c2;
+  b.gamma = gamma; b.mu = const_cast<float*>(mean); b.rstd = const_cast<float*>(rstd);
+  b.dgamma = dgamma; b.dbeta = dbeta; b.dbias_zero = dbias_zero; b.accumulate = accumulate != 0;
+  VP_HIP_CHECK(launch_bn_bwd_tail(b, dtype == VP_BF16, (hipStream_t)stream));
+  return VP_OK;
+}
+
+int vp_colsum_groups(const void* x, int groups, int pixels_per_group, int c, int creal, int dtype, float* out, int accumulate,
+                     void* workspace, void* stream) {
+  if (groups < 1 || groups > 1024 || pixels_per_group < 1 || !chan_ok(c, dtype, true) || creal < 1 || creal > c || !x || !out || !workspace) {
+    set_err("vp_colsum_groups: bad argument");
+    return VP_ERR_ARG;
+  }
+  BnArgs b;
+  memset(&b, 0, sizeof(b));
+  b.y = x; b.C = c; b.G = groups; b.Pg = pixels_per_group;
+  b.nchunk = bn_nchunk(pixels_per_group, c, groups, dtype == VP_BF16);
+  b.partial = (double*)workspace;
+  VP_HIP_CHECK(launch_colsum(b, creal, out, accumulate != 0, dtype == VP_BF16, (hipStream_t)stream));
+  return VP_OK;
+}
+
+int vp_act_apply(const void* y, const float* scale, const float* shift, int groups, int pixels_per_group, int c, int dtype,
+                 void* out_lrelu, void* out_relu, void* stream) {
+  if (groups < 1 || pixels_per_group < 1 || !chan_ok(c, dtype, false) || !y || (!scale) != (!shift) || (!out_lrelu && !out_relu)) {
+    set_err("vp_act_apply: bad argument");
+    return VP_ERR_ARG;
+  }
+  VP_HIP_CHECK(launch_act_apply(y, scale, shift, c, pixels_per_group, (size_t)groups * pixels_per_group, out_lrelu, out_relu, dtype == VP_BF16,
+                                (hipStream_t)stream));
+  return VP_OK;
+}
+
+int vp_relu_bwd(const void* y, void* d, size_t n, int dtype, void* stream) {
+  if (!y || !d || n < 1 || !dtype_ok(dtype) || n % elem_of(dtype)) { set_err("vp_relu_bwd: bad argument"); return VP_ERR_ARG; }
+  VP_HIP_CHECK(launch_relu_bwd(y, d, n, dtype == VP_BF16, (hipStream_t)stream));
+  return VP_OK;
+}
+
+int vp_tap_gather(const float* s, const float* bias, float* y, int n, int hin, int win, int ksize, int pad, void* stream) {
+  if (!s || !bias || !y || n < 1 || hin < 1 || win < 1 || ksize < 1 || ksize > 4 || pad < 0 || hin + 2 * pad - ksize + 1 < 1 ||
+      win + 2 * pad - ksize + 1 < 1) {
+    set_err("vp_tap_gather: bad argument");
+    return VP_ERR_ARG;
+  }
+  TapArgs t;
+  memset(&t, 0, sizeof(t));
+  t.S = s; t.bias = bias; t.y = y; t.N = n; t.Hin = hin; t.Win = win; t.ks = ksize; t.pad = pad;
+  t.Hout = hin + 2 * pad - ksize + 1; t.Wout = win + 2 * pad - ksize + 1;
+  VP_HIP_CHECK(launch_tap_gather(t, (hipStream_t)stream));
+  return VP_OK;
+}
+
+int vp_tap_spread(const void* dy, int ld_dy, void* dys, int n, int hin, int win, int pad, int dtype, void* stream) {
+  if (!dy || !dys || ld_dy < 1 || n < 1 || hin < 1 || win < 1 || pad < 0 || hin + 2 * pad - 3 < 1 || win + 2 * pad - 3 < 1 || !dtype_ok(dtype)) {
+    set_err("vp_tap_spread: bad argument");
+    return VP_ERR_ARG;
+  }
+  TapArgs t;
+  memset(&t, 0, sizeof(t));
+  t.dy = dy; t.dyS = dys; t.ld_dy = ld_dy; t.N = n; t.Hin = hin; t.Win = win; t.ks = 4; t.pad = pad;
+  t.Hout = hin + 2 * pad - 3; t.Wout = win + 2 * pad - 3;
+  VP_HIP_CHECK(launch_tap_spread(t, dtype == VP_BF16, (hipStream_t)stream));
+  return VP_OK;
+}
+
+int vp_pack_inputs(const float* inputs, const float* fg_inputs, int fg_c, void* gin, void* gfg, void* din, void* vin, int n, int hw,
+                   int train, int dtype, void* stream) {
+  if (!inputs || !fg_inputs || (fg_c != 3 && fg_c != 6) || !gin || !gfg || (train && (!din || !vin)) || n < 1 || hw < 1 || !dtype_ok(dtype)) {
+    set_err("vp_pack_inputs: bad argument");
+    return VP_ERR_ARG;
+  }
+  PackInputsArgs p;
+  memset(&p, 0, sizeof(p));
+  p.inputs = inputs; p.fg_inputs = fg_inputs; p.fg_c = fg_c; p.gin = gin; p.gfg = gfg; p.din = din; p.vin = vin;
+  p.N = n; p.HW = hw; p.train = train != 0;
+  VP_HIP_CHECK(launch_pack_inputs(p, dtype == VP_BF16, (hipStream_t)stream));
+  return VP_OK;
+}
+
+int vp_composite_nblocks(int n, int hw) { return (n < 1 || hw < 1) ? 0 : composite_nblocks(n, hw); }
+
+int vp_composite_fwd_train(const float* gen_out4, const float* targets, const float* masks, float* out4, float* outputs, float* outputs_fg,
+                           void* din, void* vin, double* partial, int n, int hw, int dtype, void* stream) {
+  if (!gen_out4 || !targets || !masks || !out4 || !outputs || !outputs_fg || !din || !vin || !partial || n < 1 || hw < 1 || !dtype_ok(dtype)) {
+    set_err("vp_composite_fwd_train: bad argument");
+    return VP_ERR_ARG;
+  }
+  CompositeArgs ca;
+  memset(&ca, 0, sizeof(ca));
+  ca.y4 = gen_out4; ca.targets = targets; ca.masks = masks; ca.o4 = out4; ca.outputs = outputs; ca.outputs_fg = outputs_fg;
+  ca.din = din; ca.vin = vin; ca.partial = partial; ca.N = n; ca.HW = hw; ca.train = 1;
+  VP_HIP_CHECK(launch_composite_fwd(ca, dtype == VP_BF16, (hipStream_t)stream));
+  return VP_OK;
+}
+
+int vp_composite_bwd(const float* out4, const float* targets, const float* masks, const float* outputs, const void* d_din, const void* d_vin,
+                     void* dy4, int n, int hw, float l1_weight, int dtype, void* stream) {
+  if (!out4 || !targets || !masks || !outputs || !d_din || !d_vin || !dy4 || n < 1 || hw < 1 || !dtype_ok(dtype)) {
+    set_err("vp_composite_bwd: bad argument");
+    return VP_ERR_ARG;
+  }
+  CompositeArgs ca;
+  memset(&ca, 0, sizeof(ca));
+  ca.targets = targets; ca.masks = masks; ca.o4 = const_cast<float*>(out4); ca.outputs = const_cast<float*>(outputs);
+  ca.d_din = d_din; ca.d_vin = d_vin; ca.dy4 = dy4; ca.N = n; ca.HW = hw; ca.train = 1; ca.l1_weight = l1_weight;
+  VP_HIP_CHECK(launch_composite_bwd(ca, dtype == VP_BF16, (hipStream_t)stream));
+  return VP_OK;
+}
+
+int vp_perceptual_nblocks(size_t half, int dtype) {
+  return (half < 1 || !dtype_ok(dtype) || half % elem_of(dtype)) ? 0 : perceptual_nblocks(half, dtype == VP_BF16);
+}
+
+int vp_perceptual(const void* f3, void* df3, double* partial, size_t half, float l1_weight, int dtype, void* stream) {
+  if (!f3 || !df3 || !partial || half < 1 || !dtype_ok(dtype) || half % elem_of(dtype)) { set_err("vp_perceptual: bad argument"); return VP_ERR_ARG; }
+  PerceptualArgs pa;
+  memset(&pa, 0, sizeof(pa));
+  pa.f3 = f3; pa.df3 = df3; pa.partial = partial; pa.half = half; pa.l1_weight = l1_weight;
+  VP_HIP_CHECK(launch_perceptual(pa, dtype == VP_BF16, (hipStream_t)stream));
+  return VP_OK;
+}
+
+int vp_loss_final(const double* comp_partial, int n_comp, const double* perc_partial, int n_perc, double n_out, double n_feat,
+                  float l1_weight, float gan_weight, float* losses, void* stream) {
+  if (!comp_partial || !perc_partial || !losses || n_comp < 1 || n_perc < 1 || !(n_out > 0) || !(n_feat > 0)) {
+    set_err("vp_loss_final: bad argument");
+    return VP_ERR_ARG;
+  }
+  LossFinalArgs la;
+  memset(&la, 0, sizeof(la));
+  la.comp_partial = comp_partial; la.n_comp = n_comp; la.perc_partial = perc_partial; la.n_perc = n_perc;
+  la.n_out = n_out; la.n_feat = n_feat; la.losses = losses; la.l1_weight = l1_weight; la.gan_weight = gan_weight;
+  VP_HIP_CHECK(launch_loss_final(la, (hipStream_t)stream));
+  return VP_OK;
+}
+
 int vp_dwconv7x3_bn_act(const float* x, const float* w, const float* bias, float* y, int b, int h, int wd, int c, void* stream) {
   if (!x || !w || !bias || !y || b < 1 || h < 1 || wd < 1 || c < 4 || (c & 3)) { set_err("vp_dwconv7x3_bn_act: bad argument"); return VP_ERR_ARG; }
   VP_HIP_CHECK(launch_dwconv7x3(x, w, bias, y, 0, b, h, wd, c, (hipStream_t)stream));
