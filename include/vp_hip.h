@@ -745,6 +745,46 @@ int vp_bfmfit_identity_step(const vp_bfm_model* m, const int* keypoints, int tab
                             void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Joint fit of a clip to its landmarks: ONE identity for the clip, expression and pose per frame, optionally coupled in time.  The same
+ * inverse of `Reconstruction` (utils/reconstruct_mesh.py:172-194) as vp_bfmfit_fit and the same replacement of FaceReconModel.pb
+ * (voicepuppet/pixrefer/infer_bfmvid.py:47-74, datasets/make_data_from_GRID.py:193-214), for the rows of a clip's bfmcoeff.txt: what
+ * BFMNet's loss (voicepuppet/bfmnet/bfmnet.py add_cost_function) differences in time.  A clip has frames t = 1 .. T; unknowns alpha (80) and
+ * q_t = [beta_t (64) | angles (3) | t (3)], 80 + 70 T numbers, a frame's parameters laid out as vp_bfmfit_fit's p[150]:
+ *   E = sum_t ( sum_k w_tk |pi_k(alpha, q_t) - l_tk|^2 + lam_id |alpha|^2 + lam_ex |beta_t|^2 )                  (T lam_id |alpha|^2 in all)
+ *     + sum_{t<T} ( s_ex |beta_t+1 - beta_t|^2 + s_ang |ang_t+1 - ang_t|^2 + s_t |t_t+1 - t_t|^2 ),   lam_smooth = (s_ex, s_ang, s_t)
+ * With lam_smooth = (0, 0, 0) this is the sum of vp_bfmfit_fit's cost over the frames for a shared alpha.  Useful values of lam_smooth are
+ * UNTUNED on real landmark files.
+ * Levenberg-Marquardt in float64 on the whole clip, the rule of vp_bfmfit_fit: A = J^T W J + Lambda + the coupling's Hessian, g likewise;
+ * (A + mu diag A) d = -g by Cholesky; E falls: accept, mu <- max(mu / 3, 1e-9); anything else (a non-finite cost included) rejects,
+ * mu <- 4 mu; mu > 1e8: status 2; mu0 = 1e-3; a factorisation that fails raises mu the same way without an evaluation; status 0 when
+ * |g|_inf <= gtol over all 80 + 70 T unknowns; status 1 when max_trials trial points have been evaluated; status 3 for non-finite landmarks
+ * or start values, and the start values go back.  "E falls" is sum_t (E_t(trial) - E_t(current)) + (coupling(trial) - coupling(current)) < 0,
+ * added in frame order: not a difference of two clip totals, so the float64 floor of the test stays at one frame's magnitude.
+ * A is block arrowhead: 70x70 frame blocks on a chain whose off-diagonal blocks are -diag(s), bordered by the 70x80 alpha coupling, corner
+ * 80x80.  A fit is a fixed chain of launches (init, frames, (clip, frames) x max_trials, clip), nothing is read back: `frames` (one
+ * workgroup per frame) evaluates a frame's 150x150 system at the trial point, `clip` (one workgroup per clip) applies the rule, eliminates
+ * the chain by a block Cholesky sweep forward over t (per-frame factors kept in the workspace), solves the corner's Schur complement,
+ * substitutes back and writes the next trial point.  Both leave a clip with a status alone.  Fixed summation order, no atomics: a clip's
+ * coeff, params and report are the same bits alone and in any batch.  The sweep is serial in t.
+ *   keypoints, table_ready, landmarks [F,68,2], weights, weights_per_frame    as for vp_bfmfit_fit; the table lives in THIS call's workspace
+ *   clip_offsets      HOST int32 [clips+1]: clip c is frames clip_offsets[c] .. clip_offsets[c+1]-1; clip_offsets[0] = 0, F = clip_offsets[clips]
+ *   coeff_in          [F,257] float32: the template (texture, lighting)
+ *   params            [F,150] float64, in and out: the start values (alpha is taken from the clip's FIRST row, as vp_bfmfit_identity_step
+ *                     takes it) and the solution
+ *   lam_smooth        HOST double [3]
+ *   max_trials        0: only E and |g|_inf at the start values are reported (status 0 or 1)
+ *   coeff             [F,257] float32 (may be coeff_in): the template with the fitted blocks overwritten
+ *   report            [clips,4] float64 = { status, accepted steps, final E, final |g|_inf }
+ * Refused on the host before anything is enqueued: a null pointer, clips < 1, a keypoint outside the model, clip_offsets[0] != 0, offsets
+ * that do not increase (a clip of 0 frames), a negative or non-finite lam or lam_smooth, gtol < 0, max_trials outside 0 .. 100000, a short
+ * workspace.  The call does not wait.
+ * ---------------------------------------------------------------------------------------------- */
+size_t vp_bfmfit_clip_workspace_bytes(int total_frames, int clips);
+int vp_bfmfit_clip(const vp_bfm_model* m, const int* keypoints, int table_ready, const double* landmarks, const double* weights, int weights_per_frame,
+                   const int* clip_offsets, int clips, const float* coeff_in, double* params, double lam_id, double lam_ex, const double* lam_smooth,
+                   double gtol, int max_trials, float* coeff, double* report, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Photometric fit of texture (coefficients 144:224) and lighting (227:254) to a photo's pixels, the geometry fixed at what vp_bfmfit_fit
  * returned: the inverse of face_color = Illumination_layer(Texture_formation(tex_coeff), face_norm . rotation, gamma)
  * (utils/reconstruct_mesh.py:58-62, :129-168, as Reconstruction :172-194 calls them; render_face rasterises that colour,

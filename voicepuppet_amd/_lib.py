@@ -331,6 +331,9 @@ _SIGNATURES = {
     "vp_bfmfit_fit": (ctypes.c_int, [_P, _P, ctypes.c_int, _P, _P, ctypes.c_int, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double,
                                      ctypes.c_double, ctypes.c_int, ctypes.c_int, _P, _P, _P, ctypes.c_size_t, _P]),
     "vp_bfmfit_identity_step": (ctypes.c_int, [_P, _P, ctypes.c_int, _P, _P, ctypes.c_int, _P, _P, ctypes.c_int, ctypes.c_double, _P, ctypes.c_size_t, _P]),
+    "vp_bfmfit_clip_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
+    "vp_bfmfit_clip": (ctypes.c_int, [_P, _P, ctypes.c_int, _P, _P, ctypes.c_int, _P, ctypes.c_int, _P, _P, ctypes.c_double, ctypes.c_double, _P,
+                                      ctypes.c_double, ctypes.c_int, _P, _P, _P, ctypes.c_size_t, _P]),
     "vp_bfmfit_observe_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "vp_bfmfit_observe": (ctypes.c_int, [_P, _P, _P, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
     "vp_bfmfit_observe_opts_size": (ctypes.c_size_t, []),

@@ -22,6 +22,17 @@ status 1 = max_trials used up, 3 = non-finite input or no visible vertex.  lam_t
 `FaceFitter.fit_sequence` is a FIXED SCHEDULE of block-coordinate descent for a clip of one person (per-frame fits, then identity steps
 alternating with tracking fits), not a minimiser: it stops after `rounds` rounds whatever the cost does.
 
+`FaceFitter.fit_clip` is the minimiser (vp_bfmfit_clip; csrc/bfm_clip.hip): one Levenberg-Marquardt solve, by the same rule, over a whole
+clip's unknowns, alpha (80) and q_t = [beta_t | angles | t] (70) per frame t = 1 .. T:
+  E = sum_t ( sum_k w_tk |pi_k(alpha, q_t) - l_tk|^2 + lam_id |alpha|^2 + lam_ex |beta_t|^2 )
+    + sum_{t<T} ( s_ex |beta_t+1 - beta_t|^2 + s_ang |ang_t+1 - ang_t|^2 + s_t |t_t+1 - t_t|^2 ),      lam_smooth = (s_ex, s_ang, s_t)
+With lam_smooth = (0, 0, 0), the default, E is the sum of the per-frame costs for a shared alpha (T lam_id |alpha|^2 in all, as the identity
+step counts it); the coupling terms damp the frame-to-frame jitter a landmark detector leaves in the rows BFMNet's loss differences in
+time.  Useful values of lam_smooth are UNTUNED on real landmark files.  A fixed chain of `max_trials` rounds of two launches (the frames'
+150x150 systems at the trial point, one workgroup per frame; then one workgroup per clip: accept / reject on the SUM OF THE FRAMES'
+DIFFERENCES, a block Cholesky sweep over the block-arrowhead matrix, the next trial point).  report [clips,4] = (status, accepted steps,
+final E, final |g|_inf over all 80 + 70 T unknowns); status 1 = max_trials trial points used up.
+
 The alignment helpers (`crop_alignment`, `preprocess_landmarks`) are plain numpy float64 and do no device work.  No CPU fallback for the fit.
 """
 import ctypes
@@ -156,7 +167,8 @@ class FaceFitter:
     self._ws = None
     self._table_ready = False
     self.last_params = None                                 # float64 [frames,150] of the last call
-    self._ws_obs = self._ws_app = None
+    self._ws_obs = self._ws_app = self._ws_clip = None
+    self._clip_table_ready = False
     self.last_appearance = None                             # float64 [frames,107] of the last fit_appearance
     self.last_appearance_report = None                      # enroll(image=...): fit_appearance's report [1,4]
     self.last_appearance_lams = None                        # (lam_tex, lam_gamma) of the last fit_appearance
@@ -258,6 +270,59 @@ class FaceFitter:
         self.identity_step(lm, p, coeff, weights=weights, lam_id=lam_id)
       coeff, report = self.fit(lm, init=coeff, params=p, free="tracking", **kw)
       p = self.last_params
+    return coeff, report
+
+  def fit_clip(self, landmarks, clip_lengths=None, init=None, params=None, weights=None, lam_id=1.0, lam_ex=1.0, lam_smooth=(0, 0, 0), gtol=1e-6,
+               max_trials=64):
+    """The joint fit of whole clips (vp_bfmfit_clip; the module docstring states the energy): ONE identity per clip, expression and pose per
+    frame, `lam_smooth` = (s_ex, s_ang, s_t) weighting the squared frame-to-frame differences of expression, angles and translation.  The
+    weights default to 0 (no coupling); their useful values are UNTUNED on real landmark files.  landmarks [frames,68,2]; clip_lengths: the
+    frame counts of the clips, in order (default: one clip); init [frames,257] float32 template; params [frames,150] float64 start values
+    (a clip's alpha is its first row's).  Without `params` the start is what fit_sequence(rounds=0) gives each clip: a full fit of every
+    frame from `init`, alpha set to the clip's mean.  Returns (coeff [frames,257] float32, report [clips,4] float64 = status, accepted
+    steps, final E, final |g|_inf over all 80 + 70 T unknowns), device tensors; status 0 converged, 1 `max_trials` trial points used up,
+    2 stalled, 3 non-finite input.  A fixed chain of `max_trials` rounds; the call only enqueues.  The float64 solution is kept in
+    `self.last_params`."""
+    torch, dev = self._torch, self.model.device
+    if not isinstance(landmarks, np.ndarray) and not torch.is_tensor(landmarks):
+      landmarks = np.asarray(landmarks, np.float64)
+    F = int(landmarks.shape[0])
+    if F < 1:
+      raise ValueError("fit_clip: at least one frame")
+    lengths = [F] if clip_lengths is None else [int(n) for n in clip_lengths]
+    if not lengths or min(lengths) < 1 or sum(lengths) != F:
+      raise ValueError("fit_clip: clip_lengths must be positive and add up to the %d frames" % F)
+    smooth = np.asarray(lam_smooth, np.float64).reshape(-1)
+    if smooth.shape != (3,) or not np.all(np.isfinite(smooth)) or np.any(smooth < 0):
+      raise ValueError("fit_clip: lam_smooth must be three non-negative numbers (expression, angles, translation)")
+    smooth = np.ascontiguousarray(smooth)
+    offsets = np.ascontiguousarray(np.concatenate([[0], np.cumsum(lengths)]), np.int32)
+    lm = self._device(landmarks, torch.float64, (F, 68, 2), "landmarks")
+    if weights is not None and not isinstance(weights, np.ndarray) and not torch.is_tensor(weights):
+      weights = np.asarray(weights, np.float64)
+    w, per_frame = self._weights(weights, F)
+    tmpl = torch.zeros(F, 257, dtype=torch.float32, device=dev) if init is None else self._device(init, torch.float32, (F, 257), "init")
+    if params is not None:
+      p = self._device(params, torch.float64, (F, NP), "params").clone()
+    else:
+      self.fit(lm, weights=weights, init=tmpl, free="all", lam_id=lam_id, lam_ex=lam_ex)
+      p = self.last_params
+      for a, b in zip(offsets[:-1].tolist(), offsets[1:].tolist()):
+        p[a:b, :80] = p[a:b, :80].mean(dim=0, keepdim=True)
+    coeff = torch.empty(F, 257, dtype=torch.float32, device=dev)
+    report = torch.empty(len(lengths), 4, dtype=torch.float64, device=dev)
+    n = _lib.lib().vp_bfmfit_clip_workspace_bytes(F, len(lengths))
+    ws = grow(self._ws_clip, n, dev)
+    if ws is not self._ws_clip:
+      self._ws_clip = ws
+      self._clip_table_ready = False                        # the gathered keypoint table lives at the head of this workspace too
+    P = ctypes.c_void_p
+    _lib.check(_lib.lib().vp_bfmfit_clip(ctypes.byref(self.model.c), self._kp.ctypes.data_as(P), 1 if self._clip_table_ready else 0, ptr(lm), ptr(w),
+                                         per_frame, offsets.ctypes.data_as(P), len(lengths), ptr(tmpl), ptr(p), float(lam_id), float(lam_ex),
+                                         smooth.ctypes.data_as(P), float(gtol), int(max_trials), ptr(coeff), ptr(report), ptr(ws), ws.numel(),
+                                         stream()), "vp_bfmfit_clip")
+    self._clip_table_ready = True
+    self.last_params = p
     return coeff, report
 
   def _photo(self, photo, T):

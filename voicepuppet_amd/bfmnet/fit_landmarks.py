@@ -5,6 +5,7 @@
     python voicepuppet/bfmnet/fit_landmarks.py --photo landmarks.txt --size H W --out photo.npz
     python voicepuppet/bfmnet/fit_landmarks.py --photo landmarks.txt --image photo.jpg --out photo.npz
     python voicepuppet/bfmnet/fit_landmarks.py --clip landmarks.txt --size H W --out bfmcoeff.txt
+    python voicepuppet/bfmnet/fit_landmarks.py --clip landmarks.txt --size H W --out bfmcoeff.txt --joint [--smooth EX ANG T]
 
 --photo: the first line of the landmarks file is enrolled; photo.npz is what infer_bfmvid.py / infer_bfmnet.py take as --bfmcoeff
          (bfmcoeff [1,257], transform_params [5], center_x, center_y, ratio).  With --image (read with PIL as RGB; --size is then the
@@ -14,7 +15,10 @@
          both off by default).
 --clip:  every line is a frame of ONE person; the frames are aligned one by one as the reference's data preparation does
          (datasets/make_data_from_GRID.py:193-214), fitted with FaceFitter.fit_sequence, and written as one row of 257 comma-separated
-         values per frame: the bfmcoeff.txt that BFMCoeffLoader reads and train_bfmnet.py learns from.
+         values per frame: the bfmcoeff.txt that BFMCoeffLoader reads and train_bfmnet.py learns from.  With --joint the clip is fitted by
+         FaceFitter.fit_clip instead: one Levenberg-Marquardt solve over the clip's identity and every frame's expression and pose, and
+         --smooth EX ANG T weights the squared frame-to-frame differences of expression, angles and translation (default 0 0 0; useful
+         values are untuned on real landmark files).  The line printed then holds the clip's status, accepted steps, E and |g|_inf.
 A landmarks file has one frame per line: 136 comma-separated values x0,y0,...,x67,y67 in pixels of the H x W image (any landmark model
 with the 68-point layout; the reference's README names dlib).  Needs BFM/BFM_model_front.mat and BFM/similarity_Lm3D_all.mat, as the
 reference does.  --clip never fits texture and lighting (zeros: mean albedo, ambient light): BFMNet learns expression only.  One line
@@ -76,6 +80,12 @@ def summary_line(name, report, err):
   return '%s: %d frames, status %s, reprojection mean %.3f px, worst %.3f px' % (name, status.shape[0], counts, float(err.mean()), float(err.max()))
 
 
+def joint_summary_line(name, report, err):
+  rep = report.cpu().numpy()[0]
+  return '%s: %d frames, joint status %d, %d accepted steps, E %.6f, |g| %.3e, reprojection mean %.3f px, worst %.3f px' % (
+      name, err.shape[0], int(rep[0]), int(rep[1]), rep[2], rep[3], float(err.mean()), float(err.max()))
+
+
 def appearance_summary(fitter):
   """', appearance status S, colour RMS R grey levels': R^2 = the report's E without its two regularisation terms (the weighted mean of
   the squared colour residuals at the fitted point; the lambdas are read back from E's definition: E - lam |p|^2)."""
@@ -101,6 +111,10 @@ def parse_options(argv=None):
   cmd_parser.add_option('--out', type="string", dest="out", default=None, help='output file')
   cmd_parser.add_option('--rounds', type="int", dest="rounds", default=3, help='--clip: rounds of (identity steps, tracking fit)')
   cmd_parser.add_option('--id_steps', type="int", dest="id_steps", default=3, help='--clip: identity steps per round')
+  cmd_parser.add_option('--joint', action="store_true", dest="joint", default=False, help='--clip: one joint solve of the clip (FaceFitter.fit_clip)')
+  cmd_parser.add_option('--smooth', type="float", nargs=3, dest="smooth", default=None,
+                        help='--joint: weights of the squared frame-to-frame differences of expression, angles, translation (default 0 0 0)')
+  cmd_parser.add_option('--max_trials', type="int", dest="max_trials", default=64, help='--joint: trial points of the joint solve')
   return cmd_parser.parse_args(argv)
 
 
@@ -138,6 +152,14 @@ def main(argv=None):
     return
   lms = read_landmarks(opts.clip)
   aligned = np.stack([preprocess_landmarks(crop_alignment(lm, img_h, img_w)[0], lm3D)[0] for lm in lms])
+  if opts.smooth is not None and not opts.joint:
+    logger.error('--smooth needs --joint')
+    exit(0)
+  if opts.joint:
+    coeff, report = fitter.fit_clip(aligned, lam_smooth=opts.smooth or (0.0, 0.0, 0.0), max_trials=opts.max_trials)
+    np.savetxt(opts.out, coeff.cpu().numpy(), delimiter=',', fmt='%.8g')
+    print(joint_summary_line(opts.clip, report, reprojection_error(fitter, coeff, aligned)))
+    return
   coeff, report = fitter.fit_sequence(aligned, rounds=opts.rounds, id_steps=opts.id_steps)
   np.savetxt(opts.out, coeff.cpu().numpy(), delimiter=',', fmt='%.8g')
   print(summary_line(opts.clip, report, reprojection_error(fitter, coeff, aligned)))

@@ -152,6 +152,11 @@ def parse_options(argv=None):
   p.add_option('--list', type='string', dest='list', default=None, help='dataset list to append "out_dir|count" to')
   p.add_option('--rounds', type='int', dest='rounds', default=3, help='fit_sequence: rounds of (identity steps, tracking fit)')
   p.add_option('--id_steps', type='int', dest='id_steps', default=3, help='fit_sequence: identity steps per round')
+  p.add_option('--joint', action='store_true', dest='joint', default=False,
+               help='fit the clip with FaceFitter.fit_clip (one joint solve) instead of fit_sequence')
+  p.add_option('--smooth', type='float', nargs=3, dest='smooth', default=None,
+               help='--joint: EX ANG T, weights of the squared frame-to-frame differences of expression, angles and translation '
+                    '(default 0 0 0; useful values are untuned on real landmark files)')
   return p.parse_args(argv)
 
 
@@ -206,6 +211,9 @@ def main(argv=None):
     if rows.shape[0] < frames_n or rows.shape[1] != 257:
       raise SystemExit('%s: %s, expected at least %d rows of 257' % (opts.bfmcoeff, rows.shape, frames_n))
     coeff, report = torch.from_numpy(rows[:frames_n]).cuda(), torch.zeros(frames_n, 4, dtype=torch.float64, device='cuda')
+  elif opts.joint:
+    coeff, clip_report = fitter.fit_clip(aligned, lam_smooth=opts.smooth or (0.0, 0.0, 0.0))
+    report = clip_report.repeat(frames_n, 1)                # the clip's status in every frame's row of the summary line
   else:
     coeff, report = fitter.fit_sequence(aligned, rounds=opts.rounds, id_steps=opts.id_steps)
   extra = ''
