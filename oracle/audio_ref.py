@@ -49,10 +49,12 @@ def linear_to_mel_weight_matrix(num_mel_bins=80, num_spectrogram_bins=257, sampl
   return np.pad(w, ((1, 0), (0, 0)))                                   # ... and re-inserted as a zero row
 
 
-def extract_mfcc(pcm, sample_rate=16000, num_mel_bins=80, win_length=512, hop_step=128, fft_length=512):
+def extract_mfcc(pcm, sample_rate=16000, num_mel_bins=80, win_length=512, hop_step=128, fft_length=512,
+                 lower_edge_hertz=80.0, upper_edge_hertz=7600.0):
   """[B, L] -> [B, frames, 80] = log(|STFT| . mel + 1e-6).  The mel matrix is float32 in TF."""
   mag = stft_mag(pcm, win_length, hop_step, fft_length)
-  mel = linear_to_mel_weight_matrix(num_mel_bins, fft_length // 2 + 1, sample_rate).astype(np.float32).astype(np.float64)
+  mel = linear_to_mel_weight_matrix(num_mel_bins, fft_length // 2 + 1, sample_rate, lower_edge_hertz,
+                                    upper_edge_hertz).astype(np.float32).astype(np.float64)
   return np.log(mag @ mel + 1e-6)
 
 

@@ -1,5 +1,6 @@
 """-m gpu: log-mel and BFMNet inference (vp_logmel_*, vp_bfmnet_*) against oracle/audio_ref.py.
-f32 path; tolerance 1e-4 relative L2 on the log-mel features (f32 DFT of 512 terms), 1e-3 on the coefficients."""
+f32 path; tolerance 1e-4 relative L2 on the log-mel features (f32 DFT of 512 terms), 1e-3 on the coefficients.
+The per-element check of vp_logmel_forward (both paths, derived bounds, non-default descriptors) is tests/test_gpu_logmel_ops.py."""
 import numpy as np
 import pytest
 import torch
