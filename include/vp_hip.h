@@ -34,6 +34,8 @@
  *   vp_triptych_*      replaces  datasets/make_data_from_GRID.py:430-469 (step 5: binary_fill_holes, cv2.resize, erode, GaussianBlur, the paste and the
  *                             three panels of a training triptych) and :690-695 (step 6's layout with an alpha matte)
  *   vp_frame_metrics_* replaces  nothing: the reference has no image-quality measure (L1, PSNR and SSIM per frame pair, on the device)
+ *   vp_keymatte_*      replaces  the matte that step 6 of datasets/make_data_from_GRID.py (:690-695) takes from its segmentation and matting
+ *                             models, for footage in front of a PLAIN backdrop only: a colour key with an edge-aware clean-up, no network
  *
  * Conventions: every function returns 0 on success and a negative vp_status otherwise (never throws);
  * all tensor pointers are DEVICE pointers owned by the caller (NHWC, row-major); nothing is allocated
@@ -1421,6 +1423,100 @@ int vp_triptych_blur_taps(int q[21]);
  * corner; "filled": uint8 [max_frames, face_size, face_size], stage a's 0 / 1 */
 int vp_triptych_tensor(vp_triptych_t* h, const char* name, void** ptr, int64_t shape[4]);
 void vp_triptych_destroy(vp_triptych_t* h);
+
+/* ------------------------------------------------------------------------------------------------
+ * Alpha mattes for clips in front of a plain backdrop, on the device: a colour model of the backdrop fitted to the frames' border, a soft
+ * key on the distance from it, one guided-filter pass (He, Sun & Tang 2010) with the frame's luma as the guide.  In place of the matte
+ * that step 6 of datasets/make_data_from_GRID.py pastes from its segmentation and matting networks (:690-695), for a head and shoulders
+ * in front of a studio backdrop only.  It is a key, not a matting network: on a cluttered background it is the wrong tool, and the
+ * model's status, kept and residual_rms say so.  No spill suppression, no temporal smoothing.  csrc/key_matte.hip.
+ *
+ * Frames are uint8 RGB, frame f's value (y, x, c) at p + f * frame_stride + y * row_pitch + 3 x + c, 16 <= height, width <= 1024.
+ * Everything below is integers or float64, every product, quotient and sum rounded on its own (no fused multiply-add) and in the order
+ * written: parentheses first, otherwise left to right.  (double) of an integer is the nearest double.
+ *
+ * FIT.  Samples: the pixels with y < band, or with y < side_rows and (x < band or x >= W - band): the top and the upper sides (the torso
+ *   leaves through the bottom).  band = 0 means max(2, H / 16), side_rows = 0 means H / 2 (integer divisions); refused unless
+ *   1 <= band, 2 * band <= W and band <= side_rows <= H.  Per sample v = (x, y, R, G, B, 1) in integers; the moments are the 21 entries
+ *   v[i] * v[j], i <= j, summed over the samples of all n frames in int64 (exact in any order), stored row by row of the upper triangle:
+ *   xx xy xR xG xB x | yy yR yG yB y | RR RG RB R | GG GB G | BB B | 1  (indices 0..5, 6..10, 11..14, 15..17, 18..19, 20).
+ *   Pass 1: the moments of all samples, then SOLVE.  Pass 2: the moments of the samples whose d2 (APPLY, with pass 1's model) is <= trim,
+ *   then SOLVE; kept = (double)N2 / (double)N1 (0 when N1 = 0) is written into that model, which is the fit's result.  One call, at
+ *   most max_frames frames; nothing accumulates across calls.
+ * SOLVE (vp_keymatte_solve_host, and the same source in one device lane).  With S.. the moments and N = S11 (index 20):
+ *   N < 1: every number of the model is 0 except inv00 = inv11 = inv22 = 1 / (sigma_min * sigma_min), kept = 1 and status = 1.  Otherwise
+ *   Nd = (double)N; the means mx = (double)Sx / Nd, my, mR, mG, mB alike; the centred second moments
+ *   Cab = (double)(N * Sab - Sa * Sb) / (Nd * Nd) for ab in xx, xy, yy, xc, yc and the six cd (c, d channels, c <= d): the integer is
+ *   exact (128 bits) and converted through its magnitude u = hi * 2^64 + lo as (double)hi * 2^64 + (double)lo, then given its sign, so a
+ *   border of one colour has slopes and residuals of exactly 0.
+ *   det = Cxx * Cyy - Cxy * Cxy.  degenerate = N < 16 or not (det > 1e-9 * (Cxx * Cyy)).
+ *   Per channel c, not degenerate: px = (Cxc * Cyy - Cyc * Cxy) / det, py = (Cyc * Cxx - Cxc * Cxy) / det; degenerate: px = py = 0.
+ *   p0 = (mc - px * mx) - py * my.  The plane is b_c(x, y) = (p0 + px * (double)x) + py * (double)y.
+ *   Residual covariance, c <= d: Rcd = (Ccd - px_c * Cxd) - py_c * Cyd; a negative Rcc is replaced by 0.
+ *   residual_rms = sqrt(((R00 + R11) + R22) / 3.0).
+ *   Sigma = R + (sigma_min * sigma_min) I: a = S00, b = S01, c = S02, d = S11, e = S12, f = S22.  Adjugate: A00 = d * f - e * e,
+ *   A01 = c * e - b * f, A02 = b * e - c * d, A11 = a * f - c * c, A12 = b * c - a * e, A22 = a * d - b * b;
+ *   D = (a * A00 + b * A01) + c * A02; inv_ij = A_ij / D.  When not (D > 0): inv = I / (sigma_min * sigma_min) and status = 1
+ *   (the planes stay).  Otherwise status = 1 when degenerate, else 0.  kept = 1.
+ *   The model record, VP_KEYMATTE_MODEL_DOUBLES float64: [0..8] p0, px, py of R, of G, of B; [9..14] inv00 inv01 inv02 inv11 inv12
+ *   inv22; [15] N; [16] kept; [17] residual_rms; [18] status.
+ * APPLY, per pixel (x, y) with channels c0 c1 c2:
+ *   r_c = (double)c - b_c(x, y);
+ *   q0 = (inv00 * r0 + inv01 * r1) + inv02 * r2, q1 = (inv01 * r0 + inv11 * r1) + inv12 * r2, q2 = (inv02 * r0 + inv12 * r1) + inv22 * r2;
+ *   d2 = (r0 * q0 + r1 * q1) + r2 * q2;
+ *   t = min(max((d2 - lo * lo) / (hi * hi - lo * lo), 0), 1) (a NaN gives 0); a = (t * t) * (3.0 - 2.0 * t);
+ *   raw key p = (uint8)floor(255.0 * a + 0.5).  No square root.
+ *   radius = 0: the matte is p.  Otherwise the guide is I = (77 R + 150 G + 29 B + 128) >> 8, and with the (2 radius + 1)^2 window centred
+ *   on the pixel and clipped to the image, n_w its pixel count, the integer sums sI, sp, sII = sum I^2, sIp = sum I p over it:
+ *   a_k = (double)(sIp * n_w - sI * sp) / ((double)(sII * n_w - sI * sI) + eps * (double)(n_w * n_w));
+ *   b_k = ((double)sp - a_k * (double)sI) / (double)n_w;
+ *   sa, sb: the sums of a_k, b_k over the same clipped window: first per row the sum over its columns in increasing x, then the sum of
+ *   those row sums in increasing y, each sum starting from +0.0;
+ *   q = (sa / (double)n_w) * (double)I + sb / (double)n_w;   matte = (uint8)floor(min(max(q, 0), 255) + 0.5).
+ * Defaults of the Python layer: trim 16, sigma_min 2 grey levels, lo 4 and hi 10 (standard deviations of the backdrop), radius 4,
+ * eps 25 (grey levels squared).  They come from synthetic scenes and are UNTUNED on real footage.
+ * A frame's matte depends on the model and that frame alone: the same bytes in any batch.  No floating-point atomics anywhere.
+ * ---------------------------------------------------------------------------------------------- */
+#define VP_KEYMATTE_MAX_FRAMES 4096
+#define VP_KEYMATTE_MAX_SIZE 1024
+#define VP_KEYMATTE_MAX_RADIUS 16
+#define VP_KEYMATTE_MODEL_DOUBLES 19
+typedef struct vp_keymatte_desc {
+  uint32_t struct_bytes;  /* sizeof(vp_keymatte_desc) of the caller's build: must equal vp_keymatte_desc_size() */
+  int32_t max_frames;     /* frames per call: 1 .. VP_KEYMATTE_MAX_FRAMES */
+  int32_t max_height;     /* 16 .. VP_KEYMATTE_MAX_SIZE */
+  int32_t max_width;      /* 16 .. VP_KEYMATTE_MAX_SIZE */
+  int32_t max_radius;     /* 0 .. VP_KEYMATTE_MAX_RADIUS; 0 leaves the guided filter's planes out of the workspace */
+} vp_keymatte_desc;
+size_t vp_keymatte_desc_size(void);
+typedef struct vp_keymatte vp_keymatte_t;
+/* 0 on a refused descriptor (vp_last_error names the field).  With max_radius > 0 the workspace holds a_k and b_k as float64 planes:
+ * 16 bytes per pixel of max_frames x max_height x max_width. */
+size_t vp_keymatte_workspace_bytes(const vp_keymatte_desc* d);
+/* Host only: touches no device memory.  workspace: DEVICE memory the caller keeps alive as long as the handle.  The model is undefined
+ * until vp_keymatte_fit or vp_keymatte_set_model has run. */
+int vp_keymatte_create(const vp_keymatte_desc* d, void* workspace, size_t workspace_bytes, vp_keymatte_t** out);
+void vp_keymatte_destroy(vp_keymatte_t* h);
+/* FIT on n = 1 .. max_frames frames (DEVICE).  Refused before anything is enqueued, vp_last_error naming the field: n, height, width,
+ * row_pitch < 3 * width, frame_stride < (height - 1) * row_pitch + 3 * width, band, side_rows, trim not finite or < 0, sigma_min not
+ * finite or <= 0.  One fill of the moments and four launches on `stream` (moments, solve, trimmed moments, solve); nothing is read back;
+ * never waits, never allocates. */
+int vp_keymatte_fit(vp_keymatte_t* h, const unsigned char* frames, size_t row_pitch, size_t frame_stride, int n, int height, int width,
+                    int band, int side_rows, double trim, double sigma_min, void* stream);
+/* APPLY with the handle's model.  raw: NULL or DEVICE uint8 [n, height, width], the raw key p; matte: DEVICE uint8 [n, height, width].
+ * Refused before anything is enqueued, vp_last_error naming the field: n, height, width, row_pitch, frame_stride as above; lo, hi not
+ * finite or not 0 <= lo < hi; radius outside 0 .. max_radius; eps not finite or <= 0.  One launch at radius 0, else two (the
+ * coefficients a_k, b_k of every pixel into the workspace; their window means and the matte); never waits, never allocates. */
+int vp_keymatte_apply(vp_keymatte_t* h, const unsigned char* frames, size_t row_pitch, size_t frame_stride, int n, int height, int width,
+                      double lo, double hi, int radius, double eps, unsigned char* raw, unsigned char* matte, void* stream);
+/* model: DEVICE float64 [VP_KEYMATTE_MODEL_DOUBLES] on an 8-byte boundary; one device-to-device copy enqueued on `stream`. */
+int vp_keymatte_get_model(vp_keymatte_t* h, double* model, void* stream);
+int vp_keymatte_set_model(vp_keymatte_t* h, const double* model, void* stream);
+/* "moments": int64 [2, 21], pass 1 and pass 2 of the last fit; "model": float64 [VP_KEYMATTE_MODEL_DOUBLES] */
+int vp_keymatte_tensor(vp_keymatte_t* h, const char* name, void** ptr, int64_t shape[4]);
+/* Host only: SOLVE above, the source the device lane runs.  model: VP_KEYMATTE_MODEL_DOUBLES doubles.  VP_ERR_ARG on a null pointer or
+ * a sigma_min that is not finite or <= 0. */
+int vp_keymatte_solve_host(const int64_t moments[21], double sigma_min, double* model);
 
 /* Host helper: CRC-32C (Castagnoli, the checksum of TensorFlow checkpoint bundles) of `n` bytes, continuing from `crc` (0 to start). */
 unsigned vp_crc32c(const void* data, size_t n, unsigned crc);

@@ -106,6 +106,15 @@ class AviMuxDesc(ctypes.Structure):
 AVIMUX_MAX_FRAMES, AVIMUX_MAX_SLOTS = 4096, 128   # include/vp_hip.h VP_AVIMUX_MAX_FRAMES, VP_AVIMUX_MAX_SLOTS
 
 
+class KeyMatteDesc(ctypes.Structure):
+  _fields_ = [("struct_bytes", ctypes.c_uint32), ("max_frames", ctypes.c_int32), ("max_height", ctypes.c_int32), ("max_width", ctypes.c_int32),
+              ("max_radius", ctypes.c_int32)]
+
+
+# include/vp_hip.h VP_KEYMATTE_MAX_FRAMES, VP_KEYMATTE_MAX_SIZE, VP_KEYMATTE_MAX_RADIUS, VP_KEYMATTE_MODEL_DOUBLES
+KEYMATTE_MAX_FRAMES, KEYMATTE_MAX_SIZE, KEYMATTE_MAX_RADIUS, KEYMATTE_MODEL_DOUBLES = 4096, 1024, 16, 19
+
+
 class TriptychDesc(ctypes.Structure):
   _fields_ = [("struct_bytes", ctypes.c_uint32), ("max_frames", ctypes.c_int32), ("size", ctypes.c_int32), ("face_size", ctypes.c_int32),
               ("max_side", ctypes.c_int32)]
@@ -297,6 +306,18 @@ _SIGNATURES = {
     "vp_triptych_blur_taps": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int)]),
     "vp_triptych_tensor": (ctypes.c_int, [_P, ctypes.c_char_p, ctypes.POINTER(_P), ctypes.POINTER(ctypes.c_int64)]),
     "vp_triptych_destroy": (None, [_P]),
+    "vp_keymatte_desc_size": (ctypes.c_size_t, []),
+    "vp_keymatte_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(KeyMatteDesc)]),
+    "vp_keymatte_create": (ctypes.c_int, [ctypes.POINTER(KeyMatteDesc), _P, ctypes.c_size_t, ctypes.POINTER(_P)]),
+    "vp_keymatte_destroy": (None, [_P]),
+    "vp_keymatte_fit": (ctypes.c_int, [_P, _P, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                       ctypes.c_double, ctypes.c_double, _P]),
+    "vp_keymatte_apply": (ctypes.c_int, [_P, _P, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double,
+                                         ctypes.c_double, ctypes.c_int, ctypes.c_double, _P, _P, _P]),
+    "vp_keymatte_get_model": (ctypes.c_int, [_P, _P, _P]),
+    "vp_keymatte_set_model": (ctypes.c_int, [_P, _P, _P]),
+    "vp_keymatte_tensor": (ctypes.c_int, [_P, ctypes.c_char_p, ctypes.POINTER(_P), ctypes.POINTER(ctypes.c_int64)]),
+    "vp_keymatte_solve_host": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int64), ctypes.c_double, ctypes.POINTER(ctypes.c_double)]),
     "vp_bfm_reconstruct_rows": (ctypes.c_int, [ctypes.POINTER(BfmModel), _P, _P, ctypes.c_int, _P, ctypes.c_int, _P, _P, _P, _P, ctypes.c_size_t, _P]),
     "vp_bfmstream_group_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(BfmStreamGroupDesc)]),
     "vp_bfmstream_group_plan_info": (ctypes.c_int, [ctypes.POINTER(BfmStreamGroupDesc), ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
@@ -417,6 +438,7 @@ DESC_SIZE_QUERIES = {
     "vp_frame_metrics_desc_size": FrameMetricsDesc,
     "vp_avimux_desc_size": AviMuxDesc,
     "vp_triptych_desc_size": TriptychDesc,
+    "vp_keymatte_desc_size": KeyMatteDesc,
 }
 
 _lib = None

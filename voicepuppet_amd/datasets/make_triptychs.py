@@ -16,6 +16,14 @@ deep_video_portraits_v2, :690-695), which need TensorFlow 1, MXNet, OpenCV and F
                    frames' own size, which must then be square
 --crop X0 Y0 SIDE  the square of the frame to keep, before the resize (the landmarks follow)
 --alpha_dir DIR    <i>.jpg or <i>.png mattes, S x S after the same crop and resize: step 6's layout (render on black | matte) instead of step 5's
+                   (a matte that already has the panel's size, as --write_alpha writes it, is taken as it is)
+--key_matte        step 6's layout with the matte computed here (voicepuppet_amd.matte.KeyMatte): a colour key against the backdrop, fitted
+                   to the border of the clip's first frames, and one guided-filter pass.  For a head and shoulders in front of a PLAIN
+                   backdrop only; it is no matting network.  Not together with --alpha_dir
+--key_frames N     the backdrop model is fitted once, on the first N panel-size frames (default: one device batch)
+--key_thresholds LO HI, --key_radius R, --key_eps E, --key_band B   KeyMatte's ramp (4 10), guided-filter window (4) and regulariser
+                   (25), and the width of the border band (panel size // 16); the defaults are untuned on real footage
+--write_alpha DIR  with --key_matte: gets the mattes as <i>.png, panel size, for inspection and for reuse as --alpha_dir
 --bfmcoeff FILE    rows of 257 coefficients to use instead of fitting them (fit_landmarks.py --clip writes such a file)
 --appearance first|none   first (default): texture and lighting are fitted to frame 0's pixels and shared by the clip; none: zeros
 --appearance_visibility, --appearance_prefilter   that fit without self-occluded vertices / on area means of frame 0 (both off by default)
@@ -25,7 +33,11 @@ deep_video_portraits_v2, :690-695), which need TensorFlow 1, MXNet, OpenCV and F
 The paste geometry is infer_bfmvid.paste_geometry for every frame, i.e. step 6's and inference's int(), not step 5's int(round()).  A frame
 that cannot be built (TriptychBuilder's status) repeats the frame before it, as step 6 does; a clip whose first frame cannot be built is
 refused.  Needs BFM/BFM_model_front.mat and BFM/similarity_Lm3D_all.mat, like fit_landmarks.py.  One line is printed: frames, statuses,
-repeated frames, and the reprojection error in pixels of the 224 image as fit_landmarks.py prints it."""
+repeated frames, and the reprojection error in pixels of the 224 image as fit_landmarks.py prints it; with --key_matte also the share of
+border samples the backdrop model kept and its residual, with a warning when the border was not a plain backdrop.
+
+A one-frame run with --key_matte (a folder with 0.jpg and a one-line landmark file) is how an enrolment photo for infer_bfmvid.py and
+PuppetStreamGroup.attach is made: out_dir/0.jpg is the [photo | render on black | matte] triptych they read."""
 import logging
 import math
 import os
@@ -125,16 +137,18 @@ def read_alpha(reader, alpha_dir, first, n):
       raise ValueError('%s: no %d.png or %d.jpg' % (alpha_dir, i, i))
     from PIL import Image
     a = np.array(Image.open(path).convert('L'), np.uint8)
-    if a.shape != (reader.h, reader.w):
+    if a.shape != (reader.h, reader.w) and not (a.shape == (reader.size, reader.size) and (not planes or planes[0].shape == a.shape)):
       raise ValueError('%s is %d x %d, the frames %d x %d' % (path, a.shape[1], a.shape[0], reader.w, reader.h))
     planes.append(a)
   a = torch.from_numpy(np.stack(planes)).cuda()
+  if planes[0].shape != (reader.h, reader.w):                     # panel-size mattes (--write_alpha): no crop, no resize
+    return a
   return reader.fit_to_panel(a[..., None].expand(-1, -1, -1, 3))[..., 0].contiguous()
 
 
 def parse_options(argv=None):
   p = OptionParser(usage='usage: %prog --clip_dir DIR --landmarks FILE --out_dir DIR [--size S] [--crop X0 Y0 SIDE] [--alpha_dir DIR] '
-                         '[--bfmcoeff FILE] [--appearance first|none] [--frame_batch N] [--list FILE]')
+                         '[--key_matte [--write_alpha DIR]] [--bfmcoeff FILE] [--appearance first|none] [--frame_batch N] [--list FILE]')
   p.add_option('--clip_dir', type='string', dest='clip_dir', default=None, help='folder of 0.jpg, 1.jpg, ...')
   p.add_option('--landmarks', type='string', dest='landmarks', default=None, help='68 landmarks per frame, 136 comma-separated values per line')
   p.add_option('--out_dir', type='string', dest='out_dir', default=None, help='the dataset folder to write')
@@ -157,7 +171,25 @@ def parse_options(argv=None):
   p.add_option('--smooth', type='float', nargs=3, dest='smooth', default=None,
                help='--joint: EX ANG T, weights of the squared frame-to-frame differences of expression, angles and translation '
                     '(default 0 0 0; useful values are untuned on real landmark files)')
-  return p.parse_args(argv)
+  p.add_option('--key_matte', action='store_true', dest='key_matte', default=False,
+               help='step 6\'s layout with the matte keyed against a plain backdrop on the device (KeyMatte); not with --alpha_dir')
+  p.add_option('--key_frames', type='int', dest='key_frames', default=None,
+               help='--key_matte: fit the backdrop model on the first N frames (default: one device batch)')
+  p.add_option('--key_thresholds', type='float', nargs=2, dest='key_thresholds', default=(4.0, 10.0),
+               help='--key_matte: LO HI, the key\'s ramp in standard deviations of the backdrop (untuned on real footage)')
+  p.add_option('--key_radius', type='int', dest='key_radius', default=4, help='--key_matte: guided-filter radius, 0 .. 16 (0: the raw key)')
+  p.add_option('--key_eps', type='float', dest='key_eps', default=25.0, help='--key_matte: guided-filter regulariser, grey levels squared')
+  p.add_option('--key_band', type='int', dest='key_band', default=None, help='--key_matte: width of the border band (default: size // 16)')
+  p.add_option('--write_alpha', type='string', dest='write_alpha', default=None, help='--key_matte: folder that gets the mattes as <i>.png')
+  opts, args = p.parse_args(argv)
+  if opts.key_matte and opts.alpha_dir:
+    p.error('--key_matte computes the matte that --alpha_dir reads: give one of the two')
+  if opts.write_alpha and not opts.key_matte:
+    p.error('--write_alpha writes the mattes of --key_matte')
+  lo, hi = opts.key_thresholds
+  if not (0.0 <= lo < hi < float('inf')) or not (0 <= opts.key_radius <= 16) or not (0.0 < opts.key_eps < float('inf')):
+    p.error('--key_thresholds LO HI with 0 <= LO < HI, --key_radius 0 .. 16, --key_eps above 0')
+  return opts, args
 
 
 def main(argv=None):
@@ -229,12 +261,30 @@ def main(argv=None):
   renderer = ClipRenderer(fitter.model)
   builder = TriptychBuilder(S, batch)
   status, repeated = [], []
+  keyer, key_report = None, None
+  if opts.key_matte:
+    from voicepuppet_amd.matte import STATUS_TEXT, KeyMatte
+    key_n = min(opts.key_frames or batch, frames_n)
+    if key_n < 1:
+      raise SystemExit('--key_frames must be at least 1')
+    try:
+      keyer = KeyMatte(max(batch, key_n), S, S, max_radius=opts.key_radius)
+      keyer.fit(torch.cat([reader.read(first, min(batch, key_n - first)) for first in range(0, key_n, batch)]), band=opts.key_band)
+    except (ValueError, RuntimeError) as e:
+      raise SystemExit('--key_matte: %s' % e)
+    key_report = keyer.report()
+    if opts.write_alpha:
+      os.makedirs(opts.write_alpha, exist_ok=True)
   try:
     for first in range(0, frames_n, batch):
       n = min(batch, frames_n - first)
       frames = reader.read(first, n)
       render, face_mask = renderer.render_view(coeff[first:first + n], view=0)
       alpha = read_alpha(reader, opts.alpha_dir, first, n) if opts.alpha_dir else None
+      if keyer is not None:
+        alpha = keyer.matte(frames, lo=opts.key_thresholds[0], hi=opts.key_thresholds[1], radius=opts.key_radius, eps=opts.key_eps)
+        if opts.write_alpha:
+          keyer.write_png(alpha, opts.write_alpha, first)
       trip, st = builder.build(frames, render, face_mask, geometry[first:first + n], alpha=alpha)
       repeated += builder.write(trip, st, opts.out_dir, first)
       status.append(st.cpu().numpy())
@@ -252,9 +302,18 @@ def main(argv=None):
   counts = ' '.join('%d:%d' % (s, int((status == s).sum())) for s in sorted(set(status.tolist())))
   for s in sorted(set(status.tolist()) - {0}):
     logger.warning('triptych status %d: %s', s, STATUS.get(s, '?'))
+  if key_report is not None:
+    extra += '; key matte: kept %.2f, residual %.1f levels' % (key_report['kept'], key_report['residual_rms'])
+    if key_report['status'] != 0:
+      logger.warning('key matte status %d: %s', key_report['status'], STATUS_TEXT.get(key_report['status'], '?'))
+    if key_report['kept'] < 0.5:
+      logger.warning('key matte: the robust pass kept %.2f of the border samples: the border is not a plain backdrop', key_report['kept'])
   fit = summary_line(opts.clip_dir, report, reprojection_error(fitter, coeff, aligned))
   print('%s; triptych status %s, %d repeated, %d read with PIL%s' % (fit, counts, len(repeated), reader.fallbacks, extra))
-  return {'frames': frames_n, 'status': status, 'repeated': repeated, 'geometry': geometry}
+  res = {'frames': frames_n, 'status': status, 'repeated': repeated, 'geometry': geometry}
+  if key_report is not None:
+    res['key_matte'] = key_report
+  return res
 
 
 if (__name__ == '__main__'):
