@@ -36,6 +36,8 @@
  *   vp_frame_metrics_* replaces  nothing: the reference has no image-quality measure (L1, PSNR and SSIM per frame pair, on the device)
  *   vp_keymatte_*      replaces  the matte that step 6 of datasets/make_data_from_GRID.py (:690-695) takes from its segmentation and matting
  *                             models, for footage in front of a PLAIN backdrop only: a colour key with an edge-aware clean-up, no network
+ *   vp_matteclean_*    replaces  nothing: the reference pastes its matting network's output as it is (components that are not the subject,
+ *                             holes in it); vp_key_foreground likewise: the reference trains on frame x matte, backdrop fringe included
  *
  * Conventions: every function returns 0 on success and a negative vp_status otherwise (never throws);
  * all tensor pointers are DEVICE pointers owned by the caller (NHWC, row-major); nothing is allocated
@@ -1517,6 +1519,80 @@ int vp_keymatte_tensor(vp_keymatte_t* h, const char* name, void** ptr, int64_t s
 /* Host only: SOLVE above, the source the device lane runs.  model: VP_KEYMATTE_MODEL_DOUBLES doubles.  VP_ERR_ARG on a null pointer or
  * a sigma_min that is not finite or <= 0. */
 int vp_keymatte_solve_host(const int64_t moments[21], double sigma_min, double* model);
+
+/* FOREGROUND: the subject's own colours on the matte's soft edge.  A frame pixel is I = a F + (1 - a) B; the training input frame x matte
+ * and an enrolment photo x matte therefore carry a fringe of backdrop colour, which shows as a halo over any other background.  The
+ * handle's model knows B (the planes b_c), so F is recovered per pixel and channel, float64 in the order written, no fused multiply-add:
+ *   m = 0: out = 0.  m = 255: e_c = (double)I_c.  Otherwise e_c = b_c(x, y) + ((double)I_c - b_c(x, y)) * (255.0 / (double)m), then
+ *   e_c = min(max(e_c, 0), 255).
+ *   Despill: v_c = b_c(W / 2, H / 2) (integer divisions); the key channel k is the largest v_c, the lowest index on a tie; i < j the other
+ *   two; lead = v_k - max(v_i, v_j).  When lead >= 16 and despill > 0: e_k = e_k - despill * max(0, e_k - (e_i + e_j) / 2.0).  (A neutral
+ *   backdrop has no spill to remove.)
+ *   out_c = (uint8)floor(e_c + 0.5).
+ * It is exact where the matte is: with KeyMatte's own matte it roughly halves the edge's colour error, no more.
+ * frames as in vp_keymatte_apply; matte and out contiguous: DEVICE uint8 [n, height, width] and [n, height, width, 3].  Refused before
+ * anything is enqueued, vp_last_error naming the field: n, height, width, row_pitch, frame_stride, matte, out, despill not in 0 .. 1.
+ * One launch, no workspace; never waits, never allocates.  The call returns no word on which despill case held: the model is on the
+ * device and nothing is read back.  The answer is a host read of the model's planes at the centre (KeyMatte.spill in the Python layer),
+ * by the rule above.  (Not named vp_keymatte_*: that family's list is closed.) */
+int vp_key_foreground(vp_keymatte_t* h, const unsigned char* frames, size_t row_pitch, size_t frame_stride, int n, int height, int width,
+                      const unsigned char* matte, double despill, unsigned char* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Clean-up of an alpha matte, on the device: the stage every keyer puts behind its key.  A key marks everything that is not backdrop as
+ * subject (noise speckle, a prop, the frame's edge where the backdrop ends) and a patch of backdrop colour on the subject as a hole.
+ * Works on any uint8 matte (vp_keymatte_apply's, or one from a file).  It is component bookkeeping, not a matting solve: it moves no
+ * edge and knows nothing of colour.  csrc/matte_clean.hip; the union-find core is csrc/matte_clean_core.h.
+ *
+ * Per frame, integers only, 16 <= height, width <= 1024; pixel (x, y) has the index y * W + x:
+ * COMPONENTS.  S = {m >= support}, split into 8-connected components.  A component's label is the smallest index among its pixels
+ *   (so labels depend on no schedule).  Per component: area, its pixel count; bottom: it has a pixel in row H - 1 (the torso leaves
+ *   through the bottom); anchored: it holds one of the frame's k anchor pixels (x, y) (anchors outside the frame are ignored).
+ *   pass = area >= min_area and (keep == ALL or bottom or anchored).  When keep == ANCHORED, the frame has components and none
+ *   passes, all of them are kept and status bit 1 is set (an untouched matte is better than an empty one); otherwise the kept ones are
+ *   those that pass.
+ *   m1 = m on a pixel of a kept component, 0 on a pixel of a removed one.  A pixel with m < support keeps its value when a pixel of a
+ *   kept component lies within Chebyshev distance `grow` of it (the kept component's soft fringe) and becomes 0 elsewhere (the haze).
+ * HOLES (skipped when max_hole = 0).  N = {m1 < core}, split into 4-connected components.  A component of N that has no pixel on any of
+ *   the four frame edges and at most max_hole pixels becomes 255, its soft rim included.
+ * REPORT, int32 [8] per frame: components of S; kept; pixels of removed components; pixels with 0 < m < support that became 0; holes
+ *   filled; pixels filled; status (bit 1: nothing passed, all kept - then kept = components; bit 2: a step cap of the labelling was
+ *   reached, which a correct run cannot: the result is then not to be used); 0.
+ * min_area = -1 means H * W / 1024, max_hole = -1 means H * W / 256; the Python layer's other defaults are support 32, core 224,
+ * grow 4, keep ANCHORED.  All of them are UNTUNED on real footage.
+ * A frame's result depends on that frame and its anchors alone: the same bytes in any batch.  No floating-point anything; integer
+ * atomics only; no launch waits on another workgroup.
+ * ---------------------------------------------------------------------------------------------- */
+#define VP_MATTECLEAN_MAX_FRAMES 4096
+#define VP_MATTECLEAN_MAX_SIZE 1024
+#define VP_MATTECLEAN_MAX_GROW 16
+#define VP_MATTECLEAN_MAX_ANCHORS 256
+#define VP_MATTECLEAN_REPORT_INTS 8
+#define VP_MATTECLEAN_KEEP_ALL 0
+#define VP_MATTECLEAN_KEEP_ANCHORED 1
+typedef struct vp_matteclean_desc {
+  uint32_t struct_bytes;  /* sizeof(vp_matteclean_desc) of the caller's build: must equal vp_matteclean_desc_size() */
+  int32_t max_frames;     /* frames per call: 1 .. VP_MATTECLEAN_MAX_FRAMES */
+  int32_t max_height;     /* 16 .. VP_MATTECLEAN_MAX_SIZE */
+  int32_t max_width;      /* 16 .. VP_MATTECLEAN_MAX_SIZE */
+} vp_matteclean_desc;
+size_t vp_matteclean_desc_size(void);
+typedef struct vp_matteclean vp_matteclean_t;
+/* 0 on a refused descriptor (vp_last_error names the field).  At most 12 bytes per pixel of max_frames x max_height x max_width plus
+ * 4096: the labels (4), the hole pass's parents (4), one record per pixel pair (2) and the report. */
+size_t vp_matteclean_workspace_bytes(const vp_matteclean_desc* d);
+/* Host only: touches no device memory.  workspace: DEVICE memory the caller keeps alive as long as the handle. */
+int vp_matteclean_create(const vp_matteclean_desc* d, void* workspace, size_t workspace_bytes, vp_matteclean_t** out);
+void vp_matteclean_destroy(vp_matteclean_t* h);
+/* matte, out: DEVICE uint8 [n, height, width], contiguous; out is the matte itself or disjoint from it (an overlap is refused); anchors: NULL with k = 0, else DEVICE int32
+ * [n, k, 2] of (x, y).  Refused before anything is enqueued, vp_last_error naming the field: n, height, width, support and core outside
+ * 1 .. 255, min_area and max_hole outside -1 .. height * width, grow outside 0 .. 16, keep, k outside 0 .. 256, anchors, out.  One fill of
+ * the report and twelve launches on `stream` (seven with max_hole = 0); nothing is read back; never waits, never allocates. */
+int vp_matteclean_clean(vp_matteclean_t* h, const unsigned char* matte, int n, int height, int width, int support, int core, int min_area,
+                        int max_hole, int grow, int keep, const int* anchors, int k, unsigned char* out, void* stream);
+/* "labels": int32 [max_frames, height, width] of the last call (the descriptor's before the first): -1 outside S, else the component's
+ * label; "report": int32 [max_frames, VP_MATTECLEAN_REPORT_INTS] */
+int vp_matteclean_tensor(vp_matteclean_t* h, const char* name, void** ptr, int64_t shape[4]);
 
 /* Host helper: CRC-32C (Castagnoli, the checksum of TensorFlow checkpoint bundles) of `n` bytes, continuing from `crc` (0 to start). */
 unsigned vp_crc32c(const void* data, size_t n, unsigned crc);

@@ -115,6 +115,15 @@ class KeyMatteDesc(ctypes.Structure):
 KEYMATTE_MAX_FRAMES, KEYMATTE_MAX_SIZE, KEYMATTE_MAX_RADIUS, KEYMATTE_MODEL_DOUBLES = 4096, 1024, 16, 19
 
 
+class MatteCleanDesc(ctypes.Structure):
+  _fields_ = [("struct_bytes", ctypes.c_uint32), ("max_frames", ctypes.c_int32), ("max_height", ctypes.c_int32), ("max_width", ctypes.c_int32)]
+
+
+# include/vp_hip.h VP_MATTECLEAN_MAX_FRAMES, _MAX_SIZE, _MAX_GROW, _MAX_ANCHORS, _REPORT_INTS, _KEEP_ALL, _KEEP_ANCHORED
+MATTECLEAN_MAX_FRAMES, MATTECLEAN_MAX_SIZE, MATTECLEAN_MAX_GROW, MATTECLEAN_MAX_ANCHORS, MATTECLEAN_REPORT_INTS = 4096, 1024, 16, 256, 8
+MATTECLEAN_KEEP_ALL, MATTECLEAN_KEEP_ANCHORED = 0, 1
+
+
 class TriptychDesc(ctypes.Structure):
   _fields_ = [("struct_bytes", ctypes.c_uint32), ("max_frames", ctypes.c_int32), ("size", ctypes.c_int32), ("face_size", ctypes.c_int32),
               ("max_side", ctypes.c_int32)]
@@ -318,6 +327,13 @@ _SIGNATURES = {
     "vp_keymatte_set_model": (ctypes.c_int, [_P, _P, _P]),
     "vp_keymatte_tensor": (ctypes.c_int, [_P, ctypes.c_char_p, ctypes.POINTER(_P), ctypes.POINTER(ctypes.c_int64)]),
     "vp_keymatte_solve_host": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int64), ctypes.c_double, ctypes.POINTER(ctypes.c_double)]),
+    "vp_key_foreground": (ctypes.c_int, [_P, _P, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, ctypes.c_double, _P, _P]),
+    "vp_matteclean_desc_size": (ctypes.c_size_t, []),
+    "vp_matteclean_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(MatteCleanDesc)]),
+    "vp_matteclean_create": (ctypes.c_int, [ctypes.POINTER(MatteCleanDesc), _P, ctypes.c_size_t, ctypes.POINTER(_P)]),
+    "vp_matteclean_destroy": (None, [_P]),
+    "vp_matteclean_clean": (ctypes.c_int, [_P, _P] + [ctypes.c_int] * 9 + [_P, ctypes.c_int, _P, _P]),
+    "vp_matteclean_tensor": (ctypes.c_int, [_P, ctypes.c_char_p, ctypes.POINTER(_P), ctypes.POINTER(ctypes.c_int64)]),
     "vp_bfm_reconstruct_rows": (ctypes.c_int, [ctypes.POINTER(BfmModel), _P, _P, ctypes.c_int, _P, ctypes.c_int, _P, _P, _P, _P, ctypes.c_size_t, _P]),
     "vp_bfmstream_group_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(BfmStreamGroupDesc)]),
     "vp_bfmstream_group_plan_info": (ctypes.c_int, [ctypes.POINTER(BfmStreamGroupDesc), ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
@@ -439,6 +455,7 @@ DESC_SIZE_QUERIES = {
     "vp_avimux_desc_size": AviMuxDesc,
     "vp_triptych_desc_size": TriptychDesc,
     "vp_keymatte_desc_size": KeyMatteDesc,
+    "vp_matteclean_desc_size": MatteCleanDesc,
 }
 
 _lib = None

@@ -13,6 +13,7 @@
 //             32 columns, then per pixel the column sums, a_k and b_k: two float64 planes in the workspace.
 //   mean      per plane: the tile with its halo into LDS (outside the image +0.0: adding it changes no bit of a sum that started from
 //             +0.0), row sums in increasing x, column sums in increasing y; then q and the matte byte.
+// Foreground (vp_key_foreground): one pointwise launch, the subject's colours from the frame, the matte and the model's planes.
 // LDS: coeff 2 x 64 x 64 bytes + 4 x 64 x 32 ints = 40 KiB, mean 64 x 64 + 64 x 32 doubles = 48 KiB: three workgroups per CU of 160 KiB.
 // A single launch would hold the bytes of a 96 x 96 footprint, both float64 planes of 64 x 64 and the integer row sums (over 110 KiB at
 // radius 16) and would evaluate the key 9 times per pixel there; the planes cost 16 bytes per pixel written and read back instead
@@ -291,6 +292,53 @@ __global__ __launch_bounds__(kKmLanes) void km_mean_kernel(const KmApplyArgs g) 
   }
 }
 
+struct KmForeArgs {
+  const unsigned char* frames;
+  size_t pitch, stride;                      // bytes
+  const double* model;
+  const unsigned char* matte;                // [n][H][W]
+  unsigned char* out;                        // [n][H][W][3]
+  double despill;
+  int H, W;
+};
+
+__device__ __forceinline__ double km_plane(const double* m, int c, int x, int y) { return (m[3 * c] + m[3 * c + 1] * (double)x) + m[3 * c + 2] * (double)y; }
+
+// FOREGROUND of the header: grid (ceil(H W / 256), n)
+__global__ __launch_bounds__(kKmLanes) void km_foreground_kernel(const KmForeArgs g) {
+  const int i = blockIdx.x * kKmLanes + threadIdx.x, f = blockIdx.y;
+  if (i >= g.H * g.W) return;
+  const int y = i / g.W, x = i - y * g.W;
+  const size_t o = (size_t)f * g.H * g.W + i;
+  const int m = g.matte[o];
+  unsigned char* dst = g.out + 3 * o;
+  if (m == 0) { dst[0] = dst[1] = dst[2] = 0; return; }
+  const unsigned char* px = g.frames + (size_t)f * g.stride + (size_t)y * g.pitch + 3 * x;
+  double e[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    e[c] = (double)px[c];
+    if (m != 255) {
+      const double b = km_plane(g.model, c, x, y);
+      e[c] = fmin(fmax(b + (e[c] - b) * (255.0 / (double)m), 0.0), 255.0);
+    }
+  }
+  if (g.despill > 0.0) {
+    const double v0 = km_plane(g.model, 0, g.W / 2, g.H / 2), v1 = km_plane(g.model, 1, g.W / 2, g.H / 2), v2 = km_plane(g.model, 2, g.W / 2, g.H / 2);
+    const int k = v0 >= v1 && v0 >= v2 ? 0 : (v1 >= v2 ? 1 : 2);
+    const double vk = k == 0 ? v0 : (k == 1 ? v1 : v2);
+    const double lead = vk - (k == 0 ? fmax(v1, v2) : (k == 1 ? fmax(v0, v2) : fmax(v0, v1)));
+    if (lead >= 16.0) {
+      const double ek = k == 0 ? e[0] : (k == 1 ? e[1] : e[2]);
+      const double others = k == 0 ? e[1] + e[2] : (k == 1 ? e[0] + e[2] : e[0] + e[1]);
+      const double cut = ek - g.despill * fmax(0.0, ek - others / 2.0);
+      if (k == 0) e[0] = cut; else if (k == 1) e[1] = cut; else e[2] = cut;
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < 3; ++c) dst[c] = (unsigned char)(int)floor(e[c] + 0.5);
+}
+
 }  // namespace vp
 
 struct vp_keymatte {
@@ -422,6 +470,22 @@ int vp_keymatte_apply(vp_keymatte_t* h, const unsigned char* frames, size_t row_
   hipLaunchKernelGGL(km_coeff_kernel, grid, dim3(kKmLanes), 0, st, g);
   VP_HIP_CHECK(hipGetLastError());
   hipLaunchKernelGGL(km_mean_kernel, grid, dim3(kKmLanes), 0, st, g);
+  VP_HIP_CHECK(hipGetLastError());
+  return VP_OK;
+}
+
+int vp_key_foreground(vp_keymatte_t* h, const unsigned char* frames, size_t row_pitch, size_t frame_stride, int n, int height, int width,
+                      const unsigned char* matte, double despill, unsigned char* out, void* stream) {
+  const char* who = "vp_key_foreground";
+  if (const int rc = km_frames(h, who, frames, row_pitch, frame_stride, n, height, width)) return rc;
+  if (!matte) { set_err("%s: bad argument (device matte)", who); return VP_ERR_ARG; }
+  if (!out) { set_err("%s: bad argument (device out)", who); return VP_ERR_ARG; }
+  if (!(despill >= 0.0 && despill <= 1.0)) { set_err("%s: despill %g outside 0 .. 1", who, despill); return VP_ERR_ARG; }
+  KmForeArgs g;
+  memset(&g, 0, sizeof(g));
+  g.frames = frames; g.pitch = row_pitch; g.stride = frame_stride;
+  g.model = h->model; g.matte = matte; g.out = out; g.despill = despill; g.H = height; g.W = width;
+  hipLaunchKernelGGL(km_foreground_kernel, dim3((height * width + kKmLanes - 1) / kKmLanes, n), dim3(kKmLanes), 0, (hipStream_t)stream, g);
   VP_HIP_CHECK(hipGetLastError());
   return VP_OK;
 }

@@ -24,6 +24,18 @@ deep_video_portraits_v2, :690-695), which need TensorFlow 1, MXNet, OpenCV and F
 --key_thresholds LO HI, --key_radius R, --key_eps E, --key_band B   KeyMatte's ramp (4 10), guided-filter window (4) and regulariser
                    (25), and the width of the border band (panel size // 16); the defaults are untuned on real footage
 --write_alpha DIR  with --key_matte: gets the mattes as <i>.png, panel size, for inspection and for reuse as --alpha_dir
+--clean_matte      cleans the matte of --key_matte or --alpha_dir before the build and before --write_alpha (voicepuppet_amd.matte_clean.
+                   MatteCleaner): components of the matte that are not the subject (they neither leave through the bottom edge nor hold
+                   one of the frame's 68 landmarks: speckle, a prop, the frame's edge) are removed with the haze around them, enclosed holes
+                   in the subject are filled.  Component bookkeeping: it moves no edge
+--clean_support S, --clean_core C, --clean_min_area A, --clean_max_hole A, --clean_grow G, --clean_keep all|anchored   MatteCleaner.clean's
+                   parameters (32, 224, S * S // 1024, S * S // 256, 4, anchored); the defaults are untuned on real footage
+--key_foreground   the frame panel gets the subject's own colours instead of the frame's (KeyMatte.foreground): on the matte's soft edge
+                   the frame is a mix of subject and backdrop, and frame x matte teaches the generator a fringe of backdrop colour.  With
+                   --alpha_dir the backdrop model is fitted to the border of the first frames as with --key_matte.  Exact only where the
+                   matte is; where the matte is 0 the panel is black
+--key_despill S    with --key_foreground: 0 .. 1, how much of the backdrop's key channel is taken out of the subject (default 0; acts only
+                   on a backdrop whose largest channel leads by 16 levels)
 --bfmcoeff FILE    rows of 257 coefficients to use instead of fitting them (fit_landmarks.py --clip writes such a file)
 --appearance first|none   first (default): texture and lighting are fitted to frame 0's pixels and shared by the clip; none: zeros
 --appearance_visibility, --appearance_prefilter   that fit without self-occluded vertices / on area means of frame 0 (both off by default)
@@ -34,7 +46,9 @@ The paste geometry is infer_bfmvid.paste_geometry for every frame, i.e. step 6's
 that cannot be built (TriptychBuilder's status) repeats the frame before it, as step 6 does; a clip whose first frame cannot be built is
 refused.  Needs BFM/BFM_model_front.mat and BFM/similarity_Lm3D_all.mat, like fit_landmarks.py.  One line is printed: frames, statuses,
 repeated frames, and the reprojection error in pixels of the 224 image as fit_landmarks.py prints it; with --key_matte also the share of
-border samples the backdrop model kept and its residual, with a warning when the border was not a plain backdrop.
+border samples the backdrop model kept and its residual, with a warning when the border was not a plain backdrop; with --clean_matte
+also "clean: removed 3 components / 66 px, filled 1 hole / 26 px" over all frames, with a warning for frames in which no component held a
+landmark or reached the bottom edge (they are left as they were).  The order is matte, clean, foreground, build.
 
 A one-frame run with --key_matte (a folder with 0.jpg and a one-line landmark file) is how an enrolment photo for infer_bfmvid.py and
 PuppetStreamGroup.attach is made: out_dir/0.jpg is the [photo | render on black | matte] triptych they read."""
@@ -148,7 +162,7 @@ def read_alpha(reader, alpha_dir, first, n):
 
 def parse_options(argv=None):
   p = OptionParser(usage='usage: %prog --clip_dir DIR --landmarks FILE --out_dir DIR [--size S] [--crop X0 Y0 SIDE] [--alpha_dir DIR] '
-                         '[--key_matte [--write_alpha DIR]] [--bfmcoeff FILE] [--appearance first|none] [--frame_batch N] [--list FILE]')
+                         '[--key_matte [--write_alpha DIR]] [--clean_matte] [--key_foreground [--key_despill S]] [--bfmcoeff FILE] [--appearance first|none] [--frame_batch N] [--list FILE]')
   p.add_option('--clip_dir', type='string', dest='clip_dir', default=None, help='folder of 0.jpg, 1.jpg, ...')
   p.add_option('--landmarks', type='string', dest='landmarks', default=None, help='68 landmarks per frame, 136 comma-separated values per line')
   p.add_option('--out_dir', type='string', dest='out_dir', default=None, help='the dataset folder to write')
@@ -181,11 +195,30 @@ def parse_options(argv=None):
   p.add_option('--key_eps', type='float', dest='key_eps', default=25.0, help='--key_matte: guided-filter regulariser, grey levels squared')
   p.add_option('--key_band', type='int', dest='key_band', default=None, help='--key_matte: width of the border band (default: size // 16)')
   p.add_option('--write_alpha', type='string', dest='write_alpha', default=None, help='--key_matte: folder that gets the mattes as <i>.png')
+  p.add_option('--clean_matte', action='store_true', dest='clean_matte', default=False,
+               help='clean the matte of --key_matte or --alpha_dir on the device (MatteCleaner): stray components out, enclosed holes filled')
+  p.add_option('--clean_support', type='int', dest='clean_support', default=32, help='--clean_matte: components of matte >= S (1 .. 255)')
+  p.add_option('--clean_core', type='int', dest='clean_core', default=224, help='--clean_matte: holes of matte < C (1 .. 255)')
+  p.add_option('--clean_min_area', type='int', dest='clean_min_area', default=None, help='--clean_matte: smallest component kept (default S * S // 1024)')
+  p.add_option('--clean_max_hole', type='int', dest='clean_max_hole', default=None, help='--clean_matte: largest hole filled, 0: none (default S * S // 256)')
+  p.add_option('--clean_grow', type='int', dest='clean_grow', default=4, help='--clean_matte: width of the soft fringe kept around a component, 0 .. 16')
+  p.add_option('--clean_keep', type='choice', choices=['all', 'anchored'], dest='clean_keep', default='anchored',
+               help='--clean_matte: anchored keeps the components that reach the bottom edge or hold a landmark; all keeps every large one')
+  p.add_option('--key_foreground', action='store_true', dest='key_foreground', default=False,
+               help='the frame panel gets the subject\'s colours without the backdrop\'s share (KeyMatte.foreground); needs a matte')
+  p.add_option('--key_despill', type='float', dest='key_despill', default=0.0, help='--key_foreground: 0 .. 1 of the key channel\'s spill removed')
   opts, args = p.parse_args(argv)
   if opts.key_matte and opts.alpha_dir:
     p.error('--key_matte computes the matte that --alpha_dir reads: give one of the two')
   if opts.write_alpha and not opts.key_matte:
     p.error('--write_alpha writes the mattes of --key_matte')
+  if (opts.clean_matte or opts.key_foreground) and not (opts.key_matte or opts.alpha_dir):
+    p.error('--clean_matte and --key_foreground work on the matte of --key_matte or --alpha_dir')
+  if (not (1 <= opts.clean_support <= 255) or not (1 <= opts.clean_core <= 255) or not (0 <= opts.clean_grow <= 16)
+      or (opts.clean_min_area is not None and opts.clean_min_area < 0) or (opts.clean_max_hole is not None and opts.clean_max_hole < 0)):
+    p.error('--clean_support and --clean_core 1 .. 255, --clean_grow 0 .. 16, --clean_min_area and --clean_max_hole not negative')
+  if not (0.0 <= opts.key_despill <= 1.0):
+    p.error('--key_despill 0 .. 1')
   lo, hi = opts.key_thresholds
   if not (0.0 <= lo < hi < float('inf')) or not (0 <= opts.key_radius <= 16) or not (0.0 < opts.key_eps < float('inf')):
     p.error('--key_thresholds LO HI with 0 <= LO < HI, --key_radius 0 .. 16, --key_eps above 0')
@@ -262,34 +295,49 @@ def main(argv=None):
   builder = TriptychBuilder(S, batch)
   status, repeated = [], []
   keyer, key_report = None, None
-  if opts.key_matte:
+  if opts.key_matte or opts.key_foreground:
     from voicepuppet_amd.matte import STATUS_TEXT, KeyMatte
     key_n = min(opts.key_frames or batch, frames_n)
     if key_n < 1:
       raise SystemExit('--key_frames must be at least 1')
     try:
-      keyer = KeyMatte(max(batch, key_n), S, S, max_radius=opts.key_radius)
+      keyer = KeyMatte(max(batch, key_n), S, S, max_radius=opts.key_radius if opts.key_matte else 0)
       keyer.fit(torch.cat([reader.read(first, min(batch, key_n - first)) for first in range(0, key_n, batch)]), band=opts.key_band)
     except (ValueError, RuntimeError) as e:
-      raise SystemExit('--key_matte: %s' % e)
+      raise SystemExit('%s: %s' % ('--key_matte' if opts.key_matte else '--key_foreground', e))
     key_report = keyer.report()
     if opts.write_alpha:
       os.makedirs(opts.write_alpha, exist_ok=True)
+  cleaner, clean_reports = None, []
+  if opts.clean_matte:
+    from voicepuppet_amd.matte_clean import MatteCleaner, summary as clean_summary
+    cleaner = MatteCleaner(batch, S, S)
+    cleaned = torch.empty(batch, S, S, dtype=torch.uint8, device='cuda')
+    anchors = torch.from_numpy(np.floor(lms).astype(np.int32)).cuda()       # the panel landmarks' pixels
   try:
     for first in range(0, frames_n, batch):
       n = min(batch, frames_n - first)
       frames = reader.read(first, n)
       render, face_mask = renderer.render_view(coeff[first:first + n], view=0)
       alpha = read_alpha(reader, opts.alpha_dir, first, n) if opts.alpha_dir else None
-      if keyer is not None:
+      if opts.key_matte:
         alpha = keyer.matte(frames, lo=opts.key_thresholds[0], hi=opts.key_thresholds[1], radius=opts.key_radius, eps=opts.key_eps)
-        if opts.write_alpha:
-          keyer.write_png(alpha, opts.write_alpha, first)
+      if cleaner is not None:
+        alpha = cleaner.clean(alpha.contiguous(), support=opts.clean_support, core=opts.clean_core, min_area=opts.clean_min_area,
+                              max_hole=opts.clean_max_hole, grow=opts.clean_grow, keep=opts.clean_keep, anchors=anchors[first:first + n], out=cleaned)
+        clean_reports.append(cleaner.report())
+      if opts.write_alpha:
+        keyer.write_png(alpha, opts.write_alpha, first)
+      if opts.key_foreground:
+        frames = keyer.foreground(frames, alpha.contiguous(), despill=opts.key_despill)
       trip, st = builder.build(frames, render, face_mask, geometry[first:first + n], alpha=alpha)
       repeated += builder.write(trip, st, opts.out_dir, first)
       status.append(st.cpu().numpy())
   except ValueError as e:
     raise SystemExit('%s: %s' % (opts.clip_dir, e))
+  finally:
+    if cleaner is not None:
+      cleaner.close()
   status = np.concatenate(status)
 
   np.savetxt(os.path.join(opts.out_dir, 'bfmcoeff.txt'), coeff.cpu().numpy(), delimiter=',', fmt='%.8g')
@@ -302,17 +350,27 @@ def main(argv=None):
   counts = ' '.join('%d:%d' % (s, int((status == s).sum())) for s in sorted(set(status.tolist())))
   for s in sorted(set(status.tolist()) - {0}):
     logger.warning('triptych status %d: %s', s, STATUS.get(s, '?'))
-  if key_report is not None:
+  if key_report is not None and opts.key_matte:
     extra += '; key matte: kept %.2f, residual %.1f levels' % (key_report['kept'], key_report['residual_rms'])
     if key_report['status'] != 0:
       logger.warning('key matte status %d: %s', key_report['status'], STATUS_TEXT.get(key_report['status'], '?'))
     if key_report['kept'] < 0.5:
       logger.warning('key matte: the robust pass kept %.2f of the border samples: the border is not a plain backdrop', key_report['kept'])
+  if cleaner is not None:
+    clean_reports = np.concatenate(clean_reports)
+    extra += '; clean: ' + clean_summary(clean_reports)
+    if (clean_reports[:, 6] & 1).any():
+      logger.warning('matte clean: no component of %d frames held a landmark or reached the bottom edge; they were left as they were',
+                     int((clean_reports[:, 6] & 1).sum()))
+    if (clean_reports[:, 6] & 2).any():
+      raise SystemExit('matte clean: the labelling reached a step cap (a bug); the mattes are not to be used')
   fit = summary_line(opts.clip_dir, report, reprojection_error(fitter, coeff, aligned))
   print('%s; triptych status %s, %d repeated, %d read with PIL%s' % (fit, counts, len(repeated), reader.fallbacks, extra))
   res = {'frames': frames_n, 'status': status, 'repeated': repeated, 'geometry': geometry}
   if key_report is not None:
     res['key_matte'] = key_report
+  if cleaner is not None:
+    res['clean'] = clean_reports
   return res
 
 

@@ -7,7 +7,10 @@ for a head and shoulders in front of a studio backdrop only.  It is a key, not a
 wrong tool, and report() says so (status, kept, residual_rms).  The defaults below come from synthetic scenes and are untuned on real
 footage.
 
-fit and matte only enqueue on the current stream; report() is the one host read.
+foreground() (vp_key_foreground) returns the subject's own colours on the matte's soft edge, with the backdrop's share taken out by the
+same model; voicepuppet_amd.matte_clean.MatteCleaner is the clean-up stage for the matte itself.
+
+fit, matte and foreground only enqueue on the current stream; report() and spill() are the host reads.
 """
 import ctypes
 import os
@@ -30,6 +33,15 @@ def keymatte_desc(max_frames, max_height, max_width, max_radius=16):
 
 def default_band(height):
   return max(2, int(height) // 16)
+
+
+def spill_of(model, height, width):
+  """See KeyMatte.spill; model: the record as a host array (Python floats round as the kernel's float64 does)."""
+  x, y = float(int(width) // 2), float(int(height) // 2)
+  v = [(float(model[3 * c]) + float(model[3 * c + 1]) * x) + float(model[3 * c + 2]) * y for c in range(3)]
+  k = max(range(3), key=lambda c: (v[c], -c))
+  lead = v[k] - max(v[c] for c in range(3) if c != k)
+  return {"channel": k, "lead": lead, "active": lead >= 16.0}
 
 
 class KeyMatte(Handle):
@@ -96,6 +108,29 @@ class KeyMatte(Handle):
                                   stream())
     _lib.check(rc, "vp_keymatte_apply")
     return out[:n]
+
+  def foreground(self, frames, matte, despill=0.0, out=None):
+    """-> device uint8 [n, H, W, 3]: the subject's own colours, F of I = a F + (1 - a) B with the model's planes as B: per channel
+    b + (I - b) * 255 / m, the frame's colours where the matte is 255 and 0 where it is 0.  What frame x matte then carries on the soft
+    edge is the subject's colour, not a fringe of the backdrop's.  despill (0 .. 1) also pulls the backdrop's key channel down to the
+    mean of the other two where it exceeds it - only when that channel leads by 16 grey levels at the frame's centre; spill() says
+    whether it does.  matte: contiguous device uint8 [n, H, W] (KeyMatte's own or a cleaned one); out: contiguous [>= n, H, W, 3]."""
+    pitch, stride, n, H, W = self._frames(frames, "foreground")
+    if matte.dtype != torch.uint8 or not matte.is_cuda or not matte.is_contiguous() or tuple(matte.shape) != (n, H, W):
+      raise ValueError("foreground: matte must be a contiguous device uint8 [%d, %d, %d]" % (n, H, W))
+    if out is None:
+      out = torch.empty(max(n, 1), H, W, 3, dtype=torch.uint8, device="cuda")
+    elif (out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous() or out.dim() != 4 or out.shape[0] < n
+          or tuple(out.shape[1:]) != (H, W, 3)):
+      raise ValueError("foreground: out must be a contiguous device uint8 [>= %d, %d, %d, 3]" % (n, H, W))
+    rc = self.L.vp_key_foreground(self.h, ptr(frames), pitch, stride, n, H, W, ptr(matte), float(despill), ptr(out), stream())
+    _lib.check(rc, "vp_key_foreground")
+    return out[:n]
+
+  def spill(self, height, width):
+    """{'channel', 'lead', 'active'}: the backdrop's largest channel at the centre of a height x width frame, its lead over the larger of
+    the other two in grey levels, and whether foreground's despill acts (lead >= 16).  A host read of the model."""
+    return spill_of(self.model().cpu().numpy(), height, width)
 
   def tensor(self, name):
     """'moments': int64 [2, 21], pass 1 and pass 2 of the last fit; 'model': float64 [MODEL_DOUBLES].  Views of the workspace."""
