@@ -38,6 +38,8 @@
  *                             models, for footage in front of a PLAIN backdrop only: a colour key with an edge-aware clean-up, no network
  *   vp_matteclean_*    replaces  nothing: the reference pastes its matting network's output as it is (components that are not the subject,
  *                             holes in it); vp_key_foreground likewise: the reference trains on frame x matte, backdrop fringe included
+ *   vp_mattesolve_*    replaces  datasets/make_data_from_GRID.py:654-672 (step 6's trimap from an erosion and a dilation of the mask, and
+ *                             its matting network): a closed-form matting solve in the trimap's band, no network and no weights
  *
  * Conventions: every function returns 0 on success and a negative vp_status otherwise (never throws);
  * all tensor pointers are DEVICE pointers owned by the caller (NHWC, row-major); nothing is allocated
@@ -1593,6 +1595,98 @@ int vp_matteclean_clean(vp_matteclean_t* h, const unsigned char* matte, int n, i
 /* "labels": int32 [max_frames, height, width] of the last call (the descriptor's before the first): -1 outside S, else the component's
  * label; "report": int32 [max_frames, VP_MATTECLEAN_REPORT_INTS] */
 int vp_matteclean_tensor(vp_matteclean_t* h, const char* name, void** ptr, int64_t shape[4]);
+
+/* ------------------------------------------------------------------------------------------------
+ * Trimap and closed-form matting solve, on the device: stages two and three of the matte that step 6 of the reference's
+ * datasets/make_data_from_GRID.py makes (:654-659 the trimap from a 30 x 30 erosion and a 20 x 20 dilation of the segmentation mask,
+ * :670-672 the matting network's alpha with the known pixels forced afterwards).  In place of the matting network: the closed-form
+ * matting of Levin, Lischinski and Weiss (the matting Laplacian, applied by window sums as in He, Sun and Tang's large-kernel form),
+ * a float64 linear solve inside the trimap's unknown band.  It needs no weights and no backdrop model: any binary mask will do.
+ * csrc/matte_solve.hip; tests/matte_solve_ref.py restates every number below in numpy.
+ *
+ * 16 <= height, width <= 1024; frames are addressed as in vp_keymatte_apply (row_pitch, frame_stride, RGB bytes I_c, c = 0 1 2).
+ * TRIMAP, integers only.  A k x k square covers the offsets d = -(k / 2) .. k - 1 - (k / 2) (integer division) on each axis; the square
+ *   at (x, y) is the pixels (x + dx, y + dy) of it that lie inside the image (pixels outside the image neither erode nor dilate).
+ *   fg(x, y): every pixel of the erode x erode square at (x, y) has m >= core.  maybe(x, y): some pixel of the dilate x dilate square at
+ *   (x, y) has m >= support.  trimap = 255 on fg, else 127 on maybe, else 0 (127 is what the reference's mask2 + mask // 2 gives).
+ *   1 <= erode, dilate <= VP_MATTESOLVE_MAX_SQUARE; 0 means the default by frame size: the reference's 30 and 20 are for 720 x 576
+ *   video, 1 / 19 and 1 / 29 of the shorter side, so erode = max(5, min(64, min(H, W) / 19)), dilate = max(5, min(64, min(H, W) / 29)).
+ *   This is the definition, not a claim of equality with any library's erode and dilate.
+ *   The call also writes, per 32 x 32 tile (the solver's tiling, tiles in row-major order), whether the tile holds a pixel of value 127:
+ *   tensor "tiles".  The solve takes any trimap, so it forms these flags again from the trimap it is given.
+ * SOLVE.  A trimap pixel is known 0 (value 0), known 1 (value 255) or unknown (anything else); U the unknown pixels; k = 1 on known-1
+ *   pixels and 0 elsewhere.  radius r in 1 .. max_radius; w_j the (2 r + 1)^2 window centred on j clipped to the image, n_j its pixel
+ *   count.  All float64, in the order written, no fused multiply-add; every window sum takes its rows in increasing y and within a row
+ *   increasing x, starting from +0.0.
+ *   MOMENTS of w_j, from exact integer sums S_c = sum I_c, S_cd = sum I_c I_d (c <= d): nd = (double)n_j;
+ *   mu_c = (double)S_c / nd;  Sigma_cd = (double)(n_j * S_cd - S_c * S_d) / (nd * nd);  M = Sigma + (eps / nd) Id with
+ *   a = M00, b = M01, c = M02, d = M11, e = M12, f = M22;  adjugate A00 = d * f - e * e, A01 = c * e - b * f, A02 = b * e - c * d,
+ *   A11 = a * f - c * c, A12 = b * c - a * e, A22 = a * d - b * b;  D = (a * A00 + b * A01) + c * A02;  Inv_cd = A_cd / D.
+ *   LAPLACIAN of a plane p: per window j  mp = (sum p) / nd,  v_c = (sum (double)I_c * p) / nd - mu_c * mp,
+ *   a_j = Inv v (row c: (Inv_c0 * v0 + Inv_c1 * v1) + Inv_c2 * v2),  b_j = mp - ((a_j0 * mu_0 + a_j1 * mu_1) + a_j2 * mu_2);
+ *   per pixel i with sa_c, sb the sums of a_jc, b_j over the windows j in w_i (the windows that hold i):
+ *   (L p)_i = (double)n_i * p_i - (((sa_0 * I_i0 + sa_1 * I_i1) + sa_2 * I_i2) + sb).
+ *   DIAGONAL: diag_i = sum over j in w_i of 1 - (1 + ((d_0 * q_0 + d_1 * q_1) + d_2 * q_2)) / (double)n_j with d = I_i - mu_j and q = Inv_j d.
+ *   SYSTEM: L_UU x = b, b = -(L k)_U, by conjugate gradients preconditioned with 1 / diag_i, from x = 0: r = b, z = r / diag (as
+ *   (1 / diag) * r), p = z.  Iteration it = 0, 1, ..: the frame stops when r.r <= tol * tol * b.b (then iterations = it); otherwise
+ *   q = (L p)_U with p = 0 outside U; a frame whose p.q is not positive or not finite stops where it is with status bit 2; alpha = r.z /
+ *   p.q; x += alpha p; r -= alpha q; z = r / diag; beta = (new r.z) / (old r.z); p = z + beta p.  After `iters` iterations the frame
+ *   stops with iterations = iters.  b.b = 0 (no constraint reaches the band, or the trimap has no unknown pixel): x = 0, zero
+ *   iterations, status bit 1.
+ *   Dot products: per 32 x 32 tile a fixed tree over the workgroup's lanes, then the tiles of the frame in a fixed order, summed again
+ *   by every workgroup that needs the scalar.  No floating-point atomics.  A frame's float64 solution, iteration count and matte are
+ *   therefore the same bits in any batch, at any batch position and on every run.
+ *   Matte: 0 or 255 on the known pixels (the reference's :671-672), (uint8)floor(min(max(x, 0), 1) * 255.0 + 0.5) on U.
+ *   Schedule: two fills, one init launch, two launches per iteration for all `iters` iterations (the host never learns that a frame
+ *   stopped: a stopped frame's workgroups and the tiles without an unknown pixel return at once), one finish launch.  No launch waits
+ *   on another workgroup.
+ * REPORT, per frame VP_MATTESOLVE_REPORT_INTS int32 (32 bytes): [0] unknown pixels, [1] iterations, [2] status, [3] 0, then at byte 16
+ *   the final relative residual sqrt(r.r / b.b) of the recurrence as one float64 (0 with status bit 1), [6] [7] 0.
+ * Defaults of the Python layer: support 32, core 224, erode and dilate by the rule above, radius 1, eps 1 (grey levels squared),
+ * iters 512, tol 1e-6.  They come from synthetic scenes (DESIGN.md 6 has the grid) and are UNTUNED on real footage.
+ * ---------------------------------------------------------------------------------------------- */
+#define VP_MATTESOLVE_MAX_FRAMES 4096
+#define VP_MATTESOLVE_MAX_SIZE 1024
+#define VP_MATTESOLVE_MAX_RADIUS 3
+#define VP_MATTESOLVE_MAX_SQUARE 64
+#define VP_MATTESOLVE_MAX_ITERS 1024
+#define VP_MATTESOLVE_REPORT_INTS 8
+typedef struct vp_mattesolve_desc {
+  uint32_t struct_bytes;  /* sizeof(vp_mattesolve_desc) of the caller's build: must equal vp_mattesolve_desc_size() */
+  int32_t max_frames;     /* frames per call: 1 .. VP_MATTESOLVE_MAX_FRAMES */
+  int32_t max_height;     /* 16 .. VP_MATTESOLVE_MAX_SIZE */
+  int32_t max_width;      /* 16 .. VP_MATTESOLVE_MAX_SIZE */
+  int32_t max_radius;     /* 1 .. VP_MATTESOLVE_MAX_RADIUS */
+} vp_mattesolve_desc;
+size_t vp_mattesolve_desc_size(void);
+typedef struct vp_mattesolve vp_mattesolve_t;
+/* 0 on a refused descriptor (vp_last_error names the field).  48 bytes per pixel of max_frames x max_height x max_width (six float64
+ * planes: x, r, 1 / diag, two of p, L p) plus 44 bytes per 32 x 32 tile (five partial sums and the tile's flag), 36 per frame and at
+ * most 4096. */
+size_t vp_mattesolve_workspace_bytes(const vp_mattesolve_desc* d);
+/* Host only: touches no device memory.  workspace: DEVICE memory the caller keeps alive as long as the handle. */
+int vp_mattesolve_create(const vp_mattesolve_desc* d, void* workspace, size_t workspace_bytes, vp_mattesolve_t** out);
+void vp_mattesolve_destroy(vp_mattesolve_t* h);
+/* TRIMAP.  matte, out: DEVICE uint8 [n, height, width], contiguous and disjoint (an overlap is refused).  Refused before anything is
+ * enqueued, vp_last_error naming the field: n, height, width, support and core outside 1 .. 255, erode and dilate outside 0 .. 64, out.
+ * One launch on `stream`; nothing is read back; never waits, never allocates. */
+int vp_mattesolve_trimap(vp_mattesolve_t* h, const unsigned char* matte, int n, int height, int width, int support, int core, int erode,
+                         int dilate, unsigned char* out, void* stream);
+/* SOLVE.  trimap, matte: DEVICE uint8 [n, height, width], contiguous; matte is the trimap itself or disjoint from it (an overlap at
+ * another address is refused).  Refused before anything is
+ * enqueued, vp_last_error naming the field: n, height, width, row_pitch, frame_stride (as vp_keymatte_apply), radius outside
+ * 1 .. max_radius, eps not finite or <= 0, trimap, iters outside 1 .. VP_MATTESOLVE_MAX_ITERS, tol not finite or < 0, matte.
+ * 2 fills and 2 * iters + 2 launches on `stream`; nothing is read back; never waits, never allocates. */
+int vp_mattesolve_solve(vp_mattesolve_t* h, const unsigned char* frames, size_t row_pitch, size_t frame_stride, int n, int height, int width,
+                        const unsigned char* trimap, int radius, double eps, int iters, double tol, unsigned char* matte, void* stream);
+/* The single op behind the solve, for parity tests: out = L p for DEVICE float64 planes [n, height, width] on 8-byte boundaries,
+ * contiguous and disjoint, no masking.  Refusals as above (frames, radius, eps, p, out).  One launch; touches no workspace. */
+int vp_mattesolve_laplacian(vp_mattesolve_t* h, const unsigned char* frames, size_t row_pitch, size_t frame_stride, int n, int height, int width,
+                            int radius, double eps, const double* p, double* out, void* stream);
+/* "alpha": float64 [max_frames, height, width] of the last SOLVE (the descriptor's before the first; a trimap call of another size does
+ * not change it): the unclamped solution on U, k on the known pixels; "report": int32 [max_frames, VP_MATTESOLVE_REPORT_INTS]; "tiles": int32 [max_frames, ceil(height / 32),
+ * ceil(width / 32)] with the height and width of the last trimap or solve, whichever came later: 1 where the tile holds an unknown pixel */
+int vp_mattesolve_tensor(vp_mattesolve_t* h, const char* name, void** ptr, int64_t shape[4]);
 
 /* Host helper: CRC-32C (Castagnoli, the checksum of TensorFlow checkpoint bundles) of `n` bytes, continuing from `crc` (0 to start). */
 unsigned vp_crc32c(const void* data, size_t n, unsigned crc);

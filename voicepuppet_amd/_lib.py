@@ -124,6 +124,15 @@ MATTECLEAN_MAX_FRAMES, MATTECLEAN_MAX_SIZE, MATTECLEAN_MAX_GROW, MATTECLEAN_MAX_
 MATTECLEAN_KEEP_ALL, MATTECLEAN_KEEP_ANCHORED = 0, 1
 
 
+class MatteSolveDesc(ctypes.Structure):
+  _fields_ = [("struct_bytes", ctypes.c_uint32), ("max_frames", ctypes.c_int32), ("max_height", ctypes.c_int32), ("max_width", ctypes.c_int32),
+              ("max_radius", ctypes.c_int32)]
+
+
+# include/vp_hip.h VP_MATTESOLVE_MAX_FRAMES, _MAX_SIZE, _MAX_RADIUS, _MAX_SQUARE, _MAX_ITERS, _REPORT_INTS
+MATTESOLVE_MAX_FRAMES, MATTESOLVE_MAX_SIZE, MATTESOLVE_MAX_RADIUS, MATTESOLVE_MAX_SQUARE, MATTESOLVE_MAX_ITERS, MATTESOLVE_REPORT_INTS = 4096, 1024, 3, 64, 1024, 8
+
+
 class TriptychDesc(ctypes.Structure):
   _fields_ = [("struct_bytes", ctypes.c_uint32), ("max_frames", ctypes.c_int32), ("size", ctypes.c_int32), ("face_size", ctypes.c_int32),
               ("max_side", ctypes.c_int32)]
@@ -334,6 +343,16 @@ _SIGNATURES = {
     "vp_matteclean_destroy": (None, [_P]),
     "vp_matteclean_clean": (ctypes.c_int, [_P, _P] + [ctypes.c_int] * 9 + [_P, ctypes.c_int, _P, _P]),
     "vp_matteclean_tensor": (ctypes.c_int, [_P, ctypes.c_char_p, ctypes.POINTER(_P), ctypes.POINTER(ctypes.c_int64)]),
+    "vp_mattesolve_desc_size": (ctypes.c_size_t, []),
+    "vp_mattesolve_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(MatteSolveDesc)]),
+    "vp_mattesolve_create": (ctypes.c_int, [ctypes.POINTER(MatteSolveDesc), _P, ctypes.c_size_t, ctypes.POINTER(_P)]),
+    "vp_mattesolve_destroy": (None, [_P]),
+    "vp_mattesolve_trimap": (ctypes.c_int, [_P, _P] + [ctypes.c_int] * 7 + [_P, _P]),
+    "vp_mattesolve_solve": (ctypes.c_int, [_P, _P, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, ctypes.c_int,
+                                           ctypes.c_double, ctypes.c_int, ctypes.c_double, _P, _P]),
+    "vp_mattesolve_laplacian": (ctypes.c_int, [_P, _P, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                               ctypes.c_double, _P, _P, _P]),
+    "vp_mattesolve_tensor": (ctypes.c_int, [_P, ctypes.c_char_p, ctypes.POINTER(_P), ctypes.POINTER(ctypes.c_int64)]),
     "vp_bfm_reconstruct_rows": (ctypes.c_int, [ctypes.POINTER(BfmModel), _P, _P, ctypes.c_int, _P, ctypes.c_int, _P, _P, _P, _P, ctypes.c_size_t, _P]),
     "vp_bfmstream_group_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(BfmStreamGroupDesc)]),
     "vp_bfmstream_group_plan_info": (ctypes.c_int, [ctypes.POINTER(BfmStreamGroupDesc), ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
@@ -456,6 +475,7 @@ DESC_SIZE_QUERIES = {
     "vp_triptych_desc_size": TriptychDesc,
     "vp_keymatte_desc_size": KeyMatteDesc,
     "vp_matteclean_desc_size": MatteCleanDesc,
+    "vp_mattesolve_desc_size": MatteSolveDesc,
 }
 
 _lib = None

@@ -30,6 +30,14 @@ deep_video_portraits_v2, :690-695), which need TensorFlow 1, MXNet, OpenCV and F
                    in the subject are filled.  Component bookkeeping: it moves no edge
 --clean_support S, --clean_core C, --clean_min_area A, --clean_max_hole A, --clean_grow G, --clean_keep all|anchored   MatteCleaner.clean's
                    parameters (32, 224, S * S // 1024, S * S // 256, 4, anchored); the defaults are untuned on real footage
+--solve_matte      solves the matte of --key_matte or --alpha_dir (after --clean_matte) inside a trimap's unknown band
+                   (voicepuppet_amd.matte_solve.MatteSolver): the trimap from an erosion and a dilation of the matte, then closed-form matting
+                   on the frame's colours, step 6's trimap and matting network without the network.  It moves the matte's edge to where
+                   the colours put it.  --alpha_dir with binary masks plus --solve_matte is the path for a CLUTTERED background, where
+                   --key_matte is the wrong tool
+--solve_erode E, --solve_dilate D, --solve_radius R, --solve_eps EPS, --solve_iters N, --solve_tol T   MatteSolver's squares (by panel size:
+                   max(5, S // 19) and max(5, S // 29)), window radius (1), regulariser (1), iteration cap (512) and relative residual
+                   (1e-6); the defaults are untuned on real footage
 --key_foreground   the frame panel gets the subject's own colours instead of the frame's (KeyMatte.foreground): on the matte's soft edge
                    the frame is a mix of subject and backdrop, and frame x matte teaches the generator a fringe of backdrop colour.  With
                    --alpha_dir the backdrop model is fitted to the border of the first frames as with --key_matte.  Exact only where the
@@ -48,7 +56,9 @@ refused.  Needs BFM/BFM_model_front.mat and BFM/similarity_Lm3D_all.mat, like fi
 repeated frames, and the reprojection error in pixels of the 224 image as fit_landmarks.py prints it; with --key_matte also the share of
 border samples the backdrop model kept and its residual, with a warning when the border was not a plain backdrop; with --clean_matte
 also "clean: removed 3 components / 66 px, filled 1 hole / 26 px" over all frames, with a warning for frames in which no component held a
-landmark or reached the bottom edge (they are left as they were).  The order is matte, clean, foreground, build.
+landmark or reached the bottom edge (they are left as they were); with --solve_matte also "solve: 1742 px unknown, 65 iterations,
+residual 9e-7" (means over the clip), with a warning when a frame ended with a status bit set or at its iteration cap.  The order is
+matte, clean, solve, foreground, build.
 
 A one-frame run with --key_matte (a folder with 0.jpg and a one-line landmark file) is how an enrolment photo for infer_bfmvid.py and
 PuppetStreamGroup.attach is made: out_dir/0.jpg is the [photo | render on black | matte] triptych they read."""
@@ -162,7 +172,7 @@ def read_alpha(reader, alpha_dir, first, n):
 
 def parse_options(argv=None):
   p = OptionParser(usage='usage: %prog --clip_dir DIR --landmarks FILE --out_dir DIR [--size S] [--crop X0 Y0 SIDE] [--alpha_dir DIR] '
-                         '[--key_matte [--write_alpha DIR]] [--clean_matte] [--key_foreground [--key_despill S]] [--bfmcoeff FILE] [--appearance first|none] [--frame_batch N] [--list FILE]')
+                         '[--key_matte [--write_alpha DIR]] [--clean_matte] [--solve_matte] [--key_foreground [--key_despill S]] [--bfmcoeff FILE] [--appearance first|none] [--frame_batch N] [--list FILE]')
   p.add_option('--clip_dir', type='string', dest='clip_dir', default=None, help='folder of 0.jpg, 1.jpg, ...')
   p.add_option('--landmarks', type='string', dest='landmarks', default=None, help='68 landmarks per frame, 136 comma-separated values per line')
   p.add_option('--out_dir', type='string', dest='out_dir', default=None, help='the dataset folder to write')
@@ -204,6 +214,15 @@ def parse_options(argv=None):
   p.add_option('--clean_grow', type='int', dest='clean_grow', default=4, help='--clean_matte: width of the soft fringe kept around a component, 0 .. 16')
   p.add_option('--clean_keep', type='choice', choices=['all', 'anchored'], dest='clean_keep', default='anchored',
                help='--clean_matte: anchored keeps the components that reach the bottom edge or hold a landmark; all keeps every large one')
+  p.add_option('--solve_matte', action='store_true', dest='solve_matte', default=False,
+               help='solve the matte of --key_matte or --alpha_dir inside a trimap\'s band on the device (MatteSolver: closed-form matting); '
+                    '--alpha_dir with binary masks plus --solve_matte is the path for cluttered backgrounds')
+  p.add_option('--solve_erode', type='int', dest='solve_erode', default=None, help='--solve_matte: the trimap\'s erosion square, 1 .. 64 (default max(5, S // 19))')
+  p.add_option('--solve_dilate', type='int', dest='solve_dilate', default=None, help='--solve_matte: the trimap\'s dilation square, 1 .. 64 (default max(5, S // 29))')
+  p.add_option('--solve_radius', type='int', dest='solve_radius', default=1, help='--solve_matte: window radius of the matting Laplacian, 1 .. 3')
+  p.add_option('--solve_eps', type='float', dest='solve_eps', default=1.0, help='--solve_matte: its regulariser in grey levels squared, above 0')
+  p.add_option('--solve_iters', type='int', dest='solve_iters', default=512, help='--solve_matte: most conjugate-gradient iterations, 1 .. 1024')
+  p.add_option('--solve_tol', type='float', dest='solve_tol', default=1e-6, help='--solve_matte: relative residual at which a frame stops, not negative')
   p.add_option('--key_foreground', action='store_true', dest='key_foreground', default=False,
                help='the frame panel gets the subject\'s colours without the backdrop\'s share (KeyMatte.foreground); needs a matte')
   p.add_option('--key_despill', type='float', dest='key_despill', default=0.0, help='--key_foreground: 0 .. 1 of the key channel\'s spill removed')
@@ -214,6 +233,12 @@ def parse_options(argv=None):
     p.error('--write_alpha writes the mattes of --key_matte')
   if (opts.clean_matte or opts.key_foreground) and not (opts.key_matte or opts.alpha_dir):
     p.error('--clean_matte and --key_foreground work on the matte of --key_matte or --alpha_dir')
+  if opts.solve_matte and not (opts.key_matte or opts.alpha_dir):
+    p.error('--solve_matte works on the matte of --key_matte or --alpha_dir')
+  if ((opts.solve_erode is not None and not (1 <= opts.solve_erode <= 64)) or (opts.solve_dilate is not None and not (1 <= opts.solve_dilate <= 64))
+      or not (1 <= opts.solve_radius <= 3) or not (0.0 < opts.solve_eps < float('inf')) or not (1 <= opts.solve_iters <= 1024)
+      or not (0.0 <= opts.solve_tol < float('inf'))):
+    p.error('--solve_erode and --solve_dilate 1 .. 64, --solve_radius 1 .. 3, --solve_eps above 0, --solve_iters 1 .. 1024, --solve_tol not negative')
   if (not (1 <= opts.clean_support <= 255) or not (1 <= opts.clean_core <= 255) or not (0 <= opts.clean_grow <= 16)
       or (opts.clean_min_area is not None and opts.clean_min_area < 0) or (opts.clean_max_hole is not None and opts.clean_max_hole < 0)):
     p.error('--clean_support and --clean_core 1 .. 255, --clean_grow 0 .. 16, --clean_min_area and --clean_max_hole not negative')
@@ -314,6 +339,14 @@ def main(argv=None):
     cleaner = MatteCleaner(batch, S, S)
     cleaned = torch.empty(batch, S, S, dtype=torch.uint8, device='cuda')
     anchors = torch.from_numpy(np.floor(lms).astype(np.int32)).cuda()       # the panel landmarks' pixels
+  solver, solve_reports = None, []
+  if opts.solve_matte:
+    from voicepuppet_amd.matte_solve import MatteSolver, summary as solve_summary
+    try:
+      solver = MatteSolver(batch, S, S, max_radius=opts.solve_radius)
+    except ValueError as e:
+      raise SystemExit('--solve_matte: %s' % e)
+    trimap, solved = (torch.empty(batch, S, S, dtype=torch.uint8, device='cuda') for _ in range(2))
   try:
     for first in range(0, frames_n, batch):
       n = min(batch, frames_n - first)
@@ -326,6 +359,10 @@ def main(argv=None):
         alpha = cleaner.clean(alpha.contiguous(), support=opts.clean_support, core=opts.clean_core, min_area=opts.clean_min_area,
                               max_hole=opts.clean_max_hole, grow=opts.clean_grow, keep=opts.clean_keep, anchors=anchors[first:first + n], out=cleaned)
         clean_reports.append(cleaner.report())
+      if solver is not None:
+        tri = solver.trimap(alpha.contiguous(), erode=opts.solve_erode, dilate=opts.solve_dilate, out=trimap)
+        alpha = solver.solve(frames, tri, radius=opts.solve_radius, eps=opts.solve_eps, iters=opts.solve_iters, tol=opts.solve_tol, out=solved)
+        solve_reports.append(solver.report())
       if opts.write_alpha:
         keyer.write_png(alpha, opts.write_alpha, first)
       if opts.key_foreground:
@@ -338,6 +375,8 @@ def main(argv=None):
   finally:
     if cleaner is not None:
       cleaner.close()
+    if solver is not None:
+      solver.close()
   status = np.concatenate(status)
 
   np.savetxt(os.path.join(opts.out_dir, 'bfmcoeff.txt'), coeff.cpu().numpy(), delimiter=',', fmt='%.8g')
@@ -364,6 +403,15 @@ def main(argv=None):
                      int((clean_reports[:, 6] & 1).sum()))
     if (clean_reports[:, 6] & 2).any():
       raise SystemExit('matte clean: the labelling reached a step cap (a bug); the mattes are not to be used')
+  if solver is not None:
+    solve_reports = {k: np.concatenate([r[k] for r in solve_reports]) for k in solve_reports[0]}
+    text, flagged, capped = solve_summary(solve_reports, opts.solve_iters, opts.solve_tol)
+    extra += '; ' + text
+    if flagged:
+      logger.warning('matte solve: %d frames ended with a status bit set (1: nothing to solve or no constraint reaches the band; 2: the '
+                     'iteration broke down)', flagged)
+    if capped:
+      logger.warning('matte solve: %d frames ran all %d iterations without reaching the residual %g', capped, opts.solve_iters, opts.solve_tol)
   fit = summary_line(opts.clip_dir, report, reprojection_error(fitter, coeff, aligned))
   print('%s; triptych status %s, %d repeated, %d read with PIL%s' % (fit, counts, len(repeated), reader.fallbacks, extra))
   res = {'frames': frames_n, 'status': status, 'repeated': repeated, 'geometry': geometry}
@@ -371,6 +419,8 @@ def main(argv=None):
     res['key_matte'] = key_report
   if cleaner is not None:
     res['clean'] = clean_reports
+  if solver is not None:
+    res['solve'] = solve_reports
   return res
 
 
