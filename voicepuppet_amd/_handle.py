@@ -1,6 +1,8 @@
 """What every Python wrapper of a libvp_hip.so handle shares (include/vp_hip.h: vp_X_workspace_bytes, vp_X_create, vp_X_tensor,
 vp_X_destroy): the pointer and stream arguments, the handle's life cycle, views of named tensors inside its workspace, and the host
-read of "byte rows + lengths".  Argument checking of a wrapper's own calls stays with the wrapper.
+read of "byte rows + lengths".  Argument checking of a wrapper's own calls stays with the wrapper, but for the two arguments the image
+families (KeyMatte, MatteCleaner, MatteSolver, FrameMetrics) all take, which are checked here rather than in a module of their own:
+a batch of RGB frames with its pitch and stride (frame_layout, rgb_frames) and a contiguous uint8 plane (u8_plane).
 """
 import ctypes
 import math
@@ -76,6 +78,37 @@ class Handle:
     extents = [int(v) for v in shp]
     shape = shape(extents) if callable(shape) else extents[:shape]
     return workspace_view(self.workspace if workspace is None else workspace, p.value, shape, dtype)
+
+
+def frame_layout(t, who, name="frames"):
+  """(row pitch, frame stride) in bytes of a [n, H, W, 3] view whose pixel's values and row's pixels are adjacent and whose rows and
+  frames do not overlap; any other view is refused in the name of `who`.  Reads shape and strides only: a CPU tensor will do."""
+  n, H, W, _ = t.shape
+  e = t.element_size()
+  if t.stride(3) != 1 or t.stride(2) != 3 or t.stride(1) < 3 * W or (n > 1 and t.stride(0) < (H - 1) * t.stride(1) + 3 * W):
+    raise ValueError("%s: %s has strides %s: a pixel's values and a row's pixels must be adjacent, rows and frames must not overlap"
+                     % (who, name, tuple(t.stride())))
+  pitch = t.stride(1) * e
+  return pitch, max(t.stride(0) * e, (H - 1) * pitch + 3 * W * e)         # a single frame's stride(0) is arbitrary
+
+
+def rgb_frames(t, who, name="frames"):
+  """A device uint8 RGB batch [n, H, W, 3] -> (pitch, stride, n, H, W), pitch and stride as frame_layout gives them."""
+  if t.dim() != 4 or t.shape[3] != 3 or t.dtype != torch.uint8 or not t.is_cuda:
+    raise ValueError("%s: a device uint8 tensor [n, H, W, 3]" % who)
+  return frame_layout(t, who, name) + tuple(int(v) for v in t.shape[:3])
+
+
+def u8_plane(t, who, name, n=None, H=None, W=None, exact=False, channels=None):
+  """Refuses t unless it is a contiguous device uint8 tensor: without n any [n, H, W]; with n, H, W one of [>= n, H, W] (exact: of
+  [n, H, W]), with `channels` as a fourth extent when given."""
+  tail = () if channels is None else (int(channels),)
+  ok = t.dtype == torch.uint8 and t.is_cuda and t.is_contiguous() and t.dim() == 3 + len(tail)
+  if n is None:
+    if not ok:
+      raise ValueError("%s: %s must be a contiguous device uint8 tensor [n, H, W]" % (who, name))
+  elif not ok or (t.shape[0] != n if exact else t.shape[0] < n) or tuple(t.shape[1:]) != (H, W) + tail:
+    raise ValueError("%s: %s must be a contiguous device uint8 [%s%d, %d, %d%s]" % (who, name, "" if exact else ">= ", n, H, W, "".join(", %d" % c for c in tail)))
 
 
 def rows_to_host(pairs):

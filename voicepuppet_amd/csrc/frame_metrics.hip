@@ -22,6 +22,7 @@
 #include <cmath>
 #include <string>
 
+#include "frame_args.h"
 #include "workspace.h"
 
 namespace vp {
@@ -204,12 +205,7 @@ using namespace vp;
 
 static int fm_check(const vp_frame_metrics_desc* d, vp_frame_metrics* h) {
   if (const int rc = check_desc(d, "vp_frame_metrics")) return rc;
-  if (d->max_frames < 1 || d->max_frames > VP_FRAME_METRICS_MAX_FRAMES) {
-    set_err("vp_frame_metrics: bad descriptor (max_frames %d, 1 .. %d)", d->max_frames, VP_FRAME_METRICS_MAX_FRAMES);
-    return VP_ERR_ARG;
-  }
-  if (d->max_height < kFmTaps || d->max_height > 8192) { set_err("vp_frame_metrics: bad descriptor (max_height %d, 11 .. 8192)", d->max_height); return VP_ERR_ARG; }
-  if (d->max_width < kFmTaps || d->max_width > 8192) { set_err("vp_frame_metrics: bad descriptor (max_width %d, 11 .. 8192)", d->max_width); return VP_ERR_ARG; }
+  if (const int rc = check_extents_desc("vp_frame_metrics", d->max_frames, VP_FRAME_METRICS_MAX_FRAMES, d->max_height, d->max_width, kFmTaps, 8192)) return rc;
   h->d = *d;
   return VP_OK;
 }
@@ -226,21 +222,12 @@ static size_t fm_carve(vp_frame_metrics* h, void* base) {
 static int fm_run(vp_frame_metrics* h, const char* who, int elem, const void* a, size_t a_pitch, size_t a_stride, const void* b, size_t b_pitch,
                   size_t b_stride, int n, int H, int W, double scale, double offset, double* out, void* stream) {
   if (!h || !a || !b || !out) { set_err("%s: bad argument (handle, device operands a and b, device out)", who); return VP_ERR_ARG; }
-  const vp_frame_metrics_desc& d = h->d;
   if ((uintptr_t)out & 7) { set_err("%s: out must be on an 8-byte boundary", who); return VP_ERR_ARG; }
-  if (n < 1 || n > d.max_frames) { set_err("%s: n %d outside 1 .. max_frames %d", who, n, d.max_frames); return VP_ERR_ARG; }
-  if (H < kFmTaps || H > d.max_height) { set_err("%s: height %d outside 11 .. max_height %d", who, H, d.max_height); return VP_ERR_ARG; }
-  if (W < kFmTaps || W > d.max_width) { set_err("%s: width %d outside 11 .. max_width %d", who, W, d.max_width); return VP_ERR_ARG; }
+  if (const int rc = check_batch(who, n, H, W, kFmTaps, h->d.max_frames, h->d.max_height, h->d.max_width)) return rc;
   const size_t row = (size_t)W * 3 * elem;
-  const struct { const char* name; const void* p; size_t pitch, stride; } ops[2] = {{"a", a, a_pitch, a_stride}, {"b", b, b_pitch, b_stride}};
+  const struct { const char *name, *prefix; const void* p; size_t pitch, stride; } ops[2] = {{"a", "a_", a, a_pitch, a_stride}, {"b", "b_", b, b_pitch, b_stride}};
   for (const auto& o : ops) {
-    if (o.pitch > ((size_t)1 << 40)) { set_err("%s: %s_row_pitch %zu is over 2^40 bytes", who, o.name, o.pitch); return VP_ERR_ARG; }
-    if (o.stride > ((size_t)1 << 48)) { set_err("%s: %s_frame_stride %zu is over 2^48 bytes", who, o.name, o.stride); return VP_ERR_ARG; }
-    if (o.pitch < row) { set_err("%s: %s_row_pitch %zu is smaller than a row of %zu bytes", who, o.name, o.pitch, row); return VP_ERR_ARG; }
-    if (o.stride < (size_t)(H - 1) * o.pitch + row) {
-      set_err("%s: %s_frame_stride %zu is smaller than a frame ((height - 1) * row_pitch + %zu bytes)", who, o.name, o.stride, row);
-      return VP_ERR_ARG;
-    }
+    if (const int rc = check_pitch(who, o.prefix, o.pitch, o.stride, H, row)) return rc;
     if (elem == 4 && (((uintptr_t)o.p | o.pitch | o.stride) & 3)) {
       set_err("%s: %s, its row_pitch and its frame_stride must be multiples of 4 bytes", who, o.name);
       return VP_ERR_ARG;

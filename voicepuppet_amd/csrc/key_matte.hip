@@ -27,6 +27,8 @@
 #include <cmath>
 #include <string>
 
+#include "frame_args.h"
+#include "vp_common.h"
 #include "workspace.h"
 
 #pragma clang fp contract(off)
@@ -198,9 +200,6 @@ __global__ __launch_bounds__(kKmLanes) void km_key_kernel(const KmApplyArgs g) {
   if (g.raw) g.raw[o] = p;
 }
 
-// clipped window extent around v in 0 .. size - 1
-__device__ __forceinline__ int km_extent(int v, int r, int size) { return min(v + r, size - 1) - max(v - r, 0) + 1; }
-
 // grid (tiles_x, tiles_y, n)
 __global__ __launch_bounds__(kKmLanes) void km_coeff_kernel(const KmApplyArgs g) {
   __shared__ unsigned char sI[kKmEdge][kKmEdge];
@@ -239,7 +238,7 @@ __global__ __launch_bounds__(kKmLanes) void km_coeff_kernel(const KmApplyArgs g)
     if (gx >= g.W || gy >= g.H) continue;
     long long sI_ = 0, sp = 0, sII = 0, sIp = 0;                  // at most 33 * 33 * 255 * 255: the products below need 64 bits
     for (int k = 0; k < taps; ++k) { sI_ += hs[0][ty + k][tx]; sp += hs[1][ty + k][tx]; sII += hs[2][ty + k][tx]; sIp += hs[3][ty + k][tx]; }
-    const long long nw = (long long)km_extent(gx, r, g.W) * km_extent(gy, r, g.H);
+    const long long nw = (long long)window_extent(gx, r, g.W) * window_extent(gy, r, g.H);
     const double a = (double)(sIp * nw - sI_ * sp) / ((double)(sII * nw - sI_ * sI_) + g.eps * (double)(nw * nw));
     const double b = ((double)sp - a * (double)sI_) / (double)nw;
     g.ak[plane + (size_t)gy * g.W + gx] = a;
@@ -286,7 +285,7 @@ __global__ __launch_bounds__(kKmLanes) void km_mean_kernel(const KmApplyArgs g) 
     if (gx >= g.W || gy >= g.H) continue;
     const unsigned char* px = frame + (size_t)gy * g.pitch + 3 * gx;
     const double I = (double)km_guide(px[0], px[1], px[2]);
-    const double nw = (double)(km_extent(gx, r, g.W) * km_extent(gy, r, g.H));
+    const double nw = (double)(window_extent(gx, r, g.W) * window_extent(gy, r, g.H));
     const double v = (acc[0][j] / nw) * I + acc[1][j] / nw;
     g.matte[plane + (size_t)gy * g.W + gx] = (unsigned char)(int)floor(fmin(fmax(v, 0.0), 255.0) + 0.5);
   }
@@ -352,22 +351,8 @@ using namespace vp;
 
 static int km_check(const vp_keymatte_desc* d, vp_keymatte* h) {
   if (const int rc = check_desc(d, "vp_keymatte")) return rc;
-  if (d->max_frames < 1 || d->max_frames > VP_KEYMATTE_MAX_FRAMES) {
-    set_err("vp_keymatte: bad descriptor (max_frames %d, 1 .. %d)", d->max_frames, VP_KEYMATTE_MAX_FRAMES);
-    return VP_ERR_ARG;
-  }
-  if (d->max_height < 16 || d->max_height > VP_KEYMATTE_MAX_SIZE) {
-    set_err("vp_keymatte: bad descriptor (max_height %d, 16 .. %d)", d->max_height, VP_KEYMATTE_MAX_SIZE);
-    return VP_ERR_ARG;
-  }
-  if (d->max_width < 16 || d->max_width > VP_KEYMATTE_MAX_SIZE) {
-    set_err("vp_keymatte: bad descriptor (max_width %d, 16 .. %d)", d->max_width, VP_KEYMATTE_MAX_SIZE);
-    return VP_ERR_ARG;
-  }
-  if (d->max_radius < 0 || d->max_radius > VP_KEYMATTE_MAX_RADIUS) {
-    set_err("vp_keymatte: bad descriptor (max_radius %d, 0 .. %d)", d->max_radius, VP_KEYMATTE_MAX_RADIUS);
-    return VP_ERR_ARG;
-  }
+  if (const int rc = check_extents_desc("vp_keymatte", d->max_frames, VP_KEYMATTE_MAX_FRAMES, d->max_height, d->max_width, 16, VP_KEYMATTE_MAX_SIZE)) return rc;
+  if (const int rc = check_radius_desc("vp_keymatte", d->max_radius, 0, VP_KEYMATTE_MAX_RADIUS)) return rc;
   h->d = *d;
   return VP_OK;
 }
@@ -385,19 +370,8 @@ static size_t km_carve(vp_keymatte* h, void* base) {
 // what fit and apply share: the handle, the frames and their layout
 static int km_frames(const vp_keymatte* h, const char* who, const void* frames, size_t pitch, size_t stride, int n, int H, int W) {
   if (!h || !frames) { set_err("%s: bad argument (handle, device frames)", who); return VP_ERR_ARG; }
-  const vp_keymatte_desc& d = h->d;
-  if (n < 1 || n > d.max_frames) { set_err("%s: n %d outside 1 .. max_frames %d", who, n, d.max_frames); return VP_ERR_ARG; }
-  if (H < 16 || H > d.max_height) { set_err("%s: height %d outside 16 .. max_height %d", who, H, d.max_height); return VP_ERR_ARG; }
-  if (W < 16 || W > d.max_width) { set_err("%s: width %d outside 16 .. max_width %d", who, W, d.max_width); return VP_ERR_ARG; }
-  const size_t row = (size_t)W * 3;
-  if (pitch > ((size_t)1 << 40)) { set_err("%s: row_pitch %zu is over 2^40 bytes", who, pitch); return VP_ERR_ARG; }
-  if (stride > ((size_t)1 << 48)) { set_err("%s: frame_stride %zu is over 2^48 bytes", who, stride); return VP_ERR_ARG; }
-  if (pitch < row) { set_err("%s: row_pitch %zu is smaller than a row of %zu bytes", who, pitch, row); return VP_ERR_ARG; }
-  if (stride < (size_t)(H - 1) * pitch + row) {
-    set_err("%s: frame_stride %zu is smaller than a frame ((height - 1) * row_pitch + %zu bytes)", who, stride, row);
-    return VP_ERR_ARG;
-  }
-  return VP_OK;
+  if (const int rc = check_batch(who, n, H, W, 16, h->d.max_frames, h->d.max_height, h->d.max_width)) return rc;
+  return check_pitch(who, "", pitch, stride, H, (size_t)W * 3);
 }
 
 extern "C" {

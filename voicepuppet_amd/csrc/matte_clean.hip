@@ -26,6 +26,7 @@
 
 #include <string>
 
+#include "frame_args.h"
 #include "matte_clean_core.h"
 #include "workspace.h"
 
@@ -311,18 +312,7 @@ using namespace vp;
 
 static int mc_check(const vp_matteclean_desc* d, vp_matteclean* h) {
   if (const int rc = check_desc(d, "vp_matteclean")) return rc;
-  if (d->max_frames < 1 || d->max_frames > VP_MATTECLEAN_MAX_FRAMES) {
-    set_err("vp_matteclean: bad descriptor (max_frames %d, 1 .. %d)", d->max_frames, VP_MATTECLEAN_MAX_FRAMES);
-    return VP_ERR_ARG;
-  }
-  if (d->max_height < 16 || d->max_height > VP_MATTECLEAN_MAX_SIZE) {
-    set_err("vp_matteclean: bad descriptor (max_height %d, 16 .. %d)", d->max_height, VP_MATTECLEAN_MAX_SIZE);
-    return VP_ERR_ARG;
-  }
-  if (d->max_width < 16 || d->max_width > VP_MATTECLEAN_MAX_SIZE) {
-    set_err("vp_matteclean: bad descriptor (max_width %d, 16 .. %d)", d->max_width, VP_MATTECLEAN_MAX_SIZE);
-    return VP_ERR_ARG;
-  }
+  if (const int rc = check_extents_desc("vp_matteclean", d->max_frames, VP_MATTECLEAN_MAX_FRAMES, d->max_height, d->max_width, 16, VP_MATTECLEAN_MAX_SIZE)) return rc;
   h->d = *d;
   h->height = d->max_height;
   h->width = d->max_width;
@@ -358,10 +348,7 @@ int vp_matteclean_clean(vp_matteclean_t* h, const unsigned char* matte, int n, i
                         int max_hole, int grow, int keep, const int* anchors, int k, unsigned char* out, void* stream) {
   const char* who = "vp_matteclean_clean";
   if (!h || !matte || !out) { set_err("%s: bad argument (handle, device matte, device out)", who); return VP_ERR_ARG; }
-  const vp_matteclean_desc& d = h->d;
-  if (n < 1 || n > d.max_frames) { set_err("%s: n %d outside 1 .. max_frames %d", who, n, d.max_frames); return VP_ERR_ARG; }
-  if (height < 16 || height > d.max_height) { set_err("%s: height %d outside 16 .. max_height %d", who, height, d.max_height); return VP_ERR_ARG; }
-  if (width < 16 || width > d.max_width) { set_err("%s: width %d outside 16 .. max_width %d", who, width, d.max_width); return VP_ERR_ARG; }
+  if (const int rc = check_batch(who, n, height, width, 16, h->d.max_frames, h->d.max_height, h->d.max_width)) return rc;
   if (support < 1 || support > 255) { set_err("%s: support %d outside 1 .. 255", who, support); return VP_ERR_ARG; }
   if (core < 1 || core > 255) { set_err("%s: core %d outside 1 .. 255", who, core); return VP_ERR_ARG; }
   const int pixels = height * width;                              // at most 2^20
@@ -372,8 +359,7 @@ int vp_matteclean_clean(vp_matteclean_t* h, const unsigned char* matte, int n, i
   if (k < 0 || k > VP_MATTECLEAN_MAX_ANCHORS) { set_err("%s: k %d anchors outside 0 .. %d", who, k, VP_MATTECLEAN_MAX_ANCHORS); return VP_ERR_ARG; }
   if (k > 0 && !anchors) { set_err("%s: bad argument (device anchors with k %d)", who, k); return VP_ERR_ARG; }
   // in place works because every launch reads and writes a pixel's own byte only; at a shifted address it would not
-  const size_t bytes = (size_t)n * pixels;
-  if (out != matte && (uintptr_t)out < (uintptr_t)matte + bytes && (uintptr_t)matte < (uintptr_t)out + bytes) {
+  if (out != matte && overlaps(out, matte, (size_t)n * pixels)) {
     set_err("%s: out overlaps the matte at another address (identical or disjoint buffers only)", who);
     return VP_ERR_ARG;
   }

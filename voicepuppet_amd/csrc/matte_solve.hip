@@ -33,6 +33,8 @@
 #include <cmath>
 #include <string>
 
+#include "frame_args.h"
+#include "vp_common.h"
 #include "workspace.h"
 
 #pragma clang fp contract(off)
@@ -74,8 +76,6 @@ struct MsArgs {
   double eps, tol2;
   int H, W, radius, it, iters, tiles;
 };
-
-__device__ __forceinline__ int ms_extent(int v, int r, int size) { return min(v + r, size - 1) - max(v - r, 0) + 1; }
 
 // MOMENTS of the header for the window centred on (lx, ly) of the staged bytes (0 outside the image, so every sum is the clipped
 // window's); nw its pixel count.  With kP also the sums of p and I p over it, rows in increasing y, within a row increasing x.
@@ -155,7 +155,7 @@ __device__ __forceinline__ void ms_apply(const MsArgs& g, const unsigned char* s
       const int cx = wx - r, cy = half * kMsHalf - r + wy, gx = x0 + cx, gy = y0 + cy;
       double a0 = 0.0, a1 = 0.0, a2 = 0.0, b = 0.0;
       if (gx >= 0 && gx < g.W && gy >= 0 && gy < g.H) {
-        const int nw = ms_extent(gx, r, g.W) * ms_extent(gy, r, g.H);
+        const int nw = window_extent(gx, r, g.W) * window_extent(gy, r, g.H);
         double mu[3], inv[6], s[4];
         if (kStored) {
           const double* m = g.mom + plane0 + (size_t)gy * g.W + gx;
@@ -189,7 +189,7 @@ __device__ __forceinline__ void ms_apply(const MsArgs& g, const unsigned char* s
           }
         const int at = (ty + 2 * r) * E + tx + 2 * r;
         const double I0 = (double)sI[at], I1 = (double)sI[E * E + at], I2 = (double)sI[2 * E * E + at];
-        const double nd = (double)(ms_extent(gx, r, g.W) * ms_extent(gy, r, g.H));
+        const double nd = (double)(window_extent(gx, r, g.W) * window_extent(gy, r, g.H));
         out = nd * sp[at] - (((sa0 * I0 + sa1 * I1) + sa2 * I2) + sb);
       }
       lp[2 * half + j] = out;
@@ -311,7 +311,7 @@ __global__ __launch_bounds__(kMsLanes) void ms_init_kernel(const MsArgs g) {
         for (int dx = -r; dx <= r; ++dx) {
           const int jx = gx + dx, jy = gy + dy;
           if (jx < 0 || jx >= g.W || jy < 0 || jy >= g.H) continue;
-          const int nw = ms_extent(jx, r, g.W) * ms_extent(jy, r, g.H);
+          const int nw = window_extent(jx, r, g.W) * window_extent(jy, r, g.H);
           double mu[3], inv[6];
           ms_window<false>(sI, nullptr, E, tx + 2 * r + dx, ty + 2 * r + dy, r, nw, g.eps, mu, inv, nullptr);
           const double d0 = I0 - mu[0], d1 = I1 - mu[1], d2 = I2 - mu[2];
@@ -355,7 +355,7 @@ __global__ __launch_bounds__(kMsLanes) void ms_moments_kernel(const MsArgs g) {
     const int gx = x0 + tx, gy = y0 + ty;
     if (gx >= g.W || gy >= g.H) continue;
     double mu[3], inv[6];
-    ms_window<false>(sI, nullptr, E, tx + 2 * r, ty + 2 * r, r, ms_extent(gx, r, g.W) * ms_extent(gy, r, g.H), g.eps, mu, inv, nullptr);
+    ms_window<false>(sI, nullptr, E, tx + 2 * r, ty + 2 * r, r, window_extent(gx, r, g.W) * window_extent(gy, r, g.H), g.eps, mu, inv, nullptr);
     double* m = g.mom + (size_t)f * g.H * g.W + (size_t)gy * g.W + gx;
     for (int c = 0; c < 3; ++c) m[c * g.mcap] = mu[c];
     for (int c = 0; c < 6; ++c) m[(3 + c) * g.mcap] = inv[c];
@@ -543,22 +543,8 @@ using namespace vp;
 
 static int ms_check(const vp_mattesolve_desc* d, vp_mattesolve* h) {
   if (const int rc = check_desc(d, "vp_mattesolve")) return rc;
-  if (d->max_frames < 1 || d->max_frames > VP_MATTESOLVE_MAX_FRAMES) {
-    set_err("vp_mattesolve: bad descriptor (max_frames %d, 1 .. %d)", d->max_frames, VP_MATTESOLVE_MAX_FRAMES);
-    return VP_ERR_ARG;
-  }
-  if (d->max_height < 16 || d->max_height > VP_MATTESOLVE_MAX_SIZE) {
-    set_err("vp_mattesolve: bad descriptor (max_height %d, 16 .. %d)", d->max_height, VP_MATTESOLVE_MAX_SIZE);
-    return VP_ERR_ARG;
-  }
-  if (d->max_width < 16 || d->max_width > VP_MATTESOLVE_MAX_SIZE) {
-    set_err("vp_mattesolve: bad descriptor (max_width %d, 16 .. %d)", d->max_width, VP_MATTESOLVE_MAX_SIZE);
-    return VP_ERR_ARG;
-  }
-  if (d->max_radius < 1 || d->max_radius > VP_MATTESOLVE_MAX_RADIUS) {
-    set_err("vp_mattesolve: bad descriptor (max_radius %d, 1 .. %d)", d->max_radius, VP_MATTESOLVE_MAX_RADIUS);
-    return VP_ERR_ARG;
-  }
+  if (const int rc = check_extents_desc("vp_mattesolve", d->max_frames, VP_MATTESOLVE_MAX_FRAMES, d->max_height, d->max_width, 16, VP_MATTESOLVE_MAX_SIZE)) return rc;
+  if (const int rc = check_radius_desc("vp_mattesolve", d->max_radius, 1, VP_MATTESOLVE_MAX_RADIUS)) return rc;
   h->d = *d;
   h->max_tiles = ((d->max_height + kMsTile - 1) / kMsTile) * ((d->max_width + kMsTile - 1) / kMsTile);
   h->height = h->tile_height = d->max_height;
@@ -584,25 +570,14 @@ static size_t ms_carve(vp_mattesolve* h, void* base) {
 }
 
 static int ms_size(const vp_mattesolve* h, const char* who, int n, int H, int W) {
-  const vp_mattesolve_desc& d = h->d;
-  if (n < 1 || n > d.max_frames) { set_err("%s: n %d outside 1 .. max_frames %d", who, n, d.max_frames); return VP_ERR_ARG; }
-  if (H < 16 || H > d.max_height) { set_err("%s: height %d outside 16 .. max_height %d", who, H, d.max_height); return VP_ERR_ARG; }
-  if (W < 16 || W > d.max_width) { set_err("%s: width %d outside 16 .. max_width %d", who, W, d.max_width); return VP_ERR_ARG; }
-  return VP_OK;
+  return check_batch(who, n, H, W, 16, h->d.max_frames, h->d.max_height, h->d.max_width);
 }
 
 // what solve and laplacian share: the handle, the frames and their layout, radius and eps
 static int ms_frames(const vp_mattesolve* h, const char* who, const void* frames, size_t pitch, size_t stride, int n, int H, int W, int radius, double eps) {
   if (!h || !frames) { set_err("%s: bad argument (handle, device frames)", who); return VP_ERR_ARG; }
   if (const int rc = ms_size(h, who, n, H, W)) return rc;
-  const size_t row = (size_t)W * 3;
-  if (pitch > ((size_t)1 << 40)) { set_err("%s: row_pitch %zu is over 2^40 bytes", who, pitch); return VP_ERR_ARG; }
-  if (stride > ((size_t)1 << 48)) { set_err("%s: frame_stride %zu is over 2^48 bytes", who, stride); return VP_ERR_ARG; }
-  if (pitch < row) { set_err("%s: row_pitch %zu is smaller than a row of %zu bytes", who, pitch, row); return VP_ERR_ARG; }
-  if (stride < (size_t)(H - 1) * pitch + row) {
-    set_err("%s: frame_stride %zu is smaller than a frame ((height - 1) * row_pitch + %zu bytes)", who, stride, row);
-    return VP_ERR_ARG;
-  }
+  if (const int rc = check_pitch(who, "", pitch, stride, H, (size_t)W * 3)) return rc;
   if (radius < 1 || radius > h->d.max_radius) { set_err("%s: radius %d outside 1 .. max_radius %d", who, radius, h->d.max_radius); return VP_ERR_ARG; }
   if (!(std::isfinite(eps) && eps > 0.0)) { set_err("%s: eps must be finite and positive", who); return VP_ERR_ARG; }
   return VP_OK;
@@ -637,8 +612,7 @@ int vp_mattesolve_trimap(vp_mattesolve_t* h, const unsigned char* matte, int n, 
   if (dilate == 0) dilate = side / 29 < 5 ? 5 : (side / 29 > VP_MATTESOLVE_MAX_SQUARE ? VP_MATTESOLVE_MAX_SQUARE : side / 29);
   if (erode < 1 || erode > VP_MATTESOLVE_MAX_SQUARE) { set_err("%s: erode %d outside 1 .. %d (or 0: the default)", who, erode, VP_MATTESOLVE_MAX_SQUARE); return VP_ERR_ARG; }
   if (dilate < 1 || dilate > VP_MATTESOLVE_MAX_SQUARE) { set_err("%s: dilate %d outside 1 .. %d (or 0: the default)", who, dilate, VP_MATTESOLVE_MAX_SQUARE); return VP_ERR_ARG; }
-  const size_t bytes = (size_t)n * height * width;
-  if ((uintptr_t)out < (uintptr_t)matte + bytes && (uintptr_t)matte < (uintptr_t)out + bytes) {
+  if (overlaps(out, matte, (size_t)n * height * width)) {
     set_err("%s: out overlaps the matte (a tile reads its neighbours' pixels)", who);
     return VP_ERR_ARG;
   }
@@ -663,8 +637,7 @@ int vp_mattesolve_solve(vp_mattesolve_t* h, const unsigned char* frames, size_t 
   if (iters < 1 || iters > VP_MATTESOLVE_MAX_ITERS) { set_err("%s: iters %d outside 1 .. %d", who, iters, VP_MATTESOLVE_MAX_ITERS); return VP_ERR_ARG; }
   if (!(std::isfinite(tol) && tol >= 0.0)) { set_err("%s: tol must be finite and not negative", who); return VP_ERR_ARG; }
   // in place works because the finish launch reads and writes a pixel's own byte only; at a shifted address it would not
-  const size_t bytes = (size_t)n * height * width;
-  if (matte != trimap && (uintptr_t)matte < (uintptr_t)trimap + bytes && (uintptr_t)trimap < (uintptr_t)matte + bytes) {
+  if (matte != trimap && overlaps(matte, trimap, (size_t)n * height * width)) {
     set_err("%s: matte overlaps the trimap at another address (identical or disjoint buffers only)", who);
     return VP_ERR_ARG;
   }
@@ -705,8 +678,7 @@ int vp_mattesolve_laplacian(vp_mattesolve_t* h, const unsigned char* frames, siz
   const char* who = "vp_mattesolve_laplacian";
   if (const int rc = ms_frames(h, who, frames, row_pitch, frame_stride, n, height, width, radius, eps)) return rc;
   if (!p || !out || ((uintptr_t)p & 7) || ((uintptr_t)out & 7)) { set_err("%s: bad argument (device p, device out, on 8-byte boundaries)", who); return VP_ERR_ARG; }
-  const size_t bytes = (size_t)n * height * width * sizeof(double);
-  if ((uintptr_t)out < (uintptr_t)p + bytes && (uintptr_t)p < (uintptr_t)out + bytes) {
+  if (overlaps(out, p, (size_t)n * height * width * sizeof(double))) {
     set_err("%s: out overlaps p (a tile reads its neighbours' pixels)", who);
     return VP_ERR_ARG;
   }

@@ -116,6 +116,9 @@ __device__ __forceinline__ int tile_chan0(int rowperm, int T, int q) {
   return rowperm ? ((T >> 2) << 6) + (((T >> 1) & 1) << 5) + (q << 3) + ((T & 1) << 2) : T * 16 + 4 * q;
 }
 
+// pixels of the window v - r .. v + r that lie in 0 .. size - 1 (the guided filter's and the matting Laplacian's clipped windows)
+__device__ __forceinline__ int window_extent(int v, int r, int size) { return min(v + r, size - 1) - max(v - r, 0) + 1; }
+
 // wave64 butterfly sum
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -2,6 +2,7 @@
 // is xxx_check (the descriptor), xxx_carve (the workspace -> typed pointers in the handle) and its kernels:
 //   *_workspace_bytes:  xxx_check, then xxx_carve on a stack handle with a null base;
 //   *_create:           open_handle, which runs both, refuses a short workspace and carves the heap handle on the real base.
+// The argument checks that the image families' descriptors and calls share (extents, pitch and stride, overlap) are in frame_args.h.
 #pragma once
 #include <stdint.h>
 

@@ -250,52 +250,36 @@ def parse_options(argv=None):
   return opts, args
 
 
-def main(argv=None):
-  opts, _ = parse_options(argv)
-  if opts.clip_dir is None or opts.landmarks is None or opts.out_dir is None:
-    logger.error('Please check your parameters: --clip_dir, --landmarks and --out_dir are needed.')
-    exit(0)
-  from voicepuppet_amd.bfmnet.fit_landmarks import BFM_MAT, LM3D_MAT, _BFM, read_landmarks, reprojection_error, summary_line
-  if not (os.path.exists(BFM_MAT) and os.path.exists(LM3D_MAT)):
-    logger.error('%s and %s are needed', BFM_MAT, LM3D_MAT)
-    exit(0)
-  if opts.frame_batch < 1:
-    raise SystemExit('--frame_batch must be at least 1')
-  import torch
-  from scipy.io import loadmat
-  from voicepuppet_amd.bfmfit import FaceFitter, crop_alignment, photo_affine, preprocess_landmarks
-  from voicepuppet_amd.pixrefer.infer_bfmvid import paste_geometry
-  from voicepuppet_amd.triptych import STATUS, TriptychBuilder
-  from voicepuppet_amd.utils.reconstruct_mesh import ClipRenderer
-
-  frames_n = count_frames(opts.clip_dir)
-  if frames_n < 1:
-    raise SystemExit('%s: no 0.jpg' % opts.clip_dir)
-  with open(opts.landmarks) as f:
+def read_landmarks_for(path, frames_n, clip_dir):
+  """-> (landmarks [frames_n, 68, 2] in pixels of the frames, the file's lines for them)."""
+  from voicepuppet_amd.bfmnet.fit_landmarks import read_landmarks
+  with open(path) as f:
     raw_lines = [line for line in f if line.strip()]
-  lms = read_landmarks(opts.landmarks)
+  lms = read_landmarks(path)
   if lms.shape[0] < frames_n:
-    raise SystemExit('%s has %d lines for the %d frames of %s' % (opts.landmarks, lms.shape[0], frames_n, opts.clip_dir))
-  lms, raw_lines = lms[:frames_n], raw_lines[:frames_n]
-  batch = min(opts.frame_batch, frames_n)
-  try:
-    reader = FrameReader(opts.clip_dir, batch, opts.crop, opts.size)
-  except ValueError as e:
-    raise SystemExit(str(e))
-  S = reader.size
-  lms = reader.landmarks_to_panel(lms)
+    raise SystemExit('%s has %d lines for the %d frames of %s' % (path, lms.shape[0], frames_n, clip_dir))
+  return lms[:frames_n], raw_lines[:frames_n]
 
-  # alignment and paste geometry per frame (host, float64): datasets/make_data_from_GRID.py:193-214 and infer_bfmvid.py:83-86
-  fitter = FaceFitter(_BFM(loadmat(BFM_MAT)))
-  lm3D = loadmat(LM3D_MAT)['lm']
+
+def align_landmarks(lms, S, lm3D):
+  """Alignment and paste geometry per frame (host, float64): datasets/make_data_from_GRID.py:193-214 and infer_bfmvid.py:83-86.
+  -> (aligned landmarks, int64 [frames, 4] geometry)."""
+  from voicepuppet_amd.bfmfit import crop_alignment, preprocess_landmarks
+  from voicepuppet_amd.pixrefer.infer_bfmvid import paste_geometry
   aligned, geometry = [], []
   for lm in lms:
     crop, center_x, center_y, ratio = crop_alignment(lm, S, S)
     lm_new, trans_params = preprocess_landmarks(crop, lm3D)
     aligned.append(lm_new)
     geometry.append(paste_geometry(center_x, center_y, ratio, trans_params, 224))
-  aligned, geometry = np.stack(aligned), np.array(geometry, np.int64)
+  return np.stack(aligned), np.array(geometry, np.int64)
 
+
+def choose_coefficients(opts, fitter, aligned, frames_n, reader, lms, lm3D):
+  """--bfmcoeff, --joint or fit_sequence, then --appearance -> (coeff [frames_n, 257], the fit's report, the summary line's words on
+  the appearance fit)."""
+  import torch
+  from voicepuppet_amd.bfmfit import photo_affine
   if opts.bfmcoeff:
     rows = np.loadtxt(opts.bfmcoeff, delimiter=',', dtype=np.float32, ndmin=2)
     if rows.shape[0] < frames_n or rows.shape[1] != 257:
@@ -308,77 +292,49 @@ def main(argv=None):
     coeff, report = fitter.fit_sequence(aligned, rounds=opts.rounds, id_steps=opts.id_steps)
   extra = ''
   if opts.appearance == 'first':
+    S = reader.size
     frame0 = reader.read(0, 1)[0]
     first, rep = fitter.fit_appearance(coeff[:1], photo=frame0, affine=photo_affine(lms[0], S, S, lm3D),
                                        visibility=opts.appearance_visibility, prefilter=opts.appearance_prefilter)
     coeff = coeff.clone()
     coeff[:, 144:224], coeff[:, 227:254] = first[:, 144:224], first[:, 227:254]
     extra = ', appearance status %d' % int(rep[0, 0].item())
+  return coeff, report, extra
 
-  os.makedirs(opts.out_dir, exist_ok=True)
-  renderer = ClipRenderer(fitter.model)
-  builder = TriptychBuilder(S, batch)
-  status, repeated = [], []
-  keyer, key_report = None, None
+
+def matte_chain(opts, reader, batch, frames_n):
+  """The MatteChain of --key_matte, --clean_matte, --solve_matte and --key_foreground; a stage that refuses its options ends the run in
+  that option's name."""
+  import torch
+  from voicepuppet_amd.matte_chain import MatteChain
+  chain = MatteChain(batch, reader.size, reader.size)
   if opts.key_matte or opts.key_foreground:
-    from voicepuppet_amd.matte import STATUS_TEXT, KeyMatte
     key_n = min(opts.key_frames or batch, frames_n)
     if key_n < 1:
       raise SystemExit('--key_frames must be at least 1')
     try:
-      keyer = KeyMatte(max(batch, key_n), S, S, max_radius=opts.key_radius if opts.key_matte else 0)
-      keyer.fit(torch.cat([reader.read(first, min(batch, key_n - first)) for first in range(0, key_n, batch)]), band=opts.key_band)
+      chain.add_key(torch.cat([reader.read(first, min(batch, key_n - first)) for first in range(0, key_n, batch)]), matte=opts.key_matte,
+                    lo=opts.key_thresholds[0], hi=opts.key_thresholds[1], radius=opts.key_radius, eps=opts.key_eps, band=opts.key_band)
     except (ValueError, RuntimeError) as e:
       raise SystemExit('%s: %s' % ('--key_matte' if opts.key_matte else '--key_foreground', e))
-    key_report = keyer.report()
     if opts.write_alpha:
       os.makedirs(opts.write_alpha, exist_ok=True)
-  cleaner, clean_reports = None, []
   if opts.clean_matte:
-    from voicepuppet_amd.matte_clean import MatteCleaner, summary as clean_summary
-    cleaner = MatteCleaner(batch, S, S)
-    cleaned = torch.empty(batch, S, S, dtype=torch.uint8, device='cuda')
-    anchors = torch.from_numpy(np.floor(lms).astype(np.int32)).cuda()       # the panel landmarks' pixels
-  solver, solve_reports = None, []
+    chain.add_clean(support=opts.clean_support, core=opts.clean_core, min_area=opts.clean_min_area, max_hole=opts.clean_max_hole,
+                    grow=opts.clean_grow, keep=opts.clean_keep)
   if opts.solve_matte:
-    from voicepuppet_amd.matte_solve import MatteSolver, summary as solve_summary
     try:
-      solver = MatteSolver(batch, S, S, max_radius=opts.solve_radius)
+      chain.add_solve(erode=opts.solve_erode, dilate=opts.solve_dilate, radius=opts.solve_radius, eps=opts.solve_eps, iters=opts.solve_iters,
+                      tol=opts.solve_tol)
     except ValueError as e:
       raise SystemExit('--solve_matte: %s' % e)
-    trimap, solved = (torch.empty(batch, S, S, dtype=torch.uint8, device='cuda') for _ in range(2))
-  try:
-    for first in range(0, frames_n, batch):
-      n = min(batch, frames_n - first)
-      frames = reader.read(first, n)
-      render, face_mask = renderer.render_view(coeff[first:first + n], view=0)
-      alpha = read_alpha(reader, opts.alpha_dir, first, n) if opts.alpha_dir else None
-      if opts.key_matte:
-        alpha = keyer.matte(frames, lo=opts.key_thresholds[0], hi=opts.key_thresholds[1], radius=opts.key_radius, eps=opts.key_eps)
-      if cleaner is not None:
-        alpha = cleaner.clean(alpha.contiguous(), support=opts.clean_support, core=opts.clean_core, min_area=opts.clean_min_area,
-                              max_hole=opts.clean_max_hole, grow=opts.clean_grow, keep=opts.clean_keep, anchors=anchors[first:first + n], out=cleaned)
-        clean_reports.append(cleaner.report())
-      if solver is not None:
-        tri = solver.trimap(alpha.contiguous(), erode=opts.solve_erode, dilate=opts.solve_dilate, out=trimap)
-        alpha = solver.solve(frames, tri, radius=opts.solve_radius, eps=opts.solve_eps, iters=opts.solve_iters, tol=opts.solve_tol, out=solved)
-        solve_reports.append(solver.report())
-      if opts.write_alpha:
-        keyer.write_png(alpha, opts.write_alpha, first)
-      if opts.key_foreground:
-        frames = keyer.foreground(frames, alpha.contiguous(), despill=opts.key_despill)
-      trip, st = builder.build(frames, render, face_mask, geometry[first:first + n], alpha=alpha)
-      repeated += builder.write(trip, st, opts.out_dir, first)
-      status.append(st.cpu().numpy())
-  except ValueError as e:
-    raise SystemExit('%s: %s' % (opts.clip_dir, e))
-  finally:
-    if cleaner is not None:
-      cleaner.close()
-    if solver is not None:
-      solver.close()
-  status = np.concatenate(status)
+  if opts.key_foreground:
+    chain.add_foreground(despill=opts.key_despill)
+  return chain
 
+
+def write_lists(opts, coeff, raw_lines, frames_n):
+  """out_dir/bfmcoeff.txt, out_dir/ear.txt and the line of --list."""
   np.savetxt(os.path.join(opts.out_dir, 'bfmcoeff.txt'), coeff.cpu().numpy(), delimiter=',', fmt='%.8g')
   with open(os.path.join(opts.out_dir, 'ear.txt'), 'w') as f:
     for line in raw_lines:
@@ -386,41 +342,78 @@ def main(argv=None):
   if opts.list:
     with open(opts.list, 'a') as f:
       f.write('%s|%d\n' % (opts.out_dir, frames_n))
+
+
+def main(argv=None):
+  opts, _ = parse_options(argv)
+  if opts.clip_dir is None or opts.landmarks is None or opts.out_dir is None:
+    logger.error('Please check your parameters: --clip_dir, --landmarks and --out_dir are needed.')
+    exit(0)
+  from voicepuppet_amd.bfmnet.fit_landmarks import BFM_MAT, LM3D_MAT, _BFM, reprojection_error, summary_line
+  if not (os.path.exists(BFM_MAT) and os.path.exists(LM3D_MAT)):
+    logger.error('%s and %s are needed', BFM_MAT, LM3D_MAT)
+    exit(0)
+  if opts.frame_batch < 1:
+    raise SystemExit('--frame_batch must be at least 1')
+  import torch
+  from scipy.io import loadmat
+  from voicepuppet_amd.bfmfit import FaceFitter
+  from voicepuppet_amd.triptych import STATUS, TriptychBuilder
+  from voicepuppet_amd.utils.reconstruct_mesh import ClipRenderer
+
+  frames_n = count_frames(opts.clip_dir)
+  if frames_n < 1:
+    raise SystemExit('%s: no 0.jpg' % opts.clip_dir)
+  lms, raw_lines = read_landmarks_for(opts.landmarks, frames_n, opts.clip_dir)
+  batch = min(opts.frame_batch, frames_n)
+  try:
+    reader = FrameReader(opts.clip_dir, batch, opts.crop, opts.size)
+  except ValueError as e:
+    raise SystemExit(str(e))
+  S = reader.size
+  lms = reader.landmarks_to_panel(lms)
+  fitter = FaceFitter(_BFM(loadmat(BFM_MAT)))
+  lm3D = loadmat(LM3D_MAT)['lm']
+  aligned, geometry = align_landmarks(lms, S, lm3D)
+  coeff, report, extra = choose_coefficients(opts, fitter, aligned, frames_n, reader, lms, lm3D)
+
+  os.makedirs(opts.out_dir, exist_ok=True)
+  renderer = ClipRenderer(fitter.model)
+  builder = TriptychBuilder(S, batch)
+  status, repeated = [], []
+  chain = matte_chain(opts, reader, batch, frames_n)
+  anchors = torch.from_numpy(np.floor(lms).astype(np.int32)).cuda() if opts.clean_matte else None     # the panel landmarks' pixels
+  try:
+    for first in range(0, frames_n, batch):
+      n = min(batch, frames_n - first)
+      frames = reader.read(first, n)
+      render, face_mask = renderer.render_view(coeff[first:first + n], view=0)
+      alpha = read_alpha(reader, opts.alpha_dir, first, n) if opts.alpha_dir else None
+      frames, alpha = chain.run(frames, alpha, anchors[first:first + n] if anchors is not None else None)
+      if opts.write_alpha:
+        chain.write_alpha(alpha, opts.write_alpha, first)
+      trip, st = builder.build(frames, render, face_mask, geometry[first:first + n], alpha=alpha)
+      repeated += builder.write(trip, st, opts.out_dir, first)
+      status.append(st.cpu().numpy())
+  except ValueError as e:
+    raise SystemExit('%s: %s' % (opts.clip_dir, e))
+  finally:
+    chain.close()
+  status = np.concatenate(status)
+
+  write_lists(opts, coeff, raw_lines, frames_n)
   counts = ' '.join('%d:%d' % (s, int((status == s).sum())) for s in sorted(set(status.tolist())))
   for s in sorted(set(status.tolist()) - {0}):
     logger.warning('triptych status %d: %s', s, STATUS.get(s, '?'))
-  if key_report is not None and opts.key_matte:
-    extra += '; key matte: kept %.2f, residual %.1f levels' % (key_report['kept'], key_report['residual_rms'])
-    if key_report['status'] != 0:
-      logger.warning('key matte status %d: %s', key_report['status'], STATUS_TEXT.get(key_report['status'], '?'))
-    if key_report['kept'] < 0.5:
-      logger.warning('key matte: the robust pass kept %.2f of the border samples: the border is not a plain backdrop', key_report['kept'])
-  if cleaner is not None:
-    clean_reports = np.concatenate(clean_reports)
-    extra += '; clean: ' + clean_summary(clean_reports)
-    if (clean_reports[:, 6] & 1).any():
-      logger.warning('matte clean: no component of %d frames held a landmark or reached the bottom edge; they were left as they were',
-                     int((clean_reports[:, 6] & 1).sum()))
-    if (clean_reports[:, 6] & 2).any():
-      raise SystemExit('matte clean: the labelling reached a step cap (a bug); the mattes are not to be used')
-  if solver is not None:
-    solve_reports = {k: np.concatenate([r[k] for r in solve_reports]) for k in solve_reports[0]}
-    text, flagged, capped = solve_summary(solve_reports, opts.solve_iters, opts.solve_tol)
-    extra += '; ' + text
-    if flagged:
-      logger.warning('matte solve: %d frames ended with a status bit set (1: nothing to solve or no constraint reaches the band; 2: the '
-                     'iteration broke down)', flagged)
-    if capped:
-      logger.warning('matte solve: %d frames ran all %d iterations without reaching the residual %g', capped, opts.solve_iters, opts.solve_tol)
+  text, warnings, fatal = chain.summary()
+  for w in warnings:
+    logger.warning('%s', w)
+  if fatal:
+    raise SystemExit(fatal)
   fit = summary_line(opts.clip_dir, report, reprojection_error(fitter, coeff, aligned))
-  print('%s; triptych status %s, %d repeated, %d read with PIL%s' % (fit, counts, len(repeated), reader.fallbacks, extra))
+  print('%s; triptych status %s, %d repeated, %d read with PIL%s' % (fit, counts, len(repeated), reader.fallbacks, extra + text))
   res = {'frames': frames_n, 'status': status, 'repeated': repeated, 'geometry': geometry}
-  if key_report is not None:
-    res['key_matte'] = key_report
-  if cleaner is not None:
-    res['clean'] = clean_reports
-  if solver is not None:
-    res['solve'] = solve_reports
+  res.update(chain.reports())
   return res
 
 

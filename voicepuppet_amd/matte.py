@@ -18,8 +18,7 @@ import os
 import torch
 
 from . import _lib
-from ._handle import Handle, ptr, stream
-from .metrics import FrameMetrics
+from ._handle import Handle, ptr, rgb_frames, stream, u8_plane
 
 MODEL_DOUBLES = _lib.KEYMATTE_MODEL_DOUBLES
 # the model record's fields (include/vp_hip.h): 9 plane numbers, 6 of the inverse covariance, then these
@@ -56,18 +55,11 @@ class KeyMatte(Handle):
     self.max_frames, self.max_height, self.max_width, self.max_radius = int(max_frames), int(max_height), int(max_width), int(max_radius)
     self._png = None
 
-  @staticmethod
-  def _frames(frames, who):
-    if frames.dim() != 4 or frames.shape[3] != 3 or frames.dtype != torch.uint8 or not frames.is_cuda:
-      raise ValueError("%s: a device uint8 tensor [n, H, W, 3]" % who)
-    pitch, stride = FrameMetrics._layout(frames, "frames")
-    return pitch, stride, int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
-
   def fit(self, frames, band=None, side_rows=None, trim=16.0, sigma_min=2.0):
     """The backdrop model from the border of `frames` (all of them in one call): band rows at the top and band columns at both sides of
     the first side_rows rows; defaults max(2, H // 16) and H // 2.  Two passes, the second over the samples within `trim` (a squared
     distance in standard deviations) of the first.  Returns self."""
-    pitch, stride, n, H, W = self._frames(frames, "fit")
+    pitch, stride, n, H, W = rgb_frames(frames, "fit")
     rc = self.L.vp_keymatte_fit(self.h, ptr(frames), pitch, stride, n, H, W, 0 if band is None else int(band),
                                 0 if side_rows is None else int(side_rows), float(trim), float(sigma_min), stream())
     _lib.check(rc, "vp_keymatte_fit")
@@ -97,13 +89,12 @@ class KeyMatte(Handle):
     """-> device uint8 [n, H, W]: 0 on the backdrop, 255 on the subject.  lo, hi: the key's ramp in standard deviations of the backdrop;
     radius, eps: the guided filter's window and regulariser (grey levels squared); radius 0 returns the raw key.  out, raw: contiguous
     device uint8 [>= n, H, W] to write the matte and the raw key into."""
-    pitch, stride, n, H, W = self._frames(frames, "matte")
+    pitch, stride, n, H, W = rgb_frames(frames, "matte")
     if out is None:
       out = torch.empty(max(n, 1), H, W, dtype=torch.uint8, device="cuda")
     for name, t in (("out", out), ("raw", raw)):
-      if t is not None and (t.dtype != torch.uint8 or not t.is_cuda or not t.is_contiguous() or t.dim() != 3 or t.shape[0] < n
-                            or tuple(t.shape[1:]) != (H, W)):
-        raise ValueError("matte: %s must be a contiguous device uint8 [>= %d, %d, %d]" % (name, n, H, W))
+      if t is not None:
+        u8_plane(t, "matte", name, n, H, W)
     rc = self.L.vp_keymatte_apply(self.h, ptr(frames), pitch, stride, n, H, W, float(lo), float(hi), int(radius), float(eps), ptr(raw), ptr(out),
                                   stream())
     _lib.check(rc, "vp_keymatte_apply")
@@ -115,14 +106,12 @@ class KeyMatte(Handle):
     edge is the subject's colour, not a fringe of the backdrop's.  despill (0 .. 1) also pulls the backdrop's key channel down to the
     mean of the other two where it exceeds it - only when that channel leads by 16 grey levels at the frame's centre; spill() says
     whether it does.  matte: contiguous device uint8 [n, H, W] (KeyMatte's own or a cleaned one); out: contiguous [>= n, H, W, 3]."""
-    pitch, stride, n, H, W = self._frames(frames, "foreground")
-    if matte.dtype != torch.uint8 or not matte.is_cuda or not matte.is_contiguous() or tuple(matte.shape) != (n, H, W):
-      raise ValueError("foreground: matte must be a contiguous device uint8 [%d, %d, %d]" % (n, H, W))
+    pitch, stride, n, H, W = rgb_frames(frames, "foreground")
+    u8_plane(matte, "foreground", "matte", n, H, W, exact=True)
     if out is None:
       out = torch.empty(max(n, 1), H, W, 3, dtype=torch.uint8, device="cuda")
-    elif (out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous() or out.dim() != 4 or out.shape[0] < n
-          or tuple(out.shape[1:]) != (H, W, 3)):
-      raise ValueError("foreground: out must be a contiguous device uint8 [>= %d, %d, %d, 3]" % (n, H, W))
+    else:
+      u8_plane(out, "foreground", "out", n, H, W, channels=3)
     rc = self.L.vp_key_foreground(self.h, ptr(frames), pitch, stride, n, H, W, ptr(matte), float(despill), ptr(out), stream())
     _lib.check(rc, "vp_key_foreground")
     return out[:n]

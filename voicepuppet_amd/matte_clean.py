@@ -14,7 +14,7 @@ import ctypes
 import torch
 
 from . import _lib
-from ._handle import Handle, ptr, stream
+from ._handle import Handle, ptr, stream, u8_plane
 
 REPORT_FIELDS = ("components", "kept", "pixels_removed", "pixels_zeroed", "holes_filled", "pixels_filled", "status")
 STATUS_ALL_KEPT, STATUS_CAP = 1, 2
@@ -51,8 +51,7 @@ class MatteCleaner(Handle):
     Chebyshev) of a kept component.  Then the 4-connected components of {result < core} that touch no frame edge and have at most
     max_hole pixels become 255; max_hole=0 skips that.  Defaults: min_area H * W // 1024, max_hole H * W // 256; all defaults are
     untuned on real footage.  out: a contiguous device uint8 [>= n, H, W]."""
-    if matte.dim() != 3 or matte.dtype != torch.uint8 or not matte.is_cuda or not matte.is_contiguous():
-      raise ValueError("clean: matte must be a contiguous device uint8 tensor [n, H, W]")
+    u8_plane(matte, "clean", "matte")
     n, H, W = (int(v) for v in matte.shape)
     if keep not in KEEP:
       raise ValueError("clean: keep must be 'all' or 'anchored'")
@@ -64,8 +63,8 @@ class MatteCleaner(Handle):
       k = int(anchors.shape[1])
     if out is None:
       out = torch.empty(max(n, 1), H, W, dtype=torch.uint8, device="cuda")
-    elif out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous() or out.dim() != 3 or out.shape[0] < n or tuple(out.shape[1:]) != (H, W):
-      raise ValueError("clean: out must be a contiguous device uint8 [>= %d, %d, %d]" % (n, H, W))
+    else:
+      u8_plane(out, "clean", "out", n, H, W)
     rc = self.L.vp_matteclean_clean(self.h, ptr(matte), n, H, W, int(support), int(core), -1 if min_area is None else int(min_area),
                                     -1 if max_hole is None else int(max_hole), int(grow), KEEP[keep], ptr(anchors if k else None), k, ptr(out),
                                     stream())

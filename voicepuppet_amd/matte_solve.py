@@ -14,8 +14,7 @@ import ctypes
 import torch
 
 from . import _lib
-from ._handle import Handle, ptr, stream
-from .metrics import FrameMetrics
+from ._handle import Handle, ptr, rgb_frames, stream, u8_plane
 
 REPORT_FIELDS = ("unknown", "iterations", "status", "residual")
 STATUS_NO_CONSTRAINT, STATUS_BREAKDOWN = 1, 2
@@ -48,24 +47,18 @@ class MatteSolver(Handle):
     self.max_frames, self.max_height, self.max_width, self.max_radius = int(max_frames), int(max_height), int(max_width), int(max_radius)
     self._n = 0
 
-  @staticmethod
-  def _plane(t, who, name, n=None, H=None, W=None):
-    if t.dim() != 3 or t.dtype != torch.uint8 or not t.is_cuda or not t.is_contiguous():
-      raise ValueError("%s: %s must be a contiguous device uint8 tensor [n, H, W]" % (who, name))
-    if n is not None and (t.shape[0] < n or tuple(t.shape[1:]) != (H, W)):
-      raise ValueError("%s: %s must be a contiguous device uint8 [>= %d, %d, %d]" % (who, name, n, H, W))
-
   def trimap(self, matte, support=32, core=224, erode=None, dilate=None, out=None):
     """-> device uint8 [n, H, W]: 255 where the erode x erode square around the pixel lies in {matte >= core}, else 127 where the
     dilate x dilate square meets {matte >= support}, else 0; a k x k square covers the offsets -(k // 2) .. k - 1 - (k // 2), clipped to
     the image.  erode, dilate: 1 .. 64; defaults max(5, min(H, W) // 19) and max(5, min(H, W) // 29), the reference's 30 and 20 for
     720 x 576 scaled to the frame; untuned on real footage.  out: a contiguous device uint8 [>= n, H, W], not the matte itself."""
-    self._plane(matte, "trimap", "matte")
+    u8_plane(matte, "trimap", "matte")
     n, H, W = (int(v) for v in matte.shape)
     if out is None:
       out = torch.empty(max(n, 1), H, W, dtype=torch.uint8, device="cuda")
     else:
-      self._plane(out, "trimap", "out", n, H, W)
+      u8_plane(out, "trimap", "out")
+      u8_plane(out, "trimap", "out", n, H, W)
     rc = self.L.vp_mattesolve_trimap(self.h, ptr(matte), n, H, W, int(support), int(core), 0 if erode is None else int(erode),
                                      0 if dilate is None else int(dilate), ptr(out), stream())
     _lib.check(rc, "vp_mattesolve_trimap")
@@ -77,17 +70,14 @@ class MatteSolver(Handle):
     relative residual is at most tol or `iters` iterations have run (the launches of all `iters` are enqueued; a frame that has
     stopped costs nothing more).  tensor('alpha') holds the unclamped float64 solution.  The defaults (radius 1, eps 1, iters 512)
     are untuned on real footage.  out: a contiguous device uint8 [>= n, H, W]; it may be the trimap."""
-    if frames.dim() != 4 or frames.shape[3] != 3 or frames.dtype != torch.uint8 or not frames.is_cuda:
-      raise ValueError("solve: a device uint8 tensor [n, H, W, 3]")
-    pitch, stride = FrameMetrics._layout(frames, "frames")
-    n, H, W = (int(v) for v in frames.shape[:3])
-    self._plane(trimap, "solve", "trimap")
-    if tuple(trimap.shape) != (n, H, W):
-      raise ValueError("solve: trimap must be a contiguous device uint8 [%d, %d, %d]" % (n, H, W))
+    pitch, stride, n, H, W = rgb_frames(frames, "solve")
+    u8_plane(trimap, "solve", "trimap")
+    u8_plane(trimap, "solve", "trimap", n, H, W, exact=True)
     if out is None:
       out = torch.empty(max(n, 1), H, W, dtype=torch.uint8, device="cuda")
     else:
-      self._plane(out, "solve", "out", n, H, W)
+      u8_plane(out, "solve", "out")
+      u8_plane(out, "solve", "out", n, H, W)
     rc = self.L.vp_mattesolve_solve(self.h, ptr(frames), pitch, stride, n, H, W, ptr(trimap), int(radius), float(eps), int(iters), float(tol),
                                     ptr(out), stream())
     _lib.check(rc, "vp_mattesolve_solve")
@@ -96,10 +86,7 @@ class MatteSolver(Handle):
 
   def laplacian(self, frames, p, radius=1, eps=DEFAULT_EPS):
     """The single op behind the solve (vp_mattesolve_laplacian): L p for a contiguous device float64 [n, H, W], no masking."""
-    if frames.dim() != 4 or frames.shape[3] != 3 or frames.dtype != torch.uint8 or not frames.is_cuda:
-      raise ValueError("laplacian: a device uint8 tensor [n, H, W, 3]")
-    pitch, stride = FrameMetrics._layout(frames, "frames")
-    n, H, W = (int(v) for v in frames.shape[:3])
+    pitch, stride, n, H, W = rgb_frames(frames, "laplacian")
     if p.dtype != torch.float64 or not p.is_cuda or not p.is_contiguous() or tuple(p.shape) != (n, H, W):
       raise ValueError("laplacian: p must be a contiguous device float64 [%d, %d, %d]" % (n, H, W))
     out = torch.empty_like(p)

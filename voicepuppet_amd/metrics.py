@@ -9,7 +9,7 @@ import ctypes
 import torch
 
 from . import _lib
-from ._handle import Handle, ptr, stream
+from ._handle import Handle, frame_layout, ptr, stream
 
 L1, MSE, PSNR, SSIM = 0, 1, 2, 3
 COLUMNS = ("L1", "MSE", "PSNR", "SSIM")
@@ -32,17 +32,6 @@ class FrameMetrics(Handle):
     self._open("frame_metrics", frame_metrics_desc(max_frames, max_height, max_width), invalid="invalid frame metrics descriptor")
     self.max_frames, self.max_height, self.max_width = int(max_frames), int(max_height), int(max_width)
 
-  @staticmethod
-  def _layout(t, name):
-    """(row pitch, frame stride) in bytes of a [n, H, W, 3] view"""
-    n, H, W, C = t.shape
-    e = t.element_size()
-    if t.stride(3) != 1 or t.stride(2) != 3 or t.stride(1) < 3 * W or (n > 1 and t.stride(0) < (H - 1) * t.stride(1) + 3 * W):
-      raise ValueError("compare: %s has strides %s: a pixel's values and a row's pixels must be adjacent, rows and frames must not overlap"
-                       % (name, tuple(t.stride())))
-    pitch = t.stride(1) * e
-    return pitch, max(t.stride(0) * e, (H - 1) * pitch + 3 * W * e)       # a single frame's stride(0) is arbitrary
-
   def compare(self, a, b, value_range=(-1, 1), out=None):
     """value_range: of float32 operands, (-1, 1) (the generator's output), (0, 255) or (0, 1); values outside are clamped.  uint8 ignores it.
     out: a contiguous device float64 [>= n, 4] to write into; allocated when None."""
@@ -50,8 +39,8 @@ class FrameMetrics(Handle):
        or a.dtype not in (torch.uint8, torch.float32):
       raise ValueError("compare: two device tensors [n, H, W, 3] of the same shape, both uint8 or both float32")
     n, H, W = int(a.shape[0]), int(a.shape[1]), int(a.shape[2])
-    ap, as_ = self._layout(a, "a")
-    bp, bs = self._layout(b, "b")
+    ap, as_ = frame_layout(a, "compare", "a")
+    bp, bs = frame_layout(b, "compare", "b")
     if out is None:
       out = torch.empty(max(n, 1), 4, dtype=torch.float64, device="cuda")
     if out.dtype != torch.float64 or not out.is_cuda or not out.is_contiguous() or out.dim() != 2 or out.shape[1] != 4 or out.shape[0] < n:
