@@ -1182,7 +1182,8 @@ void vp_png_destroy(vp_png_t* h);
  * JPEG decoding of training frames on the device: replaces the two cv2.imread calls per sample of generator/generator.py:956-1019 and
  * generator/loader.py's ImageLoader (a host libjpeg decode per file) for the files of a whole batch.  csrc/jpeg_dec.hip.
  *
- * Accepted: baseline sequential Huffman (SOF0), 8 bit, three components in one interleaved scan, sampling 4:2:0 (2x2, 1x1, 1x1) or 4:4:4,
+ * Accepted: baseline sequential Huffman (SOF0), 8 bit, three components in one interleaved scan, sampling 4:2:0 (2x2, 1x1, 1x1) or 4:4:4
+ * (and 4:2:2 on request, below),
  * any width and height up to the descriptor's, up to four 8-bit quantisation tables and two DC + two AC Huffman tables from the file, any
  * restart interval.  The host parses the headers (voicepuppet_amd/jpeg_dec.py::parse) and refuses the rest before anything is enqueued.
  *
@@ -1191,6 +1192,15 @@ void vp_png_destroy(vp_png_t* h);
  * +8 / +7 rounding on even / odd columns, the edge sample replicated at the border of the component's own ceil(W/2) x ceil(H/2) samples);
  * R = Y + ((91881 Cr' + 32768) >> 16), G = Y + ((-22554 Cb' - 46802 Cr' + 32768) >> 16), B = Y + ((116130 Cb' + 32768) >> 16) with
  * C' = C - 128, clamped.  All of it int32 (wrapping, which only coefficients no encoder writes can reach).  tests/jpeg_dec_ref.py restates it.
+ *
+ * 4:2:2 (sampling 3: components 2x1, 1x1, 1x1; what capture cards and Motion-JPEG encoders write) is taken when the caller passes it:
+ * parse() refuses it unless asked (accept_422).  An MCU is 16 x 8 pixels and has four blocks in scan order Y0 (left), Y1 (right), Cb, Cr;
+ * mcux = ceil(W / 16), mcuy = ceil(H / 8); a chroma component's own size is ceil(W / 2) x H.  Entropy decode, dequantisation, inverse DCT and
+ * colour conversion are the ones above.  Up-sampling is libjpeg's h2v1 "fancy" triangle filter along the row only: of a chroma row
+ * c[0 .. cw - 1], cw = ceil(W / 2), out[2i] = (3 c[i] + c[i-1] + 1) >> 2 and out[2i+1] = (3 c[i] + c[i+1] + 2) >> 2 with c[-1] = c[0] and
+ * c[cw] = c[cw-1] (the edge sample replicated at the border of the component's own samples, which gives libjpeg's unfiltered first and
+ * last output samples, also for cw == 1); nothing is filtered down the column.  tests/jpeg_dec_422_ref.py restates it.  The workspace is
+ * the same: the padded sizes are multiples of 16, so 16 mcux and 8 mcuy fit them, and a 4:2:2 file has two thirds of the 4:4:4 blocks.
  *
  * Per-file meta blob (little endian, 16-byte aligned, VP_JPEGDEC_META_BYTES + 24 * n_segments bytes):
  *   [0, 128)       reserved for the host (the device reads none of it: what it needs of the header travels in vp_jpegdec_file)
@@ -1221,7 +1231,7 @@ typedef struct vp_jpegdec_file {
   uint64_t file_offset;           /* of the file's bytes in `blob` */
   int32_t file_bytes;
   int32_t width, height;
-  int32_t sampling;               /* 2: 4:2:0, 1: 4:4:4 */
+  int32_t sampling;               /* 2: 4:2:0, 1: 4:4:4, 3: 4:2:2 */
   int32_t restart_interval;       /* MCUs, 0: none */
   int32_t n_segments;
   uint8_t tq[3], td[3], ta[3];    /* per component: quantisation table 0 .. 3, DC table 0 .. 1, AC table 0 .. 1 */
@@ -1245,7 +1255,7 @@ int vp_jpegdec_decode(vp_jpegdec_t* h, const unsigned char* blob, const vp_jpegd
                       size_t frame_stride, int* status, void* stream);
 /* "coefficients": int16 [max_files, blocks, 64], the blocks of a file in scan order, row-major inside a block, as decoded (not dequantised).
  * "entries": int32 [max_files, mcu rows, 4].  "planes": uint8 [max_files, 3, padded height, padded width] (Y, Cb, Cr; chroma of a 4:2:0
- * file fills the top left quarter).  Rows of the first axis are positions in the last decode call. */
+ * file fills the top left quarter; chroma of a 4:2:2 file fills the left half).  Rows of the first axis are positions in the last decode call. */
 int vp_jpegdec_tensor(vp_jpegdec_t* h, const char* name, void** ptr, int64_t shape[4]);
 /* Device index scan (opt-in): finds the MCU-row entry points of a file without restart markers inside the decode call that first sees
  * it, so that this very call already runs one lane per MCU row.  One workgroup per file cuts the entropy-coded segment into chunks of

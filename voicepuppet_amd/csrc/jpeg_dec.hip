@@ -12,8 +12,13 @@
 //        file's MCU-row entry points in parallel, chunk by chunk, by the self-synchronisation of Huffman streams, and writes `entries`
 //        before the entropy kernel of the same call runs, which then takes one lane per MCU row.  See the comment at the kernel.
 //   jpegdec_planes_kernel   one thread per 8 x 8 block: dequantise, libjpeg's "islow" inverse DCT in registers, uint8 to the padded plane.
-//   jpegdec_rgb_kernel      one thread per 4 pixels of a row: fancy up-sampling of chroma (4:2:0), YCbCr -> RGB, three dword stores where
-//        the row is dword aligned (a wave writes 768 contiguous bytes), bytes at a ragged right edge or on an unaligned row.
+//   jpegdec_rgb_kernel      one thread per 4 pixels of a row: fancy up-sampling of chroma (4:2:0 both ways, 4:2:2 along the row), YCbCr -> RGB,
+//        three dword stores where the row is dword aligned (a wave writes 768 contiguous bytes), bytes at a ragged right edge or on an
+//        unaligned row.
+//
+// Three layouts (vp_jpegdec_file.sampling): 1, 4:4:4, an MCU of 8 x 8 pixels and the blocks Y Cb Cr; 2, 4:2:0, 16 x 16 and Y00 Y01 Y10 Y11
+// Cb Cr; 3, 4:2:2, 16 wide and 8 high and Y0 (left) Y1 (right) Cb Cr.  blocks_per_mcu() and block_component() are the only places that
+// know the block sequences.
 //
 // Only vector loads / stores and plain C++.
 #include <hip/hip_runtime.h>
@@ -56,6 +61,10 @@ struct DecArgs {
   int chunk_bytes, chunks_cap, max_rounds;
   DecFile f[VP_JPEGDEC_FILES_PER_LAUNCH];
 };
+
+// blocks of one MCU, and the component of its block j, per layout
+__host__ __device__ __forceinline__ int blocks_per_mcu(int sampling) { return sampling == 2 ? 6 : (sampling == 3 ? 4 : 3); }
+__device__ __forceinline__ int block_component(int bpm, int j) { return bpm == 6 ? (j < 4 ? 0 : j - 3) : (bpm == 4 ? (j < 2 ? 0 : j - 1) : j); }
 
 struct HuffLds {
   uint16_t lut[512];
@@ -166,7 +175,7 @@ __global__ __launch_bounds__(kLanes) void jpegdec_entropy_kernel(const DecArgs a
 #pragma unroll
     for (int i = 0; i < 6; ++i) sg[i] = src[i];
   }
-  const int bpm = f.sampling == 2 ? 6 : 3;
+  const int bpm = blocks_per_mcu(f.sampling);
   const int total = (int)f.mcux * f.mcuy;
   int mcu0 = sg[4], count = sg[5];
   if (mcu0 < 0 || mcu0 >= total || count < 1) return;           // nothing this lane may write
@@ -177,7 +186,9 @@ __global__ __launch_bounds__(kLanes) void jpegdec_entropy_kernel(const DecArgs a
   r.p = a.blob + f.file;
   r.end = f.bytes;
   r.start((uint32_t)sg[0], sg[1]);
-  short* coef = a.coef + (size_t)slot * a.blocks_cap * 64;     // total * bpm <= blocks_cap: likewise
+  // total * bpm <= blocks_cap = 3 (Hp / 8) (Wp / 8): likewise.  4:2:2: 4 mcux mcuy <= 4 (Wp / 16) (Hp / 8) = 2 (Hp / 8) (Wp / 8), and
+  // mcuy = ceil(H / 8) <= Hp / 8 = rows_cap for `entries` above
+  short* coef = a.coef + (size_t)slot * a.blocks_cap * 64;
   bool bad = false;
   for (int mcu = mcu0; mcu < mcu0 + count && !bad; ++mcu) {
     if (f.dri && mcu > mcu0 && mcu % (int)f.dri == 0) {         // a restart inside the segment: the marker, predictors zero
@@ -198,7 +209,7 @@ __global__ __launch_bounds__(kLanes) void jpegdec_entropy_kernel(const DecArgs a
       *reinterpret_cast<int4*>(entries + 4 * (mcu / (int)f.mcux)) = e;
     }
     for (int j = 0; j < bpm && !bad; ++j) {
-      const int c = bpm == 6 ? (j < 4 ? 0 : j - 3) : j;
+      const int c = block_component(bpm, j);
       short* blk = coef + ((size_t)mcu * bpm + j) * 64;
       uint4* z = reinterpret_cast<uint4*>(blk);
 #pragma unroll
@@ -290,13 +301,13 @@ __device__ __forceinline__ uint2 scan_walk(const unsigned char* file, uint32_t b
     int c = 0, diff = 0;
     if (!stop) {
       if (k == 0) {
-        c = bpm == 6 ? (j < 4 ? 0 : j - 3) : j;
+        c = block_component(bpm, j);
         const int sy = huff_symbol(r, huff[f.td[c]]);
         if (sy < 0 || sy > 15) bad = true;
         else diff = extend(r.take(sy), sy);
         c = sy < 0 ? -1 : c;
       } else {
-        const int rs = huff_symbol(r, huff[2 + f.ta[bpm == 6 ? (j < 4 ? 0 : j - 3) : j]]);
+        const int rs = huff_symbol(r, huff[2 + f.ta[block_component(bpm, j)]]);
         if (rs < 0) bad = true;
         else if (rs & 15) r.take(rs & 15);
         c = rs;
@@ -367,7 +378,7 @@ __global__ __launch_bounds__(kScanLanes) void jpegdec_scan_kernel(const DecArgs 
     for (int i = lane; i < 4 * kHuffBytes / 4; i += kScanLanes) dst[i] = src[i];
   }
   const int* sg = reinterpret_cast<const int*>(meta + kSegAt);
-  const int bpm = f.sampling == 2 ? 6 : 3;
+  const int bpm = blocks_per_mcu(f.sampling);
   const int total = (int)f.mcux * f.mcuy;
   const uint32_t start = (uint32_t)sg[0];
   // the one segment must be the whole scan from MCU 0, and start inside the file behind its first byte (the cold start looks one back)
@@ -482,7 +493,7 @@ __device__ __forceinline__ int clamp255(int v) { return v < 0 ? 0 : (v > 255 ? 2
 
 __global__ __launch_bounds__(256) void jpegdec_planes_kernel(const DecArgs a) {
   const DecFile& f = a.f[blockIdx.y];
-  const int bpm = f.sampling == 2 ? 6 : 3;
+  const int bpm = blocks_per_mcu(f.sampling);
   const int b = blockIdx.x * 256 + threadIdx.x;
   if (b >= (int)f.mcux * f.mcuy * bpm) return;
   const int slot = a.first + blockIdx.y;
@@ -490,7 +501,8 @@ __global__ __launch_bounds__(256) void jpegdec_planes_kernel(const DecArgs a) {
   const int my = mcu / (int)f.mcux, mx = mcu - my * (int)f.mcux;
   int c, by, bx;
   if (bpm == 6 && j < 4) { c = 0; by = 2 * my + (j >> 1); bx = 2 * mx + (j & 1); }
-  else { c = bpm == 6 ? j - 3 : j; by = my; bx = mx; }
+  else if (bpm == 4 && j < 2) { c = 0; by = my; bx = 2 * mx + j; }          // 4:2:2: two luma blocks side by side
+  else { c = block_component(bpm, j); by = my; bx = mx; }
   const uint4* src = reinterpret_cast<const uint4*>(a.coef + ((size_t)slot * a.blocks_cap + b) * 64);
   const uint4* q4 = reinterpret_cast<const uint4*>(a.blob + f.meta + kQuantAt + 128 * f.tq[c]);
   int v[64];
@@ -508,7 +520,9 @@ __global__ __launch_bounds__(256) void jpegdec_planes_kernel(const DecArgs a) {
   for (int x = 0; x < 8; ++x) idct8<8, 11>(v + x);
 #pragma unroll
   for (int y = 0; y < 8; ++y) idct8<1, 18>(v + 8 * y);
-  unsigned char* plane = a.planes + ((size_t)slot * 3 + c) * a.Hp * a.Wp;       // 8 by <  Hp, 8 bx < Wp: padded sizes of the descriptor
+  // 8 by < Hp, 8 bx < Wp by the padded sizes of the descriptor (multiples of 16, at least the file's H and W).  4:2:2: bx <= 2 mcux - 1
+  // and 16 mcux = 16 ceil(W / 16) <= Wp; by <= mcuy - 1 and 8 mcuy = 8 ceil(H / 8) <= Hp.  Its chroma fills the left half of its plane
+  unsigned char* plane = a.planes + ((size_t)slot * 3 + c) * a.Hp * a.Wp;
 #pragma unroll
   for (int y = 0; y < 8; ++y) {
     uint32_t lo = 0, hi = 0;
@@ -551,6 +565,24 @@ __global__ __launch_bounds__(256) void jpegdec_rgb_kernel(const DecArgs a) {
     for (int i = 0; i < 2; ++i) {
       cb[2 * i] = (3 * sb[1 + i] + sb[i] + 8) >> 4;     cb[2 * i + 1] = (3 * sb[1 + i] + sb[2 + i] + 7) >> 4;
       cr[2 * i] = (3 * sr[1 + i] + sr[i] + 8) >> 4;     cr[2 * i + 1] = (3 * sr[1 + i] + sr[2 + i] + 7) >> 4;
+    }
+  } else if (f.sampling == 3) {
+    // libjpeg's h2v1 triangle filter along the row, none down the column: chroma row y, columns c0 - 1 .. c0 + 2 clamped to the
+    // component's own cw = ceil(W / 2) samples (cw <= 8 mcux <= Wp / 2: every read lies in the plane's left half)
+    const int cw = (W + 1) >> 1, c0 = x0 >> 1;
+    int sb[4], sr[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      int c = c0 - 1 + i;
+      c = c < 0 ? 0 : (c > cw - 1 ? cw - 1 : c);
+      sb[i] = Cb[(size_t)y * a.Wp + c];
+      sr[i] = Cr[(size_t)y * a.Wp + c];
+    }
+    // (3 this + this + 1) >> 2 and (3 this + this + 2) >> 2 at a replicated edge are libjpeg's unfiltered first and last samples
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      cb[2 * i] = (3 * sb[1 + i] + sb[i] + 1) >> 2;     cb[2 * i + 1] = (3 * sb[1 + i] + sb[2 + i] + 2) >> 2;
+      cr[2 * i] = (3 * sr[1 + i] + sr[i] + 1) >> 2;     cr[2 * i + 1] = (3 * sr[1 + i] + sr[2 + i] + 2) >> 2;
     }
   } else {
     const uint32_t wb = *reinterpret_cast<const uint32_t*>(Cb + (size_t)y * a.Wp + x0);
@@ -615,7 +647,7 @@ static int dec_check(const vp_jpegdec_desc* d, vp_jpegdec* h) {
   h->d = *d;
   h->Hp = (d->max_height + 15) & ~15;
   h->Wp = (d->max_width + 15) & ~15;
-  h->blocks_cap = 3 * (h->Hp / 8) * (h->Wp / 8);         // 4:4:4; 4:2:0 needs half of it
+  h->blocks_cap = 3 * (h->Hp / 8) * (h->Wp / 8);         // 4:4:4; 4:2:0 needs half of it, 4:2:2 two thirds
   h->rows_cap = h->Hp / 8;
   return VP_OK;
 }
@@ -695,7 +727,7 @@ int vp_jpegdec_decode(vp_jpegdec_t* h, const unsigned char* blob, const vp_jpegd
     const char* what = nullptr;
     if (f.n_segments == 0) continue;              // a gap: nothing is read or written for this position
     if (f.width < 1 || f.width > d.max_width || f.height < 1 || f.height > d.max_height) what = "width / height outside 1 .. the descriptor's maxima";
-    else if (f.sampling != 1 && f.sampling != 2) what = "sampling (1: 4:4:4, 2: 4:2:0)";
+    else if (f.sampling != 1 && f.sampling != 2 && f.sampling != 3) what = "sampling (1: 4:4:4, 2: 4:2:0, 3: 4:2:2)";
     else if (f.file_bytes < 1 || f.file_bytes > d.max_file_bytes) what = "file_bytes outside 1 .. max_file_bytes";
     else if (f.n_segments < 1 || f.n_segments > d.max_segments_per_file) what = "n_segments outside 1 .. max_segments_per_file";
     else if (f.restart_interval < 0) what = "restart_interval";
@@ -733,14 +765,14 @@ int vp_jpegdec_decode(vp_jpegdec_t* h, const unsigned char* blob, const vp_jpegd
       const vp_jpegdec_file& f = files[i0 + i];
       DecFile& g = a.f[i];
       if (f.n_segments == 0) continue;            // all zero: every kernel's bound check ends its workgroups
-      const int s = 8 * f.sampling;
+      const int sx = f.sampling == 1 ? 8 : 16, sy = f.sampling == 2 ? 16 : 8;      // the MCU in pixels; 4:2:2 is 16 wide, 8 high
       g.meta = (uint32_t)f.meta_offset; g.file = (uint32_t)f.file_offset; g.bytes = (uint32_t)f.file_bytes;
       g.nseg = (uint32_t)f.n_segments; g.dri = (uint32_t)f.restart_interval;
       g.W = (uint16_t)f.width; g.H = (uint16_t)f.height;
-      g.mcux = (uint16_t)((f.width + s - 1) / s); g.mcuy = (uint16_t)((f.height + s - 1) / s);
+      g.mcux = (uint16_t)((f.width + sx - 1) / sx); g.mcuy = (uint16_t)((f.height + sy - 1) / sy);
       g.sampling = (uint8_t)f.sampling;
       for (int c = 0; c < 3; ++c) { g.tq[c] = f.tq[c]; g.td[c] = f.td[c]; g.ta[c] = f.ta[c]; }
-      const int blocks = (int)g.mcux * g.mcuy * (f.sampling == 2 ? 6 : 3);
+      const int blocks = (int)g.mcux * g.mcuy * blocks_per_mcu(f.sampling);
       const int groups = ((f.width + 3) / 4) * f.height;
       if (h->scan_state && f.n_segments == 1 && f.restart_interval == 0 && g.mcuy >= 2) {      // whether its segment is the whole scan: the kernel
         g.scan = 1;

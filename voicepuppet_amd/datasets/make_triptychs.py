@@ -8,6 +8,10 @@ In place of steps 5 and 6 of the reference's datasets/make_data_from_GRID.py (de
 deep_video_portraits_v2, :690-695), which need TensorFlow 1, MXNet, OpenCV and FaceReconModel.pb.
 
 --clip_dir DIR     0.jpg, 1.jpg, ... (read with JpegDecoder; a file outside its subset is read with PIL)
+--clip_avi FILE    instead of --clip_dir: a Motion-JPEG AVI file (voicepuppet_amd.avi_read.AviReader: its frames are decoded on the device, 4:2:2
+                   and frames without Huffman tables included).  A PCM audio track is written to out_dir/audio.wav as stored, which is
+                   step 2 of the reference's make_data_from_GRID.py (:110-141, ffmpeg there); the summary line gains
+                   "avi: 75 frames 4:2:2, audio 44100 Hz x 2 -> audio.wav", or "no audio" for a clip without a PCM track
 --landmarks FILE   one frame per line, 136 comma-separated values x0,y0,...,x67,y67 in pixels of those frames (the _landmark.txt of the
                    reference's step 3; any landmark model with the 68-point layout)
 --out_dir DIR      gets <i>.jpg (S x 3S: frame | 3-D face on the frame | mask), bfmcoeff.txt (one row of 257 per frame), ear.txt
@@ -108,6 +112,11 @@ class FrameReader(object):
     self.torch, self.dir = torch, clip_dir
     with Image.open(os.path.join(clip_dir, '0.jpg')) as im:
       self.w, self.h = im.size
+    self._set_panel(clip_dir, crop, size)
+    self.decoder = JpegDecoder(batch, self.h, self.w, bgr=False)
+    self.fallbacks = 0
+
+  def _set_panel(self, clip_dir, crop, size):
     x0, y0, side = crop if crop is not None else (0, 0, self.h)
     if crop is None and self.h != self.w:
       raise ValueError('%s: the frames are %d x %d; --crop X0 Y0 SIDE must name a square' % (clip_dir, self.w, self.h))
@@ -115,8 +124,6 @@ class FrameReader(object):
       raise ValueError('--crop %d %d %d does not lie inside the %d x %d frames' % (x0, y0, side, self.w, self.h))
     self.crop = (int(x0), int(y0), int(side))
     self.size = int(size) if size else int(side)
-    self.decoder = JpegDecoder(batch, self.h, self.w, bgr=False)
-    self.fallbacks = 0
 
   def _decode(self, paths):
     torch = self.torch
@@ -151,6 +158,32 @@ class FrameReader(object):
     return (np.asarray(lms, np.float64) - np.array([x0, y0], np.float64)) * (float(self.size) / side)
 
 
+class AviFrameReader(FrameReader):
+  """The frames of a Motion-JPEG AVI file (AviReader) through FrameReader's crop and resize."""
+
+  def __init__(self, avi_path, batch, crop, size):
+    import torch
+    from voicepuppet_amd.avi_read import AviReader
+    self.torch, self.dir = torch, avi_path
+    self.avi = AviReader(avi_path, batch=batch)
+    self.w, self.h = self.avi.width, self.avi.height
+    self._set_panel(avi_path, crop, size)
+    self.fallbacks = 0
+
+  def read(self, first, n):
+    frames = self.avi.read(first, n)
+    self.fallbacks = self.avi.fallbacks
+    return self.fit_to_panel(frames)
+
+  def extract_audio(self, out_dir):
+    """The clip's PCM track to out_dir/audio.wav -> the summary line's words on the clip."""
+    text = 'avi: %s' % self.avi.describe()
+    if self.avi.audio_format is None:
+      return text + ', no audio' + (' (%s)' % self.avi.audio_refused if self.avi.audio_refused else '')
+    self.avi.write_wav(os.path.join(out_dir, 'audio.wav'))
+    return text + ', audio %d Hz x %d -> audio.wav' % (self.avi.audio_rate, self.avi.audio_channels)
+
+
 def read_alpha(reader, alpha_dir, first, n):
   """<i>.jpg / <i>.png mattes of the frames' size -> uint8 device [n, S, S] (PIL, grey), through the frames' crop and resize."""
   import torch
@@ -171,9 +204,11 @@ def read_alpha(reader, alpha_dir, first, n):
 
 
 def parse_options(argv=None):
-  p = OptionParser(usage='usage: %prog --clip_dir DIR --landmarks FILE --out_dir DIR [--size S] [--crop X0 Y0 SIDE] [--alpha_dir DIR] '
+  p = OptionParser(usage='usage: %prog (--clip_dir DIR | --clip_avi FILE) --landmarks FILE --out_dir DIR [--size S] [--crop X0 Y0 SIDE] [--alpha_dir DIR] '
                          '[--key_matte [--write_alpha DIR]] [--clean_matte] [--solve_matte] [--key_foreground [--key_despill S]] [--bfmcoeff FILE] [--appearance first|none] [--frame_batch N] [--list FILE]')
   p.add_option('--clip_dir', type='string', dest='clip_dir', default=None, help='folder of 0.jpg, 1.jpg, ...')
+  p.add_option('--clip_avi', type='string', dest='clip_avi', default=None,
+               help='a Motion-JPEG AVI file instead of --clip_dir; its PCM track goes to out_dir/audio.wav')
   p.add_option('--landmarks', type='string', dest='landmarks', default=None, help='68 landmarks per frame, 136 comma-separated values per line')
   p.add_option('--out_dir', type='string', dest='out_dir', default=None, help='the dataset folder to write')
   p.add_option('--size', type='int', dest='size', default=None, help='panel size S (default: the frames\' own)')
@@ -227,6 +262,8 @@ def parse_options(argv=None):
                help='the frame panel gets the subject\'s colours without the backdrop\'s share (KeyMatte.foreground); needs a matte')
   p.add_option('--key_despill', type='float', dest='key_despill', default=0.0, help='--key_foreground: 0 .. 1 of the key channel\'s spill removed')
   opts, args = p.parse_args(argv)
+  if opts.clip_dir and opts.clip_avi:
+    p.error('--clip_dir and --clip_avi both name the clip: give one of the two')
   if opts.key_matte and opts.alpha_dir:
     p.error('--key_matte computes the matte that --alpha_dir reads: give one of the two')
   if opts.write_alpha and not opts.key_matte:
@@ -346,8 +383,8 @@ def write_lists(opts, coeff, raw_lines, frames_n):
 
 def main(argv=None):
   opts, _ = parse_options(argv)
-  if opts.clip_dir is None or opts.landmarks is None or opts.out_dir is None:
-    logger.error('Please check your parameters: --clip_dir, --landmarks and --out_dir are needed.')
+  if (opts.clip_dir is None and opts.clip_avi is None) or opts.landmarks is None or opts.out_dir is None:
+    logger.error('Please check your parameters: --clip_dir (or --clip_avi), --landmarks and --out_dir are needed.')
     exit(0)
   from voicepuppet_amd.bfmnet.fit_landmarks import BFM_MAT, LM3D_MAT, _BFM, reprojection_error, summary_line
   if not (os.path.exists(BFM_MAT) and os.path.exists(LM3D_MAT)):
@@ -361,13 +398,23 @@ def main(argv=None):
   from voicepuppet_amd.triptych import STATUS, TriptychBuilder
   from voicepuppet_amd.utils.reconstruct_mesh import ClipRenderer
 
-  frames_n = count_frames(opts.clip_dir)
-  if frames_n < 1:
-    raise SystemExit('%s: no 0.jpg' % opts.clip_dir)
-  lms, raw_lines = read_landmarks_for(opts.landmarks, frames_n, opts.clip_dir)
+  clip = opts.clip_avi or opts.clip_dir
+  if opts.clip_avi:
+    from voicepuppet_amd.avi_read import AviReader
+    try:
+      frames_n = AviReader(opts.clip_avi).frames
+    except (OSError, ValueError) as e:
+      raise SystemExit(str(e))
+    if frames_n < 1:
+      raise SystemExit('%s: no video frame' % opts.clip_avi)
+  else:
+    frames_n = count_frames(opts.clip_dir)
+    if frames_n < 1:
+      raise SystemExit('%s: no 0.jpg' % opts.clip_dir)
+  lms, raw_lines = read_landmarks_for(opts.landmarks, frames_n, clip)
   batch = min(opts.frame_batch, frames_n)
   try:
-    reader = FrameReader(opts.clip_dir, batch, opts.crop, opts.size)
+    reader = AviFrameReader(opts.clip_avi, batch, opts.crop, opts.size) if opts.clip_avi else FrameReader(opts.clip_dir, batch, opts.crop, opts.size)
   except ValueError as e:
     raise SystemExit(str(e))
   S = reader.size
@@ -396,7 +443,7 @@ def main(argv=None):
       repeated += builder.write(trip, st, opts.out_dir, first)
       status.append(st.cpu().numpy())
   except ValueError as e:
-    raise SystemExit('%s: %s' % (opts.clip_dir, e))
+    raise SystemExit('%s: %s' % (clip, e))
   finally:
     chain.close()
   status = np.concatenate(status)
@@ -410,7 +457,9 @@ def main(argv=None):
     logger.warning('%s', w)
   if fatal:
     raise SystemExit(fatal)
-  fit = summary_line(opts.clip_dir, report, reprojection_error(fitter, coeff, aligned))
+  if opts.clip_avi:
+    text += '; ' + reader.extract_audio(opts.out_dir)
+  fit = summary_line(clip, report, reprojection_error(fitter, coeff, aligned))
   print('%s; triptych status %s, %d repeated, %d read with PIL%s' % (fit, counts, len(repeated), reader.fallbacks, extra + text))
   res = {'frames': frames_n, 'status': status, 'repeated': repeated, 'geometry': geometry}
   res.update(chain.reports())

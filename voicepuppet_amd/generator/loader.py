@@ -1,8 +1,9 @@
 """File loaders (reference: generator/loader.py:9-119) without cv2 / librosa.
 
 ImageLoader keeps the reference convention (cv2.imread: BGR, float32 in [0,1]); WavLoader returns mono
-float32 in [-1,1] at the requested rate (reference: librosa.load).  Only PCM .wav input is supported
-here: there is no audio decoder in the image (README of the reference feeds .aac through librosa/ffmpeg).
+float32 in [-1,1] at the requested rate (reference: librosa.load).  Only PCM input is supported here, as a
+.wav file or as the PCM track of a Motion-JPEG .avi file (voicepuppet_amd.avi_read): there is no audio
+decoder in the image (README of the reference feeds .aac through librosa/ffmpeg).
 """
 import os
 
@@ -39,7 +40,11 @@ class WavLoader(Loader):
   def get_data(self, file_path):
     from scipy.io import wavfile
     from scipy.signal import resample_poly
-    rate, data = wavfile.read(self._path(file_path))
+    from voicepuppet_amd.avi_read import AviReader, is_avi
+    if is_avi(self._path(file_path)):                           # the PCM track of a Motion-JPEG clip, as stored
+      rate, data, _ = AviReader(self._path(file_path)).audio()
+    else:
+      rate, data = wavfile.read(self._path(file_path))
     if data.dtype.kind == "i":
       data = data.astype(np.float32) / float(np.iinfo(data.dtype).max + 1)
     elif data.dtype.kind == "u":

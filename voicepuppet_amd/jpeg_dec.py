@@ -1,8 +1,9 @@
 """JPEG decoding of training frames on the device (libvp_hip.so: vp_jpegdec_*, csrc/jpeg_dec.hip).
 
 What the reference does per sample on the host (generator/generator.py:956-1019: two cv2.imread calls; loader.py: ImageLoader): here the
-host only parses headers.  parse() accepts baseline 4:2:0 / 4:4:4 files (include/vp_hip.h) and gives a refusal reason for the rest, finds
-the restart markers with one numpy scan and packs the meta blob the kernels read.  JpegDecoder packs the metas and files of a batch into
+host only parses headers.  parse() accepts baseline 4:2:0 / 4:4:4 files (include/vp_hip.h; on request also 4:2:2 files and files
+that leave their Huffman tables to T.81 Annex K.3, as Motion-JPEG frames do) and gives a refusal reason for the rest, finds the
+restart markers with one numpy scan and packs the meta blob the kernels read.  JpegDecoder packs the metas and files of a batch into
 one pinned buffer, copies it once and enqueues the decode; it never waits in decode_into.
 
 Segments.  A file with restart markers is decoded one lane per interval, a file without them by one lane - and every decode records, per
@@ -32,6 +33,24 @@ _ZIGZAG = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 
 _SOF_OTHER = {0xc1: "extended sequential", 0xc2: "progressive", 0xc3: "lossless", 0xc5: "differential", 0xc6: "differential progressive",
               0xc7: "differential lossless", 0xc9: "arithmetic", 0xca: "arithmetic progressive", 0xcb: "arithmetic lossless",
               0xcd: "arithmetic differential", 0xce: "arithmetic differential progressive", 0xcf: "arithmetic differential lossless"}
+
+# ITU T.81 Annex K.3: the BITS / HUFFVAL pairs a frame without DHT segments implies (Motion-JPEG in AVI), by (class, id): DC / AC,
+# luminance / chrominance.  tests/test_jpeg_dec_422_host.py pins them to the DHT bodies PIL writes.
+_K3_DC_VALS = bytes(range(12))
+K3_HUFFMAN = {
+    (0, 0): (bytes.fromhex("00010501010101010100000000000000"), _K3_DC_VALS),
+    (0, 1): (bytes.fromhex("00030101010101010101010000000000"), _K3_DC_VALS),
+    (1, 0): (bytes.fromhex("0002010303020403050504040000017d"), bytes.fromhex(
+        "01020300041105122131410613516107227114328191a108" "2342b1c11552d1f02433627282090a161718191a25262728"
+        "292a3435363738393a434445464748494a53545556575859" "5a636465666768696a737475767778797a83848586878889"
+        "8a92939495969798999aa2a3a4a5a6a7a8a9aab2b3b4b5b6" "b7b8b9bac2c3c4c5c6c7c8c9cad2d3d4d5d6d7d8d9dae1e2"
+        "e3e4e5e6e7e8e9eaf1f2f3f4f5f6f7f8f9fa")),
+    (1, 1): (bytes.fromhex("00020102040403040705040400010277"), bytes.fromhex(
+        "000102031104052131061241510761711322328108144291" "a1b1c109233352f0156272d10a162434e125f11718191a26"
+        "2728292a35363738393a434445464748494a535455565758" "595a636465666768696a737475767778797a828384858687"
+        "88898a92939495969798999aa2a3a4a5a6a7a8a9aab2b3b4" "b5b6b7b8b9bac2c3c4c5c6c7c8c9cad2d3d4d5d6d7d8d9da"
+        "e2e3e4e5e6e7e8e9eaf2f3f4f5f6f7f8f9fa")),
+}
 
 
 class JpegInfo:
@@ -71,10 +90,13 @@ def _huff_table(bits, vals):
   return lut.tobytes() + maxcode.tobytes() + valoff.tobytes() + v.tobytes()
 
 
-def parse(data, max_height=None, max_width=None):
-  """bytes of a .jpg -> JpegInfo: height, width, sampling (2: 4:2:0, 1: 4:4:4), mcux, mcuy, dri, scan (offset of the entropy-coded data),
-  rst (offsets of the RSTn markers), tq / td / ta per component, segments int32 [n, 6] (one per restart interval, else one), tables (the
-  quantisation and Huffman part of the meta blob).  .refused names the reason for a file outside the subset."""
+def parse(data, max_height=None, max_width=None, accept_422=False, default_huffman=False):
+  """bytes of a .jpg -> JpegInfo: height, width, sampling (2: 4:2:0, 1: 4:4:4, 3: 4:2:2), mcux, mcuy, dri, scan (offset of the
+  entropy-coded data), rst (offsets of the RSTn markers), tq / td / ta per component, segments int32 [n, 6] (one per restart interval,
+  else one), tables (the quantisation and Huffman part of the meta blob).  .refused names the reason for a file outside the subset.
+  accept_422: a (2x1, 1x1, 1x1) file is taken as sampling 3 (an MCU of 16 x 8 pixels) instead of refused.  default_huffman: a Huffman
+  table the scan uses and the file does not define is the one of T.81 Annex K.3 (K3_HUFFMAN), as for the frames of a Motion-JPEG
+  stream; a table the file defines always wins."""
   def no(why):
     r = JpegInfo()
     r.refused = why
@@ -134,9 +156,9 @@ def parse(data, max_height=None, max_width=None):
         return no("truncated header")
       comps = [(body[6 + 3 * i], body[7 + 3 * i] >> 4, body[7 + 3 * i] & 15, body[8 + 3 * i]) for i in range(3)]
       samp = [(h, v) for _, h, v, _ in comps]
-      if samp not in ([(2, 2), (1, 1), (1, 1)], [(1, 1), (1, 1), (1, 1)]):
+      if samp not in ([(2, 2), (1, 1), (1, 1)], [(1, 1), (1, 1), (1, 1)]) and not (accept_422 and samp == [(2, 1), (1, 1), (1, 1)]):
         return no("sampling %s: only 4:2:0 and 4:4:4" % "".join("%dx%d " % s for s in samp).strip())
-      sof = (int.from_bytes(body[1:3], "big"), int.from_bytes(body[3:5], "big"), samp[0][0], comps)
+      sof = (int.from_bytes(body[1:3], "big"), int.from_bytes(body[3:5], "big"), 3 if samp[0] == (2, 1) else samp[0][0], comps)
     elif m == 0xdd:
       dri = int.from_bytes(body[:2], "big")
     elif m == 0xda:
@@ -161,6 +183,10 @@ def parse(data, max_height=None, max_width=None):
     tq, td, ta = [c[3] for c in comps], [sel[c[0]][0] for c in comps], [sel[c[0]][1] for c in comps]
   except KeyError:
     return no("the scan names a component the frame does not have")
+  if default_huffman:
+    for k in [(0, t) for t in td] + [(1, t) for t in ta]:
+      if k not in huff and k in K3_HUFFMAN:
+        huff[k] = _huff_table(*K3_HUFFMAN[k])
   if any(t not in quant for t in tq) or any((0, t) not in huff for t in td) or any((1, t) not in huff for t in ta):
     return no("a table the scan uses is missing")
   # restart markers: in entropy-coded data 0xff is followed only by 0x00 or RSTn; the first other follower ends the scan
@@ -172,7 +198,7 @@ def parse(data, max_height=None, max_width=None):
   if other.size:
     ff, is_rst = ff[:other[0]], is_rst[:other[0]]
   rst = (ff[is_rst] + p).astype(np.int64)
-  mcux, mcuy = -(-W // (8 * s)), -(-H // (8 * s))
+  mcux, mcuy = -(-W // (8 if s == 1 else 16)), -(-H // (16 if s == 2 else 8))
   total = mcux * mcuy
   if dri:
     nseg = -(-total // dri)
@@ -222,18 +248,21 @@ class JpegDecoder(Handle):
   scan_max_rounds bounds its fixed-point rounds per sweep.  The default is 512, not the 32 first pencilled in: files of dense noise
   synchronise slowly (tests/test_jpeg_scan_host.py counts up to 209 rounds at 32-byte chunks, profiles/jpeg_scan.json), and a lane
   whose input did not change does not decode again, so late rounds cost little.  last_scan_rounds: the rounds per file of the last
-  harvested call (0: not scanned)."""
+  harvested call (0: not scanned).
+  accept_422 / default_huffman: parse()'s flags for the files items() reads: 4:2:2 files and files without their Huffman tables are
+  taken, not refused.  Both off by default."""
 
   RING = 3          # staging buffers: one stays untouched until two calls later (the prefetcher's contract for pinned memory)
 
   def __init__(self, max_files, max_height, max_width, bgr=True, max_file_bytes=1 << 22, max_segments_per_file=1 << 16,
-               scan_chunk_bytes=None, scan_max_rounds=512):
+               scan_chunk_bytes=None, scan_max_rounds=512, accept_422=False, default_huffman=False):
     if not torch.cuda.is_available():
       raise RuntimeError("JpegDecoder needs an MI355X (no CPU fallback)")
     desc = _lib.JpegDecDesc(ctypes.sizeof(_lib.JpegDecDesc), int(max_files), int(max_height), int(max_width), int(max_file_bytes),
                             int(max_segments_per_file), int(bool(bgr)))
     self._open("jpegdec", desc, invalid="invalid JPEG decoder descriptor")
     self.max_files, self.max_height, self.max_width, self.bgr = int(max_files), int(max_height), int(max_width), bool(bgr)
+    self.accept_422, self.default_huffman = bool(accept_422), bool(default_huffman)
     self.scan_chunk_bytes, self.scan_max_rounds, self.scan_workspace = None, None, None
     if scan_chunk_bytes is not None:
       sws = self.L.vp_jpegdec_scan_workspace_bytes(ctypes.byref(self.desc), int(scan_chunk_bytes))
@@ -300,20 +329,48 @@ class JpegDecoder(Handle):
   # ---- decoding ----
   def tensor(self, name):
     """'coefficients' int16 [max_files, blocks, 64], 'entries' int32 [max_files, rows, 4], 'planes' uint8 [max_files, 3, Hp, Wp]: views of
-    the workspace, rows in the order of the last decode.  With the index scan 'scan_ok' and 'scan_rounds', int32 [max_files]."""
+    the workspace, rows in the order of the last decode (chroma of a 4:2:0 file fills the top left quarter of its plane, chroma of a
+    4:2:2 file the left half).  With the index scan 'scan_ok' and 'scan_rounds', int32 [max_files]."""
     if name in ("scan_ok", "scan_rounds"):          # the index scan's buffers lie in its own workspace
       return self._tensor(name, torch.int32, 1, self.scan_workspace)
     dtype = {"coefficients": torch.int16, "entries": torch.int32, "planes": torch.uint8}[name]
     return self._tensor(name, dtype, 4 if name == "planes" else 3)
 
-  def pack(self, items):
+  def _staging(self, slot, nbytes, keep=0):
+    """The staging buffers of `slot`, grown to nbytes (the first `keep` bytes of the pinned one are carried over)."""
+    ring = self._ring[slot]
+    if ring is None or ring[0].numel() < nbytes:
+      cap = max(nbytes, 1 << 16) * 3 // 2
+      new = (torch.empty(cap, dtype=torch.uint8).pin_memory(), torch.empty(cap, dtype=torch.uint8, device="cuda"),
+             torch.empty(self.max_files, dtype=torch.int32).pin_memory(),
+             torch.empty(self.tensor("entries").shape, dtype=torch.int32).pin_memory(),
+             torch.empty(2, self.max_files, dtype=torch.int32).pin_memory())          # scan_ok, scan_rounds
+      if keep:
+        new[0].numpy()[:keep] = ring[0].numpy()[:keep]
+      self._ring[slot] = ring = new
+    return ring
+
+  def stage(self, nbytes):
+    """For a caller whose files lie in one span of a larger file (the chunks of an AVI clip): takes the next staging slot and returns
+    (token, uint8 numpy view of its first nbytes of pinned memory).  The caller reads the span into the view, parses its files from it
+    and hands pack() the token with items whose data is (offset in the span, length): the files then travel where they were read."""
+    slot = self._turn
+    self._turn = (self._turn + 1) % self.RING
+    bad = self.harvest(slot)
+    ring = self._staging(slot, int(nbytes) + 16)
+    return (slot, int(nbytes), bad), ring[0].numpy()[:int(nbytes)]
+
+  def pack(self, items, staged=None):
     """Host half of a decode.  items: [(bytes, JpegInfo, key or None, segments or None, name) or None (a gap: that row of the output is
     left alone)] -> what enqueue() takes: the per-file table and the metas and files in one pinned staging buffer (a ring of RING: a
     buffer stays untouched until two calls later).  Before it reuses a staging slot it reads the status and entries the decode RING
-    calls ago left there."""
+    calls ago left there.  staged: stage()'s token; the items' data are then (offset, length) pairs in the staged span, and only the
+    metas are added behind it."""
     n = len(items)
     if not 1 <= n <= self.max_files:
       raise ValueError("decode: %d files, 1 .. %d" % (n, self.max_files))
+    if staged is not None:
+      return self._pack_staged(items, staged)
     slot = self._turn
     self._turn = (self._turn + 1) % self.RING
     bad = self.harvest(slot)                # of the call RING calls ago: its event has long completed
@@ -337,15 +394,39 @@ class JpegDecoder(Handle):
       pad = -(len(meta) + len(data)) % 16
       parts += [meta, data, bytes(pad)]
       at += len(meta) + len(data) + pad
-    ring = self._ring[slot]
-    if ring is None or ring[0].numel() < at:
-      cap = max(at, 1 << 16) * 3 // 2
-      ring = (torch.empty(cap, dtype=torch.uint8).pin_memory(), torch.empty(cap, dtype=torch.uint8, device="cuda"),
-              torch.empty(self.max_files, dtype=torch.int32).pin_memory(),
-              torch.empty(self.tensor("entries").shape, dtype=torch.int32).pin_memory(),
-              torch.empty(2, self.max_files, dtype=torch.int32).pin_memory())          # scan_ok, scan_rounds
-      self._ring[slot] = ring
+    ring = self._staging(slot, at)
     ring[0].numpy()[:at] = np.frombuffer(b"".join(parts), np.uint8)
+    return slot, table, at, segments, items, bad
+
+  def _pack_staged(self, items, staged):
+    slot, span, bad = staged
+    n = len(items)
+    table = (_lib.JpegDecFile * n)()
+    at0 = (span + 15) & ~15
+    parts, at, segments = [], at0, []
+    for i, item in enumerate(items):
+      if item is None:
+        segments.append(0)
+        continue
+      (offset, length), info, key, seg, _ = item
+      if not (0 <= offset and 0 < length and offset + length <= span):
+        raise ValueError("decode: file %d lies at %d .. %d of a staged span of %d bytes" % (i, offset, offset + length, span))
+      if seg is None and key is not None and key in self.index and not info.dri:
+        seg = index_segments(info, self.index[key])
+      meta = meta_blob(info, seg)
+      f = table[i]
+      f.meta_offset, f.file_offset = at, offset
+      f.file_bytes, f.width, f.height, f.sampling, f.restart_interval = length, info.width, info.height, info.sampling, info.dri
+      f.n_segments = len(info.segments if seg is None else seg)
+      segments.append(int(f.n_segments))
+      for c in range(3):
+        f.tq[c], f.td[c], f.ta[c] = info.tq[c], info.td[c], info.ta[c]
+      pad = -len(meta) % 16
+      parts += [meta, bytes(pad)]
+      at += len(meta) + pad
+    ring = self._staging(slot, at, keep=span)
+    if at > at0:
+      ring[0].numpy()[at0:at] = np.frombuffer(b"".join(parts), np.uint8)
     return slot, table, at, segments, items, bad
 
   def enqueue(self, packed, out, row_pitch, frame_stride, status, raise_bad=True):
@@ -389,7 +470,7 @@ class JpegDecoder(Handle):
         key, name = _key(f), str(f)
         with open(f, "rb") as fh:
           data = fh.read()
-      info = parse(data, self.max_height, self.max_width)
+      info = parse(data, self.max_height, self.max_width, self.accept_422, self.default_huffman)
       if info.refused:
         raise ValueError("%s: %s" % (name, info.refused))
       seg = index_segments(info, np.asarray(indexes[i], np.int32)) if indexes is not None and indexes[i] is not None else None

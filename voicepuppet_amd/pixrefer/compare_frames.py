@@ -9,6 +9,9 @@ device JPEG encoder against PIL's) - or two `bench.py --dump-outputs` directorie
 [N, H, H, 3] in [0, 1]) is compared.  The .jpg files are decoded on the device (JpegDecoder; a file it refuses is decoded by PIL and
 uploaded) and never come back to the host.  One line per frame, then mean, min, max and the worst frame per metric (the lowest PSNR and
 SSIM, the highest L1 and MSE); --out writes the same as JSON.  The reference has no counterpart.
+
+Either side may also be a Motion-JPEG .avi file (voicepuppet_amd.avi_read.AviReader): its frame i is compared with <i>.jpg of the other
+side, or with frame i of the other file.
 """
 import argparse
 import json
@@ -34,20 +37,35 @@ def numbered_jpgs(d):
   return out
 
 
+def avi_frames(path):
+  """{i: (AviReader, i)} of the frames of a Motion-JPEG AVI file"""
+  from voicepuppet_amd.avi_read import AviReader
+  try:
+    reader = AviReader(path, batch=CHUNK)
+  except ValueError as e:
+    raise SystemExit("compare_frames: %s" % e)
+  return {i: (reader, i) for i in range(reader.frames)}
+
+
 def pair_up(a, b):
-  """-> ("jpg", indices, paths of a, paths of b) or ("npy", None, array path of a, array path of b); SystemExit names what is missing"""
-  for d in (a, b):
-    if not os.path.isdir(d):
-      raise SystemExit("compare_frames: %s is not a directory" % d)
+  """-> ("jpg", indices, paths of a, paths of b) or ("npy", None, array path of a, array path of b); SystemExit names what is missing.
+  A frame of an .avi side stands in the path lists as (AviReader, index)."""
+  from voicepuppet_amd.avi_read import is_avi
+  avi = [os.path.isfile(d) and is_avi(d) for d in (a, b)]
+  for d, v in zip((a, b), avi):
+    if not v and not os.path.isdir(d):
+      raise SystemExit("compare_frames: %s is neither a directory nor an AVI file" % d)
   na, nb = os.path.join(a, "Outputs.npy"), os.path.join(b, "Outputs.npy")
-  ja, jb = numbered_jpgs(a), numbered_jpgs(b)
-  if not ja and not jb and os.path.exists(na) and os.path.exists(nb):
+  ja, jb = (avi_frames(d) if v else numbered_jpgs(d) for d, v in zip((a, b), avi))
+  if not any(avi) and not ja and not jb and os.path.exists(na) and os.path.exists(nb):
     return "npy", None, na, nb
   if not ja or not jb:
     raise SystemExit("compare_frames: no <i>.jpg files (and no Outputs.npy in both) under %s" % (a if not ja else b))
   only = sorted(set(ja) ^ set(jb))
   if only:
-    raise SystemExit("compare_frames: %s is in only one of the two directories" % ", ".join("%d.jpg" % i for i in only[:8]))
+    raise SystemExit("compare_frames: %s is in only one of the two %s" % (", ".join("%d.jpg" % i for i in only[:8]) if not any(avi) else
+                                                                         "frame " + ", ".join("%d" % i for i in only[:8]),
+                                                                         "directories" if not any(avi) else "clips"))
   idx = sorted(ja)
   return "jpg", idx, [ja[i] for i in idx], [jb[i] for i in idx]
 
@@ -62,6 +80,9 @@ class DeviceFrames:
     import torch
     from PIL import Image
     from voicepuppet_amd import jpeg_dec as jd
+    if isinstance(paths[0], tuple):                 # frames of an .avi side: (AviReader, index), a run of consecutive indices
+      reader, first = paths[0]
+      return list(reader.read(first, len(paths)))
     datas = []
     for p in paths:
       with open(p, "rb") as f:
@@ -125,7 +146,7 @@ def _stack(frames):
 def main(argv=None, load=None, compare=None):
   """load / compare: stand-ins for the device halves (tests without a GPU); None: the device."""
   ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-  ap.add_argument("a", metavar="A", help="a directory of <i>.jpg, or a bench.py --dump-outputs directory")
+  ap.add_argument("a", metavar="A", help="a directory of <i>.jpg, a Motion-JPEG .avi file, or a bench.py --dump-outputs directory")
   ap.add_argument("b", metavar="B", help="the directory to compare it with: the same indices and sizes")
   ap.add_argument("--out", metavar="FILE", default=None, help="write the per-frame numbers and the summary as JSON")
   args = ap.parse_args(argv)
@@ -147,7 +168,7 @@ def main(argv=None, load=None, compare=None):
       fa, fb = load(pa[i0:i0 + CHUNK]), load(pb[i0:i0 + CHUNK])
       for k, (x, y) in enumerate(zip(fa, fb)):
         if tuple(x.shape) != tuple(y.shape):
-          raise SystemExit("compare_frames: %d.jpg is %s in %s and %s in %s" % (idx[i0 + k], tuple(x.shape), args.a, tuple(y.shape), args.b))
+          raise SystemExit("compare_frames: frame %d is %s in %s and %s in %s" % (idx[i0 + k], tuple(x.shape), args.a, tuple(y.shape), args.b))
       at = 0
       while at < len(fa):                           # runs of one size go to the device together
         end = at
